@@ -2,7 +2,8 @@
 """Headline benchmark: images/sec of the RoomNet forward pass (BASELINE.json metric) on
 synthetic 224x224 uint8 batches, batch 256 per GPU, 16-bit storage / fp32 accumulate.
 
-  python bench.py --gpus 1 --steps 200 --warmup 20      (the defaults: ~0.4 s of GPU time + ~20 s of cpu_baseline)
+  python bench.py --gpus 1 --steps 200 --warmup 20      (the defaults: ~0.4 s of GPU time)
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full   (+ everything below that is marked --full: ~20 s of cpu_baseline, ...)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,15 +13,25 @@ uint8 BGR [B,224,224,3] -> stage kernels -> head -> probs [B,6] + ids [B] in HBM
 scaling (each rank owns its own batch of B images: BASELINE config 4 is 8 x 256).  The library and the
 collective run on ONE explicit (non-default) stream, so the all-gather is stream-ordered behind the head kernel.
 
-Before anything is timed the SAME handle classifies the 64 parity images (roomnet_amd/synth.parity_set: all six classes) and the
-result is checked against tests/golden/parity_224.npz at the SURVEY 8c tolerance: the timed kernels are the tested ones.
+A plain run does what the headline figure needs and nothing else: set-up, the untimed steps in front of `value` (below), the K
+timed steps, `--dump-outputs DIR` when given, and the JSON line.  `--full` adds every other measurement and check: the parity gate,
+the cold pass's own figure, the folding's comparison arm, the per-launch / per-step event timing and the roofline, `--pcie`,
+`other_configs`, `cpu_baseline` and the sanity checks of the results.
 
-Two measurements per run, both complete passes, both reported.  (1) the COLD / contract pass: W warm-up steps and K timed
-steps on a chip that idled through the parity check, nothing else in front of it -> `cold_images_per_sec` (the strict reading
+`--dump-outputs DIR`: right after the timed steps, what the last of them handed its caller is written as DIR/probs.npy (float32
+[B,6]) and DIR/ids.npy (float64 [B]); N > 1: the gathered results of every rank, [N*B,6] and [N*B], rank-major.  The inputs are
+seeded (synth.perf_batch, seed = rank), so two builds run with the same arguments can be compared output for output.
+
+--full: before anything is timed the SAME handle classifies the 64 parity images (roomnet_amd/synth.parity_set: all six classes) and
+the result is checked against tests/golden/parity_224.npz at the SURVEY 8c tolerance: the timed kernels are the tested ones.
+
+Two passes per run, both complete passes.  (1) the COLD / contract pass: W warm-up steps and K timed
+steps on a chip that idled through set-up, nothing else in front of it -> with --full, `cold_images_per_sec` (the strict reading
 of the command line; with the driver's W = 5, K = 20 that is 33 ms of work, inside the tens of milliseconds the engine clock
-needs to leave its idle state: it reads ~5 % low).  (2) `value`: W warm-up steps + K timed steps again, on the same handle,
-directly behind (1) -- so `value` is preceded by W + K + W untimed-for-value steps, reported as `untimed_steps_before_value`
-(+ `--spinup-steps`, default 0).  `--no-cold-pass` drops (1): then `value` IS the strict reading.
+needs to leave its idle state: it reads ~5 % low); in a plain run its steps are run and not reported.  (2) `value`: W warm-up
+steps + K timed steps again, on the same handle, directly behind (1) -- so `value` is preceded by W + K + W untimed-for-value
+steps, reported as `untimed_steps_before_value` (+ `--spinup-steps`, default 0).  `--no-cold-pass` drops (1): then `value` IS
+the strict reading.
 
 `--handles 2` (default 1): the steps alternate between two engine handles (own activation tensors, stream, result buffer) so
 the last launch of step k overlaps the first of step k + 1 (+0.3 % since the back end is one launch).
@@ -28,12 +39,12 @@ the last launch of step k overlaps the first of step k + 1 (+0.3 % since the bac
 `python3 bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself (`self_launch`)
 before torch / HIP are touched; under torch.distributed.run it is one of the ranks.
 
-The default single-GPU invocation of the headline configuration also measures, in the same process and parity-gated the same
+With --full, the single-GPU invocation of the headline configuration also measures, in the same process and parity-gated the same
 way, BASELINE's other single-GPU shards: 64 x 600 x 600 fp16 (config 5's per-GPU shard), 256 x 224 x 224 float32 (config 2's
 arithmetic at the headline batch) and the latency of a batch-1 call (network.py:148-156's shape) -> `other_configs`
 (`--no-other-configs` skips them).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  Extra objects (--full):
   roofline      `frac` = the whole path against the roof the target is stated in (images/sec x 27.309 MB
                 / (n_gpu x 8 TB/s)); `launches[]` = every launch of a step timed live with HIP events on the launch stream, each
                 with `credited_frac` (algorithmic stage-boundary bytes of the stages it computes / time: a fused launch is
@@ -279,6 +290,13 @@ def measure_latency(torch, eng, graph, dev, stream, side, calls=200):
             "what": "one image per call (network.py:148-156), resident in HBM; wall clock call -> synchronised result"}
 
 
+def dump_outputs(out_dir, probs, ids):
+    """`--dump-outputs`: one step's results as DIR/probs.npy (float32) and DIR/ids.npy (float64: class indices are exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "probs.npy"), np.ascontiguousarray(probs, dtype=np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), np.asarray(ids, dtype=np.float64))
+
+
 class StubEngine:
     """CPU stand-in for the GPU engine (tests only, `--stub-engine`): lets the world_size-2 gloo test drive THIS
     file's N > 1 code path -- process group, packed all-gather, barriers, max-over-ranks timing, rank-0 JSON."""
@@ -384,8 +402,15 @@ def main():
                     help="run the N > 1 code path (RCCL process group, per-step all-gather, barriers, gathered-block check) "
                          "with however many ranks there are, also one: exercises it on a one-GPU box")
     ap.add_argument("--pcie", action="store_true",
-                    help="also time the host-buffer entry point (rn_forward_u8: H2D copy + forward + D2H copy); reported as "
+                    help="with --full: also time the host-buffer entry point (rn_forward_u8: H2D copy + forward + D2H copy); reported as "
                          "path.pcie_inclusive_images_per_sec, never as `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement and check beyond the headline figure: parity gate, cold_images_per_sec, the folding's "
+                         "comparison arm, per-launch / per-step event timing and roofline, --pcie, other_configs, cpu_baseline, "
+                         "sanity checks of the results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one as DIR/probs.npy (float32) and DIR/ids.npy (float64); "
+                         "N > 1: every rank's, gathered")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -502,8 +527,8 @@ def main():
         return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
     # ---- parity gate: the handle that is about to be timed reproduces the golden results
-    parity = {"checked": False, "reason": "--no-parity-check" if args.no_parity_check else "stub engine"}
-    if not stub and not args.no_parity_check:
+    parity = {"checked": False, "reason": "--no-parity-check" if args.no_parity_check else "stub engine" if stub else "plain run (--full checks it)"}
+    if args.full and not stub and not args.no_parity_check:
         def fwd_host(batch):
             t = torch.from_numpy(np.ascontiguousarray(batch)).to(dev)
             p = torch.empty((len(batch), graph.num_classes), dtype=torch.float32, device=dev)
@@ -528,8 +553,9 @@ def main():
 
     sync()
     # ---- cold / contract pass: exactly what the command line says and nothing else -- W warm-up steps, K timed steps, ONE
-    # handle, strictly serial, no spin-up, on a chip that idled through the parity check.  Reported as `cold_images_per_sec`
-    # next to `value` (which follows the spin-up and alternates two handles; both are complete passes).
+    # handle, strictly serial, no spin-up, on a chip that idled through set-up.  Reported (--full) as `cold_images_per_sec`
+    # next to `value` (which follows the spin-up and alternates two handles; both are complete passes); a plain run runs the
+    # same steps, so `value` has the same untimed steps in front of it either way.
     cold_elapsed = None
     if args.cold_pass:
         with on_stream():
@@ -571,7 +597,7 @@ def main():
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last_slot = step()
         sync()
         if multi:
             dist.barrier()
@@ -582,10 +608,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- what the last timed step handed its caller, before anything else runs on the handle (rank 0; N > 1: the gathered block)
+    if args.dump_outputs and rank == 0:
+        if multi:
+            rows = g_bufs[last_slot].view(world, bufs[last_slot][0].numel())
+            got = [unpack_results(rows[r], B, graph.num_classes) for r in range(world)]
+            dump_ids, dump_probs = torch.cat([g[0] for g in got]), torch.cat([g[1] for g in got])
+        else:
+            dump_ids, dump_probs = bufs[last_slot][2], bufs[last_slot][1]
+        dump_outputs(args.dump_outputs, dump_probs.cpu().numpy(), dump_ids.cpu().numpy())
+
     # ---- the comparison arm of the frozen-channel folding, in the same run: a handle that convolves the provably constant
     # channels too (RN_FLAG_COMPUTE_FROZEN), W warm-up + K timed steps, this rank only -> `folding.images_per_sec_computing_them`
     fold_info, unfolded_rate, unfolded_untimed = None, None, 0
-    if not stub:
+    if args.full and not stub:
         fold_info = eng.frozen_info()
         fold_info["constant_channels"] = eng.const_info()
         folded = fold_info["pair_channels_not_convolved"] > 0 or fold_info["residual_stage_folded"] >= 0
@@ -610,7 +646,7 @@ def main():
             torch.cuda.synchronize()
 
     # sanity: outputs are a distribution and an argmax of it; every rank's gathered block carries that rank's results
-    if not args.no_parity_check:
+    if args.full and not args.no_parity_check:
         for k in range(2 if n_steps_done[0] > 1 else 1):
             combo_k, probs_k, ids_k = bufs[k]
             p = probs_k.cpu().numpy()
@@ -625,7 +661,7 @@ def main():
                     assert np.allclose(gp.sum(1), 1.0, atol=1e-4) and (gp.argmax(1) == gi.cpu().numpy()).all(), \
                         "rank %d: block %d of the all-gather is not a result" % (rank, r)
 
-    if stub and multi:
+    if args.full and stub and multi:
         # stub engine: every rank knows every rank's input (perf_batch(seed = rank)), so every block of the gathered buffer is
         # checked against what that rank must have produced -- on every rank (tests/test_bench_multi.py, world 8)
         from roomnet_amd.parallel import shard_counts
@@ -642,7 +678,7 @@ def main():
     head_ms = total_ms = 0.0
     event_ms = []
     pcie_rate = pcie_pipe_rate = pcie_pinned_rate = None
-    if not stub:
+    if args.full and not stub:
         # ---- per-stage device time (HIP events on the launch stream), separate from the timed region
         eng.set_profiling(True)
         nprof = max(1, args.profile_steps)
@@ -735,13 +771,16 @@ def main():
                                 "rn_const_info: output channels whose 16-bit store is provably one number, written once at rn_create",
                 images_per_sec_computing_them=unfolded_rate, untimed_steps_before_computing_them=unfolded_untimed),
             "untimed_steps_before_value": (args.warmup + args.steps if cold_elapsed is not None else 0) + spinup_steps + args.warmup,
+            "full": args.full,
         }
-        if cold_elapsed is not None:
+        if not args.full:
+            del out["folding"]                             # (the folding's figures are --full's)
+        if args.full and cold_elapsed is not None:
             out["cold_images_per_sec"] = world * B * args.steps / cold_elapsed
             out["cold"] = {"ms_per_step": cold_elapsed / args.steps * 1e3, "steps": args.steps, "warmup": args.warmup, "handles": 1,
                            "spinup_steps": 0, "what": "the same W + K steps timed BEFORE the spin-up on one handle, strictly serial: "
                                                      "the figure of a strict reading of the command line"}
-        if not stub:
+        if args.full and not stub:
             # ---- roofline: the WHOLE PATH against the roof the target is stated in (BASELINE.md section 3:
             # img/s x algorithmic bytes per image / (n_gpu x 8 TB/s); float32: img/s x flops per image / matrix-fp32 peak).
             # Per launch (`launches[]`, HIP events on the launch stream): `credited_frac` = algorithmic stage-boundary bytes of

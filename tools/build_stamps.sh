@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic build with in-kernel s_memtime stamps (never shipped): tools/ab/libroomnet_hip_stamps[_chain].so
-# usage: tools/build_stamps.sh [chain]     then run with ROOMNET_HIP_LIB=<that .so> python bench.py --steps 1 --warmup 1 --no-cpu-baseline
+# usage: tools/build_stamps.sh [chain]     then run with ROOMNET_HIP_LIB=<that .so> python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 SRC="$ROOT/roomnet_amd/csrc"

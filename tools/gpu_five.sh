@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r5
 timeout 900 python -m pytest tests/test_hip_fused.py -x -q -m gpu 2>&1 | tail -5
-line() { python bench.py --steps ${STEPS:-300} --warmup 10 --no-cpu-baseline --no-cold-pass --no-parity-check --no-unfolded-arm "$@" 2>/dev/null | tail -1 | python -c "
+line() { python bench.py --full --steps ${STEPS:-300} --warmup 10 --no-cpu-baseline --no-cold-pass --no-parity-check --no-unfolded-arm "$@" 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline())
 print('%-22s %.0f img/s  launches ' % ('$V', d['value']) + ' '.join('%.3f'%x for x in d['path']['launch_ms']))"; }

@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 ARGS="--dtype f32 --steps 20 --warmup 3"
-cd $R && python3 bench.py $ARGS 2>/dev/null | tail -1 > $O/${tag}_line.json
+cd $R && python3 bench.py --full $ARGS 2>/dev/null | tail -1 > $O/${tag}_line.json
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/ktf && rocprofv3 --kernel-trace --stats -d /tmp/ktf -o kt --output-format csv -- python3 $R/bench.py $ARGS --no-cpu-baseline > /tmp/ktf.log 2>&1
+rm -rf /tmp/ktf && rocprofv3 --kernel-trace --stats -d /tmp/ktf -o kt --output-format csv -- python3 $R/bench.py --full $ARGS --no-cpu-baseline > /tmp/ktf.log 2>&1
 f=$(find /tmp/ktf -name "*kernel_stats.csv" | head -1); cp "$f" $O/${tag}_kernel_trace.csv
-rm -rf /tmp/pf && rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d /tmp/pf -o p --output-format csv -- python3 $R/bench.py --dtype f32 --steps 2 --warmup 1 --no-cold-pass --no-cpu-baseline > /tmp/pf.log 2>&1
+rm -rf /tmp/pf && rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d /tmp/pf -o p --output-format csv -- python3 $R/bench.py --full --dtype f32 --steps 2 --warmup 1 --no-cold-pass --no-cpu-baseline > /tmp/pf.log 2>&1
 f=$(find /tmp/pf -name "*counter_collection.csv" | head -1)
 python3 - "$f" > $O/${tag}_mfma_busy.txt <<'PY'
 import csv, sys, collections

@@ -100,8 +100,10 @@ extern "C" {
                                     * (the same stages) alike; this flag is the comparison arm that shows it.  See
                                     * rn_frozen_info, rn_const_info (the 16 constant output channels of the first step of
                                     * the 64-channel block, round 6, are computed under this flag too). */
-#define RN_FLAG_NO_DITHER 32u /* 16-bit handles: plain rounding everywhere -- conv weights rounded to nearest one by one and every
-                                store round-to-nearest-even, as in rounds 1-5.  Default (round 6): the weights' rounding residual
+#define RN_FLAG_NO_DITHER 32u /* 16-bit handles: plain rounding everywhere -- conv weights rounded to nearest one by one and no
+                                dithered store, as in rounds 1-5: every store rounds to nearest even, except that bf16 handles
+                                still store the outputs of stages 3, 4, 5 through v_cvt_sr_bf16_f32 with the plain
+                                (undithered) seed, which rounds half away from zero.  Default (round 6): the weights' rounding residual
                                 is carried from tap to tap (the nine taps of a (cin, cout) pair sum to the exact sum within half an
                                 ulp), and bf16 handles store the outputs of stages 3, 4, 5 through v_cvt_sr_bf16_f32 with a
                                 seed that depends on the output row -- a deterministic dither, each value within one ulp of the

@@ -29,6 +29,51 @@ extern "C" int rn_device_count(void) {
 }
 
 // ------------------------------------------------------------------------ helpers
+int dev_alloc(rn_handle* h, size_t bytes, void** out) {
+    void* p = nullptr;
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return RN_E_NOMEM;
+    }
+    h->allocs.push_back(p);
+    *out = p;
+    return RN_OK;
+}
+
+RelabelledWeights::RelabelledWeights(const rn_weights* src) : w(*src), stages(src->stages, src->stages + src->n_stages) {
+    w.stages = stages.data();
+}
+
+void RelabelledWeights::permute_couts(int stage, const std::vector<int>& pi) {
+    rn_conv_stage& st = stages[stage];
+    const size_t nk = static_cast<size_t>(9) * st.cin;
+    owned.emplace_back(nk * st.cout);
+    for (size_t k = 0; k < nk; ++k)
+        for (int co = 0; co < st.cout; ++co) owned.back()[k * st.cout + co] = st.kernel[k * st.cout + pi[co]];
+    st.kernel = owned.back().data();
+    const auto perm = [&](const float*& v) {
+        if (!v) return;
+        owned.emplace_back(pi.size());
+        for (size_t p = 0; p < pi.size(); ++p) owned.back()[p] = v[pi[p]];
+        v = owned.back().data();
+    };
+    for (const float** v : {&st.gamma, &st.beta, &st.mean, &st.variance}) perm(*v);
+    if (st.skip_stage >= 0)
+        for (const float** v : {&st.gamma2, &st.beta2, &st.mean2, &st.variance2}) perm(*v);
+}
+
+void RelabelledWeights::permute_cins(int stage, const std::vector<int>& pi) {
+    rn_conv_stage& st = stages[stage];
+    owned.emplace_back(static_cast<size_t>(9) * st.cin * st.cout);
+    for (int tap = 0; tap < 9; ++tap)
+        for (int ci = 0; ci < st.cin; ++ci)
+            std::memcpy(&owned.back()[(static_cast<size_t>(tap) * st.cin + ci) * st.cout],
+                        &st.kernel[(static_cast<size_t>(tap) * st.cin + pi[ci]) * st.cout], static_cast<size_t>(st.cout) * 4);
+    st.kernel = owned.back().data();
+}
+
 namespace {
 
 struct DeviceGuard {
@@ -43,33 +88,10 @@ struct DeviceGuard {
     }
 };
 
-int dev_alloc(rn_handle* h, size_t bytes, void** out) {
-    void* p = nullptr;
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return RN_E_NOMEM;
-    }
-    h->allocs.push_back(p);
-    *out = p;
-    return RN_OK;
-}
-
-template <typename T>
-int upload(rn_handle* h, const T* src, size_t count, T** out) {
-    void* p = nullptr;
-    int rc = dev_alloc(h, count * sizeof(T), &p);
-    if (rc != RN_OK) return rc;
-    RN_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<T*>(p);
-    return RN_OK;
-}
-
 int upload_bn(rn_handle* h, int c, const float* gamma, const float* beta, const float* mean, const float* var,
               float eps, BnDev* out) {
     std::vector<float> inv(c);
-    for (int i = 0; i < c; ++i) inv[i] = (1.0f / sqrtf(var[i] + eps)) * gamma[i];
+    for (int i = 0; i < c; ++i) inv[i] = rn_bn_inv(var[i], gamma[i], eps);
     int rc;
     if ((rc = upload(h, mean, c, &out->mean)) != RN_OK) return rc;
     if ((rc = upload(h, inv.data(), c, &out->inv)) != RN_OK) return rc;
@@ -237,8 +259,8 @@ int build_plan(rn_handle* h, const rn_weights* w) {
             // tf.nn.batch_normalization: inv = rsqrt(var+eps)*gamma; shift = beta - mean*inv
             std::vector<float> inv(l.nout), shift(l.nout);
             for (int j = 0; j < l.nout; ++j) {
-                inv[j] = (1.0f / sqrtf(l.variance[j] + w->bn_epsilon)) * l.gamma[j];
-                shift[j] = l.beta[j] - l.mean[j] * inv[j];
+                inv[j] = rn_bn_inv(l.variance[j], l.gamma[j], w->bn_epsilon);
+                shift[j] = rn_bn_shift(l.beta[j], l.mean[j], inv[j]);
             }
             if ((rc = upload(h, inv.data(), l.nout, &p.inv)) != RN_OK) return rc;
             if ((rc = upload(h, shift.data(), l.nout, &p.shift)) != RN_OK) return rc;
@@ -507,12 +529,15 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     // >= 32 such channels the stage's channels are relabelled on a copy of the weights (stage 4's couts, stage 5's cins + couts,
     // stage 6's cins: the residual pairs channel c of stage 4's output with channel c of stage 5's) so that the second 32-cout
     // tile is all frozen: it is not convolved (rn_f32m_launch runs the residual for it alone).  rn_tap un-relabels.
-    std::vector<rn_conv_stage> stg_copy;
-    std::vector<std::vector<float>> owned;
-    rn_weights wp;
+    RelabelledWeights rw(w);
     std::vector<int> fold_pi, kfold_pi;
     int fold_r = -1, kfold_r = -1, kfold_live = 0, kfold_proven = 0;
     if (!fused_mode(h) && !(flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN))) {
+        auto bn1_frozen = [&](const rn_conv_stage& st, int c) {
+            const float inv = rn_bn_inv(st.variance[c], st.gamma[c], w->bn_epsilon);
+            const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
+            return std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8;
+        };
         for (int r = 2; r + 1 < w->n_stages && fold_r < 0; ++r) {
             const rn_conv_stage& s5 = w->stages[r];
             const rn_conv_stage& s4 = w->stages[r - 1];
@@ -524,12 +549,7 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
             for (int k = 0; k < w->n_stages; ++k) other_use |= (k != r && w->stages[k].skip_stage == r - 1) || w->stages[k].skip_stage == r;
             if (other_use) continue;
             std::vector<int> frozen, live;
-            for (int c = 0; c < 64; ++c) {
-                const float inv = (1.0f / sqrtf(s5.variance[c] + w->bn_epsilon)) * s5.gamma[c];
-                const double reach = std::max(std::fabs(static_cast<double>(s5.mean[c])), std::fabs(6.0 - static_cast<double>(s5.mean[c])));
-                const bool fz = std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(s5.beta[c])) * 2.98023223876953125e-8;
-                (fz ? frozen : live).push_back(c);
-            }
+            for (int c = 0; c < 64; ++c) (bn1_frozen(s5, c) ? frozen : live).push_back(c);
             if (frozen.size() < 32) continue;
             while (frozen.size() > 32) {
                 live.push_back(frozen.back());
@@ -541,52 +561,11 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
             for (int p = 0; p < 32; ++p) fold_pi[32 + p] = frozen[p];
             fold_r = r;
         }
-        auto ensure_copy = [&]() {
-            if (!stg_copy.empty()) return;
-            stg_copy.assign(w->stages, w->stages + w->n_stages);
-            wp = *w;
-            wp.stages = stg_copy.data();
-            w = &wp;
-        };
-        auto perm_vec = [&](const std::vector<int>& pi, const float* src) -> const float* {
-            owned.emplace_back(pi.size());
-            for (size_t p = 0; p < pi.size(); ++p) owned.back()[p] = src[pi[p]];
-            return owned.back().data();
-        };
-        auto perm_kernel = [&](const std::vector<int>& pi, const float* src, int cin, int cout, bool pin, bool pout) -> const float* {
-            owned.emplace_back(static_cast<size_t>(9) * cin * cout);
-            std::vector<float>& dst = owned.back();
-            for (int tap = 0; tap < 9; ++tap)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int co = 0; co < cout; ++co)
-                        dst[(static_cast<size_t>(tap) * cin + ci) * cout + co] = src[(static_cast<size_t>(tap) * cin + (pin ? pi[ci] : ci)) * cout + (pout ? pi[co] : co)];
-            return dst.data();
-        };
-        auto bn1_frozen = [&](const rn_conv_stage& st, int c) {
-            const float inv = (1.0f / sqrtf(st.variance[c] + w->bn_epsilon)) * st.gamma[c];
-            const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
-            return std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8;
-        };
         if (fold_r >= 0) {
-            const std::vector<int>& pi = fold_pi;
-            ensure_copy();
-            const int r = fold_r;
-            const rn_conv_stage s4 = stg_copy[r - 1], s5 = stg_copy[r], s6 = stg_copy[r + 1];
-            stg_copy[r - 1].kernel = perm_kernel(pi, s4.kernel, s4.cin, 64, false, true);
-            stg_copy[r - 1].gamma = perm_vec(pi, s4.gamma);
-            stg_copy[r - 1].beta = perm_vec(pi, s4.beta);
-            stg_copy[r - 1].mean = perm_vec(pi, s4.mean);
-            stg_copy[r - 1].variance = perm_vec(pi, s4.variance);
-            stg_copy[r].kernel = perm_kernel(pi, s5.kernel, 64, 64, true, true);
-            stg_copy[r].gamma = perm_vec(pi, s5.gamma);
-            stg_copy[r].beta = perm_vec(pi, s5.beta);
-            stg_copy[r].mean = perm_vec(pi, s5.mean);
-            stg_copy[r].variance = perm_vec(pi, s5.variance);
-            stg_copy[r].gamma2 = perm_vec(pi, s5.gamma2);
-            stg_copy[r].beta2 = perm_vec(pi, s5.beta2);
-            stg_copy[r].mean2 = perm_vec(pi, s5.mean2);
-            stg_copy[r].variance2 = perm_vec(pi, s5.variance2);
-            stg_copy[r + 1].kernel = perm_kernel(pi, s6.kernel, 64, s6.cout, true, false);
+            rw.permute_couts(fold_r - 1, fold_pi);
+            rw.permute_couts(fold_r, fold_pi);
+            rw.permute_cins(fold_r, fold_pi);
+            rw.permute_cins(fold_r + 1, fold_pi);
         }
         // ---- ... and frozen INPUT channels: a pooled stage p without a second BN whose output only feeds the convolution of stage
         // p + 1 (nobody's residual) and whose BN freezes >= 8 channels (same inequality).  Its couts / the consumer's cins are
@@ -594,8 +573,8 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
         // from the frozen ones' contribution (rn_f32m_prepare: a variant of the stage kernel must exist for that channel count)
         for (int r = 1; r < w->n_stages && kfold_r < 0; ++r) {
             const int p = r - 1;
-            const rn_conv_stage& sp = w->stages[p];
-            const rn_conv_stage& sc = w->stages[r];
+            const rn_conv_stage& sp = rw.stages[p];
+            const rn_conv_stage& sc = rw.stages[r];
             if (fold_r >= 0 && (p == fold_r - 1 || p == fold_r)) continue;          // (those channels are relabelled already)
             if (sp.skip_stage >= 0 || sp.gamma2 || sp.pool_k != 4 || !sp.gamma || !sp.beta || !sp.mean || !sp.variance) continue;
             if (sc.cin != sp.cout || sp.cout % 8 != 0 || sp.cout > 64) continue;
@@ -618,18 +597,11 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
             kfold_proven = proven;
         }
         if (kfold_r >= 0) {
-            const std::vector<int>& pi = kfold_pi;
-            ensure_copy();
-            const int r = kfold_r;
-            const rn_conv_stage sp = stg_copy[r - 1], sc = stg_copy[r];
-            stg_copy[r - 1].kernel = perm_kernel(pi, sp.kernel, sp.cin, sp.cout, false, true);
-            stg_copy[r - 1].gamma = perm_vec(pi, sp.gamma);
-            stg_copy[r - 1].beta = perm_vec(pi, sp.beta);
-            stg_copy[r - 1].mean = perm_vec(pi, sp.mean);
-            stg_copy[r - 1].variance = perm_vec(pi, sp.variance);
-            stg_copy[r].kernel = perm_kernel(pi, sc.kernel, sc.cin, sc.cout, true, false);
+            rw.permute_couts(kfold_r - 1, kfold_pi);
+            rw.permute_cins(kfold_r, kfold_pi);
         }
     }
+    w = &rw.w;
     if ((rc = build_plan(h, w)) != RN_OK) return fail(rc);
     if (fold_r >= 0) {
         h->f32_fold_stage = fold_r;
@@ -1080,12 +1052,9 @@ extern "C" int rn_tap(rn_handle* h, int node_id, float* out, size_t cap_elems, s
     // a handle may store this tensor with its channels relabelled (frozen-channel folding, rn_fused_prepare): hand it out in the
     // reference's channel order
     {
-        const int* perm = fused_mode(h) ? rn_fused_node_perm(h, node_id) : nullptr;
-        if (!perm) {
-            auto it = h->node_perm.find(node_id);
-            if (it != h->node_perm.end()) perm = it->second.data();
-        }
-        if (perm) {
+        auto it = h->node_perm.find(node_id);
+        if (it != h->node_perm.end()) {
+            const int* perm = it->second.data();
             const int c = nb.info.c;
             std::vector<float> px(static_cast<size_t>(c));
             for (size_t q = 0; q < total / static_cast<size_t>(c); ++q) {

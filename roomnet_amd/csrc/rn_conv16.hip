@@ -393,8 +393,7 @@ int rn_conv16_colblocks(int out_side) { return (out_side + C16_BLKW - 1) / C16_B
 
 // A-operand fragments: frag[chunk c][cout tile t][lane][j] = W[k = 32 c + 8 (lane / 16) + j][cout = 16 t + lane % 16]
 // (k = tap * 64 + channel, the HWIO order of the checkpoint)
-void rn_conv16_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                    std::vector<unsigned short>* out) {
+void rn_conv16_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(C16_KC) * 8 * 64 * 8, 0);
     for (int c = 0; c < C16_KC; ++c)
         for (int t = 0; t < 8; ++t)
@@ -402,7 +401,7 @@ void rn_conv16_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(f
                 for (int j = 0; j < 8; ++j) {
                     const int k = 32 * c + 8 * (l >> 4) + j, co = 16 * t + (l & 15);
                     const float v = w_hwio[static_cast<size_t>(k) * C16_COUT + co];
-                    (*out)[((static_cast<size_t>(c) * 8 + t) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(c) * 8 + t) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 
@@ -429,15 +428,14 @@ int rn_conv16p_colblocks(int out_side) {
 }
 
 // A-operand fragments: frag[chunk c][lane][j] = W[k = 32 c + 8 (lane / 16) + j][cout = lane % 16]
-void rn_conv16p_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out) {
+void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(P16_KC) * 64 * 8, 0);
     for (int c = 0; c < P16_KC; ++c)
         for (int l = 0; l < 64; ++l)
             for (int j = 0; j < 8; ++j) {
                 const int k = 32 * c + 8 * (l >> 4) + j, co = l & 15;
                 const float v = w_hwio[static_cast<size_t>(k) * P16_COUT + co];
-                (*out)[(static_cast<size_t>(c) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                (*out)[(static_cast<size_t>(c) * 64 + l) * 8 + j] = rn_to16(v, dtype);
             }
 }
 

@@ -14,8 +14,6 @@ void rn_fused_release(rn_handle* h);
 int rn_fused_launch_rep(const rn_handle* h, int stage);
 // the stage's output tensor is never written to HBM on this handle (it only exists in LDS inside a fused launch)
 bool rn_fused_stage_elided(const rn_handle* h, int stage);
-// channel relabelling of a node's stored tensor on this handle (position p holds the reference's channel perm[p]), or null
-const int* rn_fused_node_perm(const rn_handle* h, int node_id);
 void rn_fused_frozen_info(const rn_handle* h, int info[4]);
 // constant channels nobody computes (round 6): info = {stage whose last cout quarter is constant in the handle's 16-bit store or -1,
 // channels of it proven constant, channels folded (16), input channels the stage behind it still contracts (48)}
@@ -52,50 +50,40 @@ bool rn_stage23_supported(int in_side);
 // rn_conv16.hip: the un-pooled 64 -> 128 stage on 16x16x32 matrix tiles
 bool rn_conv16_supported(int cin, int cout, int pool_k, bool res);
 int rn_conv16_colblocks(int out_side);
-void rn_conv16_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                    std::vector<unsigned short>* out);
+void rn_conv16_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_conv16_launch(int dtype, hipStream_t s, const rnk::Conv16Args& a, int n);
 // ... and the 128 -> 16 stage with avg-pool 4/2 (one wave = one 16-pixel tile x all 16 couts, no K split)
 bool rn_conv16p_supported(int cin, int cout, int pool_k, int pool_s, bool res);
 int rn_conv16p_colblocks(int out_side);
 int rn_conv16p_wgs_per_cu(int out_side);
-void rn_conv16p_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out);
+void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_conv16p_launch(int dtype, hipStream_t s, const rnk::Conv16Args& a, int n);
 bool rn_stage23_plan(int in_side, int* n_cblocks, int* x0, int* wo);   // column blocks (x0, wo: 4 entries)
 int rn_stage23_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
 // the un-pooled 64 -> 128 stage with row-register blocking (rn_stage6x.hip)
 bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side);
 bool rn_stage6x_plan(int out_side, int* n_cb, int* xo0, int* wo);       // column blocks (xo0, wo: 4 entries)
-void rn_stage6x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out);
+void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage6x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // ... without its input channels 48..63 (constants of the handle): StageArgs::cstart carries their sum
-void rn_stage6x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                       std::vector<unsigned short>* out);
+void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 // the 32 -> 64 stage with pool 4/2 on 16x16x32 tiles with row-register blocking (rn_stage4x.hip)
 bool rn_stage4x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side);
 bool rn_stage4x_plan(int out_side, int* n_cb, int* xo0, int* wo);
-void rn_stage4x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out);
+void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage4x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // the 64 -> 64 residual stage with pool 4/2 on 16x16x32 tiles with row-register blocking (rn_stage5x.hip)
 bool rn_stage5x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side, int skip_side);
 bool rn_stage5x_plan(int out_side, int* n_cb, int* xo0, int* wo);
-void rn_stage5x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out);
+void rn_stage5x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage5x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // ... without its input channels 48..63 (constants on the handle): 15 fragments per cout quarter (StageArgs::cstart carries their sum)
-void rn_stage5x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                       std::vector<unsigned short>* out);
+void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 // the same pair on 16x16x32 tiles (rn_stage23x.hip): own weight fragment order, same launch arguments and column blocks
-void rn_stage23x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                      std::vector<unsigned short>* out);
+void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage23x_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
-void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                             std::vector<unsigned short>* out);
-void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                              std::vector<unsigned short>* out);
+void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
+void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
 
 // ---- float32 conv stages on the matrix cores (rn_stage_f32m.hip): the throughput path of RN_DTYPE_F32 handles without RN_FLAG_TAPS
 int rn_f32m_prepare(rn_handle* h, const rn_weights* w);

@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <cmath>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -126,8 +128,8 @@ struct rn_handle {
     std::vector<void*> allocs;   // everything to hipFree on destroy
     void* fused = nullptr;       // plan of the fused 16-bit path (rn_fused.hip)
     void* f32m = nullptr;        // plan of the float32 matrix-core stage kernels (rn_stage_f32m.hip)
-    // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1), the
-    // couts whose convolution still runs, and the relabelling of the tensors it touches (node id -> position p holds channel perm[p])
+    // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
+    // couts whose convolution still runs
     int f32_fold_stage = -1;
     int f32_fold_live = 0;
     // ... and frozen INPUT channels of a stage (its producer's BN freezes them; relabelled to the end): the stage's index (or -1),
@@ -135,6 +137,8 @@ struct rn_handle {
     int f32_kfold_stage = -1;
     int f32_kfold_live = 0;
     int f32_kfold_proven = 0;
+    // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_create) and 16-bit (rn_fused_prepare) alike:
+    // node id -> position p of the stored tensor holds the reference's channel perm[p] (rn_tap puts them back in order)
     std::map<int, std::vector<int>> node_perm;
     // profiling
     bool profiling = false;
@@ -172,3 +176,99 @@ int rn_launch_resize_u8(hipStream_t s, const uint8_t* d_src, int src_h, int src_
 int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const HeadArgs& a, float* probs,
                    int64_t* ids);
 int rn_launch_convert_to_f32(hipStream_t s, const void* in, int dtype, float* out, int64_t n);
+
+// ---- host helpers of rn_create (rn_api.hip) ---------------------------------------------
+// device memory owned by the handle (freed by rn_destroy); errors as "hipMalloc(N bytes) failed: ..."
+int dev_alloc(rn_handle* h, size_t bytes, void** out);
+template <typename T>
+int upload(rn_handle* h, const T* src, size_t count, T** out) {
+    void* p = nullptr;
+    int rc = dev_alloc(h, count * sizeof(T), &p);
+    if (rc != RN_OK) return rc;
+    RN_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *out = static_cast<T*>(p);
+    return RN_OK;
+}
+
+// tf.nn.batch_normalization folded to y = x * inv + shift, in float32 as every path of the library evaluates it
+inline float rn_bn_inv(float var, float gamma, float eps) { return (1.0f / sqrtf(var + eps)) * gamma; }
+inline float rn_bn_shift(float beta, float mean, float inv) { return beta - mean * inv; }
+
+// A copy of a network's conv stages whose channels can be relabelled (frozen-channel folding): the permuted arrays are owned
+// here, `w` describes the copy.  Position p of a relabelled tensor holds the reference's channel pi[p].
+struct RelabelledWeights {
+    rn_weights w;
+    std::vector<rn_conv_stage> stages;
+    std::vector<std::vector<float>> owned;
+    explicit RelabelledWeights(const rn_weights* src);
+    RelabelledWeights(const RelabelledWeights&) = delete;
+    RelabelledWeights& operator=(const RelabelledWeights&) = delete;
+    void permute_couts(int stage, const std::vector<int>& pi);     // its kernel's couts, its BN (and the second BN of a residual stage)
+    void permute_cins(int stage, const std::vector<int>& pi);      // its kernel's cins
+};
+
+// ---- the 16-bit storage types on the host: round to nearest even, and back
+inline unsigned short f32_to_bf16(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<unsigned short>((u >> 16) | 0x40);   // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return static_cast<unsigned short>(u >> 16);
+}
+
+inline unsigned short f32_to_f16(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x7f800000u) return static_cast<unsigned short>(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0));
+    if (x >= 0x477ff000u) return static_cast<unsigned short>(sign | 0x7c00u);          // overflow -> inf
+    if (x < 0x33000001u) return static_cast<unsigned short>(sign);                     // underflow -> 0
+    int e = static_cast<int>(x >> 23) - 127;
+    uint32_t m = (x & 0x7fffffu) | 0x800000u;
+    int shift;
+    if (e < -14) {
+        shift = 13 + (-14 - e);
+        e = -15;
+    } else {
+        shift = 13;
+    }
+    uint32_t half = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1), halfway = 1u << (shift - 1);
+    if (rem > halfway || (rem == halfway && (half & 1))) ++half;
+    uint32_t out;
+    if (e == -15)
+        out = half;                                   // subnormal (may carry into exponent 1)
+    else
+        out = (static_cast<uint32_t>(e + 15) << 10) + (half - 0x400u);
+    return static_cast<unsigned short>(sign | out);
+}
+
+inline float bf16_bits_to_f32(unsigned short u) {
+    const unsigned bits = static_cast<unsigned>(u) << 16;
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+
+inline float f16_to_f32(unsigned short h) {
+    const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16;
+    const int e = (h >> 10) & 0x1f;
+    const uint32_t m = h & 0x3ffu;
+    float mag;
+    if (e == 0)
+        mag = std::ldexp(static_cast<float>(m), -24);                    // zero / subnormal
+    else if (e == 31)
+        mag = m ? std::nanf("") : INFINITY;
+    else
+        mag = std::ldexp(static_cast<float>(m | 0x400u), e - 25);
+    uint32_t u;
+    std::memcpy(&u, &mag, 4);
+    u |= sign;
+    std::memcpy(&mag, &u, 4);
+    return mag;
+}
+
+// a handle's storage type (RN_DTYPE_BF16 / RN_DTYPE_F16)
+inline unsigned short rn_to16(float v, int dtype) { return dtype == RN_DTYPE_BF16 ? f32_to_bf16(v) : f32_to_f16(v); }
+inline float rn_from16(unsigned short u, int dtype) { return dtype == RN_DTYPE_BF16 ? bf16_bits_to_f32(u) : f16_to_f32(u); }

@@ -970,8 +970,7 @@ bool rn_stage23_supported(int in_side) { return rn_stage23_plan(in_side, nullptr
 
 // B-operand fragments of the 16x16x32 form: frag[tap][half][lane][j] = W[k = 32 tap + 8 (lane / 16) + j][cout(half, lane % 16)]
 // with cout(h, n) = 8 (n / 4) + 4 h + n % 4 (so that a lane's pooled rows 4 g + i of the two halves are couts 8 g .. 8 g + 7)
-void rn_stage23x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                      std::vector<unsigned short>* out) {
+void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(2 * X_KT) * 64 * 8, 0);
     for (int tap = 0; tap < X_KT; ++tap)
         for (int h = 0; h < 2; ++h)
@@ -980,14 +979,13 @@ void rn_stage23x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)
                     const int k = 32 * tap + 8 * (l >> 4) + j, nn = l & 15;
                     const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
                     const float v = w_hwio[static_cast<size_t>(k) * 32 + co];
-                    (*out)[((static_cast<size_t>(tap) * 2 + h) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(tap) * 2 + h) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 
 // Narrow second conv (NB): frag[(2 ky + j)][half][lane][jj] = W[ky][kx = 2 j + (lane / 32)][cin = ring_cin[8 ((lane / 16) & 1) + jj]][cout(half, lane % 16)]
 // (kx = 3: zero); ring_cin[r] = the stage-2 channel at ring channel r (16 entries).  `w_hwio` is the UNpermuted [tap][cin][cout] kernel.
-void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                             std::vector<unsigned short>* out) {
+void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(10) * 64 * 8, 0);
     for (int c = 0; c < 5; ++c)
         for (int h = 0; h < 2; ++h)
@@ -998,14 +996,13 @@ void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype
                     const int cin = ring_cin[8 * ((l >> 4) & 1) + jj];
                     const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
                     const float v = w_hwio[(static_cast<size_t>(tap) * 32 + cin) * 32 + co];
-                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = rn_to16(v, dtype);
                 }
 }
 
 // Eight-channel second conv (N8): frag[c][half][lane][jj] = W[tap 4 c + lane / 16][cin = ring_cin[jj]][cout(half, lane % 16)] (taps > 8: zero);
 // ring_cin[r] = the stage-2 channel at ring channel r (8 entries).  `w_hwio` is the UNpermuted [tap][cin][cout] kernel.
-void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                              std::vector<unsigned short>* out) {
+void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(6) * 64 * 8, 0);
     for (int c = 0; c < 3; ++c)
         for (int h = 0; h < 2; ++h)
@@ -1016,7 +1013,7 @@ void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtyp
                     const int cin = ring_cin[jj];
                     const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
                     const float v = w_hwio[(static_cast<size_t>(tap) * 32 + cin) * 32 + co];
-                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = rn_to16(v, dtype);
                 }
 }
 

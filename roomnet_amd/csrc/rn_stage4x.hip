@@ -367,8 +367,7 @@ bool rn_stage4x_supported(int cin, int cout, int pool_k, int pool_s, bool res, i
 }
 
 // B-operand fragments: frag[f = ky * 3 + kx][cout quarter q][lane][j] = W[tap f][channel 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage4x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out) {
+void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(9) * 4 * 64 * 8, 0);
     for (int f = 0; f < 9; ++f)
         for (int q = 0; q < 4; ++q)
@@ -376,7 +375,7 @@ void rn_stage4x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(
                 for (int j = 0; j < 8; ++j) {
                     const int k = f * 32 + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
                     const float v = w_hwio[static_cast<size_t>(k) * 64 + co];
-                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 

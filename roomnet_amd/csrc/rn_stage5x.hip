@@ -513,8 +513,7 @@ bool rn_stage5x_supported(int cin, int cout, int pool_k, int pool_s, bool res, i
 }
 
 // B-operand fragments: frag[f = (ky * 3 + kx) * 2 + ch][cout quarter q][lane][j] = W[tap ky * 3 + kx][channel 32 ch + 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage5x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out) {
+void rn_stage5x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(18) * 4 * 64 * 8, 0);
     for (int f = 0; f < 18; ++f)
         for (int q = 0; q < 4; ++q)
@@ -523,15 +522,14 @@ void rn_stage5x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(
                     const int tap = f >> 1, ch = f & 1;
                     const int k = tap * 64 + 32 * ch + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
                     const float v = w_hwio[static_cast<size_t>(k) * 64 + co];
-                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 
 // K48 fragments: frag[f = ky * 5 + j][cout quarter q][lane][e]: j < 3 = W[tap (ky, kx = j)][channel 8 (lane / 16) + e]; j = 3: lane groups
 // 0, 1 = W[tap (ky, 0)][channel 32 + 8 g + e], groups 2, 3 = W[tap (ky, 1)][channel 32 + 8 (g - 2) + e]; j = 4: groups 0, 1 =
 // W[tap (ky, 2)][channel 32 + 8 g + e], groups 2, 3 = 0.  Channels 48..63 (constants on the handle) do not appear.
-void rn_stage5x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                       std::vector<unsigned short>* out) {
+void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(15) * 4 * 64 * 8, 0);
     for (int ky = 0; ky < 3; ++ky)
         for (int j = 0; j < 5; ++j)
@@ -552,7 +550,7 @@ void rn_stage5x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16
                             ch = 32 + 8 * g + e;
                         }
                         const float v = w_hwio[(static_cast<size_t>(ky * 3 + kx) * 64 + ch) * 64 + co];
-                        (*out)[((static_cast<size_t>(ky * 5 + j) * 4 + q) * 64 + l) * 8 + e] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                        (*out)[((static_cast<size_t>(ky * 5 + j) * 4 + q) * 64 + l) * 8 + e] = rn_to16(v, dtype);
                     }
 }
 

@@ -279,8 +279,7 @@ bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side) 
 }
 
 // A-operand fragments: frag[f = (ky * 3 + kx) * 2 + ch][cout group q][lane][j] = W[tap][channel 32 ch + 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage6x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                     std::vector<unsigned short>* out) {
+void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(18) * 8 * 64 * 8, 0);
     for (int f = 0; f < 18; ++f)
         for (int q = 0; q < 8; ++q)
@@ -289,13 +288,12 @@ void rn_stage6x_pack(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(
                     const int tap = f >> 1, ch = f & 1;
                     const int k = tap * 64 + 32 * ch + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
                     const float v = w_hwio[static_cast<size_t>(k) * 128 + co];
-                    (*out)[((static_cast<size_t>(f) * 8 + q) * 64 + l) * 8 + j] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                    (*out)[((static_cast<size_t>(f) * 8 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 
 // K48 fragments (rn_stage5x_pack48's layout with eight 16-cout groups): frag[f = ky * 5 + j][group q][lane][e]
-void rn_stage6x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16)(float), unsigned short (*cvt_f16)(float),
-                       std::vector<unsigned short>* out) {
+void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
     out->assign(static_cast<size_t>(15) * 8 * 64 * 8, 0);
     for (int ky = 0; ky < 3; ++ky)
         for (int j = 0; j < 5; ++j)
@@ -316,7 +314,7 @@ void rn_stage6x_pack48(const float* w_hwio, int dtype, unsigned short (*cvt_bf16
                             ch = 32 + 8 * g + e;
                         }
                         const float v = w_hwio[(static_cast<size_t>(ky * 3 + kx) * 64 + ch) * 128 + co];
-                        (*out)[((static_cast<size_t>(ky * 5 + j) * 8 + q) * 64 + l) * 8 + e] = dtype == RN_DTYPE_BF16 ? cvt_bf16(v) : cvt_f16(v);
+                        (*out)[((static_cast<size_t>(ky * 5 + j) * 8 + q) * 64 + l) * 8 + e] = rn_to16(v, dtype);
                     }
 }
 

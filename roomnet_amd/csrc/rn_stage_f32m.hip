@@ -654,17 +654,6 @@ int rn_f32m_prepare(rn_handle* h, const rn_weights* w) {
     auto* fs = new F32mState();
     fs->st.resize(h->stages.size());
     h->f32m = fs;
-    auto upload = [&](const std::vector<float>& v, const char* what, float** out) -> int {
-        void* d = nullptr;
-        if (hipMalloc(&d, v.size() * 4) != hipSuccess) {
-            rn_set_error("hipMalloc(%s) failed", what);
-            return RN_E_NOMEM;
-        }
-        h->allocs.push_back(d);
-        RN_HIP(hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-        *out = static_cast<float*>(d);
-        return RN_OK;
-    };
     auto prepare_stage = [&](size_t si) -> int {
         const StagePlan& s = h->stages[si];
         F32mStage& f = fs->st[si];
@@ -712,10 +701,8 @@ int rn_f32m_prepare(rn_handle* h, const rn_weights* w) {
                             for (int i = 0; i < 4; ++i)
                                 frag[((static_cast<size_t>(tap) * kg + q) * 64 + l) * 4 + i] =
                                     wsrc[(static_cast<size_t>(tap) * s.cin + 16 * q + 4 * (l >> 4) + i) * s.cout + (l & 15)];
-                float* d = nullptr;
-                const int rc = upload(frag, "fp32 MFMA weights", &d);
+                const int rc = upload(h, reinterpret_cast<const f32x4*>(frag.data()), frag.size() / 4, &f.wfrag);
                 if (rc != RN_OK) return rc;
-                f.wfrag = reinterpret_cast<f32x4*>(d);
                 f.m16 = true;
                 f.variant = static_cast<int>(v);
                 f.ks16 = k.ks;
@@ -766,10 +753,8 @@ int rn_f32m_prepare(rn_handle* h, const rn_weights* w) {
                                 frag[((static_cast<size_t>(tap * kq + q) * ct_n + t) * 64 + l) * 4 + i] =
                                     wsrc[(static_cast<size_t>(tap) * s.cin + c) * s.cout + co];
                         }
-        float* d = nullptr;
-        int rc = upload(frag, "fp32 MFMA weights", &d);
+        int rc = upload(h, reinterpret_cast<const f32x4*>(frag.data()), frag.size() / 4, &f.wfrag);
         if (rc != RN_OK) return rc;
-        f.wfrag = reinterpret_cast<f32x4*>(d);
         if (want_live < s.cin) {
             // the producer writes beta[c] for its frozen channel c at every pixel: sum over the nine taps, in double
             const float* beta = w->stages[si - 1].beta;
@@ -781,7 +766,7 @@ int rn_f32m_prepare(rn_handle* h, const rn_weights* w) {
                         acc += static_cast<double>(wsrc[(static_cast<size_t>(tap) * s.cin + c) * s.cout + co]) * static_cast<double>(beta[c]);
                 ci[co] = static_cast<float>(acc);
             }
-            if ((rc = upload(ci, "fp32 frozen-input constants", &f.cinit)) != RN_OK) return rc;
+            if ((rc = upload(h, ci.data(), ci.size(), &f.cinit)) != RN_OK) return rc;
         }
         f.on = true;
         return RN_OK;

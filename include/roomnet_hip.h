@@ -248,6 +248,37 @@ RN_API int rn_sync(rn_handle* h);
 RN_API int rn_set_stream(rn_handle* h, void* hip_stream);
 RN_API int rn_set_stream_null(rn_handle* h);
 
+/* ---- grad-CAM class-evidence maps ---------------------------------------------
+ * Where in the image did the network see class c?  For image i and class c_i (class_ids[i], or
+ * the argmax of this call's own softmax when class_ids is NULL):
+ *   S     = z[c_i], z = node "d3.mm": the last dense layer's x @ W + b BEFORE its ReLU6
+ *           (reference network.py:237).  The reference applies ReLU6 to its logits, whose gradient
+ *           is zero wherever the winning logit is <= 0 or >= 6 -- and a confident prediction can
+ *           sit exactly there; the pre-activation is the only score that always has a gradient.
+ *   A     = layer_node, the rn_node_info id of "s6.bn" (the 128-channel conv_block, 46 x 46 at
+ *           224, 140 x 140 at 600) or "s7.bn" (first step of the last block, 21 x 21 x 16 at 224,
+ *           68 x 68 x 16 at 600), as this call's forward pass stored it.  Other nodes: RN_E_INVALID.
+ *   G     = dS/dA in float32 with TensorFlow's gradient rules: Relu6Grad passes where 0 < x < 6
+ *           (pre-activations recomputed from the stored activations), AvgPool VALID spreads g/k^2
+ *           over each (overlapping) window, inference BN multiplies by gamma/sqrt(var+eps), Add
+ *           sends g to both inputs (s7.bn gets gradient through conv 8 AND the stage-9 skip), the
+ *           legacy ResizeBilinear takes its transpose, MatMul the transposed kernel.
+ *   alpha[c]  = mean over (y, x) of G[y, x, c]           -> alpha [n, c] (may be NULL)
+ *   cam[y, x] = max(0, sum_c alpha[c] A[y, x, c])         -> cam [n, h, w], float32, not normalised
+ * probs / ids are bit-identical to rn_forward_u8 of the same batch on the same handle.  On 16-bit
+ * handles the call runs the back end as its split launches (stage 6, stage 7, the tail) whatever
+ * n is, so that s6.bn and s7.bn are written; that choice is per call.  Runs on the handle's stream.
+ * RN_E_INVALID (with a message) for an unsupported layer, class_ids[i] outside [0, num_classes)
+ * or n outside [1, max_batch]; the handle stays usable.  The first call allocates the adjoint's
+ * device workspace (sized for max_batch; freed by rn_destroy).  The host entry points block;
+ * the device one only enqueues (its class ids, when given, are read back first to be checked). */
+RN_API int rn_grad_cam_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, const int32_t* class_ids, int layer_node, float* cam,
+                          float* alpha, float* probs, int64_t* ids);
+RN_API int rn_grad_cam_f32(rn_handle* h, const float* rgb_nhwc, int n, const int32_t* class_ids, int layer_node, float* cam,
+                           float* alpha, float* probs, int64_t* ids);
+RN_API int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, const int32_t* d_class_ids, int layer_node,
+                                 float* d_cam, float* d_alpha, float* d_probs, int64_t* d_ids);
+
 /* ---- introspection -----------------------------------------------------------
  * rn_tap copies graph node `node_id` of the last forward call to host float32
  * (layout [n, h, w, c]); needs RN_FLAG_TAPS for conv/pool/add nodes; the
@@ -258,7 +289,10 @@ RN_API int rn_set_stream_null(rn_handle* h);
  * with RN_FLAG_TAPS, and stages the matrix-core float32 kernels do not cover);
  * 16-bit handles never materialise it.  Asking for a node that was not written
  * returns RN_E_STATE.  This is the per-layer
- * debug read-out the reference gets from self.layers (network.py:30, :207). */
+ * debug read-out the reference gets from self.layers (network.py:30, :207).
+ * After a grad-CAM call (rn_grad_cam_*) rn_tap returns THAT call's forward tensors: on 16-bit
+ * handles it ran the back end as its split launches, so s6.bn and s7.bn are readable even
+ * at a batch where rn_forward_* fuses them away; the next rn_forward_* chooses as before. */
 /* What rn_create folded on this handle (zero / -1 where nothing is): info[0] = channels of the first 32 -> 32 stage's output
  * (16-bit handles: the fused pair's on-chip tensor) that are provably constant and therefore not contracted by the next stage
  * (24, 16 or 0; 16-bit handles since round 6 prove it on the tensor's 16-BIT STORE -- the two ends of the pooled sum's range store

@@ -42,7 +42,11 @@ EXPORTED_SYMBOLS = (
     "rn_crop_resize_u8_device", "rn_crop_resize_batch_u8_device", "rn_classify_images_u8", "rn_host_alloc", "rn_host_free", "rn_frozen_info", "rn_const_info",
     "rn_group_create", "rn_group_destroy", "rn_group_size", "rn_group_handle", "rn_group_forward_u8",
     "rn_group_forward_u8_device", "rn_group_result_buffer", "rn_group_sync", "rn_group_plan",
+    "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
 )
+
+# the layers rn_grad_cam_* explains (include/roomnet_hip.h: grad-CAM)
+GRAD_CAM_LAYERS = ("s6.bn", "s7.bn")
 
 
 class RoomNetLibraryError(RuntimeError):
@@ -180,6 +184,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "rn_group_plan"):
         lib.rn_group_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(sz)]
         lib.rn_group_plan.restype = i32
+    if hasattr(lib, "rn_grad_cam_u8"):
+        for name in ("rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device"):
+            fn = getattr(lib, name)
+            fn.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+            fn.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -395,6 +404,49 @@ class Engine:
         rc = self.lib.rn_forward_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_probs),
                                            C.c_void_p(d_ids))
         _check(self.lib, rc, "rn_forward_u8_device")
+
+    def grad_cam(self, x: np.ndarray, class_ids=None, layer: str = "s6.bn", with_alpha: bool = False):
+        """Grad-CAM maps of a batch (``rn_grad_cam_u8`` for uint8 BGR ``[N,S,S,3]``, ``rn_grad_cam_f32`` for a pre-processed
+        float RGB batch on float32 handles).  ``class_ids``: int per image or None (each image's argmax); ``layer``: "s6.bn" or
+        "s7.bn".  Returns ``(cam [N,h,w] float32, ids [N] int64, probs [N,C] float32)`` and, with ``with_alpha``, ``alpha [N,c]``
+        last.  Score, gradient rules and layers: include/roomnet_hip.h, grad-CAM."""
+        if layer not in GRAD_CAM_LAYERS:
+            raise ValueError("grad_cam: layer must be one of %s, got %r" % (GRAD_CAM_LAYERS, layer))
+        s = self.graph.im_side
+        x = np.asarray(x)
+        if x.ndim != 4 or x.shape[1:] != (s, s, 3):
+            raise ValueError("expected a [N,%d,%d,3] batch, got %s" % (s, s, x.shape))
+        u8 = x.dtype == np.uint8
+        x = np.ascontiguousarray(x, dtype=np.uint8 if u8 else np.float32)
+        fn = self.lib.rn_grad_cam_u8 if u8 else self.lib.rn_grad_cam_f32
+        nid, (h, w, c) = self.nodes()[layer]
+        n = x.shape[0]
+        cls = None
+        if class_ids is not None:
+            cls = np.ascontiguousarray(np.broadcast_to(np.asarray(class_ids), (n,)), dtype=np.int32)
+        cam = np.empty((n, h, w), np.float32)
+        alpha = np.empty((n, c), np.float32)
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            rc = fn(self.handle, x[i:i + m].ctypes.data, m, None if cls is None else cls[i:i + m].ctypes.data, nid,
+                    cam[i:i + m].ctypes.data, alpha[i:i + m].ctypes.data if with_alpha else None, probs[i:i + m].ctypes.data,
+                    ids[i:i + m].ctypes.data)
+            _check(self.lib, rc, "rn_grad_cam")
+        if with_alpha:
+            return cam, ids, probs, alpha
+        return cam, ids, probs
+
+    def grad_cam_u8_device(self, d_bgr: int, n: int, d_class_ids: Optional[int], layer: str, d_cam: int, d_alpha: Optional[int],
+                           d_probs: int, d_ids: int) -> None:
+        """Asynchronous ``rn_grad_cam_u8_device`` on raw device pointers."""
+        if layer not in GRAD_CAM_LAYERS:
+            raise ValueError("grad_cam: layer must be one of %s, got %r" % (GRAD_CAM_LAYERS, layer))
+        rc = self.lib.rn_grad_cam_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_class_ids) if d_class_ids else None,
+                                            self.nodes()[layer][0], C.c_void_p(d_cam), C.c_void_p(d_alpha) if d_alpha else None,
+                                            C.c_void_p(d_probs), C.c_void_p(d_ids))
+        _check(self.lib, rc, "rn_grad_cam_u8_device")
 
     def sync(self) -> None:
         _check(self.lib, self.lib.rn_sync(self.handle), "rn_sync")

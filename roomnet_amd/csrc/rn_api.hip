@@ -601,6 +601,8 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
             rw.permute_cins(kfold_r, kfold_pi);
         }
     }
+    // (the grad-CAM adjoint keeps its host copies from the caller's weights, in the reference's channel order)
+    if ((rc = rn_gradcam_keep(h, w)) != RN_OK) return fail(rc);
     w = &rw.w;
     if ((rc = build_plan(h, w)) != RN_OK) return fail(rc);
     if (fold_r >= 0) {
@@ -661,6 +663,7 @@ extern "C" void rn_destroy(rn_handle* h) {
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     rn_fused_release(h);
     rn_f32m_release(h);
+    rn_gradcam_release(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -753,6 +756,131 @@ extern "C" int rn_forward_u8(rn_handle* h, const uint8_t* bgr, int n, float* pro
     RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
     RN_HIP(hipStreamSynchronize(h->stream));
     return RN_OK;
+}
+
+// ---- grad-CAM class-evidence maps (rn_gradcam.hip): the forward pass of the call (16-bit handles: the back end as its split
+// launches, so that s6.bn and s7.bn reach HBM), then the adjoint of the last conv block and the head
+namespace {
+int gradcam_check(rn_handle* h, int n, int layer_node, bool* layer6) {
+    if (!h) {
+        rn_set_error("null handle");
+        return RN_E_INVALID;
+    }
+    if (const char* why = rn_gradcam_unsupported(h)) {
+        rn_set_error("rn_grad_cam: not supported on this graph (%s)", why);
+        return RN_E_INVALID;
+    }
+    if (n < 1 || n > h->max_batch) {
+        rn_set_error("rn_grad_cam: n = %d out of range (1..%d)", n, h->max_batch);
+        return RN_E_INVALID;
+    }
+    int node6, node7;
+    rn_gradcam_layers(h, &node6, &node7);
+    if (layer_node != node6 && layer_node != node7) {
+        const char* nm = layer_node >= 0 && layer_node < static_cast<int>(h->nodes.size()) ? h->nodes[layer_node].info.name : "?";
+        rn_set_error("rn_grad_cam: layer node %d (%s) is not supported (s6.bn = %d, s7.bn = %d)", layer_node, nm, node6, node7);
+        return RN_E_INVALID;
+    }
+    *layer6 = layer_node == node6;
+    return RN_OK;
+}
+
+int gradcam_check_classes(rn_handle* h, const int32_t* cls, int n) {
+    for (int i = 0; i < n; ++i)
+        if (cls[i] < 0 || cls[i] >= h->num_classes) {
+            rn_set_error("rn_grad_cam: class_ids[%d] = %d outside [0, %d)", i, cls[i], h->num_classes);
+            return RN_E_INVALID;
+        }
+    return RN_OK;
+}
+
+// forward on the device input (exactly one of d_bgr / d_rgb), then the adjoint; classes already validated
+int gradcam_device(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int n, const int32_t* d_cls, bool layer6, float* d_cam,
+                   float* d_alpha, float* d_probs, int64_t* d_ids) {
+    h->split_backend = true;
+    int rc = d_bgr ? rn_forward_u8_device(h, d_bgr, n, d_probs, d_ids) : rn_forward_f32_device(h, d_rgb, n, d_probs, d_ids);
+    h->split_backend = false;
+    if (rc != RN_OK) return rc;
+    DeviceGuard guard(h->device);
+    for (int s = 0; s < static_cast<int>(h->stages.size()); ++s)
+        if (fused_mode(h) && rn_fused_stage_elided(h, s)) {
+            int node6, node7;
+            rn_gradcam_layers(h, &node6, &node7);
+            if (h->stages[s].node_bn == node6 || h->stages[s].node_bn == node7) {
+                rn_set_error("rn_grad_cam: the forward pass did not write %s", h->nodes[h->stages[s].node_bn].info.name);
+                return RN_E_STATE;
+            }
+        }
+    return rn_gradcam_launch(h, n, d_cls, d_ids, layer6, d_cam, d_alpha);
+}
+
+int gradcam_host(rn_handle* h, const uint8_t* bgr, const float* rgb, int n, const int32_t* class_ids, int layer_node, float* cam,
+                 float* alpha, float* probs, int64_t* ids) {
+    bool layer6 = false;
+    int rc = gradcam_check(h, n, layer_node, &layer6);
+    if (rc != RN_OK) return rc;
+    if ((!bgr && !rgb) || !cam || !probs || !ids) {
+        rn_set_error("null buffer");
+        return RN_E_INVALID;
+    }
+    if (class_ids && (rc = gradcam_check_classes(h, class_ids, n)) != RN_OK) return rc;
+    DeviceGuard guard(h->device);
+    int32_t* d_cls = nullptr;
+    float *d_cam = nullptr, *d_alpha = nullptr;
+    if ((rc = rn_gradcam_staging(h, &d_cls, &d_cam, &d_alpha)) != RN_OK) return rc;
+    const size_t px = static_cast<size_t>(h->im_side) * h->im_side * 3;
+    if (bgr)
+        RN_HIP(hipMemcpyAsync(h->d_in_u8, bgr, static_cast<size_t>(n) * px, hipMemcpyHostToDevice, h->stream));
+    else if (!fused_mode(h))
+        RN_HIP(hipMemcpyAsync(h->nodes[h->node_input].ptr, rgb, static_cast<size_t>(n) * px * 4, hipMemcpyHostToDevice, h->stream));
+    else {
+        rn_set_error("16-bit handles take uint8 BGR input (the pre-processing is folded into stage 0's weights)");
+        return RN_E_STATE;
+    }
+    if (class_ids) RN_HIP(hipMemcpyAsync(d_cls, class_ids, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, h->stream));
+    rc = gradcam_device(h, bgr ? h->d_in_u8 : nullptr, bgr ? nullptr : static_cast<const float*>(h->nodes[h->node_input].ptr), n,
+                        class_ids ? d_cls : nullptr, layer6, d_cam, d_alpha, h->d_probs, h->d_ids);
+    if (rc != RN_OK) return rc;
+    int node6, node7;
+    rn_gradcam_layers(h, &node6, &node7);
+    const rn_node_info& li = h->nodes[layer_node].info;
+    RN_HIP(hipMemcpyAsync(cam, d_cam, static_cast<size_t>(n) * li.h * li.w * 4, hipMemcpyDeviceToHost, h->stream));
+    if (alpha) RN_HIP(hipMemcpyAsync(alpha, d_alpha, static_cast<size_t>(n) * li.c * 4, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipStreamSynchronize(h->stream));
+    return RN_OK;
+}
+}  // namespace
+
+extern "C" int rn_grad_cam_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, const int32_t* class_ids, int layer_node, float* cam,
+                              float* alpha, float* probs, int64_t* ids) {
+    return gradcam_host(h, bgr_nhwc, nullptr, n, class_ids, layer_node, cam, alpha, probs, ids);
+}
+
+extern "C" int rn_grad_cam_f32(rn_handle* h, const float* rgb_nhwc, int n, const int32_t* class_ids, int layer_node, float* cam,
+                               float* alpha, float* probs, int64_t* ids) {
+    return gradcam_host(h, nullptr, rgb_nhwc, n, class_ids, layer_node, cam, alpha, probs, ids);
+}
+
+extern "C" int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, const int32_t* d_class_ids, int layer_node,
+                                     float* d_cam, float* d_alpha, float* d_probs, int64_t* d_ids) {
+    bool layer6 = false;
+    int rc = gradcam_check(h, n, layer_node, &layer6);
+    if (rc != RN_OK) return rc;
+    if (!d_bgr_nhwc || !d_cam || !d_probs || !d_ids) {
+        rn_set_error("null buffer");
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(h->device);
+    if (d_class_ids) {
+        // (validated before anything is launched: the classes are read back on the handle's stream)
+        std::vector<int32_t> cls(static_cast<size_t>(n));
+        RN_HIP(hipMemcpyAsync(cls.data(), d_class_ids, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, h->stream));
+        RN_HIP(hipStreamSynchronize(h->stream));
+        if ((rc = gradcam_check_classes(h, cls.data(), n)) != RN_OK) return rc;
+    }
+    return gradcam_device(h, d_bgr_nhwc, nullptr, n, d_class_ids, layer6, d_cam, d_alpha, d_probs, d_ids);
 }
 
 // ---- two-slot host pipeline: the upload of batch k+1 overlaps the forward pass of batch k

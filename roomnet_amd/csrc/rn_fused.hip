@@ -1273,7 +1273,7 @@ int rn_fused_forward(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int
         const StagePlan& s = h->stages[i];
         const FusedStage& f = fs->st[i];
         const StagePlan& prev = h->stages[i - 1];
-        if (fs->use_backend && i + 4 == h->stages.size() && 2 * n >= h->n_cu) {
+        if (fs->use_backend && !h->split_backend && i + 4 == h->stages.size() && 2 * n >= h->n_cu) {
             // stage 6 .. head in one launch: reported under the last stage
             const size_t ns = h->stages.size();
             for (size_t k = i; k + 1 < ns; ++k) rn_record_event(h, 2 + static_cast<int>(k));

@@ -128,6 +128,8 @@ struct rn_handle {
     std::vector<void*> allocs;   // everything to hipFree on destroy
     void* fused = nullptr;       // plan of the fused 16-bit path (rn_fused.hip)
     void* f32m = nullptr;        // plan of the float32 matrix-core stage kernels (rn_stage_f32m.hip)
+    void* gradcam = nullptr;     // what the grad-CAM adjoint keeps from rn_create + its device workspace (rn_gradcam.hip)
+    bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
     // couts whose convolution still runs
     int f32_fold_stage = -1;
@@ -176,6 +178,14 @@ int rn_launch_resize_u8(hipStream_t s, const uint8_t* d_src, int src_h, int src_
 int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const HeadArgs& a, float* probs,
                    int64_t* ids);
 int rn_launch_convert_to_f32(hipStream_t s, const void* in, int dtype, float* out, int64_t n);
+
+// ---- grad-CAM (rn_gradcam.hip)
+int rn_gradcam_keep(rn_handle* h, const rn_weights* w);
+void rn_gradcam_release(rn_handle* h);
+void rn_gradcam_layers(const rn_handle* h, int* node6, int* node7);
+const char* rn_gradcam_unsupported(const rn_handle* h);
+int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* d_ids, bool layer6, float* d_cam, float* d_alpha);
+int rn_gradcam_staging(rn_handle* h, int32_t** d_cls, float** d_cam, float** d_alpha);
 
 // ---- host helpers of rn_create (rn_api.hip) ---------------------------------------------
 // device memory owned by the handle (freed by rn_destroy); errors as "hipMalloc(N bytes) failed: ..."

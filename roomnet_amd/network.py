@@ -306,5 +306,47 @@ class RoomNet:
             prepared.append(np.ascontiguousarray(im))
         return self.infer(np.stack(prepared, 0))
 
+    def grad_cam(self, im_in, class_ids=None, layer="s6.bn"):
+        """Grad-CAM class-evidence maps (not in the reference): where in each image the network saw its class.
+        ``im_in`` is an ``[N,S,S,3]`` BGR batch (the feed rules of ``infer``), or one BGR ``[H,W,3]`` image or a list of
+        them, of any size (centre-cropped and resized exactly as ``infer_images`` does).  ``class_ids``: the class per image to explain
+        (None: each image's argmax); ``layer``: "s6.bn" (46 x 46 at 224) or "s7.bn" (21 x 21).  Returns ``(cams [N,h,w]
+        float32, not normalised, ids int64[N], probs float32[N,C])``; ``roomnet_amd.cam`` upsamples and overlays a map.
+        The score is the last dense layer's pre-ReLU6 logit (include/roomnet_hip.h, grad-CAM)."""
+        from ._capi import GRAD_CAM_LAYERS
+        if layer not in GRAD_CAM_LAYERS:
+            raise ValueError("grad_cam: layer must be one of %s, got %r" % (GRAD_CAM_LAYERS, layer))
+        if isinstance(im_in, np.ndarray) and im_in.ndim == 3:
+            im_in = [im_in]                                   # one HWC image: a batch of one
+        if isinstance(im_in, np.ndarray) and im_in.ndim == 4:
+            im = im_in
+            if im.shape[1:] != (self.im_side, self.im_side, 3):
+                raise ValueError("Cannot feed value of shape %s for Tensor 'input_x_tensor:0', which has shape "
+                                 "'(?, %d, %d, 3)'" % (im.shape, self.im_side, self.im_side))
+        elif isinstance(im_in, np.ndarray):
+            raise ValueError("grad_cam: expected an [N,S,S,3] batch, one [H,W,3] image or a list of images, got shape %s"
+                             % (im_in.shape,))
+        else:
+            prepared = []
+            for one in im_in:
+                one = np.asarray(one)
+                if one.ndim != 3 or one.shape[2] != 3:
+                    raise ValueError("grad_cam: expected [H,W,3] BGR images, got shape %s" % (one.shape,))
+                one = self.center_crop(one)
+                if one.shape[0] != self.im_side or one.shape[1] != self.im_side:
+                    one = resize_linear_u8(np.ascontiguousarray(one, dtype=np.uint8), self.im_side, self.im_side)
+                prepared.append(np.ascontiguousarray(one))
+            if not prepared:
+                raise ValueError("grad_cam: no images")
+            im = np.stack(prepared, 0)
+        eng = self._engine()
+        im = self._as_feed(im)
+        if im.dtype == np.uint8:
+            cams, ids, probs = eng.grad_cam(im, class_ids=class_ids, layer=layer)
+        else:
+            x = (((im[:, :, :, [2, 1, 0]] / 255.) * 2) - 1).astype(np.float32)
+            cams, ids, probs = eng.grad_cam(x, class_ids=class_ids, layer=layer)
+        return cams, ids, probs
+
     def train_step(self, x_in, y):
         raise NotImplementedError("training (network.py:158-170) is out of scope of the MI355X inference path")

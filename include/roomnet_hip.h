@@ -376,6 +376,27 @@ RN_API int rn_group_sync(rn_group* g);
  * followed by ids [max_batch_per_device] int64.  n > ndev * max_batch_per_device is RN_E_RANGE. */
 RN_API int rn_group_plan(int n, int ndev, int max_batch_per_device, int num_classes, int* counts, int* offsets, size_t* slot_bytes);
 
+/* ---- launch geometry of the conv stages, as a pure function (no handle, no device -- testable on any host) -------------
+ * A stage's launch cuts every image into bands of output rows; a workgroup is image x column block x band.  Bands change
+ * no result bit, only how the launch fills the chip.  rn_band_plan returns what rn_forward_* chooses for a launch of
+ * `family` with n images on a chip of n_cu compute units: *rows_per_band rows in each of *n_bands bands.
+ *   out_side     the stage's output side (the second stage's for RN_BANDS_PAIR)
+ *   n_colblocks  workgroups per image and band (column blocks; x cout-tile groups for RN_BANDS_GENERIC / RN_BANDS_F32M)
+ *   wgs_per_cu   workgroups resident on one CU (RN_BANDS_RW: 1 or 4; RN_BANDS_CONV16P: 2 for the 3-wave form, 1 for the
+ *                5-wave form; ignored by the other families)
+ *   pool_k, pool_s  the stage's pooling (pool_k == 0: none; RN_BANDS_ROWREG, RN_BANDS_RW, RN_BANDS_F32M)
+ * n_cu is ignored by RN_BANDS_STAGE0 and RN_BANDS_GENERIC.  A bad argument or an unknown family is RN_E_INVALID. */
+#define RN_BANDS_STAGE0 0   /* stage 0 in a launch of its own */
+#define RN_BANDS_GENERIC 1  /* the generic 16-bit stage kernel */
+#define RN_BANDS_PAIR 2     /* the cross-stage fused pair */
+#define RN_BANDS_CONV16 3   /* the un-pooled 64 -> 128 stage on 16x16x32 tiles */
+#define RN_BANDS_CONV16P 4  /* the pooled 128 -> 16 stage on 16x16x32 tiles */
+#define RN_BANDS_ROWREG 5   /* the row-register kernels (32 -> 64, 64 -> 64 residual, 64 -> 128) */
+#define RN_BANDS_RW 6       /* the register-weights kernels */
+#define RN_BANDS_F32M 7     /* float32 stages on the matrix cores */
+RN_API int rn_band_plan(int family, int n, int n_cu, int out_side, int n_colblocks, int wgs_per_cu, int pool_k, int pool_s,
+                        int* rows_per_band, int* n_bands);
+
 /* ---- simple device memory helpers (so a host language without a HIP binding
  * can keep batches resident in HBM) ---------------------------------------- */
 RN_API int rn_device_malloc(rn_handle* h, size_t bytes, void** d_ptr);

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "rn_crop_resize_u8_device", "rn_crop_resize_batch_u8_device", "rn_classify_images_u8", "rn_host_alloc", "rn_host_free", "rn_frozen_info", "rn_const_info",
     "rn_group_create", "rn_group_destroy", "rn_group_size", "rn_group_handle", "rn_group_forward_u8",
     "rn_group_forward_u8_device", "rn_group_result_buffer", "rn_group_sync", "rn_group_plan",
+    "rn_band_plan",
     "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
 )
 
@@ -184,6 +185,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "rn_group_plan"):
         lib.rn_group_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(sz)]
         lib.rn_group_plan.restype = i32
+    if hasattr(lib, "rn_band_plan"):
+        lib.rn_band_plan.argtypes = [i32] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.rn_band_plan.restype = i32
     if hasattr(lib, "rn_grad_cam_u8"):
         for name in ("rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device"):
             fn = getattr(lib, name)
@@ -598,6 +602,20 @@ def group_plan(n: int, ndev: int, max_batch_per_device: int, num_classes: int = 
     counts, offsets, slot = (C.c_int * ndev)(), (C.c_int * ndev)(), C.c_size_t(0)
     _check(lib, lib.rn_group_plan(n, ndev, max_batch_per_device, num_classes, counts, offsets, C.byref(slot)), "rn_group_plan")
     return list(counts), list(offsets), int(slot.value)
+
+
+# launch families of rn_band_plan (include/roomnet_hip.h: RN_BANDS_*)
+BAND_FAMILIES = {"stage0": 0, "generic": 1, "pair": 2, "conv16": 3, "conv16p": 4, "rowreg": 5, "rw": 6, "f32m": 7}
+
+
+def band_plan(family, n: int, n_cu: int, out_side: int, n_colblocks: int, wgs_per_cu: int = 1, pool_k: int = 0, pool_s: int = 1,
+              lib_path: Optional[str] = None) -> Tuple[int, int]:
+    """``rn_band_plan``: (rows_per_band, n_bands) the forward pass chooses for a launch of ``family`` -- no GPU needed."""
+    lib = load_library(lib_path)
+    fam = BAND_FAMILIES[family] if isinstance(family, str) else int(family)
+    rows, bands = C.c_int(0), C.c_int(0)
+    _check(lib, lib.rn_band_plan(fam, n, n_cu, out_side, n_colblocks, wgs_per_cu, pool_k, pool_s, C.byref(rows), C.byref(bands)), "rn_band_plan")
+    return int(rows.value), int(bands.value)
 
 
 class Group:

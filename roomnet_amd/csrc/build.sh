@@ -1,64 +1,86 @@
 #!/bin/bash
-# Build libroomnet_hip.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+# Build libroomnet_hip.so and the test / A-B library libroomnet_hip_ab.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
+#
+# Every translation unit is named once, in the lists below; the compile loop and the link lines are derived from them.
+# Environment (all optional; tools/build_inc.sh, build_variant.sh, build_variant2.sh and build_clock.sh are thin calls of this):
+#   RN_FILES="FILE ..."       compile only these files; the other objects are reused from build/obj (run a full build first)
+#   RN_VARIANT=NAME           experimental build: RN_FILES are compiled with RN_VARIANT_FLAGS added, into build/var_NAME, and linked
+#                             with the other objects of build/obj into tools/ab/libroomnet_hip_NAME.so; the two libraries stay
+#   RN_VARIANT_FLAGS="..."    extra hipcc flags of the variant's files (defines, -mllvm options)
+#   RN_RW_FLAGS               replaces -mllvm -amdgpu-mfma-vgpr-form for the files of VGPR_FORM
+#   RN_EXTRA_FLAGS            added to the link of libroomnet_hip.so
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
-OUT="$ROOT/roomnet_amd/lib"
-mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-FLAGS=(--offload-arch=gfx950 -O3 -std=c++20 -fno-slp-vectorize -fPIC -shared -fvisibility=hidden
-       -I"$ROOT/include" -I"$HERE" -Wall -Wno-unused-function -DRN_BUILDING)
-# objects are built separately so that per-file scheduler options can be applied
-OBJ="$ROOT/build/obj"
-mkdir -p "$OBJ"
-CFLAGS=("${FLAGS[@]/-shared/}")
-# (a failed background compile must fail the build: a bare `wait` returns 0 and the link would pick up a stale object)
-PIDS=()
-for f in rn_api rn_kernels_f32 rn_fused rn_imageops rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam; do
-    rm -f "$OBJ/$f.o"
-    "$HIPCC" "${CFLAGS[@]}" -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
-    PIDS+=($!)
-done
+
+PLAIN="rn_api rn_kernels_f32 rn_fused rn_imageops rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam"
 # MFMA results stay in VGPRs: the epilogue reads every accumulator with the VALU, and AGPR
 # accumulators cost one v_accvgpr_read each (64 per row in the residual variant).
 # (max-ilp scheduling was measured slower, see NOTES.md)
-rm -f "$OBJ/rn_stage_rw.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage_rw.hip" -o "$OBJ/rn_stage_rw.o" &
-PIDS+=($!)
-rm -f "$OBJ/rn_stage23.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage23.hip" -o "$OBJ/rn_stage23.o" &
-PIDS+=($!)
-rm -f "$OBJ/rn_stage23x.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage23x.hip" -o "$OBJ/rn_stage23x.o" &
-PIDS+=($!)
-rm -f "$OBJ/rn_stage5x.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage5x.hip" -o "$OBJ/rn_stage5x.o" &
-PIDS+=($!)
-rm -f "$OBJ/rn_stage4x.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage4x.hip" -o "$OBJ/rn_stage4x.o" &
-PIDS+=($!)
-rm -f "$OBJ/rn_stage6x.o"
-"$HIPCC" "${CFLAGS[@]}" ${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form} -c "$HERE/rn_stage6x.hip" -o "$OBJ/rn_stage6x.o" &
-PIDS+=($!)
-for p in "${PIDS[@]}"; do wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$OBJ"/rn_api.o "$OBJ"/rn_kernels_f32.o "$OBJ"/rn_fused.o "$OBJ"/rn_imageops.o "$OBJ"/rn_group.o "$OBJ"/rn_tail.o "$OBJ"/rn_conv16.o "$OBJ"/rn_stage_rw.o "$OBJ"/rn_stage23x.o "$OBJ"/rn_stage5x.o "$OBJ"/rn_stage4x.o "$OBJ"/rn_stage6x.o "$OBJ"/rn_stage_f32m.o "$OBJ"/rn_backend.o "$OBJ"/rn_gradcam.o -ldl -lpthread \
-    ${RN_EXTRA_FLAGS:-} -o "$OUT/libroomnet_hip.so"
-echo "built $OUT/libroomnet_hip.so"
-# the test / A-B library: the same objects + the round-2 comparison kernels (RN_FLAG_PAIR_32X32: rn_stage23.hip), which the
-# product library does not carry
+VGPR_FORM="rn_stage_rw rn_stage23x rn_stage5x rn_stage4x rn_stage6x"
+# the test / A-B library: the same objects + the round-2 comparison kernels (RN_FLAG_PAIR_32X32), which the product library
+# does not carry; the files that dispatch to them are compiled again with -DRN_ROUND2_ARMS
+AB_ONLY="rn_stage23"            # (compiled like VGPR_FORM)
+AB_REBUILT="rn_api rn_fused"
+# register report: a spill in one of the hot kernels costs ~25 % of its time (seen on the fused stage pair) and hipcc
+# does not warn about it
+REPORTED="$AB_ONLY $VGPR_FORM rn_tail rn_conv16"
+
+CFLAGS=(--offload-arch=gfx950 -O3 -std=c++20 -fno-slp-vectorize -fPIC -fvisibility=hidden
+        -I"$ROOT/include" -I"$HERE" -Wall -Wno-unused-function -DRN_BUILDING)
+LINK=("$HIPCC" --offload-arch=gfx950 -shared -fPIC)
+OBJ="$ROOT/build/obj"
 AB="$OBJ/ab"
-mkdir -p "$AB"
-rm -f "$AB"/rn_api.o "$AB"/rn_fused.o
-"$HIPCC" "${CFLAGS[@]}" -DRN_ROUND2_ARMS -c "$HERE/rn_api.hip" -o "$AB/rn_api.o" &
-P1=$!
-"$HIPCC" "${CFLAGS[@]}" -DRN_ROUND2_ARMS -c "$HERE/rn_fused.hip" -o "$AB/rn_fused.o" &
-P2=$!
-wait "$P1"; wait "$P2"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$AB"/rn_api.o "$OBJ"/rn_kernels_f32.o "$AB"/rn_fused.o "$OBJ"/rn_imageops.o "$OBJ"/rn_group.o "$OBJ"/rn_tail.o "$OBJ"/rn_conv16.o "$OBJ"/rn_stage_rw.o "$OBJ"/rn_stage23.o "$OBJ"/rn_stage23x.o "$OBJ"/rn_stage5x.o "$OBJ"/rn_stage4x.o "$OBJ"/rn_stage6x.o "$OBJ"/rn_stage_f32m.o "$OBJ"/rn_backend.o "$OBJ"/rn_gradcam.o -ldl -lpthread \
-    -o "$OUT/libroomnet_hip_ab.so"
-echo "built $OUT/libroomnet_hip_ab.so"
-# register report of the hot kernels: a spill in one of them costs ~25 % of its time (seen on the fused stage pair) and
-# hipcc does not warn about it
+VARIANT="${RN_VARIANT:-}"
+FILES="${RN_FILES:-$PLAIN $VGPR_FORM $AB_ONLY}"
+DEST="$OBJ"
+[ -n "$VARIANT" ] && DEST="$ROOT/build/var_$VARIANT"
+mkdir -p "$OBJ" "$AB" "$DEST" "$ROOT/roomnet_amd/lib"
+
+has() { [[ " $1 " == *" $2 "* ]]; }
+# objects are built separately so that per-file scheduler options can be applied
+# (a failed background compile must fail the build: a bare `wait` returns 0 and the link would pick up a stale object)
+PIDS=()
+compile() {     # compile FILE OBJECT [flags]
+    local f="$1" o="$2"
+    shift 2
+    local form=()
+    if has "$VGPR_FORM $AB_ONLY" "$f"; then form=(${RN_RW_FLAGS:--mllvm -amdgpu-mfma-vgpr-form}); fi
+    rm -f "$o"
+    "$HIPCC" "${CFLAGS[@]}" "${form[@]}" "$@" -c "$HERE/$f.hip" -o "$o" &
+    PIDS+=($!)
+}
+for f in $FILES; do
+    has "$PLAIN $VGPR_FORM $AB_ONLY" "$f" || { echo "build.sh: unknown file $f" >&2; exit 2; }
+    compile "$f" "$DEST/$f.o" ${VARIANT:+${RN_VARIANT_FLAGS:-}}
+    if [ -z "$VARIANT" ] && has "$AB_REBUILT" "$f"; then compile "$f" "$AB/$f.o" -DRN_ROUND2_ARMS; fi
+done
+for p in "${PIDS[@]}"; do wait "$p"; done
+
+objects() {     # objects LIST: the object of every file of LIST, the variant's own where it has one
+    local f
+    for f in $1; do
+        if [ -n "$VARIANT" ] && has "$FILES" "$f"; then echo "$DEST/$f.o"; else echo "$OBJ/$f.o"; fi
+    done
+}
+if [ -n "$VARIANT" ]; then
+    mkdir -p "$ROOT/tools/ab"
+    "${LINK[@]}" $(objects "$PLAIN $VGPR_FORM $AB_ONLY") -ldl -lpthread -o "$ROOT/tools/ab/libroomnet_hip_$VARIANT.so"
+    echo "built $ROOT/tools/ab/libroomnet_hip_$VARIANT.so"
+else
+    OUT="$ROOT/roomnet_amd/lib"
+    "${LINK[@]}" $(objects "$PLAIN $VGPR_FORM") -ldl -lpthread ${RN_EXTRA_FLAGS:-} -o "$OUT/libroomnet_hip.so"
+    echo "built $OUT/libroomnet_hip.so"
+    AB_OBJS=()
+    for o in $(objects "$PLAIN $VGPR_FORM $AB_ONLY"); do
+        if has "$AB_REBUILT" "$(basename "$o" .o)"; then AB_OBJS+=("$AB/$(basename "$o")"); else AB_OBJS+=("$o"); fi
+    done
+    "${LINK[@]}" "${AB_OBJS[@]}" -ldl -lpthread -o "$OUT/libroomnet_hip_ab.so"
+    echo "built $OUT/libroomnet_hip_ab.so"
+fi
 if [ -x "$ROOT/tools/spills.sh" ]; then
-    "$ROOT/tools/spills.sh" "$OBJ"/rn_stage23.o "$OBJ"/rn_stage23x.o "$OBJ"/rn_stage5x.o "$OBJ"/rn_stage4x.o "$OBJ"/rn_stage6x.o "$OBJ"/rn_stage_rw.o "$OBJ"/rn_tail.o "$OBJ"/rn_conv16.o | awk '$0 ~ /spills +[1-9]/ {print "  spills: " $0}' | cut -c1-70,95-200 || true
+    for f in $REPORTED; do
+        if has "$FILES" "$f"; then "$ROOT/tools/spills.sh" "$DEST/$f.o"; fi
+    done | awk '$0 ~ /spills +[1-9]/ {print "  spills: " $0}' | cut -c1-70,95-200 || true
 fi

@@ -23,7 +23,6 @@
 // Same arithmetic, operand values and summation order as the three launches: bit-identical (tests/test_hip_fused.py).
 #include "rn_tail_body.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -433,22 +432,16 @@ int rn_backend_launch(rn_handle* h, const i32x4* wfrag6, const float* ptab6, con
     a.ptab7 = ptab7;
     a.So7 = s7.out_side;
     rn_tail_fill_args(h, wfrag_a, wfrag_b, head, d_probs, d_ids, &a.tail);
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(n), dim3(704), B_LDS, h->stream, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(n), dim3(704), B_LDS, h->stream, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
     if (cstart6) {
-        if (h->dtype == RN_DTYPE_BF16) return launch(backend_kernel<RN_DTYPE_BF16, true>);
-        return launch(backend_kernel<RN_DTYPE_F16, true>);
+        if (h->dtype == RN_DTYPE_BF16) return launch(rn_kernel<backend_kernel<RN_DTYPE_BF16, true>>{});
+        return launch(rn_kernel<backend_kernel<RN_DTYPE_F16, true>>{});
     }
-    if (h->dtype == RN_DTYPE_BF16) return launch(backend_kernel<RN_DTYPE_BF16, false>);
-    return launch(backend_kernel<RN_DTYPE_F16, false>);
+    if (h->dtype == RN_DTYPE_BF16) return launch(rn_kernel<backend_kernel<RN_DTYPE_BF16, false>>{});
+    return launch(rn_kernel<backend_kernel<RN_DTYPE_F16, false>>{});
 }

@@ -18,7 +18,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 #include <vector>
 
@@ -441,22 +440,16 @@ void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>
 
 int rn_conv16p_launch(int dtype, hipStream_t s, const Conv16Args& a, int n) {
     const int nt = conv16p_nt(a.Wo);
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};     // 72 KB of dynamic LDS: per device and instantiation
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * nt), static_cast<size_t>(nt == 3 ? P16<3>::LDS : P16<5>::LDS), s, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * nt), static_cast<size_t>(nt == 3 ? P16<3>::LDS : P16<5>::LDS), s, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
     if (nt == 3) {
-        if (dtype == RN_DTYPE_BF16) return launch(conv16p_kernel<RN_DTYPE_BF16, 3>);
-        return launch(conv16p_kernel<RN_DTYPE_F16, 3>);
+        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<conv16p_kernel<RN_DTYPE_BF16, 3>>{});
+        return launch(rn_kernel<conv16p_kernel<RN_DTYPE_F16, 3>>{});
     }
-    if (dtype == RN_DTYPE_BF16) return launch(conv16p_kernel<RN_DTYPE_BF16, 5>);
-    return launch(conv16p_kernel<RN_DTYPE_F16, 5>);
+    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<conv16p_kernel<RN_DTYPE_BF16, 5>>{});
+    return launch(rn_kernel<conv16p_kernel<RN_DTYPE_F16, 5>>{});
 }

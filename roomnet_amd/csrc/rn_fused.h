@@ -1,6 +1,7 @@
 // Fused 16-bit (bf16 / fp16 storage, fp32 accumulate) MFMA execution path.
 #pragma once
 #include <vector>
+#include "rn_bands.h"
 #include "rn_internal.h"
 #include "rn_stage.h"
 
@@ -45,9 +46,18 @@ bool rn_rw_supported(int cin, int cout, int pool_k, int pool_s, bool res, int ou
 int rn_rw_launch(const RwPlan& p, int dtype, hipStream_t s, const rnk::StageArgs& a, dim3 grid);
 int rn_rw_s0sh_colblocks(int out_side);      // column blocks (227 wide) of the shared-ring stage 0 + 1 kernel
 
-// ---- cross-stage fused pair: conv-pool-BN -> conv-pool-BN + residual of a depth-3 block (rn_stage23.hip)
+// ---- cross-stage fused pair: conv-pool-BN -> conv-pool-BN + residual of a depth-3 block.  rn_stage23.hip (32x32x16 tiles, the
+// round-2 form: test / A-B library only) and rn_stage23x.hip (16x16x32 tiles) take the same launch arguments and column blocks
 bool rn_stage23_supported(int in_side);
-// rn_conv16.hip: the un-pooled 64 -> 128 stage on 16x16x32 matrix tiles
+bool rn_stage23_plan(int in_side, int* n_cblocks, int* x0, int* wo);   // column blocks (x0, wo: 4 entries)
+int rn_stage23_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
+// rn_stage23x.hip: own weight fragment order
+void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
+void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
+void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
+int rn_stage23x_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
+
+// ---- 16x16x32 matrix tiles without row-register blocking (rn_conv16.hip): the un-pooled 64 -> 128 stage ...
 bool rn_conv16_supported(int cin, int cout, int pool_k, bool res);
 int rn_conv16_colblocks(int out_side);
 void rn_conv16_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
@@ -58,32 +68,26 @@ int rn_conv16p_colblocks(int out_side);
 int rn_conv16p_wgs_per_cu(int out_side);
 void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_conv16p_launch(int dtype, hipStream_t s, const rnk::Conv16Args& a, int n);
-bool rn_stage23_plan(int in_side, int* n_cblocks, int* x0, int* wo);   // column blocks (x0, wo: 4 entries)
-int rn_stage23_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
-// the un-pooled 64 -> 128 stage with row-register blocking (rn_stage6x.hip)
-bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side);
-bool rn_stage6x_plan(int out_side, int* n_cb, int* xo0, int* wo);       // column blocks (xo0, wo: 4 entries)
-void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-int rn_stage6x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
-// ... without its input channels 48..63 (constants of the handle): StageArgs::cstart carries their sum
-void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-// the 32 -> 64 stage with pool 4/2 on 16x16x32 tiles with row-register blocking (rn_stage4x.hip)
+
+// ---- 16x16x32 tiles with row-register blocking.  rn_stage4x.hip: the 32 -> 64 stage with pool 4/2
 bool rn_stage4x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side);
-bool rn_stage4x_plan(int out_side, int* n_cb, int* xo0, int* wo);
+bool rn_stage4x_plan(int out_side, int* n_cb, int* xo0, int* wo);       // column blocks (xo0, wo: 4 entries)
 void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage4x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
-// the 64 -> 64 residual stage with pool 4/2 on 16x16x32 tiles with row-register blocking (rn_stage5x.hip)
+// rn_stage5x.hip: the 64 -> 64 residual stage with pool 4/2
 bool rn_stage5x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side, int skip_side);
 bool rn_stage5x_plan(int out_side, int* n_cb, int* xo0, int* wo);
 void rn_stage5x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-int rn_stage5x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // ... without its input channels 48..63 (constants on the handle): 15 fragments per cout quarter (StageArgs::cstart carries their sum)
 void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-// the same pair on 16x16x32 tiles (rn_stage23x.hip): own weight fragment order, same launch arguments and column blocks
-void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-int rn_stage23x_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
-void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
-void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
+int rn_stage5x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
+// rn_stage6x.hip: the un-pooled 64 -> 128 stage
+bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side);
+bool rn_stage6x_plan(int out_side, int* n_cb, int* xo0, int* wo);
+void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
+// ... without its input channels 48..63 (constants of the handle): StageArgs::cstart carries their sum
+void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
+int rn_stage6x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 
 // ---- float32 conv stages on the matrix cores (rn_stage_f32m.hip): the throughput path of RN_DTYPE_F32 handles without RN_FLAG_TAPS
 int rn_f32m_prepare(rn_handle* h, const rn_weights* w);

@@ -26,11 +26,10 @@
 // Stage 0 (3 input channels, K = 27) runs on the matrix cores too (`stage0_kernel` below): its operand is the
 // uint8 pixel value, the uint8 -> [-1,1] pre-processing of network.py:129 is folded into its weights.
 #include "rn_fused.h"
-#include <map>
 #include <vector>
 #include <algorithm>
-#include <atomic>
 #include "rn_stage.h"
+#include "rn_clock.h"
 
 #include <cmath>
 #include <cstring>
@@ -430,66 +429,6 @@ __global__ __launch_bounds__(512) void stage_mfma_kernel(const StageArgs a) {
 }
 
 // ------------------------------------------------------------------------- host side
-// Cost of running `wgs` equal workgroups of `rows` row steps each with `slots` of them resident at a time, for the
-// variants with several small workgroups per CU (they are back-filled as slots free up, so a launch does not run in
-// whole rounds of the chip).  Fitted to band-count sweeps on the GPU (NOTES.md, rounds 1-2, "Band counts"):
-//   * 2-wave workgroups, four per CU (32->64 stage): the fractional number of rounds plus an eighth of a round for the
-//     ragged end, 1.5 row steps of prologue per workgroup (224: 2 bands; 600: 4);
-//   * 4-wave workgroups, two per CU (64->128 stage): a partial last round costs at least 0.6 of a round (1.125 and 2.25
-//     rounds measured as bad as 2 and 3), 3 row steps of prologue (224: 2 bands; 600: 5).
-static double rn_backfill_cost(long wgs, long slots, int rows, int wgs_per_cu) {
-    const double r = std::max(1.0, static_cast<double>(wgs) / static_cast<double>(slots));
-    if (wgs_per_cu >= 4) return (r + 0.12) * (rows + 1.5);
-    const double whole = std::floor(r), frac = r - whole;
-    return (whole + (frac > 1e-9 ? std::max(frac, 0.6) : 0.0)) * (rows + 3.0);
-}
-
-#ifdef RN_CLOCK
-// diagnostic build: every launch of a forward pass gets its own region of one host-visible buffer for the per-workgroup
-// (delta s_memtime, delta s_memrealtime) pairs; nothing is synchronised or printed unless RN_CLOCK_REPORT is set in the
-// environment WHEN the pass is enqueued (tools/gpu_clock.sh sets it for the last pass of a multi-second run), so the
-// stamped pass runs back to back with the ones before it
-struct ClockRegion {
-    char what[32];
-    size_t off, nwg;
-};
-static unsigned long long* g_clock_buf = nullptr;
-static std::vector<ClockRegion> g_clock_regions;
-static size_t g_clock_used = 0;
-static unsigned long long* rn_clock_region(const char* what, size_t nwg) {
-    if (!g_clock_buf) (void)hipHostMalloc(reinterpret_cast<void**>(&g_clock_buf), 16u << 20, 0);
-    ClockRegion r{};
-    snprintf(r.what, sizeof r.what, "%s", what);
-    r.off = g_clock_used;
-    r.nwg = nwg;
-    g_clock_used += 2 * nwg;
-    g_clock_regions.push_back(r);
-    return g_clock_buf + r.off;
-}
-static void rn_clock_begin() {
-    g_clock_regions.clear();
-    g_clock_used = 0;
-}
-static void rn_clock_end(hipStream_t stream) {
-    if (!getenv("RN_CLOCK_REPORT")) return;
-    (void)hipStreamSynchronize(stream);
-    for (const ClockRegion& r : g_clock_regions) {
-        const unsigned long long* buf = g_clock_buf + r.off;
-        std::vector<double> ghz, us;
-        for (size_t k = 0; k < r.nwg; ++k)
-            if (buf[2 * k + 1]) {
-                ghz.push_back(static_cast<double>(buf[2 * k]) / static_cast<double>(buf[2 * k + 1]) * 0.1);
-                us.push_back(static_cast<double>(buf[2 * k + 1]) * 0.01);
-            }
-        if (ghz.empty()) continue;
-        std::sort(ghz.begin(), ghz.end());
-        std::sort(us.begin(), us.end());
-        fprintf(stderr, "[clock] %-12s in-kernel clock %.3f GHz (median of %zu workgroups; 10th / 90th percentile %.3f / %.3f), workgroup lifetime %.1f us median\n",
-                r.what, ghz[ghz.size() / 2], ghz.size(), ghz[ghz.size() / 10], ghz[ghz.size() * 9 / 10], us[us.size() / 2]);
-    }
-}
-#endif
-
 struct FusedStage {
     bool use_rw = false;         // register-weights kernel (rn_stage_rw.hip) covers this stage
     bool use_c16 = false;        // 16x16x32-tile kernel (rn_conv16.hip) runs this stage instead
@@ -515,15 +454,8 @@ using LaunchFn = int (*)(hipStream_t, const StageArgs&, dim3, dim3, size_t);
 
 template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int CTW>
 int launch_variant(hipStream_t s, const StageArgs& a, dim3 grid, dim3 block, size_t lds) {
-    auto kern = stage_mfma_kernel<DT, CIN, COUT, PK, PS, RES, CTW>;
-    static std::atomic<unsigned long long> attr_devices{0};     // per device, see launch_rw
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-        RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    constexpr auto kern = stage_mfma_kernel<DT, CIN, COUT, PK, PS, RES, CTW>;
+    if (int rc = rn_allow_big_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
     RN_CHECK_LAUNCH();
     return RN_OK;
@@ -1223,6 +1155,226 @@ int rn_fused_launch_rep(const rn_handle* h, int stage) {
     return fs->launch_rep[stage];
 }
 
+// ---- the launch steps of a forward pass: each builds its kernel's arguments, asks the band picker (rn_bands.h), launches and
+// returns a status.  rn_fused_forward below decides which one runs and records the events.
+namespace {
+
+int launch_stage0(const rn_handle* h, const FusedState* fs, const uint8_t* d_bgr, int n) {
+    const StagePlan& s = h->stages[0];
+    Stage0Args a0{};
+    a0.bgr = d_bgr;
+    a0.wfrag = fs->s0_wfrag;
+    a0.ptab = fs->s0_ptab;
+    a0.out = static_cast<unsigned short*>(h->nodes[s.node_bn].ptr);
+    a0.S = s.in_side;
+    a0.So = s.out_side;
+    const int tiles = (s.out_side + S0_TSTRIDE - 1) / S0_TSTRIDE;
+    a0.npt = tiles >= 8 ? 8 : tiles;
+    a0.n_colblocks = (tiles + a0.npt - 1) / a0.npt;
+    const Bands b = rn_bands_stage0(n, s.out_side, a0.n_colblocks);
+    a0.rows_per_band = b.rows_per_band;
+    a0.n_bands = b.n_bands;
+    dim3 grid(a0.n_bands * a0.n_colblocks, n);
+    if (h->dtype == RN_DTYPE_BF16)
+        hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_BF16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
+    else
+        hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_F16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
+// stage 6 .. head in one launch
+int launch_backend(rn_handle* h, const FusedState* fs, int n, float* d_probs, int64_t* d_ids) {
+    const size_t ns = h->stages.size();
+    HeadArgs head;
+    rn_fill_head_args(h, &head);
+    const bool k48_6 = fs->s6_cstart && static_cast<int>(ns) - 4 == fs->fold5_stage + 1;
+    return rn_backend_launch(h, k48_6 ? fs->s6_wfrag48 : fs->st[ns - 4].wfrag16, fs->st[ns - 4].ptab, k48_6 ? fs->s6_cstart : nullptr,
+                             fs->st[ns - 3].wfrag16, fs->st[ns - 3].ptab, fs->st[ns - 2].wfrag, fs->st[ns - 1].wfrag, head, n, d_probs, d_ids);
+}
+
+// the last two stages (i, i + 1), the flatten, the dense head, softmax and argmax in one launch
+int launch_tail(rn_handle* h, const FusedState* fs, size_t i, int n, float* d_probs, int64_t* d_ids) {
+    HeadArgs head;
+    rn_fill_head_args(h, &head);
+    return rn_tail_launch(h, fs->st[i].wfrag, fs->st[i + 1].wfrag, head, n, d_probs, d_ids);
+}
+
+// both stages of the pair (i, i + 1) in one launch
+int launch_pair(const rn_handle* h, const FusedState* fs, size_t i, int n) {
+    const StagePlan &prev = h->stages[i - 1], &s = h->stages[i], &s2 = h->stages[i + 1];
+    Stage23Args fa{};
+    fa.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
+    fa.out = static_cast<unsigned short*>(h->nodes[s2.node_bn2].ptr);
+    fa.wfrag2 = fs->pair_x16 ? fs->pair_wfrag_a : fs->st[i].wfrag;
+    fa.wfrag3 = fs->pair_x16 ? fs->pair_wfrag_b : fs->st[i + 1].wfrag;
+    fa.ptab = fs->pair_x16 ? fs->pair_ptab_x : fs->pair_ptab;
+    fa.producer_halves = fs->pair_x16 ? fs->pair_producer_halves : 2;
+    fa.dither = fs->dither_out[i + 1];
+    fa.narrow_b = fa.producer_halves == 1 ? fs->pair_narrow : 0;
+    fa.rlo = s2.rt.lo;
+    fa.rhi = s2.rt.hi;
+    fa.rlerp = s2.rt.lerp;
+    fa.rscale = static_cast<float>(s2.skip_side) / static_cast<float>(s2.out_side);
+    fa.W = s.in_side;
+    fa.Wo = s2.out_side;
+    if (!rn_stage23_plan(s.in_side, &fa.n_cblocks, fa.cb_x0, fa.cb_wo)) {
+        rn_set_error("fused stage pair: no column-block plan for input side %d", s.in_side);
+        return RN_E_STATE;
+    }
+    const Bands b = rn_bands_pair(n, h->n_cu, s2.out_side, fa.n_cblocks);
+    fa.rows_per_band = b.rows_per_band;
+    fa.n_bands = b.n_bands;
+    if (fs->pair_x16) fa.stamp_buf = rn_clock_region("stages 2+3", static_cast<size_t>(fa.n_bands) * fa.n_cblocks * n);
+#ifdef RN_ROUND2_ARMS
+    return fs->pair_x16 ? rn_stage23x_launch(h->dtype, h->stream, fa, n) : rn_stage23_launch(h->dtype, h->stream, fa, n);
+#else
+    // (the round-2 pair kernel, rn_stage23.hip, is part of the test / A-B library only: rn_create refuses RN_FLAG_PAIR_32X32 here)
+    return rn_stage23x_launch(h->dtype, h->stream, fa, n);
+#endif
+}
+
+// what every kernel of a single stage i >= 1 is told: input and output tensor, BN, skip and resize tables, rounding
+int fill_stage_args(const rn_handle* h, const FusedState* fs, size_t i, StageArgs* out) {
+    const StagePlan &prev = h->stages[i - 1], &s = h->stages[i];
+    StageArgs& a = *out;
+    a.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
+    a.out = static_cast<unsigned short*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr);
+    a.wfrag = fs->st[i].wfrag;
+    a.bn_mean = s.bn.mean;
+    a.bn_inv = s.bn.inv;
+    a.bn_beta = s.bn.beta;
+    if (s.skip_stage >= 0) {
+        const StagePlan& sk = h->stages[s.skip_stage];
+        // the skip source is the first BN output of the block (network.py:195-196)
+        if (sk.node_bn2 >= 0) {
+            rn_set_error("16-bit path: skip source with its own residual is not supported");
+            return RN_E_INVALID;
+        }
+        a.skip = static_cast<const unsigned short*>(h->nodes[sk.node_bn].ptr);
+        a.bn2_mean = s.bn2.mean;
+        a.bn2_inv = s.bn2.inv;
+        a.bn2_beta = s.bn2.beta;
+        a.rlo = s.rt.lo;
+        a.rhi = s.rt.hi;
+        a.rlerp = s.rt.lerp;
+        a.Ss = s.skip_side;
+        a.rscale = static_cast<float>(s.skip_side) / static_cast<float>(s.out_side);
+    }
+    a.H = a.W = s.in_side;
+    a.Ho = a.Wo = s.out_side;
+    a.dither = fs->dither_out[i];
+    a.plain_q = -1;
+    // (both arms: the constant channels sit in the last quarter of the two relabelled tensors and keep the plain rounding)
+    if (fs->const_layout && (static_cast<int>(i) == fs->relabel_stage || static_cast<int>(i) + 1 == fs->relabel_stage)) a.plain_q = 3;
+    return RN_OK;
+}
+
+// rn_conv16 (the un-pooled 64 -> 128 stage) and, `pooled`, rn_conv16p (128 -> 16 with avg-pool 4/2)
+int launch_conv16(const rn_handle* h, const FusedState* fs, size_t i, const StageArgs& a, int n, bool pooled) {
+    const StagePlan& s = h->stages[i];
+    Conv16Args ca{};
+    ca.in = a.in;
+    ca.out = a.out;
+    ca.wfrag = fs->st[i].wfrag16;
+    ca.ptab = fs->st[i].ptab;
+    ca.H = ca.W = s.in_side;
+    ca.Ho = ca.Wo = s.out_side;
+    ca.n_colblocks = pooled ? rn_conv16p_colblocks(s.out_side) : rn_conv16_colblocks(s.out_side);
+    const Bands b = rn_bands_conv16(n, h->n_cu, s.out_side, ca.n_colblocks, pooled ? rn_conv16p_wgs_per_cu(s.out_side) : 2, pooled);
+    ca.rows_per_band = b.rows_per_band;
+    ca.n_bands = b.n_bands;
+    return pooled ? rn_conv16p_launch(h->dtype, h->stream, ca, n) : rn_conv16_launch(h->dtype, h->stream, ca, n);
+}
+
+// the row-register kernels: rn_stage4x (32 -> 64), rn_stage5x (64 -> 64 residual), rn_stage6x (64 -> 128)
+int launch_rowreg(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, int n) {
+    const StagePlan& s = h->stages[i];
+    const FusedStage& f = fs->st[i];
+    a.wfrag = f.wfrag16;
+    a.ptab = f.ptab;
+    const bool planned = f.use_s5x   ? rn_stage5x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
+                         : f.use_s4x ? rn_stage4x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
+                                     : rn_stage6x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo);
+    if (!planned) {
+        rn_set_error("stage %zu: no column-block plan for output side %d", i, s.out_side);
+        return RN_E_STATE;
+    }
+    const Bands b = rn_bands_rowreg(n, h->n_cu, s.out_side, a.n_cb, s.pool_k != 0);
+    a.rows_per_band = b.rows_per_band;
+    a.n_bands = b.n_bands;
+    char what[32];
+    snprintf(what, sizeof what, "stage %d", static_cast<int>(i));
+    a.stamp_buf = rn_clock_region(what, static_cast<size_t>(a.n_bands) * a.n_cb * n);
+    a.live_q = (f.use_s5x && static_cast<int>(i) == fs->fold5_stage) ? fs->fold5_live_q : 4;
+    if (fs->const4 && f.use_s4x && static_cast<int>(i) + 1 == fs->fold5_stage) {      // its last cout quarter is constant
+        a.live_q = 3;
+        a.cvals = fs->const_vals_dev;
+    }
+    if (fs->s6_cstart && f.use_s6x && static_cast<int>(i) == fs->fold5_stage + 1) {
+        a.wfrag = fs->s6_wfrag48;
+        a.cstart = fs->s6_cstart;
+    }
+    if (fs->const4 && f.use_s5x && static_cast<int>(i) == fs->fold5_stage) {
+        a.wfrag = fs->s5_wfrag48;
+        a.cstart = fs->s5_cstart;
+        a.cvals = fs->const_vals_dev + 16;
+    }
+    return f.use_s5x   ? rn_stage5x_launch(h->dtype, h->stream, a, n)
+           : f.use_s4x ? rn_stage4x_launch(h->dtype, h->stream, a, n)
+                       : rn_stage6x_launch(h->dtype, h->stream, a, n);
+}
+
+// the register-weights kernels (rn_stage_rw.hip); stage 1 computes stage 0 too when the handle fuses them
+int launch_regweights(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, const uint8_t* d_bgr, int n) {
+    const StagePlan& s = h->stages[i];
+    const FusedStage& f = fs->st[i];
+    // `sixth` weights (/ 6, BN scale x 6) are only right for kernels that clamp to [0, 1]: the pool 4/1 variants of the
+    // register-weights kernel and rn_stage4x / 5x (launch_rowreg).  Its stride-2 (DPP) variants clamp at 6.
+    if (f.sixth && !(s.pool_k == 4 && s.pool_s == 1)) {
+        rn_set_error("16-bit path: stage %zu has weights / 6 but would run a kernel that applies ReLU6 at 6", i);
+        return RN_E_STATE;
+    }
+    if (i == 1 && fs->fuse_s0) {
+        a.s0_bgr = d_bgr;
+        a.s0_wfrag = fs->s0_wfrag;
+        a.s0_ptab = fs->s0_ptab;
+        a.s0_S = h->stages[0].in_side;
+        a.s0_private = (h->flags & RN_FLAG_PAIR_32X32) ? 1 : 0;
+    }
+    a.ptab = f.ptab;
+    a.skipcols = f.rw.skipcols;
+    a.n_colblocks = f.rw.n_colblocks;
+    // the shared-ring form of the fused stages 0 + 1 cuts rows into 227-column blocks (eight 29-column tiles minus the
+    // 5 halo columns of the last one)
+    if (a.s0_bgr && !a.s0_private && f.rw.variant == 0 && f.rw.npt == 8) a.n_colblocks = rn_rw_s0sh_colblocks(s.out_side);
+    a.npt = f.rw.npt;
+    a.n_ctg = 1;
+    const Bands b = rn_bands_rw(n, h->n_cu, s.out_side, a.n_colblocks, f.rw.wgs_per_cu, s.pool_k, s.pool_s);
+    a.rows_per_band = b.rows_per_band;
+    a.n_bands = b.n_bands;
+    dim3 grid(a.n_bands * a.n_colblocks, n);
+    char what[32];
+    snprintf(what, sizeof what, a.s0_bgr ? "stages 0+%zu" : "stage %zu", i);
+    a.stamp_buf = rn_clock_region(what, static_cast<size_t>(grid.x) * grid.y);
+    return rn_rw_launch(f.rw, h->dtype, h->stream, a, grid);
+}
+
+int launch_generic(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, int n) {
+    const StagePlan& s = h->stages[i];
+    const FusedStage& f = fs->st[i];
+    a.n_colblocks = f.n_colblocks;
+    a.n_ctg = ((s.cout + 31) / 32) / f.ctw;
+    a.npt = f.npt;
+    const Bands b = rn_bands_generic(n, s.out_side, a.n_colblocks * a.n_ctg);
+    a.rows_per_band = b.rows_per_band;
+    a.n_bands = b.n_bands;
+    dim3 grid(a.n_bands * a.n_colblocks * a.n_ctg, n);
+    return kVariants[f.variant].fn[h->dtype == RN_DTYPE_BF16 ? 0 : 1](h->stream, a, grid, dim3(64 * f.npt), f.lds_bytes);
+}
+
+}  // namespace
+
 int rn_fused_forward(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int n, float* d_probs,
                      int64_t* d_ids) {
     if (!d_bgr || d_rgb) {
@@ -1234,497 +1386,72 @@ int rn_fused_forward(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int
         rn_set_error("fused plan missing");
         return RN_E_STATE;
     }
-    const int dti = h->dtype == RN_DTYPE_BF16 ? 0 : 1;
-#ifdef RN_CLOCK
+    // The events are the rn_timing / rn_stage_launch contract: slot 2 + i closes stage i, slot 2 + ns the head.  A fused launch
+    // is reported under its last stage: the events of the stages in front of it are recorded before the launch and read ~0.
+    const size_t ns = h->stages.size();
+    auto event = [&](size_t stage) { rn_record_event(h, 2 + static_cast<int>(stage)); };
+    int rc;
     rn_clock_begin();
-#endif
     // stage 0 (a launch of its own unless stage 1's kernel computes it)
-    if (fs->fuse_s0) {
-        rn_record_event(h, 2);
-    } else {
-        const StagePlan& s = h->stages[0];
-        Stage0Args a0{};
-        a0.bgr = d_bgr;
-        a0.wfrag = fs->s0_wfrag;
-        a0.ptab = fs->s0_ptab;
-        a0.out = static_cast<unsigned short*>(h->nodes[s.node_bn].ptr);
-        a0.S = s.in_side;
-        a0.So = s.out_side;
-        const int tiles = (s.out_side + S0_TSTRIDE - 1) / S0_TSTRIDE;
-        a0.npt = tiles >= 8 ? 8 : tiles;
-        a0.n_colblocks = (tiles + a0.npt - 1) / a0.npt;
-        // ~4 workgroups of 8 waves per CU across the launch, at least 8 output rows per band
-        const int per_band = n * a0.n_colblocks;
-        int bands = (1024 + per_band - 1) / per_band;
-        const int max_bands = (s.out_side + 7) / 8;
-        if (bands > max_bands) bands = max_bands;
-        if (bands < 1) bands = 1;
-        a0.rows_per_band = (s.out_side + bands - 1) / bands;
-        a0.n_bands = (s.out_side + a0.rows_per_band - 1) / a0.rows_per_band;
-        dim3 grid(a0.n_bands * a0.n_colblocks, n);
-        if (dti == 0)
-            hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_BF16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
-        else
-            hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_F16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
-        RN_CHECK_LAUNCH();
-        rn_record_event(h, 2);
-    }
-    for (size_t i = 1; i < h->stages.size(); ++i) {
-        const StagePlan& s = h->stages[i];
+    if (!fs->fuse_s0 && (rc = launch_stage0(h, fs, d_bgr, n)) != RN_OK) return rc;
+    event(0);
+    bool head_done = false;
+    for (size_t i = 1; i < ns && !head_done; ++i) {
         const FusedStage& f = fs->st[i];
-        const StagePlan& prev = h->stages[i - 1];
-        if (fs->use_backend && !h->split_backend && i + 4 == h->stages.size() && 2 * n >= h->n_cu) {
-            // stage 6 .. head in one launch: reported under the last stage
-            const size_t ns = h->stages.size();
-            for (size_t k = i; k + 1 < ns; ++k) rn_record_event(h, 2 + static_cast<int>(k));
-            HeadArgs head;
-            rn_fill_head_args(h, &head);
-            const bool k48_6 = fs->s6_cstart && static_cast<int>(ns) - 4 == fs->fold5_stage + 1;
-            int rc = rn_backend_launch(h, k48_6 ? fs->s6_wfrag48 : fs->st[ns - 4].wfrag16, fs->st[ns - 4].ptab, k48_6 ? fs->s6_cstart : nullptr,
-                                       fs->st[ns - 3].wfrag16, fs->st[ns - 3].ptab, fs->st[ns - 2].wfrag, fs->st[ns - 1].wfrag, head, n, d_probs, d_ids);
-            if (rc != RN_OK) return rc;
+        if (fs->use_backend && !h->split_backend && i + 4 == ns && 2 * n >= h->n_cu) {
+            for (size_t k = i; k + 1 < ns; ++k) event(k);
+            if ((rc = launch_backend(h, fs, n, d_probs, d_ids)) != RN_OK) return rc;
             fs->last_backend = true;         // (only now: a failed launch must not report s6.bn / s7.bn as elided)
-            rn_record_event(h, 2 + static_cast<int>(ns - 1));
-            rn_record_event(h, 2 + static_cast<int>(ns));
-#ifdef RN_CLOCK
-            rn_clock_end(h->stream);
-#endif
-            return RN_OK;
+            event(ns - 1);
+            head_done = true;
+            continue;
         }
         fs->last_backend = false;
-        if (fs->use_tail && i + 2 == h->stages.size()) {
-            // the last two stages, the flatten, the dense head, softmax and argmax in one launch: reported under the last
-            // stage, the head's own slot reads ~0
-            rn_record_event(h, 2 + static_cast<int>(i));
-            HeadArgs head;
-            rn_fill_head_args(h, &head);
-            int rc = rn_tail_launch(h, fs->st[i].wfrag, fs->st[i + 1].wfrag, head, n, d_probs, d_ids);
-            if (rc != RN_OK) return rc;
-            rn_record_event(h, 2 + static_cast<int>(i) + 1);
-            rn_record_event(h, 2 + static_cast<int>(h->stages.size()));
-#ifdef RN_CLOCK
-            rn_clock_end(h->stream);
-#endif
-            return RN_OK;
+        if (fs->use_tail && i + 2 == ns) {
+            event(i);
+            if ((rc = launch_tail(h, fs, i, n, d_probs, d_ids)) != RN_OK) return rc;
+            event(i + 1);
+            head_done = true;
+            continue;
         }
         if (static_cast<int>(i) == fs->pair_first) {
-            // both stages of the pair in one launch; the event of the first stage is recorded in front of it, so
-            // rn_timing reports the whole launch under the second stage
-            rn_record_event(h, 2 + static_cast<int>(i));
-            const StagePlan& s2 = h->stages[i + 1];
-            Stage23Args fa{};
-            fa.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
-            fa.out = static_cast<unsigned short*>(h->nodes[s2.node_bn2].ptr);
-            fa.wfrag2 = fs->pair_x16 ? fs->pair_wfrag_a : f.wfrag;
-            fa.wfrag3 = fs->pair_x16 ? fs->pair_wfrag_b : fs->st[i + 1].wfrag;
-            fa.ptab = fs->pair_x16 ? fs->pair_ptab_x : fs->pair_ptab;
-            fa.producer_halves = fs->pair_x16 ? fs->pair_producer_halves : 2;
-            fa.dither = fs->dither_out[i + 1];
-            fa.narrow_b = fa.producer_halves == 1 ? fs->pair_narrow : 0;
-            fa.rlo = s2.rt.lo;
-            fa.rhi = s2.rt.hi;
-            fa.rlerp = s2.rt.lerp;
-            fa.rscale = static_cast<float>(s2.skip_side) / static_cast<float>(s2.out_side);
-            fa.W = s.in_side;
-            fa.Wo = s2.out_side;
-            if (!rn_stage23_plan(s.in_side, &fa.n_cblocks, fa.cb_x0, fa.cb_wo)) {
-                rn_set_error("fused stage pair: no column-block plan for input side %d", s.in_side);
-                return RN_E_STATE;
-            }
-            // one workgroup per CU: workgroup = image x column block x band of rows; bands only to fill the chip / even
-            // out the rounds (a band costs its rows plus 11 steps of pipeline fill)
-            const int n_cu = h->n_cu;
-            const long per_band = static_cast<long>(n) * fa.n_cblocks;
-            int bands = 1;
-            long best_cost = -1;
-            const int max_bands = (s2.out_side + 7) / 8;
-            for (int b = 1; b <= 8 && b <= max_bands; ++b) {
-                const long rounds = (per_band * b + n_cu - 1) / n_cu;
-                const long cost = rounds * ((s2.out_side + b - 1) / b + 11);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    bands = b;
-                }
-            }
-            if (per_band * bands < n_cu) {
-                bands = static_cast<int>((n_cu + per_band - 1) / per_band);
-                if (bands > max_bands) bands = max_bands;
-            }
-            fa.rows_per_band = (s2.out_side + bands - 1) / bands;
-            fa.n_bands = (s2.out_side + fa.rows_per_band - 1) / fa.rows_per_band;
-#ifdef RN_STAMPS
-            static unsigned long long* stamp_host23 = nullptr;
-            const size_t nwaves23 = static_cast<size_t>(fa.n_bands) * fa.n_cblocks * n * 8;
-            if (!stamp_host23) (void)hipHostMalloc(reinterpret_cast<void**>(&stamp_host23), 16u << 20, 0);
-            std::memset(stamp_host23, 0, nwaves23 * 96);
-            fa.stamp_buf = stamp_host23;
-#endif
-#ifdef RN_CLOCK
-            if (fs->pair_x16) fa.stamp_buf = rn_clock_region("stages 2+3", static_cast<size_t>(fa.n_bands) * fa.n_cblocks * n);
-#endif
-#ifdef RN_ROUND2_ARMS
-            int rc = fs->pair_x16 ? rn_stage23x_launch(h->dtype, h->stream, fa, n) : rn_stage23_launch(h->dtype, h->stream, fa, n);
-#else
-            // (the round-2 pair kernel, rn_stage23.hip, is part of the test / A-B library only: rn_create refuses RN_FLAG_PAIR_32X32 here)
-            int rc = rn_stage23x_launch(h->dtype, h->stream, fa, n);
-#endif
-            if (rc != RN_OK) return rc;
-#ifdef RN_STAMPS
-            (void)hipStreamSynchronize(h->stream);
-            {
-                double wtot[8] = {0}, wbar[8] = {0}, wsteps[8] = {0};
-                for (size_t k = 0; k < nwaves23; ++k) {
-                    wtot[k & 7] += stamp_host23[k * 4];
-                    wbar[k & 7] += stamp_host23[k * 4 + 2];
-                    wsteps[k & 7] += stamp_host23[k * 4 + 3];
-                }
-                {
-                    double seg[2][6] = {{0}, {0}};
-                    double st[2] = {0, 0};
-                    const unsigned long long* base = stamp_host23 + nwaves23 * 4;
-                    for (size_t k = 0; k < nwaves23; ++k) {
-                        const int role = (k & 7) < 4 ? 0 : 1;
-                        st[role] += stamp_host23[k * 4 + 3];
-                        for (int j = 0; j < 6; ++j) seg[role][j] += base[k * 8 + j];
-                    }
-                    fprintf(stderr, "[stamps]   producer segments (chain0 epi0 chain1 epi1): %.0f %.0f %.0f %.0f\n", seg[0][0] / st[0], seg[0][1] / st[0],
-                            seg[0][2] / st[0], seg[0][3] / st[0]);
-                    fprintf(stderr, "[stamps]   consumer segments (bookkeeping+own-fetch chain0 skip-wait epi0 chain1+epi1): %.0f %.0f %.0f %.0f %.0f\n", seg[1][0] / st[1],
-                            seg[1][2] / st[1], seg[1][3] / st[1], seg[1][4] / st[1], seg[1][5] / st[1]);
-                }
-                for (int w8 = 0; w8 < 8; ++w8)
-                    if (wsteps[w8] > 0)
-                        fprintf(stderr, "[stamps] fused stages %zu+%zu wave %d (%s): cycles/step %.0f, of which barrier wait %.0f\n", i, i + 1, w8,
-                                w8 < 4 ? "producer" : "consumer", wtot[w8] / wsteps[w8], wbar[w8] / wsteps[w8]);
-            }
-#endif
-            rn_record_event(h, 2 + static_cast<int>(i) + 1);
-            ++i;
+            event(i);
+            if ((rc = launch_pair(h, fs, i, n)) != RN_OK) return rc;
+            event(++i);
             continue;
         }
         StageArgs a{};
-        a.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
-        a.out = static_cast<unsigned short*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr);
-        a.wfrag = f.wfrag;
-        a.bn_mean = s.bn.mean;
-        a.bn_inv = s.bn.inv;
-        a.bn_beta = s.bn.beta;
-        if (s.skip_stage >= 0) {
-            const StagePlan& sk = h->stages[s.skip_stage];
-            // the skip source is the first BN output of the block (network.py:195-196)
-            if (sk.node_bn2 >= 0) {
-                rn_set_error("16-bit path: skip source with its own residual is not supported");
-                return RN_E_INVALID;
-            }
-            a.skip = static_cast<const unsigned short*>(h->nodes[sk.node_bn].ptr);
-            a.bn2_mean = s.bn2.mean;
-            a.bn2_inv = s.bn2.inv;
-            a.bn2_beta = s.bn2.beta;
-            a.rlo = s.rt.lo;
-            a.rhi = s.rt.hi;
-            a.rlerp = s.rt.lerp;
-            a.Ss = s.skip_side;
-            a.rscale = static_cast<float>(s.skip_side) / static_cast<float>(s.out_side);
-        }
-        a.H = a.W = s.in_side;
-        a.Ho = a.Wo = s.out_side;
-        a.dither = fs->dither_out[i];
-        a.plain_q = -1;
-        // (both arms: the constant channels sit in the last quarter of the two relabelled tensors and keep the plain rounding)
-        if (fs->const_layout && (static_cast<int>(i) == fs->relabel_stage || static_cast<int>(i) + 1 == fs->relabel_stage)) a.plain_q = 3;
-        if (f.use_c16) {
-            Conv16Args ca{};
-            ca.in = a.in;
-            ca.out = a.out;
-            ca.wfrag = f.wfrag16;
-            ca.ptab = f.ptab;
-            ca.H = ca.W = s.in_side;
-            ca.Ho = ca.Wo = s.out_side;
-            ca.n_colblocks = rn_conv16_colblocks(s.out_side);
-            // 4-wave workgroups, two per CU; back-filled, so the cost of a band count is the fractional number of rounds
-            const long per_band = static_cast<long>(n) * ca.n_colblocks;
-            const long slots = 2L * h->n_cu;
-            const int max_bands = (s.out_side + 3) / 4;
-            int bands = 1;
-            double best_cost = -1;
-            for (int b = 1; b <= 8 && b <= max_bands; ++b) {
-                if (per_band * b < slots && b < max_bands) continue;          // fill the chip first
-                const double cost = rn_backfill_cost(per_band * b, slots, (s.out_side + b - 1) / b, 2);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    bands = b;
-                }
-            }
-            if (per_band * bands < slots) {
-                bands = static_cast<int>((slots + per_band - 1) / per_band);
-                if (bands > max_bands) bands = max_bands;
-            }
-            ca.rows_per_band = (s.out_side + bands - 1) / bands;
-            ca.n_bands = (s.out_side + ca.rows_per_band - 1) / ca.rows_per_band;
-            int rc = rn_conv16_launch(h->dtype, h->stream, ca, n);
-            if (rc != RN_OK) return rc;
-            rn_record_event(h, 2 + static_cast<int>(i));
-            continue;
-        }
-        if (f.use_s5x || f.use_s4x || f.use_s6x) {
-            a.wfrag = f.wfrag16;
-            a.ptab = f.ptab;
-            const bool planned = f.use_s5x   ? rn_stage5x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
-                                 : f.use_s4x ? rn_stage4x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
-                                             : rn_stage6x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo);
-            if (!planned) {
-                rn_set_error("stage %zu: no column-block plan for output side %d", i, s.out_side);
-                return RN_E_STATE;
-            }
-            // one workgroup (8 waves) per CU, workgroup = image x column block x band of rows: whole rounds of the chip.  A
-            // band costs its input rows plus the rows its neighbour reads again (6 of the pooled stages, 2 of the un-pooled
-            // one); small batches take as many bands as it needs to fill the chip.
-            const long per_band = static_cast<long>(n) * a.n_cb;
-            const int rows_in = s.pool_k ? 2 : 1, overlap = s.pool_k ? 6 : 2;
-            const int max_bands = std::max(1, s.out_side / 4);
-            int bands = 1;
-            long best_cost = -1;
-            for (int b = 1; b <= 8 && b <= max_bands; ++b) {
-                const long rounds = (per_band * b + h->n_cu - 1) / h->n_cu;
-                const long cost = rounds * (rows_in * ((s.out_side + b - 1) / b) + overlap);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    bands = b;
-                }
-            }
-            if (per_band * bands < h->n_cu) bands = static_cast<int>(std::min<long>((h->n_cu + per_band - 1) / per_band, max_bands));
-            a.rows_per_band = (s.out_side + bands - 1) / bands;
-            a.n_bands = (s.out_side + a.rows_per_band - 1) / a.rows_per_band;
-#ifdef RN_CLOCK
-            {
-                char what[32];
-                snprintf(what, sizeof what, "stage %d", static_cast<int>(i));
-                a.stamp_buf = rn_clock_region(what, static_cast<size_t>(a.n_bands) * a.n_cb * n);
-            }
-#endif
-            a.live_q = (f.use_s5x && static_cast<int>(i) == fs->fold5_stage) ? fs->fold5_live_q : 4;
-            if (fs->const4 && f.use_s4x && static_cast<int>(i) + 1 == fs->fold5_stage) {      // its last cout quarter is constant
-                a.live_q = 3;
-                a.cvals = fs->const_vals_dev;
-            }
-            if (fs->s6_cstart && f.use_s6x && static_cast<int>(i) == fs->fold5_stage + 1) {
-                a.wfrag = fs->s6_wfrag48;
-                a.cstart = fs->s6_cstart;
-            }
-            if (fs->const4 && f.use_s5x && static_cast<int>(i) == fs->fold5_stage) {
-                a.wfrag = fs->s5_wfrag48;
-                a.cstart = fs->s5_cstart;
-                a.cvals = fs->const_vals_dev + 16;
-            }
-            int rc = f.use_s5x   ? rn_stage5x_launch(h->dtype, h->stream, a, n)
-                     : f.use_s4x ? rn_stage4x_launch(h->dtype, h->stream, a, n)
-                                 : rn_stage6x_launch(h->dtype, h->stream, a, n);
-            if (rc != RN_OK) return rc;
-            rn_record_event(h, 2 + static_cast<int>(i));
-            continue;
-        }
-        if (f.use_c16p) {
-            Conv16Args ca{};
-            ca.in = a.in;
-            ca.out = a.out;
-            ca.wfrag = f.wfrag16;
-            ca.ptab = f.ptab;
-            ca.H = ca.W = s.in_side;
-            ca.Ho = ca.Wo = s.out_side;
-            ca.n_colblocks = rn_conv16p_colblocks(s.out_side);
-            const long per_band = static_cast<long>(n) * ca.n_colblocks;
-            const int per_cu = rn_conv16p_wgs_per_cu(s.out_side);    // 3-wave workgroups (72 KB of LDS): two per CU; 5-wave ones (123 KB): one
-            const long slots = static_cast<long>(per_cu) * h->n_cu;
-            const int max_bands = (s.out_side + 3) / 4;
-            int bands = 1;
-            double best_cost = -1;
-            for (int b = 1; b <= 8 && b <= max_bands; ++b) {
-                if (per_band * b < slots && b < max_bands) continue;          // fill the chip first
-                const double cost = rn_backfill_cost(per_band * b, slots, 2 * ((s.out_side + b - 1) / b) + 2, per_cu);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    bands = b;
-                }
-            }
-            if (per_band * bands < slots) {
-                bands = static_cast<int>((slots + per_band - 1) / per_band);
-                if (bands > max_bands) bands = max_bands;
-            }
-            ca.rows_per_band = (s.out_side + bands - 1) / bands;
-            ca.n_bands = (s.out_side + ca.rows_per_band - 1) / ca.rows_per_band;
-            int rc = rn_conv16p_launch(h->dtype, h->stream, ca, n);
-            if (rc != RN_OK) return rc;
-            rn_record_event(h, 2 + static_cast<int>(i));
-            continue;
-        }
-        if (f.use_rw) {
-            // `sixth` weights (/ 6, BN scale x 6) are only right for kernels that clamp to [0, 1]: the pool 4/1 variants of the
-            // register-weights kernel and rn_stage4x / 5x (handled above).  Its stride-2 (DPP) variants clamp at 6.
-            if (f.sixth && !(s.pool_k == 4 && s.pool_s == 1)) {
-                rn_set_error("16-bit path: stage %zu has weights / 6 but would run a kernel that applies ReLU6 at 6", i);
-                return RN_E_STATE;
-            }
-#ifdef RN_DIAG
-            if (const char* dbg = getenv("RN_DEBUG_FLAGS")) a.dbg_flags = atoi(dbg);   // diagnostic builds only
-#endif
-            if (i == 1 && fs->fuse_s0) {
-                a.s0_bgr = d_bgr;
-                a.s0_wfrag = fs->s0_wfrag;
-                a.s0_ptab = fs->s0_ptab;
-                a.s0_S = h->stages[0].in_side;
-                a.s0_private = (h->flags & RN_FLAG_PAIR_32X32) ? 1 : 0;
-            }
-            a.ptab = f.ptab;
-            a.skipcols = f.rw.skipcols;
-            a.n_colblocks = f.rw.n_colblocks;
-            // the shared-ring form of the fused stages 0 + 1 cuts rows into 227-column blocks (eight 29-column tiles minus the
-            // 5 halo columns of the last one)
-            if (a.s0_bgr && !a.s0_private && f.rw.variant == 0 && f.rw.npt == 8) a.n_colblocks = rn_rw_s0sh_colblocks(s.out_side);
-            a.npt = f.rw.npt;
-            a.n_ctg = 1;
-            // Workgroups per CU: one (8-wave variants; checked with HW_ID stamps) or four (the 2-wave workgroups of the
-            // 32->64 stage).  A band costs its rows plus ~10 rows of prologue / pool warm-up; pick the band count that
-            // gives the least time.  One workgroup per CU runs in whole rounds of the chip: 1 band at batch 256 x 224^2,
-            // 2 when e.g. 64 x 600^2 images x 6 column blocks = 384 workgroups would otherwise run 1.5 rounds.  Small
-            // workgroups are back-filled as slots free up, so their cost is the fractional number of rounds (>= 1).
-            const int per_band = n * a.n_colblocks;
-            const long slots = static_cast<long>(h->n_cu) * f.rw.wgs_per_cu;
-            const int max_bands = (s.out_side + 7) / 8;
-            int bands = 1;
-            double best_cost = -1;
-            for (int b = 1; b <= 8 && b <= max_bands; ++b) {
-                const long wgs = static_cast<long>(per_band) * b;
-                const long rows_b = (s.out_side + b - 1) / b * (s.pool_k ? s.pool_s : 1);     // conv rows of a band
-                const double cost = f.rw.wgs_per_cu == 1 ? static_cast<double>((wgs + slots - 1) / slots) * static_cast<double>(rows_b + 10)
-                                                         : rn_backfill_cost(wgs, slots, static_cast<int>(rows_b) + 2, f.rw.wgs_per_cu);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    bands = b;
-                }
-            }
-            if (static_cast<long>(per_band) * bands < slots) {      // small batches: fill the chip first
-                bands = static_cast<int>((slots + per_band - 1) / per_band);
-                if (bands > max_bands) bands = max_bands;
-            }
-            a.rows_per_band = (s.out_side + bands - 1) / bands;
-            if (s.pool_k == 0 && a.rows_per_band < 4) a.rows_per_band = 4;   // ring prologue depth
-            a.n_bands = (s.out_side + a.rows_per_band - 1) / a.rows_per_band;
-            dim3 grid(a.n_bands * a.n_colblocks, n);
-#ifdef RN_STAMPS
-            // diagnostic build: per-wave phase cycle sums, printed per stage after the launch
-            static unsigned long long* stamp_host = nullptr;
-            const size_t nwaves = static_cast<size_t>(grid.x) * grid.y * 16;
-            if (!stamp_host) (void)hipHostMalloc(reinterpret_cast<void**>(&stamp_host), 64u << 20, 0);
-            std::memset(stamp_host, 0, nwaves * 32);
-            a.stamp_buf = stamp_host;
-#endif
-#ifdef RN_CLOCK
-            {
-                char what[32];
-                snprintf(what, sizeof what, a.s0_bgr ? "stages 0+%zu" : "stage %zu", i);
-                a.stamp_buf = rn_clock_region(what, static_cast<size_t>(grid.x) * grid.y);
-            }
-#endif
-            int rc = rn_rw_launch(f.rw, h->dtype, h->stream, a, grid);
-            if (rc != RN_OK) return rc;
-#ifdef RN_STAMPS
-            (void)hipStreamSynchronize(h->stream);
-            {
-                double w = 0, d = 0, b = 0, rows = 0, ch = 0, life = 0, pro = 0;
-                size_t cnt = 0;
-                for (size_t k = 0; k < nwaves; ++k)
-                    if (stamp_host[k * 4 + 3]) {
-                        w += stamp_host[k * 4];
-                        d += static_cast<double>(stamp_host[k * 4 + 1] & 0xffffffffull);
-                        life += static_cast<double>(stamp_host[k * 4 + 1] >> 32);
-                        pro += static_cast<double>(stamp_host[k * 4 + 3] >> 32);
-                        b += static_cast<double>(stamp_host[k * 4 + 2] & 0xffffffffull);
-                        ch += static_cast<double>(stamp_host[k * 4 + 2] >> 32);
-                        rows += static_cast<double>(stamp_host[k * 4 + 3] & 0xffffffffull);
-                        ++cnt;
-                    }
-#ifdef RN_STAMP_HWID
-                {
-                    // how many workgroups of this launch were resident on one CU at the same time?
-                    struct Iv { unsigned long long t0, t1; unsigned cu; };
-                    std::vector<Iv> iv;
-                    for (size_t k = 0; k < nwaves; ++k)
-                        if (stamp_host[k * 4 + 3] & 0xffffffffull) {
-                            const unsigned hw = static_cast<unsigned>(stamp_host[k * 4 + 3] >> 32);
-                            const unsigned xcc = static_cast<unsigned>(stamp_host[k * 4 + 1]) & 0xf;
-                            // gfx9 HW_ID: wave[3:0] simd[5:4] pipe[7:6] cu[11:8] sh[12] se[15:13]
-                            const unsigned cu = ((hw >> 8) & 0xf) | (((hw >> 12) & 1) << 4) | (((hw >> 13) & 7) << 5) | (xcc << 8);
-                            iv.push_back({stamp_host[k * 4 + 0], stamp_host[k * 4 + 2], cu});
-                        }
-                    std::map<unsigned, std::vector<Iv>> per;
-                    for (auto& v : iv) per[v.cu].push_back(v);
-                    double avg_conc = 0; size_t ncu = 0; size_t maxc = 0;
-                    for (auto& kv : per) {
-                        // time-weighted mean number of resident waves on this CU
-                        std::vector<std::pair<unsigned long long, int>> ev;
-                        for (auto& v : kv.second) { ev.push_back({v.t0, 1}); ev.push_back({v.t1, -1}); }
-                        std::sort(ev.begin(), ev.end());
-                        double area = 0; int cur = 0; unsigned long long last = ev.front().first; size_t mx = 0;
-                        for (auto& e : ev) { area += static_cast<double>(e.first - last) * cur; last = e.first; cur += e.second; if (static_cast<size_t>(cur) > mx) mx = cur; }
-                        avg_conc += area / static_cast<double>(ev.back().first - ev.front().first);
-                        maxc = std::max(maxc, mx); ++ncu;
-                    }
-                    fprintf(stderr, "[hwid] stage %zu: %zu waves on %zu distinct CUs; resident waves per CU: mean %.2f, max %zu\n", i, iv.size(), ncu,
-                            avg_conc / ncu, maxc);
-                }
-#endif
-                if (cnt && getenv("RN_STAMPS_PER_WAVE")) {
-                    // per wave index inside the workgroup: who is the straggler the others wait for at the barrier?
-                    const size_t wpw = 16;      // stamp slots per workgroup (rn_stage_rw.hip writes NTHREADS / 64 of them)
-                    double ww[16] = {0}, bb[16] = {0}, rr[16] = {0};
-                    const size_t real = static_cast<size_t>(getenv("RN_STAMPS_WAVES") ? atoi(getenv("RN_STAMPS_WAVES")) : 8);
-                    for (size_t k = 0; k < nwaves; ++k)
-                        if (stamp_host[k * 4 + 3]) {
-                            const size_t wi = k % real;
-                            ww[wi] += stamp_host[k * 4];
-                            bb[wi] += static_cast<double>(stamp_host[k * 4 + 2] & 0xffffffffull);
-                            rr[wi] += static_cast<double>(stamp_host[k * 4 + 3] & 0xffffffffull);
-                        }
-                    (void)wpw;
-                    for (size_t wi = 0; wi < real; ++wi)
-                        if (rr[wi] > 0) fprintf(stderr, "[stamps]   stage %zu wave %zu: work %.0f barrier %.0f\n", i, wi, ww[wi] / rr[wi], bb[wi] / rr[wi]);
-                }
-                if (cnt)
-                    fprintf(stderr, "[stamps] stage %zu: waves %zu, cycles/step: work %.0f (MFMA chain alone %.0f)  dma-wait %.0f  barrier %.0f  (steps/wave %.0f)\n",
-                            i, cnt, w / rows, ch / rows, d / rows, b / rows, rows / cnt);
-                if (cnt)
-                    fprintf(stderr, "[stamps]   stage %zu: wave lifetime %.0f cycles, of which prologue %.0f, row loop %.0f\n", i, life / cnt,
-                            pro / cnt, (w + d + b) / cnt);
-            }
-#endif
-            rn_record_event(h, 2 + static_cast<int>(i));
-            continue;
-        }
-        const int n_ctg = ((s.cout + 31) / 32) / f.ctw;
-        // bands: aim for >= ~2 workgroups per CU across the launch, at least 4 output rows per band
-        const int per_band_wgs = n * f.n_colblocks * n_ctg;
-        int bands = (768 + per_band_wgs - 1) / per_band_wgs;
-        // tiny stages are pure latency chains (one wave per workgroup, a global-load round trip per row): give
-        // every output row its own workgroup instead of 4 rows each
-        const int max_bands = s.out_side <= 8 ? s.out_side : (s.out_side + 3) / 4;
-        if (bands > max_bands) bands = max_bands;
-        if (s.out_side <= 8) bands = max_bands;
-        if (bands < 1) bands = 1;
-        a.rows_per_band = (s.out_side + bands - 1) / bands;
-        a.n_bands = (s.out_side + a.rows_per_band - 1) / a.rows_per_band;
-        a.n_colblocks = f.n_colblocks;
-        a.n_ctg = n_ctg;
-        a.npt = f.npt;
-        dim3 grid(a.n_bands * a.n_colblocks * a.n_ctg, n);
-        int rc = kVariants[f.variant].fn[dti](h->stream, a, grid, dim3(64 * f.npt), f.lds_bytes);
+        if ((rc = fill_stage_args(h, fs, i, &a)) != RN_OK) return rc;
+        if (f.use_c16)
+            rc = launch_conv16(h, fs, i, a, n, false);
+        else if (f.use_s5x || f.use_s4x || f.use_s6x)
+            rc = launch_rowreg(h, fs, i, a, n);
+        else if (f.use_c16p)
+            rc = launch_conv16(h, fs, i, a, n, true);
+        else if (f.use_rw)
+            rc = launch_regweights(h, fs, i, a, d_bgr, n);
+        else
+            rc = launch_generic(h, fs, i, a, n);
         if (rc != RN_OK) return rc;
-        rn_record_event(h, 2 + static_cast<int>(i));
+        event(i);
     }
-    int rc = rn_run_head(h, n, d_probs, d_ids);
-    if (rc != RN_OK) return rc;
-    rn_record_event(h, 2 + static_cast<int>(h->stages.size()));
-#ifdef RN_CLOCK
+    if (!head_done && (rc = rn_run_head(h, n, d_probs, d_ids)) != RN_OK) return rc;
+    event(ns);
     rn_clock_end(h->stream);
-#endif
+    return RN_OK;
+}
+
+// the band picker of the launch steps above (and of rn_f32m_launch), exported for tests
+extern "C" int rn_band_plan(int family, int n, int n_cu, int out_side, int n_colblocks, int wgs_per_cu, int pool_k, int pool_s,
+                            int* rows_per_band, int* n_bands) {
+    Bands b;
+    if (n < 1 || n_cu < 1 || out_side < 1 || n_colblocks < 1 || wgs_per_cu < 1 || pool_k < 0 || pool_s < 1 || !rows_per_band || !n_bands ||
+        !rn_bands_family(family, n, n_cu, out_side, n_colblocks, wgs_per_cu, pool_k, pool_s, &b)) {
+        rn_set_error("rn_band_plan: bad argument (family %d, n %d, n_cu %d, out_side %d, n_colblocks %d, wgs_per_cu %d, pool %d/%d)", family, n, n_cu,
+                     out_side, n_colblocks, wgs_per_cu, pool_k, pool_s);
+        return RN_E_INVALID;
+    }
+    *rows_per_band = b.rows_per_band;
+    *n_bands = b.n_bands;
     return RN_OK;
 }

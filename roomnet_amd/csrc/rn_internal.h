@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libroomnet_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
@@ -38,6 +39,25 @@ void rn_set_error(const char* fmt, ...);
             return RN_E_HIP;                                                                  \
         }                                                                                     \
     } while (0)
+
+// Kernels with more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised before their first launch.
+// The attribute is per device: remember which devices of this process have it (one handle per GPU per process is the
+// normal deployment, several handles on several GPUs / threads in one process must work too).  Kern is a template argument
+// so that every kernel instantiation has a mask of its own.
+template <auto Kern>
+int rn_allow_big_lds() {
+    static std::atomic<unsigned long long> attr_devices{0};
+    int dev = 0;
+    RN_HIP(hipGetDevice(&dev));
+    if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
+        RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
+    }
+    return RN_OK;
+}
+// names a kernel instantiation as a value, for launch lambdas:  launch(rn_kernel<my_kernel<RN_DTYPE_BF16>>{})
+template <auto Kern>
+struct rn_kernel {};
 
 // per-channel affine form of an inference BN: y = (x - mean) * inv + beta
 struct BnDev {

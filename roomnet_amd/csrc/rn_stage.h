@@ -282,8 +282,8 @@ struct StageArgs {
     int rows_per_band, n_bands, n_colblocks, n_ctg, npt;
     const float* ptab;            // folded BN tables [4][COUT]: scale1, shift1, scale2, shift2 (rw kernels)
     int skipcols;                 // skip-row columns staged in LDS per workgroup (rw residual kernels)
-    int dbg_flags;                // timing experiments only: bit 0 = skip output stores, bit 1 = skip MFMAs
-    unsigned long long* stamp_buf; // diagnostic build (-DRN_STAMPS) only: per-wave phase cycle sums
+    int dbg_flags;                // unused (kept: removing a member moves the kernel-argument offsets of every stage kernel)
+    unsigned long long* stamp_buf; // diagnostic build (-DRN_CLOCK) only: per-workgroup clock pairs (rn_clock.h); else null
     float rscale;                 // residual resize scale = float(Ss) / float(Ho), fp32 as TF computes it
     // stage-0 fusion (8-channel rw variant only; s0_bgr == nullptr: the stage reads `in` as usual)
     const uint8_t* s0_bgr;        // [N, S, S, 3] uint8 image batch
@@ -349,7 +349,7 @@ struct Stage23Args {
     // columns cb_x0[b] .. cb_x0[b] + cb_wo[b] + 9 (whole rows when n_cblocks == 1: the 224 x 224 network)
     int n_cblocks;
     int cb_x0[4], cb_wo[4];
-    unsigned long long* stamp_buf; // diagnostic build (-DRN_STAMPS) only: per-wave cycle sums
+    unsigned long long* stamp_buf; // diagnostic build (-DRN_CLOCK) only: per-workgroup clock pairs (rn_clock.h); else null
     // rn_stage23x.hip only: 1 = the first stage computes the first half of every 8-cout group only (B-ring channels 8 j .. 8 j + 3);
     // the other 16 channels of B are FROZEN -- constants whatever the input (rn_fused_prepare proves it per channel for the
     // handle's dtype and orders the channels accordingly) -- and are written from the table, bit for bit what the full

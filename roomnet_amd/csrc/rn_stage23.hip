@@ -22,7 +22,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -38,7 +37,7 @@ using namespace rnk;
 namespace {
 
 constexpr int F_NA = 4, F_NB = 4, F_NSK = 3;     // ring depths: A rows, B rows, private skip rows
-constexpr int F_WMAX = 215, F_WMIN = 193;        // supported widths of A (the tail DMA piece needs W > 192)
+constexpr int F_WMAX = 215;                      // widest A supported (193 .. 215: the tail DMA piece needs W > 192)
 constexpr int F_ROWA = F_WMAX * 64;              // bytes per A ring row (32 channels x 16 bit per pixel)
 constexpr int F_BDUMMY = F_WMAX - 5;             // B ring column that invalid lanes write to (never read)
 constexpr int F_ROWB = (F_BDUMMY + 1) * 64;
@@ -61,16 +60,6 @@ __device__ __forceinline__ int swz4(int pix) { return (pix >> 2) & 3; }   // chu
 
 using i32x2 = __attribute__((ext_vector_type(2))) int;
 
-#ifdef RN_STAMPS
-// diagnostic build only (tools/build_stamps.sh): s_memtime + its wait in one statement, fenced
-__device__ __forceinline__ unsigned long long stamp23() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#endif
 
 // Producer / consumer workgroup: 8 waves, two per SIMD.  Waves 0-3 ("producers") run the first stage of the pair for
 // two column tiles each, fetch the A rows and write their B-row segments into the B ring; waves 4-7 ("consumers") run
@@ -314,9 +303,6 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
                 asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(wb[T] ^ static_cast<unsigned>(g << 4)), "v"(d), "n"(off) : "memory");
             }
         };
-#ifdef RN_STAMPS
-        unsigned long long st_bar = 0, st_seg[6] = {0, 0, 0, 0, 0, 0};
-#endif
         auto step = [&](auto PC, int t) __attribute__((always_inline)) {
             constexpr int P = decltype(PC)::value;
             if (t < nrows + 9) a_next += Win * 64;
@@ -353,42 +339,14 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
                 if constexpr (i == 13) issue_skip_piece(IC<3>{}, sk_f, sk_slot);
             };
             f32x16 acc;
-#ifdef RN_STAMPS
-            const unsigned long long tp0 = stamp23();
-#endif
             chain(IC<(P + 2) % 4>{}, IC<F_ROWA>{}, baseA[0], w2, acc, hook0);     // conv row t-2: A rows t-2 .. t
-#ifdef RN_STAMPS
-            const unsigned long long tp1 = stamp23();
-#endif
             epi(IC<0>{}, PC, acc);
-#ifdef RN_STAMPS
-            const unsigned long long tp2 = stamp23();
-#endif
             chain(IC<(P + 2) % 4>{}, IC<F_ROWA>{}, baseA[1], w2, acc, hook1);
-#ifdef RN_STAMPS
-            const unsigned long long tp3 = stamp23();
-#endif
             epi(IC<1>{}, PC, acc);
-#ifdef RN_STAMPS
-            const unsigned long long tp4 = stamp23();
-            st_seg[0] += tp1 - tp0;
-            st_seg[1] += tp2 - tp1;
-            st_seg[2] += tp3 - tp2;
-            st_seg[3] += tp4 - tp3;
-#endif
-#ifdef RN_STAMPS
-            const unsigned long long tb0 = stamp23();
-#endif
             wait_vmcnt<0>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             raw_barrier();
-#ifdef RN_STAMPS
-            st_bar += stamp23() - tb0;
-#endif
         };
-#ifdef RN_STAMPS
-        const unsigned long long st_loop0 = stamp23();
-#endif
         int t = 0;
         for (; t + 3 < nsteps; t += 4) {
             step(IC<0>{}, t);
@@ -401,17 +359,6 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
         if (rem > 1) step(IC<1>{}, t + 1);
         if (rem > 2) step(IC<2>{}, t + 2);
         wait_vmcnt<0>();
-#ifdef RN_STAMPS
-        if (a.stamp_buf && lane == 0) {
-            const int64_t w = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * 8 + wave;
-            a.stamp_buf[w * 4 + 0] = stamp23() - st_loop0;
-            a.stamp_buf[w * 4 + 1] = 0;
-            a.stamp_buf[w * 4 + 2] = st_bar;
-            a.stamp_buf[w * 4 + 3] = static_cast<unsigned long long>(nsteps);
-            unsigned long long* sg = a.stamp_buf + static_cast<int64_t>(gridDim.x) * gridDim.y * 32 + w * 8;
-            for (int k = 0; k < 6; ++k) sg[k] = st_seg[k];
-        }
-#endif
         return;
     }
 
@@ -601,9 +548,6 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
         __builtin_amdgcn_raw_buffer_store_b128(vv[0], cx.rs, vo, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(vv[1], cx.rs, vo + 32, 0, 0);
     };
-#ifdef RN_STAMPS
-    unsigned long long st_bar = 0, st_seg[6] = {0, 0, 0, 0, 0, 0};
-#endif
     auto step = [&](auto PC, int t) __attribute__((always_inline)) {
         constexpr int P = decltype(PC)::value;
         constexpr int PR = P & 1;
@@ -614,9 +558,6 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
         cx_cur.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(out_row), 0, out_row_bytes, 0x00020000);
         cx_cur.emit_mask = jo >= 0 ? 0 : OOB;
         if (jo >= 0 && jo < nrows - 1) out_row += out_row_bytes;
-#ifdef RN_STAMPS
-        const unsigned long long tc0 = stamp23();
-#endif
         // skip rows: the rare second new row of a step whose lo row jumped by 2 is fetched here; the regular one for the
         // next step is fetched by the partner producer during this step (mirrored in sk_f / sk_slot)
         const VLerp vl_next = vl_pre;                  // (computed behind the previous step's second chain)
@@ -633,53 +574,24 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
                 sk_slot = sk_slot == F_NSK - 1 ? 0 : sk_slot + 1;
             }
         }
-#ifdef RN_STAMPS
-        const unsigned long long tc1 = stamp23();
-        st_seg[0] += tc1 - tc0;
-        const unsigned long long tc2 = tc1;
-#endif
         f32x16 acc0;
         chain(IC<P>{}, IC<F_ROWB>{}, baseB[0], w3, acc0, no_hook);       // conv row t-8: B rows t-8 .. t-6
-#ifdef RN_STAMPS
-        const unsigned long long tc3 = stamp23();
-        st_seg[2] += tc3 - tc2;
-#endif
         wait_vmcnt<0>();                                       // a skip row fetched at the top of this step has landed
-#ifdef RN_STAMPS
-        const unsigned long long tc4 = stamp23();
-        st_seg[3] += tc4 - tc3;
-#endif
         epi(IC<0>{}, IC<PR>{}, acc0, cx_cur);
-#ifdef RN_STAMPS
-        const unsigned long long tc5 = stamp23();
-        st_seg[4] += tc5 - tc4;
-#endif
         // the next step's vertical interpolation (float multiply -> floor -> two readfirstlanes) rides behind this chain's MFMAs
         auto hook_c1 = [&](auto IC_) __attribute__((always_inline)) {
             if constexpr (decltype(IC_)::value == 2) vl_pre = vlerp_of(yo0 + min(max(jo + 2, 0), nrows - 1));
         };
         chain(IC<P>{}, IC<F_ROWB>{}, baseB[1], w3, acc1, hook_c1);
         epi(IC<1>{}, IC<PR>{}, acc1, cx_cur);
-#ifdef RN_STAMPS
-        st_seg[5] += stamp23() - tc5;
-#endif
         {
             int sl = slot_cur + (vl_next.ylo - vl_cur.ylo);
             slot_cur = sl >= F_NSK ? sl - F_NSK : sl;
             vl_cur = vl_next;
         }
-#ifdef RN_STAMPS
-        const unsigned long long tb0 = stamp23();
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         raw_barrier();
-#ifdef RN_STAMPS
-        st_bar += stamp23() - tb0;
-#endif
     };
-#ifdef RN_STAMPS
-    const unsigned long long st_loop0 = stamp23();
-#endif
     int t = 0;
     for (; t + 3 < nsteps; t += 4) {
         step(IC<0>{}, t);
@@ -692,34 +604,17 @@ __global__ __launch_bounds__(512, 2) void stage23pc_kernel(const Stage23Args a) 
     if (rem > 1) step(IC<1>{}, t + 1);
     if (rem > 2) step(IC<2>{}, t + 2);
     wait_vmcnt<0>();
-#ifdef RN_STAMPS
-    if (a.stamp_buf && lane == 0) {
-        const int64_t w = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * 8 + wave;
-        a.stamp_buf[w * 4 + 0] = stamp23() - st_loop0;
-        a.stamp_buf[w * 4 + 1] = 0;
-        a.stamp_buf[w * 4 + 2] = st_bar;
-        a.stamp_buf[w * 4 + 3] = static_cast<unsigned long long>(nsteps);
-        unsigned long long* sg = a.stamp_buf + static_cast<int64_t>(gridDim.x) * gridDim.y * 32 + w * 8;
-        for (int k = 0; k < 6; ++k) sg[k] = st_seg[k];
-    }
-#endif
 }
 
 }  // namespace
 
 int rn_stage23_launch(int dtype, hipStream_t s, const Stage23Args& a, int n) {
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};     // per device and instantiation, see launch_rw
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), F_LDS, s, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), F_LDS, s, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
-    if (dtype == RN_DTYPE_BF16) return launch(stage23pc_kernel<RN_DTYPE_BF16>);
-    return launch(stage23pc_kernel<RN_DTYPE_F16>);
+    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23pc_kernel<RN_DTYPE_BF16>>{});
+    return launch(rn_kernel<stage23pc_kernel<RN_DTYPE_F16>>{});
 }

@@ -32,7 +32,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -1018,30 +1017,24 @@ void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtyp
 }
 
 int rn_stage23x_launch(int dtype, hipStream_t s, const Stage23Args& a, int n) {
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};     // per device and instantiation
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), X_LDS, s, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), X_LDS, s, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
     if (a.producer_halves == 1 && a.narrow_b == 2) {
-        if (dtype == RN_DTYPE_BF16) return launch(stage23x_kernel<RN_DTYPE_BF16, 1, true, true>);
-        return launch(stage23x_kernel<RN_DTYPE_F16, 1, true, true>);
+        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 1, true, true>>{});
+        return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 1, true, true>>{});
     }
     if (a.producer_halves == 1 && a.narrow_b) {
-        if (dtype == RN_DTYPE_BF16) return launch(stage23x_kernel<RN_DTYPE_BF16, 1, true>);
-        return launch(stage23x_kernel<RN_DTYPE_F16, 1, true>);
+        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 1, true>>{});
+        return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 1, true>>{});
     }
     if (a.producer_halves == 1) {
         rn_set_error("stage23x: producer_halves == 1 runs in the narrow form only");
         return RN_E_STATE;
     }
-    if (dtype == RN_DTYPE_BF16) return launch(stage23x_kernel<RN_DTYPE_BF16, 2, false>);
-    return launch(stage23x_kernel<RN_DTYPE_F16, 2, false>);
+    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 2, false>>{});
+    return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 2, false>>{});
 }

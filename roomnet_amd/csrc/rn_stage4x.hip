@@ -23,7 +23,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -381,15 +380,9 @@ void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>
 
 int rn_stage4x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
     int nthreads = 512;
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cb, n), dim3(nthreads), U_LDS, s, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cb, n), dim3(nthreads), U_LDS, s, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
@@ -398,9 +391,9 @@ int rn_stage4x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
     for (int b = 0; b < a.n_cb; ++b) q3 = q3 && a.cb_wo[b] <= 100;
     if (q3) {
         nthreads = 768;
-        if (dtype == RN_DTYPE_BF16) return launch(stage4x_kernel<RN_DTYPE_BF16, 3>);
-        return launch(stage4x_kernel<RN_DTYPE_F16, 3>);
+        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage4x_kernel<RN_DTYPE_BF16, 3>>{});
+        return launch(rn_kernel<stage4x_kernel<RN_DTYPE_F16, 3>>{});
     }
-    if (dtype == RN_DTYPE_BF16) return launch(stage4x_kernel<RN_DTYPE_BF16, 4>);
-    return launch(stage4x_kernel<RN_DTYPE_F16, 4>);
+    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage4x_kernel<RN_DTYPE_BF16, 4>>{});
+    return launch(rn_kernel<stage4x_kernel<RN_DTYPE_F16, 4>>{});
 }

@@ -29,7 +29,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -555,22 +554,16 @@ void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned shor
 }
 
 int rn_stage5x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> attr_devices{0};
-        int dev = 0;
-        RN_HIP(hipGetDevice(&dev));
-        if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-            RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cb, n), dim3(512), V_LDS, s, a);
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cb, n), dim3(512), V_LDS, s, a);
         RN_CHECK_LAUNCH();
         return RN_OK;
     };
     if (a.cstart && a.live_q == 2) {
-        if (dtype == RN_DTYPE_BF16) return launch(stage5x_kernel<RN_DTYPE_BF16, true>);
-        return launch(stage5x_kernel<RN_DTYPE_F16, true>);
+        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage5x_kernel<RN_DTYPE_BF16, true>>{});
+        return launch(rn_kernel<stage5x_kernel<RN_DTYPE_F16, true>>{});
     }
-    if (dtype == RN_DTYPE_BF16) return launch(stage5x_kernel<RN_DTYPE_BF16, false>);
-    return launch(stage5x_kernel<RN_DTYPE_F16, false>);
+    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage5x_kernel<RN_DTYPE_BF16, false>>{});
+    return launch(rn_kernel<stage5x_kernel<RN_DTYPE_F16, false>>{});
 }

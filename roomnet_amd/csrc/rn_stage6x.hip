@@ -14,7 +14,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <utility>
 
 using namespace rnk;
@@ -22,7 +21,6 @@ using namespace rnk;
 namespace {
 
 constexpr int S6_NS = 4, S6_AHEAD = 3;
-constexpr int S6_RINGPX = 50;                     // 3 tiles + 2 halo columns
 constexpr int S6_ROW = 52 * 128;                  // bytes per ring row (padded)
 constexpr int S6_LDS = S6_NS * S6_ROW;
 constexpr int S6_WMIN = 35, S6_WMAX = 50;

@@ -21,7 +21,6 @@
 #include "rn_fused.h"
 #include "rn_stage.h"
 
-#include <atomic>
 #include <cstring>
 
 using namespace rnk;
@@ -584,19 +583,15 @@ struct F32mState {
     std::vector<F32mStage> st;
 };
 
-using F32LaunchFn = void (*)(const F32StageArgs&, dim3, dim3, size_t, hipStream_t);
+using F32LaunchFn = int (*)(const F32StageArgs&, dim3, dim3, size_t, hipStream_t);
 
 template <int CIN, int COUT, int PK, int PS, bool RES, int NSL, int LPT, int KS, int KQL = CIN / 8>
-void launch_f32m(const F32StageArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    auto kern = stage_f32m_kernel<CIN, COUT, PK, PS, RES, NSL, LPT, KS, KQL>;
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+int launch_f32m(const F32StageArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    constexpr auto kern = stage_f32m_kernel<CIN, COUT, PK, PS, RES, NSL, LPT, KS, KQL>;
+    if (int rc = rn_allow_big_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
 }
 
 struct F32Variant {
@@ -615,16 +610,12 @@ const F32Variant kF32Variants[] = {
 };
 
 template <int CIN, int KS, int LPT, int PS = 2, int CFZ = 0>
-void launch_f32m16(const F32StageArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    auto kern = stage_f32m16_kernel<CIN, KS, LPT, PS, CFZ>;
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+int launch_f32m16(const F32StageArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    constexpr auto kern = stage_f32m16_kernel<CIN, KS, LPT, PS, CFZ>;
+    if (int rc = rn_allow_big_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
 }
 struct F32Variant16 {
     int cin, ks, lpt;
@@ -823,29 +814,13 @@ int rn_f32m_launch(rn_handle* h, int stage, const float* in, int n) {
     const bool fold = !f.m16 && stage == h->f32_fold_stage && s.skip_stage >= 0 && h->f32_fold_live > 0 && h->f32_fold_live < s.cout &&
                       h->f32_fold_live % 32 == 0;
     if (fold) a.n_ctg = h->f32_fold_live / 32;
-    // bands: whole rounds of the chip (one workgroup per CU: the weights and the ring fill most of its LDS); a band costs its
-    // rows plus the rows its neighbour reads again
-    const long per_band = static_cast<long>(n) * f.n_colblocks * a.n_ctg;
-    const int rows_in = s.pool_k ? s.pool_s : 1, overlap = s.pool_k ? 5 : 2;
-    const int max_bands = std::max(1, s.out_side / 4);
-    int bands = 1;
-    long best = -1;
-    for (int b = 1; b <= 16 && b <= max_bands; ++b) {
-        const long rounds = (per_band * b + h->n_cu - 1) / h->n_cu;
-        const long cost = rounds * (rows_in * ((s.out_side + b - 1) / b) + overlap);
-        if (best < 0 || cost < best) {
-            best = cost;
-            bands = b;
-        }
-    }
-    if (per_band * bands < h->n_cu) bands = static_cast<int>(std::min<long>((h->n_cu + per_band - 1) / per_band, max_bands));
-    a.rows_per_band = (s.out_side + bands - 1) / bands;
-    a.n_bands = (s.out_side + a.rows_per_band - 1) / a.rows_per_band;
-    if (f.m16)
-        kF32Variants16[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * f.npt * f.ks16), f.lds, h->stream);
-    else
-        kF32Variants[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks * a.n_ctg, n), dim3(64 * f.npt * kF32Variants[f.variant].ks), f.lds, h->stream);
-    RN_CHECK_LAUNCH();
+    const Bands bands = rn_bands_f32m(n, h->n_cu, s.out_side, f.n_colblocks * a.n_ctg, s.pool_k, s.pool_s);
+    a.rows_per_band = bands.rows_per_band;
+    a.n_bands = bands.n_bands;
+    const int rc = f.m16 ? kF32Variants16[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * f.npt * f.ks16), f.lds, h->stream)
+                         : kF32Variants[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks * a.n_ctg, n), dim3(64 * f.npt * kF32Variants[f.variant].ks),
+                                                      f.lds, h->stream);
+    if (rc != RN_OK) return rc;
     if (fold) {
         const int c_begin = h->f32_fold_live, c_count = s.cout - c_begin;
         const int64_t n_pix = static_cast<int64_t>(n) * s.out_side * s.out_side;

@@ -24,7 +24,6 @@
 #include "rn_stage.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -163,17 +162,6 @@ struct RwCfg {
     static_assert(VMCNT_STEADY <= 63, "vmcnt field");
 };
 
-#ifdef RN_STAMPS
-// In-kernel stamps (diagnostic build only; never in the shipped library): s_memtime + its own wait
-// in ONE asm statement, fenced by sched_barrier so the segments hold what they are named for.
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#endif
 
 template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS, bool S0F, bool WIDE, int S0SH>
 __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>::NTHREADS), 1) void stage_rw_kernel(const StageArgs a) {
@@ -184,9 +172,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     constexpr int RW_NSLOT = C::NSLOT, RW_AHEAD = C::AHEAD;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef RN_STAMPS
-    const unsigned long long st_entry = stamp();
-#endif
 #ifdef RN_CLOCK
     unsigned long long ck_t0, ck_r0;
     clock_pair(ck_t0, ck_r0);
@@ -592,16 +577,11 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(out_img) + static_cast<int64_t>(yo) * out_row_bytes, 0,
                                                  out_row_bytes, 0x00020000);
     };
-#ifdef RN_DIAG
-    const bool stores_on = !(a.dbg_flags & 1);     // diagnostic builds only: timing without the output stores
-#else
-    constexpr bool stores_on = true;
-#endif
     // direct stores: this lane's 16-byte chunk of pixel xo (second chunk at +32 bytes)
-    const int voff_lane = (lane_out && stores_on) ? (xo * COUT + ct * 32 + 8 * hh) * 2 : OOB;
+    const int voff_lane = lane_out ? (xo * COUT + ct * 32 + 8 * hh) * 2 : OOB;
     // staged stores: lane-linear 16-byte chunks of the tile-row (second instruction + 1024 bytes)
-    const int voff_st0 = (stores_on && lane < 4 * nvalid) ? xo_t0s * COUT * 2 + lane * 16 : OOB;
-    const int voff_st1 = (stores_on && lane + 64 < 4 * nvalid) ? xo_t0s * COUT * 2 + lane * 16 + 1024 : OOB;
+    const int voff_st0 = (lane < 4 * nvalid) ? xo_t0s * COUT * 2 + lane * 16 : OOB;
+    const int voff_st1 = (lane + 64 < 4 * nvalid) ? xo_t0s * COUT * 2 + lane * 16 + 1024 : OOB;
 
     // ---- residual on the matrix cores: R[cout][x_out] = Skip^T[cout][x_in] * Wx[x_in][x_out]
     // (Wx = the legacy-bilinear interpolation matrix of this tile: two non-zeros per column).
@@ -932,10 +912,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     int sbuf_issue = PS == 1 ? 1 : 2;
     int sbuf_read = PS == 1 ? 0 : 2;
 
-#ifdef RN_STAMPS
-    unsigned long long st_work = 0, st_dma = 0, st_bar = 0, st_chain = 0;
-    const unsigned long long st_loop0 = stamp();
-#endif
     // One pipeline step s (ring phase P = s mod RW_NSLOT): DMA for row s+RW_AHEAD, MFMA chain of conv row s,
     // epilogue of conv row s-1, counted wait, barrier.
     //
@@ -948,9 +924,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     // 32-cycle MFMAs holds ~6 of them (12 with two waves per SIMD taking turns on the matrix pipe).
     auto step = [&](auto PC, auto MMAC, auto EPIC, int s) __attribute__((always_inline)) {
         constexpr int P = decltype(PC)::value;
-#ifdef RN_STAMPS
-        const unsigned long long ts0 = stamp();
-#endif
         constexpr bool MMA = decltype(MMAC)::value != 0, EPI = decltype(EPIC)::value != 0;
         constexpr int JP = (P + RW_NSLOT - 1) % RW_NSLOT;                     // phase of conv row s-1 (the epilogue's row)
         constexpr bool emit_phase = PK == 0 || PS == 1 || (JP & 1) == 1;
@@ -1167,13 +1140,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                 if constexpr (!RN_SPREAD_DMA) issue_skip((s - 2) / PS, sbuf_issue);
                 sbuf_issue = sbuf_issue == RW_SKIPBUF - 1 ? 0 : sbuf_issue + 1;
             }
-#if defined(RN_STAMPS) && defined(RN_STAMP_CHAIN)
-            const unsigned long long tc0 = stamp();
-#endif
             mma_row(PC, acc_new, slot);
-#if defined(RN_STAMPS) && defined(RN_STAMP_CHAIN)
-            st_chain += stamp() - tc0;
-#endif
             if constexpr (KS > 1) {
                 // waves of kernel rows 1, 2 publish their partial sums for the epilogue of the next step
                 if (ks > 0) part_write(P & 1, acc_new);
@@ -1196,24 +1163,12 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         }
         // the epilogue of this step handled conv row s-1: rotate the skip buffers after an emit phase
         if constexpr (RESW) sbuf_read = sbuf_read == RW_SKIPBUF - 1 ? 0 : sbuf_read + 1;
-#ifdef RN_STAMPS
-        const unsigned long long ts1 = stamp();
-#endif
         if constexpr (MMA && !C::S0F) {
             // retire the DMA of input row s+3 (and of the skip pair the next epilogue reads)
             wait_vmcnt<C::vmcnt_steady(P)>();
         }
-#ifdef RN_STAMPS
-        const unsigned long long ts2 = stamp();
-#endif
         if constexpr (C::S0SH) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this step's stage-0 row is in LDS
         if constexpr (!C::PRIV) raw_barrier();
-#ifdef RN_STAMPS
-        const unsigned long long ts3 = stamp();
-        st_work += ts1 - ts0;
-        st_dma += ts2 - ts1;
-        st_bar += ts3 - ts2;
-#endif
     };
 
     using T = IC<1>;
@@ -1244,54 +1199,13 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
     }
 #endif
-#ifdef RN_STAMPS
-    if (a.stamp_buf && lane == 0) {
-        const int64_t w = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * (NTHREADS / 64) + wave;
-        a.stamp_buf[w * 4 + 0] = st_work;
-        a.stamp_buf[w * 4 + 1] = st_dma;
-        a.stamp_buf[w * 4 + 2] = st_bar | (st_chain << 32);
-        // prologue (entry -> first step) in the upper half of slot 3, whole lifetime in the upper half of slot 1
-        a.stamp_buf[w * 4 + 3] = static_cast<unsigned long long>(nconv) | ((st_loop0 - st_entry) << 32);
-        a.stamp_buf[w * 4 + 1] = (st_dma & 0xffffffffull) | ((stamp() - st_entry) << 32);
-#ifdef RN_STAMP_HWID
-        // residency experiment: where and when did this wave run?  (HW_ID: wave slot, SIMD, CU, SH, SE, ...)
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        a.stamp_buf[w * 4 + 0] = st_entry;
-        a.stamp_buf[w * 4 + 2] = stamp();
-        a.stamp_buf[w * 4 + 3] = static_cast<unsigned long long>(nconv) | (static_cast<unsigned long long>(hwid) << 32);
-        a.stamp_buf[w * 4 + 1] = xcc;
-#endif
-    }
-#endif
 }
 
 template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS = 1, bool S0F = false, bool WIDE = false, int S0SH = 0>
 int launch_rw(hipStream_t s, const StageArgs& a, dim3 grid) {
     using C = RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
-    auto kern = stage_rw_kernel<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
-    // the attribute is per device: remember which devices of this process have it (one handle per GPU per process
-    // is the normal deployment, several handles on several GPUs / threads in one process must work too)
-    static std::atomic<unsigned long long> attr_devices{0};
-    int dev = 0;
-    RN_HIP(hipGetDevice(&dev));
-    if (!(attr_devices.load(std::memory_order_acquire) >> (dev & 63) & 1ull)) {
-        RN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        attr_devices.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
-#ifdef RN_DIAG
-    if (getenv("RN_DEBUG_OCC")) {
-        int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), C::NTHREADS, C::LDS_BYTES);
-        hipFuncAttributes fa{};
-        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-        fprintf(stderr, "[occ] CIN %d COUT %d RES %d NPT %d: threads %d, LDS %d B, regs %d, static LDS %zu, max blocks per CU %d\n", CIN, COUT,
-                int(RES), NPT, C::NTHREADS, C::LDS_BYTES, fa.numRegs, fa.sharedSizeBytes, nb);
-    }
-#endif
+    constexpr auto kern = stage_rw_kernel<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
+    if (int rc = rn_allow_big_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), C::LDS_BYTES, s, a);
     RN_CHECK_LAUNCH();
     return RN_OK;

@@ -12,7 +12,6 @@
 // (rn_kernels_f32.hip) on dense kernels that were staged in LDS while the conv phases ran.
 #include "rn_tail_body.h"
 
-#include <atomic>
 
 using namespace rnk;
 

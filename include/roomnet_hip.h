@@ -122,6 +122,18 @@ extern "C" {
                                TEST / A-B LIBRARY ONLY (round 6): the round-2 pair kernel is linked into
                                roomnet_amd/lib/libroomnet_hip_ab.so (same exports, csrc/build.sh builds both); the
                                product library answers this flag with RN_E_INVALID */
+#define RN_FLAG_BATCH_STATS 64u /* RN_DTYPE_F32 only: every BN normalises with the moments of the batch being fed, the forward
+                               pass of tf.layers.batch_normalization(training=True) -- what the reference's default
+                               RoomNet(compute_bn_mean_var=True) computes (network.py:193, :202, :217).  Per-node float32 path
+                               (no matrix-core stage kernels, no channel folding: rn_frozen_info / rn_const_info report
+                               nothing); at each of the 16 BN nodes: per-channel mean and biased variance of the node's
+                               input over n * h * w (dense BNs: over n), inv = rsqrt(var + eps) * gamma written on the
+                               device, then the same BN kernel as an inference handle.  The checkpoint's moving_mean /
+                               moving_variance are not read.  Every rn_forward_* / rn_submit_u8 call then depends on the
+                               whole batch (n = 1: variance 0, every BN returns beta); rn_tap as on any per-node handle
+                               (with RN_FLAG_TAPS: every node); rn_bn_batch_stats reads the moments back.  16-bit dtypes
+                               and RN_FLAG_GENERIC_KERNELS / _STAGE_LAUNCHES / _PAIR_32X32: RN_E_INVALID; rn_grad_cam_*:
+                               RN_E_STATE; groups: RN_E_INVALID (the moments would need an all-reduce) */
 
 #define RN_MAX_STAGES 16
 #define RN_MAX_DENSE 8
@@ -313,6 +325,24 @@ RN_API int rn_const_info(const rn_handle* h, int info[4]);
 RN_API int rn_node_count(const rn_handle* h);
 RN_API int rn_node_info_get(const rn_handle* h, int node_id, rn_node_info* out);
 RN_API int rn_tap(rn_handle* h, int node_id, float* out, size_t cap_elems, size_t* n_elems);
+
+/* ---- batch moments of the last forward call (RN_FLAG_BATCH_STATS handles) ------------------
+ * What the reference's update ops read (network.py:64-67: tf.GraphKeys.UPDATE_OPS of every
+ * tf.layers.batch_normalization(training=True)).  The BNs are numbered in the reference's variable order
+ * batch_normalization, _1, ... _15: per conv stage its BN, then the BN behind the residual add where there is
+ * one, then the three dense BNs.
+ *   rn_bn_count        how many there are (16), or a negative code
+ *   rn_bn_info         the BN's OUTPUT node ("s3.bn2", "d0.bn", ...) and its channel count in out->c
+ *   rn_bn_batch_stats  mean[c] = sum x / count and var_biased[c] = sum (x - mean)^2 / count over the count =
+ *                      n * h * w values per channel of the BN's input (dense BNs: n), float32; any of the three
+ *                      output pointers may be NULL.  Computed as float32 Welford partials merged in float64
+ *                      (rn_bnstats.hip): deterministic, and close to a float64 two-pass result.  The update
+ *                      of the moving statistics itself is host arithmetic on 32 short vectors
+ *                      (roomnet_amd/bnstats.py: moving_update, variance_for_update).
+ * RN_E_STATE on a handle without the flag or before the first forward call, RN_E_RANGE for a bad index. */
+RN_API int rn_bn_count(const rn_handle* h);
+RN_API int rn_bn_info(const rn_handle* h, int i, rn_node_info* out);
+RN_API int rn_bn_batch_stats(rn_handle* h, int i, float* mean, float* var_biased, int64_t* count);
 
 /* Enable/disable per-stage event timing (adds event records to every forward). */
 RN_API int rn_set_profiling(rn_handle* h, int enable);

@@ -21,6 +21,7 @@ RN_FLAG_GENERIC_KERNELS = 4     # 16-bit handles: generic stage kernel everywher
 RN_FLAG_PAIR_32X32 = 8          # 16-bit handles: the fused stage pair on the round-2 32x32x16 kernel (comparison arm)
 RN_FLAG_COMPUTE_FROZEN = 16     # convolve the provably constant channels too (comparison arm of the frozen-channel folding)
 RN_FLAG_NO_DITHER = 32          # 16-bit handles: plain rounding of weights and stores (comparison arm of the round-6 dither)
+RN_FLAG_BATCH_STATS = 64        # float32 handles: every BN normalises with the moments of the batch being fed (training=True forward)
 RN_MAX_STAGES = 16
 RN_MAX_DENSE = 8
 RN_NAME_LEN = 32
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "rn_group_forward_u8_device", "rn_group_result_buffer", "rn_group_sync", "rn_group_plan",
     "rn_band_plan",
     "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
+    "rn_bn_count", "rn_bn_info", "rn_bn_batch_stats",
 )
 
 # the layers rn_grad_cam_* explains (include/roomnet_hip.h: grad-CAM)
@@ -193,6 +195,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             fn = getattr(lib, name)
             fn.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
             fn.restype = i32
+    if hasattr(lib, "rn_bn_count"):
+        lib.rn_bn_count.argtypes = [vp]
+        lib.rn_bn_count.restype = i32
+        lib.rn_bn_info.argtypes = [vp, i32, C.POINTER(rn_node_info)]
+        lib.rn_bn_info.restype = i32
+        lib.rn_bn_batch_stats.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int64)]
+        lib.rn_bn_batch_stats.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -269,7 +278,7 @@ class Engine:
     def __init__(self, graph: Graph, weights: Dict[str, np.ndarray], device: int = 0, dtype="f32",
                  max_batch: int = 64, taps: bool = False, lib_path: Optional[str] = None,
                  stage_launches: bool = False, generic_kernels: bool = False, pair32: bool = False,
-                 compute_frozen: bool = False, no_dither: bool = False):
+                 compute_frozen: bool = False, no_dither: bool = False, batch_stats: bool = False):
         if pair32 and lib_path is None and "ROOMNET_HIP_LIB" not in os.environ:
             lib_path = AB_LIB_PATH           # (the round-2 comparison kernels are not in the product library)
         self.lib = load_library(lib_path)
@@ -284,7 +293,8 @@ class Engine:
                                 | (RN_FLAG_GENERIC_KERNELS if generic_kernels else 0)
                                 | (RN_FLAG_PAIR_32X32 if pair32 else 0)
                                 | (RN_FLAG_COMPUTE_FROZEN if compute_frozen else 0)
-                                | (RN_FLAG_NO_DITHER if no_dither else 0), C.byref(h))
+                                | (RN_FLAG_NO_DITHER if no_dither else 0)
+                                | (RN_FLAG_BATCH_STATS if batch_stats else 0), C.byref(h))
         _check(self.lib, rc, "rn_create")
         self._h = h
         self._nodes: Optional[Dict[str, Tuple[int, Tuple[int, int, int]]]] = None
@@ -544,6 +554,34 @@ class Engine:
             _check(self.lib, self.lib.rn_const_info(self.handle, info), "rn_const_info")
         return {"stage": info[0], "channels_proven_constant": info[1], "channels_not_convolved": info[2],
                 "next_stage_input_channels": info[3]}
+
+    def bn_batch_stats(self) -> Dict[str, Tuple[np.ndarray, np.ndarray, int]]:
+        """The batch moments of the last forward call on a ``batch_stats`` engine (``rn_bn_batch_stats``):
+        ``{bn_variable_prefix: (mean float32[c], var_biased float32[c], count)}`` in the reference's variable order
+        ``batch_normalization``, ``batch_normalization_1``, ... (count = n * h * w of the BN's input; n for the dense BNs)."""
+        n = self.lib.rn_bn_count(self.handle)
+        _check(self.lib, min(n, 0), "rn_bn_count")
+        out = {}
+        for i in range(n):
+            info = rn_node_info()
+            _check(self.lib, self.lib.rn_bn_info(self.handle, i, C.byref(info)), "rn_bn_info")
+            mean, var = np.empty(info.c, np.float32), np.empty(info.c, np.float32)
+            count = C.c_int64(0)
+            _check(self.lib, self.lib.rn_bn_batch_stats(self.handle, i, mean.ctypes.data, var.ctypes.data, C.byref(count)),
+                   "rn_bn_batch_stats")
+            out["batch_normalization" if i == 0 else "batch_normalization_%d" % i] = (mean, var, int(count.value))
+        return out
+
+    def bn_nodes(self) -> List[str]:
+        """Output node of every BN of a ``batch_stats`` engine, in the order of ``bn_batch_stats`` (``rn_bn_info``)."""
+        n = self.lib.rn_bn_count(self.handle)
+        _check(self.lib, min(n, 0), "rn_bn_count")
+        names = []
+        for i in range(n):
+            info = rn_node_info()
+            _check(self.lib, self.lib.rn_bn_info(self.handle, i, C.byref(info)), "rn_bn_info")
+            names.append(info.name.decode())
+        return names
 
     def set_profiling(self, enable: bool) -> None:
         _check(self.lib, self.lib.rn_set_profiling(self.handle, 1 if enable else 0), "rn_set_profiling")

@@ -151,7 +151,7 @@ int validate(const rn_weights* w, int dtype, int max_batch, unsigned flags) {
         rn_set_error("rn_create: unknown dtype %d", dtype);
         return RN_E_INVALID;
     }
-    if (flags & ~(RN_FLAG_TAPS | RN_FLAG_STAGE_LAUNCHES | RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32 | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_NO_DITHER)) {
+    if (flags & ~(RN_FLAG_TAPS | RN_FLAG_STAGE_LAUNCHES | RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32 | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_NO_DITHER | RN_FLAG_BATCH_STATS)) {
         rn_set_error("rn_create: unknown flag bits 0x%x", flags);
         return RN_E_INVALID;
     }
@@ -165,6 +165,17 @@ int validate(const rn_weights* w, int dtype, int max_batch, unsigned flags) {
     if ((flags & RN_FLAG_TAPS) && dtype != RN_DTYPE_F32) {
         rn_set_error("rn_create: RN_FLAG_TAPS needs RN_DTYPE_F32 (the unfused per-node path)");
         return RN_E_INVALID;
+    }
+    if (flags & RN_FLAG_BATCH_STATS) {
+        if (dtype != RN_DTYPE_F32) {
+            rn_set_error("rn_create: RN_FLAG_BATCH_STATS needs RN_DTYPE_F32 (batch moments run on the float32 per-node path)");
+            return RN_E_INVALID;
+        }
+        if (flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_STAGE_LAUNCHES | RN_FLAG_PAIR_32X32)) {
+            rn_set_error("rn_create: RN_FLAG_BATCH_STATS does not combine with the 16-bit handles' flags (0x%x)",
+                         flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_STAGE_LAUNCHES | RN_FLAG_PAIR_32X32));
+            return RN_E_INVALID;
+        }
     }
     if (max_batch < 1) {
         rn_set_error("rn_create: max_batch must be >= 1");
@@ -420,6 +431,8 @@ int forward_unfused(rn_handle* h, const float* d_rgb, int n, float* d_probs, int
         }
         float* bn = static_cast<float*>(h->nodes[s.node_bn].ptr);
         const int64_t npix = static_cast<int64_t>(n) * s.out_side * s.out_side;
+        // (batch-statistics handles: the table s.bn is written on the device from this tensor's moments first)
+        if (h->bnstats && (rc = rn_bnstats_conv(h, static_cast<int>(i), false, pooled, npix)) != RN_OK) return rc;
         if ((rc = rn_launch_bn_f32(h->stream, pooled, bn, npix, s.cout, s.bn)) != RN_OK) return rc;
         cur = bn;
         if (s.skip_stage >= 0) {
@@ -430,12 +443,13 @@ int forward_unfused(rn_handle* h, const float* d_rgb, int n, float* d_probs, int
                                                s.rt)) != RN_OK)
                 return rc;
             float* bn2 = static_cast<float*>(h->nodes[s.node_bn2].ptr);
+            if (h->bnstats && (rc = rn_bnstats_conv(h, static_cast<int>(i), true, add, npix)) != RN_OK) return rc;
             if ((rc = rn_launch_bn_f32(h->stream, add, bn2, npix, s.cout, s.bn2)) != RN_OK) return rc;
             cur = bn2;
         }
         record(h, 2 + static_cast<int>(i));
     }
-    if ((rc = run_head(h, n, d_probs, d_ids)) != RN_OK) return rc;
+    if ((rc = h->bnstats ? rn_bnstats_head(h, n, d_probs, d_ids) : run_head(h, n, d_probs, d_ids)) != RN_OK) return rc;
     record(h, 2 + static_cast<int>(h->stages.size()));
     return RN_OK;
 }
@@ -532,7 +546,7 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     RelabelledWeights rw(w);
     std::vector<int> fold_pi, kfold_pi;
     int fold_r = -1, kfold_r = -1, kfold_live = 0, kfold_proven = 0;
-    if (!fused_mode(h) && !(flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN))) {
+    if (!fused_mode(h) && !(flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_BATCH_STATS))) {
         auto bn1_frozen = [&](const rn_conv_stage& st, int c) {
             const float inv = rn_bn_inv(st.variance[c], st.gamma[c], w->bn_epsilon);
             const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
@@ -625,7 +639,9 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     }
     if (fused_mode(h) && (rc = rn_fused_prepare(h, w)) != RN_OK) return fail(rc);
     // float32 handles without per-node taps run their conv stages on the matrix cores (rn_stage_f32m.hip)
-    if (!fused_mode(h) && !(h->flags & RN_FLAG_TAPS) && (rc = rn_f32m_prepare(h, w)) != RN_OK) return fail(rc);
+    // (not the batch-statistics handles: their BN tables do not exist before the stage's input has been reduced)
+    if (!fused_mode(h) && !(h->flags & (RN_FLAG_TAPS | RN_FLAG_BATCH_STATS)) && (rc = rn_f32m_prepare(h, w)) != RN_OK) return fail(rc);
+    if ((h->flags & RN_FLAG_BATCH_STATS) && (rc = rn_bnstats_prepare(h, w)) != RN_OK) return fail(rc);
     if ((rc = alloc_buffers(h)) != RN_OK) return fail(rc);
     if (fused_mode(h) && (rc = rn_fused_post_alloc(h)) != RN_OK) return fail(rc);
     h->events.resize(3 + h->stages.size());
@@ -664,6 +680,7 @@ extern "C" void rn_destroy(rn_handle* h) {
     rn_fused_release(h);
     rn_f32m_release(h);
     rn_gradcam_release(h);
+    rn_bnstats_release(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -765,6 +782,10 @@ int gradcam_check(rn_handle* h, int n, int layer_node, bool* layer6) {
     if (!h) {
         rn_set_error("null handle");
         return RN_E_INVALID;
+    }
+    if (h->bnstats) {
+        rn_set_error("rn_grad_cam: the adjoint is that of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)");
+        return RN_E_STATE;
     }
     if (const char* why = rn_gradcam_unsupported(h)) {
         rn_set_error("rn_grad_cam: not supported on this graph (%s)", why);

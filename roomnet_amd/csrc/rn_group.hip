@@ -207,6 +207,10 @@ extern "C" int rn_group_create(const rn_weights* w, int ndev, const int* devices
                 rn_set_error("rn_group_create: device %d listed twice", devices[a]);
                 return RN_E_INVALID;
             }
+    if (flags & RN_FLAG_BATCH_STATS) {
+        rn_set_error("rn_group_create: RN_FLAG_BATCH_STATS is a one-device flag (a group would need an all-reduce of the moments' partials)");
+        return RN_E_INVALID;
+    }
     if (!load_rccl()) {
         rn_set_error("rn_group_create: %s", g_rccl_error.c_str());
         return RN_E_STATE;

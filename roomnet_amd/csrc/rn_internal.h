@@ -149,6 +149,7 @@ struct rn_handle {
     void* fused = nullptr;       // plan of the fused 16-bit path (rn_fused.hip)
     void* f32m = nullptr;        // plan of the float32 matrix-core stage kernels (rn_stage_f32m.hip)
     void* gradcam = nullptr;     // what the grad-CAM adjoint keeps from rn_create + its device workspace (rn_gradcam.hip)
+    void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
     // couts whose convolution still runs
@@ -206,6 +207,13 @@ void rn_gradcam_layers(const rn_handle* h, int* node6, int* node7);
 const char* rn_gradcam_unsupported(const rn_handle* h);
 int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* d_ids, bool layer6, float* d_cam, float* d_alpha);
 int rn_gradcam_staging(rn_handle* h, int32_t** d_cls, float** d_cam, float** d_alpha);
+
+// ---- batch-statistics BN (rn_bnstats.hip): float32 per-node handles created with RN_FLAG_BATCH_STATS
+int rn_bnstats_prepare(rn_handle* h, const rn_weights* w);     // after the plan is built: what the moments launches need
+void rn_bnstats_release(rn_handle* h);
+// moments of x [npix, cout] on the handle's stream -> the (mean, inv) table of stage `stage`'s first / second BN
+int rn_bnstats_conv(rn_handle* h, int stage, bool second, const float* x, int64_t npix);
+int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
 
 // ---- host helpers of rn_create (rn_api.hip) ---------------------------------------------
 // device memory owned by the handle (freed by rn_destroy); errors as "hipMalloc(N bytes) failed: ..."

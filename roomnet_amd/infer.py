@@ -101,25 +101,11 @@ def _progress(n):
     return bar.update, bar.close
 
 
-def _infer_files(nn, fpaths, batch_size, decode_threads=None):
-    """Yield ``(index, image_bgr, idx, conf)`` per readable file, in list order.  Files are decoded on a small thread
-    pool (Pillow releases the GIL while it decodes) that runs up to two batches ahead of the GPU; the GPU gets the
-    decoded images in batches of ``batch_size``."""
+def _decode_files(fpaths, batch_size, decode_threads=None):
+    """Yield ``(index, fpath, image_bgr or None)`` per file, in list order: decoded on a small thread pool (Pillow releases
+    the GIL while it decodes) that runs up to two batches of ``batch_size`` ahead of the consumer."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
-    pending = []
-
-    def flush():
-        if not pending:
-            return []
-        ids, probs = _classify(nn, [p[1] for p in pending])
-        # the confidence stays an np.float32 scalar like infer_outs[1][0][idx] of the reference (infer.py:84): its
-        # printed form, round(conf * 100, 2) and str(conf) are float32 results
-        res = [(p[0], p[1], int(ids[k]), (probs[k][ids[k]] if probs is not None else np.float32('nan')))
-               for k, p in enumerate(pending)]
-        pending.clear()
-        return res
-
     nthreads = max(1, int(decode_threads or DECODE_THREADS))
     window = max(2 * batch_size, nthreads)
     todo = iter(enumerate(fpaths))
@@ -138,16 +124,37 @@ def _infer_files(nn, fpaths, batch_size, decode_threads=None):
             im = fut.result()
             tick(1)
             top_up()
-            if im is None:
-                # the reference crashes here (cv2.imread returns None, infer.py:81-82); report and go on
-                print(fpath, '---> unreadable image, skipped')
-                continue
-            pending.append((i, im))
-            if len(pending) >= batch_size:
-                for r in flush():
-                    yield r
-        for r in flush():
-            yield r
+            yield i, fpath, im
+
+
+def _infer_files(nn, fpaths, batch_size, decode_threads=None):
+    """Yield ``(index, image_bgr, idx, conf)`` per readable file, in list order.  Files are decoded on a small thread
+    pool (Pillow releases the GIL while it decodes) that runs up to two batches ahead of the GPU; the GPU gets the
+    decoded images in batches of ``batch_size``."""
+    pending = []
+
+    def flush():
+        if not pending:
+            return []
+        ids, probs = _classify(nn, [p[1] for p in pending])
+        # the confidence stays an np.float32 scalar like infer_outs[1][0][idx] of the reference (infer.py:84): its
+        # printed form, round(conf * 100, 2) and str(conf) are float32 results
+        res = [(p[0], p[1], int(ids[k]), (probs[k][ids[k]] if probs is not None else np.float32('nan')))
+               for k, p in enumerate(pending)]
+        pending.clear()
+        return res
+
+    for i, fpath, im in _decode_files(fpaths, batch_size, decode_threads):
+        if im is None:
+            # the reference crashes here (cv2.imread returns None, infer.py:81-82); report and go on
+            print(fpath, '---> unreadable image, skipped')
+            continue
+        pending.append((i, im))
+        if len(pending) >= batch_size:
+            for r in flush():
+                yield r
+    for r in flush():
+        yield r
 
 
 def groundtruth_validation(nn, list_fpath=None, batch_size=64):
@@ -231,6 +238,29 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64):
             writers.shutdown(wait=True)
     excel_file.save(xl_fpath)
     return xl_fpath
+
+
+def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None):
+    """Re-estimate the model's BN statistics on the images of a directory (``RoomNet.recalibrate_bn``; not in the reference,
+    whose statistics only move while it trains, network.py:64-67): the files are decoded as ``classify_im_dir`` decodes them
+    and fed in batches of ``batch_size`` (at most the model's ``max_batch``; a last batch of ONE image is dropped: its variance is 0).
+    ``momentum=None``: the statistics become the average over the batches.  Returns the new statistics."""
+    all_im_paths = sorted(glob(imgs_dir + '/*'))
+
+    def batches():
+        pending = []
+        for _i, fpath, im in _decode_files(all_im_paths, batch_size):
+            if im is None:
+                print(fpath, '---> unreadable image, skipped')
+                continue
+            pending.append(im)
+            if len(pending) >= batch_size:
+                yield pending
+                pending = []
+        if len(pending) > 1:
+            yield pending
+
+    return nn.recalibrate_bn(batches(), momentum=momentum)
 
 
 if __name__ == '__main__':

@@ -6,6 +6,8 @@ Kept from the reference (same names, argument meaning, return shapes/dtypes):
 ``RoomNet(num_classes, im_side=600, ...)``, attributes ``num_classes``,
 ``im_side``, ``sess``; ``init()``, ``load(model_path=None)``, ``save(suffix=None)``,
 ``center_crop(x)``, ``infer(im_batch)``, ``infer_optimized(im)``.
+Batch-statistics BN, the forward pass of the reference's default ``compute_bn_mean_var=True`` model, arrives through
+``infer_batch_stats`` and ``recalibrate_bn`` (the constructor still refuses the flag: that model is the training graph).
 Training (``train_step``, loss/optimizer graph, ``network.py:49-85,158-170``) is out
 of scope and raises ``NotImplementedError``.
 
@@ -33,11 +35,15 @@ class _Session:
     def __init__(self, variables: Dict[str, np.ndarray]):
         self.variables = variables
         self.engine: Optional[Engine] = None
+        self.bs_engine: Optional[Engine] = None      # the float32 batch-statistics engine (infer_batch_stats, recalibrate_bn)
 
     def close(self) -> None:
         if self.engine is not None:
             self.engine.close()
             self.engine = None
+        if self.bs_engine is not None:
+            self.bs_engine.close()
+            self.bs_engine = None
 
 
 def _initializer_values(graph: Graph, seed: int = 0) -> Dict[str, np.ndarray]:
@@ -215,6 +221,16 @@ class RoomNet:
                                       max_batch=self.max_batch)
         return self.sess.engine
 
+    def _bs_engine(self) -> Engine:
+        """The float32 engine whose BNs normalise with the moments of the batch (``RN_FLAG_BATCH_STATS``), built beside the
+        model's own engine from the same variables, whatever ``dtype`` the model has."""
+        if not self.sess:
+            raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
+        if self.sess.bs_engine is None:
+            self.sess.bs_engine = Engine(self.graph, self.sess.variables, device=self.device, dtype="f32",
+                                         max_batch=self.max_batch, batch_stats=True)
+        return self.sess.bs_engine
+
     def tap(self, name, n=1):
         """The per-layer read-out the reference gets from ``sess.run(self.layers[k][j], ...)``: tensor ``name`` (an entry of
         ``self.layers``) of the LAST inference call, float32 ``[n, h, w, c]`` (``rn_tap``).  Float32 engines built with taps hold
@@ -347,6 +363,77 @@ class RoomNet:
             x = (((im[:, :, :, [2, 1, 0]] / 255.) * 2) - 1).astype(np.float32)
             cams, ids, probs = eng.grad_cam(x, class_ids=class_ids, layer=layer)
         return cams, ids, probs
+
+    # ------------------------------------------------------ batch-statistics BN
+    def _batch_from(self, im_in, who):
+        """``[N,S,S,3]`` array as it is (the feed rules of ``infer``); a list of BGR ``[H,W,3]`` images of any size through
+        ``center_crop`` + the ``cv2.resize`` restatement, as ``infer_images`` prepares them."""
+        if isinstance(im_in, np.ndarray):
+            if im_in.ndim != 4 or im_in.shape[1:] != (self.im_side, self.im_side, 3):
+                raise ValueError("Cannot feed value of shape %s for Tensor 'input_x_tensor:0', which has shape "
+                                 "'(?, %d, %d, 3)'" % (im_in.shape, self.im_side, self.im_side))
+            return im_in
+        prepared = []
+        for one in im_in:
+            one = np.asarray(one)
+            if one.ndim != 3 or one.shape[2] != 3:
+                raise ValueError("%s: expected [H,W,3] BGR images, got shape %s" % (who, one.shape))
+            one = self.center_crop(one)
+            if one.shape[0] != self.im_side or one.shape[1] != self.im_side:
+                one = resize_linear_u8(np.ascontiguousarray(one, dtype=np.uint8), self.im_side, self.im_side)
+            prepared.append(np.ascontiguousarray(one))
+        if not prepared:
+            raise ValueError("%s: no images" % who)
+        return np.stack(prepared, 0)
+
+    def _forward_batch_stats(self, im):
+        eng = self._bs_engine()
+        if im.shape[0] > eng.max_batch:
+            raise ValueError("a batch-statistics pass normalises over the WHOLE batch: %d images exceed max_batch=%d "
+                             "(construct with a larger max_batch)" % (im.shape[0], eng.max_batch))
+        if im.dtype == np.uint8:
+            return eng.forward_u8(im)
+        x = (((im[:, :, :, [2, 1, 0]] / 255.) * 2) - 1).astype(np.float32)
+        return eng.forward_f32(x)
+
+    def infer_batch_stats(self, im_in):
+        """``infer`` of a model the reference builds with its default ``compute_bn_mean_var=True``: every BN normalises with
+        the moments of THIS batch (network.py:193, :202, :217) instead of the checkpoint's moving statistics, so each row
+        of the result depends on the whole batch.  Same feed rules and return convention as ``infer``; runs in float32 on the
+        batch-statistics engine whatever ``dtype`` the model has; the batch must fit ``max_batch``.  ``bn_batch_stats()`` of
+        that engine then holds the moments."""
+        im = np.asarray(im_in)
+        if im.ndim != 4 or im.shape[1:] != (self.im_side, self.im_side, 3):
+            raise ValueError("Cannot feed value of shape %s for Tensor 'input_x_tensor:0', which has shape "
+                             "'(?, %d, %d, 3)'" % (im.shape, self.im_side, self.im_side))
+        ids, probs = self._forward_batch_stats(im)
+        if self.optimized_inference:
+            return ids, probs
+        return ids
+
+    def recalibrate_bn(self, batches, momentum=0.99):
+        """Re-estimate the moving statistics of all 16 BNs from data, without gradients (AdaBN; also what a fresh ``init()``
+        or retrained model needs before ``infer`` means anything).  ``batches``: an iterable of ``[N,S,S,3]`` BGR batches,
+        or of lists of BGR images of any size.  Each batch takes one batch-statistics forward pass on the GPU; then all 32
+        ``moving_*`` variables are updated on the host (``roomnet_amd.bnstats``): with a number for ``momentum`` by the
+        reference's rule, batch after batch (network.py:64-67; ``tf.layers`` default 0.99); with ``momentum=None`` they
+        BECOME the equal-weight average of the per-batch moments.  The forward passes all run with the statistics-free
+        batch normalisation, so the order of the batches only matters through the momentum rule.  Updates
+        ``sess.variables`` and closes the engines (the next ``infer`` builds its engine on the new statistics); returns
+        ``{variable name: new value}`` for the 32 variables.  An empty iterable raises ``ValueError``."""
+        from . import bnstats
+        if not self.sess:
+            self.init()
+        seen = []
+        for batch in batches:
+            im = self._batch_from(batch, "recalibrate_bn")
+            self._forward_batch_stats(im)
+            seen.append(self._bs_engine().bn_batch_stats())
+        if not seen:
+            raise ValueError("recalibrate_bn: no batches")
+        new = bnstats.updated_statistics(self.graph, self.sess.variables, seen, momentum)
+        self.set_variables(new)
+        return new
 
     def train_step(self, x_in, y):
         raise NotImplementedError("training (network.py:158-170) is out of scope of the MI355X inference path")

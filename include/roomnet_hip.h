@@ -291,6 +291,75 @@ RN_API int rn_grad_cam_f32(rn_handle* h, const float* rgb_nhwc, int n, const int
 RN_API int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, const int32_t* d_class_ids, int layer_node,
                                  float* d_cam, float* d_alpha, float* d_probs, int64_t* d_ids);
 
+/* ---- fine-tuning stages 8-9 and the dense head on cached features ------------------------------
+ * What the reference's RoomNet(optimized_inference=False).load() prepares (network.py:242, restore_excluded_vars: the conv trunk
+ * restored, the dense head left at its initial values, to be trained), cut where it is cheap: stages 0-7 stay frozen, and
+ * everything behind "s7.bn" depends on s7.bn alone (21 x 21 x 16 at 224, 68 x 68 x 16 at 600).  rn_features_* fill a cache of
+ * those features with the handle's fast forward pass; an rn_ft trainer then runs Adam steps on the resident cache with no
+ * trunk pass, no host round trip and no inference handle.  Mathematics (forward, loss, TensorFlow's gradient rules, Adam, the
+ * learning-rate schedule): the header of csrc/rn_finetune.hip.  In short: every BN is the inference BN with trainable gamma and
+ * beta and fixed moving statistics (train.py:40-41), no dropout; loss = mean CE(softmax(relu6(z)), y) + l2_coeff sum(v^2) / 2 over
+ * the TRAINED variables; tf.train.AdamOptimizer in float32 with lr(step) = learn_rate * decay_rate^(step / num_steps).
+ *
+ * rn_features_shape     side and channels of one feature ([side, side, channels] float32 per image)
+ * rn_features_u8        BGR uint8 [n, S, S, 3] on the host -> this call's s7.bn widened to float32 [n, side, side, 16] on the
+ *                       host; n <= max_batch; blocks
+ * rn_features_u8_device the same on device buffers; only enqueues on the handle's stream
+ * Both run a forward pass (on 16-bit handles with the back end as its split launches, as rn_grad_cam_* does, so that s7.bn
+ * is written whatever n is); rn_tap afterwards returns that pass's tensors.  RN_E_INVALID on a graph without the last block,
+ * RN_E_STATE on RN_FLAG_BATCH_STATS handles, RN_E_RANGE for n outside [1, max_batch]. */
+RN_API int rn_features_shape(const rn_handle* h, int* side, int* channels);
+RN_API int rn_features_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, float* feat);
+RN_API int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, float* d_feat);
+
+typedef struct rn_ft rn_ft;
+typedef struct rn_ft_config {
+    float learn_rate;         /* RoomNet(learn_rate=...)                            */
+    float decay_rate;         /* 0.068 in the reference (network.py:36)             */
+    int32_t num_steps;        /* RoomNet(num_steps=...): the decay's time constant  */
+    int32_t start_step;       /* RoomNet(start_step=...): the global step to resume */
+    float l2_coeff;           /* RoomNet(l2_regularizer_coeff=...)                  */
+    float beta1, beta2, epsilon; /* tf.train.AdamOptimizer: 0.9, 0.999, 1e-8        */
+} rn_ft_config;
+
+#define RN_FT_PARAM 0       /* the float32 master copy of a trained variable      */
+#define RN_FT_GRAD 1        /* its gradient at the last step, L2 term included    */
+#define RN_FT_ADAM_M 2      /* Adam's first-moment slot                           */
+#define RN_FT_ADAM_V 3      /* Adam's second-moment slot                          */
+
+/* rn_ft_create takes the model as rn_create does and keeps float32 master copies of the trained variables -- the last two conv
+ * stages' kernels and BN gamma / beta (both BNs of the residual stage), every dense layer's kernel, BN gamma / beta or bias: 19
+ * variables for the reference graph, in checkpoint order (rn_ft_var_info) -- with zeroed Adam slots, on `device`, with a
+ * stream of its own.  It needs no rn_handle and allocates no trunk workspace; max_batch bounds the minibatch of rn_ft_run.
+ * Graphs rn_grad_cam_* refuses are refused here with the same reasons (RN_E_INVALID).
+ * rn_ft_run     `steps` Adam steps; step s trains on items d_index[s * batch .. (s + 1) * batch) of the resident d_feats
+ *               [n_items, side, side, 16] float32 with classes d_labels [n_items] int32 (all device memory, e.g. of
+ *               rn_ft_upload); two launches per step enqueued back to back, one synchronisation at the end; losses [steps]
+ *               on the host: each step's loss evaluated BEFORE that step's update.  An index outside [0, n_items), a label
+ *               (of an indexed item) outside [0, num_classes) or batch outside [1, max_batch] is RN_E_RANGE, checked on the
+ *               host before anything is enqueued: the trainer is unchanged.  No floating-point atomics: the same calls give
+ *               the same bits, and one call of k steps equals k calls of one step.
+ * rn_ft_eval    forward only, from the current master parameters, for any n (chunks of max_batch inside): mean_loss (the
+ *               training loss, L2 term included; needs d_labels), probs [n, num_classes], ids [n] on the host; each may be NULL.
+ * rn_ft_read    one variable's values of kind `what` to host float32 (cap: elements available).
+ * rn_ft_step_count  the global step: start_step + steps run.
+ * rn_ft_last_run_ms  device time of the last rn_ft_run's step loop (events on the trainer's stream around its launches).
+ * rn_ft_upload / rn_ft_free  device memory for the caller's features, labels and indices: allocate + copy from the host, and
+ *               free (rn_ft_destroy frees what is left).  Calls on one trainer must be serialised by the caller. */
+RN_API int rn_ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, rn_ft** out);
+RN_API void rn_ft_destroy(rn_ft* ft);
+RN_API int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
+                     int steps, float* losses);
+RN_API int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n, float* mean_loss, float* probs,
+                      int64_t* ids);
+RN_API int rn_ft_var_count(const rn_ft* ft);
+RN_API int rn_ft_var_info(const rn_ft* ft, int var, char* name, size_t name_cap, int64_t* count);
+RN_API int rn_ft_read(rn_ft* ft, int what, int var, float* out, size_t cap);
+RN_API int64_t rn_ft_step_count(const rn_ft* ft);
+RN_API int rn_ft_last_run_ms(rn_ft* ft, float* ms);
+RN_API int rn_ft_upload(rn_ft* ft, const void* src, size_t bytes, void** d_ptr);
+RN_API int rn_ft_free(rn_ft* ft, void* d_ptr);
+
 /* ---- introspection -----------------------------------------------------------
  * rn_tap copies graph node `node_id` of the last forward call to host float32
  * (layout [n, h, w, c]); needs RN_FLAG_TAPS for conv/pool/add nodes; the

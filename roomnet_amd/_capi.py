@@ -46,7 +46,13 @@ EXPORTED_SYMBOLS = (
     "rn_band_plan",
     "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
     "rn_bn_count", "rn_bn_info", "rn_bn_batch_stats",
+    "rn_features_shape", "rn_features_u8", "rn_features_u8_device",
+    "rn_ft_create", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
+    "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
 )
+
+# what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
+RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V = 0, 1, 2, 3
 
 # the layers rn_grad_cam_* explains (include/roomnet_hip.h: grad-CAM)
 GRAD_CAM_LAYERS = ("s6.bn", "s7.bn")
@@ -84,6 +90,11 @@ class rn_stage_ms(C.Structure):
 
 class rn_node_info(C.Structure):
     _fields_ = [("name", C.c_char * RN_NAME_LEN), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32)]
+
+
+class rn_ft_config(C.Structure):
+    _fields_ = [("learn_rate", C.c_float), ("decay_rate", C.c_float), ("num_steps", C.c_int32), ("start_step", C.c_int32),
+                ("l2_coeff", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -202,6 +213,35 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_bn_info.restype = i32
         lib.rn_bn_batch_stats.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int64)]
         lib.rn_bn_batch_stats.restype = i32
+    if hasattr(lib, "rn_ft_create"):
+        lib.rn_features_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.rn_features_shape.restype = i32
+        lib.rn_features_u8.argtypes = [vp, vp, i32, vp]
+        lib.rn_features_u8.restype = i32
+        lib.rn_features_u8_device.argtypes = [vp, vp, i32, vp]
+        lib.rn_features_u8_device.restype = i32
+        lib.rn_ft_create.argtypes = [C.POINTER(rn_weights), i32, i32, C.POINTER(rn_ft_config), C.POINTER(vp)]
+        lib.rn_ft_create.restype = i32
+        lib.rn_ft_destroy.argtypes = [vp]
+        lib.rn_ft_destroy.restype = None
+        lib.rn_ft_run.argtypes = [vp, vp, vp, C.c_int64, vp, i32, i32, vp]
+        lib.rn_ft_run.restype = i32
+        lib.rn_ft_eval.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
+        lib.rn_ft_eval.restype = i32
+        lib.rn_ft_var_count.argtypes = [vp]
+        lib.rn_ft_var_count.restype = i32
+        lib.rn_ft_var_info.argtypes = [vp, i32, C.c_char_p, sz, C.POINTER(C.c_int64)]
+        lib.rn_ft_var_info.restype = i32
+        lib.rn_ft_read.argtypes = [vp, i32, i32, vp, sz]
+        lib.rn_ft_read.restype = i32
+        lib.rn_ft_step_count.argtypes = [vp]
+        lib.rn_ft_step_count.restype = C.c_int64
+        lib.rn_ft_last_run_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_ft_last_run_ms.restype = i32
+        lib.rn_ft_upload.argtypes = [vp, vp, sz, C.POINTER(vp)]
+        lib.rn_ft_upload.restype = i32
+        lib.rn_ft_free.argtypes = [vp, vp]
+        lib.rn_ft_free.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -462,6 +502,32 @@ class Engine:
                                             C.c_void_p(d_probs), C.c_void_p(d_ids))
         _check(self.lib, rc, "rn_grad_cam_u8_device")
 
+    def features_shape(self) -> Tuple[int, int, int]:
+        """Per-image shape of the fine-tuning feature ``s7.bn`` (``rn_features_shape``)."""
+        side, ch = C.c_int(0), C.c_int(0)
+        _check(self.lib, self.lib.rn_features_shape(self.handle, C.byref(side), C.byref(ch)), "rn_features_shape")
+        return side.value, side.value, ch.value
+
+    def features_u8(self, im_bgr_u8: np.ndarray) -> np.ndarray:
+        """``s7.bn`` of a uint8 BGR ``[N,S,S,3]`` batch, widened to float32 ``[N, side, side, 16]`` (``rn_features_u8``): what
+        ``Trainer`` trains on."""
+        s = self.graph.im_side
+        im = np.ascontiguousarray(im_bgr_u8, dtype=np.uint8)
+        if im.ndim != 4 or im.shape[1:] != (s, s, 3):
+            raise ValueError("expected a [N,%d,%d,3] uint8 batch, got %s" % (s, s, im.shape))
+        n = im.shape[0]
+        out = np.empty((n,) + self.features_shape(), np.float32)
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            _check(self.lib, self.lib.rn_features_u8(self.handle, im[i:i + m].ctypes.data, m, out[i:i + m].ctypes.data),
+                   "rn_features_u8")
+        return out
+
+    def features_u8_device(self, d_bgr: int, n: int, d_feat: int) -> None:
+        """Asynchronous ``rn_features_u8_device`` on raw device pointers."""
+        _check(self.lib, self.lib.rn_features_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_feat)),
+               "rn_features_u8_device")
+
     def sync(self) -> None:
         _check(self.lib, self.lib.rn_sync(self.handle), "rn_sync")
 
@@ -605,6 +671,125 @@ class Engine:
                 raise RoomNetLibraryError(self.lib.rn_last_error().decode())
             groups.setdefault(rep, []).append(i)
         return [groups[k] for k in sorted(groups)]
+
+
+class Trainer:
+    """One rn_ft: float32 master copies of the last two conv stages and the dense head, Adam slots and the step counter on one
+    GPU (include/roomnet_hip.h: fine-tuning).  Trains on features that stay resident in device memory: ``upload`` the
+    ``[n_items, side, side, 16]`` float32 features of ``Engine.features_u8`` and the int32 labels once, then ``run``."""
+
+    def __init__(self, graph: Graph, weights: Dict[str, np.ndarray], device: int = 0, max_batch: int = 64, learn_rate: float = 1e-4,
+                 num_steps: int = 10000, start_step: int = 0, l2_coeff: float = 1e-2, decay_rate: float = 0.068,
+                 beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        self.graph = graph
+        self.max_batch = int(max_batch)
+        packed = _Packed(graph, weights)
+        cfg = rn_ft_config(learn_rate, decay_rate, int(num_steps), int(start_step), l2_coeff, beta1, beta2, epsilon)
+        h = C.c_void_p()
+        self._h = None
+        _check(self.lib, self.lib.rn_ft_create(C.byref(packed.w), int(device), self.max_batch, C.byref(cfg), C.byref(h)),
+               "rn_ft_create")
+        self._h = h
+        self._vars: Optional[List[Tuple[str, int]]] = None
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self.lib.rn_ft_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if not self._h:
+            raise RoomNetLibraryError("trainer is closed")
+        return self._h
+
+    def upload(self, a: np.ndarray) -> int:
+        """Copy an array into device memory the trainer owns (``rn_ft_upload``); returns the device pointer."""
+        a = np.ascontiguousarray(a)
+        p = C.c_void_p()
+        _check(self.lib, self.lib.rn_ft_upload(self.handle, a.ctypes.data, a.nbytes, C.byref(p)), "rn_ft_upload")
+        return int(p.value)
+
+    def free(self, d_ptr: int) -> None:
+        _check(self.lib, self.lib.rn_ft_free(self.handle, C.c_void_p(d_ptr)), "rn_ft_free")
+
+    def run(self, d_feats: int, d_labels: int, n_items: int, d_index: int, batch: int, steps: int) -> np.ndarray:
+        """``steps`` Adam steps on device-resident features, labels and ``[steps, batch]`` int32 indices (``rn_ft_run``); returns each
+        step's loss (before its update) as float32 ``[steps]``."""
+        losses = np.empty((max(int(steps), 1),), np.float32)
+        _check(self.lib, self.lib.rn_ft_run(self.handle, C.c_void_p(d_feats), C.c_void_p(d_labels), int(n_items), C.c_void_p(d_index),
+                                            int(batch), int(steps), losses.ctypes.data), "rn_ft_run")
+        return losses[:steps]
+
+    def run_host(self, feats: np.ndarray, labels, index, batch: Optional[int] = None) -> np.ndarray:
+        """``run`` for host arrays: uploads them, runs ``index.shape[0]`` steps, frees them."""
+        feats = np.ascontiguousarray(feats, np.float32)
+        index = np.ascontiguousarray(index, np.int32)
+        if index.ndim == 1:
+            index = index.reshape(-1, int(batch))
+        d = [self.upload(feats), self.upload(np.ascontiguousarray(labels, np.int32)), self.upload(index)]
+        try:
+            return self.run(d[0], d[1], feats.shape[0], d[2], index.shape[1], index.shape[0])
+        finally:
+            for p in d:
+                self.free(p)
+
+    def eval(self, d_feats: int, n: int, d_labels: Optional[int] = None):
+        """Forward only from the current parameters (``rn_ft_eval``): ``(mean_loss or None, probs [n, C], ids [n])``."""
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        loss = C.c_float(0)
+        _check(self.lib, self.lib.rn_ft_eval(self.handle, C.c_void_p(d_feats), C.c_void_p(d_labels) if d_labels else None, int(n),
+                                             C.byref(loss) if d_labels else None, probs.ctypes.data, ids.ctypes.data), "rn_ft_eval")
+        return (float(loss.value) if d_labels else None), probs, ids
+
+    def eval_host(self, feats: np.ndarray, labels=None):
+        feats = np.ascontiguousarray(feats, np.float32)
+        d = [self.upload(feats)] + ([self.upload(np.ascontiguousarray(labels, np.int32))] if labels is not None else [])
+        try:
+            return self.eval(d[0], feats.shape[0], d[1] if labels is not None else None)
+        finally:
+            for p in d:
+                self.free(p)
+
+    def variables(self) -> List[Tuple[str, int]]:
+        """``[(checkpoint name, element count)]`` of the trained variables, in the trainer's order (``rn_ft_var_info``)."""
+        if self._vars is None:
+            n = self.lib.rn_ft_var_count(self.handle)
+            _check(self.lib, min(n, 0), "rn_ft_var_count")
+            out = []
+            for i in range(n):
+                name, cnt = C.create_string_buffer(64), C.c_int64(0)
+                _check(self.lib, self.lib.rn_ft_var_info(self.handle, i, name, 64, C.byref(cnt)), "rn_ft_var_info")
+                out.append((name.value.decode(), int(cnt.value)))
+            self._vars = out
+        return self._vars
+
+    def read(self, what: int = RN_FT_PARAM) -> Dict[str, np.ndarray]:
+        """Every trained variable's parameters, last gradient or Adam slot (``rn_ft_read``), in its checkpoint shape."""
+        shapes = self.graph.variable_shapes()
+        out = {}
+        for i, (name, cnt) in enumerate(self.variables()):
+            a = np.empty((cnt,), np.float32)
+            _check(self.lib, self.lib.rn_ft_read(self.handle, int(what), i, a.ctypes.data, a.size), "rn_ft_read")
+            out[name] = a.reshape(shapes[name])
+        return out
+
+    def step_count(self) -> int:
+        return int(self.lib.rn_ft_step_count(self.handle))
+
+    def last_run_ms(self) -> float:
+        """Device time of the last ``run``'s step loop (``rn_ft_last_run_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_ft_last_run_ms(self.handle, C.byref(ms)), "rn_ft_last_run_ms")
+        return float(ms.value)
 
 
 class PinnedArray:

@@ -904,6 +904,103 @@ extern "C" int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, in
     return gradcam_device(h, d_bgr_nhwc, nullptr, n, d_class_ids, layer6, d_cam, d_alpha, d_probs, d_ids);
 }
 
+// ---- feature read-out for the fine-tuning cache (rn_finetune.hip): a forward pass that leaves s7.bn in HBM, widened to float32
+namespace {
+int features_check(rn_handle* h, int n, int* node7) {
+    if (!h) {
+        rn_set_error("null handle");
+        return RN_E_INVALID;
+    }
+    if (h->bnstats) {
+        rn_set_error("rn_features: the cached features are those of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)");
+        return RN_E_STATE;
+    }
+    if (const char* why = rn_gradcam_unsupported(h)) {
+        rn_set_error("rn_features: not supported on this graph (%s)", why);
+        return RN_E_INVALID;
+    }
+    if (n < 1 || n > h->max_batch) {
+        rn_set_error("rn_features: n = %d out of range (1..%d)", n, h->max_batch);
+        return RN_E_RANGE;
+    }
+    int node6;
+    rn_gradcam_layers(h, &node6, node7);
+    return RN_OK;
+}
+
+int features_device(rn_handle* h, const uint8_t* d_bgr, int n, int node7, float* d_feat) {
+    h->split_backend = true;
+    int rc = rn_forward_u8_device(h, d_bgr, n, h->d_probs, h->d_ids);
+    h->split_backend = false;
+    if (rc != RN_OK) return rc;
+    const NodeBuf& nb = h->nodes[node7];
+    bool elided = false;
+    for (int s = 0; s < static_cast<int>(h->stages.size()); ++s)
+        elided |= fused_mode(h) && h->stages[s].node_bn == node7 && rn_fused_stage_elided(h, s);
+    if (!nb.ptr || elided || h->node_perm.count(node7)) {
+        rn_set_error("rn_features: the forward pass did not write %s in the reference's layout", nb.info.name);
+        return RN_E_STATE;
+    }
+    DeviceGuard guard(h->device);
+    const int64_t total = static_cast<int64_t>(n) * nb.info.h * nb.info.w * nb.info.c;
+    if (nb.dtype == RN_DTYPE_F32) {
+        RN_HIP(hipMemcpyAsync(d_feat, nb.ptr, static_cast<size_t>(total) * 4, hipMemcpyDeviceToDevice, h->stream));
+        return RN_OK;
+    }
+    return rn_launch_convert_to_f32(h->stream, nb.ptr, nb.dtype, d_feat, total);
+}
+}  // namespace
+
+extern "C" int rn_features_shape(const rn_handle* h, int* side, int* channels) {
+    if (!h) {
+        rn_set_error("null handle");
+        return RN_E_INVALID;
+    }
+    if (const char* why = rn_gradcam_unsupported(h)) {
+        rn_set_error("rn_features: not supported on this graph (%s)", why);
+        return RN_E_INVALID;
+    }
+    int node6, node7;
+    rn_gradcam_layers(h, &node6, &node7);
+    if (side) *side = h->nodes[node7].info.h;
+    if (channels) *channels = h->nodes[node7].info.c;
+    return RN_OK;
+}
+
+extern "C" int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, float* d_feat) {
+    int node7 = -1;
+    int rc = features_check(h, n, &node7);
+    if (rc != RN_OK) return rc;
+    if (!d_bgr_nhwc || !d_feat) {
+        rn_set_error("null buffer");
+        return RN_E_INVALID;
+    }
+    return features_device(h, d_bgr_nhwc, n, node7, d_feat);
+}
+
+extern "C" int rn_features_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, float* feat) {
+    int node7 = -1;
+    int rc = features_check(h, n, &node7);
+    if (rc != RN_OK) return rc;
+    if (!bgr_nhwc || !feat) {
+        rn_set_error("null buffer");
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(h->device);
+    const rn_node_info& li = h->nodes[node7].info;
+    const size_t per = static_cast<size_t>(li.h) * li.w * li.c;
+    if (!h->d_feat) {
+        void* p = nullptr;
+        if ((rc = dev_alloc(h, static_cast<size_t>(h->max_batch) * per * 4, &p)) != RN_OK) return rc;
+        h->d_feat = static_cast<float*>(p);
+    }
+    RN_HIP(hipMemcpyAsync(h->d_in_u8, bgr_nhwc, static_cast<size_t>(n) * h->im_side * h->im_side * 3, hipMemcpyHostToDevice, h->stream));
+    if ((rc = features_device(h, h->d_in_u8, n, node7, h->d_feat)) != RN_OK) return rc;
+    RN_HIP(hipMemcpyAsync(feat, h->d_feat, static_cast<size_t>(n) * per * 4, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipStreamSynchronize(h->stream));
+    return RN_OK;
+}
+
 // ---- two-slot host pipeline: the upload of batch k+1 overlaps the forward pass of batch k
 extern "C" int rn_submit_u8(rn_handle* h, const uint8_t* bgr, int n, int slot) {
     if (!h || !bgr || slot < 0 || slot > 1) {

@@ -1,0 +1,1090 @@
+// Fine-tuning of the last two conv stages and the dense head on cached features (rn_ft_*), and the feature read-out that fills
+// the cache (rn_features_*).
+//
+// Frozen: stages 0-7.  Everything behind x7 = s7.bn depends on x7 alone (stage 9's skip starts there), so a training set is a
+// resident float32 array [n_items, S7, S7, 16] and a step never runs the trunk.
+//
+// Trained variables, in this order (checkpoint names; 19 for the reference graph): conv 8's kernel, its BN's gamma and beta; conv 9's
+// kernel, its BN's gamma and beta, gamma and beta of the BN behind the residual add; per dense block its kernel and its BN's gamma and
+// beta; the last dense layer's kernel and bias.  moving_mean / moving_variance are read and never written: every BN is the inference
+// BN y = (x - mean) rsqrt(var + eps) gamma + beta with trainable gamma and beta (the reference's shipped training configuration,
+// train.py:40-41: COMPUTE_BN_MEAN_VAR = False, UPDATE_BATCHNORM_MOVING_VARS = False).  No dropout.
+//
+// Forward, per item, float32:  stage 8 (conv 3x3 VALID -> ReLU6 -> avg-pool 4/2 -> BN), stage 9 (the same, + legacy-bilinear
+// resize of x7 -> add -> BN), flatten, dense blocks x @ W [+ b] -> ReLU6 -> [BN]; the last block's ReLU6 is applied to the logits
+// as well (network.py:237, dense_block): r = relu6(z).
+// Loss (network.py:56-59):  L = mean_i CE(softmax(r_i), y_i) + l2_coeff * sum_v sum(v^2) / 2 over the TRAINED variables; the
+// frozen variables' share of the reference's regulariser is a constant the gradient does not see and is left out.
+// Gradients, TensorFlow's rules as rn_gradcam.hip states them: Relu6Grad passes strictly inside (0, 6) -- here the last ReLU6 is on the
+// path: dL/dz = (softmax - onehot) where 0 < z < 6 --, AvgPool spreads g / 16 over each window, Add feeds both inputs (the resize
+// branch ends in x7: no gradient is needed there), BN: d gamma = sum g (x - mean) rsqrt(var + eps), d beta = sum g,
+// dx = g gamma rsqrt(var + eps); conv: dW[ky, kx, ci, co] = sum_p in[p + k, ci] dconv[p, co]; MatMul: dW = X^T G.
+// Adam (tf.train.AdamOptimizer; slots zero at rn_ft_create), all float32 on the device:
+//   g = dL/dv (L2 term included);  m += (g - m)(1 - beta1);  v += (g^2 - v)(1 - beta2);  var -= lr_t m / (sqrt(v) + eps)
+//   lr_t = lr(step) sqrt(1 - beta2^t) / (1 - beta1^t),  lr(step) = learn_rate * decay_rate^(step / num_steps)  (network.py:36, no
+//   staircase); step counts from start_step, t from 1 at the trainer's first step.  lr_t is formed on the host in float64 and
+//   handed to the launch as one float32.
+//
+// Two launches per step, enqueued back to back on the trainer's stream (no graph capture; one synchronisation per rn_ft_run):
+//   ft_item_kernel    one workgroup per item of the minibatch (modelled on gc_tail_kernel): conv weights and BN tables in LDS,
+//                     intermediates in a per-item float32 workspace, the item's feature read from the resident cache through the
+//                     index.  Forward, softmax and the item's CE term, then the adjoint; writes the item's partials of every
+//                     gradient: dW8, dW9 (plain FMAs: 144 (tap, cin) pairs x 3 row groups of threads, 16 cout accumulators each,
+//                     one conv row summed apart before it joins the total), the BN d gamma / d beta terms, and for every dense
+//                     layer its input vector and its output-gradient vector (no per-item outer products).  Workgroup 0 also sums
+//                     v^2 over the parameters for the loss.
+//   ft_update_kernel  one thread per parameter: sums the partials over the items in index order (dense kernels: X^T G over the
+//                     items) -- no floating-point atomics, the same minibatch gives the same bits --, divides by n, adds
+//                     l2_coeff v, applies Adam to the float32 master copy, keeps the gradient readable, and writes the step's loss
+//                     (evaluated before the update) into its slot of a device array.
+// rn_ft_eval runs the item kernel forward-only (loss, softmax, argmax) from the current master parameters.
+// The loss's scalar sums (item CE terms, sum v^2, the log-sum-exp of num_classes values) are float64; everything else is float32.
+#include "rn_internal.h"
+#include "rn_stage.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace rnk;
+
+namespace {
+
+constexpr int FT_C = 16;             // channels of the last block
+constexpr int FT_NT = 512;           // threads of the item workgroup
+constexpr int FT_HMAX = 64;          // widest dense layer (rn_tail_graph_reason enforces nout <= 64)
+constexpr int FT_W = 9 * FT_C * FT_C;
+constexpr int FT_WG_PAIRS = 9 * FT_C;  // (tap, cin) pairs of a weight gradient
+constexpr int FT_WG_GROUPS = 3;        // row groups (FT_WG_PAIRS * FT_WG_GROUPS <= FT_NT)
+constexpr int FT_MAX_VARS = 8 + 3 * RN_MAX_DENSE;
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+struct FtItemArgs {
+    const float* feats;              // [n_items, S7, S7, 16]
+    const int32_t* labels;           // [n_items] (eval: may be null)
+    const int32_t* index;            // item of workgroup b = index[base + b]; null: base + b
+    int64_t base;
+    int S7, C8, S8, C9, S9;
+    const float* P;                  // master parameters
+    const float* F;                  // frozen [mean | rsqrt(var + eps)] per BN
+    int o_w8, o_g8, o_b8, o_w9, o_g9, o_b9, o_g9b, o_b9b;
+    int f_bn8, f_bn9, f_bn9b;
+    const int32_t* rlo;              // legacy bilinear tables S7 -> S9
+    const int32_t* rhi;
+    const float* rlerp;
+    int n_dense, nc;
+    int nin[RN_MAX_DENSE], nout[RN_MAX_DENSE];
+    int o_dw[RN_MAX_DENSE], o_db[RN_MAX_DENSE], o_dg[RN_MAX_DENSE], o_dbeta[RN_MAX_DENSE], f_dbn[RN_MAX_DENSE];   // -1: absent
+    float* ws;                       // per-workgroup workspace
+    int64_t ws_item, off_c8, off_xh8, off_s8, off_gs8, off_c9, off_xh9, off_xh9b, off_fl, off_gfl;
+    float* part;                     // per-workgroup partials record
+    int64_t rec;
+    int p_w8, p_w9, p_bn8, p_bn9, p_bn9b;
+    int p_x[RN_MAX_DENSE], p_gz[RN_MAX_DENSE], p_dg[RN_MAX_DENSE], p_dbeta[RN_MAX_DENSE];
+    double* item_loss;               // [batch] CE term of the workgroup's item
+    double* l2sum;                   // sum v^2 over the parameter slab (workgroup 0; null: not wanted)
+    int n_param;                     // floats of the parameter slab
+    float* probs;                    // eval: [batch, nc], one chunk's staging (null in training)
+    int64_t* ids;                    // eval: [batch]
+};
+
+__device__ __forceinline__ bool relu6_passes(float v) { return v > 0.f && v < 6.f; }
+
+// pooled rows (or columns) whose 4 x 4 / stride-2 window covers conv row Y
+__device__ __forceinline__ void pool_span(int Y, int So, int* lo, int* hi) {
+    *lo = Y < 3 ? 0 : (Y - 2) / 2;
+    *hi = min(So - 1, Y / 2);
+}
+
+// conv3x3 VALID 16 -> 16 pre-activation of one output element: in [S][S][16] float32 (global), w [9][16][16] (LDS)
+__device__ __forceinline__ float conv16_at(const float* in, int S, const float* w, int y, int x, int co) {
+    float acc = 0.f;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) {
+            const f32x4* px = reinterpret_cast<const f32x4*>(in + (static_cast<int64_t>(y + ky) * S + x + kx) * FT_C);
+            const float* wt = w + (ky * 3 + kx) * FT_C * FT_C + co;
+#pragma unroll
+            for (int c4 = 0; c4 < FT_C / 4; ++c4) {
+                const f32x4 v = px[c4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc = fmaf(v[q], wt[(4 * c4 + q) * FT_C], acc);
+            }
+        }
+    return acc;
+}
+
+__device__ __forceinline__ float dot16(const float* g, const float* w, float t) {
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+#pragma unroll
+    for (int c4 = 0; c4 < FT_C / 4; ++c4) {
+        const f32x4 v = g4[c4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t = fmaf(v[q], w[4 * c4 + q], t);
+    }
+    return t;
+}
+
+// sum of `val` over the 32 threads that share channel tid & 15, in a fixed order; the result is valid for tid < 16
+__device__ __forceinline__ float channel_sum(float val, float* red, int tid) {
+    red[tid] = val;
+    __syncthreads();
+    float t = 0.f;
+    if (tid < FT_C)
+        for (int part = 0; part < FT_NT / FT_C; ++part) t += red[part * FT_C + tid];
+    __syncthreads();
+    return t;
+}
+
+// dW[k][ci][co] = sum_p in[p + k][ci] dout[p][co] over the Co x Co positions of a VALID 3x3 conv: in [S][S][16], dout [Co][Co][16]
+// (both global float32), out [9][16][16].  Thread (pair, group): one (tap, cin) pair, conv rows group, group + 3, ...; every row is
+// summed apart and then added to the total (two-level sum: the error grows with sqrt(Co) + sqrt(Co / 3), not with Co^2 / 3).
+__device__ __forceinline__ void wgrad16(const float* in, int S, const float* dout, int Co, float* out, float* red3, int tid) {
+    if (tid < FT_WG_PAIRS * FT_WG_GROUPS) {
+        const int pair = tid % FT_WG_PAIRS, grp = tid / FT_WG_PAIRS;
+        const int k = pair / FT_C, ci = pair % FT_C, ky = k / 3, kx = k % 3;
+        float acc[FT_C];
+#pragma unroll
+        for (int q = 0; q < FT_C; ++q) acc[q] = 0.f;
+        for (int y = grp; y < Co; y += FT_WG_GROUPS) {
+            float row[FT_C];
+#pragma unroll
+            for (int q = 0; q < FT_C; ++q) row[q] = 0.f;
+            const float* pin = in + (static_cast<int64_t>(y + ky) * S + kx) * FT_C + ci;
+            const f32x4* pd = reinterpret_cast<const f32x4*>(dout + static_cast<int64_t>(y) * Co * FT_C);
+            for (int x = 0; x < Co; ++x) {
+                const float a = pin[x * FT_C];
+#pragma unroll
+                for (int c4 = 0; c4 < FT_C / 4; ++c4) {
+                    const f32x4 d = pd[x * (FT_C / 4) + c4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) row[4 * c4 + q] = fmaf(a, d[q], row[4 * c4 + q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < FT_C; ++q) acc[q] += row[q];
+        }
+#pragma unroll
+        for (int q = 0; q < FT_C; ++q) red3[grp * FT_W + pair * FT_C + q] = acc[q];
+    }
+    __syncthreads();
+    for (int o = tid; o < FT_W; o += FT_NT) out[o] = (red3[o] + red3[FT_W + o]) + red3[2 * FT_W + o];
+    __syncthreads();
+}
+
+template <bool TRAIN>
+__global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
+    __shared__ float w8[FT_W];
+    __shared__ float w9[FT_W];
+    __shared__ float tab[3 * 4 * FT_C];                  // bn8 | bn9 | bn9b, each [mean | rsq | gamma | beta]
+    __shared__ float hx[RN_MAX_DENSE][FT_HMAX];           // input of dense layer d (d >= 1)
+    __shared__ float hxh[RN_MAX_DENSE][FT_HMAX];          // normalised ReLU6 output of dense layer d, before gamma and beta
+    __shared__ float hmm[RN_MAX_DENSE][FT_HMAX];          // pre-activation of dense layer d
+    __shared__ float hg[2][FT_HMAX];
+    __shared__ float red[FT_NT];
+    __shared__ float red3[TRAIN ? FT_WG_GROUPS * FT_W : 1];
+    __shared__ double dred[TRAIN ? FT_NT : 1];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int S7 = a.S7, C8 = a.C8, S8 = a.S8, C9 = a.C9, S9 = a.S9;
+    const int64_t item = a.index ? static_cast<int64_t>(a.index[a.base + b]) : a.base + b;
+    const float* x7 = a.feats + item * S7 * S7 * FT_C;
+    float* wsi = a.ws + b * a.ws_item;
+    float* c8 = wsi + a.off_c8;
+    float* xh8 = wsi + a.off_xh8;
+    float* s8 = wsi + a.off_s8;
+    float* c9 = wsi + a.off_c9;
+    float* xh9 = wsi + a.off_xh9;
+    float* xh9b = wsi + a.off_xh9b;
+    float* fl = wsi + a.off_fl;
+    const float* P = a.P;
+    const float* F = a.F;
+    for (int i = tid; i < FT_W; i += FT_NT) {
+        w8[i] = P[a.o_w8 + i];
+        w9[i] = P[a.o_w9 + i];
+    }
+    if (tid < 2 * FT_C) {
+        tab[tid] = F[a.f_bn8 + tid];
+        tab[64 + tid] = F[a.f_bn9 + tid];
+        tab[128 + tid] = F[a.f_bn9b + tid];
+    } else if (tid < 3 * FT_C) {
+        const int c = tid - 2 * FT_C;
+        tab[32 + c] = P[a.o_g8 + c];
+        tab[48 + c] = P[a.o_b8 + c];
+        tab[96 + c] = P[a.o_g9 + c];
+        tab[112 + c] = P[a.o_b9 + c];
+        tab[160 + c] = P[a.o_g9b + c];
+        tab[176 + c] = P[a.o_b9b + c];
+    }
+    __syncthreads();
+    // ---- forward
+    for (int i = tid; i < C8 * C8 * FT_C; i += FT_NT) {
+        const int co = i & 15, p = i >> 4;
+        c8[i] = conv16_at(x7, S7, w8, p / C8, p % C8, co);
+    }
+    __syncthreads();
+    for (int i = tid; i < S8 * S8 * FT_C; i += FT_NT) {
+        const int co = i & 15, p = i >> 4, y = p / S8, x = p % S8;
+        float t = 0.f;
+        for (int ky = 0; ky < 4; ++ky)
+            for (int kx = 0; kx < 4; ++kx) t += relu6f(c8[((2 * y + ky) * C8 + 2 * x + kx) * FT_C + co]);
+        const float xh = (t * (1.0f / 16.0f) - tab[co]) * tab[16 + co];
+        if (TRAIN) xh8[i] = xh;
+        s8[i] = fmaf(xh, tab[32 + co], tab[48 + co]);
+    }
+    __syncthreads();
+    for (int i = tid; i < C9 * C9 * FT_C; i += FT_NT) {
+        const int co = i & 15, p = i >> 4;
+        c9[i] = conv16_at(s8, S8, w9, p / C9, p % C9, co);
+    }
+    __syncthreads();
+    for (int i = tid; i < S9 * S9 * FT_C; i += FT_NT) {
+        const int co = i & 15, p = i >> 4, y = p / S9, x = p % S9;
+        float t = 0.f;
+        for (int ky = 0; ky < 4; ++ky)
+            for (int kx = 0; kx < 4; ++kx) t += relu6f(c9[((2 * y + ky) * C9 + 2 * x + kx) * FT_C + co]);
+        const float xh = (t * (1.0f / 16.0f) - tab[64 + co]) * tab[80 + co];
+        const float bv = fmaf(xh, tab[96 + co], tab[112 + co]);
+        const int ylo = a.rlo[y], yhi = a.rhi[y], xlo = a.rlo[x], xhi = a.rhi[x];
+        const float yl = a.rlerp[y], xl = a.rlerp[x];
+        const float tl = x7[(ylo * S7 + xlo) * FT_C + co], tr = x7[(ylo * S7 + xhi) * FT_C + co];
+        const float bl = x7[(yhi * S7 + xlo) * FT_C + co], br = x7[(yhi * S7 + xhi) * FT_C + co];
+        const float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
+        const float xhb = ((bv + (top + (bot - top) * yl)) - tab[128 + co]) * tab[144 + co];
+        if (TRAIN) {
+            xh9[i] = xh;
+            xh9b[i] = xhb;
+        }
+        fl[i] = fmaf(xhb, tab[160 + co], tab[176 + co]);
+    }
+    __syncthreads();
+    // ---- dense head forward: each layer's dot products split over FT_NT / 64 groups of k, summed in a fixed order
+    constexpr int NG = FT_NT / FT_HMAX;
+    for (int d = 0; d < a.n_dense; ++d) {
+        const int nin = a.nin[d], nout = a.nout[d];
+        const float* xin = d == 0 ? fl : hx[d];
+        const float* W = P + a.o_dw[d];
+        const int j = tid % FT_HMAX, gi = tid / FT_HMAX;
+        const int per = (nin + NG - 1) / NG;
+        float v = 0.f;
+        if (j < nout)
+            for (int k = gi * per; k < min(nin, (gi + 1) * per); ++k) v = fmaf(xin[k], W[k * nout + j], v);
+        red[tid] = v;
+        __syncthreads();
+        if (tid < nout) {
+            float t = 0.f;
+            for (int g = 0; g < NG; ++g) t += red[g * FT_HMAX + tid];
+            if (a.o_db[d] >= 0) t += P[a.o_db[d] + tid];
+            hmm[d][tid] = t;
+            if (d + 1 < a.n_dense) {
+                float r = relu6f(t);
+                if (a.o_dg[d] >= 0) {
+                    const float xh = (r - F[a.f_dbn[d] + tid]) * F[a.f_dbn[d] + nout + tid];
+                    hxh[d][tid] = xh;
+                    r = fmaf(xh, P[a.o_dg[d] + tid], P[a.o_dbeta[d] + tid]);
+                }
+                hx[d + 1][tid] = r;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- softmax of relu6(z), the item's CE term, dL/dz of the last layer (the 1 / n of the mean is applied by the update kernel)
+    const int L = a.n_dense - 1;
+    if (tid == 0) {
+        const int nc = a.nc;
+        const float* z = hmm[L];
+        float mx = relu6f(z[0]);
+        int best = 0;
+        for (int j = 1; j < nc; ++j) {
+            const float r = relu6f(z[j]);
+            if (r > mx) {
+                mx = r;
+                best = j;
+            }
+        }
+        double se = 0.0;
+        for (int j = 0; j < nc; ++j) se += exp(static_cast<double>(relu6f(z[j])) - static_cast<double>(mx));
+        const int y = a.labels ? a.labels[item] : -1;
+        if (y >= 0) a.item_loss[b] = log(se) - (static_cast<double>(relu6f(z[y])) - static_cast<double>(mx));
+        for (int j = 0; j < nc; ++j) {
+            const float p = static_cast<float>(exp(static_cast<double>(relu6f(z[j])) - static_cast<double>(mx)) / se);
+            if (TRAIN)
+                hg[L & 1][j] = relu6_passes(z[j]) ? p - (j == y ? 1.f : 0.f) : 0.f;
+            else
+                a.probs[b * nc + j] = p;
+        }
+        if (!TRAIN) a.ids[b] = best;
+    }
+    if constexpr (TRAIN) {
+        float* gs8 = wsi + a.off_gs8;
+        float* gfl = wsi + a.off_gfl;
+        float* prt = a.part + b * a.rec;
+        __syncthreads();
+        // ---- adjoint of the head: per layer its input and dL/dz go to the partials; MatMul -> transposed kernel, BN, ReLU6 mask
+        for (int d = L; d >= 0; --d) {
+            const int nin = a.nin[d], nout = a.nout[d];
+            const float* gz = hg[d & 1];
+            const float* xin = d == 0 ? fl : hx[d];
+            const float* W = P + a.o_dw[d];
+            if (tid < nout) prt[a.p_gz[d] + tid] = gz[tid];
+            for (int k = tid; k < nin; k += FT_NT) {
+                prt[a.p_x[d] + k] = xin[k];
+                float v = 0.f;
+                for (int j = 0; j < nout; ++j) v = fmaf(W[k * nout + j], gz[j], v);
+                if (d == 0) {
+                    gfl[k] = v;
+                } else {
+                    if (a.o_dg[d - 1] >= 0) {
+                        prt[a.p_dg[d - 1] + k] = v * hxh[d - 1][k];
+                        prt[a.p_dbeta[d - 1] + k] = v;
+                        v *= P[a.o_dg[d - 1] + k] * F[a.f_dbn[d - 1] + nin + k];
+                    }
+                    hg[(d - 1) & 1][k] = relu6_passes(hmm[d - 1][k]) ? v : 0.f;
+                }
+            }
+            __syncthreads();
+        }
+        // ---- stage 9: the BN behind the add, the add (only the conv branch is followed), the first BN; gfl becomes dL/d pool9
+        {
+            const int c = tid & 15;
+            float dg2 = 0.f, db2 = 0.f, dg1 = 0.f, db1 = 0.f;
+            const float k2 = tab[160 + c] * tab[144 + c], k1 = tab[96 + c] * tab[80 + c];
+            for (int p = tid >> 4; p < S9 * S9; p += FT_NT / FT_C) {
+                const int i = p * FT_C + c;
+                const float g = gfl[i];
+                dg2 = fmaf(g, xh9b[i], dg2);
+                db2 += g;
+                const float ga = g * k2;
+                dg1 = fmaf(ga, xh9[i], dg1);
+                db1 += ga;
+                gfl[i] = ga * k1;
+            }
+            float t;
+            t = channel_sum(dg2, red, tid);
+            if (tid < FT_C) prt[a.p_bn9b + tid] = t;
+            t = channel_sum(db2, red, tid);
+            if (tid < FT_C) prt[a.p_bn9b + FT_C + tid] = t;
+            t = channel_sum(dg1, red, tid);
+            if (tid < FT_C) prt[a.p_bn9 + tid] = t;
+            t = channel_sum(db1, red, tid);
+            if (tid < FT_C) prt[a.p_bn9 + FT_C + tid] = t;
+        }
+        // ---- pool 9 adjoint and conv 9's ReLU6 mask, in place over c9: dL/dconv9
+        for (int i = tid; i < C9 * C9 * FT_C; i += FT_NT) {
+            const int co = i & 15, p = i >> 4, Y = p / C9, X = p % C9;
+            int ylo, yhi, xlo, xhi;
+            pool_span(Y, S9, &ylo, &yhi);
+            pool_span(X, S9, &xlo, &xhi);
+            float t = 0.f;
+            for (int y = ylo; y <= yhi; ++y)
+                for (int x = xlo; x <= xhi; ++x) t += gfl[(y * S9 + x) * FT_C + co];
+            c9[i] = relu6_passes(c9[i]) ? t * (1.0f / 16.0f) : 0.f;
+        }
+        __syncthreads();
+#ifndef FT_NO_WGRAD   // (measurement arm: csrc/build.sh RN_VARIANT_FLAGS=-DFT_NO_WGRAD times the step without the two weight gradients)
+        wgrad16(s8, S8, c9, C9, prt + a.p_w9, red3, tid);
+#endif
+        // ---- conv 9 adjoint -> dL/ds8.bn
+        for (int i = tid; i < S8 * S8 * FT_C; i += FT_NT) {
+            const int ci = i & 15, p = i >> 4, Y = p / S8, X = p % S8;
+            float t = 0.f;
+            for (int ky = 0; ky < 3; ++ky) {
+                const int y = Y - ky;
+                if (y < 0 || y >= C9) continue;
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int x = X - kx;
+                    if (x < 0 || x >= C9) continue;
+                    t = dot16(c9 + (y * C9 + x) * FT_C, w9 + ((ky * 3 + kx) * FT_C + ci) * FT_C, t);
+                }
+            }
+            gs8[i] = t;
+        }
+        __syncthreads();
+        // ---- stage 8's BN; gs8 becomes dL/d pool8
+        {
+            const int c = tid & 15;
+            float dg = 0.f, db = 0.f;
+            const float k1 = tab[32 + c] * tab[16 + c];
+            for (int p = tid >> 4; p < S8 * S8; p += FT_NT / FT_C) {
+                const int i = p * FT_C + c;
+                const float g = gs8[i];
+                dg = fmaf(g, xh8[i], dg);
+                db += g;
+                gs8[i] = g * k1;
+            }
+            float t;
+            t = channel_sum(dg, red, tid);
+            if (tid < FT_C) prt[a.p_bn8 + tid] = t;
+            t = channel_sum(db, red, tid);
+            if (tid < FT_C) prt[a.p_bn8 + FT_C + tid] = t;
+        }
+        for (int i = tid; i < C8 * C8 * FT_C; i += FT_NT) {
+            const int co = i & 15, p = i >> 4, Y = p / C8, X = p % C8;
+            int ylo, yhi, xlo, xhi;
+            pool_span(Y, S8, &ylo, &yhi);
+            pool_span(X, S8, &xlo, &xhi);
+            float t = 0.f;
+            for (int y = ylo; y <= yhi; ++y)
+                for (int x = xlo; x <= xhi; ++x) t += gs8[(y * S8 + x) * FT_C + co];
+            c8[i] = relu6_passes(c8[i]) ? t * (1.0f / 16.0f) : 0.f;
+        }
+        __syncthreads();
+#ifndef FT_NO_WGRAD
+        wgrad16(x7, S7, c8, C8, prt + a.p_w8, red3, tid);
+#endif
+        // ---- sum v^2 over the parameter slab (its padding is zero), for the loss's L2 term
+        if (b == 0 && a.l2sum) {
+            double t = 0.0;
+            for (int i = tid; i < a.n_param; i += FT_NT) t += static_cast<double>(P[i]) * static_cast<double>(P[i]);
+            dred[tid] = t;
+            __syncthreads();
+            for (int s = FT_NT / 2; s > 0; s >>= 1) {
+                if (tid < s) dred[tid] += dred[tid + s];
+                __syncthreads();
+            }
+            if (tid == 0) *a.l2sum = dred[0];
+        }
+    }
+}
+
+// how the update kernel forms one variable's gradient from the items' partials
+enum { FT_SUM = 0, FT_OUTER = 1 };
+struct FtVarDev {
+    int off, count;                  // in the parameter slab
+    int kind;
+    int src;                         // FT_SUM: offset in the partials record;  FT_OUTER: the layer's input vector
+    int src_g, nout;                 // FT_OUTER: the layer's dL/dz vector and its length
+};
+
+struct FtUpdateArgs {
+    int nvars, total;
+    FtVarDev v[FT_MAX_VARS];
+    float *P, *G, *M, *V;
+    const float* part;
+    int64_t rec;
+    int n;
+    float l2, lr_t, omb1, omb2, eps;   // omb = 1 - beta, formed in float64 on the host
+    const double* item_loss;
+    const double* l2sum;
+    float* loss_out;                 // this step's slot
+};
+
+__global__ __launch_bounds__(256) void ft_update_kernel(const FtUpdateArgs a) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e == 0) {
+        double s = 0.0;
+        for (int i = 0; i < a.n; ++i) s += a.item_loss[i];
+        *a.loss_out = static_cast<float>(s / a.n + 0.5 * static_cast<double>(a.l2) * *a.l2sum);
+    }
+    if (e >= a.total) return;
+    int vi = -1;
+    for (int i = 0; i < a.nvars; ++i)
+        if (e >= a.v[i].off && e < a.v[i].off + a.v[i].count) vi = i;
+    if (vi < 0) return;                // padding between two variables
+    const FtVarDev var = a.v[vi];
+    const int le = e - var.off;
+    float s = 0.f;
+    if (var.kind == FT_SUM) {
+        const float* p = a.part + var.src + le;
+#pragma unroll 8
+        for (int i = 0; i < a.n; ++i) s += p[i * a.rec];             // (the loads do not depend on the sum: eight are in flight)
+    } else {
+        const float* px = a.part + var.src + le / var.nout;
+        const float* pg = a.part + var.src_g + le % var.nout;
+#pragma unroll 8
+        for (int i = 0; i < a.n; ++i) s = fmaf(px[i * a.rec], pg[i * a.rec], s);
+    }
+    const float p = a.P[e];
+    const float g = fmaf(a.l2, p, s / static_cast<float>(a.n));
+    float m = a.M[e], v = a.V[e];
+    m += (g - m) * a.omb1;
+    v += (g * g - v) * a.omb2;
+    a.G[e] = g;
+    a.M[e] = m;
+    a.V[e] = v;
+    a.P[e] = p - a.lr_t * m / (sqrtf(v) + a.eps);
+}
+
+struct FtVarHost {
+    std::string name;
+    int off = 0, count = 0;
+};
+
+}  // namespace
+
+struct rn_ft {
+    int device = 0, max_batch = 0, nc = 0;
+    rn_ft_config cfg{};
+    hipStream_t stream = nullptr;
+    int S7 = 0, C8 = 0, S8 = 0, C9 = 0, S9 = 0;
+    std::vector<FtVarHost> vars;
+    int n_param = 0;                               // floats of the parameter slab (every variable padded to 4 floats)
+    FtItemArgs item{};                             // everything but the per-call fields
+    FtUpdateArgs upd{};
+    float *d_P = nullptr, *d_G = nullptr, *d_M = nullptr, *d_V = nullptr, *d_F = nullptr, *d_rlerp = nullptr;
+    int32_t* d_rtab = nullptr;
+    float *d_ws = nullptr, *d_part = nullptr;
+    double *d_item_loss = nullptr, *d_l2sum = nullptr;
+    float* d_losses = nullptr;                     // [losses_cap]
+    int losses_cap = 0;
+    float* d_probs = nullptr;                      // eval staging [max_batch, nc]
+    int64_t* d_ids = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the step loop of the last rn_ft_run
+    bool timed = false;
+    int64_t steps_done = 0;                        // t of the next step is steps_done + 1; global step = start_step + steps_done
+    std::vector<void*> allocs;                     // trainer-owned device memory (freed by rn_ft_destroy)
+    std::vector<void*> user;                       // rn_ft_upload buffers not yet freed
+};
+
+namespace {
+
+int ft_alloc(rn_ft* ft, size_t bytes, void** out) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
+    if (e != hipSuccess) {
+        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        (void)hipGetLastError();
+        return RN_E_NOMEM;
+    }
+    ft->allocs.push_back(p);
+    *out = p;
+    return RN_OK;
+}
+
+template <typename T>
+int ft_upload(rn_ft* ft, const T* src, size_t count, T** out) {
+    void* p = nullptr;
+    int rc = ft_alloc(ft, count * sizeof(T), &p);
+    if (rc != RN_OK) return rc;
+    RN_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *out = static_cast<T*>(p);
+    return RN_OK;
+}
+
+template <typename T>
+int ft_zeroed(rn_ft* ft, size_t count, T** out) {
+    void* p = nullptr;
+    int rc = ft_alloc(ft, count * sizeof(T), &p);
+    if (rc != RN_OK) return rc;
+    RN_HIP(hipMemset(p, 0, count * sizeof(T)));
+    *out = static_cast<T*>(p);
+    return RN_OK;
+}
+
+int ft_build(rn_ft* ft, const rn_weights* w) {
+    const int ns = w->n_stages;
+    const rn_conv_stage &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
+    {
+        int side = w->im_side;
+        std::vector<int> conv(ns), out(ns);
+        for (int i = 0; i < ns; ++i) {
+            conv[i] = side - 2;
+            side = w->stages[i].pool_k ? (conv[i] - w->stages[i].pool_k) / w->stages[i].pool_s + 1 : conv[i];
+            if (conv[i] < 1 || side < 1) {
+                rn_set_error("rn_ft_create: im_side %d is too small for the graph", w->im_side);
+                return RN_E_INVALID;
+            }
+            out[i] = side;
+        }
+        ft->S7 = out[ns - 3];
+        ft->C8 = conv[ns - 2];
+        ft->S8 = out[ns - 2];
+        ft->C9 = conv[ns - 1];
+        ft->S9 = out[ns - 1];
+    }
+    if (w->dense[0].nin != ft->S9 * ft->S9 * FT_C) {
+        rn_set_error("rn_ft_create: the first dense layer takes %d inputs, the last block delivers %d", w->dense[0].nin,
+                     ft->S9 * ft->S9 * FT_C);
+        return RN_E_INVALID;
+    }
+    for (int d = 1; d < w->n_dense; ++d)
+        if (w->dense[d].nin != w->dense[d - 1].nout) {
+            rn_set_error("rn_ft_create: dense layer %d takes %d inputs, the layer before it delivers %d", d, w->dense[d].nin,
+                         w->dense[d - 1].nout);
+            return RN_E_INVALID;
+        }
+    if (w->dense[w->n_dense - 1].nout != w->num_classes) {
+        rn_set_error("rn_ft_create: the last dense layer has %d outputs for %d classes", w->dense[w->n_dense - 1].nout, w->num_classes);
+        return RN_E_INVALID;
+    }
+    const float eps = w->bn_epsilon;
+    std::vector<float> P, F;
+    auto suffix = [](const char* base, int i) { return i == 0 ? std::string(base) : std::string(base) + "_" + std::to_string(i); };
+    auto put_var = [&](const std::string& name, const float* src, int cnt) {
+        FtVarHost v;
+        v.name = name;
+        v.off = static_cast<int>(P.size());
+        v.count = cnt;
+        P.insert(P.end(), src, src + cnt);
+        P.resize((P.size() + 3) & ~static_cast<size_t>(3));
+        ft->vars.push_back(v);
+        return v.off;
+    };
+    auto put_frozen = [&](const float* mean, const float* var, int cnt) {
+        const int off = static_cast<int>(F.size());
+        F.insert(F.end(), mean, mean + cnt);
+        for (int c = 0; c < cnt; ++c) F.push_back(1.0f / sqrtf(var[c] + eps));
+        F.resize((F.size() + 3) & ~static_cast<size_t>(3));
+        return off;
+    };
+    // TensorFlow numbers its variables by creation: conv stage i is conv2d_i; BNs count every stage's and every residual add's
+    int bn_index = 0;
+    for (int i = 0; i < ns - 2; ++i) bn_index += w->stages[i].gamma2 ? 2 : 1;
+    FtItemArgs& a = ft->item;
+    FtUpdateArgs& u = ft->upd;
+    // the partials record of one item
+    int rec = 0;
+    auto take = [&](int cnt) {
+        const int off = rec;
+        rec += (cnt + 3) & ~3;
+        return off;
+    };
+    auto add_upd = [&](int off, int count, int kind, int src, int src_g, int nout) {
+        FtVarDev& v = u.v[u.nvars++];
+        v.off = off;
+        v.count = count;
+        v.kind = kind;
+        v.src = src;
+        v.src_g = src_g;
+        v.nout = nout;
+    };
+    a.p_w8 = take(FT_W);
+    a.p_w9 = take(FT_W);
+    a.p_bn8 = take(2 * FT_C);
+    a.p_bn9 = take(2 * FT_C);
+    a.p_bn9b = take(2 * FT_C);
+    a.o_w8 = put_var(suffix("conv2d", ns - 2) + "/kernel", st8.kernel, FT_W);
+    add_upd(a.o_w8, FT_W, FT_SUM, a.p_w8, 0, 0);
+    a.o_g8 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st8.gamma, FT_C);
+    add_upd(a.o_g8, FT_C, FT_SUM, a.p_bn8, 0, 0);
+    a.o_b8 = put_var(suffix("batch_normalization", bn_index) + "/beta", st8.beta, FT_C);
+    add_upd(a.o_b8, FT_C, FT_SUM, a.p_bn8 + FT_C, 0, 0);
+    a.f_bn8 = put_frozen(st8.mean, st8.variance, FT_C);
+    ++bn_index;
+    a.o_w9 = put_var(suffix("conv2d", ns - 1) + "/kernel", st9.kernel, FT_W);
+    add_upd(a.o_w9, FT_W, FT_SUM, a.p_w9, 0, 0);
+    a.o_g9 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st9.gamma, FT_C);
+    add_upd(a.o_g9, FT_C, FT_SUM, a.p_bn9, 0, 0);
+    a.o_b9 = put_var(suffix("batch_normalization", bn_index) + "/beta", st9.beta, FT_C);
+    add_upd(a.o_b9, FT_C, FT_SUM, a.p_bn9 + FT_C, 0, 0);
+    a.f_bn9 = put_frozen(st9.mean, st9.variance, FT_C);
+    ++bn_index;
+    a.o_g9b = put_var(suffix("batch_normalization", bn_index) + "/gamma", st9.gamma2, FT_C);
+    add_upd(a.o_g9b, FT_C, FT_SUM, a.p_bn9b, 0, 0);
+    a.o_b9b = put_var(suffix("batch_normalization", bn_index) + "/beta", st9.beta2, FT_C);
+    add_upd(a.o_b9b, FT_C, FT_SUM, a.p_bn9b + FT_C, 0, 0);
+    a.f_bn9b = put_frozen(st9.mean2, st9.variance2, FT_C);
+    ++bn_index;
+    a.n_dense = w->n_dense;
+    a.nc = w->num_classes;
+    for (int d = 0; d < w->n_dense; ++d) {
+        const rn_dense_layer& l = w->dense[d];
+        a.nin[d] = l.nin;
+        a.nout[d] = l.nout;
+        a.p_x[d] = take(l.nin);
+        a.p_gz[d] = take(l.nout);
+        a.o_db[d] = a.o_dg[d] = a.o_dbeta[d] = a.f_dbn[d] = a.p_dg[d] = a.p_dbeta[d] = -1;
+        a.o_dw[d] = put_var(suffix("dense", d) + "/kernel", l.kernel, l.nin * l.nout);
+        add_upd(a.o_dw[d], l.nin * l.nout, FT_OUTER, a.p_x[d], a.p_gz[d], l.nout);
+        if (l.bias) {
+            a.o_db[d] = put_var(suffix("dense", d) + "/bias", l.bias, l.nout);
+            add_upd(a.o_db[d], l.nout, FT_SUM, a.p_gz[d], 0, 0);
+        }
+        if (l.gamma) {
+            a.p_dg[d] = take(l.nout);
+            a.p_dbeta[d] = take(l.nout);
+            a.o_dg[d] = put_var(suffix("batch_normalization", bn_index) + "/gamma", l.gamma, l.nout);
+            add_upd(a.o_dg[d], l.nout, FT_SUM, a.p_dg[d], 0, 0);
+            a.o_dbeta[d] = put_var(suffix("batch_normalization", bn_index) + "/beta", l.beta, l.nout);
+            add_upd(a.o_dbeta[d], l.nout, FT_SUM, a.p_dbeta[d], 0, 0);
+            a.f_dbn[d] = put_frozen(l.mean, l.variance, l.nout);
+            ++bn_index;
+        }
+    }
+    ft->n_param = static_cast<int>(P.size());
+    a.rec = rec;
+    // legacy bilinear tables S7 -> S9 (TF-1.13 compute_interpolation_weights, as rn_gradcam_keep)
+    std::vector<int32_t> rt(2 * static_cast<size_t>(ft->S9));
+    std::vector<float> lerp(ft->S9);
+    {
+        const float scale = static_cast<float>(ft->S7) / static_cast<float>(ft->S9);
+        for (int i = 0; i < ft->S9; ++i) {
+            const float src = static_cast<float>(i) * scale;
+            const int32_t lo = static_cast<int32_t>(src);
+            rt[i] = lo;
+            rt[ft->S9 + i] = lo + 1 < ft->S7 - 1 ? lo + 1 : ft->S7 - 1;
+            lerp[i] = src - static_cast<float>(lo);
+        }
+    }
+    int rc;
+    const size_t np = static_cast<size_t>(ft->n_param), nb = static_cast<size_t>(ft->max_batch);
+    if ((rc = ft_upload(ft, P.data(), np, &ft->d_P)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, np, &ft->d_G)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, np, &ft->d_M)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, np, &ft->d_V)) != RN_OK) return rc;
+    if ((rc = ft_upload(ft, F.data(), F.size(), &ft->d_F)) != RN_OK) return rc;
+    if ((rc = ft_upload(ft, rt.data(), rt.size(), &ft->d_rtab)) != RN_OK) return rc;
+    if ((rc = ft_upload(ft, lerp.data(), lerp.size(), &ft->d_rlerp)) != RN_OK) return rc;
+    // per-workgroup workspace, every piece a multiple of 16 floats
+    const int64_t n8 = static_cast<int64_t>(ft->S8) * ft->S8 * FT_C, n9 = static_cast<int64_t>(ft->S9) * ft->S9 * FT_C;
+    a.off_c8 = 0;
+    a.off_xh8 = a.off_c8 + static_cast<int64_t>(ft->C8) * ft->C8 * FT_C;
+    a.off_s8 = a.off_xh8 + n8;
+    a.off_gs8 = a.off_s8 + n8;
+    a.off_c9 = a.off_gs8 + n8;
+    a.off_xh9 = a.off_c9 + static_cast<int64_t>(ft->C9) * ft->C9 * FT_C;
+    a.off_xh9b = a.off_xh9 + n9;
+    a.off_fl = a.off_xh9b + n9;
+    a.off_gfl = a.off_fl + n9;
+    a.ws_item = a.off_gfl + n9;
+    if ((rc = ft_zeroed(ft, nb * a.ws_item, &ft->d_ws)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * static_cast<size_t>(rec), &ft->d_part)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb, &ft->d_item_loss)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, 1, &ft->d_l2sum)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * w->num_classes, &ft->d_probs)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb, &ft->d_ids)) != RN_OK) return rc;
+    a.S7 = ft->S7;
+    a.C8 = ft->C8;
+    a.S8 = ft->S8;
+    a.C9 = ft->C9;
+    a.S9 = ft->S9;
+    a.P = ft->d_P;
+    a.F = ft->d_F;
+    a.rlo = ft->d_rtab;
+    a.rhi = ft->d_rtab + ft->S9;
+    a.rlerp = ft->d_rlerp;
+    a.ws = ft->d_ws;
+    a.part = ft->d_part;
+    a.item_loss = ft->d_item_loss;
+    a.n_param = ft->n_param;
+    u.total = ft->n_param;
+    u.P = ft->d_P;
+    u.G = ft->d_G;
+    u.M = ft->d_M;
+    u.V = ft->d_V;
+    u.part = ft->d_part;
+    u.rec = rec;
+    u.l2 = ft->cfg.l2_coeff;
+    u.omb1 = static_cast<float>(1.0 - static_cast<double>(ft->cfg.beta1));
+    u.omb2 = static_cast<float>(1.0 - static_cast<double>(ft->cfg.beta2));
+    u.eps = ft->cfg.epsilon;
+    u.item_loss = ft->d_item_loss;
+    u.l2sum = ft->d_l2sum;
+    return RN_OK;
+}
+
+double ft_learn_rate(const rn_ft_config& c, int64_t step) {
+    return static_cast<double>(c.learn_rate) * std::pow(static_cast<double>(c.decay_rate), static_cast<double>(step) / c.num_steps);
+}
+
+}  // namespace
+
+extern "C" int rn_ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, rn_ft** out) {
+    if (!w || !cfg || !out || !w->stages || !w->dense) {
+        rn_set_error("rn_ft_create: null argument");
+        return RN_E_INVALID;
+    }
+    *out = nullptr;
+    if (w->n_stages > RN_MAX_STAGES || w->n_dense > RN_MAX_DENSE) {
+        rn_set_error("rn_ft_create: more than %d conv stages or %d dense layers", RN_MAX_STAGES, RN_MAX_DENSE);
+        return RN_E_INVALID;
+    }
+    if (const char* why = rn_tail_graph_reason(w)) {
+        rn_set_error("rn_ft_create: not supported on this graph (%s)", why);
+        return RN_E_INVALID;
+    }
+    if (max_batch < 1) {
+        rn_set_error("rn_ft_create: max_batch = %d", max_batch);
+        return RN_E_INVALID;
+    }
+    if (!(cfg->num_steps >= 1) || !(cfg->decay_rate > 0.f) || !(cfg->learn_rate >= 0.f) || !(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) ||
+        !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f) || !(cfg->epsilon > 0.f) || cfg->start_step < 0 || !(cfg->l2_coeff >= 0.f)) {
+        rn_set_error("rn_ft_create: bad configuration (learn_rate %g, decay_rate %g, num_steps %d, start_step %d, l2_coeff %g, beta1 %g, "
+                     "beta2 %g, epsilon %g)", cfg->learn_rate, cfg->decay_rate, cfg->num_steps, cfg->start_step, cfg->l2_coeff, cfg->beta1,
+                     cfg->beta2, cfg->epsilon);
+        return RN_E_INVALID;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        (void)hipGetLastError();
+        rn_set_error("rn_ft_create: device %d not available (%d visible)", device, ndev);
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(device);
+    rn_ft* ft = new rn_ft();
+    ft->device = device;
+    ft->max_batch = max_batch;
+    ft->nc = w->num_classes;
+    ft->cfg = *cfg;
+    int rc = RN_OK;
+    if (hipStreamCreateWithFlags(&ft->stream, hipStreamNonBlocking) != hipSuccess) {
+        (void)hipGetLastError();
+        rn_set_error("rn_ft_create: hipStreamCreate failed");
+        rc = RN_E_HIP;
+    }
+    if (rc == RN_OK && (hipEventCreate(&ft->ev0) != hipSuccess || hipEventCreate(&ft->ev1) != hipSuccess)) {
+        (void)hipGetLastError();
+        rn_set_error("rn_ft_create: hipEventCreate failed");
+        rc = RN_E_HIP;
+    }
+    if (rc == RN_OK) rc = ft_build(ft, w);
+    if (rc != RN_OK) {
+        rn_ft_destroy(ft);
+        return rc;
+    }
+    *out = ft;
+    return RN_OK;
+}
+
+extern "C" void rn_ft_destroy(rn_ft* ft) {
+    if (!ft) return;
+    DeviceGuard guard(ft->device);
+    if (ft->stream) (void)hipStreamSynchronize(ft->stream);
+    for (void* p : ft->allocs) (void)hipFree(p);
+    for (void* p : ft->user) (void)hipFree(p);
+    if (ft->d_losses) (void)hipFree(ft->d_losses);
+    if (ft->ev0) (void)hipEventDestroy(ft->ev0);
+    if (ft->ev1) (void)hipEventDestroy(ft->ev1);
+    if (ft->stream) (void)hipStreamDestroy(ft->stream);
+    (void)hipGetLastError();
+    delete ft;
+}
+
+extern "C" int rn_ft_upload(rn_ft* ft, const void* src, size_t bytes, void** d_ptr) {
+    if (!ft || !d_ptr || (!src && bytes)) {
+        rn_set_error("rn_ft_upload: null argument");
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(ft->device);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
+    if (e != hipSuccess) {
+        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        (void)hipGetLastError();
+        return RN_E_NOMEM;
+    }
+    if (bytes && (e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        rn_set_error("rn_ft_upload: hipMemcpy failed: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return RN_E_HIP;
+    }
+    ft->user.push_back(p);
+    *d_ptr = p;
+    return RN_OK;
+}
+
+extern "C" int rn_ft_free(rn_ft* ft, void* d_ptr) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    auto it = std::find(ft->user.begin(), ft->user.end(), d_ptr);
+    if (it == ft->user.end()) {
+        rn_set_error("rn_ft_free: not a buffer of rn_ft_upload on this trainer");
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(ft->device);
+    RN_HIP(hipStreamSynchronize(ft->stream));
+    ft->user.erase(it);
+    RN_HIP(hipFree(d_ptr));
+    return RN_OK;
+}
+
+extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
+                         int steps, float* losses) {
+    if (!ft || !d_feats || !d_labels || !d_index || !losses) {
+        rn_set_error("rn_ft_run: null argument");
+        return RN_E_INVALID;
+    }
+    if (batch < 1 || batch > ft->max_batch) {
+        rn_set_error("rn_ft_run: batch = %d out of range (1..%d)", batch, ft->max_batch);
+        return RN_E_RANGE;
+    }
+    if (steps < 1 || n_items < 1) {
+        rn_set_error("rn_ft_run: steps = %d, n_items = %lld", steps, static_cast<long long>(n_items));
+        return RN_E_RANGE;
+    }
+    DeviceGuard guard(ft->device);
+    (void)hipGetLastError();
+    // every index and the label it selects are checked on the host before anything is enqueued
+    {
+        const size_t ni = static_cast<size_t>(steps) * batch;
+        std::vector<int32_t> idx(ni), lab(static_cast<size_t>(n_items));
+        RN_HIP(hipStreamSynchronize(ft->stream));
+        RN_HIP(hipMemcpy(idx.data(), d_index, ni * 4, hipMemcpyDeviceToHost));
+        RN_HIP(hipMemcpy(lab.data(), d_labels, lab.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < ni; ++i) {
+            if (idx[i] < 0 || idx[i] >= n_items) {
+                rn_set_error("rn_ft_run: index[%zu] = %d outside [0, %lld)", i, idx[i], static_cast<long long>(n_items));
+                return RN_E_RANGE;
+            }
+            const int32_t y = lab[idx[i]];
+            if (y < 0 || y >= ft->nc) {
+                rn_set_error("rn_ft_run: label[%d] = %d outside [0, %d)", idx[i], y, ft->nc);
+                return RN_E_RANGE;
+            }
+        }
+    }
+    if (steps > ft->losses_cap) {
+        if (ft->d_losses) RN_HIP(hipFree(ft->d_losses));
+        ft->d_losses = nullptr;
+        ft->losses_cap = 0;
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&ft->d_losses), static_cast<size_t>(steps) * 4));
+        ft->losses_cap = steps;
+    }
+    FtItemArgs a = ft->item;
+    a.feats = d_feats;
+    a.labels = d_labels;
+    a.index = d_index;
+    a.l2sum = ft->d_l2sum;
+    a.probs = nullptr;
+    a.ids = nullptr;
+    FtUpdateArgs u = ft->upd;
+    u.n = batch;
+    const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
+    const int ublocks = (ft->n_param + 255) / 256;
+    ft->timed = false;
+    RN_HIP(hipEventRecord(ft->ev0, ft->stream));
+    for (int s = 0; s < steps; ++s) {
+        const int64_t t = ft->steps_done + 1;
+        const double lr = ft_learn_rate(ft->cfg, ft->cfg.start_step + ft->steps_done);
+        u.lr_t = static_cast<float>(lr * std::sqrt(1.0 - std::pow(b2, static_cast<double>(t))) / (1.0 - std::pow(b1, static_cast<double>(t))));
+        u.loss_out = ft->d_losses + s;
+        a.base = static_cast<int64_t>(s) * batch;
+        hipLaunchKernelGGL(ft_item_kernel<true>, dim3(batch), dim3(FT_NT), 0, ft->stream, a);
+        RN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(ft_update_kernel, dim3(ublocks), dim3(256), 0, ft->stream, u);
+        RN_CHECK_LAUNCH();
+        ++ft->steps_done;
+    }
+    RN_HIP(hipEventRecord(ft->ev1, ft->stream));
+    RN_HIP(hipMemcpyAsync(losses, ft->d_losses, static_cast<size_t>(steps) * 4, hipMemcpyDeviceToHost, ft->stream));
+    RN_HIP(hipStreamSynchronize(ft->stream));
+    ft->timed = true;
+    return RN_OK;
+}
+
+extern "C" int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n, float* mean_loss, float* probs,
+                          int64_t* ids) {
+    if (!ft || !d_feats || n < 1) {
+        rn_set_error("rn_ft_eval: bad argument");
+        return RN_E_INVALID;
+    }
+    if (mean_loss && !d_labels) {
+        rn_set_error("rn_ft_eval: a loss needs labels");
+        return RN_E_INVALID;
+    }
+    DeviceGuard guard(ft->device);
+    (void)hipGetLastError();
+    if (d_labels) {
+        std::vector<int32_t> lab(static_cast<size_t>(n));
+        RN_HIP(hipStreamSynchronize(ft->stream));
+        RN_HIP(hipMemcpy(lab.data(), d_labels, lab.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i)
+            if (lab[i] < 0 || lab[i] >= ft->nc) {
+                rn_set_error("rn_ft_eval: label[%lld] = %d outside [0, %d)", static_cast<long long>(i), lab[i], ft->nc);
+                return RN_E_RANGE;
+            }
+    }
+    FtItemArgs a = ft->item;
+    a.feats = d_feats;
+    a.labels = d_labels;
+    a.index = nullptr;
+    a.l2sum = nullptr;
+    double ce = 0.0;
+    std::vector<double> il(static_cast<size_t>(ft->max_batch));
+    for (int64_t i = 0; i < n; i += ft->max_batch) {
+        const int m = static_cast<int>(std::min<int64_t>(ft->max_batch, n - i));
+        a.base = i;
+        a.probs = ft->d_probs;
+        a.ids = ft->d_ids;
+        hipLaunchKernelGGL(ft_item_kernel<false>, dim3(m), dim3(FT_NT), 0, ft->stream, a);
+        RN_CHECK_LAUNCH();
+        if (probs) RN_HIP(hipMemcpyAsync(probs + i * ft->nc, ft->d_probs, static_cast<size_t>(m) * ft->nc * 4, hipMemcpyDeviceToHost, ft->stream));
+        if (ids) RN_HIP(hipMemcpyAsync(ids + i, ft->d_ids, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, ft->stream));
+        if (mean_loss) RN_HIP(hipMemcpyAsync(il.data(), ft->d_item_loss, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, ft->stream));
+        RN_HIP(hipStreamSynchronize(ft->stream));
+        if (mean_loss)
+            for (int k = 0; k < m; ++k) ce += il[k];
+    }
+    if (mean_loss) {
+        // the L2 term over the trained variables, as the training loss has it
+        std::vector<float> P(static_cast<size_t>(ft->n_param));
+        RN_HIP(hipMemcpy(P.data(), ft->d_P, P.size() * 4, hipMemcpyDeviceToHost));
+        double s2 = 0.0;
+        for (float v : P) s2 += static_cast<double>(v) * v;
+        *mean_loss = static_cast<float>(ce / static_cast<double>(n) + 0.5 * static_cast<double>(ft->cfg.l2_coeff) * s2);
+    }
+    return RN_OK;
+}
+
+extern "C" int rn_ft_var_count(const rn_ft* ft) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    return static_cast<int>(ft->vars.size());
+}
+
+extern "C" int rn_ft_var_info(const rn_ft* ft, int var, char* name, size_t name_cap, int64_t* count) {
+    if (!ft || var < 0 || var >= static_cast<int>(ft->vars.size())) {
+        rn_set_error("rn_ft_var_info: variable %d out of range", var);
+        return RN_E_RANGE;
+    }
+    const FtVarHost& v = ft->vars[var];
+    if (name && name_cap) {
+        std::strncpy(name, v.name.c_str(), name_cap - 1);
+        name[name_cap - 1] = 0;
+    }
+    if (count) *count = v.count;
+    return RN_OK;
+}
+
+extern "C" int rn_ft_read(rn_ft* ft, int what, int var, float* out, size_t cap) {
+    if (!ft || !out || var < 0 || var >= static_cast<int>(ft->vars.size())) {
+        rn_set_error("rn_ft_read: bad argument (variable %d)", var);
+        return RN_E_RANGE;
+    }
+    const float* src = what == RN_FT_PARAM ? ft->d_P : what == RN_FT_GRAD ? ft->d_G : what == RN_FT_ADAM_M ? ft->d_M :
+                       what == RN_FT_ADAM_V ? ft->d_V : nullptr;
+    if (!src) {
+        rn_set_error("rn_ft_read: what = %d is none of RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V", what);
+        return RN_E_INVALID;
+    }
+    const FtVarHost& v = ft->vars[var];
+    if (cap < static_cast<size_t>(v.count)) {
+        rn_set_error("rn_ft_read: buffer too small (%zu < %d elements)", cap, v.count);
+        return RN_E_RANGE;
+    }
+    DeviceGuard guard(ft->device);
+    RN_HIP(hipStreamSynchronize(ft->stream));
+    RN_HIP(hipMemcpy(out, src + v.off, static_cast<size_t>(v.count) * 4, hipMemcpyDeviceToHost));
+    return RN_OK;
+}
+
+extern "C" int rn_ft_last_run_ms(rn_ft* ft, float* ms) {
+    if (!ft || !ms) {
+        rn_set_error("rn_ft_last_run_ms: null argument");
+        return RN_E_INVALID;
+    }
+    if (!ft->timed) {
+        rn_set_error("rn_ft_last_run_ms: no rn_ft_run has completed on this trainer");
+        return RN_E_STATE;
+    }
+    DeviceGuard guard(ft->device);
+    RN_HIP(hipEventElapsedTime(ms, ft->ev0, ft->ev1));
+    return RN_OK;
+}
+
+extern "C" int64_t rn_ft_step_count(const rn_ft* ft) { return ft ? ft->cfg.start_step + ft->steps_done : -1; }

@@ -600,6 +600,22 @@ int ensure_device(rn_handle* h, GradCamState* g) {
 
 }  // namespace
 
+// The graphs whose last block and head the adjoint kernels walk (grad-CAM here, the fine-tuning trainer in rn_finetune.hip): null, or
+// the reason a graph is refused.
+const char* rn_tail_graph_reason(const rn_weights* w) {
+    const int ns = w->n_stages;
+    if (ns < 4 || w->n_dense < 1) return "the graph has no 128 -> 16 -> 16 -> 16 last block";
+    const rn_conv_stage &st6 = w->stages[ns - 4], &st7 = w->stages[ns - 3], &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
+    auto last_block = [](const rn_conv_stage& s) { return s.cout == GC_C && s.pool_k == 4 && s.pool_s == 2; };
+    if (st6.cout != GC_CIN7 || st7.cin != GC_CIN7 || !last_block(st7) || !last_block(st8) || !last_block(st9) || st8.cin != GC_C ||
+        st9.cin != GC_C || st7.skip_stage >= 0 || st8.skip_stage >= 0 || st9.skip_stage != ns - 3 || !st9.gamma2 || st6.skip_stage >= 0)
+        return "the graph's last two blocks are not conv_block(128, pooling=False) + conv_block(16, 4, 2, depth 3)";
+    for (int d = 0; d < w->n_dense; ++d)
+        if (w->dense[d].nout > GC_HMAX || (d + 1 < w->n_dense && !w->dense[d].gamma) || (d + 1 == w->n_dense && w->dense[d].gamma))
+            return "the dense head is not BN dense blocks followed by one plain dense layer";
+    return nullptr;
+}
+
 int rn_gradcam_keep(rn_handle* h, const rn_weights* w) {
     auto* g = new GradCamState();
     h->gradcam = g;
@@ -608,19 +624,12 @@ int rn_gradcam_keep(rn_handle* h, const rn_weights* w) {
         g->why = why;
         return RN_OK;
     };
-    if (ns < 4 || w->n_dense < 1) return no("the graph has no 128 -> 16 -> 16 -> 16 last block");
+    if (const char* why = rn_tail_graph_reason(w)) return no(why);
     g->s6 = ns - 4;
     g->s7 = ns - 3;
     g->s8 = ns - 2;
     g->s9 = ns - 1;
-    const rn_conv_stage &st6 = w->stages[g->s6], &st7 = w->stages[g->s7], &st8 = w->stages[g->s8], &st9 = w->stages[g->s9];
-    auto last_block = [](const rn_conv_stage& s) { return s.cout == GC_C && s.pool_k == 4 && s.pool_s == 2; };
-    if (st6.cout != GC_CIN7 || st7.cin != GC_CIN7 || !last_block(st7) || !last_block(st8) || !last_block(st9) || st8.cin != GC_C ||
-        st9.cin != GC_C || st7.skip_stage >= 0 || st8.skip_stage >= 0 || st9.skip_stage != g->s7 || !st9.gamma2 || st6.skip_stage >= 0)
-        return no("the graph's last two blocks are not conv_block(128, pooling=False) + conv_block(16, 4, 2, depth 3)");
-    for (int d = 0; d < w->n_dense; ++d)
-        if (w->dense[d].nout > GC_HMAX || (d + 1 < w->n_dense && !w->dense[d].gamma) || (d + 1 == w->n_dense && w->dense[d].gamma))
-            return no("the dense head is not BN dense blocks followed by one plain dense layer");
+    const rn_conv_stage &st7 = w->stages[g->s7], &st8 = w->stages[g->s8], &st9 = w->stages[g->s9];
     const float eps = w->bn_epsilon;
     std::vector<float>& b = g->blob;
     auto put = [&](const float* src, size_t cnt) {

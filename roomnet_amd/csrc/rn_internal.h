@@ -149,6 +149,7 @@ struct rn_handle {
     void* fused = nullptr;       // plan of the fused 16-bit path (rn_fused.hip)
     void* f32m = nullptr;        // plan of the float32 matrix-core stage kernels (rn_stage_f32m.hip)
     void* gradcam = nullptr;     // what the grad-CAM adjoint keeps from rn_create + its device workspace (rn_gradcam.hip)
+    float* d_feat = nullptr;     // rn_features_u8: float32 staging of s7.bn, [max_batch, S7, S7, 16] (allocated by the first call)
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
@@ -201,6 +202,7 @@ int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const
 int rn_launch_convert_to_f32(hipStream_t s, const void* in, int dtype, float* out, int64_t n);
 
 // ---- grad-CAM (rn_gradcam.hip)
+const char* rn_tail_graph_reason(const rn_weights* w);
 int rn_gradcam_keep(rn_handle* h, const rn_weights* w);
 void rn_gradcam_release(rn_handle* h);
 void rn_gradcam_layers(const rn_handle* h, int* node6, int* node7);

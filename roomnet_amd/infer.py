@@ -263,6 +263,38 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None):
     return nn.recalibrate_bn(batches(), momentum=momentum)
 
 
+def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64):
+    """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
+    infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
+    batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
+    features.  ``val_list_fpath``: a second list evaluated after the last step.  Returns what ``fine_tune`` returns."""
+    def features_of(path):
+        fpaths, labels, _n = read_fpaths(path)
+        feats, kept, pending = [], [], []
+
+        def flush():
+            if pending:
+                feats.append(nn.extract_features([p[1] for p in pending]))
+                kept.extend(labels[p[0]] for p in pending)
+                pending.clear()
+
+        for i, fpath, im in _decode_files(fpaths, extract_batch):
+            if im is None:
+                print(fpath, '---> unreadable image, skipped')
+                continue
+            pending.append((i, im))
+            if len(pending) >= extract_batch:
+                flush()
+        flush()
+        if not feats:
+            raise ValueError("fine_tune_from_list: no readable image in %r" % path)
+        return np.concatenate(feats, 0), np.asarray(kept, np.int32)
+
+    feats, labels = features_of(list_fpath)
+    val = features_of(val_list_fpath) if val_list_fpath else None
+    return nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val)
+
+
 if __name__ == '__main__':
     nn = RoomNet(num_classes=len(CLASS_LABELS), im_side=IMG_SIDE, compute_bn_mean_var=False,
                  optimized_inference=True)

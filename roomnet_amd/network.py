@@ -8,8 +8,9 @@ Kept from the reference (same names, argument meaning, return shapes/dtypes):
 ``center_crop(x)``, ``infer(im_batch)``, ``infer_optimized(im)``.
 Batch-statistics BN, the forward pass of the reference's default ``compute_bn_mean_var=True`` model, arrives through
 ``infer_batch_stats`` and ``recalibrate_bn`` (the constructor still refuses the flag: that model is the training graph).
-Training (``train_step``, loss/optimizer graph, ``network.py:49-85,158-170``) is out
-of scope and raises ``NotImplementedError``.
+Whole-network training (``train_step``, loss/optimizer graph, ``network.py:49-85,158-170``) is out
+of scope and raises ``NotImplementedError``; ``extract_features`` + ``fine_tune`` train the last two conv stages and the
+dense head on the GPU, from cached ``s7.bn`` features.
 
 MI355X-only keyword arguments (not in the reference): ``device``, ``dtype``
 ("f32" | "bf16" | "f16"), ``max_batch``.
@@ -119,6 +120,8 @@ class RoomNet:
         self.start_step = start_step
         self.step = start_step
         self.learn_rate = learn_rate
+        self.l2_regularizer_coeff = l2_regularizer_coeff
+        self.num_steps = num_steps
         self.dropout_enabled = False if optimized_inference else dropout_enabled
         self.model_folder = 'all_trained_models/trained_models'
         self.model_fpath_prefix = self.model_folder + '/' + 'roomnet-'
@@ -434,6 +437,71 @@ class RoomNet:
         new = bnstats.updated_statistics(self.graph, self.sess.variables, seen, momentum)
         self.set_variables(new)
         return new
+
+    # ------------------------------------------------------------ fine-tuning
+    def extract_features(self, im_in):
+        """The features ``fine_tune`` trains on: ``s7.bn``, the output of the last block's first step (21 x 21 x 16 at 224, 68 x 68 x
+        16 at 600), of every image as float32 ``[N, S7, S7, 16]`` (``rn_features_u8``).  ``im_in`` as ``grad_cam`` takes it: an
+        ``[N,S,S,3]`` BGR batch, one BGR ``[H,W,3]`` image, or a list of images of any size (centre-cropped and resized as
+        ``infer_images`` does).  Everything behind these features depends on them alone, so a training set is extracted once."""
+        if isinstance(im_in, np.ndarray) and im_in.ndim == 3:
+            im_in = [im_in]
+        if isinstance(im_in, np.ndarray) and im_in.ndim != 4:
+            raise ValueError("extract_features: expected an [N,S,S,3] batch, one [H,W,3] image or a list of images, got shape %s"
+                             % (im_in.shape,))
+        im = self._as_feed(self._batch_from(im_in, "extract_features"))
+        if im.dtype != np.uint8:
+            if im.size and bool(np.all(im == np.rint(im))) and im.min() >= 0 and im.max() <= 255:
+                im = im.astype(np.uint8)
+            else:
+                raise ValueError("extract_features takes uint8 images (or integral values in [0, 255]), got %s" % im.dtype)
+        return self._engine().features_u8(im)
+
+    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None):
+        """Train stages 8 and 9 and the dense head on cached features, on the GPU (``rn_ft_*``; not the reference's whole-network
+        ``train_step``): stages 0-7 stay as loaded, every BN keeps its moving statistics and trains gamma and beta (the
+        reference's shipped configuration, train.py:40-41), Adam with the constructor's ``learn_rate``, ``num_steps`` (decay),
+        ``l2_regularizer_coeff`` and ``start_step``.  ``features``: float32 ``[N, S7, S7, 16]`` of ``extract_features``;
+        ``labels``: N class ids; minibatches of ``batch_size`` in the reference feeder's order (``finetune.epoch_indices``, a
+        fresh shuffle per epoch from ``seed`` and the current step).  ``val``: ``(features, labels)`` evaluated after the last step.
+        The trained variables are written back through ``set_variables`` (the next ``infer`` builds its engine on them, ``save()``
+        writes them) and ``self.step`` advances.  Returns ``{"losses": float32[steps] (each before its update), "step",
+        "learn_rate" (at the new step), "val": (loss, accuracy) or None}``.  Adam's slots start at zero in every call."""
+        from . import finetune
+        from ._capi import Trainer
+        if self.dropout_enabled:
+            raise ValueError("fine_tune: dropout is not implemented on the GPU path; construct with dropout_enabled=False")
+        if not self.sess:
+            raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
+        feats = np.ascontiguousarray(features, np.float32)
+        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        shape = finetune.feature_shape(self.graph)
+        if feats.ndim != 4 or feats.shape[1:] != shape or feats.shape[0] != labels.shape[0] or feats.shape[0] < 1:
+            raise ValueError("fine_tune: features %s and labels %s do not form [N, %d, %d, %d] and [N]"
+                             % (feats.shape, labels.shape, shape[0], shape[1], shape[2]))
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("fine_tune: steps = %d" % steps)
+        index = finetune.epoch_indices(feats.shape[0], batch_size, steps, seed=[int(seed), int(self.step)])
+        tr = Trainer(self.graph, self.sess.variables, device=self.device, max_batch=max(index.shape[1], min(self.max_batch, 256)),
+                     learn_rate=self.learn_rate, num_steps=self.num_steps, start_step=self.step,
+                     l2_coeff=self.l2_regularizer_coeff)
+        try:
+            losses = tr.run_host(feats, labels, index)
+            out_val = None
+            if val is not None:
+                vf, vl = val
+                vl = np.ascontiguousarray(vl, np.int32).reshape(-1)
+                loss, _probs, ids = tr.eval_host(vf, vl)
+                out_val = (loss, float(np.mean(ids == vl)))
+            new = tr.read()
+            step = tr.step_count()
+        finally:
+            tr.close()
+        self.set_variables(new)
+        self.step = step
+        return {"losses": losses, "step": step, "val": out_val,
+                "learn_rate": finetune.learn_rate_at(step, self.learn_rate, self.num_steps)}
 
     def train_step(self, x_in, y):
         raise NotImplementedError("training (network.py:158-170) is out of scope of the MI355X inference path")

@@ -1,0 +1,182 @@
+"""Fine-tuning cost (rn_ft_*, rn_features_*): one JSON line with
+  - us per Adam step at batch 45 and 256 (224 geometry) and batch 45 at the 600 geometry: 200 steps per rn_ft_run, device time of the
+    step loop between events on the trainer's stream (rn_ft_last_run_ms), after a warm-up run;
+  - features/s of rn_features_u8_device at 256 x 224 x 224 bf16 beside images/s of rn_forward_u8_device on the same handle;
+  - ms per step of the float32 torch restatement (tests/finetune_ref.py) on 16 CPU threads, batch 45 at 224: what a user has today.
+
+    python tools/bench_finetune.py [--steps 200] [--runs 5]
+    rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py --trace-run
+    python tools/bench_finetune.py --summarise DIR/.../kt_kernel_trace.csv [--out profiles/finetune_kernel_stats.txt]
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CASES = ((224, 45), (224, 256), (600, 45))
+N_ITEMS = 512
+
+
+def _weights(side):
+    from roomnet_amd.graph import build_graph
+    from roomnet_amd.tf_bundle import BundleReader
+    w = BundleReader(os.path.join(ROOT, "roomnet_amd", "final_model", "roomnet")).load_all()
+    g = build_graph(6, side)
+    if side != 224:
+        w = dict(w)
+        w["dense/kernel"] = np.random.default_rng(600).uniform(-0.04, 0.04, (g.flat_len, 32)).astype(np.float32)
+    return g, w
+
+
+def _data(g, n_items=N_ITEMS):
+    from roomnet_amd import finetune
+    rng = np.random.default_rng(7)
+    feats = (rng.standard_normal((n_items,) + finetune.feature_shape(g)) * 0.5).astype(np.float32)
+    labels = rng.integers(0, 6, n_items).astype(np.int32)
+    return feats, labels
+
+
+def step_case(side, batch, steps, runs):
+    from roomnet_amd import _capi, finetune
+    g, w = _weights(side)
+    feats, labels = _data(g)
+    index = finetune.epoch_indices(N_ITEMS, batch, steps, seed=1)
+    tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06)
+    try:
+        d = [tr.upload(feats), tr.upload(labels), tr.upload(index)]
+        tr.run(d[0], d[1], N_ITEMS, d[2], batch, steps)            # warm-up
+        us = []
+        for _ in range(runs):
+            tr.run(d[0], d[1], N_ITEMS, d[2], batch, steps)
+            us.append(tr.last_run_ms() * 1e3 / steps)
+        return {"side": side, "batch": batch, "steps_per_run": steps, "us_per_step": round(statistics.median(us), 2),
+                "us_per_step_min": round(min(us), 2), "us_per_step_max": round(max(us), 2)}
+    finally:
+        tr.close()
+
+
+def features_case(steps=20, warmup=5):
+    import torch
+    from roomnet_amd import _capi
+    from roomnet_amd.synth import parity_set
+    g, w = _weights(224)
+    fields = np.load(os.path.join(ROOT, "tests", "golden", "class_fields.npz"))["fields_u8"]
+    ims = parity_set(224, fields)
+    ims = np.ascontiguousarray(np.concatenate([ims] * 4)[:256])
+    eng = _capi.Engine(g, w, device=0, dtype="bf16", max_batch=256)
+    try:
+        eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        d_in = torch.from_numpy(ims).cuda()
+        d_f = torch.empty((256, 21, 21, 16), dtype=torch.float32, device="cuda")
+        d_probs = torch.empty((256, 6), dtype=torch.float32, device="cuda")
+        d_ids = torch.empty((256,), dtype=torch.int64, device="cuda")
+
+        def timed(fn):
+            for _ in range(warmup):
+                fn()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(steps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / steps
+
+        fwd = timed(lambda: eng.forward_u8_device(d_in.data_ptr(), 256, d_probs.data_ptr(), d_ids.data_ptr()))
+        fea = timed(lambda: eng.features_u8_device(d_in.data_ptr(), 256, d_f.data_ptr()))
+        eng.set_stream(None)
+        return {"side": 224, "dtype": "bf16", "batch": 256, "forward_ms": round(fwd, 4), "features_ms": round(fea, 4),
+                "forward_images_per_s": round(256e3 / fwd, 1), "features_per_s": round(256e3 / fea, 1)}
+    finally:
+        eng.close()
+
+
+def torch_case(batch=45, steps=5, threads=16):
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from finetune_ref import FineTuneRef
+    from roomnet_amd import finetune
+    torch.set_num_threads(threads)
+    g, w = _weights(224)
+    feats, labels = _data(g)
+    index = finetune.epoch_indices(N_ITEMS, batch, steps + 1, seed=1)
+    ref = FineTuneRef(w, 6, 224, dtype=torch.float32)
+    ref.train(feats, labels, index[:1], 2e-4, 10000, 0.06)
+    t0 = time.perf_counter()
+    ref.train(feats, labels, index[1:], 2e-4, 10000, 0.06)
+    return {"side": 224, "batch": batch, "threads": threads, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 2)}
+
+
+def trace_run():
+    for side, batch in CASES:
+        step_case(side, batch, TRACE_STEPS, 1)
+
+
+TRACE_STEPS = 20                                  # steps per rn_ft_run of --trace-run (a warm-up run and a measured one per case)
+
+
+def summarise(trace_csv):
+    rows = []
+    for r in csv.DictReader(open(trace_csv)):
+        for key in ("ft_item_kernel", "ft_update_kernel"):
+            if key in r["Kernel_Name"]:
+                rows.append((int(r["Start_Timestamp"]), key, int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1),
+                             (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    rows.sort()
+    per_case = 2 * 2 * TRACE_STEPS                # the cases run one after the other: two runs x two launches per step
+    if len(rows) != per_case * len(CASES):
+        raise SystemExit("expected %d ft_* launches (%d cases), found %d" % (per_case * len(CASES), len(CASES), len(rows)))
+    lines = ["# rocprofv3 --kernel-trace --stats -- python tools/bench_finetune.py --trace-run (one MI355X, its own run)",
+             "# the two launches of an Adam step per case: workgroups, calls, median / max duration in us, and the step's sum",
+             "%5s %6s  %-17s %6s %6s %11s %9s" % ("side", "batch", "kernel", "wgs", "calls", "median_us", "max_us")]
+    for ci, (side, batch) in enumerate(CASES):
+        total = 0.0
+        for key in ("ft_item_kernel", "ft_update_kernel"):
+            sel = [r for r in rows[ci * per_case:(ci + 1) * per_case] if r[1] == key]
+            us = [r[3] for r in sel]
+            total += statistics.median(us)
+            lines.append("%5d %6d  %-17s %6d %6d %11.1f %9.1f" % (side, batch, key, sel[0][2], len(us), statistics.median(us), max(us)))
+        lines.append("%5d %6d  %-17s %6s %6s %11.1f" % (side, batch, "both", "", "", total))
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--steps-only", action="store_true", help="only the us-per-step cases")
+    ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if not args.summarise:
+        import torch  # noqa: F401  (before libroomnet_hip.so is loaded: one HIP runtime in the process, torch's)
+    if args.summarise:
+        text = summarise(args.summarise)
+        if args.out:
+            open(args.out, "w").write(text)
+        print(text, end="")
+        return
+    if args.trace_run:
+        trace_run()
+        return
+    if args.steps_only:
+        print(json.dumps({"steps": [step_case(s, b, args.steps, args.runs) for s, b in CASES]}))
+        return
+    print(json.dumps({"what": "fine-tuning on cached s7.bn features: us per Adam step (two launches, enqueued back to back), feature "
+                              "extraction beside the plain forward pass, and the float32 torch restatement on the CPU",
+                      "steps": [step_case(s, b, args.steps, args.runs) for s, b in CASES],
+                      "features": features_case(), "torch_float32_cpu": torch_case()}))
+
+
+if __name__ == "__main__":
+    main()

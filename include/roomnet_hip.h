@@ -311,6 +311,13 @@ RN_API int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n,
 RN_API int rn_features_shape(const rn_handle* h, int* side, int* channels);
 RN_API int rn_features_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, float* feat);
 RN_API int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, float* d_feat);
+/* The same for a trainer of a given depth = its number of trained conv stages.  depth 2: exactly rn_features_*.  depth 3: the
+ * feature is this call's "s6.bn", the input of the last conv block, widened to float32 [n, side, side, 128] (46 x 46 at 224,
+ * 140 x 140 at 600: 1.08 MB per image at 224 against 28 KB at depth 2), byte for byte what rn_tap("s6.bn") returns after the call.
+ * Any other depth is RN_E_INVALID; the other error codes are those of rn_features_*. */
+RN_API int rn_features_depth_shape(const rn_handle* h, int depth, int* side, int* channels);
+RN_API int rn_features_depth_u8(rn_handle* h, int depth, const uint8_t* bgr_nhwc, int n, float* feat);
+RN_API int rn_features_depth_u8_device(rn_handle* h, int depth, const uint8_t* d_bgr_nhwc, int n, float* d_feat);
 
 typedef struct rn_ft rn_ft;
 typedef struct rn_ft_config {
@@ -347,6 +354,14 @@ typedef struct rn_ft_config {
  * rn_ft_upload / rn_ft_free  device memory for the caller's features, labels and indices: allocate + copy from the host, and
  *               free (rn_ft_destroy frees what is left).  Calls on one trainer must be serialised by the caller. */
 RN_API int rn_ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, rn_ft** out);
+/* rn_ft_create_depth: depth 2 is rn_ft_create.  depth 3 trains the whole last conv block from cached "s6.bn" features
+ * (rn_features_depth_*, depth 3): conv 7's kernel and its BN's gamma and beta come in front of the list (22 variables for the
+ * reference graph; the L2 term runs over all of them), rn_ft_run and rn_ft_eval read d_feats as [n_items, S6, S6, 128] float32,
+ * and a step is four launches: conv 7 forward and its weight gradient run on the float32 matrix cores, on a grid of (row band,
+ * item), with one weight-gradient partial per (item, band) summed in index order (csrc/rn_finetune7.hip).  Every guarantee of
+ * rn_ft_run above holds at depth 3.  Any other depth is RN_E_INVALID.  rn_ft_depth: the depth of a trainer. */
+RN_API int rn_ft_create_depth(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, int depth, rn_ft** out);
+RN_API int rn_ft_depth(const rn_ft* ft);
 RN_API void rn_ft_destroy(rn_ft* ft);
 RN_API int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
                      int steps, float* losses);

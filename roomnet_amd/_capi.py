@@ -47,7 +47,8 @@ EXPORTED_SYMBOLS = (
     "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
     "rn_bn_count", "rn_bn_info", "rn_bn_batch_stats",
     "rn_features_shape", "rn_features_u8", "rn_features_u8_device",
-    "rn_ft_create", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
+    "rn_features_depth_shape", "rn_features_depth_u8", "rn_features_depth_u8_device",
+    "rn_ft_create", "rn_ft_create_depth", "rn_ft_depth", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
 )
 
@@ -242,6 +243,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_ft_upload.restype = i32
         lib.rn_ft_free.argtypes = [vp, vp]
         lib.rn_ft_free.restype = i32
+    if hasattr(lib, "rn_ft_create_depth"):
+        lib.rn_features_depth_shape.argtypes = [vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.rn_features_depth_shape.restype = i32
+        lib.rn_features_depth_u8.argtypes = [vp, i32, vp, i32, vp]
+        lib.rn_features_depth_u8.restype = i32
+        lib.rn_features_depth_u8_device.argtypes = [vp, i32, vp, i32, vp]
+        lib.rn_features_depth_u8_device.restype = i32
+        lib.rn_ft_create_depth.argtypes = [C.POINTER(rn_weights), i32, i32, C.POINTER(rn_ft_config), i32, C.POINTER(vp)]
+        lib.rn_ft_create_depth.restype = i32
+        lib.rn_ft_depth.argtypes = [vp]
+        lib.rn_ft_depth.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -502,31 +514,45 @@ class Engine:
                                             C.c_void_p(d_probs), C.c_void_p(d_ids))
         _check(self.lib, rc, "rn_grad_cam_u8_device")
 
-    def features_shape(self) -> Tuple[int, int, int]:
-        """Per-image shape of the fine-tuning feature ``s7.bn`` (``rn_features_shape``)."""
+    def features_shape(self, depth: int = 2) -> Tuple[int, int, int]:
+        """Per-image shape of the fine-tuning feature of a trainer of ``depth``: ``s7.bn`` at depth 2 (``rn_features_shape``),
+        ``s6.bn`` at depth 3 (``rn_features_depth_shape``)."""
         side, ch = C.c_int(0), C.c_int(0)
-        _check(self.lib, self.lib.rn_features_shape(self.handle, C.byref(side), C.byref(ch)), "rn_features_shape")
+        if depth == 2:
+            _check(self.lib, self.lib.rn_features_shape(self.handle, C.byref(side), C.byref(ch)), "rn_features_shape")
+        else:
+            _check(self.lib, self.lib.rn_features_depth_shape(self.handle, int(depth), C.byref(side), C.byref(ch)),
+                   "rn_features_depth_shape")
         return side.value, side.value, ch.value
 
-    def features_u8(self, im_bgr_u8: np.ndarray) -> np.ndarray:
-        """``s7.bn`` of a uint8 BGR ``[N,S,S,3]`` batch, widened to float32 ``[N, side, side, 16]`` (``rn_features_u8``): what
-        ``Trainer`` trains on."""
+    def features_u8(self, im_bgr_u8: np.ndarray, depth: int = 2) -> np.ndarray:
+        """The feature a ``Trainer`` of ``depth`` trains on, of a uint8 BGR ``[N,S,S,3]`` batch, widened to float32: ``s7.bn``
+        ``[N, side, side, 16]`` at depth 2 (``rn_features_u8``; 28 KB per image at 224), ``s6.bn`` ``[N, side, side, 128]`` at
+        depth 3 (``rn_features_depth_u8``; 1.08 MB per image at 224)."""
         s = self.graph.im_side
         im = np.ascontiguousarray(im_bgr_u8, dtype=np.uint8)
         if im.ndim != 4 or im.shape[1:] != (s, s, 3):
             raise ValueError("expected a [N,%d,%d,3] uint8 batch, got %s" % (s, s, im.shape))
         n = im.shape[0]
-        out = np.empty((n,) + self.features_shape(), np.float32)
+        out = np.empty((n,) + self.features_shape(depth), np.float32)
         for i in range(0, n, self.max_batch):
             m = min(self.max_batch, n - i)
-            _check(self.lib, self.lib.rn_features_u8(self.handle, im[i:i + m].ctypes.data, m, out[i:i + m].ctypes.data),
-                   "rn_features_u8")
+            if depth == 2:
+                _check(self.lib, self.lib.rn_features_u8(self.handle, im[i:i + m].ctypes.data, m, out[i:i + m].ctypes.data),
+                       "rn_features_u8")
+            else:
+                _check(self.lib, self.lib.rn_features_depth_u8(self.handle, int(depth), im[i:i + m].ctypes.data, m,
+                                                               out[i:i + m].ctypes.data), "rn_features_depth_u8")
         return out
 
-    def features_u8_device(self, d_bgr: int, n: int, d_feat: int) -> None:
-        """Asynchronous ``rn_features_u8_device`` on raw device pointers."""
-        _check(self.lib, self.lib.rn_features_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_feat)),
-               "rn_features_u8_device")
+    def features_u8_device(self, d_bgr: int, n: int, d_feat: int, depth: int = 2) -> None:
+        """Asynchronous ``rn_features_u8_device`` (depth 3: ``rn_features_depth_u8_device``) on raw device pointers."""
+        if depth == 2:
+            _check(self.lib, self.lib.rn_features_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_feat)),
+                   "rn_features_u8_device")
+        else:
+            _check(self.lib, self.lib.rn_features_depth_u8_device(self.handle, int(depth), C.c_void_p(d_bgr), n, C.c_void_p(d_feat)),
+                   "rn_features_depth_u8_device")
 
     def sync(self) -> None:
         _check(self.lib, self.lib.rn_sync(self.handle), "rn_sync")
@@ -676,20 +702,28 @@ class Engine:
 class Trainer:
     """One rn_ft: float32 master copies of the last two conv stages and the dense head, Adam slots and the step counter on one
     GPU (include/roomnet_hip.h: fine-tuning).  Trains on features that stay resident in device memory: ``upload`` the
-    ``[n_items, side, side, 16]`` float32 features of ``Engine.features_u8`` and the int32 labels once, then ``run``."""
+    ``[n_items, side, side, 16]`` float32 features of ``Engine.features_u8`` and the int32 labels once, then ``run``.
+    ``depth=3`` (``rn_ft_create_depth``) trains the whole last conv block, stage 7 included, on the ``[n_items, side, side, 128]``
+    features of ``Engine.features_u8(..., depth=3)``: 1.08 MB per image at 224 against 28 KB at depth 2."""
 
     def __init__(self, graph: Graph, weights: Dict[str, np.ndarray], device: int = 0, max_batch: int = 64, learn_rate: float = 1e-4,
                  num_steps: int = 10000, start_step: int = 0, l2_coeff: float = 1e-2, decay_rate: float = 0.068,
-                 beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, lib_path: Optional[str] = None):
+                 beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, lib_path: Optional[str] = None,
+                 depth: int = 2):
         self.lib = load_library(lib_path)
         self.graph = graph
+        self.depth = int(depth)
         self.max_batch = int(max_batch)
         packed = _Packed(graph, weights)
         cfg = rn_ft_config(learn_rate, decay_rate, int(num_steps), int(start_step), l2_coeff, beta1, beta2, epsilon)
         h = C.c_void_p()
         self._h = None
-        _check(self.lib, self.lib.rn_ft_create(C.byref(packed.w), int(device), self.max_batch, C.byref(cfg), C.byref(h)),
-               "rn_ft_create")
+        if self.depth == 2:
+            _check(self.lib, self.lib.rn_ft_create(C.byref(packed.w), int(device), self.max_batch, C.byref(cfg), C.byref(h)),
+                   "rn_ft_create")
+        else:
+            _check(self.lib, self.lib.rn_ft_create_depth(C.byref(packed.w), int(device), self.max_batch, C.byref(cfg), self.depth,
+                                                         C.byref(h)), "rn_ft_create_depth")
         self._h = h
         self._vars: Optional[List[Tuple[str, int]]] = None
 

@@ -904,9 +904,14 @@ extern "C" int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, in
     return gradcam_device(h, d_bgr_nhwc, nullptr, n, d_class_ids, layer6, d_cam, d_alpha, d_probs, d_ids);
 }
 
-// ---- feature read-out for the fine-tuning cache (rn_finetune.hip): a forward pass that leaves s7.bn in HBM, widened to float32
+// ---- feature read-out for the fine-tuning cache (rn_finetune.hip): a forward pass that leaves s7.bn (depth 2) or s6.bn (depth 3)
+// in HBM, widened to float32
 namespace {
-int features_check(rn_handle* h, int n, int* node7) {
+int features_check(rn_handle* h, int n, int* node7, int depth = 2) {
+    if (depth != 2 && depth != 3) {
+        rn_set_error("rn_features_depth: depth = %d is neither 2 (s7.bn) nor 3 (s6.bn)", depth);
+        return RN_E_INVALID;
+    }
     if (!h) {
         rn_set_error("null handle");
         return RN_E_INVALID;
@@ -925,6 +930,7 @@ int features_check(rn_handle* h, int n, int* node7) {
     }
     int node6;
     rn_gradcam_layers(h, &node6, node7);
+    if (depth == 3) *node7 = node6;
     return RN_OK;
 }
 
@@ -967,6 +973,31 @@ extern "C" int rn_features_shape(const rn_handle* h, int* side, int* channels) {
     return RN_OK;
 }
 
+extern "C" int rn_features_depth_shape(const rn_handle* h, int depth, int* side, int* channels) {
+    if (depth != 2 && depth != 3) {
+        rn_set_error("rn_features_depth: depth = %d is neither 2 (s7.bn) nor 3 (s6.bn)", depth);
+        return RN_E_INVALID;
+    }
+    int rc = rn_features_shape(h, side, channels);
+    if (rc != RN_OK || depth == 2) return rc;
+    int node6, node7;
+    rn_gradcam_layers(h, &node6, &node7);
+    if (side) *side = h->nodes[node6].info.h;
+    if (channels) *channels = h->nodes[node6].info.c;
+    return RN_OK;
+}
+
+extern "C" int rn_features_depth_u8_device(rn_handle* h, int depth, const uint8_t* d_bgr_nhwc, int n, float* d_feat) {
+    int node = -1;
+    int rc = features_check(h, n, &node, depth);
+    if (rc != RN_OK) return rc;
+    if (!d_bgr_nhwc || !d_feat) {
+        rn_set_error("null buffer");
+        return RN_E_INVALID;
+    }
+    return features_device(h, d_bgr_nhwc, n, node, d_feat);
+}
+
 extern "C" int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, float* d_feat) {
     int node7 = -1;
     int rc = features_check(h, n, &node7);
@@ -978,27 +1009,36 @@ extern "C" int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, in
     return features_device(h, d_bgr_nhwc, n, node7, d_feat);
 }
 
-extern "C" int rn_features_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, float* feat) {
-    int node7 = -1;
-    int rc = features_check(h, n, &node7);
+namespace {
+int features_host(rn_handle* h, int depth, const uint8_t* bgr_nhwc, int n, float* feat) {
+    int node = -1;
+    int rc = features_check(h, n, &node, depth);
     if (rc != RN_OK) return rc;
     if (!bgr_nhwc || !feat) {
         rn_set_error("null buffer");
         return RN_E_INVALID;
     }
     DeviceGuard guard(h->device);
-    const rn_node_info& li = h->nodes[node7].info;
+    const rn_node_info& li = h->nodes[node].info;
     const size_t per = static_cast<size_t>(li.h) * li.w * li.c;
-    if (!h->d_feat) {
+    float*& stage = depth == 3 ? h->d_feat6 : h->d_feat;
+    if (!stage) {
         void* p = nullptr;
         if ((rc = dev_alloc(h, static_cast<size_t>(h->max_batch) * per * 4, &p)) != RN_OK) return rc;
-        h->d_feat = static_cast<float*>(p);
+        stage = static_cast<float*>(p);
     }
     RN_HIP(hipMemcpyAsync(h->d_in_u8, bgr_nhwc, static_cast<size_t>(n) * h->im_side * h->im_side * 3, hipMemcpyHostToDevice, h->stream));
-    if ((rc = features_device(h, h->d_in_u8, n, node7, h->d_feat)) != RN_OK) return rc;
-    RN_HIP(hipMemcpyAsync(feat, h->d_feat, static_cast<size_t>(n) * per * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = features_device(h, h->d_in_u8, n, node, stage)) != RN_OK) return rc;
+    RN_HIP(hipMemcpyAsync(feat, stage, static_cast<size_t>(n) * per * 4, hipMemcpyDeviceToHost, h->stream));
     RN_HIP(hipStreamSynchronize(h->stream));
     return RN_OK;
+}
+}  // namespace
+
+extern "C" int rn_features_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, float* feat) { return features_host(h, 2, bgr_nhwc, n, feat); }
+
+extern "C" int rn_features_depth_u8(rn_handle* h, int depth, const uint8_t* bgr_nhwc, int n, float* feat) {
+    return features_host(h, depth, bgr_nhwc, n, feat);
 }
 
 // ---- two-slot host pipeline: the upload of batch k+1 overlaps the forward pass of batch k

@@ -39,12 +39,25 @@
 //                     (evaluated before the update) into its slot of a device array.
 // rn_ft_eval runs the item kernel forward-only (loss, softmax, argmax) from the current master parameters.
 // The loss's scalar sums (item CE terms, sum v^2, the log-sum-exp of num_classes values) are float64; everything else is float32.
+//
+// Depth.  The above is a trainer of depth 2 (rn_ft_create): two trained conv stages.  A trainer of depth 3 (rn_ft_create_depth)
+// trains the whole last block: the feature is x6 = s6.bn [S6, S6, 128], stage 7's kernel, gamma and beta come in front of the list
+// (22 variables), and a step is four launches; stage 7's mathematics and its two kernels are in rn_finetune7.hip:
+//   ft7_fwd_kernel    x6 (through the index) -> x7 into a per-step workspace, with what the adjoint needs
+//   ft_item_kernel    the depth-3 instantiation reads x7 from that workspace and goes on behind conv 8's weight gradient:
+//                     g7 = dL/dx7 = conv 8's adjoint + the transpose of the skip resize (as gc_tail_kernel has them), the item's
+//                     d gamma7 = sum g7 xh7 and d beta7 = sum g7, and dL/dpool7 = g7 gamma7 rsqrt(var7 + eps) for the next launch
+//   ft7_bwd_kernel    dL/dconv7 and one dW7 partial per (item, band)
+//   ft_update_kernel  the depth-3 instantiation sums the dW7 partials over bands, then over items, in index order, in float64
+// The depth-2 instantiations take the arguments and run the code they always did.
+#include "rn_finetune7.h"
 #include "rn_internal.h"
 #include "rn_stage.h"
 
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace rnk;
@@ -97,6 +110,15 @@ struct FtItemArgs {
     int n_param;                     // floats of the parameter slab
     float* probs;                    // eval: [batch, nc], one chunk's staging (null in training)
     int64_t* ids;                    // eval: [batch]
+};
+
+// depth 3: what the item kernel takes on top
+struct FtItemArgs7 : FtItemArgs {
+    const float* x7ws;               // [batch, S7, S7, 16] s7.bn of the step (ft7_fwd_kernel)
+    const float* xh7;                // [batch, S7, S7, 16] its normalised value before gamma and beta
+    float* dpool7;                   // [batch, S7, S7, 16] dL/dpool7 for ft7_bwd_kernel
+    int64_t off_gadd;                // workspace: dL/d(stage 9's add), which the skip branch carries back to x7
+    int o_g7, f_bn7, p_bn7;
 };
 
 __device__ __forceinline__ bool relu6_passes(float v) { return v > 0.f && v < 6.f; }
@@ -182,8 +204,9 @@ __device__ __forceinline__ void wgrad16(const float* in, int S, const float* dou
     __syncthreads();
 }
 
-template <bool TRAIN>
-__global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
+template <bool TRAIN, typename Args>
+__global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
+    constexpr bool D3 = std::is_same_v<Args, FtItemArgs7>;
     __shared__ float w8[FT_W];
     __shared__ float w9[FT_W];
     __shared__ float tab[3 * 4 * FT_C];                  // bn8 | bn9 | bn9b, each [mean | rsq | gamma | beta]
@@ -198,7 +221,11 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
     const int b = blockIdx.x;
     const int S7 = a.S7, C8 = a.C8, S8 = a.S8, C9 = a.C9, S9 = a.S9;
     const int64_t item = a.index ? static_cast<int64_t>(a.index[a.base + b]) : a.base + b;
-    const float* x7 = a.feats + item * S7 * S7 * FT_C;
+    const float* x7;
+    if constexpr (D3)
+        x7 = a.x7ws + static_cast<int64_t>(b) * S7 * S7 * FT_C;
+    else
+        x7 = a.feats + item * S7 * S7 * FT_C;
     float* wsi = a.ws + b * a.ws_item;
     float* c8 = wsi + a.off_c8;
     float* xh8 = wsi + a.off_xh8;
@@ -365,6 +392,7 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
                 dg2 = fmaf(g, xh9b[i], dg2);
                 db2 += g;
                 const float ga = g * k2;
+                if constexpr (D3) (wsi + a.off_gadd)[i] = ga;
                 dg1 = fmaf(ga, xh9[i], dg1);
                 db1 += ga;
                 gfl[i] = ga * k1;
@@ -442,6 +470,50 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
 #ifndef FT_NO_WGRAD
         wgrad16(x7, S7, c8, C8, prt + a.p_w8, red3, tid);
 #endif
+        if constexpr (D3) {
+            // ---- g7 = conv 8 adjoint + transpose of the skip resize (weights (1-yl)(1-xl), (1-yl)xl, yl(1-xl), yl xl); stage 7's BN
+            const float* gadd = wsi + a.off_gadd;
+            const float* xh7 = a.xh7 + static_cast<int64_t>(b) * S7 * S7 * FT_C;
+            float* dp7 = a.dpool7 + static_cast<int64_t>(b) * S7 * S7 * FT_C;
+            const int ci = tid & 15;
+            const float k1 = P[a.o_g7 + ci] * F[a.f_bn7 + FT_C + ci];
+            float dg = 0.f, db = 0.f;
+            for (int p = tid >> 4; p < S7 * S7; p += FT_NT / FT_C) {
+                const int i = p * FT_C + ci, Y = p / S7, X = p % S7;
+                float t = 0.f;
+                for (int ky = 0; ky < 3; ++ky) {
+                    const int y = Y - ky;
+                    if (y < 0 || y >= C8) continue;
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int x = X - kx;
+                        if (x < 0 || x >= C8) continue;
+                        t = dot16(c8 + (y * C8 + x) * FT_C, w8 + ((ky * 3 + kx) * FT_C + ci) * FT_C, t);
+                    }
+                }
+                float r = 0.f;
+                for (int y = 0; y < S9; ++y) {
+                    const float yl = a.rlerp[y];
+                    const float wy = (a.rlo[y] == Y ? 1.f - yl : 0.f) + (a.rhi[y] == Y ? yl : 0.f);
+                    if (wy == 0.f) continue;
+                    float rx = 0.f;
+                    for (int x = 0; x < S9; ++x) {
+                        const float xl = a.rlerp[x];
+                        const float wx = (a.rlo[x] == X ? 1.f - xl : 0.f) + (a.rhi[x] == X ? xl : 0.f);
+                        if (wx != 0.f) rx = fmaf(wx, gadd[(y * S9 + x) * FT_C + ci], rx);
+                    }
+                    r = fmaf(wy, rx, r);
+                }
+                const float g = t + r;
+                dg = fmaf(g, xh7[i], dg);
+                db += g;
+                dp7[i] = g * k1;
+            }
+            float t;
+            t = channel_sum(dg, red, tid);
+            if (tid < FT_C) prt[a.p_bn7 + tid] = t;
+            t = channel_sum(db, red, tid);
+            if (tid < FT_C) prt[a.p_bn7 + FT_C + tid] = t;
+        }
         // ---- sum v^2 over the parameter slab (its padding is zero), for the loss's L2 term
         if (b == 0 && a.l2sum) {
             double t = 0.0;
@@ -458,7 +530,7 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
 }
 
 // how the update kernel forms one variable's gradient from the items' partials
-enum { FT_SUM = 0, FT_OUTER = 1 };
+enum { FT_SUM = 0, FT_OUTER = 1, FT_BANDS = 2 };
 struct FtVarDev {
     int off, count;                  // in the parameter slab
     int kind;
@@ -479,7 +551,16 @@ struct FtUpdateArgs {
     float* loss_out;                 // this step's slot
 };
 
-__global__ __launch_bounds__(256) void ft_update_kernel(const FtUpdateArgs a) {
+// depth 3: conv 7's kernel (its partials: one per (item, band), rn_finetune7.hip), gamma7 and beta7 (FT_SUM over the items' records)
+struct FtUpdateArgs7 : FtUpdateArgs {
+    FtVarDev v7[3];
+    const float* part7;              // [n, bands, FT7_W]
+    int bands;
+};
+
+template <typename Args>
+__global__ __launch_bounds__(256) void ft_update_kernel(const Args a) {
+    constexpr bool D3 = std::is_same_v<Args, FtUpdateArgs7>;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e == 0) {
         double s = 0.0;
@@ -490,11 +571,30 @@ __global__ __launch_bounds__(256) void ft_update_kernel(const FtUpdateArgs a) {
     int vi = -1;
     for (int i = 0; i < a.nvars; ++i)
         if (e >= a.v[i].off && e < a.v[i].off + a.v[i].count) vi = i;
-    if (vi < 0) return;                // padding between two variables
-    const FtVarDev var = a.v[vi];
+    FtVarDev var;
+    if constexpr (D3) {
+        int v7 = -1;
+        for (int i = 0; i < 3; ++i)
+            if (e >= a.v7[i].off && e < a.v7[i].off + a.v7[i].count) v7 = i;
+        if (vi < 0 && v7 < 0) return;
+        var = v7 >= 0 ? a.v7[v7] : a.v[vi];
+    } else {
+        if (vi < 0) return;            // padding between two variables
+        var = a.v[vi];
+    }
     const int le = e - var.off;
     float s = 0.f;
-    if (var.kind == FT_SUM) {
+    if (D3 && var.kind == FT_BANDS) {
+        if constexpr (D3) {
+            // (float64: the items' gradients of a trained model all but cancel, and a float32 running sum over n x bands partials
+            //  of the items' size was the largest rounding term of dW7 -- 1.1e-5 of its largest entry at batch 32, the bound 1e-5)
+            const float* p = a.part7 + le;
+            double t = 0.0;
+            for (int i = 0; i < a.n; ++i)
+                for (int k = 0; k < a.bands; ++k) t += static_cast<double>(p[(static_cast<int64_t>(i) * a.bands + k) * FT7_W]);
+            s = static_cast<float>(t);
+        }
+    } else if (var.kind == FT_SUM) {
         const float* p = a.part + var.src + le;
 #pragma unroll 8
         for (int i = 0; i < a.n; ++i) s += p[i * a.rec];             // (the loads do not depend on the sum: eight are in flight)
@@ -524,13 +624,18 @@ struct FtVarHost {
 
 struct rn_ft {
     int device = 0, max_batch = 0, nc = 0;
+    int depth = 2;                                 // trained conv stages: 2 (feature s7.bn) or 3 (feature s6.bn)
     rn_ft_config cfg{};
     hipStream_t stream = nullptr;
-    int S7 = 0, C8 = 0, S8 = 0, C9 = 0, S9 = 0;
+    int S6 = 0, C7 = 0, S7 = 0, C8 = 0, S8 = 0, C9 = 0, S9 = 0;
     std::vector<FtVarHost> vars;
     int n_param = 0;                               // floats of the parameter slab (every variable padded to 4 floats)
     FtItemArgs item{};                             // everything but the per-call fields
     FtUpdateArgs upd{};
+    // depth 3 (the base parts of item7 / upd7 are copied from item / upd at every call)
+    FtItemArgs7 item7{};
+    FtUpdateArgs7 upd7{};
+    Ft7Args s7{};
     float *d_P = nullptr, *d_G = nullptr, *d_M = nullptr, *d_V = nullptr, *d_F = nullptr, *d_rlerp = nullptr;
     int32_t* d_rtab = nullptr;
     float *d_ws = nullptr, *d_part = nullptr;
@@ -596,6 +701,8 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
             }
             out[i] = side;
         }
+        ft->S6 = out[ns - 4];
+        ft->C7 = conv[ns - 3];
         ft->S7 = out[ns - 3];
         ft->C8 = conv[ns - 2];
         ft->S8 = out[ns - 2];
@@ -638,10 +745,29 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
         return off;
     };
     // TensorFlow numbers its variables by creation: conv stage i is conv2d_i; BNs count every stage's and every residual add's
+    const bool d3 = ft->depth == 3;
     int bn_index = 0;
-    for (int i = 0; i < ns - 2; ++i) bn_index += w->stages[i].gamma2 ? 2 : 1;
+    for (int i = 0; i < ns - (d3 ? 3 : 2); ++i) bn_index += w->stages[i].gamma2 ? 2 : 1;
     FtItemArgs& a = ft->item;
     FtUpdateArgs& u = ft->upd;
+    if (d3) {
+        if (const char* why = rn_ft7_geometry_reason(ft->S6, ft->C7, ft->S7)) {
+            rn_set_error("rn_ft_create_depth: not supported on this graph (%s)", why);
+            return RN_E_INVALID;
+        }
+        // conv 7's kernel, its BN's gamma and beta: in front of the others, as the checkpoint orders them
+        const rn_conv_stage& st7 = w->stages[ns - 3];
+        Ft7Args& s = ft->s7;
+        FtUpdateArgs7& u7 = ft->upd7;
+        s.o_w7 = put_var(suffix("conv2d", ns - 3) + "/kernel", st7.kernel, FT7_W);
+        s.o_g7 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st7.gamma, FT_C);
+        s.o_b7 = put_var(suffix("batch_normalization", bn_index) + "/beta", st7.beta, FT_C);
+        s.f_bn7 = put_frozen(st7.mean, st7.variance, FT_C);
+        ++bn_index;
+        u7.v7[0] = FtVarDev{s.o_w7, FT7_W, FT_BANDS, 0, 0, 0};
+        u7.v7[1] = FtVarDev{s.o_g7, FT_C, FT_SUM, 0, 0, 0};             // (src: the record's p_bn7, taken below)
+        u7.v7[2] = FtVarDev{s.o_b7, FT_C, FT_SUM, 0, 0, 0};
+    }
     // the partials record of one item
     int rec = 0;
     auto take = [&](int cnt) {
@@ -663,6 +789,11 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
     a.p_bn8 = take(2 * FT_C);
     a.p_bn9 = take(2 * FT_C);
     a.p_bn9b = take(2 * FT_C);
+    if (d3) {
+        ft->item7.p_bn7 = take(2 * FT_C);
+        ft->upd7.v7[1].src = ft->item7.p_bn7;
+        ft->upd7.v7[2].src = ft->item7.p_bn7 + FT_C;
+    }
     a.o_w8 = put_var(suffix("conv2d", ns - 2) + "/kernel", st8.kernel, FT_W);
     add_upd(a.o_w8, FT_W, FT_SUM, a.p_w8, 0, 0);
     a.o_g8 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st8.gamma, FT_C);
@@ -747,6 +878,10 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
     a.off_fl = a.off_xh9b + n9;
     a.off_gfl = a.off_fl + n9;
     a.ws_item = a.off_gfl + n9;
+    if (d3) {
+        ft->item7.off_gadd = a.ws_item;
+        a.ws_item += n9;
+    }
     if ((rc = ft_zeroed(ft, nb * a.ws_item, &ft->d_ws)) != RN_OK) return rc;
     if ((rc = ft_zeroed(ft, nb * static_cast<size_t>(rec), &ft->d_part)) != RN_OK) return rc;
     if ((rc = ft_zeroed(ft, nb, &ft->d_item_loss)) != RN_OK) return rc;
@@ -780,7 +915,54 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
     u.eps = ft->cfg.epsilon;
     u.item_loss = ft->d_item_loss;
     u.l2sum = ft->d_l2sum;
+    if (d3) {
+        // stage 7's per-step workspace, and one weight-gradient partial per (item, band) for the batch size that needs the most
+        Ft7Args& s = ft->s7;
+        const size_t n7 = static_cast<size_t>(ft->S7) * ft->S7 * FT_C;
+        size_t nparts = 0;
+        for (int b = 1; b <= ft->max_batch; ++b) {
+            int bf, rf, bb, rb;
+            rn_ft7_bands(b, ft->C7, ft->S7, &bf, &rf, &bb, &rb);
+            nparts = std::max(nparts, static_cast<size_t>(b) * bb);
+        }
+        float *d_pre = nullptr, *d_xh7 = nullptr, *d_x7 = nullptr, *d_dp7 = nullptr, *d_part7 = nullptr;
+        if ((rc = ft_zeroed(ft, nb * ft->C7 * ft->C7 * FT_C, &d_pre)) != RN_OK) return rc;
+        if ((rc = ft_zeroed(ft, nb * n7, &d_xh7)) != RN_OK) return rc;
+        if ((rc = ft_zeroed(ft, nb * n7, &d_x7)) != RN_OK) return rc;
+        if ((rc = ft_zeroed(ft, nb * n7, &d_dp7)) != RN_OK) return rc;
+        if ((rc = ft_zeroed(ft, nparts * FT7_W, &d_part7)) != RN_OK) return rc;
+        s.S6 = ft->S6;
+        s.C7 = ft->C7;
+        s.S7 = ft->S7;
+        s.P = ft->d_P;
+        s.F = ft->d_F;
+        s.pre = d_pre;
+        s.xh7 = d_xh7;
+        s.x7 = d_x7;
+        s.dpool = d_dp7;
+        s.part = d_part7;
+        ft->item7.x7ws = d_x7;
+        ft->item7.xh7 = d_xh7;
+        ft->item7.dpool7 = d_dp7;
+        ft->item7.o_g7 = s.o_g7;
+        ft->item7.f_bn7 = s.f_bn7;
+        ft->upd7.part7 = d_part7;
+    }
     return RN_OK;
+}
+
+// the depth-3 arguments of one call: the trainer's own, over the base this call filled in
+FtItemArgs7 ft_item7(const rn_ft* ft, const FtItemArgs& base) {
+    FtItemArgs7 a = ft->item7;
+    static_cast<FtItemArgs&>(a) = base;
+    return a;
+}
+
+FtUpdateArgs7 ft_upd7(const rn_ft* ft, const FtUpdateArgs& base, int bands) {
+    FtUpdateArgs7 u = ft->upd7;
+    static_cast<FtUpdateArgs&>(u) = base;
+    u.bands = bands;
+    return u;
 }
 
 double ft_learn_rate(const rn_ft_config& c, int64_t step) {
@@ -789,7 +971,8 @@ double ft_learn_rate(const rn_ft_config& c, int64_t step) {
 
 }  // namespace
 
-extern "C" int rn_ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, rn_ft** out) {
+namespace {
+int ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, int depth, rn_ft** out) {
     if (!w || !cfg || !out || !w->stages || !w->dense) {
         rn_set_error("rn_ft_create: null argument");
         return RN_E_INVALID;
@@ -826,6 +1009,7 @@ extern "C" int rn_ft_create(const rn_weights* w, int device, int max_batch, cons
     ft->max_batch = max_batch;
     ft->nc = w->num_classes;
     ft->cfg = *cfg;
+    ft->depth = depth;
     int rc = RN_OK;
     if (hipStreamCreateWithFlags(&ft->stream, hipStreamNonBlocking) != hipSuccess) {
         (void)hipGetLastError();
@@ -844,6 +1028,28 @@ extern "C" int rn_ft_create(const rn_weights* w, int device, int max_batch, cons
     }
     *out = ft;
     return RN_OK;
+}
+}  // namespace
+
+extern "C" int rn_ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, rn_ft** out) {
+    return ft_create(w, device, max_batch, cfg, 2, out);
+}
+
+extern "C" int rn_ft_create_depth(const rn_weights* w, int device, int max_batch, const rn_ft_config* cfg, int depth, rn_ft** out) {
+    if (depth != 2 && depth != 3) {
+        if (out) *out = nullptr;
+        rn_set_error("rn_ft_create_depth: depth = %d is neither 2 (features s7.bn) nor 3 (features s6.bn)", depth);
+        return RN_E_INVALID;
+    }
+    return ft_create(w, device, max_batch, cfg, depth, out);
+}
+
+extern "C" int rn_ft_depth(const rn_ft* ft) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    return ft->depth;
 }
 
 extern "C" void rn_ft_destroy(rn_ft* ft) {
@@ -954,6 +1160,13 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     u.n = batch;
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
     const int ublocks = (ft->n_param + 255) / 256;
+    const bool d3 = ft->depth == 3;
+    Ft7Args s7 = ft->s7;
+    if (d3) {
+        s7.feats = d_feats;
+        s7.index = d_index;
+        rn_ft7_bands(batch, ft->C7, ft->S7, &s7.bands_f, &s7.rows_f, &s7.bands_b, &s7.rows_b);
+    }
     ft->timed = false;
     RN_HIP(hipEventRecord(ft->ev0, ft->stream));
     for (int s = 0; s < steps; ++s) {
@@ -962,10 +1175,21 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
         u.lr_t = static_cast<float>(lr * std::sqrt(1.0 - std::pow(b2, static_cast<double>(t))) / (1.0 - std::pow(b1, static_cast<double>(t))));
         u.loss_out = ft->d_losses + s;
         a.base = static_cast<int64_t>(s) * batch;
-        hipLaunchKernelGGL(ft_item_kernel<true>, dim3(batch), dim3(FT_NT), 0, ft->stream, a);
-        RN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(ft_update_kernel, dim3(ublocks), dim3(256), 0, ft->stream, u);
-        RN_CHECK_LAUNCH();
+        if (d3) {
+            int rc;
+            s7.base = a.base;
+            if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
+            hipLaunchKernelGGL((ft_item_kernel<true, FtItemArgs7>), dim3(batch), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));
+            RN_CHECK_LAUNCH();
+            if ((rc = rn_ft7_backward(ft->stream, s7, batch)) != RN_OK) return rc;
+            hipLaunchKernelGGL(ft_update_kernel<FtUpdateArgs7>, dim3(ublocks), dim3(256), 0, ft->stream, ft_upd7(ft, u, s7.bands_b));
+            RN_CHECK_LAUNCH();
+        } else {
+            hipLaunchKernelGGL((ft_item_kernel<true, FtItemArgs>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
+            RN_CHECK_LAUNCH();
+            hipLaunchKernelGGL(ft_update_kernel<FtUpdateArgs>, dim3(ublocks), dim3(256), 0, ft->stream, u);
+            RN_CHECK_LAUNCH();
+        }
         ++ft->steps_done;
     }
     RN_HIP(hipEventRecord(ft->ev1, ft->stream));
@@ -1009,7 +1233,18 @@ extern "C" int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labe
         a.base = i;
         a.probs = ft->d_probs;
         a.ids = ft->d_ids;
-        hipLaunchKernelGGL(ft_item_kernel<false>, dim3(m), dim3(FT_NT), 0, ft->stream, a);
+        if (ft->depth == 3) {
+            Ft7Args s7 = ft->s7;
+            s7.feats = d_feats;
+            s7.index = nullptr;
+            s7.base = i;
+            rn_ft7_bands(m, ft->C7, ft->S7, &s7.bands_f, &s7.rows_f, &s7.bands_b, &s7.rows_b);
+            int rc;
+            if ((rc = rn_ft7_forward(ft->stream, s7, m)) != RN_OK) return rc;
+            hipLaunchKernelGGL((ft_item_kernel<false, FtItemArgs7>), dim3(m), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));
+        } else {
+            hipLaunchKernelGGL((ft_item_kernel<false, FtItemArgs>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
+        }
         RN_CHECK_LAUNCH();
         if (probs) RN_HIP(hipMemcpyAsync(probs + i * ft->nc, ft->d_probs, static_cast<size_t>(m) * ft->nc * 4, hipMemcpyDeviceToHost, ft->stream));
         if (ids) RN_HIP(hipMemcpyAsync(ids + i, ft->d_ids, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, ft->stream));

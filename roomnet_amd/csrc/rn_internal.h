@@ -150,6 +150,7 @@ struct rn_handle {
     void* f32m = nullptr;        // plan of the float32 matrix-core stage kernels (rn_stage_f32m.hip)
     void* gradcam = nullptr;     // what the grad-CAM adjoint keeps from rn_create + its device workspace (rn_gradcam.hip)
     float* d_feat = nullptr;     // rn_features_u8: float32 staging of s7.bn, [max_batch, S7, S7, 16] (allocated by the first call)
+    float* d_feat6 = nullptr;    // rn_features_depth_u8, depth 3: float32 staging of s6.bn, [max_batch, S6, S6, 128] (the same)
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the

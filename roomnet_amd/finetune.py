@@ -1,6 +1,9 @@
-"""Host side of fine-tuning stages 8-9 and the dense head (``RoomNet.fine_tune``, C ABI ``rn_ft_*``): which variables are
+"""Host side of fine-tuning the last conv stages and the dense head (``RoomNet.fine_tune``, C ABI ``rn_ft_*``): which variables are
 trained, the learning-rate schedule, the minibatch order and a NumPy statement of the Adam rule.  Pure host code; the
-mathematics is stated once in the header of ``csrc/rn_finetune.hip``."""
+mathematics is stated once in the headers of ``csrc/rn_finetune.hip`` and ``csrc/rn_finetune7.hip``.
+
+The *depth* of a trainer or a feature is its number of trained conv stages: 2 trains stages 8-9 on cached ``s7.bn`` (28 KB per
+image at 224), 3 trains the whole last block, stages 7-9, on cached ``s6.bn`` (1.08 MB per image at 224)."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -13,11 +16,21 @@ DECAY_RATE = 0.068                       # network.py:36
 ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults
 
 
-def trained_variables(graph: Graph) -> List[str]:
-    """Checkpoint names of the variables ``rn_ft_*`` trains, in the trainer's order: the last two conv stages' kernels and BN
-    gamma / beta (both BNs of the residual stage), then per dense layer its kernel and its BN's gamma / beta or its bias."""
+DEPTHS = (2, 3)
+
+
+def _checked_depth(depth) -> int:
+    if depth not in DEPTHS:
+        raise ValueError("depth = %r is neither 2 (features s7.bn) nor 3 (features s6.bn)" % (depth,))
+    return int(depth)
+
+
+def trained_variables(graph: Graph, depth: int = 2) -> List[str]:
+    """Checkpoint names of the variables ``rn_ft_*`` trains, in the trainer's order: the last ``depth`` conv stages' kernels and BN
+    gamma / beta (both BNs of the residual stage), then per dense layer its kernel and its BN's gamma / beta or its bias: 19
+    names at depth 2, 22 at depth 3 for the reference graph."""
     names = []
-    for s in graph.stages[-2:]:
+    for s in graph.stages[-_checked_depth(depth):]:
         names.append(s.conv_name + "/kernel")
         for bn in (s.bn_name, s.bn2_name):
             if bn:
@@ -31,10 +44,21 @@ def trained_variables(graph: Graph) -> List[str]:
     return names
 
 
-def feature_shape(graph: Graph) -> Tuple[int, int, int]:
-    """Per-image shape of the cached feature ``s7.bn``: the output of the last block's first step."""
-    s = graph.stages[-3]
+def feature_shape(graph: Graph, depth: int = 2) -> Tuple[int, int, int]:
+    """Per-image shape of the cached feature: the input of the first trained stage.  Depth 2: ``s7.bn``, the output of the last
+    block's first step (21 x 21 x 16 at 224: 28 KB in float32); depth 3: ``s6.bn``, the input of the last block (46 x 46 x 128 at
+    224: 1.08 MB)."""
+    s = graph.stages[-_checked_depth(depth) - 1]
     return s.out_side, s.out_side, s.cout
+
+
+def depth_of_features(graph: Graph, shape) -> int:
+    """The depth whose feature has the per-image ``shape``; ``ValueError`` when neither has."""
+    for depth in DEPTHS:
+        if tuple(shape) == feature_shape(graph, depth):
+            return depth
+    raise ValueError("features of per-image shape %s match neither depth 2 %s nor depth 3 %s"
+                     % (tuple(shape), feature_shape(graph, 2), feature_shape(graph, 3)))
 
 
 def learn_rate_at(step, learn_rate, num_steps, decay_rate=DECAY_RATE):

@@ -263,18 +263,19 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None):
     return nn.recalibrate_bn(batches(), momentum=momentum)
 
 
-def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64):
+def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2):
     """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
     infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
     batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
-    features.  ``val_list_fpath``: a second list evaluated after the last step.  Returns what ``fine_tune`` returns."""
+    features.  ``val_list_fpath``: a second list evaluated after the last step.  ``depth=3`` trains the whole last conv block on
+    cached ``s6.bn`` (1.08 MB per image at 224, against 28 KB at depth 2).  Returns what ``fine_tune`` returns."""
     def features_of(path):
         fpaths, labels, _n = read_fpaths(path)
         feats, kept, pending = [], [], []
 
         def flush():
             if pending:
-                feats.append(nn.extract_features([p[1] for p in pending]))
+                feats.append(nn.extract_features([p[1] for p in pending], depth=depth))
                 kept.extend(labels[p[0]] for p in pending)
                 pending.clear()
 
@@ -292,7 +293,7 @@ def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_f
 
     feats, labels = features_of(list_fpath)
     val = features_of(val_list_fpath) if val_list_fpath else None
-    return nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val)
+    return nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val, depth=depth)
 
 
 if __name__ == '__main__':

@@ -9,8 +9,8 @@ Kept from the reference (same names, argument meaning, return shapes/dtypes):
 Batch-statistics BN, the forward pass of the reference's default ``compute_bn_mean_var=True`` model, arrives through
 ``infer_batch_stats`` and ``recalibrate_bn`` (the constructor still refuses the flag: that model is the training graph).
 Whole-network training (``train_step``, loss/optimizer graph, ``network.py:49-85,158-170``) is out
-of scope and raises ``NotImplementedError``; ``extract_features`` + ``fine_tune`` train the last two conv stages and the
-dense head on the GPU, from cached ``s7.bn`` features.
+of scope and raises ``NotImplementedError``; ``extract_features`` + ``fine_tune`` train the last two or three conv stages and the
+dense head on the GPU, from cached ``s7.bn`` (or ``s6.bn``) features.
 
 MI355X-only keyword arguments (not in the reference): ``device``, ``dtype``
 ("f32" | "bf16" | "f16"), ``max_batch``.
@@ -439,11 +439,16 @@ class RoomNet:
         return new
 
     # ------------------------------------------------------------ fine-tuning
-    def extract_features(self, im_in):
+    def extract_features(self, im_in, depth=2):
         """The features ``fine_tune`` trains on: ``s7.bn``, the output of the last block's first step (21 x 21 x 16 at 224, 68 x 68 x
-        16 at 600), of every image as float32 ``[N, S7, S7, 16]`` (``rn_features_u8``).  ``im_in`` as ``grad_cam`` takes it: an
+        16 at 600), of every image as float32 ``[N, S7, S7, 16]`` (``rn_features_u8``).  ``depth=3``: ``s6.bn``, the input of the
+        last block (46 x 46 x 128 at 224, 140 x 140 x 128 at 600), for training the whole block, stage 7 included
+        (``rn_features_depth_u8``); that cache costs 1.08 MB per image at 224, against 28 KB at depth 2.
+        ``im_in`` as ``grad_cam`` takes it: an
         ``[N,S,S,3]`` BGR batch, one BGR ``[H,W,3]`` image, or a list of images of any size (centre-cropped and resized as
         ``infer_images`` does).  Everything behind these features depends on them alone, so a training set is extracted once."""
+        from . import finetune
+        depth = finetune._checked_depth(depth)
         if isinstance(im_in, np.ndarray) and im_in.ndim == 3:
             im_in = [im_in]
         if isinstance(im_in, np.ndarray) and im_in.ndim != 4:
@@ -455,15 +460,18 @@ class RoomNet:
                 im = im.astype(np.uint8)
             else:
                 raise ValueError("extract_features takes uint8 images (or integral values in [0, 255]), got %s" % im.dtype)
-        return self._engine().features_u8(im)
+        return self._engine().features_u8(im, depth=depth)
 
-    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None):
+    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None):
         """Train stages 8 and 9 and the dense head on cached features, on the GPU (``rn_ft_*``; not the reference's whole-network
         ``train_step``): stages 0-7 stay as loaded, every BN keeps its moving statistics and trains gamma and beta (the
         reference's shipped configuration, train.py:40-41), Adam with the constructor's ``learn_rate``, ``num_steps`` (decay),
         ``l2_regularizer_coeff`` and ``start_step``.  ``features``: float32 ``[N, S7, S7, 16]`` of ``extract_features``;
         ``labels``: N class ids; minibatches of ``batch_size`` in the reference feeder's order (``finetune.epoch_indices``, a
         fresh shuffle per epoch from ``seed`` and the current step).  ``val``: ``(features, labels)`` evaluated after the last step.
+        The depth is taken from the features' shape: ``[N, S6, S6, 128]`` of ``extract_features(..., depth=3)`` trains stage 7 as
+        well, the whole last conv block (that cache is 1.08 MB per image at 224, against 28 KB at depth 2); a shape of neither
+        depth, or one that contradicts an explicit ``depth``, raises ``ValueError``.
         The trained variables are written back through ``set_variables`` (the next ``infer`` builds its engine on them, ``save()``
         writes them) and ``self.step`` advances.  Returns ``{"losses": float32[steps] (each before its update), "step",
         "learn_rate" (at the new step), "val": (loss, accuracy) or None}``.  Adam's slots start at zero in every call."""
@@ -475,17 +483,26 @@ class RoomNet:
             raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
         feats = np.ascontiguousarray(features, np.float32)
         labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
-        shape = finetune.feature_shape(self.graph)
+        if depth is not None:
+            shape = finetune.feature_shape(self.graph, depth)
+        elif feats.ndim == 4:
+            try:
+                depth = finetune.depth_of_features(self.graph, feats.shape[1:])
+            except ValueError as e:
+                raise ValueError("fine_tune: %s" % e) from None
+            shape = finetune.feature_shape(self.graph, depth)
+        else:
+            depth, shape = 2, finetune.feature_shape(self.graph)
         if feats.ndim != 4 or feats.shape[1:] != shape or feats.shape[0] != labels.shape[0] or feats.shape[0] < 1:
-            raise ValueError("fine_tune: features %s and labels %s do not form [N, %d, %d, %d] and [N]"
-                             % (feats.shape, labels.shape, shape[0], shape[1], shape[2]))
+            raise ValueError("fine_tune: features %s and labels %s do not form [N, %d, %d, %d] and [N] (depth %d)"
+                             % (feats.shape, labels.shape, shape[0], shape[1], shape[2], depth))
         steps = int(steps)
         if steps < 1:
             raise ValueError("fine_tune: steps = %d" % steps)
         index = finetune.epoch_indices(feats.shape[0], batch_size, steps, seed=[int(seed), int(self.step)])
         tr = Trainer(self.graph, self.sess.variables, device=self.device, max_batch=max(index.shape[1], min(self.max_batch, 256)),
                      learn_rate=self.learn_rate, num_steps=self.num_steps, start_step=self.step,
-                     l2_coeff=self.l2_regularizer_coeff)
+                     l2_coeff=self.l2_regularizer_coeff, depth=depth)
         try:
             losses = tr.run_host(feats, labels, index)
             out_val = None

@@ -4,9 +4,13 @@
   - features/s of rn_features_u8_device at 256 x 224 x 224 bf16 beside images/s of rn_forward_u8_device on the same handle;
   - ms per step of the float32 torch restatement (tests/finetune_ref.py) on 16 CPU threads, batch 45 at 224: what a user has today.
 
-    python tools/bench_finetune.py [--steps 200] [--runs 5]
-    rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py --trace-run
-    python tools/bench_finetune.py --summarise DIR/.../kt_kernel_trace.csv [--out profiles/finetune_kernel_stats.txt]
+--depth 3 measures the trainer of the whole last conv block on cached s6.bn (rn_ft_create_depth: four launches per step, 256 resident
+items at 224 and 48 at 600 -- an item is 1.08 MB and 10 MB) against the float32 torch restatement tests/finetune7_ref.py, and states
+each step against its arithmetic floor.  --lib PATH measures another build of the library (depth 2 of the commit before, say).
+
+    python tools/bench_finetune.py [--depth 3] [--steps 200] [--runs 5] [--steps-only] [--lib PATH]
+    rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py [--depth 3] --trace-run
+    python tools/bench_finetune.py [--depth 3] --summarise DIR/.../kt_kernel_trace.csv [--out profiles/finetune_kernel_stats.txt]
 """
 import argparse
 import csv
@@ -23,6 +27,13 @@ sys.path.insert(0, ROOT)
 
 CASES = ((224, 45), (224, 256), (600, 45))
 N_ITEMS = 512
+KERNELS = {2: ("ft_item_kernel", "ft_update_kernel"), 3: ("ft7_fwd_kernel", "ft_item_kernel", "ft7_bwd_kernel", "ft_update_kernel")}
+F32_MFMA_TFLOPS = 155.0                          # float32 MFMA = the float32 vector rate (measured peak of the part)
+HBM_TBPS = 6.0
+
+
+def n_items_of(side, depth):
+    return N_ITEMS if depth == 2 else (256 if side == 224 else 48)
 
 
 def _weights(side):
@@ -36,29 +47,47 @@ def _weights(side):
     return g, w
 
 
-def _data(g, n_items=N_ITEMS):
+def _data(g, n_items=N_ITEMS, depth=2):
     from roomnet_amd import finetune
     rng = np.random.default_rng(7)
-    feats = (rng.standard_normal((n_items,) + finetune.feature_shape(g)) * 0.5).astype(np.float32)
+    shape = finetune.feature_shape(g, depth) if depth != 2 else finetune.feature_shape(g)
+    feats = (rng.standard_normal((n_items,) + shape, dtype=np.float32) * np.float32(0.5)) if depth != 2 else \
+        (rng.standard_normal((n_items,) + shape) * 0.5).astype(np.float32)
     labels = rng.integers(0, 6, n_items).astype(np.int32)
     return feats, labels
 
 
-def step_case(side, batch, steps, runs):
+def step_floor(g, batch):
+    """Arithmetic floor of a depth-3 step: conv 7 forward and its weight gradient on the float32 matrix cores, and one read of the
+    minibatch's cached features from HBM."""
+    s7 = g.stages[-3]
+    flop = 2 * 2.0 * batch * s7.conv_side ** 2 * 9 * s7.cin * s7.cout
+    cache = 4.0 * batch * g.stages[-4].out_side ** 2 * s7.cin
+    return {"conv7_gflop": round(flop / 1e9, 2), "mfma_floor_us": round(flop / F32_MFMA_TFLOPS / 1e6, 1),
+            "cache_read_mb": round(cache / 1e6, 1), "hbm_floor_us": round(cache / HBM_TBPS / 1e6, 1)}
+
+
+def step_case(side, batch, steps, runs, depth=2, lib=None):
     from roomnet_amd import _capi, finetune
     g, w = _weights(side)
-    feats, labels = _data(g)
-    index = finetune.epoch_indices(N_ITEMS, batch, steps, seed=1)
-    tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06)
+    n_items = n_items_of(side, depth)
+    feats, labels = _data(g, n_items, depth)
+    index = finetune.epoch_indices(n_items, batch, steps, seed=1)
+    kw = {"depth": depth} if depth != 2 else {}
+    tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06, lib_path=lib, **kw)
     try:
         d = [tr.upload(feats), tr.upload(labels), tr.upload(index)]
-        tr.run(d[0], d[1], N_ITEMS, d[2], batch, steps)            # warm-up
+        del feats
+        tr.run(d[0], d[1], n_items, d[2], batch, steps)            # warm-up
         us = []
         for _ in range(runs):
-            tr.run(d[0], d[1], N_ITEMS, d[2], batch, steps)
+            tr.run(d[0], d[1], n_items, d[2], batch, steps)
             us.append(tr.last_run_ms() * 1e3 / steps)
-        return {"side": side, "batch": batch, "steps_per_run": steps, "us_per_step": round(statistics.median(us), 2),
-                "us_per_step_min": round(min(us), 2), "us_per_step_max": round(max(us), 2)}
+        out = {"side": side, "batch": batch, "depth": depth, "steps_per_run": steps, "us_per_step": round(statistics.median(us), 2),
+               "us_per_step_min": round(min(us), 2), "us_per_step_max": round(max(us), 2)}
+        if depth == 3:
+            out["floor"] = step_floor(g, batch)
+        return out
     finally:
         tr.close()
 
@@ -100,52 +129,58 @@ def features_case(steps=20, warmup=5):
         eng.close()
 
 
-def torch_case(batch=45, steps=5, threads=16):
+def torch_case(batch=45, steps=5, threads=16, depth=2):
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from finetune_ref import FineTuneRef
+    from finetune7_ref import FineTune7Ref
     from roomnet_amd import finetune
     torch.set_num_threads(threads)
     g, w = _weights(224)
-    feats, labels = _data(g)
-    index = finetune.epoch_indices(N_ITEMS, batch, steps + 1, seed=1)
-    ref = FineTuneRef(w, 6, 224, dtype=torch.float32)
+    n_items = n_items_of(224, depth)
+    feats, labels = _data(g, n_items, depth)
+    index = finetune.epoch_indices(n_items, batch, steps + 1, seed=1)
+    ref = (FineTuneRef if depth == 2 else FineTune7Ref)(w, 6, 224, dtype=torch.float32)
     ref.train(feats, labels, index[:1], 2e-4, 10000, 0.06)
     t0 = time.perf_counter()
     ref.train(feats, labels, index[1:], 2e-4, 10000, 0.06)
     return {"side": 224, "batch": batch, "threads": threads, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 2)}
 
 
-def trace_run():
+def trace_run(depth=2):
     for side, batch in CASES:
-        step_case(side, batch, TRACE_STEPS, 1)
+        step_case(side, batch, TRACE_STEPS, 1, depth)
 
 
 TRACE_STEPS = 20                                  # steps per rn_ft_run of --trace-run (a warm-up run and a measured one per case)
 
 
-def summarise(trace_csv):
+def summarise(trace_csv, depth=2):
+    kernels = KERNELS[depth]
     rows = []
     for r in csv.DictReader(open(trace_csv)):
-        for key in ("ft_item_kernel", "ft_update_kernel"):
+        for key in kernels:
             if key in r["Kernel_Name"]:
-                rows.append((int(r["Start_Timestamp"]), key, int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1),
+                wgs = int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1) * max(int(r.get("Grid_Size_Y") or 1), 1)
+                rows.append((int(r["Start_Timestamp"]), key, wgs,
                              (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     rows.sort()
-    per_case = 2 * 2 * TRACE_STEPS                # the cases run one after the other: two runs x two launches per step
+    per_case = 2 * len(kernels) * TRACE_STEPS     # the cases run one after the other: two runs x the launches of a step
     if len(rows) != per_case * len(CASES):
         raise SystemExit("expected %d ft_* launches (%d cases), found %d" % (per_case * len(CASES), len(CASES), len(rows)))
-    lines = ["# rocprofv3 --kernel-trace --stats -- python tools/bench_finetune.py --trace-run (one MI355X, its own run)",
-             "# the two launches of an Adam step per case: workgroups, calls, median / max duration in us, and the step's sum",
+    lines = ["# rocprofv3 --kernel-trace --stats -- python tools/bench_finetune.py%s --trace-run (one MI355X, its own run)"
+             % (" --depth 3" if depth == 3 else ""),
+             "# the %s launches of an Adam step per case: workgroups, calls, median / max duration in us, and the step's sum"
+             % ("two" if depth == 2 else "four"),
              "%5s %6s  %-17s %6s %6s %11s %9s" % ("side", "batch", "kernel", "wgs", "calls", "median_us", "max_us")]
     for ci, (side, batch) in enumerate(CASES):
         total = 0.0
-        for key in ("ft_item_kernel", "ft_update_kernel"):
+        for key in kernels:
             sel = [r for r in rows[ci * per_case:(ci + 1) * per_case] if r[1] == key]
             us = [r[3] for r in sel]
             total += statistics.median(us)
             lines.append("%5d %6d  %-17s %6d %6d %11.1f %9.1f" % (side, batch, key, sel[0][2], len(us), statistics.median(us), max(us)))
-        lines.append("%5d %6d  %-17s %6s %6s %11.1f" % (side, batch, "both", "", "", total))
+        lines.append("%5d %6d  %-17s %6s %6s %11.1f" % (side, batch, "both" if depth == 2 else "all four", "", "", total))
     return "\n".join(lines) + "\n"
 
 
@@ -157,20 +192,29 @@ def main():
     ap.add_argument("--trace-run", action="store_true")
     ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
     ap.add_argument("--out")
+    ap.add_argument("--depth", type=int, default=2, choices=(2, 3), help="trained conv stages: 2 (features s7.bn) or 3 (s6.bn)")
+    ap.add_argument("--lib", help="measure this build of libroomnet_hip.so instead of the package's")
     args = ap.parse_args()
     if not args.summarise:
         import torch  # noqa: F401  (before libroomnet_hip.so is loaded: one HIP runtime in the process, torch's)
     if args.summarise:
-        text = summarise(args.summarise)
+        text = summarise(args.summarise, args.depth)
         if args.out:
             open(args.out, "w").write(text)
         print(text, end="")
         return
     if args.trace_run:
-        trace_run()
+        trace_run(args.depth)
         return
     if args.steps_only:
-        print(json.dumps({"steps": [step_case(s, b, args.steps, args.runs) for s, b in CASES]}))
+        print(json.dumps({"depth": args.depth, "lib": args.lib,
+                          "steps": [step_case(s, b, args.steps, args.runs, args.depth, args.lib) for s, b in CASES]}))
+        return
+    if args.depth == 3:
+        print(json.dumps({"what": "fine-tuning the whole last conv block on cached s6.bn features: us per Adam step (four launches, "
+                                  "enqueued back to back) against its arithmetic floor, and the float32 torch restatement on the CPU",
+                          "steps": [step_case(s, b, args.steps, args.runs, 3, args.lib) for s, b in CASES],
+                          "torch_float32_cpu": torch_case(depth=3)}))
         return
     print(json.dumps({"what": "fine-tuning on cached s7.bn features: us per Adam step (two launches, enqueued back to back), feature "
                               "extraction beside the plain forward pass, and the float32 torch restatement on the CPU",

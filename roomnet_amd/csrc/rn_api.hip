@@ -29,17 +29,49 @@ extern "C" int rn_device_count(void) {
 }
 
 // ------------------------------------------------------------------------ helpers
-int dev_alloc(rn_handle* h, size_t bytes, void** out) {
+DeviceGuard::DeviceGuard() {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+}
+DeviceGuard::DeviceGuard(int dev) : DeviceGuard() { ok = hipSetDevice(dev) == hipSuccess; }
+DeviceGuard::~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+// (the failure's status is consumed: it must not come back as the "launch failure" of the thread's next kernel, see RN_HIP)
+int rn_owned_alloc(std::vector<void*>& owner, size_t bytes, size_t min_bytes, void** out) {
     void* p = nullptr;
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&p, bytes);
+    hipError_t e = hipMalloc(&p, bytes ? bytes : min_bytes);
     if (e != hipSuccess) {
         rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        (void)hipGetLastError();
         return RN_E_NOMEM;
     }
-    h->allocs.push_back(p);
+    owner.push_back(p);
     *out = p;
     return RN_OK;
+}
+
+void rn_legacy_resize_table(int in_size, int out_size, int32_t* lo, int32_t* hi, float* lerp) {
+    const float scale = static_cast<float>(in_size) / static_cast<float>(out_size);
+    for (int i = 0; i < out_size; ++i) {
+        const float src = static_cast<float>(i) * scale;
+        lo[i] = static_cast<int32_t>(src);
+        hi[i] = lo[i] + 1 < in_size - 1 ? lo[i] + 1 : in_size - 1;
+        lerp[i] = src - static_cast<float>(lo[i]);
+    }
+}
+
+int rn_stage_sides(const rn_weights* w, std::vector<int>& conv, std::vector<int>& out) {
+    conv.assign(w->n_stages, 0);
+    out.assign(w->n_stages, 0);
+    int side = w->im_side;
+    for (int i = 0; i < w->n_stages; ++i) {
+        const int pool_k = w->stages[i].pool_k, pool_s = w->stages[i].pool_s;
+        conv[i] = side - 2;
+        if (conv[i] < 1 || (pool_k && (conv[i] < pool_k || pool_s < 1))) return i;
+        out[i] = side = pool_k ? (conv[i] - pool_k) / pool_s + 1 : conv[i];
+    }
+    return w->n_stages;
 }
 
 RelabelledWeights::RelabelledWeights(const rn_weights* src) : w(*src), stages(src->stages, src->stages + src->n_stages) {
@@ -76,18 +108,6 @@ void RelabelledWeights::permute_cins(int stage, const std::vector<int>& pi) {
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 int upload_bn(rn_handle* h, int c, const float* gamma, const float* beta, const float* mean, const float* var,
               float eps, BnDev* out) {
     std::vector<float> inv(c);
@@ -99,17 +119,10 @@ int upload_bn(rn_handle* h, int c, const float* gamma, const float* beta, const 
     return RN_OK;
 }
 
-// TF-1.13 compute_interpolation_weights, align_corners=False, no half-pixel centres
 int upload_resize_tab(rn_handle* h, int in_size, int out_size, ResizeTab* rt) {
     std::vector<int32_t> lo(out_size), hi(out_size);
     std::vector<float> lerp(out_size);
-    const float scale = static_cast<float>(in_size) / static_cast<float>(out_size);
-    for (int i = out_size - 1; i >= 0; --i) {
-        const float src = static_cast<float>(i) * scale;
-        lo[i] = static_cast<int32_t>(src);
-        hi[i] = lo[i] + 1 < in_size - 1 ? lo[i] + 1 : in_size - 1;
-        lerp[i] = src - static_cast<float>(lo[i]);
-    }
+    rn_legacy_resize_table(in_size, out_size, lo.data(), hi.data(), lerp.data());
     int rc;
     if ((rc = upload(h, lo.data(), out_size, &rt->lo)) != RN_OK) return rc;
     if ((rc = upload(h, hi.data(), out_size, &rt->hi)) != RN_OK) return rc;
@@ -192,6 +205,8 @@ int build_plan(rn_handle* h, const rn_weights* w) {
     int side = w->im_side, ch = 3, rc;
     h->node_input = add_node(h, "input", side, side, 3);
     char name[RN_NAME_LEN];
+    std::vector<int> conv_side, out_side;
+    const int n_fit = rn_stage_sides(w, conv_side, out_side);
     for (int i = 0; i < w->n_stages; ++i) {
         const rn_conv_stage& s = w->stages[i];
         if (s.cin != ch || s.cout < 1 || s.cout > 512 || !s.kernel || !s.gamma || !s.beta || !s.mean ||
@@ -203,14 +218,14 @@ int build_plan(rn_handle* h, const rn_weights* w) {
         p.cin = s.cin;
         p.cout = s.cout;
         p.in_side = side;
-        p.conv_side = side - 2;
         p.pool_k = s.pool_k;
         p.pool_s = s.pool_k ? s.pool_s : 1;
-        if (p.conv_side < 1 || (p.pool_k && (p.conv_side < p.pool_k || p.pool_s < 1))) {
+        if (i >= n_fit) {
             rn_set_error("stage %d: im_side too small for this graph", i);
             return RN_E_INVALID;
         }
-        p.out_side = p.pool_k ? (p.conv_side - p.pool_k) / p.pool_s + 1 : p.conv_side;
+        p.conv_side = conv_side[i];
+        p.out_side = out_side[i];
         p.skip_stage = s.skip_stage;
         if (s.skip_stage >= 0) {
             if (s.skip_stage >= i || h->stages[s.skip_stage].cout != s.cout || !s.gamma2 || !s.beta2 ||
@@ -470,6 +485,119 @@ int check_call(rn_handle* h, int n, const void* a, const void* b, const void* c)
     return RN_OK;
 }
 
+// the kernels are gfx950 code sized for its 160 KiB of LDS per CU: refuse anything else up front
+int check_device(int device, int* n_cu) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        rn_set_error("rn_create: no HIP device available");
+        return RN_E_HIP;
+    }
+    if (device < 0 || device >= ndev) {
+        rn_set_error("rn_create: device %d out of range (%d devices)", device, ndev);
+        return RN_E_INVALID;
+    }
+    hipDeviceProp_t prop{};
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
+        rn_set_error("rn_create: hipGetDeviceProperties(%d) failed", device);
+        return RN_E_HIP;
+    }
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 || prop.maxSharedMemoryPerMultiProcessor < 160 * 1024) {
+        rn_set_error("rn_create: device %d is %s with %zu bytes of LDS per CU; this library is built for gfx950 (MI355X, 160 KiB)",
+                     device, prop.gcnArchName, static_cast<size_t>(prop.maxSharedMemoryPerMultiProcessor));
+        return RN_E_INVALID;
+    }
+    *n_cu = prop.multiProcessorCount;
+    return RN_OK;
+}
+
+// The frozen-channel folds of a float32 handle (rn_create): the stage each applies to (-1: none) and its channel relabelling.
+struct F32Folds {
+    int fold_r = -1;                 // the 64 -> 64 residual stage whose second 32-cout tile is all frozen
+    std::vector<int> fold_pi;
+    int kfold_r = -1;                // the stage whose last input channels are frozen
+    std::vector<int> kfold_pi;
+    int kfold_live = 0, kfold_proven = 0;
+};
+
+// relabelling of `n` channels that puts the first `keep` of `frozen` behind all the others, those in ascending order
+std::vector<int> frozen_last(int n, std::vector<int> frozen, size_t keep) {
+    frozen.resize(keep);
+    std::vector<int> pi;
+    for (int c = 0; c < n; ++c)
+        if (std::find(frozen.begin(), frozen.end(), c) == frozen.end()) pi.push_back(c);
+    pi.insert(pi.end(), frozen.begin(), frozen.end());
+    return pi;
+}
+
+// ---- float32 handles on the matrix-core path: frozen first-BN channels of a 64 -> 64 residual stage (stage 5).  The stage
+// kernels form y1 = ((x * 1/16 - mean) * inv + beta) un-contracted: where |inv| * max(|mean|, |6 - mean|) < 2^-25 |beta| the
+// product vanishes against beta and y1 IS beta for every input (the reference's float32 computes the same expression).  With
+// >= 32 such channels the stage's channels are relabelled on a copy of the weights (stage 4's couts, stage 5's cins + couts,
+// stage 6's cins: the residual pairs channel c of stage 4's output with channel c of stage 5's) so that the second 32-cout
+// tile is all frozen: it is not convolved (rn_f32m_launch runs the residual for it alone).  rn_tap un-relabels.
+F32Folds plan_f32_folds(const rn_weights* w, int dtype, unsigned flags, RelabelledWeights& rw) {
+    F32Folds f;
+    if (dtype != RN_DTYPE_F32 || (flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_BATCH_STATS))) return f;
+    auto frozen_couts = [&](const rn_conv_stage& st) {
+        std::vector<int> frozen;
+        for (int c = 0; c < st.cout; ++c) {
+            const float inv = rn_bn_inv(st.variance[c], st.gamma[c], w->bn_epsilon);
+            const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
+            if (std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8)
+                frozen.push_back(c);
+        }
+        return frozen;
+    };
+    for (int r = 2; r + 1 < w->n_stages && f.fold_r < 0; ++r) {
+        const rn_conv_stage& s5 = w->stages[r];
+        const rn_conv_stage& s4 = w->stages[r - 1];
+        const rn_conv_stage& s6 = w->stages[r + 1];
+        if (!(s5.cin == 64 && s5.cout == 64 && s5.pool_k == 4 && s5.pool_s == 2 && s5.skip_stage == r - 1 && s5.gamma2 && s4.cout == 64 &&
+              s4.skip_stage < 0 && s6.cin == 64 && s6.skip_stage < 0 && s5.gamma && s5.beta && s5.mean && s5.variance))
+            continue;
+        bool other_use = false;
+        for (int k = 0; k < w->n_stages; ++k) other_use |= (k != r && w->stages[k].skip_stage == r - 1) || w->stages[k].skip_stage == r;
+        if (other_use) continue;
+        const std::vector<int> frozen = frozen_couts(s5);
+        if (frozen.size() < 32) continue;
+        f.fold_pi = frozen_last(64, frozen, 32);
+        f.fold_r = r;
+    }
+    if (f.fold_r >= 0) {
+        rw.permute_couts(f.fold_r - 1, f.fold_pi);
+        rw.permute_couts(f.fold_r, f.fold_pi);
+        rw.permute_cins(f.fold_r, f.fold_pi);
+        rw.permute_cins(f.fold_r + 1, f.fold_pi);
+    }
+    // ---- ... and frozen INPUT channels: a pooled stage p without a second BN whose output only feeds the convolution of stage
+    // p + 1 (nobody's residual) and whose BN freezes >= 8 channels (same inequality).  Its couts / the consumer's cins are
+    // relabelled so that the last 8 k channels are all frozen; the consumer contracts the others and starts its accumulators
+    // from the frozen ones' contribution (rn_f32m_prepare: a variant of the stage kernel must exist for that channel count)
+    for (int r = 1; r < w->n_stages && f.kfold_r < 0; ++r) {
+        const int p = r - 1;
+        const rn_conv_stage& sp = rw.stages[p];
+        const rn_conv_stage& sc = rw.stages[r];
+        if (f.fold_r >= 0 && (p == f.fold_r - 1 || p == f.fold_r)) continue;          // (those channels are relabelled already)
+        if (sp.skip_stage >= 0 || sp.gamma2 || sp.pool_k != 4 || !sp.gamma || !sp.beta || !sp.mean || !sp.variance) continue;
+        if (sc.cin != sp.cout || sp.cout % 8 != 0 || sp.cout > 64) continue;
+        bool other_use = false;
+        for (int k = 0; k < w->n_stages; ++k) other_use |= w->stages[k].skip_stage == p;
+        if (other_use) continue;
+        const std::vector<int> frozen = frozen_couts(sp);
+        const int proven = static_cast<int>(frozen.size()), nf = proven / 8 * 8;
+        if (nf < 8 || nf >= sp.cout) continue;
+        f.kfold_pi = frozen_last(sp.cout, frozen, nf);
+        f.kfold_r = r;
+        f.kfold_live = sp.cout - nf;
+        f.kfold_proven = proven;
+    }
+    if (f.kfold_r >= 0) {
+        rw.permute_couts(f.kfold_r - 1, f.kfold_pi);
+        rw.permute_cins(f.kfold_r, f.kfold_pi);
+    }
+    return f;
+}
+
 }  // namespace
 
 int rn_run_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids) { return run_head(h, n, d_probs, d_ids); }
@@ -486,15 +614,8 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     *out = nullptr;
     int rc = validate(w, dtype, max_batch, flags);
     if (rc != RN_OK) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        rn_set_error("rn_create: no HIP device available");
-        return RN_E_HIP;
-    }
-    if (device < 0 || device >= ndev) {
-        rn_set_error("rn_create: device %d out of range (%d devices)", device, ndev);
-        return RN_E_INVALID;
-    }
+    int n_cu = 0;
+    if ((rc = check_device(device, &n_cu)) != RN_OK) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) {
         rn_set_error("rn_create: hipSetDevice(%d) failed", device);
@@ -505,22 +626,7 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
         rn_set_error("rn_create: out of host memory");
         return RN_E_NOMEM;
     }
-    {
-        // the kernels are gfx950 code sized for its 160 KiB of LDS per CU: refuse anything else up front
-        hipDeviceProp_t prop{};
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-            rn_set_error("rn_create: hipGetDeviceProperties(%d) failed", device);
-            delete h;
-            return RN_E_HIP;
-        }
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 || prop.maxSharedMemoryPerMultiProcessor < 160 * 1024) {
-            rn_set_error("rn_create: device %d is %s with %zu bytes of LDS per CU; this library is built for gfx950 (MI355X, 160 KiB)",
-                         device, prop.gcnArchName, static_cast<size_t>(prop.maxSharedMemoryPerMultiProcessor));
-            delete h;
-            return RN_E_INVALID;
-        }
-        h->n_cu = prop.multiProcessorCount;
-    }
+    h->n_cu = n_cu;
     h->device = device;
     h->dtype = dtype;
     h->flags = flags;
@@ -537,99 +643,23 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
         return fail(RN_E_HIP);
     }
     h->stream = h->own_stream;
-    // ---- float32 handles on the matrix-core path: frozen first-BN channels of a 64 -> 64 residual stage (stage 5).  The stage
-    // kernels form y1 = ((x * 1/16 - mean) * inv + beta) un-contracted: where |inv| * max(|mean|, |6 - mean|) < 2^-25 |beta| the
-    // product vanishes against beta and y1 IS beta for every input (the reference's float32 computes the same expression).  With
-    // >= 32 such channels the stage's channels are relabelled on a copy of the weights (stage 4's couts, stage 5's cins + couts,
-    // stage 6's cins: the residual pairs channel c of stage 4's output with channel c of stage 5's) so that the second 32-cout
-    // tile is all frozen: it is not convolved (rn_f32m_launch runs the residual for it alone).  rn_tap un-relabels.
     RelabelledWeights rw(w);
-    std::vector<int> fold_pi, kfold_pi;
-    int fold_r = -1, kfold_r = -1, kfold_live = 0, kfold_proven = 0;
-    if (!fused_mode(h) && !(flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_BATCH_STATS))) {
-        auto bn1_frozen = [&](const rn_conv_stage& st, int c) {
-            const float inv = rn_bn_inv(st.variance[c], st.gamma[c], w->bn_epsilon);
-            const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
-            return std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8;
-        };
-        for (int r = 2; r + 1 < w->n_stages && fold_r < 0; ++r) {
-            const rn_conv_stage& s5 = w->stages[r];
-            const rn_conv_stage& s4 = w->stages[r - 1];
-            const rn_conv_stage& s6 = w->stages[r + 1];
-            if (!(s5.cin == 64 && s5.cout == 64 && s5.pool_k == 4 && s5.pool_s == 2 && s5.skip_stage == r - 1 && s5.gamma2 && s4.cout == 64 &&
-                  s4.skip_stage < 0 && s6.cin == 64 && s6.skip_stage < 0 && s5.gamma && s5.beta && s5.mean && s5.variance))
-                continue;
-            bool other_use = false;
-            for (int k = 0; k < w->n_stages; ++k) other_use |= (k != r && w->stages[k].skip_stage == r - 1) || w->stages[k].skip_stage == r;
-            if (other_use) continue;
-            std::vector<int> frozen, live;
-            for (int c = 0; c < 64; ++c) (bn1_frozen(s5, c) ? frozen : live).push_back(c);
-            if (frozen.size() < 32) continue;
-            while (frozen.size() > 32) {
-                live.push_back(frozen.back());
-                frozen.pop_back();
-            }
-            std::sort(live.begin(), live.end());
-            fold_pi.resize(64);
-            for (int p = 0; p < 32; ++p) fold_pi[p] = live[p];
-            for (int p = 0; p < 32; ++p) fold_pi[32 + p] = frozen[p];
-            fold_r = r;
-        }
-        if (fold_r >= 0) {
-            rw.permute_couts(fold_r - 1, fold_pi);
-            rw.permute_couts(fold_r, fold_pi);
-            rw.permute_cins(fold_r, fold_pi);
-            rw.permute_cins(fold_r + 1, fold_pi);
-        }
-        // ---- ... and frozen INPUT channels: a pooled stage p without a second BN whose output only feeds the convolution of stage
-        // p + 1 (nobody's residual) and whose BN freezes >= 8 channels (same inequality).  Its couts / the consumer's cins are
-        // relabelled so that the last 8 k channels are all frozen; the consumer contracts the others and starts its accumulators
-        // from the frozen ones' contribution (rn_f32m_prepare: a variant of the stage kernel must exist for that channel count)
-        for (int r = 1; r < w->n_stages && kfold_r < 0; ++r) {
-            const int p = r - 1;
-            const rn_conv_stage& sp = rw.stages[p];
-            const rn_conv_stage& sc = rw.stages[r];
-            if (fold_r >= 0 && (p == fold_r - 1 || p == fold_r)) continue;          // (those channels are relabelled already)
-            if (sp.skip_stage >= 0 || sp.gamma2 || sp.pool_k != 4 || !sp.gamma || !sp.beta || !sp.mean || !sp.variance) continue;
-            if (sc.cin != sp.cout || sp.cout % 8 != 0 || sp.cout > 64) continue;
-            bool other_use = false;
-            for (int k = 0; k < w->n_stages; ++k) other_use |= w->stages[k].skip_stage == p;
-            if (other_use) continue;
-            std::vector<int> frozen, live;
-            for (int c = 0; c < sp.cout; ++c) (bn1_frozen(sp, c) ? frozen : live).push_back(c);
-            const int proven = static_cast<int>(frozen.size()), nf = proven / 8 * 8;
-            if (nf < 8 || nf >= sp.cout) continue;
-            while (static_cast<int>(frozen.size()) > nf) {
-                live.push_back(frozen.back());
-                frozen.pop_back();
-            }
-            std::sort(live.begin(), live.end());
-            kfold_pi = live;
-            kfold_pi.insert(kfold_pi.end(), frozen.begin(), frozen.end());
-            kfold_r = r;
-            kfold_live = sp.cout - nf;
-            kfold_proven = proven;
-        }
-        if (kfold_r >= 0) {
-            rw.permute_couts(kfold_r - 1, kfold_pi);
-            rw.permute_cins(kfold_r, kfold_pi);
-        }
-    }
+    const F32Folds folds = plan_f32_folds(w, dtype, flags, rw);
     // (the grad-CAM adjoint keeps its host copies from the caller's weights, in the reference's channel order)
     if ((rc = rn_gradcam_keep(h, w)) != RN_OK) return fail(rc);
     w = &rw.w;
     if ((rc = build_plan(h, w)) != RN_OK) return fail(rc);
-    if (fold_r >= 0) {
-        h->f32_fold_stage = fold_r;
+    if (folds.fold_r >= 0) {
+        h->f32_fold_stage = folds.fold_r;
         h->f32_fold_live = 32;
-        h->node_perm[h->stages[fold_r - 1].node_bn] = fold_pi;
-        h->node_perm[h->stages[fold_r].node_bn2] = fold_pi;
+        h->node_perm[h->stages[folds.fold_r - 1].node_bn] = folds.fold_pi;
+        h->node_perm[h->stages[folds.fold_r].node_bn2] = folds.fold_pi;
     }
-    if (kfold_r >= 0) {
-        h->f32_kfold_stage = kfold_r;           // (rn_f32m_prepare takes it back if no kernel variant contracts that channel count)
-        h->f32_kfold_live = kfold_live;
-        h->f32_kfold_proven = kfold_proven;
-        h->node_perm[h->stages[kfold_r - 1].node_bn] = kfold_pi;
+    if (folds.kfold_r >= 0) {
+        h->f32_kfold_stage = folds.kfold_r;     // (rn_f32m_prepare takes it back if no kernel variant contracts that channel count)
+        h->f32_kfold_live = folds.kfold_live;
+        h->f32_kfold_proven = folds.kfold_proven;
+        h->node_perm[h->stages[folds.kfold_r - 1].node_bn] = folds.kfold_pi;
     }
     // uint8 -> float32 table, evaluated in float64 like the reference's NumPy expression
     {
@@ -713,22 +743,31 @@ extern "C" int rn_sync(rn_handle* h) {
     return RN_OK;
 }
 
-extern "C" int rn_forward_f32_device(rn_handle* h, const float* d_rgb, int n, float* d_probs, int64_t* d_ids) {
-    int rc = check_call(h, n, d_rgb, d_probs, d_ids);
+// One forward pass on a device input: exactly one of d_bgr (uint8 BGR) / d_rgb (pre-processed float32) is given.
+static int forward_device(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int n, float* d_probs, int64_t* d_ids) {
+    int rc = check_call(h, n, d_bgr ? static_cast<const void*>(d_bgr) : d_rgb, d_probs, d_ids);
     if (rc != RN_OK) return rc;
     DeviceGuard guard(h->device);
     (void)hipGetLastError();      // a stale status of the CALLER's own runtime calls on this thread is not this pass's launch failure
     h->timing_valid = false;
     record(h, 0);
-    record(h, 1);
-    if (fused_mode(h))
-        rc = rn_fused_forward(h, nullptr, d_rgb, n, d_probs, d_ids);
-    else {
-        // keep the "input" node readable through rn_tap
+    // events 0 .. 1 bracket the pre-processing: only the unfused uint8 pass has a launch of its own for it
+    if (fused_mode(h)) {
+        record(h, 1);
+        rc = rn_fused_forward(h, d_bgr, d_rgb, n, d_probs, d_ids);
+    } else {
         float* in_node = static_cast<float*>(h->nodes[h->node_input].ptr);
-        if (in_node != d_rgb)
-            RN_HIP(hipMemcpyAsync(in_node, d_rgb, static_cast<size_t>(n) * h->im_side * h->im_side * 3 * 4,
-                                  hipMemcpyDeviceToDevice, h->stream));
+        if (d_bgr) {
+            rc = rn_launch_preprocess_u8(h->stream, d_bgr, in_node, h->lut, static_cast<int64_t>(n) * h->im_side * h->im_side);
+            if (rc != RN_OK) return rc;
+            record(h, 1);
+        } else {
+            record(h, 1);
+            // keep the "input" node readable through rn_tap
+            if (in_node != d_rgb)
+                RN_HIP(hipMemcpyAsync(in_node, d_rgb, static_cast<size_t>(n) * h->im_side * h->im_side * 3 * 4,
+                                      hipMemcpyDeviceToDevice, h->stream));
+        }
         rc = forward_unfused(h, in_node, n, d_probs, d_ids);
     }
     if (rc != RN_OK) return rc;
@@ -737,28 +776,12 @@ extern "C" int rn_forward_f32_device(rn_handle* h, const float* d_rgb, int n, fl
     return RN_OK;
 }
 
+extern "C" int rn_forward_f32_device(rn_handle* h, const float* d_rgb, int n, float* d_probs, int64_t* d_ids) {
+    return forward_device(h, nullptr, d_rgb, n, d_probs, d_ids);
+}
+
 extern "C" int rn_forward_u8_device(rn_handle* h, const uint8_t* d_bgr, int n, float* d_probs, int64_t* d_ids) {
-    int rc = check_call(h, n, d_bgr, d_probs, d_ids);
-    if (rc != RN_OK) return rc;
-    DeviceGuard guard(h->device);
-    (void)hipGetLastError();      // (see rn_forward_f32_device)
-    h->timing_valid = false;
-    record(h, 0);
-    if (fused_mode(h)) {
-        record(h, 1);
-        rc = rn_fused_forward(h, d_bgr, nullptr, n, d_probs, d_ids);
-    } else {
-        float* in_node = static_cast<float*>(h->nodes[h->node_input].ptr);
-        rc = rn_launch_preprocess_u8(h->stream, d_bgr, in_node, h->lut,
-                                     static_cast<int64_t>(n) * h->im_side * h->im_side);
-        if (rc != RN_OK) return rc;
-        record(h, 1);
-        rc = forward_unfused(h, in_node, n, d_probs, d_ids);
-    }
-    if (rc != RN_OK) return rc;
-    h->last_n = n;
-    h->timing_valid = h->profiling;
-    return RN_OK;
+    return forward_device(h, d_bgr, nullptr, n, d_probs, d_ids);
 }
 
 extern "C" int rn_forward_u8(rn_handle* h, const uint8_t* bgr, int n, float* probs, int64_t* ids) {

@@ -63,21 +63,7 @@ struct BackendArgs {
     TailArgs tail;
 };
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-__device__ __forceinline__ int swz8(int pix) { return pix & 7; }                   // stage-6 input ring (rn_stage6x.hip)
 __device__ __forceinline__ int swz16(int pix) { return (pix & 7) << 1; }           // mid ring (conv16p: 16 chunks per pixel)
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 template <int DT, bool K48>
 __global__ __launch_bounds__(704) void backend_kernel(const BackendArgs a) {

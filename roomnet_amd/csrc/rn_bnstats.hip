@@ -421,13 +421,11 @@ extern "C" int rn_bn_batch_stats(rn_handle* h, int i, float* mean, float* var_bi
         return RN_E_STATE;
     }
     const BnSlot& b = pl->bns[i];
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    RN_HIP(hipSetDevice(h->device));
+    DeviceGuard guard(h->device);
+    if (!guard.ok) RN_HIP(hipSetDevice(h->device));      // (fails again: reports it)
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && mean) e = hipMemcpy(mean, b.mean, static_cast<size_t>(b.c) * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && var_biased) e = hipMemcpy(var_biased, b.var, static_cast<size_t>(b.c) * 4, hipMemcpyDeviceToHost);
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) {
         rn_set_error("rn_bn_batch_stats: device copy failed: %s", hipGetErrorString(e));
         (void)hipGetLastError();

@@ -34,21 +34,6 @@ constexpr int C16_KC = 18;                        // K chunks of 32: (tap, chann
 constexpr int C16_TAB_OFF = C16_NSLOT * C16_ROWB;     // folded BN tables behind the ring: scale[128], shift[128]
 constexpr int C16_LDS = C16_TAB_OFF + 2 * C16_COUT * 4;
 
-using f32x4v = __attribute__((ext_vector_type(4))) float;
-using i32x2v = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4v mfma16(i32x4 a, i32x4 b, f32x4v c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// conflict-free for all three tap columns and both channel halves under ds_read_b128's lane grouping (checked by enumeration;
-// (pix >> 1) & 7, the rings' swizzle for 32-pixel tiles, is 2-way conflicted here for kx = 1, 2)
-__device__ __forceinline__ int c16_swz(int pix) { return pix & 7; }
-
 template <int DT>
 __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
     extern __shared__ __attribute__((aligned(64))) char smem[];
@@ -92,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
         const int q = tid + 256 * i;
         const int p = min(q >> 3, C16_RINGW - 1), c = q & 7;          // chunks past the 50th pixel land in the row's padding
         const int pc = min(x0 + p, a.W - 1);
-        goff[i] = static_cast<unsigned>((pc * C16_CIN + ((c ^ c16_swz(p)) << 3)) * 2);
+        goff[i] = static_cast<unsigned>((pc * C16_CIN + ((c ^ swz8(p)) << 3)) * 2);
     }
     auto issue_row = [&](int j, int slot) __attribute__((always_inline)) {
         const char* row = in_img + static_cast<int64_t>(yo0 + min(j, nin - 1)) * in_row_bytes;
@@ -114,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int p = i16 + kx;                                    // (pixel tiles add 16 pixels = 2048 bytes: same swizzle)
-            boff[kx][h] = ring_lds + static_cast<unsigned>(p * 128 + (((4 * h + kg) ^ c16_swz(p)) << 4));
+            boff[kx][h] = ring_lds + static_cast<unsigned>(p * 128 + (((4 * h + kg) ^ swz8(p)) << 4));
         }
     // BN tables in LDS (read per row in the epilogue: keeping 16 more registers live through the MFMA loop spills)
     float* const tab = reinterpret_cast<float*>(smem + C16_TAB_OFF);
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
         wait_vmcnt<4>();
         raw_barrier();
         issue_row(s + C16_AHEAD, (P + C16_AHEAD) % C16_NSLOT);
-        f32x4v acc[3][2];
+        f32x4 acc[3][2];
         // fragment double buffer: the three reads of chunk C + 1 are issued before the six MFMAs of chunk C and retired by a
         // counted wait (LDS returns in order), so their latency hides behind 96 cycles of matrix work
         i32x4 bq[2][3];
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
         rd(IC<0>{}, bq[0]);
         [&]<int... C>(std::integer_sequence<int, C...>) {
             (([&] {
-                 const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                  i32x4(&b)[3] = bq[C & 1];
                  if constexpr (C + 1 < C16_KC) {
                      rd(IC<(C + 1 < C16_KC ? C + 1 : 0)>{}, bq[(C + 1) & 1]);
@@ -189,12 +174,12 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16Args a) {
         for (int pt = 0; pt < 3; ++pt)
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
-                const f32x4v sc = *reinterpret_cast<const f32x4v*>(tab_lane + 16 * ct);
-                const f32x4v sh = *reinterpret_cast<const f32x4v*>(tab_lane + 16 * ct + C16_COUT);
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(tab_lane + 16 * ct);
+                const f32x4 sh = *reinterpret_cast<const f32x4*>(tab_lane + 16 * ct + C16_COUT);
                 float y[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) y[j] = fmaf(relu6f(acc[pt][ct][j]), sc[j], sh[j]);
-                const i32x2v d = {static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
+                const i32x2 d = {static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
                 __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff[pt] + 32 * ct, 0, 0);
             }
         out_row += out_row_bytes;
@@ -298,8 +283,8 @@ __global__ __launch_bounds__(64 * NT, NT == 3 ? 2 : 1) void conv16p_kernel(const
             const int p = 14 * wave + i16 + kx;
             boff[kx][q] = ring_lds + static_cast<unsigned>(p * 256 + (((4 * q + kg) ^ p16_swz(p)) << 4));
         }
-    const f32x4v sc = *reinterpret_cast<const f32x4v*>(a.ptab + 4 * kg);
-    const f32x4v sh = *reinterpret_cast<const f32x4v*>(a.ptab + P16_COUT + 4 * kg);
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(a.ptab + 4 * kg);
+    const f32x4 sh = *reinterpret_cast<const f32x4*>(a.ptab + P16_COUT + 4 * kg);
     constexpr int OOB = 0x40000000;
     const int xo = P16_BLKO * cb + 7 * wave + (i16 >> 1);
     const int voff_lane = ((i16 & 1) == 0 && i16 <= 12 && xo < a.Wo) ? (xo * P16_COUT + 4 * kg) * 2 : OOB;
@@ -323,7 +308,7 @@ __global__ __launch_bounds__(64 * NT, NT == 3 ? 2 : 1) void conv16p_kernel(const
         wait_vmcnt<2 * P16_PIECES>();
         raw_barrier();
         issue_row(s + C16_AHEAD, (P + C16_AHEAD) % C16_NSLOT);
-        f32x4v acc[3];                                   // one chain per kernel row, summed (ky 0 + ky 1) + ky 2: the order the
+        f32x4 acc[3];                                   // one chain per kernel row, summed (ky 0 + ky 1) + ky 2: the order the
                                                          // one-launch back end (rn_backend.hip) adds its per-kernel-row partials in
         // operand reads run P16_RD - 1 chunks ahead of their MFMA behind counted waits
         constexpr int RD = P16_RD;
@@ -340,7 +325,7 @@ __global__ __launch_bounds__(64 * NT, NT == 3 ? 2 : 1) void conv16p_kernel(const
         [&]<int... C>(std::integer_sequence<int, C...>) { (rd(IC<C>{}, bq[C]), ...); }(std::make_integer_sequence<int, RD - 1>{});
         [&]<int... C>(std::integer_sequence<int, C...>) {
             (([&] {
-                 const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                  if constexpr (C + RD - 1 < P16_KC) rd(IC<(C + RD - 1 < P16_KC ? C + RD - 1 : 0)>{}, bq[(C + RD - 1) % RD]);
                  constexpr int newer = (P16_KC - 1 - C) < RD - 1 ? (P16_KC - 1 - C) : RD - 1;
                  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bq[C % RD]) : "n"(newer));
@@ -370,7 +355,7 @@ __global__ __launch_bounds__(64 * NT, NT == 3 ? 2 : 1) void conv16p_kernel(const
             for (int j = 0; j < 4; ++j) hprev[j] = v[j];
         }
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(out_row), 0, out_row_bytes, 0x00020000);
-        const i32x2v d = {static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
+        const i32x2 d = {static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
         __builtin_amdgcn_raw_buffer_store_b64(d, rs, vo, 0, 0);
         if ((P & 1) == 1 && s >= 3) out_row += out_row_bytes;
     };

@@ -72,17 +72,6 @@ constexpr int FT_WG_PAIRS = 9 * FT_C;  // (tap, cin) pairs of a weight gradient
 constexpr int FT_WG_GROUPS = 3;        // row groups (FT_WG_PAIRS * FT_WG_GROUPS <= FT_NT)
 constexpr int FT_MAX_VARS = 8 + 3 * RN_MAX_DENSE;
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 struct FtItemArgs {
     const float* feats;              // [n_items, S7, S7, 16]
     const int32_t* labels;           // [n_items] (eval: may be null)
@@ -653,53 +642,24 @@ struct rn_ft {
 
 namespace {
 
-int ft_alloc(rn_ft* ft, size_t bytes, void** out) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
-    if (e != hipSuccess) {
-        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        (void)hipGetLastError();
-        return RN_E_NOMEM;
-    }
-    ft->allocs.push_back(p);
-    *out = p;
-    return RN_OK;
-}
-
+// trainer-owned device memory (an empty request gets 4 bytes)
 template <typename T>
 int ft_upload(rn_ft* ft, const T* src, size_t count, T** out) {
-    void* p = nullptr;
-    int rc = ft_alloc(ft, count * sizeof(T), &p);
-    if (rc != RN_OK) return rc;
-    RN_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<T*>(p);
-    return RN_OK;
+    return rn_owned_upload(ft->allocs, 4, src, count, out);
 }
-
 template <typename T>
 int ft_zeroed(rn_ft* ft, size_t count, T** out) {
-    void* p = nullptr;
-    int rc = ft_alloc(ft, count * sizeof(T), &p);
-    if (rc != RN_OK) return rc;
-    RN_HIP(hipMemset(p, 0, count * sizeof(T)));
-    *out = static_cast<T*>(p);
-    return RN_OK;
+    return rn_owned_zeroed(ft->allocs, 4, count, out);
 }
 
 int ft_build(rn_ft* ft, const rn_weights* w) {
     const int ns = w->n_stages;
     const rn_conv_stage &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
     {
-        int side = w->im_side;
-        std::vector<int> conv(ns), out(ns);
-        for (int i = 0; i < ns; ++i) {
-            conv[i] = side - 2;
-            side = w->stages[i].pool_k ? (conv[i] - w->stages[i].pool_k) / w->stages[i].pool_s + 1 : conv[i];
-            if (conv[i] < 1 || side < 1) {
-                rn_set_error("rn_ft_create: im_side %d is too small for the graph", w->im_side);
-                return RN_E_INVALID;
-            }
-            out[i] = side;
+        std::vector<int> conv, out;
+        if (rn_stage_sides(w, conv, out) < ns) {
+            rn_set_error("rn_ft_create: im_side %d is too small for the graph", w->im_side);
+            return RN_E_INVALID;
         }
         ft->S6 = out[ns - 4];
         ft->C7 = conv[ns - 3];
@@ -844,19 +804,10 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
     }
     ft->n_param = static_cast<int>(P.size());
     a.rec = rec;
-    // legacy bilinear tables S7 -> S9 (TF-1.13 compute_interpolation_weights, as rn_gradcam_keep)
+    // legacy bilinear tables S7 -> S9: [lo | hi], lerp
     std::vector<int32_t> rt(2 * static_cast<size_t>(ft->S9));
     std::vector<float> lerp(ft->S9);
-    {
-        const float scale = static_cast<float>(ft->S7) / static_cast<float>(ft->S9);
-        for (int i = 0; i < ft->S9; ++i) {
-            const float src = static_cast<float>(i) * scale;
-            const int32_t lo = static_cast<int32_t>(src);
-            rt[i] = lo;
-            rt[ft->S9 + i] = lo + 1 < ft->S7 - 1 ? lo + 1 : ft->S7 - 1;
-            lerp[i] = src - static_cast<float>(lo);
-        }
-    }
+    rn_legacy_resize_table(ft->S7, ft->S9, rt.data(), rt.data() + ft->S9, lerp.data());
     int rc;
     const size_t np = static_cast<size_t>(ft->n_param), nb = static_cast<size_t>(ft->max_batch);
     if ((rc = ft_upload(ft, P.data(), np, &ft->d_P)) != RN_OK) return rc;
@@ -1073,19 +1024,16 @@ extern "C" int rn_ft_upload(rn_ft* ft, const void* src, size_t bytes, void** d_p
     }
     DeviceGuard guard(ft->device);
     void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
-    if (e != hipSuccess) {
-        rn_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        (void)hipGetLastError();
-        return RN_E_NOMEM;
-    }
+    int rc = rn_owned_alloc(ft->user, bytes, 4, &p);
+    if (rc != RN_OK) return rc;
+    hipError_t e;
     if (bytes && (e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
         rn_set_error("rn_ft_upload: hipMemcpy failed: %s", hipGetErrorString(e));
         (void)hipGetLastError();
+        ft->user.pop_back();
         (void)hipFree(p);
         return RN_E_HIP;
     }
-    ft->user.push_back(p);
     *d_ptr = p;
     return RN_OK;
 }
@@ -1105,6 +1053,16 @@ extern "C" int rn_ft_free(rn_ft* ft, void* d_ptr) {
     ft->user.erase(it);
     RN_HIP(hipFree(d_ptr));
     return RN_OK;
+}
+
+// the depth-3 launches' arguments of one call: `m` items of `feats` from `base` on, through `index` or (null) in order
+static Ft7Args ft7_call(const rn_ft* ft, const float* feats, const int32_t* index, int64_t base, int m) {
+    Ft7Args s = ft->s7;
+    s.feats = feats;
+    s.index = index;
+    s.base = base;
+    rn_ft7_bands(m, ft->C7, ft->S7, &s.bands_f, &s.rows_f, &s.bands_b, &s.rows_b);
+    return s;
 }
 
 extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
@@ -1161,12 +1119,6 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
     const int ublocks = (ft->n_param + 255) / 256;
     const bool d3 = ft->depth == 3;
-    Ft7Args s7 = ft->s7;
-    if (d3) {
-        s7.feats = d_feats;
-        s7.index = d_index;
-        rn_ft7_bands(batch, ft->C7, ft->S7, &s7.bands_f, &s7.rows_f, &s7.bands_b, &s7.rows_b);
-    }
     ft->timed = false;
     RN_HIP(hipEventRecord(ft->ev0, ft->stream));
     for (int s = 0; s < steps; ++s) {
@@ -1177,7 +1129,7 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
         a.base = static_cast<int64_t>(s) * batch;
         if (d3) {
             int rc;
-            s7.base = a.base;
+            const Ft7Args s7 = ft7_call(ft, d_feats, d_index, a.base, batch);
             if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
             hipLaunchKernelGGL((ft_item_kernel<true, FtItemArgs7>), dim3(batch), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));
             RN_CHECK_LAUNCH();
@@ -1234,11 +1186,7 @@ extern "C" int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labe
         a.probs = ft->d_probs;
         a.ids = ft->d_ids;
         if (ft->depth == 3) {
-            Ft7Args s7 = ft->s7;
-            s7.feats = d_feats;
-            s7.index = nullptr;
-            s7.base = i;
-            rn_ft7_bands(m, ft->C7, ft->S7, &s7.bands_f, &s7.rows_f, &s7.bands_b, &s7.rows_b);
+            const Ft7Args s7 = ft7_call(ft, d_feats, nullptr, i, m);
             int rc;
             if ((rc = rn_ft7_forward(ft->stream, s7, m)) != RN_OK) return rc;
             hipLaunchKernelGGL((ft_item_kernel<false, FtItemArgs7>), dim3(m), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));

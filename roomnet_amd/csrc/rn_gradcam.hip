@@ -322,14 +322,6 @@ struct GcStage7Args {
     int npart;
 };
 
-template <int DT>
-__device__ __forceinline__ f32x4 gc_mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // One workgroup = 4 waves x GC_R7 conv-7 rows of one image; a wave walks its rows in 16-pixel tiles x all 16 couts.
 // MFMA operands: A = pixels (lane & 15) x K, B = K x couts (lane & 15); C/D: pixel 4 (lane >> 4) + j, cout lane & 15.
 template <int DT>
@@ -405,8 +397,8 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
                     const i32x4* wlo = reinterpret_cast<const i32x4*>(wl) + ky * 12 * 64 + lane;
 #pragma unroll
                     for (int q = 0; q < 12; ++q) {
-                        acc[yi] = gc_mfma16<DT>(av[q], wreg[ky * 12 + q], acc[yi]);
-                        acc[yi] = gc_mfma16<DT>(av[q], wlo[q * 64], acc[yi]);
+                        acc[yi] = mfma16<DT>(av[q], wreg[ky * 12 + q], acc[yi]);
+                        acc[yi] = mfma16<DT>(av[q], wlo[q * 64], acc[yi]);
                     }
                 }
             }
@@ -662,26 +654,15 @@ int rn_gradcam_keep(rn_handle* h, const rn_weights* w) {
     g->o_bn8 = put_bn(st8.gamma, st8.beta, st8.mean, st8.variance);
     g->o_bn9 = put_bn(st9.gamma, st9.beta, st9.mean, st9.variance);
     g->o_bn9b = put_bn(st9.gamma2, st9.beta2, st9.mean2, st9.variance2);
-    // legacy bilinear tables S7 -> S9 (TF-1.13 compute_interpolation_weights, as upload_resize_tab)
+    // legacy bilinear tables S7 -> S9
     {
-        int side = w->im_side;
-        std::vector<int> out(ns);
-        for (int i = 0; i < ns; ++i) {
-            const int conv = side - 2;
-            side = w->stages[i].pool_k ? (conv - w->stages[i].pool_k) / w->stages[i].pool_s + 1 : conv;
-            out[i] = side;
-        }
-        const int in_size = out[g->s7], out_size = out[g->s9];
+        std::vector<int> conv, out;
+        if (rn_stage_sides(w, conv, out) < ns) return no("im_side is too small for the graph");      // (build_plan reports it)
+        const int out_size = out[g->s9];
         g->rlo.resize(out_size);
         g->rhi.resize(out_size);
         std::vector<float> lerp(out_size);
-        const float scale = static_cast<float>(in_size) / static_cast<float>(out_size);
-        for (int i = 0; i < out_size; ++i) {
-            const float src = static_cast<float>(i) * scale;
-            g->rlo[i] = static_cast<int32_t>(src);
-            g->rhi[i] = g->rlo[i] + 1 < in_size - 1 ? g->rlo[i] + 1 : in_size - 1;
-            lerp[i] = src - static_cast<float>(g->rlo[i]);
-        }
+        rn_legacy_resize_table(out[g->s7], out_size, g->rlo.data(), g->rhi.data(), lerp.data());
         g->o_rlerp = put(lerp.data(), lerp.size());
     }
     for (int d = 0; d < w->n_dense; ++d) {

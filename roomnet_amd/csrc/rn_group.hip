@@ -88,17 +88,6 @@ bool load_rccl() {
         }                                                                                                  \
     } while (0)
 
-// the caller's current HIP device, put back when an entry point returns (the per-handle entry points do the same)
-struct CurrentDeviceRestore {
-    int prev = -1;
-    CurrentDeviceRestore() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~CurrentDeviceRestore() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 // One upload worker per device: bound to its device once, then: wait for a job (source, bytes) -> hipMemcpyAsync on the
@@ -175,7 +164,7 @@ struct rn_group {
 
 extern "C" void rn_group_destroy(rn_group* g) {
     if (!g) return;
-    CurrentDeviceRestore restore;
+    DeviceGuard restore;
     for (auto& w : g->workers)
         if (w) w->stop();
     for (int d = 0; d < static_cast<int>(g->handles.size()); ++d) {
@@ -215,7 +204,7 @@ extern "C" int rn_group_create(const rn_weights* w, int ndev, const int* devices
         rn_set_error("rn_group_create: %s", g_rccl_error.c_str());
         return RN_E_STATE;
     }
-    CurrentDeviceRestore restore;
+    DeviceGuard restore;
     rn_group* g = new (std::nothrow) rn_group();
     if (!g) {
         rn_set_error("rn_group_create: out of host memory");
@@ -354,7 +343,7 @@ extern "C" int rn_group_forward_u8_device(rn_group* g, const uint8_t* const* d_s
             rn_set_error("rn_group_forward_u8_device: device %d: %d images out of range (max_batch_per_device %d)", d, counts[d], g->cap);
             return RN_E_RANGE;
         }
-    CurrentDeviceRestore restore;
+    DeviceGuard restore;
     return group_run(g, d_shards, counts);
 }
 
@@ -373,7 +362,7 @@ extern "C" int rn_group_sync(rn_group* g) {
         rn_set_error("null group");
         return RN_E_INVALID;
     }
-    CurrentDeviceRestore restore;
+    DeviceGuard restore;
     for (int d = 0; d < g->ndev; ++d) {
         RN_HIP(hipSetDevice(g->devices[d]));
         RN_HIP(hipStreamSynchronize(g->handles[d]->stream));
@@ -390,7 +379,7 @@ extern "C" int rn_group_forward_u8(rn_group* g, const uint8_t* bgr_nhwc, int n, 
         rn_set_error("rn_group_forward_u8: n = %d out of range (1..%d)", n, g->cap * g->ndev);
         return RN_E_RANGE;
     }
-    CurrentDeviceRestore restore;
+    DeviceGuard restore;
     const size_t img_bytes = static_cast<size_t>(g->im_side) * g->im_side * 3;
     std::vector<const uint8_t*> shards(g->ndev, nullptr);
     std::vector<int> counts(g->ndev, 0);

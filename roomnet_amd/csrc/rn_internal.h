@@ -218,18 +218,54 @@ void rn_bnstats_release(rn_handle* h);
 int rn_bnstats_conv(rn_handle* h, int stage, bool second, const float* x, int64_t npix);
 int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
 
-// ---- host helpers of rn_create (rn_api.hip) ---------------------------------------------
-// device memory owned by the handle (freed by rn_destroy); errors as "hipMalloc(N bytes) failed: ..."
-int dev_alloc(rn_handle* h, size_t bytes, void** out);
+// ---- host helpers (rn_api.hip) -----------------------------------------------------------
+// Makes `dev` the current HIP device and puts the caller's back on scope exit; `ok` = the device could be set.  Without an
+// argument it only restores (the group entry points walk several devices).
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    DeviceGuard();
+    explicit DeviceGuard(int dev);
+    ~DeviceGuard();
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// device memory owned through a list (freed by the list's owner: rn_destroy, rn_ft_destroy); a failure is RN_E_NOMEM with
+// "hipMalloc(N bytes) failed: ...".  An empty request gets `min_bytes`.
+int rn_owned_alloc(std::vector<void*>& owner, size_t bytes, size_t min_bytes, void** out);
 template <typename T>
-int upload(rn_handle* h, const T* src, size_t count, T** out) {
+int rn_owned_upload(std::vector<void*>& owner, size_t min_bytes, const T* src, size_t count, T** out) {
     void* p = nullptr;
-    int rc = dev_alloc(h, count * sizeof(T), &p);
+    int rc = rn_owned_alloc(owner, count * sizeof(T), min_bytes, &p);
     if (rc != RN_OK) return rc;
     RN_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
     *out = static_cast<T*>(p);
     return RN_OK;
 }
+template <typename T>
+int rn_owned_zeroed(std::vector<void*>& owner, size_t min_bytes, size_t count, T** out) {
+    void* p = nullptr;
+    int rc = rn_owned_alloc(owner, count * sizeof(T), min_bytes, &p);
+    if (rc != RN_OK) return rc;
+    RN_HIP(hipMemset(p, 0, count * sizeof(T)));
+    *out = static_cast<T*>(p);
+    return RN_OK;
+}
+// ... by the handle (an empty request gets 16 bytes)
+inline int dev_alloc(rn_handle* h, size_t bytes, void** out) { return rn_owned_alloc(h->allocs, bytes, 16, out); }
+template <typename T>
+int upload(rn_handle* h, const T* src, size_t count, T** out) {
+    return rn_owned_upload(h->allocs, 16, src, count, out);
+}
+
+// TF-1.13 compute_interpolation_weights (align_corners=False, no half-pixel centres) for in -> out samples, in float32:
+// lo = int(i * scale), hi = min(lo + 1, in - 1), lerp = i * scale - lo.  The one host copy of the legacy bilinear table.
+void rn_legacy_resize_table(int in_size, int out_size, int32_t* lo, int32_t* hi, float* lerp);
+
+// Side of every stage's convolution output and of its output (after pooling) for w->im_side.  Returns the number of stages that
+// fit: w->n_stages, or the index of the first stage for which im_side is too small (conv / out are valid in front of it).
+int rn_stage_sides(const rn_weights* w, std::vector<int>& conv, std::vector<int>& out);
 
 // tf.nn.batch_normalization folded to y = x * inv + shift, in float32 as every path of the library evaluates it
 inline float rn_bn_inv(float var, float gamma, float eps) { return (1.0f / sqrtf(var + eps)) * gamma; }

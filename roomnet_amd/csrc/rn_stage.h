@@ -1,4 +1,7 @@
-// Device helpers and launch-argument block shared by the fused stage kernels.
+// Device helpers and launch-argument blocks shared by the fused stage kernels: the vector types, the MFMA wrappers (mfma32,
+// mfma16), 16-bit packing and dithered stores, DPP shifts, the LDS address / chunk swizzles of the 16x16x32 kernels (lds_addr,
+// swz8, swz4x), the stage-0 operands, the clock stamps of the diagnostic build (RN_CLOCK_ENTRY / RN_CLOCK_EXIT), the LDS-DMA and
+// barrier helpers, and StageArgs / Stage23Args / Conv16Args with the column-block plan.
 #pragma once
 #include "rn_internal.h"
 
@@ -7,6 +10,7 @@
 namespace rnk {
 
 using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x2 = __attribute__((ext_vector_type(2))) int;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
@@ -30,6 +34,14 @@ __device__ __forceinline__ f32x16 mfma32(i32x4 a, i32x4 b, f32x16 c) {
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
                                                       0, 0, 0);
+}
+
+template <int DT>
+__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
+    if constexpr (DT == RN_DTYPE_BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
 template <int DT>
@@ -209,6 +221,22 @@ __device__ __forceinline__ float s0_relu6(const f32x16& acc, int j) {
 __device__ __forceinline__ void clock_pair(unsigned long long& t, unsigned long long& r) {
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t), "=s"(r)::"memory");
 }
+// first statement of a stamped kernel / its last: the thread for which `writer` holds stores the workgroup's pair
+#define RN_CLOCK_ENTRY()               \
+    unsigned long long ck_t0, ck_r0;   \
+    clock_pair(ck_t0, ck_r0)
+#define RN_CLOCK_EXIT(stamp_buf, writer)                                                         \
+    if ((stamp_buf) && (writer)) {                                                               \
+        unsigned long long t1, r1;                                                               \
+        clock_pair(t1, r1);                                                                      \
+        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;            \
+        (stamp_buf)[wg * 2 + 0] = t1 - ck_t0;                                                    \
+        (stamp_buf)[wg * 2 + 1] = r1 - ck_r0;                                                    \
+    }                                                                                            \
+    static_assert(true)
+#else
+#define RN_CLOCK_ENTRY() static_assert(true)
+#define RN_CLOCK_EXIT(stamp_buf, writer) static_assert(true)
 #endif
 
 // ------------------------------------------------------------------------ LDS-DMA / barrier helpers
@@ -216,6 +244,11 @@ template <int P>
 using IC = std::integral_constant<int, P>;
 
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
+
+// LDS byte address of a __shared__ pointer (base of DS instructions written as inline asm)
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
+}
 
 // Bare workgroup barrier.  No fence: a fence would make the compiler drain the LDS-DMA queue
 // (vmcnt(0)) at every barrier.  Correctness is by construction: DMA data is retired by the
@@ -398,5 +431,40 @@ __device__ __forceinline__ int chunk_swz(int pix) {
         return (pix / (16 / CP)) & (CP - 1);
 }
 
+// chunk swizzles of the kernels on 16x16x32 tiles (the operand read is one ds_read_b128 per lane: 16 pixels x one K group)
+// 8 chunks per 128-byte pixel: chunk ^ (pixel & 7) is conflict-free for all three tap columns and both channel halves under
+// ds_read_b128's lane grouping (checked by enumeration; (pix >> 1) & 7, the rings' swizzle for 32-pixel tiles, is 2-way
+// conflicted here for kx = 1, 2)
+__device__ __forceinline__ int swz8(int pix) { return pix & 7; }
+// 4 chunks per 64-byte pixel: the A and B rings of rn_stage23x.hip and the ring of rn_stage4x.hip (16x16x32 operand reads)
+__device__ __forceinline__ int swz4x(int pix) { return (pix >> 1) & 3; }
+
+// Band matrices of the stride-2 pooling MFMA (rn_stage4x.hip, rn_stage5x.hip) of lane (px16 = lane & 15, g = lane >> 4), as fp16
+// ones: declares the three i32x4.  The 16 pooled columns n of a tile PAIR: n < 8 start in the pair's first tile (window = its
+// columns 2n .. 2n+3; n = 7 ends in the second tile), n >= 8 in the second (n = 15 ends in the tile after).  K element 8 g + e of
+// an operand = pixel 4 g + (e & 3) of the tile (older pair sum for e < 4, newer for e >= 4).
+// (A macro: as a function returning the three matrices it changes the schedule of both kernels.)
+#define RN_POOL_BANDS_S2(pmA, pmB, pmC, px16, g)                                                                                              \
+    i32x4 pmA, pmB, pmC;                                                                                                                      \
+    _Pragma("unroll")                                                                                                                         \
+    for (int d = 0; d < 4; ++d) {                                                                                                             \
+        unsigned wa = 0, wb = 0, wc = 0;                                                                                                      \
+        _Pragma("unroll")                                                                                                                     \
+        for (int e2 = 0; e2 < 2; ++e2) {                                                                                                      \
+            const int e = 2 * d + e2;                                                                                                         \
+            const int p = 4 * g + (e & 3);                                                                                                    \
+            const int nn = px16;                                                                                                              \
+            const bool inA = nn < 8 && p >= 2 * nn && p <= 2 * nn + 3;                                                                        \
+            const bool inB = (nn < 8 && 16 + p >= 2 * nn && 16 + p <= 2 * nn + 3) || (nn >= 8 && p >= 2 * (nn - 8) && p <= 2 * (nn - 8) + 3); \
+            const bool inC = nn >= 8 && 16 + p >= 2 * (nn - 8) && 16 + p <= 2 * (nn - 8) + 3;                                                 \
+            wa |= (inA ? 0x3C00u : 0u) << (16 * e2);                                                                                          \
+            wb |= (inB ? 0x3C00u : 0u) << (16 * e2);                                                                                          \
+            wc |= (inC ? 0x3C00u : 0u) << (16 * e2);                                                                                          \
+        }                                                                                                                                     \
+        pmA[d] = static_cast<int>(wa);                                                                                                        \
+        pmB[d] = static_cast<int>(wb);                                                                                                        \
+        pmC[d] = static_cast<int>(wc);                                                                                                        \
+    }                                                                                                                                         \
+    asm volatile("" : "+v"(pmA), "+v"(pmB), "+v"(pmC))
 
 }  // namespace rnk

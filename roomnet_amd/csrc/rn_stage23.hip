@@ -52,13 +52,7 @@ static_assert(F_LDS <= 160 * 1024, "LDS budget");
 static_assert(F_RINGA_OFF % 64 == 0 && F_ROWA % 64 == 0 && F_ROWB % 64 == 0, "B-write addresses are composed with OR/XOR");
 static_assert((F_NA - 1) * F_ROWA < 65536 && (F_NB - 1) * F_ROWB < 65536, "slot offsets are DS immediates");
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-
 __device__ __forceinline__ int swz4(int pix) { return (pix >> 2) & 3; }   // chunk_swz<4>
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
 
 
 // Producer / consumer workgroup: 8 waves, two per SIMD.  Waves 0-3 ("producers") run the first stage of the pair for

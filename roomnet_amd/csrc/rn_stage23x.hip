@@ -75,22 +75,6 @@ __device__ __forceinline__ int xc_start(int w) { return w == 0 ? 0 : w == 1 ? 45
 // (consumer 2 ends at column 147, not 150: a consumer interpolates from a 64-column private skip ring, enough for 58
 //  output columns at the block's 215 -> 205 scale)
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-
-__device__ __forceinline__ int swzx(int pix) { return (pix >> 1) & 3; }   // A and B rings (16x16x32 operand reads)
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // PH = halves of every 8-cout group the PRODUCER computes: 2 = all 32 channels of B; 1 = the first half only -- the other 16
 // channels are frozen (Stage23Args::producer_halves: constants for every input, proven per channel by rn_fused_prepare) and are
 // written from the table, the same bits the full computation stores.  Half of the first conv's matrix instructions (9 + 2 of
@@ -122,10 +106,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wq = wave & 3;
     const int px16 = lane & 15, g = lane >> 4;           // tile column / K group (conv operand), pixel / cout group (pooled tiles)
-#ifdef RN_CLOCK
-    unsigned long long ck_t0, ck_r0;
-    clock_pair(ck_t0, ck_r0);
-#endif
+    RN_CLOCK_ENTRY();
     const int cblk = blockIdx.x % a.n_cblocks, band = blockIdx.x / a.n_cblocks, n = blockIdx.y;
     const int Win = a.W, Hout = a.Wo, x0 = a.cb_x0[cblk];
     const int Wo = a.cb_wo[cblk], W = Wo + 10, Wb = W - 5;
@@ -291,12 +272,12 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
         const int ptid = wq * 64 + lane;
         const int tailn = W - 192;
         const unsigned long long tail_mask = (1ull << tailn) - 1ull;
-        const unsigned ld_goff = static_cast<unsigned>((ptid >> 2) * 64 + (((ptid & 3) ^ swzx(ptid >> 2)) << 4));
+        const unsigned ld_goff = static_cast<unsigned>((ptid >> 2) * 64 + (((ptid & 3) ^ swz4x(ptid >> 2)) << 4));
         unsigned ld_goff_tail;
         {
             const int q = 768 + tailn * wq + min(lane, tailn - 1);
             const int p = q >> 2, c = q & 3;
-            ld_goff_tail = static_cast<unsigned>(min(p, W - 1) * 64 + ((c ^ swzx(p)) << 4));
+            ld_goff_tail = static_cast<unsigned>(min(p, W - 1) * 64 + ((c ^ swz4x(p)) << 4));
         }
         auto issue_A_piece = [&](auto IC_, const char* row, int slot) __attribute__((always_inline)) {
             constexpr int i = decltype(IC_)::value;
@@ -321,7 +302,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
             const int p = xw + px16 + kx;                 // (tile k adds 16 pixels = 1024 bytes: same swizzle; no clamp: columns right
-            baseA[kx] = ringA_lds + static_cast<unsigned>(p * 64 + ((g ^ swzx(p)) << 4));   //  of the row only feed columns that are dropped)
+            baseA[kx] = ringA_lds + static_cast<unsigned>(p * 64 + ((g ^ swz4x(p)) << 4));   //  of the row only feed columns that are dropped)
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -333,7 +314,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
             else if constexpr (NB)  // 8 bytes (the lane's 4 computed couts) at 8 g of the 32-byte pixel (no swizzle: see baseN0)
                 wbB[k] = ringB_lds + static_cast<unsigned>(col * 32 + 8 * g);
             else
-                wbB[k] = ringB_lds + static_cast<unsigned>(col * 64 + ((g ^ swzx(col)) << 4));
+                wbB[k] = ringB_lds + static_cast<unsigned>(col * 64 + ((g ^ swz4x(col)) << 4));
         }
         // folded BN of the lane's 8 couts (8 g .. 8 g + 7)
         f32x4 scv[2], shv[2];
@@ -605,7 +586,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
         const int p = xw + px16 + kx;
-        baseB[kx] = ringB_lds + static_cast<unsigned>(p * 64 + ((g ^ swzx(p)) << 4));
+        baseB[kx] = ringB_lds + static_cast<unsigned>(p * 64 + ((g ^ swz4x(p)) << 4));
     }
     // narrow form: the 9 taps x 16 channels are contracted as five K = 32 chunks of two taps, tap 2 c + (g >> 1) of chunk c (tap 9 has
     // zero weights): (ky0: kx0 | kx1) (ky0: kx2 | ky1: kx0) (ky1: kx1 | kx2) (ky2: kx0 | kx1) (ky2: kx2 | -); a lane reads channels
@@ -932,15 +913,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
     if (rem > 1) step(IC<1>{}, t + 1);
     if (rem > 2) step(IC<2>{}, t + 2);
     wait_vmcnt<0>();
-#ifdef RN_CLOCK
-    if (a.stamp_buf && tid == 256) {
-        unsigned long long t1, r1;
-        clock_pair(t1, r1);
-        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
-        a.stamp_buf[wg * 2 + 0] = t1 - ck_t0;
-        a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
-    }
-#endif
+    RN_CLOCK_EXIT(a.stamp_buf, tid == 256);
 }
 
 }  // namespace

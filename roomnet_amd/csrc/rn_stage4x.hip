@@ -38,31 +38,13 @@ constexpr int U_RING_OFF = U_TAB_BYTES;
 constexpr int U_LDS = U_RING_OFF + U_NS * U_ROW;
 constexpr int U_WMIN = 193, U_WMAX = 206;
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-__device__ __forceinline__ int swz4x(int pix) { return (pix >> 1) & 3; }   // 4 chunks per 64-byte pixel (rn_stage23x.hip)
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 template <int DT, int NQ>
 __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_kernel(const StageArgs a) {
     constexpr int U_NW = NQ == 4 ? 8 : 12;            // waves
     constexpr int U_NTH = U_NW * 64;
     constexpr int U_NT = NQ == 4 ? 7 : 4;             // tiles of the longest run
     constexpr int U_NU = (U_NT + 1) / 2;              // tile pairs (output stores per odd step) of the longest run
-#ifdef RN_CLOCK
-    unsigned long long ck_t0, ck_r0;
-    clock_pair(ck_t0, ck_r0);
-#endif
+    RN_CLOCK_ENTRY();
     extern __shared__ __attribute__((aligned(64))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -143,28 +125,8 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
         base[kx] = ring_lds + static_cast<unsigned>(p * 64 + ((g ^ swz4x(p)) << 4));
     }
 
-    // ---- pooling band matrices (stride 2): see rn_stage5x.hip
-    i32x4 pmA, pmB, pmC;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned wa = 0, wb = 0, wc = 0;
-#pragma unroll
-        for (int e2 = 0; e2 < 2; ++e2) {
-            const int e = 2 * d + e2;
-            const int p = 4 * g + (e & 3);
-            const int nn = px16;
-            const bool inA = nn < 8 && p >= 2 * nn && p <= 2 * nn + 3;
-            const bool inB = (nn < 8 && 16 + p >= 2 * nn && 16 + p <= 2 * nn + 3) || (nn >= 8 && p >= 2 * (nn - 8) && p <= 2 * (nn - 8) + 3);
-            const bool inC = nn >= 8 && 16 + p >= 2 * (nn - 8) && 16 + p <= 2 * (nn - 8) + 3;
-            wa |= (inA ? 0x3C00u : 0u) << (16 * e2);
-            wb |= (inB ? 0x3C00u : 0u) << (16 * e2);
-            wc |= (inC ? 0x3C00u : 0u) << (16 * e2);
-        }
-        pmA[d] = static_cast<int>(wa);
-        pmB[d] = static_cast<int>(wb);
-        pmC[d] = static_cast<int>(wc);
-    }
-    asm volatile("" : "+v"(pmA), "+v"(pmB), "+v"(pmC));
+    // ---- pooling band matrices (stride 2)
+    RN_POOL_BANDS_S2(pmA, pmB, pmC, px16, g);
 
     // ---- output stores: tile pair u = 16 pooled columns (pair 3 of the longer run: its 7th tile alone, 7 columns)
     int voff[U_NU];
@@ -341,15 +303,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
     if (rem > 3) step(IC<0>{}, IC<1>{}, s + 3);
     if (rem > 4) step(IC<1>{}, IC<0>{}, s + 4);
     wait_vmcnt<0>();
-#ifdef RN_CLOCK
-    if (a.stamp_buf && threadIdx.x == 256) {
-        unsigned long long t1, r1;
-        clock_pair(t1, r1);
-        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
-        a.stamp_buf[wg * 2 + 0] = t1 - ck_t0;
-        a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
-    }
-#endif
+    RN_CLOCK_EXIT(a.stamp_buf, threadIdx.x == 256);
 }
 
 }  // namespace

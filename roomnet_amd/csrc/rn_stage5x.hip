@@ -45,29 +45,10 @@ constexpr int V_LDS = V_RING_OFF + V_NS * V_ROW;
 constexpr int V_WMIN = 66, V_WMAX = 110;
 static_assert(V_LDS <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-// 8 chunks per 128-byte pixel: chunk ^ (pixel & 7) is conflict-free for the 16x16x32 operand read (rn_conv16.hip)
-__device__ __forceinline__ int swz8(int pix) { return pix & 7; }
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 template <int DT, bool K48>
 __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     constexpr int NF = K48 ? 5 : 6;                   // operand fragments per tile and row step
-#ifdef RN_CLOCK
-    unsigned long long ck_t0, ck_r0;
-    clock_pair(ck_t0, ck_r0);
-#endif
+    RN_CLOCK_ENTRY();
     extern __shared__ __attribute__((aligned(64))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -161,30 +142,8 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
         }
     }
 
-    // ---- pooling band matrices (stride 2).  The 16 pooled columns n of a tile PAIR: n < 8 start in the pair's first tile
-    // (window = its columns 2n .. 2n+3; n = 7 ends in the second tile), n >= 8 in the second (n = 15 ends in the tile after).
-    // K element 8 g + e of an operand = pixel 4 g + (e & 3) of the tile (older pair sum for e < 4, newer for e >= 4).
-    i32x4 pmA, pmB, pmC;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned wa = 0, wb = 0, wc = 0;
-#pragma unroll
-        for (int e2 = 0; e2 < 2; ++e2) {
-            const int e = 2 * d + e2;
-            const int p = 4 * g + (e & 3);
-            const int nn = px16;
-            const bool inA = nn < 8 && p >= 2 * nn && p <= 2 * nn + 3;
-            const bool inB = (nn < 8 && 16 + p >= 2 * nn && 16 + p <= 2 * nn + 3) || (nn >= 8 && p >= 2 * (nn - 8) && p <= 2 * (nn - 8) + 3);
-            const bool inC = nn >= 8 && 16 + p >= 2 * (nn - 8) && 16 + p <= 2 * (nn - 8) + 3;
-            wa |= (inA ? 0x3C00u : 0u) << (16 * e2);
-            wb |= (inB ? 0x3C00u : 0u) << (16 * e2);
-            wc |= (inC ? 0x3C00u : 0u) << (16 * e2);
-        }
-        pmA[d] = static_cast<int>(wa);
-        pmB[d] = static_cast<int>(wb);
-        pmC[d] = static_cast<int>(wc);
-    }
-    asm volatile("" : "+v"(pmA), "+v"(pmB), "+v"(pmC));
+    // ---- pooling band matrices (stride 2)
+    RN_POOL_BANDS_S2(pmA, pmB, pmC, px16, g);
 
     // ---- residual: tile pair u interpolates its 16 pooled columns from 64 source columns starting at xs_u (kept inside the
     // row); two K halves.  Transposed reads: lane 4 q + p' of a 16-lane group supplies pixel row q, couts 16 cq + 4 p' .. + 3.
@@ -484,15 +443,7 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     if (rem > 3) step(IC<0>{}, IC<1>{}, s + 3);
     if (rem > 4) step(IC<1>{}, IC<0>{}, s + 4);
     wait_vmcnt<0>();
-#ifdef RN_CLOCK
-    if (a.stamp_buf && threadIdx.x == 256) {
-        unsigned long long t1, r1;
-        clock_pair(t1, r1);
-        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
-        a.stamp_buf[wg * 2 + 0] = t1 - ck_t0;
-        a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
-    }
-#endif
+    RN_CLOCK_EXIT(a.stamp_buf, threadIdx.x == 256);
 }
 
 }  // namespace

@@ -25,21 +25,6 @@ constexpr int S6_ROW = 52 * 128;                  // bytes per ring row (padded)
 constexpr int S6_LDS = S6_NS * S6_ROW;
 constexpr int S6_WMIN = 35, S6_WMAX = 50;
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
-}
-__device__ __forceinline__ int swz8(int pix) { return pix & 7; }
-
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    if constexpr (DT == RN_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // K48 (round 6): the input channels 48..63 are constants of the handle (the residual stage in front writes them from a table,
 // rn_fused_prepare): five operand fragments per tile and row step instead of six -- rn_stage5x.hip's scheme: (kx, channels 0..31)
 // for kx = 0, 1, 2, then [kx 0 | kx 1] and [kx 2 | zero weights] of channels 32..47 -- read a whole tile ahead, and the
@@ -47,10 +32,7 @@ __device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
 template <int DT, bool K48>
 __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
     constexpr int NF = K48 ? 5 : 6;
-#ifdef RN_CLOCK
-    unsigned long long ck_t0, ck_r0;
-    clock_pair(ck_t0, ck_r0);
-#endif
+    RN_CLOCK_ENTRY();
     extern __shared__ __attribute__((aligned(64))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -254,15 +236,7 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
     if (rem > 0) step(IC<0>{}, s);
     if (rem > 1) step(IC<1>{}, s + 1);
     wait_vmcnt<0>();
-#ifdef RN_CLOCK
-    if (a.stamp_buf && threadIdx.x == 256) {
-        unsigned long long t1, r1;
-        clock_pair(t1, r1);
-        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
-        a.stamp_buf[wg * 2 + 0] = t1 - ck_t0;
-        a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
-    }
-#endif
+    RN_CLOCK_EXIT(a.stamp_buf, threadIdx.x == 256);
 }
 
 }  // namespace

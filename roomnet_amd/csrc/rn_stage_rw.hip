@@ -172,10 +172,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     constexpr int RW_NSLOT = C::NSLOT, RW_AHEAD = C::AHEAD;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef RN_CLOCK
-    unsigned long long ck_t0, ck_r0;
-    clock_pair(ck_t0, ck_r0);
-#endif
+    RN_CLOCK_ENTRY();
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -634,7 +631,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     // in-flight LDS-DMA writes and inserts s_waitcnt vmcnt(0) in front of it, draining the whole
     // prefetch queue every row.  The skip pair read here was retired by the counted wait of the
     // previous step.  The asm loads are waited for by skip_wait() (names every destination).
-    using i32x2 = __attribute__((ext_vector_type(2))) int;
     auto tr_read = [&](const char* p) __attribute__((always_inline)) -> i32x2 {
         i32x2 v;
         const unsigned addr = static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) const char*)p));
@@ -1190,15 +1186,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         ((s % RW_NSLOT == I ? (step(IC<I>{}, F{}, T{}, s), 0) : 0), ...);
     }(std::make_integer_sequence<int, RW_NSLOT>{});
     wait_vmcnt<0>();   // the clamped re-fetches of the last steps are still in flight
-#ifdef RN_CLOCK
-    if (a.stamp_buf && tid == 0) {
-        unsigned long long t1, r1;
-        clock_pair(t1, r1);
-        const int64_t wg = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
-        a.stamp_buf[wg * 2 + 0] = t1 - ck_t0;
-        a.stamp_buf[wg * 2 + 1] = r1 - ck_r0;
-    }
-#endif
+    RN_CLOCK_EXIT(a.stamp_buf, tid == 0);
 }
 
 template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS = 1, bool S0F = false, bool WIDE = false, int S0SH = 0>

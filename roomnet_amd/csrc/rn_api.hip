@@ -74,6 +74,19 @@ int rn_stage_sides(const rn_weights* w, std::vector<int>& conv, std::vector<int>
     return w->n_stages;
 }
 
+int rn_lastblock_sides(const rn_weights* w, rn_lastblock* s) {
+    std::vector<int> conv, out;
+    const int ns = w->n_stages, fit = rn_stage_sides(w, conv, out);
+    if (fit == ns && ns >= 4) *s = rn_lastblock{out[ns - 4], conv[ns - 3], out[ns - 3], conv[ns - 2], out[ns - 2], conv[ns - 1], out[ns - 1]};
+    return fit;
+}
+
+void rn_lastblock_resize_tables(const rn_lastblock& s, std::vector<int32_t>& rtab, std::vector<float>& lerp) {
+    rtab.resize(2 * static_cast<size_t>(s.S9));
+    lerp.resize(s.S9);
+    rn_legacy_resize_table(s.S7, s.S9, rtab.data(), rtab.data() + s.S9, lerp.data());
+}
+
 RelabelledWeights::RelabelledWeights(const rn_weights* src) : w(*src), stages(src->stages, src->stages + src->n_stages) {
     w.stages = stages.data();
 }
@@ -784,6 +797,14 @@ extern "C" int rn_forward_u8_device(rn_handle* h, const uint8_t* d_bgr, int n, f
     return forward_device(h, d_bgr, nullptr, n, d_probs, d_ids);
 }
 
+// the tail of the host entry points: the call's probabilities and classes (h->d_probs, h->d_ids) to the caller, one synchronisation
+static int results_to_host(rn_handle* h, int n, float* probs, int64_t* ids) {
+    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipStreamSynchronize(h->stream));
+    return RN_OK;
+}
+
 extern "C" int rn_forward_u8(rn_handle* h, const uint8_t* bgr, int n, float* probs, int64_t* ids) {
     int rc = check_call(h, n, bgr, probs, ids);
     if (rc != RN_OK) return rc;
@@ -791,33 +812,38 @@ extern "C" int rn_forward_u8(rn_handle* h, const uint8_t* bgr, int n, float* pro
     const size_t in_bytes = static_cast<size_t>(n) * h->im_side * h->im_side * 3;
     RN_HIP(hipMemcpyAsync(h->d_in_u8, bgr, in_bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost,
-                          h->stream));
-    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipStreamSynchronize(h->stream));
-    return RN_OK;
+    return results_to_host(h, n, probs, ids);
 }
 
 // ---- grad-CAM class-evidence maps (rn_gradcam.hip): the forward pass of the call (16-bit handles: the back end as its split
 // launches, so that s6.bn and s7.bn reach HBM), then the adjoint of the last conv block and the head
 namespace {
-int gradcam_check(rn_handle* h, int n, int layer_node, bool* layer6) {
+// The shared front of the grad-CAM and the feature entry points (`name`): a handle of the inference graph whose last block the
+// adjoint kernels walk, and n inside the handle's batch.  `what` is the entry point's product, for the RN_FLAG_BATCH_STATS refusal;
+// `range_rc` what n out of range returns (grad-CAM: RN_E_INVALID, features: RN_E_RANGE).
+int last_block_check(const rn_handle* h, int n, const char* name, const char* what, int range_rc) {
     if (!h) {
         rn_set_error("null handle");
         return RN_E_INVALID;
     }
     if (h->bnstats) {
-        rn_set_error("rn_grad_cam: the adjoint is that of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)");
+        rn_set_error("%s: %s of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)", name, what);
         return RN_E_STATE;
     }
     if (const char* why = rn_gradcam_unsupported(h)) {
-        rn_set_error("rn_grad_cam: not supported on this graph (%s)", why);
+        rn_set_error("%s: not supported on this graph (%s)", name, why);
         return RN_E_INVALID;
     }
     if (n < 1 || n > h->max_batch) {
-        rn_set_error("rn_grad_cam: n = %d out of range (1..%d)", n, h->max_batch);
-        return RN_E_INVALID;
+        rn_set_error("%s: n = %d out of range (1..%d)", name, n, h->max_batch);
+        return range_rc;
     }
+    return RN_OK;
+}
+
+int gradcam_check(rn_handle* h, int n, int layer_node, bool* layer6) {
+    int rc = last_block_check(h, n, "rn_grad_cam", "the adjoint is that", RN_E_INVALID);
+    if (rc != RN_OK) return rc;
     int node6, node7;
     rn_gradcam_layers(h, &node6, &node7);
     if (layer_node != node6 && layer_node != node7) {
@@ -885,15 +911,10 @@ int gradcam_host(rn_handle* h, const uint8_t* bgr, const float* rgb, int n, cons
     rc = gradcam_device(h, bgr ? h->d_in_u8 : nullptr, bgr ? nullptr : static_cast<const float*>(h->nodes[h->node_input].ptr), n,
                         class_ids ? d_cls : nullptr, layer6, d_cam, d_alpha, h->d_probs, h->d_ids);
     if (rc != RN_OK) return rc;
-    int node6, node7;
-    rn_gradcam_layers(h, &node6, &node7);
     const rn_node_info& li = h->nodes[layer_node].info;
     RN_HIP(hipMemcpyAsync(cam, d_cam, static_cast<size_t>(n) * li.h * li.w * 4, hipMemcpyDeviceToHost, h->stream));
     if (alpha) RN_HIP(hipMemcpyAsync(alpha, d_alpha, static_cast<size_t>(n) * li.c * 4, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipStreamSynchronize(h->stream));
-    return RN_OK;
+    return results_to_host(h, n, probs, ids);
 }
 }  // namespace
 
@@ -930,30 +951,20 @@ extern "C" int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, in
 // ---- feature read-out for the fine-tuning cache (rn_finetune.hip): a forward pass that leaves s7.bn (depth 2) or s6.bn (depth 3)
 // in HBM, widened to float32
 namespace {
-int features_check(rn_handle* h, int n, int* node7, int depth = 2) {
-    if (depth != 2 && depth != 3) {
-        rn_set_error("rn_features_depth: depth = %d is neither 2 (s7.bn) nor 3 (s6.bn)", depth);
-        return RN_E_INVALID;
-    }
-    if (!h) {
-        rn_set_error("null handle");
-        return RN_E_INVALID;
-    }
-    if (h->bnstats) {
-        rn_set_error("rn_features: the cached features are those of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)");
-        return RN_E_STATE;
-    }
-    if (const char* why = rn_gradcam_unsupported(h)) {
-        rn_set_error("rn_features: not supported on this graph (%s)", why);
-        return RN_E_INVALID;
-    }
-    if (n < 1 || n > h->max_batch) {
-        rn_set_error("rn_features: n = %d out of range (1..%d)", n, h->max_batch);
-        return RN_E_RANGE;
-    }
-    int node6;
-    rn_gradcam_layers(h, &node6, node7);
-    if (depth == 3) *node7 = node6;
+int features_depth_check(int depth) {
+    if (depth == 2 || depth == 3) return RN_OK;
+    rn_set_error("rn_features_depth: depth = %d is neither 2 (s7.bn) nor 3 (s6.bn)", depth);
+    return RN_E_INVALID;
+}
+
+// the node the features of `depth` are read from: s7.bn (2) or s6.bn (3)
+int features_check(rn_handle* h, int n, int* node, int depth) {
+    int rc = features_depth_check(depth);
+    if (rc == RN_OK) rc = last_block_check(h, n, "rn_features", "the cached features are those", RN_E_RANGE);
+    if (rc != RN_OK) return rc;
+    int node6, node7;
+    rn_gradcam_layers(h, &node6, &node7);
+    *node = depth == 3 ? node6 : node7;
     return RN_OK;
 }
 
@@ -980,7 +991,9 @@ int features_device(rn_handle* h, const uint8_t* d_bgr, int n, int node7, float*
 }
 }  // namespace
 
-extern "C" int rn_features_shape(const rn_handle* h, int* side, int* channels) {
+extern "C" int rn_features_depth_shape(const rn_handle* h, int depth, int* side, int* channels) {
+    int rc = features_depth_check(depth);
+    if (rc != RN_OK) return rc;
     if (!h) {
         rn_set_error("null handle");
         return RN_E_INVALID;
@@ -991,24 +1004,13 @@ extern "C" int rn_features_shape(const rn_handle* h, int* side, int* channels) {
     }
     int node6, node7;
     rn_gradcam_layers(h, &node6, &node7);
-    if (side) *side = h->nodes[node7].info.h;
-    if (channels) *channels = h->nodes[node7].info.c;
+    const rn_node_info& li = h->nodes[depth == 3 ? node6 : node7].info;
+    if (side) *side = li.h;
+    if (channels) *channels = li.c;
     return RN_OK;
 }
 
-extern "C" int rn_features_depth_shape(const rn_handle* h, int depth, int* side, int* channels) {
-    if (depth != 2 && depth != 3) {
-        rn_set_error("rn_features_depth: depth = %d is neither 2 (s7.bn) nor 3 (s6.bn)", depth);
-        return RN_E_INVALID;
-    }
-    int rc = rn_features_shape(h, side, channels);
-    if (rc != RN_OK || depth == 2) return rc;
-    int node6, node7;
-    rn_gradcam_layers(h, &node6, &node7);
-    if (side) *side = h->nodes[node6].info.h;
-    if (channels) *channels = h->nodes[node6].info.c;
-    return RN_OK;
-}
+extern "C" int rn_features_shape(const rn_handle* h, int* side, int* channels) { return rn_features_depth_shape(h, 2, side, channels); }
 
 extern "C" int rn_features_depth_u8_device(rn_handle* h, int depth, const uint8_t* d_bgr_nhwc, int n, float* d_feat) {
     int node = -1;
@@ -1022,14 +1024,7 @@ extern "C" int rn_features_depth_u8_device(rn_handle* h, int depth, const uint8_
 }
 
 extern "C" int rn_features_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, float* d_feat) {
-    int node7 = -1;
-    int rc = features_check(h, n, &node7);
-    if (rc != RN_OK) return rc;
-    if (!d_bgr_nhwc || !d_feat) {
-        rn_set_error("null buffer");
-        return RN_E_INVALID;
-    }
-    return features_device(h, d_bgr_nhwc, n, node7, d_feat);
+    return rn_features_depth_u8_device(h, 2, d_bgr_nhwc, n, d_feat);
 }
 
 namespace {
@@ -1254,11 +1249,7 @@ extern "C" int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images,
     RN_HIP(hipMemcpyAsync(h->d_items, h->items_host.data(), static_cast<size_t>(n) * sizeof(rn_resize_item), hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_launch_resize_batch_u8(h->stream, h->d_items, n, h->d_in_u8, S)) != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost,
-                          h->stream));
-    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipStreamSynchronize(h->stream));
-    return RN_OK;
+    return results_to_host(h, n, probs, ids);
 }
 
 extern "C" int rn_forward_f32(rn_handle* h, const float* rgb, int n, float* probs, int64_t* ids) {
@@ -1273,11 +1264,7 @@ extern "C" int rn_forward_f32(rn_handle* h, const float* rgb, int n, float* prob
     const size_t in_bytes = static_cast<size_t>(n) * h->im_side * h->im_side * 3 * 4;
     RN_HIP(hipMemcpyAsync(in_node, rgb, in_bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_forward_f32_device(h, in_node, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost,
-                          h->stream));
-    RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
-    RN_HIP(hipStreamSynchronize(h->stream));
-    return RN_OK;
+    return results_to_host(h, n, probs, ids);
 }
 
 extern "C" int rn_node_count(const rn_handle* h) { return h ? static_cast<int>(h->nodes.size()) : 0; }

@@ -26,7 +26,8 @@
 //   handed to the launch as one float32.
 //
 // Two launches per step, enqueued back to back on the trainer's stream (no graph capture; one synchronisation per rn_ft_run):
-//   ft_item_kernel    one workgroup per item of the minibatch (modelled on gc_tail_kernel): conv weights and BN tables in LDS,
+//   ft_item_kernel    one workgroup per item of the minibatch (the per-element steps of rn_lastblock.h, which gc_tail_kernel is built
+//                     from as well, under this kernel's own loops and epilogues): conv weights and BN tables in LDS,
 //                     intermediates in a per-item float32 workspace, the item's feature read from the resident cache through the
 //                     index.  Forward, softmax and the item's CE term, then the adjoint; writes the item's partials of every
 //                     gradient: dW8, dW9 (plain FMAs: 144 (tap, cin) pairs x 3 row groups of threads, 16 cout accumulators each,
@@ -45,35 +46,35 @@
 // (22 variables), and a step is four launches; stage 7's mathematics and its two kernels are in rn_finetune7.hip:
 //   ft7_fwd_kernel    x6 (through the index) -> x7 into a per-step workspace, with what the adjoint needs
 //   ft_item_kernel    the depth-3 instantiation reads x7 from that workspace and goes on behind conv 8's weight gradient:
-//                     g7 = dL/dx7 = conv 8's adjoint + the transpose of the skip resize (as gc_tail_kernel has them), the item's
+//                     g7 = dL/dx7 = conv 8's adjoint + the transpose of the skip resize (rn_lastblock.h), the item's
 //                     d gamma7 = sum g7 xh7 and d beta7 = sum g7, and dL/dpool7 = g7 gamma7 rsqrt(var7 + eps) for the next launch
 //   ft7_bwd_kernel    dL/dconv7 and one dW7 partial per (item, band)
 //   ft_update_kernel  the depth-3 instantiation sums the dW7 partials over bands, then over items, in index order, in float64
-// The depth-2 instantiations take the arguments and run the code they always did.
+// Both depths pass the same FtItemArgs / FtUpdateArgs: the depth-3 fields are null or zero at depth 2, and the one variable list has
+// conv 7's three variables in front at depth 3.  The kernels are templates on the depth; the depth-2 instantiations run the code they
+// always did.
 #include "rn_finetune7.h"
 #include "rn_internal.h"
+#include "rn_lastblock.h"
 #include "rn_stage.h"
 
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 using namespace rnk;
 
 namespace {
 
-constexpr int FT_C = 16;             // channels of the last block
 constexpr int FT_NT = 512;           // threads of the item workgroup
-constexpr int FT_HMAX = 64;          // widest dense layer (rn_tail_graph_reason enforces nout <= 64)
-constexpr int FT_W = 9 * FT_C * FT_C;
-constexpr int FT_WG_PAIRS = 9 * FT_C;  // (tap, cin) pairs of a weight gradient
+constexpr int FT_W = 9 * LB_C * LB_C;
+constexpr int FT_WG_PAIRS = 9 * LB_C;  // (tap, cin) pairs of a weight gradient
 constexpr int FT_WG_GROUPS = 3;        // row groups (FT_WG_PAIRS * FT_WG_GROUPS <= FT_NT)
-constexpr int FT_MAX_VARS = 8 + 3 * RN_MAX_DENSE;
+constexpr int FT_MAX_VARS = 11 + 3 * RN_MAX_DENSE;   // depth 3: conv 7's three in front
 
 struct FtItemArgs {
-    const float* feats;              // [n_items, S7, S7, 16]
+    const float* feats;              // [n_items, S7, S7, 16] (depth 3: unused, the item kernel reads x7ws)
     const int32_t* labels;           // [n_items] (eval: may be null)
     const int32_t* index;            // item of workgroup b = index[base + b]; null: base + b
     int64_t base;
@@ -82,9 +83,7 @@ struct FtItemArgs {
     const float* F;                  // frozen [mean | rsqrt(var + eps)] per BN
     int o_w8, o_g8, o_b8, o_w9, o_g9, o_b9, o_g9b, o_b9b;
     int f_bn8, f_bn9, f_bn9b;
-    const int32_t* rlo;              // legacy bilinear tables S7 -> S9
-    const int32_t* rhi;
-    const float* rlerp;
+    LbResize rs;                     // legacy bilinear tables S7 -> S9
     int n_dense, nc;
     int nin[RN_MAX_DENSE], nout[RN_MAX_DENSE];
     int o_dw[RN_MAX_DENSE], o_db[RN_MAX_DENSE], o_dg[RN_MAX_DENSE], o_dbeta[RN_MAX_DENSE], f_dbn[RN_MAX_DENSE];   // -1: absent
@@ -99,10 +98,7 @@ struct FtItemArgs {
     int n_param;                     // floats of the parameter slab
     float* probs;                    // eval: [batch, nc], one chunk's staging (null in training)
     int64_t* ids;                    // eval: [batch]
-};
-
-// depth 3: what the item kernel takes on top
-struct FtItemArgs7 : FtItemArgs {
+    // depth 3 (null / zero at depth 2)
     const float* x7ws;               // [batch, S7, S7, 16] s7.bn of the step (ft7_fwd_kernel)
     const float* xh7;                // [batch, S7, S7, 16] its normalised value before gamma and beta
     float* dpool7;                   // [batch, S7, S7, 16] dL/dpool7 for ft7_bwd_kernel
@@ -110,49 +106,13 @@ struct FtItemArgs7 : FtItemArgs {
     int o_g7, f_bn7, p_bn7;
 };
 
-__device__ __forceinline__ bool relu6_passes(float v) { return v > 0.f && v < 6.f; }
-
-// pooled rows (or columns) whose 4 x 4 / stride-2 window covers conv row Y
-__device__ __forceinline__ void pool_span(int Y, int So, int* lo, int* hi) {
-    *lo = Y < 3 ? 0 : (Y - 2) / 2;
-    *hi = min(So - 1, Y / 2);
-}
-
-// conv3x3 VALID 16 -> 16 pre-activation of one output element: in [S][S][16] float32 (global), w [9][16][16] (LDS)
-__device__ __forceinline__ float conv16_at(const float* in, int S, const float* w, int y, int x, int co) {
-    float acc = 0.f;
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) {
-            const f32x4* px = reinterpret_cast<const f32x4*>(in + (static_cast<int64_t>(y + ky) * S + x + kx) * FT_C);
-            const float* wt = w + (ky * 3 + kx) * FT_C * FT_C + co;
-#pragma unroll
-            for (int c4 = 0; c4 < FT_C / 4; ++c4) {
-                const f32x4 v = px[c4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc = fmaf(v[q], wt[(4 * c4 + q) * FT_C], acc);
-            }
-        }
-    return acc;
-}
-
-__device__ __forceinline__ float dot16(const float* g, const float* w, float t) {
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-#pragma unroll
-    for (int c4 = 0; c4 < FT_C / 4; ++c4) {
-        const f32x4 v = g4[c4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t = fmaf(v[q], w[4 * c4 + q], t);
-    }
-    return t;
-}
-
 // sum of `val` over the 32 threads that share channel tid & 15, in a fixed order; the result is valid for tid < 16
 __device__ __forceinline__ float channel_sum(float val, float* red, int tid) {
     red[tid] = val;
     __syncthreads();
     float t = 0.f;
-    if (tid < FT_C)
-        for (int part = 0; part < FT_NT / FT_C; ++part) t += red[part * FT_C + tid];
+    if (tid < LB_C)
+        for (int part = 0; part < FT_NT / LB_C; ++part) t += red[part * LB_C + tid];
     __syncthreads();
     return t;
 }
@@ -163,46 +123,45 @@ __device__ __forceinline__ float channel_sum(float val, float* red, int tid) {
 __device__ __forceinline__ void wgrad16(const float* in, int S, const float* dout, int Co, float* out, float* red3, int tid) {
     if (tid < FT_WG_PAIRS * FT_WG_GROUPS) {
         const int pair = tid % FT_WG_PAIRS, grp = tid / FT_WG_PAIRS;
-        const int k = pair / FT_C, ci = pair % FT_C, ky = k / 3, kx = k % 3;
-        float acc[FT_C];
+        const int k = pair / LB_C, ci = pair % LB_C, ky = k / 3, kx = k % 3;
+        float acc[LB_C];
 #pragma unroll
-        for (int q = 0; q < FT_C; ++q) acc[q] = 0.f;
+        for (int q = 0; q < LB_C; ++q) acc[q] = 0.f;
         for (int y = grp; y < Co; y += FT_WG_GROUPS) {
-            float row[FT_C];
+            float row[LB_C];
 #pragma unroll
-            for (int q = 0; q < FT_C; ++q) row[q] = 0.f;
-            const float* pin = in + (static_cast<int64_t>(y + ky) * S + kx) * FT_C + ci;
-            const f32x4* pd = reinterpret_cast<const f32x4*>(dout + static_cast<int64_t>(y) * Co * FT_C);
+            for (int q = 0; q < LB_C; ++q) row[q] = 0.f;
+            const float* pin = in + (static_cast<int64_t>(y + ky) * S + kx) * LB_C + ci;
+            const f32x4* pd = reinterpret_cast<const f32x4*>(dout + static_cast<int64_t>(y) * Co * LB_C);
             for (int x = 0; x < Co; ++x) {
-                const float a = pin[x * FT_C];
+                const float a = pin[x * LB_C];
 #pragma unroll
-                for (int c4 = 0; c4 < FT_C / 4; ++c4) {
-                    const f32x4 d = pd[x * (FT_C / 4) + c4];
+                for (int c4 = 0; c4 < LB_C / 4; ++c4) {
+                    const f32x4 d = pd[x * (LB_C / 4) + c4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) row[4 * c4 + q] = fmaf(a, d[q], row[4 * c4 + q]);
                 }
             }
 #pragma unroll
-            for (int q = 0; q < FT_C; ++q) acc[q] += row[q];
+            for (int q = 0; q < LB_C; ++q) acc[q] += row[q];
         }
 #pragma unroll
-        for (int q = 0; q < FT_C; ++q) red3[grp * FT_W + pair * FT_C + q] = acc[q];
+        for (int q = 0; q < LB_C; ++q) red3[grp * FT_W + pair * LB_C + q] = acc[q];
     }
     __syncthreads();
     for (int o = tid; o < FT_W; o += FT_NT) out[o] = (red3[o] + red3[FT_W + o]) + red3[2 * FT_W + o];
     __syncthreads();
 }
 
-template <bool TRAIN, typename Args>
-__global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
-    constexpr bool D3 = std::is_same_v<Args, FtItemArgs7>;
+template <bool TRAIN, bool D3>
+__global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
     __shared__ float w8[FT_W];
     __shared__ float w9[FT_W];
-    __shared__ float tab[3 * 4 * FT_C];                  // bn8 | bn9 | bn9b, each [mean | rsq | gamma | beta]
-    __shared__ float hx[RN_MAX_DENSE][FT_HMAX];           // input of dense layer d (d >= 1)
-    __shared__ float hxh[RN_MAX_DENSE][FT_HMAX];          // normalised ReLU6 output of dense layer d, before gamma and beta
-    __shared__ float hmm[RN_MAX_DENSE][FT_HMAX];          // pre-activation of dense layer d
-    __shared__ float hg[2][FT_HMAX];
+    __shared__ float tab[3 * 4 * LB_C];                  // bn8 | bn9 | bn9b, each [mean | rsq | gamma | beta]
+    __shared__ float hx[RN_MAX_DENSE][LB_HMAX];           // input of dense layer d (d >= 1)
+    __shared__ float hxh[RN_MAX_DENSE][LB_HMAX];          // normalised ReLU6 output of dense layer d, before gamma and beta
+    __shared__ float hmm[RN_MAX_DENSE][LB_HMAX];          // pre-activation of dense layer d
+    __shared__ float hg[2][LB_HMAX];
     __shared__ float red[FT_NT];
     __shared__ float red3[TRAIN ? FT_WG_GROUPS * FT_W : 1];
     __shared__ double dred[TRAIN ? FT_NT : 1];
@@ -212,9 +171,9 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
     const int64_t item = a.index ? static_cast<int64_t>(a.index[a.base + b]) : a.base + b;
     const float* x7;
     if constexpr (D3)
-        x7 = a.x7ws + static_cast<int64_t>(b) * S7 * S7 * FT_C;
+        x7 = a.x7ws + static_cast<int64_t>(b) * S7 * S7 * LB_C;
     else
-        x7 = a.feats + item * S7 * S7 * FT_C;
+        x7 = a.feats + item * S7 * S7 * LB_C;
     float* wsi = a.ws + b * a.ws_item;
     float* c8 = wsi + a.off_c8;
     float* xh8 = wsi + a.off_xh8;
@@ -229,12 +188,12 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
         w8[i] = P[a.o_w8 + i];
         w9[i] = P[a.o_w9 + i];
     }
-    if (tid < 2 * FT_C) {
+    if (tid < 2 * LB_C) {
         tab[tid] = F[a.f_bn8 + tid];
         tab[64 + tid] = F[a.f_bn9 + tid];
         tab[128 + tid] = F[a.f_bn9b + tid];
-    } else if (tid < 3 * FT_C) {
-        const int c = tid - 2 * FT_C;
+    } else if (tid < 3 * LB_C) {
+        const int c = tid - 2 * LB_C;
         tab[32 + c] = P[a.o_g8 + c];
         tab[48 + c] = P[a.o_b8 + c];
         tab[96 + c] = P[a.o_g9 + c];
@@ -244,39 +203,30 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
     }
     __syncthreads();
     // ---- forward
-    for (int i = tid; i < C8 * C8 * FT_C; i += FT_NT) {
+    for (int i = tid; i < C8 * C8 * LB_C; i += FT_NT) {
         const int co = i & 15, p = i >> 4;
         c8[i] = conv16_at(x7, S7, w8, p / C8, p % C8, co);
     }
     __syncthreads();
-    for (int i = tid; i < S8 * S8 * FT_C; i += FT_NT) {
+    for (int i = tid; i < S8 * S8 * LB_C; i += FT_NT) {
         const int co = i & 15, p = i >> 4, y = p / S8, x = p % S8;
-        float t = 0.f;
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) t += relu6f(c8[((2 * y + ky) * C8 + 2 * x + kx) * FT_C + co]);
+        const float t = pool_relu6_sum(c8, C8, y, x, co);
         const float xh = (t * (1.0f / 16.0f) - tab[co]) * tab[16 + co];
         if (TRAIN) xh8[i] = xh;
         s8[i] = fmaf(xh, tab[32 + co], tab[48 + co]);
     }
     __syncthreads();
-    for (int i = tid; i < C9 * C9 * FT_C; i += FT_NT) {
+    for (int i = tid; i < C9 * C9 * LB_C; i += FT_NT) {
         const int co = i & 15, p = i >> 4;
         c9[i] = conv16_at(s8, S8, w9, p / C9, p % C9, co);
     }
     __syncthreads();
-    for (int i = tid; i < S9 * S9 * FT_C; i += FT_NT) {
+    for (int i = tid; i < S9 * S9 * LB_C; i += FT_NT) {
         const int co = i & 15, p = i >> 4, y = p / S9, x = p % S9;
-        float t = 0.f;
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) t += relu6f(c9[((2 * y + ky) * C9 + 2 * x + kx) * FT_C + co]);
+        const float t = pool_relu6_sum(c9, C9, y, x, co);
         const float xh = (t * (1.0f / 16.0f) - tab[64 + co]) * tab[80 + co];
         const float bv = fmaf(xh, tab[96 + co], tab[112 + co]);
-        const int ylo = a.rlo[y], yhi = a.rhi[y], xlo = a.rlo[x], xhi = a.rhi[x];
-        const float yl = a.rlerp[y], xl = a.rlerp[x];
-        const float tl = x7[(ylo * S7 + xlo) * FT_C + co], tr = x7[(ylo * S7 + xhi) * FT_C + co];
-        const float bl = x7[(yhi * S7 + xlo) * FT_C + co], br = x7[(yhi * S7 + xhi) * FT_C + co];
-        const float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
-        const float xhb = ((bv + (top + (bot - top) * yl)) - tab[128 + co]) * tab[144 + co];
+        const float xhb = ((bv + skip_resize_at(x7, S7, a.rs, y, x, co)) - tab[128 + co]) * tab[144 + co];
         if (TRAIN) {
             xh9[i] = xh;
             xh9b[i] = xhb;
@@ -285,21 +235,10 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
     }
     __syncthreads();
     // ---- dense head forward: each layer's dot products split over FT_NT / 64 groups of k, summed in a fixed order
-    constexpr int NG = FT_NT / FT_HMAX;
     for (int d = 0; d < a.n_dense; ++d) {
-        const int nin = a.nin[d], nout = a.nout[d];
-        const float* xin = d == 0 ? fl : hx[d];
-        const float* W = P + a.o_dw[d];
-        const int j = tid % FT_HMAX, gi = tid / FT_HMAX;
-        const int per = (nin + NG - 1) / NG;
-        float v = 0.f;
-        if (j < nout)
-            for (int k = gi * per; k < min(nin, (gi + 1) * per); ++k) v = fmaf(xin[k], W[k * nout + j], v);
-        red[tid] = v;
-        __syncthreads();
+        const int nout = a.nout[d];
+        float t = dense_splitk<FT_NT>(d == 0 ? fl : hx[d], P + a.o_dw[d], a.nin[d], nout, red, tid);
         if (tid < nout) {
-            float t = 0.f;
-            for (int g = 0; g < NG; ++g) t += red[g * FT_HMAX + tid];
             if (a.o_db[d] >= 0) t += P[a.o_db[d] + tid];
             hmm[d][tid] = t;
             if (d + 1 < a.n_dense) {
@@ -355,8 +294,7 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
             if (tid < nout) prt[a.p_gz[d] + tid] = gz[tid];
             for (int k = tid; k < nin; k += FT_NT) {
                 prt[a.p_x[d] + k] = xin[k];
-                float v = 0.f;
-                for (int j = 0; j < nout; ++j) v = fmaf(W[k * nout + j], gz[j], v);
+                float v = dense_adjoint_at(W, nout, gz, k);
                 if (d == 0) {
                     gfl[k] = v;
                 } else {
@@ -375,8 +313,8 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
             const int c = tid & 15;
             float dg2 = 0.f, db2 = 0.f, dg1 = 0.f, db1 = 0.f;
             const float k2 = tab[160 + c] * tab[144 + c], k1 = tab[96 + c] * tab[80 + c];
-            for (int p = tid >> 4; p < S9 * S9; p += FT_NT / FT_C) {
-                const int i = p * FT_C + c;
+            for (int p = tid >> 4; p < S9 * S9; p += FT_NT / LB_C) {
+                const int i = p * LB_C + c;
                 const float g = gfl[i];
                 dg2 = fmaf(g, xh9b[i], dg2);
                 db2 += g;
@@ -388,23 +326,18 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
             }
             float t;
             t = channel_sum(dg2, red, tid);
-            if (tid < FT_C) prt[a.p_bn9b + tid] = t;
+            if (tid < LB_C) prt[a.p_bn9b + tid] = t;
             t = channel_sum(db2, red, tid);
-            if (tid < FT_C) prt[a.p_bn9b + FT_C + tid] = t;
+            if (tid < LB_C) prt[a.p_bn9b + LB_C + tid] = t;
             t = channel_sum(dg1, red, tid);
-            if (tid < FT_C) prt[a.p_bn9 + tid] = t;
+            if (tid < LB_C) prt[a.p_bn9 + tid] = t;
             t = channel_sum(db1, red, tid);
-            if (tid < FT_C) prt[a.p_bn9 + FT_C + tid] = t;
+            if (tid < LB_C) prt[a.p_bn9 + LB_C + tid] = t;
         }
         // ---- pool 9 adjoint and conv 9's ReLU6 mask, in place over c9: dL/dconv9
-        for (int i = tid; i < C9 * C9 * FT_C; i += FT_NT) {
+        for (int i = tid; i < C9 * C9 * LB_C; i += FT_NT) {
             const int co = i & 15, p = i >> 4, Y = p / C9, X = p % C9;
-            int ylo, yhi, xlo, xhi;
-            pool_span(Y, S9, &ylo, &yhi);
-            pool_span(X, S9, &xlo, &xhi);
-            float t = 0.f;
-            for (int y = ylo; y <= yhi; ++y)
-                for (int x = xlo; x <= xhi; ++x) t += gfl[(y * S9 + x) * FT_C + co];
+            const float t = pool_cover_sum(gfl, S9, Y, X, co);
             c9[i] = relu6_passes(c9[i]) ? t * (1.0f / 16.0f) : 0.f;
         }
         __syncthreads();
@@ -412,19 +345,9 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
         wgrad16(s8, S8, c9, C9, prt + a.p_w9, red3, tid);
 #endif
         // ---- conv 9 adjoint -> dL/ds8.bn
-        for (int i = tid; i < S8 * S8 * FT_C; i += FT_NT) {
+        for (int i = tid; i < S8 * S8 * LB_C; i += FT_NT) {
             const int ci = i & 15, p = i >> 4, Y = p / S8, X = p % S8;
-            float t = 0.f;
-            for (int ky = 0; ky < 3; ++ky) {
-                const int y = Y - ky;
-                if (y < 0 || y >= C9) continue;
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int x = X - kx;
-                    if (x < 0 || x >= C9) continue;
-                    t = dot16(c9 + (y * C9 + x) * FT_C, w9 + ((ky * 3 + kx) * FT_C + ci) * FT_C, t);
-                }
-            }
-            gs8[i] = t;
+            gs8[i] = conv16_adjoint_at(c9, C9, w9, Y, X, ci);
         }
         __syncthreads();
         // ---- stage 8's BN; gs8 becomes dL/d pool8
@@ -432,8 +355,8 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
             const int c = tid & 15;
             float dg = 0.f, db = 0.f;
             const float k1 = tab[32 + c] * tab[16 + c];
-            for (int p = tid >> 4; p < S8 * S8; p += FT_NT / FT_C) {
-                const int i = p * FT_C + c;
+            for (int p = tid >> 4; p < S8 * S8; p += FT_NT / LB_C) {
+                const int i = p * LB_C + c;
                 const float g = gs8[i];
                 dg = fmaf(g, xh8[i], dg);
                 db += g;
@@ -441,18 +364,13 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
             }
             float t;
             t = channel_sum(dg, red, tid);
-            if (tid < FT_C) prt[a.p_bn8 + tid] = t;
+            if (tid < LB_C) prt[a.p_bn8 + tid] = t;
             t = channel_sum(db, red, tid);
-            if (tid < FT_C) prt[a.p_bn8 + FT_C + tid] = t;
+            if (tid < LB_C) prt[a.p_bn8 + LB_C + tid] = t;
         }
-        for (int i = tid; i < C8 * C8 * FT_C; i += FT_NT) {
+        for (int i = tid; i < C8 * C8 * LB_C; i += FT_NT) {
             const int co = i & 15, p = i >> 4, Y = p / C8, X = p % C8;
-            int ylo, yhi, xlo, xhi;
-            pool_span(Y, S8, &ylo, &yhi);
-            pool_span(X, S8, &xlo, &xhi);
-            float t = 0.f;
-            for (int y = ylo; y <= yhi; ++y)
-                for (int x = xlo; x <= xhi; ++x) t += gs8[(y * S8 + x) * FT_C + co];
+            const float t = pool_cover_sum(gs8, S8, Y, X, co);
             c8[i] = relu6_passes(c8[i]) ? t * (1.0f / 16.0f) : 0.f;
         }
         __syncthreads();
@@ -460,48 +378,25 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const Args a) {
         wgrad16(x7, S7, c8, C8, prt + a.p_w8, red3, tid);
 #endif
         if constexpr (D3) {
-            // ---- g7 = conv 8 adjoint + transpose of the skip resize (weights (1-yl)(1-xl), (1-yl)xl, yl(1-xl), yl xl); stage 7's BN
+            // ---- g7 = conv 8 adjoint + transpose of the skip resize; stage 7's BN
             const float* gadd = wsi + a.off_gadd;
-            const float* xh7 = a.xh7 + static_cast<int64_t>(b) * S7 * S7 * FT_C;
-            float* dp7 = a.dpool7 + static_cast<int64_t>(b) * S7 * S7 * FT_C;
+            const float* xh7 = a.xh7 + static_cast<int64_t>(b) * S7 * S7 * LB_C;
+            float* dp7 = a.dpool7 + static_cast<int64_t>(b) * S7 * S7 * LB_C;
             const int ci = tid & 15;
-            const float k1 = P[a.o_g7 + ci] * F[a.f_bn7 + FT_C + ci];
+            const float k1 = P[a.o_g7 + ci] * F[a.f_bn7 + LB_C + ci];
             float dg = 0.f, db = 0.f;
-            for (int p = tid >> 4; p < S7 * S7; p += FT_NT / FT_C) {
-                const int i = p * FT_C + ci, Y = p / S7, X = p % S7;
-                float t = 0.f;
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int y = Y - ky;
-                    if (y < 0 || y >= C8) continue;
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const int x = X - kx;
-                        if (x < 0 || x >= C8) continue;
-                        t = dot16(c8 + (y * C8 + x) * FT_C, w8 + ((ky * 3 + kx) * FT_C + ci) * FT_C, t);
-                    }
-                }
-                float r = 0.f;
-                for (int y = 0; y < S9; ++y) {
-                    const float yl = a.rlerp[y];
-                    const float wy = (a.rlo[y] == Y ? 1.f - yl : 0.f) + (a.rhi[y] == Y ? yl : 0.f);
-                    if (wy == 0.f) continue;
-                    float rx = 0.f;
-                    for (int x = 0; x < S9; ++x) {
-                        const float xl = a.rlerp[x];
-                        const float wx = (a.rlo[x] == X ? 1.f - xl : 0.f) + (a.rhi[x] == X ? xl : 0.f);
-                        if (wx != 0.f) rx = fmaf(wx, gadd[(y * S9 + x) * FT_C + ci], rx);
-                    }
-                    r = fmaf(wy, rx, r);
-                }
-                const float g = t + r;
+            for (int p = tid >> 4; p < S7 * S7; p += FT_NT / LB_C) {
+                const int i = p * LB_C + ci, Y = p / S7, X = p % S7;
+                const float g = conv16_adjoint_at(c8, C8, w8, Y, X, ci) + skip_resize_adjoint_at(gadd, S9, a.rs, Y, X, ci);
                 dg = fmaf(g, xh7[i], dg);
                 db += g;
                 dp7[i] = g * k1;
             }
             float t;
             t = channel_sum(dg, red, tid);
-            if (tid < FT_C) prt[a.p_bn7 + tid] = t;
+            if (tid < LB_C) prt[a.p_bn7 + tid] = t;
             t = channel_sum(db, red, tid);
-            if (tid < FT_C) prt[a.p_bn7 + FT_C + tid] = t;
+            if (tid < LB_C) prt[a.p_bn7 + LB_C + tid] = t;
         }
         // ---- sum v^2 over the parameter slab (its padding is zero), for the loss's L2 term
         if (b == 0 && a.l2sum) {
@@ -523,7 +418,7 @@ enum { FT_SUM = 0, FT_OUTER = 1, FT_BANDS = 2 };
 struct FtVarDev {
     int off, count;                  // in the parameter slab
     int kind;
-    int src;                         // FT_SUM: offset in the partials record;  FT_OUTER: the layer's input vector
+    int src;                         // FT_SUM: offset in the partials record;  FT_OUTER: the layer's input vector;  FT_BANDS: unused
     int src_g, nout;                 // FT_OUTER: the layer's dL/dz vector and its length
 };
 
@@ -538,18 +433,14 @@ struct FtUpdateArgs {
     const double* item_loss;
     const double* l2sum;
     float* loss_out;                 // this step's slot
-};
-
-// depth 3: conv 7's kernel (its partials: one per (item, band), rn_finetune7.hip), gamma7 and beta7 (FT_SUM over the items' records)
-struct FtUpdateArgs7 : FtUpdateArgs {
-    FtVarDev v7[3];
+    // depth 3: conv 7's kernel is FT_BANDS, its partials one per (item, band) (rn_finetune7.hip)
     const float* part7;              // [n, bands, FT7_W]
     int bands;
 };
 
-template <typename Args>
-__global__ __launch_bounds__(256) void ft_update_kernel(const Args a) {
-    constexpr bool D3 = std::is_same_v<Args, FtUpdateArgs7>;
+// (templated on the depth so that the depth-2 instantiation carries no float64 band sum)
+template <bool D3>
+__global__ __launch_bounds__(256) void ft_update_kernel(const FtUpdateArgs a) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e == 0) {
         double s = 0.0;
@@ -560,17 +451,8 @@ __global__ __launch_bounds__(256) void ft_update_kernel(const Args a) {
     int vi = -1;
     for (int i = 0; i < a.nvars; ++i)
         if (e >= a.v[i].off && e < a.v[i].off + a.v[i].count) vi = i;
-    FtVarDev var;
-    if constexpr (D3) {
-        int v7 = -1;
-        for (int i = 0; i < 3; ++i)
-            if (e >= a.v7[i].off && e < a.v7[i].off + a.v7[i].count) v7 = i;
-        if (vi < 0 && v7 < 0) return;
-        var = v7 >= 0 ? a.v7[v7] : a.v[vi];
-    } else {
-        if (vi < 0) return;            // padding between two variables
-        var = a.v[vi];
-    }
+    if (vi < 0) return;                // padding between two variables
+    const FtVarDev var = a.v[vi];
     const int le = e - var.off;
     float s = 0.f;
     if (D3 && var.kind == FT_BANDS) {
@@ -616,15 +498,12 @@ struct rn_ft {
     int depth = 2;                                 // trained conv stages: 2 (feature s7.bn) or 3 (feature s6.bn)
     rn_ft_config cfg{};
     hipStream_t stream = nullptr;
-    int S6 = 0, C7 = 0, S7 = 0, C8 = 0, S8 = 0, C9 = 0, S9 = 0;
+    rn_lastblock sd{};                             // the block's sides
     std::vector<FtVarHost> vars;
     int n_param = 0;                               // floats of the parameter slab (every variable padded to 4 floats)
     FtItemArgs item{};                             // everything but the per-call fields
     FtUpdateArgs upd{};
-    // depth 3 (the base parts of item7 / upd7 are copied from item / upd at every call)
-    FtItemArgs7 item7{};
-    FtUpdateArgs7 upd7{};
-    Ft7Args s7{};
+    Ft7Args s7{};                                  // depth 3
     float *d_P = nullptr, *d_G = nullptr, *d_M = nullptr, *d_V = nullptr, *d_F = nullptr, *d_rlerp = nullptr;
     int32_t* d_rtab = nullptr;
     float *d_ws = nullptr, *d_part = nullptr;
@@ -652,26 +531,11 @@ int ft_zeroed(rn_ft* ft, size_t count, T** out) {
     return rn_owned_zeroed(ft->allocs, 4, count, out);
 }
 
-int ft_build(rn_ft* ft, const rn_weights* w) {
-    const int ns = w->n_stages;
-    const rn_conv_stage &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
-    {
-        std::vector<int> conv, out;
-        if (rn_stage_sides(w, conv, out) < ns) {
-            rn_set_error("rn_ft_create: im_side %d is too small for the graph", w->im_side);
-            return RN_E_INVALID;
-        }
-        ft->S6 = out[ns - 4];
-        ft->C7 = conv[ns - 3];
-        ft->S7 = out[ns - 3];
-        ft->C8 = conv[ns - 2];
-        ft->S8 = out[ns - 2];
-        ft->C9 = conv[ns - 1];
-        ft->S9 = out[ns - 1];
-    }
-    if (w->dense[0].nin != ft->S9 * ft->S9 * FT_C) {
+// the dense head must continue the last block and end in the classes
+int ft_check_head(const rn_ft* ft, const rn_weights* w) {
+    if (w->dense[0].nin != ft->sd.S9 * ft->sd.S9 * LB_C) {
         rn_set_error("rn_ft_create: the first dense layer takes %d inputs, the last block delivers %d", w->dense[0].nin,
-                     ft->S9 * ft->S9 * FT_C);
+                     ft->sd.S9 * ft->sd.S9 * LB_C);
         return RN_E_INVALID;
     }
     for (int d = 1; d < w->n_dense; ++d)
@@ -684,10 +548,23 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
         rn_set_error("rn_ft_create: the last dense layer has %d outputs for %d classes", w->dense[w->n_dense - 1].nout, w->num_classes);
         return RN_E_INVALID;
     }
+    return RN_OK;
+}
+
+// The trained variables in checkpoint order (ft->vars, the parameter slab P, the frozen BN moments F), one item's partials record
+// and how the update kernel forms each variable's gradient from it (ft->upd.v); the offsets go into ft->item and ft->s7.
+void ft_build_vars(rn_ft* ft, const rn_weights* w, std::vector<float>& P, std::vector<float>& F) {
+    const int ns = w->n_stages;
     const float eps = w->bn_epsilon;
-    std::vector<float> P, F;
-    auto suffix = [](const char* base, int i) { return i == 0 ? std::string(base) : std::string(base) + "_" + std::to_string(i); };
-    auto put_var = [&](const std::string& name, const float* src, int cnt) {
+    FtItemArgs& a = ft->item;
+    FtUpdateArgs& u = ft->upd;
+    int rec = 0;
+    auto take = [&](int cnt) {                     // a piece of the partials record
+        const int off = rec;
+        rec += (cnt + 3) & ~3;
+        return off;
+    };
+    auto put_var = [&](const std::string& name, const float* src, int cnt, int kind, int src_off, int src_g = 0, int nout = 0) {
         FtVarHost v;
         v.name = name;
         v.off = static_cast<int>(P.size());
@@ -695,6 +572,7 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
         P.insert(P.end(), src, src + cnt);
         P.resize((P.size() + 3) & ~static_cast<size_t>(3));
         ft->vars.push_back(v);
+        u.v[u.nvars++] = FtVarDev{v.off, cnt, kind, src_off, src_g, nout};
         return v.off;
     };
     auto put_frozen = [&](const float* mean, const float* var, int cnt) {
@@ -705,77 +583,38 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
         return off;
     };
     // TensorFlow numbers its variables by creation: conv stage i is conv2d_i; BNs count every stage's and every residual add's
-    const bool d3 = ft->depth == 3;
+    auto suffix = [](const char* base, int i) { return i == 0 ? std::string(base) : std::string(base) + "_" + std::to_string(i); };
+    const int first = ns - ft->depth;              // the first trained stage
     int bn_index = 0;
-    for (int i = 0; i < ns - (d3 ? 3 : 2); ++i) bn_index += w->stages[i].gamma2 ? 2 : 1;
-    FtItemArgs& a = ft->item;
-    FtUpdateArgs& u = ft->upd;
-    if (d3) {
-        if (const char* why = rn_ft7_geometry_reason(ft->S6, ft->C7, ft->S7)) {
-            rn_set_error("rn_ft_create_depth: not supported on this graph (%s)", why);
-            return RN_E_INVALID;
-        }
-        // conv 7's kernel, its BN's gamma and beta: in front of the others, as the checkpoint orders them
-        const rn_conv_stage& st7 = w->stages[ns - 3];
-        Ft7Args& s = ft->s7;
-        FtUpdateArgs7& u7 = ft->upd7;
-        s.o_w7 = put_var(suffix("conv2d", ns - 3) + "/kernel", st7.kernel, FT7_W);
-        s.o_g7 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st7.gamma, FT_C);
-        s.o_b7 = put_var(suffix("batch_normalization", bn_index) + "/beta", st7.beta, FT_C);
-        s.f_bn7 = put_frozen(st7.mean, st7.variance, FT_C);
-        ++bn_index;
-        u7.v7[0] = FtVarDev{s.o_w7, FT7_W, FT_BANDS, 0, 0, 0};
-        u7.v7[1] = FtVarDev{s.o_g7, FT_C, FT_SUM, 0, 0, 0};             // (src: the record's p_bn7, taken below)
-        u7.v7[2] = FtVarDev{s.o_b7, FT_C, FT_SUM, 0, 0, 0};
-    }
-    // the partials record of one item
-    int rec = 0;
-    auto take = [&](int cnt) {
-        const int off = rec;
-        rec += (cnt + 3) & ~3;
-        return off;
-    };
-    auto add_upd = [&](int off, int count, int kind, int src, int src_g, int nout) {
-        FtVarDev& v = u.v[u.nvars++];
-        v.off = off;
-        v.count = count;
-        v.kind = kind;
-        v.src = src;
-        v.src_g = src_g;
-        v.nout = nout;
+    for (int i = 0; i < first; ++i) bn_index += w->stages[i].gamma2 ? 2 : 1;
+    // a BN's gamma and beta, their partials [d gamma | d beta] at p_bn, its frozen moments
+    auto put_bn = [&](const float* gamma, const float* beta, const float* mean, const float* var, int p_bn, int* o_g, int* o_b, int* f_bn) {
+        const std::string name = suffix("batch_normalization", bn_index++);
+        *o_g = put_var(name + "/gamma", gamma, LB_C, FT_SUM, p_bn);
+        *o_b = put_var(name + "/beta", beta, LB_C, FT_SUM, p_bn + LB_C);
+        *f_bn = put_frozen(mean, var, LB_C);
     };
     a.p_w8 = take(FT_W);
     a.p_w9 = take(FT_W);
-    a.p_bn8 = take(2 * FT_C);
-    a.p_bn9 = take(2 * FT_C);
-    a.p_bn9b = take(2 * FT_C);
-    if (d3) {
-        ft->item7.p_bn7 = take(2 * FT_C);
-        ft->upd7.v7[1].src = ft->item7.p_bn7;
-        ft->upd7.v7[2].src = ft->item7.p_bn7 + FT_C;
+    a.p_bn8 = take(2 * LB_C);
+    a.p_bn9 = take(2 * LB_C);
+    a.p_bn9b = take(2 * LB_C);
+    if (ft->depth == 3) {
+        // conv 7's kernel, its BN's gamma and beta: in front of the others, as the checkpoint orders them
+        const rn_conv_stage& st7 = w->stages[ns - 3];
+        Ft7Args& s = ft->s7;
+        a.p_bn7 = take(2 * LB_C);
+        s.o_w7 = put_var(suffix("conv2d", ns - 3) + "/kernel", st7.kernel, FT7_W, FT_BANDS, 0);
+        put_bn(st7.gamma, st7.beta, st7.mean, st7.variance, a.p_bn7, &s.o_g7, &s.o_b7, &s.f_bn7);
+        a.o_g7 = s.o_g7;
+        a.f_bn7 = s.f_bn7;
     }
-    a.o_w8 = put_var(suffix("conv2d", ns - 2) + "/kernel", st8.kernel, FT_W);
-    add_upd(a.o_w8, FT_W, FT_SUM, a.p_w8, 0, 0);
-    a.o_g8 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st8.gamma, FT_C);
-    add_upd(a.o_g8, FT_C, FT_SUM, a.p_bn8, 0, 0);
-    a.o_b8 = put_var(suffix("batch_normalization", bn_index) + "/beta", st8.beta, FT_C);
-    add_upd(a.o_b8, FT_C, FT_SUM, a.p_bn8 + FT_C, 0, 0);
-    a.f_bn8 = put_frozen(st8.mean, st8.variance, FT_C);
-    ++bn_index;
-    a.o_w9 = put_var(suffix("conv2d", ns - 1) + "/kernel", st9.kernel, FT_W);
-    add_upd(a.o_w9, FT_W, FT_SUM, a.p_w9, 0, 0);
-    a.o_g9 = put_var(suffix("batch_normalization", bn_index) + "/gamma", st9.gamma, FT_C);
-    add_upd(a.o_g9, FT_C, FT_SUM, a.p_bn9, 0, 0);
-    a.o_b9 = put_var(suffix("batch_normalization", bn_index) + "/beta", st9.beta, FT_C);
-    add_upd(a.o_b9, FT_C, FT_SUM, a.p_bn9 + FT_C, 0, 0);
-    a.f_bn9 = put_frozen(st9.mean, st9.variance, FT_C);
-    ++bn_index;
-    a.o_g9b = put_var(suffix("batch_normalization", bn_index) + "/gamma", st9.gamma2, FT_C);
-    add_upd(a.o_g9b, FT_C, FT_SUM, a.p_bn9b, 0, 0);
-    a.o_b9b = put_var(suffix("batch_normalization", bn_index) + "/beta", st9.beta2, FT_C);
-    add_upd(a.o_b9b, FT_C, FT_SUM, a.p_bn9b + FT_C, 0, 0);
-    a.f_bn9b = put_frozen(st9.mean2, st9.variance2, FT_C);
-    ++bn_index;
+    const rn_conv_stage &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
+    a.o_w8 = put_var(suffix("conv2d", ns - 2) + "/kernel", st8.kernel, FT_W, FT_SUM, a.p_w8);
+    put_bn(st8.gamma, st8.beta, st8.mean, st8.variance, a.p_bn8, &a.o_g8, &a.o_b8, &a.f_bn8);
+    a.o_w9 = put_var(suffix("conv2d", ns - 1) + "/kernel", st9.kernel, FT_W, FT_SUM, a.p_w9);
+    put_bn(st9.gamma, st9.beta, st9.mean, st9.variance, a.p_bn9, &a.o_g9, &a.o_b9, &a.f_bn9);
+    put_bn(st9.gamma2, st9.beta2, st9.mean2, st9.variance2, a.p_bn9b, &a.o_g9b, &a.o_b9b, &a.f_bn9b);
     a.n_dense = w->n_dense;
     a.nc = w->num_classes;
     for (int d = 0; d < w->n_dense; ++d) {
@@ -785,135 +624,132 @@ int ft_build(rn_ft* ft, const rn_weights* w) {
         a.p_x[d] = take(l.nin);
         a.p_gz[d] = take(l.nout);
         a.o_db[d] = a.o_dg[d] = a.o_dbeta[d] = a.f_dbn[d] = a.p_dg[d] = a.p_dbeta[d] = -1;
-        a.o_dw[d] = put_var(suffix("dense", d) + "/kernel", l.kernel, l.nin * l.nout);
-        add_upd(a.o_dw[d], l.nin * l.nout, FT_OUTER, a.p_x[d], a.p_gz[d], l.nout);
-        if (l.bias) {
-            a.o_db[d] = put_var(suffix("dense", d) + "/bias", l.bias, l.nout);
-            add_upd(a.o_db[d], l.nout, FT_SUM, a.p_gz[d], 0, 0);
-        }
+        a.o_dw[d] = put_var(suffix("dense", d) + "/kernel", l.kernel, l.nin * l.nout, FT_OUTER, a.p_x[d], a.p_gz[d], l.nout);
+        if (l.bias) a.o_db[d] = put_var(suffix("dense", d) + "/bias", l.bias, l.nout, FT_SUM, a.p_gz[d]);
         if (l.gamma) {
             a.p_dg[d] = take(l.nout);
             a.p_dbeta[d] = take(l.nout);
-            a.o_dg[d] = put_var(suffix("batch_normalization", bn_index) + "/gamma", l.gamma, l.nout);
-            add_upd(a.o_dg[d], l.nout, FT_SUM, a.p_dg[d], 0, 0);
-            a.o_dbeta[d] = put_var(suffix("batch_normalization", bn_index) + "/beta", l.beta, l.nout);
-            add_upd(a.o_dbeta[d], l.nout, FT_SUM, a.p_dbeta[d], 0, 0);
+            const std::string name = suffix("batch_normalization", bn_index++);
+            a.o_dg[d] = put_var(name + "/gamma", l.gamma, l.nout, FT_SUM, a.p_dg[d]);
+            a.o_dbeta[d] = put_var(name + "/beta", l.beta, l.nout, FT_SUM, a.p_dbeta[d]);
             a.f_dbn[d] = put_frozen(l.mean, l.variance, l.nout);
-            ++bn_index;
         }
     }
-    ft->n_param = static_cast<int>(P.size());
-    a.rec = rec;
-    // legacy bilinear tables S7 -> S9: [lo | hi], lerp
-    std::vector<int32_t> rt(2 * static_cast<size_t>(ft->S9));
-    std::vector<float> lerp(ft->S9);
-    rn_legacy_resize_table(ft->S7, ft->S9, rt.data(), rt.data() + ft->S9, lerp.data());
+    ft->n_param = a.n_param = u.total = static_cast<int>(P.size());
+    a.rec = u.rec = rec;
+}
+
+// the item kernel's per-workgroup workspace (every piece a multiple of 16 floats), the partials records and the loss / eval staging
+int ft_build_workspace(rn_ft* ft) {
+    FtItemArgs& a = ft->item;
+    const rn_lastblock& sd = ft->sd;
+    const int64_t n8 = static_cast<int64_t>(sd.S8) * sd.S8 * LB_C, n9 = static_cast<int64_t>(sd.S9) * sd.S9 * LB_C;
+    a.off_c8 = 0;
+    a.off_xh8 = a.off_c8 + static_cast<int64_t>(sd.C8) * sd.C8 * LB_C;
+    a.off_s8 = a.off_xh8 + n8;
+    a.off_gs8 = a.off_s8 + n8;
+    a.off_c9 = a.off_gs8 + n8;
+    a.off_xh9 = a.off_c9 + static_cast<int64_t>(sd.C9) * sd.C9 * LB_C;
+    a.off_xh9b = a.off_xh9 + n9;
+    a.off_fl = a.off_xh9b + n9;
+    a.off_gfl = a.off_fl + n9;
+    a.ws_item = a.off_gfl + n9;
+    if (ft->depth == 3) {
+        a.off_gadd = a.ws_item;
+        a.ws_item += n9;
+    }
     int rc;
-    const size_t np = static_cast<size_t>(ft->n_param), nb = static_cast<size_t>(ft->max_batch);
+    const size_t nb = static_cast<size_t>(ft->max_batch);
+    if ((rc = ft_zeroed(ft, nb * a.ws_item, &ft->d_ws)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * static_cast<size_t>(a.rec), &ft->d_part)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb, &ft->d_item_loss)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, 1, &ft->d_l2sum)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * ft->nc, &ft->d_probs)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb, &ft->d_ids)) != RN_OK) return rc;
+    return RN_OK;
+}
+
+// depth 3: stage 7's per-step workspace, and one weight-gradient partial per (item, band) for the batch size that needs the most
+int ft_build_depth3(rn_ft* ft) {
+    Ft7Args& s = ft->s7;
+    const rn_lastblock& sd = ft->sd;
+    const size_t nb = static_cast<size_t>(ft->max_batch), n7 = static_cast<size_t>(sd.S7) * sd.S7 * LB_C;
+    size_t nparts = 0;
+    for (int b = 1; b <= ft->max_batch; ++b) {
+        int bf, rf, bb, rb;
+        rn_ft7_bands(b, sd.C7, sd.S7, &bf, &rf, &bb, &rb);
+        nparts = std::max(nparts, static_cast<size_t>(b) * bb);
+    }
+    int rc;
+    float* d_x7 = nullptr;
+    if ((rc = ft_zeroed(ft, nb * sd.C7 * sd.C7 * LB_C, &s.pre)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * n7, &s.xh7)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * n7, &d_x7)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nb * n7, &ft->item.dpool7)) != RN_OK) return rc;
+    if ((rc = ft_zeroed(ft, nparts * FT7_W, &s.part)) != RN_OK) return rc;
+    s.S6 = sd.S6;
+    s.C7 = sd.C7;
+    s.S7 = sd.S7;
+    s.P = ft->d_P;
+    s.F = ft->d_F;
+    s.x7 = d_x7;
+    s.dpool = ft->item.dpool7;
+    ft->item.x7ws = d_x7;
+    ft->item.xh7 = s.xh7;
+    ft->upd.part7 = s.part;
+    return RN_OK;
+}
+
+int ft_build(rn_ft* ft, const rn_weights* w) {
+    if (rn_lastblock_sides(w, &ft->sd) < w->n_stages) {
+        rn_set_error("rn_ft_create: im_side %d is too small for the graph", w->im_side);
+        return RN_E_INVALID;
+    }
+    int rc;
+    if ((rc = ft_check_head(ft, w)) != RN_OK) return rc;
+    if (ft->depth == 3)
+        if (const char* why = rn_ft7_geometry_reason(ft->sd.S6, ft->sd.C7, ft->sd.S7)) {
+            rn_set_error("rn_ft_create_depth: not supported on this graph (%s)", why);
+            return RN_E_INVALID;
+        }
+    std::vector<float> P, F, lerp;
+    std::vector<int32_t> rtab;
+    ft_build_vars(ft, w, P, F);
+    rn_lastblock_resize_tables(ft->sd, rtab, lerp);
+    const size_t np = P.size();
     if ((rc = ft_upload(ft, P.data(), np, &ft->d_P)) != RN_OK) return rc;
     if ((rc = ft_zeroed(ft, np, &ft->d_G)) != RN_OK) return rc;
     if ((rc = ft_zeroed(ft, np, &ft->d_M)) != RN_OK) return rc;
     if ((rc = ft_zeroed(ft, np, &ft->d_V)) != RN_OK) return rc;
     if ((rc = ft_upload(ft, F.data(), F.size(), &ft->d_F)) != RN_OK) return rc;
-    if ((rc = ft_upload(ft, rt.data(), rt.size(), &ft->d_rtab)) != RN_OK) return rc;
+    if ((rc = ft_upload(ft, rtab.data(), rtab.size(), &ft->d_rtab)) != RN_OK) return rc;
     if ((rc = ft_upload(ft, lerp.data(), lerp.size(), &ft->d_rlerp)) != RN_OK) return rc;
-    // per-workgroup workspace, every piece a multiple of 16 floats
-    const int64_t n8 = static_cast<int64_t>(ft->S8) * ft->S8 * FT_C, n9 = static_cast<int64_t>(ft->S9) * ft->S9 * FT_C;
-    a.off_c8 = 0;
-    a.off_xh8 = a.off_c8 + static_cast<int64_t>(ft->C8) * ft->C8 * FT_C;
-    a.off_s8 = a.off_xh8 + n8;
-    a.off_gs8 = a.off_s8 + n8;
-    a.off_c9 = a.off_gs8 + n8;
-    a.off_xh9 = a.off_c9 + static_cast<int64_t>(ft->C9) * ft->C9 * FT_C;
-    a.off_xh9b = a.off_xh9 + n9;
-    a.off_fl = a.off_xh9b + n9;
-    a.off_gfl = a.off_fl + n9;
-    a.ws_item = a.off_gfl + n9;
-    if (d3) {
-        ft->item7.off_gadd = a.ws_item;
-        a.ws_item += n9;
-    }
-    if ((rc = ft_zeroed(ft, nb * a.ws_item, &ft->d_ws)) != RN_OK) return rc;
-    if ((rc = ft_zeroed(ft, nb * static_cast<size_t>(rec), &ft->d_part)) != RN_OK) return rc;
-    if ((rc = ft_zeroed(ft, nb, &ft->d_item_loss)) != RN_OK) return rc;
-    if ((rc = ft_zeroed(ft, 1, &ft->d_l2sum)) != RN_OK) return rc;
-    if ((rc = ft_zeroed(ft, nb * w->num_classes, &ft->d_probs)) != RN_OK) return rc;
-    if ((rc = ft_zeroed(ft, nb, &ft->d_ids)) != RN_OK) return rc;
-    a.S7 = ft->S7;
-    a.C8 = ft->C8;
-    a.S8 = ft->S8;
-    a.C9 = ft->C9;
-    a.S9 = ft->S9;
+    if ((rc = ft_build_workspace(ft)) != RN_OK) return rc;
+    FtItemArgs& a = ft->item;
+    a.S7 = ft->sd.S7;
+    a.C8 = ft->sd.C8;
+    a.S8 = ft->sd.S8;
+    a.C9 = ft->sd.C9;
+    a.S9 = ft->sd.S9;
     a.P = ft->d_P;
     a.F = ft->d_F;
-    a.rlo = ft->d_rtab;
-    a.rhi = ft->d_rtab + ft->S9;
-    a.rlerp = ft->d_rlerp;
+    a.rs = LbResize{ft->d_rtab, ft->d_rtab + ft->sd.S9, ft->d_rlerp};
     a.ws = ft->d_ws;
     a.part = ft->d_part;
     a.item_loss = ft->d_item_loss;
-    a.n_param = ft->n_param;
-    u.total = ft->n_param;
+    FtUpdateArgs& u = ft->upd;
     u.P = ft->d_P;
     u.G = ft->d_G;
     u.M = ft->d_M;
     u.V = ft->d_V;
     u.part = ft->d_part;
-    u.rec = rec;
     u.l2 = ft->cfg.l2_coeff;
     u.omb1 = static_cast<float>(1.0 - static_cast<double>(ft->cfg.beta1));
     u.omb2 = static_cast<float>(1.0 - static_cast<double>(ft->cfg.beta2));
     u.eps = ft->cfg.epsilon;
     u.item_loss = ft->d_item_loss;
     u.l2sum = ft->d_l2sum;
-    if (d3) {
-        // stage 7's per-step workspace, and one weight-gradient partial per (item, band) for the batch size that needs the most
-        Ft7Args& s = ft->s7;
-        const size_t n7 = static_cast<size_t>(ft->S7) * ft->S7 * FT_C;
-        size_t nparts = 0;
-        for (int b = 1; b <= ft->max_batch; ++b) {
-            int bf, rf, bb, rb;
-            rn_ft7_bands(b, ft->C7, ft->S7, &bf, &rf, &bb, &rb);
-            nparts = std::max(nparts, static_cast<size_t>(b) * bb);
-        }
-        float *d_pre = nullptr, *d_xh7 = nullptr, *d_x7 = nullptr, *d_dp7 = nullptr, *d_part7 = nullptr;
-        if ((rc = ft_zeroed(ft, nb * ft->C7 * ft->C7 * FT_C, &d_pre)) != RN_OK) return rc;
-        if ((rc = ft_zeroed(ft, nb * n7, &d_xh7)) != RN_OK) return rc;
-        if ((rc = ft_zeroed(ft, nb * n7, &d_x7)) != RN_OK) return rc;
-        if ((rc = ft_zeroed(ft, nb * n7, &d_dp7)) != RN_OK) return rc;
-        if ((rc = ft_zeroed(ft, nparts * FT7_W, &d_part7)) != RN_OK) return rc;
-        s.S6 = ft->S6;
-        s.C7 = ft->C7;
-        s.S7 = ft->S7;
-        s.P = ft->d_P;
-        s.F = ft->d_F;
-        s.pre = d_pre;
-        s.xh7 = d_xh7;
-        s.x7 = d_x7;
-        s.dpool = d_dp7;
-        s.part = d_part7;
-        ft->item7.x7ws = d_x7;
-        ft->item7.xh7 = d_xh7;
-        ft->item7.dpool7 = d_dp7;
-        ft->item7.o_g7 = s.o_g7;
-        ft->item7.f_bn7 = s.f_bn7;
-        ft->upd7.part7 = d_part7;
-    }
-    return RN_OK;
-}
-
-// the depth-3 arguments of one call: the trainer's own, over the base this call filled in
-FtItemArgs7 ft_item7(const rn_ft* ft, const FtItemArgs& base) {
-    FtItemArgs7 a = ft->item7;
-    static_cast<FtItemArgs&>(a) = base;
-    return a;
-}
-
-FtUpdateArgs7 ft_upd7(const rn_ft* ft, const FtUpdateArgs& base, int bands) {
-    FtUpdateArgs7 u = ft->upd7;
-    static_cast<FtUpdateArgs&>(u) = base;
-    u.bands = bands;
-    return u;
+    return ft->depth == 3 ? ft_build_depth3(ft) : RN_OK;
 }
 
 double ft_learn_rate(const rn_ft_config& c, int64_t step) {
@@ -1061,7 +897,7 @@ static Ft7Args ft7_call(const rn_ft* ft, const float* feats, const int32_t* inde
     s.feats = feats;
     s.index = index;
     s.base = base;
-    rn_ft7_bands(m, ft->C7, ft->S7, &s.bands_f, &s.rows_f, &s.bands_b, &s.rows_b);
+    rn_ft7_bands(m, ft->sd.C7, ft->sd.S7, &s.bands_f, &s.rows_f, &s.bands_b, &s.rows_b);
     return s;
 }
 
@@ -1131,15 +967,16 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
             int rc;
             const Ft7Args s7 = ft7_call(ft, d_feats, d_index, a.base, batch);
             if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
-            hipLaunchKernelGGL((ft_item_kernel<true, FtItemArgs7>), dim3(batch), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));
+            hipLaunchKernelGGL((ft_item_kernel<true, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
             RN_CHECK_LAUNCH();
             if ((rc = rn_ft7_backward(ft->stream, s7, batch)) != RN_OK) return rc;
-            hipLaunchKernelGGL(ft_update_kernel<FtUpdateArgs7>, dim3(ublocks), dim3(256), 0, ft->stream, ft_upd7(ft, u, s7.bands_b));
+            u.bands = s7.bands_b;
+            hipLaunchKernelGGL(ft_update_kernel<true>, dim3(ublocks), dim3(256), 0, ft->stream, u);
             RN_CHECK_LAUNCH();
         } else {
-            hipLaunchKernelGGL((ft_item_kernel<true, FtItemArgs>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
+            hipLaunchKernelGGL((ft_item_kernel<true, false>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
             RN_CHECK_LAUNCH();
-            hipLaunchKernelGGL(ft_update_kernel<FtUpdateArgs>, dim3(ublocks), dim3(256), 0, ft->stream, u);
+            hipLaunchKernelGGL(ft_update_kernel<false>, dim3(ublocks), dim3(256), 0, ft->stream, u);
             RN_CHECK_LAUNCH();
         }
         ++ft->steps_done;
@@ -1189,9 +1026,9 @@ extern "C" int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labe
             const Ft7Args s7 = ft7_call(ft, d_feats, nullptr, i, m);
             int rc;
             if ((rc = rn_ft7_forward(ft->stream, s7, m)) != RN_OK) return rc;
-            hipLaunchKernelGGL((ft_item_kernel<false, FtItemArgs7>), dim3(m), dim3(FT_NT), 0, ft->stream, ft_item7(ft, a));
+            hipLaunchKernelGGL((ft_item_kernel<false, true>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
         } else {
-            hipLaunchKernelGGL((ft_item_kernel<false, FtItemArgs>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
+            hipLaunchKernelGGL((ft_item_kernel<false, false>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
         }
         RN_CHECK_LAUNCH();
         if (probs) RN_HIP(hipMemcpyAsync(probs + i * ft->nc, ft->d_probs, static_cast<size_t>(m) * ft->nc * 4, hipMemcpyDeviceToHost, ft->stream));

@@ -1,10 +1,9 @@
 // Stage 7 of a depth-3 fine-tuning step (rn_finetune7.hip), as rn_finetune.hip launches it.
 #pragma once
 #include "rn_internal.h"
+#include "rn_lastblock.h"
 
-constexpr int FT7_CIN = 128;                        // channels of s6.bn
-constexpr int FT7_C = 16;                           // channels of the last block
-constexpr int FT7_W = 9 * FT7_CIN * FT7_C;          // floats of conv 7's kernel (and of one weight-gradient partial)
+constexpr int FT7_W = 9 * rnk::LB_CIN7 * rnk::LB_C;   // floats of conv 7's kernel (and of one weight-gradient partial)
 
 struct Ft7Args {
     const float* feats;              // the resident cache [n_items, S6, S6, 128]

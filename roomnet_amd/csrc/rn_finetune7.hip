@@ -26,7 +26,8 @@
 //                   the 16 ci of a fragment are 64 contiguous bytes), B = dconv7[p, co], K runs over 4 consecutive positions of a
 //                   conv row.  Every conv row is summed apart and then joins the band's total (the two-level sum of wgrad16).  One
 //                   partial [9][128][16] per (item, band); ft_update_kernel sums them over bands, then over items, in index order (in float64).
-// No atomics: the same minibatch gives the same bits.
+// No atomics: the same minibatch gives the same bits.  The pool's window sum and its adjoint's sum over the covering windows are the
+// functions of rn_lastblock.h that stages 8 and 9 use; the float64-chained convolution is this file's own.
 #include "rn_finetune7.h"
 #include "rn_stage.h"
 
@@ -40,14 +41,6 @@ constexpr int F7_NT = 512;           // threads of both workgroups: 8 waves
 constexpr int F7_NW = F7_NT / 64;
 constexpr int F7_R = 2;              // conv rows of a forward unit
 
-__device__ __forceinline__ bool relu6_passes(float v) { return v > 0.f && v < 6.f; }
-
-// pooled rows (or columns) whose 4 x 4 / stride-2 window covers conv row Y (lo > hi: none)
-__device__ __forceinline__ void pool_span(int Y, int So, int* lo, int* hi) {
-    *lo = Y < 3 ? 0 : (Y - 2) / 2;
-    *hi = min(So - 1, Y / 2);
-}
-
 __global__ __launch_bounds__(F7_NT) void ft7_fwd_kernel(const Ft7Args a) {
     extern __shared__ __attribute__((aligned(16))) float wl[];        // W7 [9 * 128][16]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -55,8 +48,8 @@ __global__ __launch_bounds__(F7_NT) void ft7_fwd_kernel(const Ft7Args a) {
     const int i16 = lane & 15, kg = lane >> 4, co = lane & 15;
     const int S6 = a.S6, C7 = a.C7, S7 = a.S7;
     const int64_t item = a.index ? static_cast<int64_t>(a.index[a.base + b]) : a.base + b;
-    const float* x6 = a.feats + item * S6 * S6 * FT7_CIN;
-    float* pre = a.pre + static_cast<int64_t>(b) * C7 * C7 * FT7_C;
+    const float* x6 = a.feats + item * S6 * S6 * LB_CIN7;
+    float* pre = a.pre + static_cast<int64_t>(b) * C7 * C7 * LB_C;
     {
         const f32x4* src = reinterpret_cast<const f32x4*>(a.P + a.o_w7);
         for (int i = tid; i < FT7_W / 4; i += F7_NT) reinterpret_cast<f32x4*>(wl)[i] = src[i];
@@ -80,20 +73,20 @@ __global__ __launch_bounds__(F7_NT) void ft7_fwd_kernel(const Ft7Args a) {
         // A conv row's sum runs in the order (ky, kx, ci) whichever unit and band computes it.
 #pragma unroll
         for (int rr = 0; rr < F7_R + 2; ++rr) {
-            const float* prow = x6 + (static_cast<int64_t>(y0 + rr) * S6 + X) * FT7_CIN + 4 * kg;
+            const float* prow = x6 + (static_cast<int64_t>(y0 + rr) * S6 + X) * LB_CIN7 + 4 * kg;
             for (int kx = 0; kx < 3; ++kx) {
-                const float* px = prow + kx * FT7_CIN;
+                const float* px = prow + kx * LB_CIN7;
 #pragma unroll 2
-                for (int c16 = 0; c16 < FT7_CIN / 16; ++c16) {
+                for (int c16 = 0; c16 < LB_CIN7 / 16; ++c16) {
                     const f32x4 v = *reinterpret_cast<const f32x4*>(px + c16 * 16);
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky) {
                         const int yi = rr - ky;
                         if (yi < 0 || yi >= F7_R) continue;
-                        const float* wt = wl + (ky * 3 + kx) * FT7_CIN * FT7_C + (4 * kg + c16 * 16) * FT7_C + co;
+                        const float* wt = wl + (ky * 3 + kx) * LB_CIN7 * LB_C + (4 * kg + c16 * 16) * LB_C + co;
                         f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) t = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], wt[q * FT7_C], t, 0, 0, 0);
+                        for (int q = 0; q < 4; ++q) t = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], wt[q * LB_C], t, 0, 0, 0);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) acc[yi][j] += static_cast<double>(t[j]);
                     }
@@ -106,20 +99,18 @@ __global__ __launch_bounds__(F7_NT) void ft7_fwd_kernel(const Ft7Args a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int x = x0 + 4 * kg + j;
-                if (x < C7) pre[(static_cast<int64_t>(y0 + yi) * C7 + x) * FT7_C + co] = static_cast<float>(acc[yi][j]);
+                if (x < C7) pre[(static_cast<int64_t>(y0 + yi) * C7 + x) * LB_C + co] = static_cast<float>(acc[yi][j]);
             }
     }
     __syncthreads();
     // the band's pooled rows: every conv row they read was written by this workgroup
     const float* F = a.F + a.f_bn7;
-    const int64_t ob = static_cast<int64_t>(b) * S7 * S7 * FT7_C;
-    for (int i = tid; i < (p1 - p0) * S7 * FT7_C; i += F7_NT) {
+    const int64_t ob = static_cast<int64_t>(b) * S7 * S7 * LB_C;
+    for (int i = tid; i < (p1 - p0) * S7 * LB_C; i += F7_NT) {
         const int c = i & 15, p = i >> 4, y = p0 + p / S7, x = p % S7;
-        float t = 0.f;
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) t += relu6f(pre[(static_cast<int64_t>(2 * y + ky) * C7 + 2 * x + kx) * FT7_C + c]);
-        const float xh = (t * (1.0f / 16.0f) - F[c]) * F[FT7_C + c];
-        const int64_t o = ob + (static_cast<int64_t>(y) * S7 + x) * FT7_C + c;
+        const float t = pool_relu6_sum(pre, C7, y, x, c);
+        const float xh = (t * (1.0f / 16.0f) - F[c]) * F[LB_C + c];
+        const int64_t o = ob + (static_cast<int64_t>(y) * S7 + x) * LB_C + c;
         a.xh7[o] = xh;
         a.x7[o] = fmaf(xh, a.P[a.o_g7 + c], a.P[a.o_b7 + c]);
     }
@@ -131,20 +122,15 @@ __global__ __launch_bounds__(F7_NT) void ft7_bwd_kernel(const Ft7Args a) {
     const int kg = lane >> 4, co = lane & 15;
     const int S6 = a.S6, C7 = a.C7, S7 = a.S7;
     const int64_t item = a.index ? static_cast<int64_t>(a.index[a.base + b]) : a.base + b;
-    const float* x6 = a.feats + item * S6 * S6 * FT7_CIN;
-    float* dc = a.pre + static_cast<int64_t>(b) * C7 * C7 * FT7_C;
-    const float* dp = a.dpool + static_cast<int64_t>(b) * S7 * S7 * FT7_C;
+    const float* x6 = a.feats + item * S6 * S6 * LB_CIN7;
+    float* dc = a.pre + static_cast<int64_t>(b) * C7 * C7 * LB_C;
+    const float* dp = a.dpool + static_cast<int64_t>(b) * S7 * S7 * LB_C;
     const int y0 = band * a.rows_b, y1 = min(C7, y0 + a.rows_b);
     // ---- the pool adjoint and the ReLU6 mask, in place over the band's rows of pre: dL/dconv7
-    for (int i = tid; i < (y1 - y0) * C7 * FT7_C; i += F7_NT) {
+    for (int i = tid; i < (y1 - y0) * C7 * LB_C; i += F7_NT) {
         const int c = i & 15, p = i >> 4, Y = y0 + p / C7, X = p % C7;
-        int ylo, yhi, xlo, xhi;
-        pool_span(Y, S7, &ylo, &yhi);
-        pool_span(X, S7, &xlo, &xhi);
-        float t = 0.f;
-        for (int y = ylo; y <= yhi; ++y)
-            for (int x = xlo; x <= xhi; ++x) t += dp[(y * S7 + x) * FT7_C + c];
-        const int64_t o = (static_cast<int64_t>(Y) * C7 + X) * FT7_C + c;
+        const float t = pool_cover_sum(dp, S7, Y, X, c);
+        const int64_t o = (static_cast<int64_t>(Y) * C7 + X) * LB_C + c;
         dc[o] = relu6_passes(dc[o]) ? t * (1.0f / 16.0f) : 0.f;
     }
     __syncthreads();
@@ -161,12 +147,12 @@ __global__ __launch_bounds__(F7_NT) void ft7_bwd_kernel(const Ft7Args a) {
         for (int x0 = 0; x0 < C7; x0 += 4) {
             const int x = x0 + kg;
             const int xc = min(x, C7 - 1);                             // (a position past the row: B = 0, A read inside the row)
-            const float bv = x < C7 ? dc[(static_cast<int64_t>(Y) * C7 + xc) * FT7_C + co] : 0.f;
+            const float bv = x < C7 ? dc[(static_cast<int64_t>(Y) * C7 + xc) * LB_C + co] : 0.f;
             float av[9];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx) av[ky * 3 + kx] = xa[(static_cast<int64_t>(Y + ky) * S6 + xc + kx) * FT7_CIN];
+                for (int kx = 0; kx < 3; ++kx) av[ky * 3 + kx] = xa[(static_cast<int64_t>(Y + ky) * S6 + xc + kx) * LB_CIN7];
 #pragma unroll
             for (int k = 0; k < 9; ++k) row[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[k], bv, row[k], 0, 0, 0);
         }
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(F7_NT) void ft7_bwd_kernel(const Ft7Args a) {
 #pragma unroll
     for (int k = 0; k < 9; ++k)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) out[(k * FT7_CIN + wave * 16 + 4 * kg + j) * FT7_C + co] = tot[k][j];
+        for (int j = 0; j < 4; ++j) out[(k * LB_CIN7 + wave * 16 + 4 * kg + j) * LB_C + co] = tot[k][j];
 }
 
 }  // namespace

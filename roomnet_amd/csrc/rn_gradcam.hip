@@ -19,8 +19,13 @@
 //   gc_map6_kernel    alpha6[c] = 1/(H6 W6) sum_co (sum_{ky,kx} W7[ky, kx, c, co]) Gamma[co] -- conv 7 is VALID, every tap maps
 //                     the whole output grid one-to-one into its input, so the 46 x 46 x 128 gradient field never exists --
 //                     then one pass over s6.bn for the map.
+// The per-element float32 steps gc_tail_kernel is built from (pool sums, conv adjoint gather, skip resize and its transpose, the head's
+// dot products) are in rn_lastblock.h, shared with the trainers; gc_stage7_kernel's fixed 2 x 2 gather is its own form on purpose.
 #include "rn_internal.h"
+#include "rn_lastblock.h"
 #include "rn_stage.h"
+
+#include <type_traits>
 
 #include <algorithm>
 #include <vector>
@@ -29,10 +34,7 @@ using namespace rnk;
 
 namespace {
 
-constexpr int GC_C = 16;             // channels of the last block (s7 .. s9)
-constexpr int GC_CIN7 = 128;         // channels of s6.bn
 constexpr int GC_NT = 512;           // threads of the tail-adjoint workgroup
-constexpr int GC_HMAX = 64;          // widest dense layer (rn_create enforces nout <= 64)
 constexpr int GC_R7 = 4;             // conv-7 rows per wave of gc_stage7_kernel
 constexpr int GC_G7ROWS = 10;        // pooled rows of g7 one stage-7 workgroup (16 conv rows) reaches
 
@@ -44,9 +46,7 @@ struct GcTailArgs {
     const float* bn8;                // [mean | inv | beta] x 16
     const float* bn9;
     const float* bn9b;               // the residual step's second BN
-    const int32_t* rlo;              // legacy bilinear tables S7 -> S9
-    const int32_t* rhi;
-    const float* rlerp;
+    LbResize rs;                     // legacy bilinear tables S7 -> S9
     int n_dense;
     int nin[RN_MAX_DENSE], nout[RN_MAX_DENSE];
     const float* dw[RN_MAX_DENSE];
@@ -70,51 +70,14 @@ __device__ __forceinline__ float ld_act(const void* p, int64_t i) {
         return from16<DT>(static_cast<const unsigned short*>(p)[i]);
 }
 
-__device__ __forceinline__ bool relu6_passes(float v) { return v > 0.f && v < 6.f; }
-
-// pooled rows (or columns) whose 4 x 4 / stride-2 window covers conv row Y
-__device__ __forceinline__ void pool_span(int Y, int So, int* lo, int* hi) {
-    *lo = Y < 3 ? 0 : (Y - 2) / 2;
-    *hi = min(So - 1, Y / 2);
-}
-
-// conv3x3 VALID 16 -> 16 pre-activation of one output element: in [S][S][16] fp32 (workspace), w [9][16][16] (LDS)
-__device__ __forceinline__ float conv16_at(const float* in, int S, const float* w, int y, int x, int co) {
-    float acc = 0.f;
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) {
-            const f32x4* px = reinterpret_cast<const f32x4*>(in + ((y + ky) * S + x + kx) * GC_C);
-            const float* wt = w + (ky * 3 + kx) * GC_C * GC_C + co;
-#pragma unroll
-            for (int c4 = 0; c4 < GC_C / 4; ++c4) {
-                const f32x4 v = px[c4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc = fmaf(v[q], wt[(4 * c4 + q) * GC_C], acc);
-            }
-        }
-    return acc;
-}
-
-// sum_co g[co] w[co]: g 16 fp32 of the workspace, w 16 of LDS
-__device__ __forceinline__ float dot16(const float* g, const float* w, float t) {
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-#pragma unroll
-    for (int c4 = 0; c4 < GC_C / 4; ++c4) {
-        const f32x4 v = g4[c4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t = fmaf(v[q], w[4 * c4 + q], t);
-    }
-    return t;
-}
-
 template <int DT>
 __global__ __launch_bounds__(GC_NT) void gc_tail_kernel(const GcTailArgs a) {
-    __shared__ float w8[9 * GC_C * GC_C];
-    __shared__ float w9[9 * GC_C * GC_C];
-    __shared__ float tab[9 * GC_C];                       // bn8 | bn9 | bn9b, each [mean | inv | beta]
-    __shared__ float hx[RN_MAX_DENSE][GC_HMAX];           // input of dense layer d (d >= 1)
-    __shared__ float hmm[RN_MAX_DENSE][GC_HMAX];          // pre-activation of dense layer d
-    __shared__ float hg[2][GC_HMAX];
+    __shared__ float w8[9 * LB_C * LB_C];
+    __shared__ float w9[9 * LB_C * LB_C];
+    __shared__ float tab[9 * LB_C];                       // bn8 | bn9 | bn9b, each [mean | inv | beta]
+    __shared__ float hx[RN_MAX_DENSE][LB_HMAX];           // input of dense layer d (d >= 1)
+    __shared__ float hmm[RN_MAX_DENSE][LB_HMAX];          // pre-activation of dense layer d
+    __shared__ float hg[2][LB_HMAX];
     __shared__ float red[GC_NT];
     const int tid = threadIdx.x;
     const int img = blockIdx.x;
@@ -126,66 +89,47 @@ __global__ __launch_bounds__(GC_NT) void gc_tail_kernel(const GcTailArgs a) {
     float* fl = wsi + a.off_fl;
     float* g7 = wsi + a.off_g7;
     float* x7 = wsi + a.off_x7;                           // s7.bn of this image in fp32
-    const int64_t x7b = static_cast<int64_t>(img) * S7 * S7 * GC_C;
-    for (int i = tid; i < S7 * S7 * GC_C; i += GC_NT) x7[i] = ld_act<DT>(a.x7, x7b + i);
-    for (int i = tid; i < 9 * GC_C * GC_C; i += GC_NT) {
+    const int64_t x7b = static_cast<int64_t>(img) * S7 * S7 * LB_C;
+    for (int i = tid; i < S7 * S7 * LB_C; i += GC_NT) x7[i] = ld_act<DT>(a.x7, x7b + i);
+    for (int i = tid; i < 9 * LB_C * LB_C; i += GC_NT) {
         w8[i] = a.w8[i];
         w9[i] = a.w9[i];
     }
-    if (tid < 3 * GC_C) {
+    if (tid < 3 * LB_C) {
         tab[tid] = a.bn8[tid];
         tab[48 + tid] = a.bn9[tid];
         tab[96 + tid] = a.bn9b[tid];
     }
     __syncthreads();
     // ---- forward recompute in fp32 from the stored s7.bn
-    for (int i = tid; i < C8 * C8 * GC_C; i += GC_NT) {
+    for (int i = tid; i < C8 * C8 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4;
         c8[i] = conv16_at(x7, S7, w8, p / C8, p % C8, co);
     }
     __syncthreads();
-    for (int i = tid; i < S8 * S8 * GC_C; i += GC_NT) {
+    for (int i = tid; i < S8 * S8 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4, y = p / S8, x = p % S8;
-        float t = 0.f;
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) t += relu6f(c8[((2 * y + ky) * C8 + 2 * x + kx) * GC_C + co]);
+        const float t = pool_relu6_sum(c8, C8, y, x, co);
         s8[i] = (t * (1.0f / 16.0f) - tab[co]) * tab[16 + co] + tab[32 + co];
     }
     __syncthreads();
-    for (int i = tid; i < C9 * C9 * GC_C; i += GC_NT) {
+    for (int i = tid; i < C9 * C9 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4;
         c9[i] = conv16_at(s8, S8, w9, p / C9, p % C9, co);
     }
     __syncthreads();
-    for (int i = tid; i < S9 * S9 * GC_C; i += GC_NT) {
+    for (int i = tid; i < S9 * S9 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4, y = p / S9, x = p % S9;
-        float t = 0.f;
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) t += relu6f(c9[((2 * y + ky) * C9 + 2 * x + kx) * GC_C + co]);
+        const float t = pool_relu6_sum(c9, C9, y, x, co);
         const float b = (t * (1.0f / 16.0f) - tab[48 + co]) * tab[64 + co] + tab[80 + co];
-        const int ylo = a.rlo[y], yhi = a.rhi[y], xlo = a.rlo[x], xhi = a.rhi[x];
-        const float yl = a.rlerp[y], xl = a.rlerp[x];
-        const float tl = x7[(ylo * S7 + xlo) * GC_C + co], tr = x7[(ylo * S7 + xhi) * GC_C + co];
-        const float bl = x7[(yhi * S7 + xlo) * GC_C + co], br = x7[(yhi * S7 + xhi) * GC_C + co];
-        const float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
-        fl[i] = ((b + (top + (bot - top) * yl)) - tab[96 + co]) * tab[112 + co] + tab[128 + co];
+        fl[i] = ((b + skip_resize_at(x7, S7, a.rs, y, x, co)) - tab[96 + co]) * tab[112 + co] + tab[128 + co];
     }
     __syncthreads();
     // ---- dense head forward: each layer's dot products split over GC_NT / 64 groups of k, summed in a fixed order
-    constexpr int NG = GC_NT / GC_HMAX;
     for (int d = 0; d < a.n_dense; ++d) {
-        const int nin = a.nin[d], nout = a.nout[d];
-        const float* xin = d == 0 ? fl : hx[d];
-        const int j = tid % GC_HMAX, gi = tid / GC_HMAX;
-        const int per = (nin + NG - 1) / NG;
-        float v = 0.f;
-        if (j < nout)
-            for (int k = gi * per; k < min(nin, (gi + 1) * per); ++k) v = fmaf(xin[k], a.dw[d][k * nout + j], v);
-        red[tid] = v;
-        __syncthreads();
+        const int nout = a.nout[d];
+        float t = dense_splitk<GC_NT>(d == 0 ? fl : hx[d], a.dw[d], a.nin[d], nout, red, tid);
         if (tid < nout) {
-            float t = 0.f;
-            for (int g = 0; g < NG; ++g) t += red[g * GC_HMAX + tid];
             if (a.db[d]) t += a.db[d][tid];
             hmm[d][tid] = t;
             if (d + 1 < a.n_dense) {
@@ -199,14 +143,13 @@ __global__ __launch_bounds__(GC_NT) void gc_tail_kernel(const GcTailArgs a) {
     // ---- adjoint of the head: dS/dz = one-hot at the class, MatMul -> transposed kernel, BN -> inv, ReLU6 -> mask
     int cls = a.cls ? a.cls[img] : static_cast<int>(a.ids[img]);
     cls = min(max(cls, 0), a.nc - 1);
-    if (tid < GC_HMAX) hg[(a.n_dense - 1) & 1][tid] = tid == cls ? 1.f : 0.f;
+    if (tid < LB_HMAX) hg[(a.n_dense - 1) & 1][tid] = tid == cls ? 1.f : 0.f;
     __syncthreads();
     for (int d = a.n_dense - 1; d >= 0; --d) {
         const int nin = a.nin[d], nout = a.nout[d];
         const float* gz = hg[d & 1];
         for (int k = tid; k < nin; k += GC_NT) {
-            float v = 0.f;
-            for (int j = 0; j < nout; ++j) v = fmaf(a.dw[d][k * nout + j], gz[j], v);
+            float v = dense_adjoint_at(a.dw[d], nout, gz, k);
             if (d == 0) {
                 fl[k] = v;                                // dS/dflat (the flat input is no longer needed)
             } else {
@@ -217,73 +160,30 @@ __global__ __launch_bounds__(GC_NT) void gc_tail_kernel(const GcTailArgs a) {
         __syncthreads();
     }
     // ---- stage 9: second BN, the residual Add (fl keeps dS/d(add)), first BN, pool, ReLU6 mask; in place over c9
-    for (int i = tid; i < S9 * S9 * GC_C; i += GC_NT) fl[i] *= tab[112 + (i & 15)];
+    for (int i = tid; i < S9 * S9 * LB_C; i += GC_NT) fl[i] *= tab[112 + (i & 15)];
     __syncthreads();
-    for (int i = tid; i < C9 * C9 * GC_C; i += GC_NT) {
+    for (int i = tid; i < C9 * C9 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4, Y = p / C9, X = p % C9;
-        int ylo, yhi, xlo, xhi;
-        pool_span(Y, S9, &ylo, &yhi);
-        pool_span(X, S9, &xlo, &xhi);
-        float t = 0.f;
-        for (int y = ylo; y <= yhi; ++y)
-            for (int x = xlo; x <= xhi; ++x) t += fl[(y * S9 + x) * GC_C + co];
+        const float t = pool_cover_sum(fl, S9, Y, X, co);
         c9[i] = relu6_passes(c9[i]) ? t * tab[64 + co] * (1.0f / 16.0f) : 0.f;
     }
     __syncthreads();
     // ---- conv 9 adjoint -> dS/ds8.bn, times stage 8's inv (dS/d pool8), in place over s8
-    for (int i = tid; i < S8 * S8 * GC_C; i += GC_NT) {
+    for (int i = tid; i < S8 * S8 * LB_C; i += GC_NT) {
         const int ci = i & 15, p = i >> 4, Y = p / S8, X = p % S8;
-        float t = 0.f;
-        for (int ky = 0; ky < 3; ++ky) {
-            const int y = Y - ky;
-            if (y < 0 || y >= C9) continue;
-            for (int kx = 0; kx < 3; ++kx) {
-                const int x = X - kx;
-                if (x < 0 || x >= C9) continue;
-                t = dot16(c9 + (y * C9 + x) * GC_C, w9 + ((ky * 3 + kx) * GC_C + ci) * GC_C, t);
-            }
-        }
-        s8[i] = t * tab[16 + ci];
+        s8[i] = conv16_adjoint_at(c9, C9, w9, Y, X, ci) * tab[16 + ci];
     }
     __syncthreads();
-    for (int i = tid; i < C8 * C8 * GC_C; i += GC_NT) {
+    for (int i = tid; i < C8 * C8 * LB_C; i += GC_NT) {
         const int co = i & 15, p = i >> 4, Y = p / C8, X = p % C8;
-        int ylo, yhi, xlo, xhi;
-        pool_span(Y, S8, &ylo, &yhi);
-        pool_span(X, S8, &xlo, &xhi);
-        float t = 0.f;
-        for (int y = ylo; y <= yhi; ++y)
-            for (int x = xlo; x <= xhi; ++x) t += s8[(y * S8 + x) * GC_C + co];
+        const float t = pool_cover_sum(s8, S8, Y, X, co);
         c8[i] = relu6_passes(c8[i]) ? t * (1.0f / 16.0f) : 0.f;
     }
     __syncthreads();
-    // ---- g7 = conv 8 adjoint + transpose of the skip resize (weights (1-yl)(1-xl), (1-yl)xl, yl(1-xl), yl xl)
-    for (int i = tid; i < S7 * S7 * GC_C; i += GC_NT) {
+    // ---- g7 = conv 8 adjoint + transpose of the skip resize
+    for (int i = tid; i < S7 * S7 * LB_C; i += GC_NT) {
         const int ci = i & 15, p = i >> 4, Y = p / S7, X = p % S7;
-        float t = 0.f;
-        for (int ky = 0; ky < 3; ++ky) {
-            const int y = Y - ky;
-            if (y < 0 || y >= C8) continue;
-            for (int kx = 0; kx < 3; ++kx) {
-                const int x = X - kx;
-                if (x < 0 || x >= C8) continue;
-                t = dot16(c8 + (y * C8 + x) * GC_C, w8 + ((ky * 3 + kx) * GC_C + ci) * GC_C, t);
-            }
-        }
-        float r = 0.f;
-        for (int y = 0; y < S9; ++y) {
-            const float yl = a.rlerp[y];
-            const float wy = (a.rlo[y] == Y ? 1.f - yl : 0.f) + (a.rhi[y] == Y ? yl : 0.f);
-            if (wy == 0.f) continue;
-            float rx = 0.f;
-            for (int x = 0; x < S9; ++x) {
-                const float xl = a.rlerp[x];
-                const float wx = (a.rlo[x] == X ? 1.f - xl : 0.f) + (a.rhi[x] == X ? xl : 0.f);
-                if (wx != 0.f) rx = fmaf(wx, fl[(y * S9 + x) * GC_C + ci], rx);
-            }
-            r = fmaf(wy, rx, r);
-        }
-        g7[i] = t + r;
+        g7[i] = conv16_adjoint_at(c8, C8, w8, Y, X, ci) + skip_resize_adjoint_at(fl, S9, a.rs, Y, X, ci);
     }
     if (!a.cam) return;
     __syncthreads();
@@ -291,22 +191,22 @@ __global__ __launch_bounds__(GC_NT) void gc_tail_kernel(const GcTailArgs a) {
     {
         const int c = tid & 15, part = tid >> 4;
         float t = 0.f;
-        for (int p = part; p < S7 * S7; p += GC_NT / 16) t += g7[p * GC_C + c];
+        for (int p = part; p < S7 * S7; p += GC_NT / 16) t += g7[p * LB_C + c];
         red[tid] = t;
     }
     __syncthreads();
-    if (tid < GC_C) {
+    if (tid < LB_C) {
         float t = 0.f;
         for (int part = 0; part < GC_NT / 16; ++part) t += red[part * 16 + tid];
         t /= static_cast<float>(S7 * S7);
         hg[0][tid] = t;
-        if (a.alpha) a.alpha[img * GC_C + tid] = t;
+        if (a.alpha) a.alpha[img * LB_C + tid] = t;
     }
     __syncthreads();
     for (int p = tid; p < S7 * S7; p += GC_NT) {
         float t = 0.f;
 #pragma unroll
-        for (int c = 0; c < GC_C; ++c) t = fmaf(hg[0][c], x7[p * GC_C + c], t);
+        for (int c = 0; c < LB_C; ++c) t = fmaf(hg[0][c], x7[p * LB_C + c], t);
         a.cam[static_cast<int64_t>(img) * S7 * S7 + p] = fmaxf(t, 0.f);
     }
 }
@@ -334,7 +234,7 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
     const float* g7 = a.ws + img * a.ws_img + a.off_g7;
     [[maybe_unused]] i32x4 wreg[36];
     if constexpr (DT == RN_DTYPE_F32) {
-        for (int i = tid; i < 9 * GC_CIN7 * GC_C; i += 256) wl[i] = a.w7[i];
+        for (int i = tid; i < 9 * LB_CIN7 * LB_C; i += 256) wl[i] = a.w7[i];
         __syncthreads();
     } else {
 #pragma unroll
@@ -344,12 +244,12 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
     }
     // the pooled rows of g7 this workgroup's conv rows reach (<= GC_G7ROWS), in LDS behind the weights: the pool adjoint's gathers
     // as global loads inside the epilogue serialised behind each other (0.37 ms for batch 256 at 224)
-    float* g7l = wl + (DT == RN_DTYPE_F32 ? 9 * GC_CIN7 * GC_C : 36 * 64 * 4);
+    float* g7l = wl + (DT == RN_DTYPE_F32 ? 9 * LB_CIN7 * LB_C : 36 * 64 * 4);
     const int wy0 = blockIdx.x * 4 * GC_R7;
     int glo, ghi, dummy;
     pool_span(wy0, S7, &glo, &dummy);
     pool_span(min(C7, wy0 + 4 * GC_R7) - 1, S7, &dummy, &ghi);
-    for (int i = tid; i < (ghi - glo + 1) * S7 * GC_C; i += 256) g7l[i] = g7[glo * S7 * GC_C + i];
+    for (int i = tid; i < (ghi - glo + 1) * S7 * LB_C; i += 256) g7l[i] = g7[glo * S7 * LB_C + i];
     __syncthreads();
     // Each input row is loaded once per tile and feeds the (up to) three conv rows of the wave it reaches: GC_R7 conv rows cost
     // GC_R7 + 2 operand rows instead of 3 GC_R7 (one load per (row, ky) read s6.bn nine times from the caches: 0.25 ms at batch 256)
@@ -368,17 +268,17 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
             if constexpr (DT == RN_DTYPE_F32) {
                 const float* x6 = static_cast<const float*>(a.x6);
                 for (int kx = 0; kx < 3; ++kx) {
-                    const float* px = x6 + (rowb + X + kx) * GC_CIN7 + 4 * kg;
+                    const float* px = x6 + (rowb + X + kx) * LB_CIN7 + 4 * kg;
 #pragma unroll 2
-                    for (int c16 = 0; c16 < GC_CIN7 / 16; ++c16) {
+                    for (int c16 = 0; c16 < LB_CIN7 / 16; ++c16) {
                         const f32x4 v = *reinterpret_cast<const f32x4*>(px + c16 * 16);
 #pragma unroll
                         for (int ky = 0; ky < 3; ++ky) {
                             const int yi = rr - ky;
                             if (yi < 0 || yi >= GC_R7) continue;
-                            const float* wt = wl + (ky * 3 + kx) * GC_CIN7 * GC_C + (4 * kg + c16 * 16) * GC_C + co;
+                            const float* wt = wl + (ky * 3 + kx) * LB_CIN7 * LB_C + (4 * kg + c16 * 16) * LB_C + co;
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) acc[yi] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], wt[q * GC_C], acc[yi], 0, 0, 0);
+                            for (int q = 0; q < 4; ++q) acc[yi] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[q], wt[q * LB_C], acc[yi], 0, 0, 0);
                         }
                     }
                 }
@@ -389,7 +289,7 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
                 for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
                     for (int cb = 0; cb < 4; ++cb)
-                        av[kx * 4 + cb] = *reinterpret_cast<const i32x4*>(x6 + (rowb + X + kx) * GC_CIN7 + cb * 32 + 8 * kg);
+                        av[kx * 4 + cb] = *reinterpret_cast<const i32x4*>(x6 + (rowb + X + kx) * LB_CIN7 + cb * 32 + 8 * kg);
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky) {
                     const int yi = rr - ky;
@@ -419,10 +319,10 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
                 int xlo, xhi;
                 pool_span(Xp, S7, &xlo, &xhi);
                 const bool cov = ylo <= yhi && xlo <= xhi;
-                const float* r0 = g7l + ylo * S7 * GC_C + co;
-                const float* r1 = g7l + yhi * S7 * GC_C + co;
-                const float t00 = cov ? r0[xlo * GC_C] : 0.f, t01 = cov && xhi > xlo ? r0[xhi * GC_C] : 0.f;
-                const float t10 = cov && yhi > ylo ? r1[xlo * GC_C] : 0.f, t11 = cov && yhi > ylo && xhi > xlo ? r1[xhi * GC_C] : 0.f;
+                const float* r0 = g7l + ylo * S7 * LB_C + co;
+                const float* r1 = g7l + yhi * S7 * LB_C + co;
+                const float t00 = cov ? r0[xlo * LB_C] : 0.f, t01 = cov && xhi > xlo ? r0[xhi * LB_C] : 0.f;
+                const float t10 = cov && yhi > ylo ? r1[xlo * LB_C] : 0.f, t11 = cov && yhi > ylo && xhi > xlo ? r1[xhi * LB_C] : 0.f;
                 const float t = (t00 + t01) + (t10 + t11);
                 gsum += x0 + 4 * kg + j < C7 && relu6_passes(acc[yi][j]) ? t : 0.f;
             }
@@ -430,7 +330,7 @@ __global__ __launch_bounds__(256) void gc_stage7_kernel(const GcStage7Args a) {
     }
     gsum += __shfl_xor(gsum, 16);
     gsum += __shfl_xor(gsum, 32);
-    if (lane < 16) a.part[(static_cast<int64_t>(img) * a.npart + blockIdx.x * 4 + wave) * GC_C + lane] = gsum;
+    if (lane < 16) a.part[(static_cast<int64_t>(img) * a.npart + blockIdx.x * 4 + wave) * LB_C + lane] = gsum;
 }
 
 struct GcMap6Args {
@@ -447,24 +347,24 @@ struct GcMap6Args {
 
 template <int DT>
 __global__ __launch_bounds__(256) void gc_map6_kernel(const GcMap6Args a) {
-    __shared__ float gam[GC_C];
-    __shared__ __attribute__((aligned(16))) float al[GC_CIN7];
+    __shared__ float gam[LB_C];
+    __shared__ __attribute__((aligned(16))) float al[LB_CIN7];
     const int tid = threadIdx.x, img = blockIdx.y;
     const int S6 = a.S6;
-    if (tid < GC_C) {
-        const float* p = a.part + static_cast<int64_t>(img) * a.npart * GC_C + tid;
+    if (tid < LB_C) {
+        const float* p = a.part + static_cast<int64_t>(img) * a.npart * LB_C + tid;
         float t = 0.f;
-        for (int k = 0; k < a.npart; ++k) t += p[k * GC_C];
+        for (int k = 0; k < a.npart; ++k) t += p[k * LB_C];
         gam[tid] = t * (a.inv7[tid] * (1.0f / 16.0f));       // dS/d pool7 = inv7 g7; the pool adjoint's 1/16
     }
     __syncthreads();
-    if (tid < GC_CIN7) {
+    if (tid < LB_CIN7) {
         float t = 0.f;
 #pragma unroll
-        for (int c = 0; c < GC_C; ++c) t = fmaf(a.w7sum[tid * GC_C + c], gam[c], t);
+        for (int c = 0; c < LB_C; ++c) t = fmaf(a.w7sum[tid * LB_C + c], gam[c], t);
         t /= static_cast<float>(S6 * S6);
         al[tid] = t;
-        if (a.alpha && blockIdx.x == 0) a.alpha[img * GC_CIN7 + tid] = t;
+        if (a.alpha && blockIdx.x == 0) a.alpha[img * LB_CIN7 + tid] = t;
     }
     __syncthreads();
     // 16 lanes per pixel, 8 channels per lane
@@ -476,7 +376,7 @@ __global__ __launch_bounds__(256) void gc_map6_kernel(const GcMap6Args a) {
         const int p = pb + slot;
         float t = 0.f;
         if (p < p1) {
-            const int64_t off = (static_cast<int64_t>(img) * S6 * S6 + p) * GC_CIN7 + 8 * sub;
+            const int64_t off = (static_cast<int64_t>(img) * S6 * S6 + p) * LB_CIN7 + 8 * sub;
             float v[8];
             if constexpr (DT == RN_DTYPE_F32) {
                 const f32x4 u0 = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.x6) + off);
@@ -520,7 +420,8 @@ struct GradCamState {
     size_t o_w7 = 0, o_w7sum = 0, o_inv7 = 0, o_w8 = 0, o_w9 = 0, o_bn8 = 0, o_bn9 = 0, o_bn9b = 0, o_rlerp = 0;
     size_t o_dw[RN_MAX_DENSE] = {}, o_db[RN_MAX_DENSE] = {}, o_dinv[RN_MAX_DENSE] = {}, o_dshift[RN_MAX_DENSE] = {};
     bool has_b[RN_MAX_DENSE] = {}, has_bn[RN_MAX_DENSE] = {};
-    std::vector<int32_t> rlo, rhi;
+    rn_lastblock sd{};                             // the block's sides
+    std::vector<int32_t> rtab;                     // rlo | rhi
     std::vector<unsigned short> wfrag;             // 16-bit handles: W7 as MFMA B fragments
     // device (first call)
     float* d_blob = nullptr;
@@ -538,27 +439,24 @@ struct GradCamState {
 
 GradCamState* state(rn_handle* h) { return static_cast<GradCamState*>(h->gradcam); }
 
-int sides(const rn_handle* h, const GradCamState* g, int* S6, int* C7, int* S7, int* C8, int* S8, int* C9, int* S9) {
-    *S6 = h->stages[g->s6].out_side;
-    *C7 = h->stages[g->s7].conv_side;
-    *S7 = h->stages[g->s7].out_side;
-    *C8 = h->stages[g->s8].conv_side;
-    *S8 = h->stages[g->s8].out_side;
-    *C9 = h->stages[g->s9].conv_side;
-    *S9 = h->stages[g->s9].out_side;
-    return RN_OK;
+// calls f with the handle's storage type as a compile-time constant: one launch line per kernel template
+template <typename F>
+void by_dtype(int dtype, F&& f) {
+    if (dtype == RN_DTYPE_F32)
+        f(std::integral_constant<int, RN_DTYPE_F32>{});
+    else if (dtype == RN_DTYPE_BF16)
+        f(std::integral_constant<int, RN_DTYPE_BF16>{});
+    else
+        f(std::integral_constant<int, RN_DTYPE_F16>{});
 }
 
 int ensure_device(rn_handle* h, GradCamState* g) {
     if (g->ready) return RN_OK;
-    int S6, C7, S7, C8, S8, C9, S9;
-    sides(h, g, &S6, &C7, &S7, &C8, &S8, &C9, &S9);
+    const auto [S6, C7, S7, C8, S8, C9, S9] = g->sd;
     const size_t nb = static_cast<size_t>(h->max_batch);
     int rc;
     if ((rc = upload(h, g->blob.data(), g->blob.size(), &g->d_blob)) != RN_OK) return rc;
-    std::vector<int32_t> rt(g->rlo);
-    rt.insert(rt.end(), g->rhi.begin(), g->rhi.end());
-    if ((rc = upload(h, rt.data(), rt.size(), &g->d_rtab)) != RN_OK) return rc;
+    if ((rc = upload(h, g->rtab.data(), g->rtab.size(), &g->d_rtab)) != RN_OK) return rc;
     if (!g->wfrag.empty()) {
         unsigned short* p = nullptr;
         if ((rc = upload(h, g->wfrag.data(), g->wfrag.size(), &p)) != RN_OK) return rc;
@@ -566,25 +464,25 @@ int ensure_device(rn_handle* h, GradCamState* g) {
     }
     // per-image workspace: c8 | s8 | c9 | flat | g7 | s7.bn in fp32, each a multiple of 16 floats
     g->off_c8 = 0;
-    g->off_s8 = g->off_c8 + static_cast<int64_t>(C8) * C8 * GC_C;
-    g->off_c9 = g->off_s8 + static_cast<int64_t>(S8) * S8 * GC_C;
-    g->off_fl = g->off_c9 + static_cast<int64_t>(C9) * C9 * GC_C;
-    g->off_g7 = g->off_fl + static_cast<int64_t>(S9) * S9 * GC_C;
-    g->off_x7 = g->off_g7 + static_cast<int64_t>(S7) * S7 * GC_C;
-    g->ws_img = g->off_x7 + static_cast<int64_t>(S7) * S7 * GC_C;
+    g->off_s8 = g->off_c8 + static_cast<int64_t>(C8) * C8 * LB_C;
+    g->off_c9 = g->off_s8 + static_cast<int64_t>(S8) * S8 * LB_C;
+    g->off_fl = g->off_c9 + static_cast<int64_t>(C9) * C9 * LB_C;
+    g->off_g7 = g->off_fl + static_cast<int64_t>(S9) * S9 * LB_C;
+    g->off_x7 = g->off_g7 + static_cast<int64_t>(S7) * S7 * LB_C;
+    g->ws_img = g->off_x7 + static_cast<int64_t>(S7) * S7 * LB_C;
     void* p = nullptr;
     if ((rc = dev_alloc(h, nb * g->ws_img * 4, &p)) != RN_OK) return rc;
     g->d_ws = static_cast<float*>(p);
     const int nblk = (C7 + 4 * GC_R7 - 1) / (4 * GC_R7);
     g->npart = nblk * 4;
-    if ((rc = dev_alloc(h, nb * g->npart * GC_C * 4, &p)) != RN_OK) return rc;
+    if ((rc = dev_alloc(h, nb * g->npart * LB_C * 4, &p)) != RN_OK) return rc;
     g->d_part = static_cast<float*>(p);
     if ((rc = dev_alloc(h, nb * 4, &p)) != RN_OK) return rc;
     g->d_cls = static_cast<int32_t*>(p);
     const size_t cam_px = static_cast<size_t>(std::max(S6 * S6, S7 * S7));
     if ((rc = dev_alloc(h, nb * cam_px * 4, &p)) != RN_OK) return rc;
     g->d_cam = static_cast<float*>(p);
-    if ((rc = dev_alloc(h, nb * GC_CIN7 * 4, &p)) != RN_OK) return rc;
+    if ((rc = dev_alloc(h, nb * LB_CIN7 * 4, &p)) != RN_OK) return rc;
     g->d_alpha = static_cast<float*>(p);
     g->ready = true;          // (last: after a failed allocation the next call starts over; what was allocated is freed by rn_destroy)
     return RN_OK;
@@ -598,12 +496,12 @@ const char* rn_tail_graph_reason(const rn_weights* w) {
     const int ns = w->n_stages;
     if (ns < 4 || w->n_dense < 1) return "the graph has no 128 -> 16 -> 16 -> 16 last block";
     const rn_conv_stage &st6 = w->stages[ns - 4], &st7 = w->stages[ns - 3], &st8 = w->stages[ns - 2], &st9 = w->stages[ns - 1];
-    auto last_block = [](const rn_conv_stage& s) { return s.cout == GC_C && s.pool_k == 4 && s.pool_s == 2; };
-    if (st6.cout != GC_CIN7 || st7.cin != GC_CIN7 || !last_block(st7) || !last_block(st8) || !last_block(st9) || st8.cin != GC_C ||
-        st9.cin != GC_C || st7.skip_stage >= 0 || st8.skip_stage >= 0 || st9.skip_stage != ns - 3 || !st9.gamma2 || st6.skip_stage >= 0)
+    auto last_block = [](const rn_conv_stage& s) { return s.cout == LB_C && s.pool_k == 4 && s.pool_s == 2; };
+    if (st6.cout != LB_CIN7 || st7.cin != LB_CIN7 || !last_block(st7) || !last_block(st8) || !last_block(st9) || st8.cin != LB_C ||
+        st9.cin != LB_C || st7.skip_stage >= 0 || st8.skip_stage >= 0 || st9.skip_stage != ns - 3 || !st9.gamma2 || st6.skip_stage >= 0)
         return "the graph's last two blocks are not conv_block(128, pooling=False) + conv_block(16, 4, 2, depth 3)";
     for (int d = 0; d < w->n_dense; ++d)
-        if (w->dense[d].nout > GC_HMAX || (d + 1 < w->n_dense && !w->dense[d].gamma) || (d + 1 == w->n_dense && w->dense[d].gamma))
+        if (w->dense[d].nout > LB_HMAX || (d + 1 < w->n_dense && !w->dense[d].gamma) || (d + 1 == w->n_dense && w->dense[d].gamma))
             return "the dense head is not BN dense blocks followed by one plain dense layer";
     return nullptr;
 }
@@ -631,38 +529,34 @@ int rn_gradcam_keep(rn_handle* h, const rn_weights* w) {
         return off;
     };
     auto put_bn = [&](const float* gamma, const float* beta, const float* mean, const float* var) {
-        std::vector<float> t(3 * GC_C);
-        for (int c = 0; c < GC_C; ++c) {
+        std::vector<float> t(3 * LB_C);
+        for (int c = 0; c < LB_C; ++c) {
             t[c] = mean[c];
-            t[GC_C + c] = rn_bn_inv(var[c], gamma[c], eps);
-            t[2 * GC_C + c] = beta[c];
+            t[LB_C + c] = rn_bn_inv(var[c], gamma[c], eps);
+            t[2 * LB_C + c] = beta[c];
         }
         return put(t.data(), t.size());
     };
-    const size_t n7 = static_cast<size_t>(9) * GC_CIN7 * GC_C;
+    const size_t n7 = static_cast<size_t>(9) * LB_CIN7 * LB_C;
     g->o_w7 = put(st7.kernel, n7);
     {
-        std::vector<float> ws(static_cast<size_t>(GC_CIN7) * GC_C, 0.f), inv(GC_C);
+        std::vector<float> ws(static_cast<size_t>(LB_CIN7) * LB_C, 0.f), inv(LB_C);
         for (int t = 0; t < 9; ++t)
             for (size_t i = 0; i < ws.size(); ++i) ws[i] += st7.kernel[t * ws.size() + i];
         g->o_w7sum = put(ws.data(), ws.size());
-        for (int c = 0; c < GC_C; ++c) inv[c] = rn_bn_inv(st7.variance[c], st7.gamma[c], eps);
+        for (int c = 0; c < LB_C; ++c) inv[c] = rn_bn_inv(st7.variance[c], st7.gamma[c], eps);
         g->o_inv7 = put(inv.data(), inv.size());
     }
-    g->o_w8 = put(st8.kernel, 9 * GC_C * GC_C);
-    g->o_w9 = put(st9.kernel, 9 * GC_C * GC_C);
+    g->o_w8 = put(st8.kernel, 9 * LB_C * LB_C);
+    g->o_w9 = put(st9.kernel, 9 * LB_C * LB_C);
     g->o_bn8 = put_bn(st8.gamma, st8.beta, st8.mean, st8.variance);
     g->o_bn9 = put_bn(st9.gamma, st9.beta, st9.mean, st9.variance);
     g->o_bn9b = put_bn(st9.gamma2, st9.beta2, st9.mean2, st9.variance2);
     // legacy bilinear tables S7 -> S9
     {
-        std::vector<int> conv, out;
-        if (rn_stage_sides(w, conv, out) < ns) return no("im_side is too small for the graph");      // (build_plan reports it)
-        const int out_size = out[g->s9];
-        g->rlo.resize(out_size);
-        g->rhi.resize(out_size);
-        std::vector<float> lerp(out_size);
-        rn_legacy_resize_table(out[g->s7], out_size, g->rlo.data(), g->rhi.data(), lerp.data());
+        if (rn_lastblock_sides(w, &g->sd) < ns) return no("im_side is too small for the graph");      // (build_plan reports it)
+        std::vector<float> lerp;
+        rn_lastblock_resize_tables(g->sd, g->rtab, lerp);
         g->o_rlerp = put(lerp.data(), lerp.size());
     }
     for (int d = 0; d < w->n_dense; ++d) {
@@ -692,7 +586,7 @@ int rn_gradcam_keep(rn_handle* h, const rn_weights* w) {
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
                     const int ci = cb * 32 + 8 * (l >> 4) + j, co = l & 15;
-                    const float wv = st7.kernel[(static_cast<size_t>(tap) * GC_CIN7 + ci) * GC_C + co];
+                    const float wv = st7.kernel[(static_cast<size_t>(tap) * LB_CIN7 + ci) * LB_C + co];
                     const unsigned short hi = rn_to16(wv, h->dtype);
                     g->wfrag[(static_cast<size_t>(q) * 64 + l) * 8 + j] = hi;
                     g->wfrag[(static_cast<size_t>(36 + q) * 64 + l) * 8 + j] = rn_to16(wv - rn_from16(hi, h->dtype), h->dtype);
@@ -729,8 +623,7 @@ int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* 
     GradCamState* g = state(h);
     int rc;
     if ((rc = ensure_device(h, g)) != RN_OK) return rc;
-    int S6, C7, S7, C8, S8, C9, S9;
-    sides(h, g, &S6, &C7, &S7, &C8, &S8, &C9, &S9);
+    const auto [S6, C7, S7, C8, S8, C9, S9] = g->sd;
     const NodeBuf& n6 = h->nodes[h->stages[g->s6].node_bn];
     const NodeBuf& n7 = h->nodes[h->stages[g->s7].node_bn];
     if (!n6.ptr || !n7.ptr || h->node_perm.count(h->stages[g->s6].node_bn) || h->node_perm.count(h->stages[g->s7].node_bn)) {
@@ -750,9 +643,7 @@ int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* 
     t.bn8 = B + g->o_bn8;
     t.bn9 = B + g->o_bn9;
     t.bn9b = B + g->o_bn9b;
-    t.rlo = g->d_rtab;
-    t.rhi = g->d_rtab + S9;
-    t.rlerp = B + g->o_rlerp;
+    t.rs = LbResize{g->d_rtab, g->d_rtab + S9, B + g->o_rlerp};
     t.n_dense = static_cast<int>(h->dense.size());
     for (int d = 0; d < t.n_dense; ++d) {
         t.nin[d] = h->dense[d].nin;
@@ -775,12 +666,7 @@ int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* 
     t.off_x7 = g->off_x7;
     t.cam = layer6 ? nullptr : d_cam;
     t.alpha = layer6 ? nullptr : d_alpha;
-    if (h->dtype == RN_DTYPE_F32)
-        hipLaunchKernelGGL(gc_tail_kernel<RN_DTYPE_F32>, dim3(n), dim3(GC_NT), 0, h->stream, t);
-    else if (h->dtype == RN_DTYPE_BF16)
-        hipLaunchKernelGGL(gc_tail_kernel<RN_DTYPE_BF16>, dim3(n), dim3(GC_NT), 0, h->stream, t);
-    else
-        hipLaunchKernelGGL(gc_tail_kernel<RN_DTYPE_F16>, dim3(n), dim3(GC_NT), 0, h->stream, t);
+    by_dtype(h->dtype, [&](auto dt) { hipLaunchKernelGGL(gc_tail_kernel<decltype(dt)::value>, dim3(n), dim3(GC_NT), 0, h->stream, t); });
     RN_CHECK_LAUNCH();
     if (!layer6) return RN_OK;
     GcStage7Args s{};
@@ -796,13 +682,9 @@ int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* 
     s.part = g->d_part;
     s.npart = g->npart;
     const dim3 grid7(g->npart / 4, n);
-    const size_t g7_lds = static_cast<size_t>(GC_G7ROWS) * S7 * GC_C * 4;
-    if (h->dtype == RN_DTYPE_F32)
-        hipLaunchKernelGGL(gc_stage7_kernel<RN_DTYPE_F32>, grid7, dim3(256), 9 * GC_CIN7 * GC_C * 4 + g7_lds, h->stream, s);
-    else if (h->dtype == RN_DTYPE_BF16)
-        hipLaunchKernelGGL(gc_stage7_kernel<RN_DTYPE_BF16>, grid7, dim3(256), 36 * 64 * 16 + g7_lds, h->stream, s);
-    else
-        hipLaunchKernelGGL(gc_stage7_kernel<RN_DTYPE_F16>, grid7, dim3(256), 36 * 64 * 16 + g7_lds, h->stream, s);
+    const size_t g7_lds = static_cast<size_t>(GC_G7ROWS) * S7 * LB_C * 4;
+    const size_t w7_lds = h->dtype == RN_DTYPE_F32 ? 9 * LB_CIN7 * LB_C * 4 : 36 * 64 * 16;
+    by_dtype(h->dtype, [&](auto dt) { hipLaunchKernelGGL(gc_stage7_kernel<decltype(dt)::value>, grid7, dim3(256), w7_lds + g7_lds, h->stream, s); });
     RN_CHECK_LAUNCH();
     GcMap6Args m{};
     m.x6 = n6.ptr;
@@ -815,12 +697,7 @@ int rn_gradcam_launch(rn_handle* h, int n, const int32_t* d_cls, const int64_t* 
     m.alpha = d_alpha;
     m.pix_per_block = 128;
     const dim3 grid6((S6 * S6 + m.pix_per_block - 1) / m.pix_per_block, n);
-    if (h->dtype == RN_DTYPE_F32)
-        hipLaunchKernelGGL(gc_map6_kernel<RN_DTYPE_F32>, grid6, dim3(256), 0, h->stream, m);
-    else if (h->dtype == RN_DTYPE_BF16)
-        hipLaunchKernelGGL(gc_map6_kernel<RN_DTYPE_BF16>, grid6, dim3(256), 0, h->stream, m);
-    else
-        hipLaunchKernelGGL(gc_map6_kernel<RN_DTYPE_F16>, grid6, dim3(256), 0, h->stream, m);
+    by_dtype(h->dtype, [&](auto dt) { hipLaunchKernelGGL(gc_map6_kernel<decltype(dt)::value>, grid6, dim3(256), 0, h->stream, m); });
     RN_CHECK_LAUNCH();
     return RN_OK;
 }

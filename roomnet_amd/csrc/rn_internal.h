@@ -267,6 +267,16 @@ void rn_legacy_resize_table(int in_size, int out_size, int32_t* lo, int32_t* hi,
 // fit: w->n_stages, or the index of the first stage for which im_side is too small (conv / out are valid in front of it).
 int rn_stage_sides(const rn_weights* w, std::vector<int>& conv, std::vector<int>& out);
 
+// The last conv block (stages 7-9 behind s6.bn), as grad-CAM and the fine-tuning trainers walk it: the side of s6.bn, then conv side and
+// output side of stages 7, 8 and 9.  rn_lastblock_sides fills it from the graph's last four stages and returns what rn_stage_sides
+// returns (less than w->n_stages: im_side is too small, `s` is not filled).
+struct rn_lastblock {
+    int S6, C7, S7, C8, S8, C9, S9;
+};
+int rn_lastblock_sides(const rn_weights* w, rn_lastblock* s);
+// the legacy bilinear tables of stage 9's skip resize S7 -> S9, as both users upload them: rtab = [lo | hi] (2 S9), lerp (S9)
+void rn_lastblock_resize_tables(const rn_lastblock& s, std::vector<int32_t>& rtab, std::vector<float>& lerp);
+
 // tf.nn.batch_normalization folded to y = x * inv + shift, in float32 as every path of the library evaluates it
 inline float rn_bn_inv(float var, float gamma, float eps) { return (1.0f / sqrtf(var + eps)) * gamma; }
 inline float rn_bn_shift(float beta, float mean, float inv) { return beta - mean * inv; }

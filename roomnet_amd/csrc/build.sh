@@ -14,13 +14,14 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 
-PLAIN="rn_api rn_kernels_f32 rn_fused rn_imageops rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam rn_bnstats rn_finetune rn_finetune7"
+PLAIN="rn_api rn_kernels_f32 rn_fused rn_generic rn_imageops rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam rn_bnstats rn_finetune rn_finetune7"
 # MFMA results stay in VGPRs: the epilogue reads every accumulator with the VALU, and AGPR
 # accumulators cost one v_accvgpr_read each (64 per row in the residual variant).
 # (max-ilp scheduling was measured slower, see NOTES.md)
 VGPR_FORM="rn_stage_rw rn_stage23x rn_stage5x rn_stage4x rn_stage6x"
 # the test / A-B library: the same objects + the round-2 comparison kernels (RN_FLAG_PAIR_32X32), which the product library
-# does not carry; the files that dispatch to them are compiled again with -DRN_ROUND2_ARMS
+# does not carry; the files that dispatch to them are compiled again with -DRN_ROUND2_ARMS (host code: rn_fused's only kernel is the
+# constant-channel fill)
 AB_ONLY="rn_stage23"            # (compiled like VGPR_FORM)
 AB_REBUILT="rn_api rn_fused"
 # register report: a spill in one of the hot kernels costs ~25 % of its time (seen on the fused stage pair) and hipcc

@@ -31,6 +31,19 @@ bool rn_tail_supported(const rn_handle* h);
 int rn_tail_launch(rn_handle* h, const rnk::i32x4* wfrag_a, const rnk::i32x4* wfrag_b, const HeadArgs& head, int n, float* d_probs,
                    int64_t* d_ids);
 
+// ---- the generic family (rn_generic.hip): stage_mfma_kernel, one variant per stage shape, and stage 0 as a launch of its own
+struct GenericPlan {
+    int variant = -1;        // index into the dispatch table
+    int npt = 1;             // pixel tiles (= waves) per workgroup
+    int n_colblocks = 1;
+    int n_ctg = 1;           // workgroups the cout tiles are split over
+    size_t lds_bytes = 0;    // (above 160 KB with npt == 1: the stage does not fit)
+};
+bool rn_generic_plan(int cin, int cout, int pool_k, int pool_s, bool res, int out_side, GenericPlan* plan);    // false: no variant
+void rn_generic_pack(const float* w_hwio, int cin, int cout, int dtype, std::vector<unsigned short>* out);
+int rn_generic_launch(const GenericPlan& p, int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
+int rn_stage0_launch(int dtype, hipStream_t s, const rnk::Stage0Args& a, int n);
+
 // ---- register-weights stage kernels (rn_stage_rw.hip)
 struct RwPlan {
     int variant = -1;

@@ -1,496 +1,45 @@
-// Fused 16-bit execution path (RN_DTYPE_BF16 / RN_DTYPE_F16): one launch per conv stage.
-//
-// A stage is   conv3x3 VALID s1 (no bias) -> ReLU6 -> [avg-pool k x k / s] -> BN
-//              -> [ + legacy-bilinear(skip) -> BN ]          (reference network.py:172-208)
-// Activations live in HBM as NHWC 16-bit tensors; a stage reads its input once and
-// writes its post-BN output once (the stage-boundary traffic model of SURVEY.md 8d).
-// Accumulation, ReLU6, pooling, BN and the residual are float32 in registers.
-//
-// Kernel structure (stages 1..N, `stage_mfma_kernel`):
-//   * a workgroup owns one image, one band of output rows and one block of columns and
-//     walks down its band one conv row per iteration ("row streaming"): the last
-//     3 input rows live in an LDS ring, the next row is prefetched into registers while
-//     the current one is computed -- every input row is fetched once per band.
-//   * implicit GEMM on the matrix cores, D[cout][pixel] = W^T[cout][k] * im2col[k][pixel]
-//     with v_mfma_f32_32x32x16_{bf16,f16}: a wave owns a tile of 32 consecutive conv
-//     columns; the B operand (8 consecutive channels of one tap of one pixel = 16 B) is a
-//     single ds_read_b128 from the NHWC ring, made bank-conflict free by XOR-swizzling the
-//     16-byte channel chunk inside each pixel; the A operand (weights) is pre-packed on
-//     the host in fragment order and read from LDS with lane-linear ds_read_b128.
-//   * the accumulator layout puts the pixel on the lane and the channel in the
-//     register, so ReLU6 is per register, the horizontal pool sum is two DPP wave shifts
-//     per register, the vertical pool sum is a register ring across iterations, BN is
-//     an fma, and the pooled tile never touches LDS or HBM before its final store.
-//   * neighbouring pixel tiles overlap by k-1 columns so that no cross-wave exchange is
-//     needed for the horizontal pool.
-// Stage 0 (3 input channels, K = 27) runs on the matrix cores too (`stage0_kernel` below): its operand is the
-// uint8 pixel value, the uint8 -> [-1,1] pre-processing of network.py:129 is folded into its weights.
+// Fused 16-bit execution path (RN_DTYPE_BF16 / RN_DTYPE_F16), host side.  rn_fused_prepare decides once per handle which kernel family
+// (rn_fused.h lists their files) runs every conv stage, packs its weights and tables and binds its launch arguments; rn_fused_forward
+// walks the stages, adds what depends on the call (the bands of this batch size, the image pointer) and launches.
 #include "rn_fused.h"
-#include <vector>
-#include <algorithm>
-#include "rn_stage.h"
 #include "rn_clock.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <cstdlib>
 
 using namespace rnk;
 
 namespace {
 
-// ------------------------------------------------------------------------------ stage 0
-// uint8 BGR [N,S,S,3] -> table -> conv3x3 (3 -> 8) -> ReLU6 -> avg-pool 3x3/1 -> BN -> 16-bit NHWC.
-//
-// Row streaming on the matrix cores with the im2col built entirely in registers:
-//   * K is laid out as (ky, kx in 0..3, c in 0..3) = 48 (kx = 3 and c = 3 are zero weights), i.e.
-//     ONE 16-deep MFMA K-chunk per input row ky.  For v_mfma_f32_32x32x16 the B operand of lane
-//     (r, h) is then: h = 0: pixels r and r+1 (4 x 16-bit each), h = 1: pixel r+2 and zeros.
-//   * lane (r, h) loads ITS pixel x0 + r + 2h (3 bytes) and packs the byte values as fp16 numbers
-//     (R,G | B,0) -- exact; the pre-processing table of network.py:129 is folded into the weights
-//     (s0_pixel_halves, rn_stage.h); the lower half-wave gets pixel r+1 from its neighbour lane
-//     with a DPP shift.  The fragments of the last 3 input rows stay in 12 VGPRs.
-//   * D[cout][pixel]: rows 0..7 hold the hi halves of the folded weights, rows 8..15 the lo halves,
-//     so a lane owns 4 channels of one conv pixel in 4 + 4 accumulator registers: add, ReLU6,
-//     3-wide horizontal sum by DPP, 3-row vertical sum in a register ring, one fma for BN, one
-//     8-byte store.  No LDS traffic.
-// A wave owns 32 conv columns (29 output columns, tiles overlap by 3) and walks down a band of
-// rows; a workgroup is up to 8 such waves side by side.
-// The MFMA inputs of this stage are ALWAYS fp16, whatever the storage type of the activations:
-// fp16 holds the 256 input levels exactly and the weights as hi + lo pairs, so the stage computes
-// the fp32 convolution of the exact input (bf16's 8-bit significand cannot represent the levels).
-constexpr int S0_CO = 8;
-constexpr int S0_TSTRIDE = 29;      // output columns per 32-column tile: 32 - (3 - 1) - 1
-constexpr int S0_AHEAD = 8;         // input rows prefetched (one dword per lane and row in registers)
+// The kernel family that runs a stage as a launch of its own; a stage has exactly one (choose_family).  Generic: stage_mfma_kernel
+// (rn_generic.hip), any shape; RegWeights: rn_stage_rw.hip; Conv16 / Conv16P: rn_conv16.hip; Row4x / 5x / 6x: rn_stage4x / 5x / 6x.hip.
+enum class Family { Generic, RegWeights, Conv16, Conv16P, Row4x, Row5x, Row6x };
 
-struct Stage0Args {
-    const uint8_t* bgr;             // [N, S, S, 3]
-    const i32x4* wfrag;             // [3 (ky)][64 lanes] A fragments, 8 x fp16: cout rows 0..7 hi, 8..15 lo
-    const float* ptab;              // [2][8] folded BN: scale (inv / 9 / 2^8), shift
-    unsigned short* out;            // [N, So, So, 8]
-    int S, So;
-    int rows_per_band, n_bands, n_colblocks, npt;
-};
-
-template <int DT>
-__global__ __launch_bounds__(512) void stage0_kernel(const Stage0Args a) {
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
-    const int cb = blockIdx.x % a.n_colblocks;
-    const int band = blockIdx.x / a.n_colblocks;
-    const int n = blockIdx.y;
-
-    const int yo0 = band * a.rows_per_band;
-    const int yo1 = min(a.So, yo0 + a.rows_per_band);
-    const int nconv = (yo1 - yo0) + 2;                 // conv rows of the band (pool 3, stride 1)
-    const int nin = nconv + 2;                         // input rows
-    const int xt0 = (cb * a.npt + wave) * S0_TSTRIDE;  // first conv / input column of this wave's tile
-    const int px = min(xt0 + r + 2 * hh, a.S - 1);     // this lane's input column (clamped at the edge)
-    // One (unaligned) dword load per lane and row covers the pixel's 3 bytes -- three byte loads cost the
-    // address coalescer three passes per row.  The last column reads one byte early and shifts, so no lane
-    // ever touches the byte behind the caller's buffer.
-    const int sh0 = px == a.S - 1 ? 8 : 0;
-    const uint8_t* src = a.bgr + (static_cast<int64_t>(n) * a.S * a.S + static_cast<int64_t>(yo0) * a.S + px) * 3 - (sh0 >> 3);
-    const int row_bytes = a.S * 3;
-
-    i32x4 wreg[3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) wreg[ky] = a.wfrag[ky * 64 + lane];
-    const f32x4 scale = *reinterpret_cast<const f32x4*>(a.ptab + 4 * hh);
-    const f32x4 shift = *reinterpret_cast<const f32x4*>(a.ptab + 8 + 4 * hh);
-    const int xo = xt0 + r;
-    const bool lane_out = r < S0_TSTRIDE && xo < a.So && (xo - cb * a.npt * S0_TSTRIDE) < a.npt * S0_TSTRIDE;
-    unsigned short* out_lane = a.out + (static_cast<int64_t>(n) * a.So * a.So + xo) * S0_CO + 4 * hh;
-    const unsigned nb_mask = hh ? 0u : 0xffffffffu;    // the upper half-wave's second pixel slot is zero
-
-    // prefetch queue of raw bytes
-    unsigned pw[S0_AHEAD];
-    auto load_px = [&](int j) -> unsigned {
-        unsigned w;
-        __builtin_memcpy(&w, src + static_cast<int64_t>(min(j, nin - 1)) * row_bytes, 4);   // unaligned dword
-        return w;
-    };
-#pragma unroll
-    for (int i = 0; i < S0_AHEAD; ++i) pw[i] = load_px(i);
-
-    i32x4 bfr[3];                                      // B fragments of the 3 live input rows
-    float h1[4], h2[4];                                // horizontal sums of the two previous conv rows
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h1[j] = h2[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) bfr[i] = i32x4{0, 0, 0, 0};
-
-    // consume the oldest prefetched row into a B fragment, refill the queue slot
-    auto next_frag = [&](int jrow) -> i32x4 {
-        const unsigned w = pw[0] >> sh0;                       // bytes: B, G, R
-        int d0, d1;
-        s0_pixel_halves(w, d0, d1);
-#pragma unroll
-        for (int i = 0; i + 1 < S0_AHEAD; ++i) pw[i] = pw[i + 1];
-        pw[S0_AHEAD - 1] = load_px(jrow + S0_AHEAD);
-        i32x4 f;
-        f[0] = d0;
-        f[1] = d1;
-        f[2] = static_cast<int>(static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, d0, 0x130, 0xf, 0xf, true)) & nb_mask);
-        f[3] = static_cast<int>(static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, d1, 0x130, 0xf, 0xf, true)) & nb_mask);
-        return f;
-    };
-    bfr[0] = next_frag(0);
-    bfr[1] = next_frag(1);
-
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int it = 0; it < nconv; ++it) {
-        bfr[2] = next_frag(it + 2);
-        f32x16 acc = mfma32<RN_DTYPE_F16>(wreg[0], bfr[0], zero);
-        acc = mfma32<RN_DTYPE_F16>(wreg[1], bfr[1], acc);
-        acc = mfma32<RN_DTYPE_F16>(wreg[2], bfr[2], acc);
-        bfr[0] = bfr[1];
-        bfr[1] = bfr[2];
-        float y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = s0_relu6(acc, j);
-            const float v1 = lane_next(v);
-            const float hs = (v + v1) + lane_next(v1);
-            y[j] = fmaf((h2[j] + h1[j]) + hs, scale[j], shift[j]);
-            h2[j] = h1[j];
-            h1[j] = hs;
-        }
-        if (it >= 2 && lane_out)
-            *reinterpret_cast<uint2*>(out_lane + static_cast<int64_t>(yo0 + it - 2) * a.So * S0_CO) =
-                pack4<DT>(y[0], y[1], y[2], y[3]);
-    }
-}
-
-// ------------------------------------------------------------------------ MFMA stage
-template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int CTW>
-__global__ __launch_bounds__(512) void stage_mfma_kernel(const StageArgs a) {
-    using G = StageGeom<CIN>;
-    constexpr int CP = G::CP, KC = G::KC, LPT = G::LPT;
-    constexpr int CT = (COUT + 31) / 32;                 // 32-wide cout tiles in the stage
-    constexpr int NG = COUT >= 32 ? 4 : COUT / 8;        // groups of 4 consecutive couts per lane half-row
-    constexpr int TSTRIDE = tile_stride(PK, PS);
-    constexpr int NOUT_T = tile_nout(PK, PS);
-    constexpr int RING = PK ? PK - 1 : 0;
-    constexpr int PIXB = CIN * 2;                        // bytes per pixel
-    static_assert(CIN % 8 == 0 && COUT % 8 == 0, "channels must be multiples of 8");
-    static_assert(CT % CTW == 0, "cout tiles must split evenly over workgroups");
-    static_assert(!PK || PS == 1 || PS == 2, "pool stride 1 or 2");
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
-    const int nthreads = blockDim.x;
-    const int npt = a.npt;
-
-    int bid = blockIdx.x;
-    const int ctg = bid % a.n_ctg;
-    bid /= a.n_ctg;
-    const int cb = bid % a.n_colblocks;
-    const int band = bid / a.n_colblocks;
-    const int n = blockIdx.y;
-
-    const int ringcols = (npt - 1) * TSTRIDE + 34;
-    const int rowbytes = ringcols * PIXB;
-    char* const wl = smem;                                  // weights [KC][CTW][64] x 16 B
-    char* const ring = smem + KC * CTW * 1024;              // NSLOT rows
-
-    // rows of this band
-    const int yo0 = band * a.rows_per_band;
-    const int yo1 = min(a.Ho, yo0 + a.rows_per_band);
-    const int yc0 = PK ? yo0 * PS : yo0;
-    const int nconv = PK ? (yo1 - yo0 - 1) * PS + PK : (yo1 - yo0);
-    const int nin = nconv + 2;
-    // columns of this block
-    const int x0c = cb * npt * TSTRIDE;                     // first conv / input column of the block
-    const int xo_blk0 = PK ? x0c / PS : x0c;
-
-    // ---- weights -> LDS (fragment order, lane linear)
-    {
-        const i32x4* src = a.wfrag;
-        for (int i = tid; i < KC * CTW * 64; i += nthreads) {
-            const int l = i & 63, t = i >> 6;
-            const int ct = t % CTW, kc = t / CTW;
-            reinterpret_cast<i32x4*>(wl)[i] = src[(kc * CT + ctg * CTW + ct) * 64 + l];
-        }
-    }
-
-    // ---- input-row loader: thread owns up to LPT 16-byte chunks of a ring row
-    const int nchunks = ringcols * CP;
-    const unsigned short* const in_img = a.in + static_cast<int64_t>(n) * a.H * a.W * CIN;
-    int ld_goff[LPT];     // element offset inside an input row, or -1 (zero fill / not mine)
-    int ld_loff[LPT];     // byte offset inside a ring row
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-        const int q = tid + i * nthreads;
-        const int p = q / CP, c8 = q % CP;
-        ld_loff[i] = q < nchunks ? (p * CP + (c8 ^ chunk_swz<CP>(p))) * 16 : -1;
-        // columns past the image edge only feed discarded lanes: clamp instead of branching
-        ld_goff[i] = (q < nchunks ? min(x0c + p, a.W - 1) : 0) * CIN + c8 * 8;
-    }
-    i32x4 pre[LPT];
-    auto fetch_row = [&](int j) {   // input row yc0 + j -> registers
-        const unsigned short* row = in_img + static_cast<int64_t>(yc0 + j) * a.W * CIN;
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) pre[i] = *reinterpret_cast<const i32x4*>(row + ld_goff[i]);
-    };
-    auto store_row = [&](int j) {   // registers -> ring slot j % NSLOT
-        char* dst = ring + (j & (NSLOT - 1)) * rowbytes;
-#pragma unroll
-        for (int i = 0; i < LPT; ++i)
-            if (ld_loff[i] >= 0) *reinterpret_cast<i32x4*>(dst + ld_loff[i]) = pre[i];
-    };
-    for (int j = 0; j < 3; ++j) {
-        fetch_row(j);
-        store_row(j);
-    }
-    __syncthreads();
-
-    // ---- per-lane constants of this wave's pixel tile
-    const int xrel0 = wave * TSTRIDE + r;             // ring column of conv column (tap kx = 0)
-    int boff[3];                                      // byte offset of pixel (xrel0 + kx) chunk 0
-    int bswz[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        boff[kx] = (xrel0 + kx) * PIXB;
-        bswz[kx] = chunk_swz<CP>(xrel0 + kx);
-    }
-    const int xc = x0c + xrel0;                       // conv column of this lane
-    const int xo = PK ? xc / PS : xc;                 // output column of this lane
-    const bool lane_out = (PK ? (r % PS == 0 && r <= 32 - PK) : true) && xo < a.Wo &&
-                          (xo - xo_blk0) < npt * NOUT_T;
-    const int cout_lane = ctg * CTW * 32 + 4 * hh;    // + ct*32 + 8*g + j
-
-    int rx_lo = 0, rx_hi = 0;
-    float rx_l = 0.f;
-    if constexpr (RES) {
-        const int xq = min(xo, a.Wo - 1);
-        rx_lo = a.rlo[xq];
-        rx_hi = a.rhi[xq];
-        rx_l = a.rlerp[xq];
-    }
-
-    float vring[RING > 0 ? RING : 1][CTW][16];
-#pragma unroll
-    for (int i = 0; i < (RING > 0 ? RING : 1); ++i)
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) vring[i][ct][g] = 0.f;
-
-    const char* const wl_lane = wl + lane * 16;
-
-    for (int it = 0; it < nconv; ++it) {
-        const bool have_next = it + 3 < nin;
-        if (have_next) fetch_row(it + 3);
-
-        // ---------------- implicit GEMM for conv row yc0 + it
-        f32x16 acc[CTW];
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[ct][g] = 0.f;
-
-        const char* rowp[3];
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) rowp[ky] = ring + ((it + ky) & (NSLOT - 1)) * rowbytes;
-
-        if constexpr (CIN >= 16) {
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap % 3;
-                const char* pb = rowp[ky] + boff[kx];
-#pragma unroll
-                for (int cc = 0; cc < CIN / 16; ++cc) {
-                    const int kc = tap * (CIN / 16) + cc;
-                    const int c8 = cc * 2 + hh;
-                    const i32x4 b = *reinterpret_cast<const i32x4*>(pb + ((c8 ^ bswz[kx]) << 4));
-#pragma unroll
-                    for (int ct = 0; ct < CTW; ++ct) {
-                        const i32x4 wv = *reinterpret_cast<const i32x4*>(wl_lane + (kc * CTW + ct) * 1024);
-                        acc[ct] = mfma32<DT>(wv, b, acc[ct]);
-                    }
-                }
-            }
-        } else {
-            // CIN == 8: a 16-deep chunk spans two taps; the lane half selects the tap
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) {
-                int tap = 2 * kc + hh;
-                tap = tap > 8 ? 8 : tap;                      // K padded 72 -> 80: weights are zero there
-                const int ky = tap / 3, kx = tap - ky * 3;
-                const char* pb = ring + ((it + ky) & (NSLOT - 1)) * rowbytes + (xrel0 + kx) * PIXB;
-                const i32x4 b = *reinterpret_cast<const i32x4*>(pb);
-#pragma unroll
-                for (int ct = 0; ct < CTW; ++ct) {
-                    const i32x4 wv = *reinterpret_cast<const i32x4*>(wl_lane + (kc * CTW + ct) * 1024);
-                    acc[ct] = mfma32<DT>(wv, b, acc[ct]);
-                }
-            }
-        }
-
-        // ---------------- ReLU6 + horizontal pool sum (lanes) + vertical pool sum (register ring)
-        const int lrow = it;
-        bool emit;
-        int yo;
-        if constexpr (PK > 0) {
-            emit = lrow >= PK - 1 && ((lrow - (PK - 1)) % PS) == 0;
-            yo = yo0 + (lrow - (PK - 1)) / PS;
-        } else {
-            emit = true;
-            yo = yo0 + lrow;
-        }
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct) {
-            float hs[16];
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const float v = relu6f(acc[ct][g]);
-                if constexpr (PK == 4) {
-                    const float t = v + lane_next(v);
-                    hs[g] = t + lane_next(lane_next(t));
-                } else if constexpr (PK == 3) {
-                    const float v1 = lane_next(v);
-                    hs[g] = (v + v1) + lane_next(v1);
-                } else if constexpr (PK == 2) {
-                    hs[g] = v + lane_next(v);
-                } else {
-                    hs[g] = v;
-                }
-            }
-            float tot[16];
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                float s = hs[g];
-                if constexpr (RING > 0) {
-                    float t = vring[0][ct][g];
-#pragma unroll
-                    for (int i = 1; i < RING; ++i) t += vring[i][ct][g];
-                    s = t + s;
-#pragma unroll
-                    for (int i = 0; i + 1 < RING; ++i) vring[i][ct][g] = vring[i + 1][ct][g];
-                    vring[RING - 1][ct][g] = hs[g];
-                }
-                tot[g] = s;
-            }
-            if (emit) {
-                // ---------------- BN (+ residual + BN) + store, 4 consecutive channels at a time
-                constexpr float inv_area = PK ? 1.0f / static_cast<float>(PK * PK) : 1.0f;
-                float yl = 0.f;
-                const unsigned short* sk0 = nullptr;
-                const unsigned short* sk1 = nullptr;
-                if constexpr (RES) {
-                    const int ylo = a.rlo[yo], yhi = a.rhi[yo];
-                    yl = a.rlerp[yo];
-                    const unsigned short* skn = a.skip + static_cast<int64_t>(n) * a.Ss * a.Ss * COUT;
-                    sk0 = skn + static_cast<int64_t>(ylo) * a.Ss * COUT;
-                    sk1 = skn + static_cast<int64_t>(yhi) * a.Ss * COUT;
-                }
-                unsigned short* orow = a.out + ((static_cast<int64_t>(n) * a.Ho + yo) * a.Wo + xo) * COUT;
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    const int c0 = cout_lane + ct * 32 + 8 * g;
-                    const f32x4 mean = *reinterpret_cast<const f32x4*>(a.bn_mean + c0);
-                    const f32x4 inv = *reinterpret_cast<const f32x4*>(a.bn_inv + c0);
-                    const f32x4 beta = *reinterpret_cast<const f32x4*>(a.bn_beta + c0);
-                    float y[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) y[j] = (tot[4 * g + j] * inv_area - mean[j]) * inv[j] + beta[j];
-                    if constexpr (RES) {
-                        if (lane_out) {
-                            const f32x4 tl = unpack4<DT>(*reinterpret_cast<const uint2*>(sk0 + rx_lo * COUT + c0));
-                            const f32x4 tr = unpack4<DT>(*reinterpret_cast<const uint2*>(sk0 + rx_hi * COUT + c0));
-                            const f32x4 bl = unpack4<DT>(*reinterpret_cast<const uint2*>(sk1 + rx_lo * COUT + c0));
-                            const f32x4 br = unpack4<DT>(*reinterpret_cast<const uint2*>(sk1 + rx_hi * COUT + c0));
-                            const f32x4 mean2 = *reinterpret_cast<const f32x4*>(a.bn2_mean + c0);
-                            const f32x4 inv2 = *reinterpret_cast<const f32x4*>(a.bn2_inv + c0);
-                            const f32x4 beta2 = *reinterpret_cast<const f32x4*>(a.bn2_beta + c0);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const float top = tl[j] + (tr[j] - tl[j]) * rx_l;
-                                const float bot = bl[j] + (br[j] - bl[j]) * rx_l;
-                                const float rs = top + (bot - top) * yl;
-                                y[j] = ((y[j] + rs) - mean2[j]) * inv2[j] + beta2[j];
-                            }
-                        }
-                    }
-                    if (lane_out) *reinterpret_cast<uint2*>(orow + c0) = pack4<DT>(y[0], y[1], y[2], y[3]);
-                }
-            }
-        }
-
-        if (have_next) store_row(it + 3);
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------- host side
 struct FusedStage {
-    bool use_rw = false;         // register-weights kernel (rn_stage_rw.hip) covers this stage
-    bool use_c16 = false;        // 16x16x32-tile kernel (rn_conv16.hip) runs this stage instead
-    bool use_c16p = false;       // ... its pooled 128 -> 16 sibling
-    bool use_s5x = false;        // the 64 -> 64 residual stage on 16x16x32 tiles with row-register blocking (rn_stage5x.hip)
-    bool use_s4x = false;        // the 32 -> 64 stage likewise (rn_stage4x.hip)
-    bool use_s6x = false;        // the un-pooled 64 -> 128 stage likewise (rn_stage6x.hip)
-    bool sixth = false;          // conv weights stored / 6, folded BN scale x 6 (pack2_relu6_sixth in the stage's kernel)
-    i32x4* wfrag16 = nullptr;    // its weight fragments
+    Family family = Family::Generic;
+    // the register-weights kernel could run this stage (rn_rw_supported, no RN_FLAG_GENERIC_KERNELS): it then has `rw`, `ptab` and,
+    // where its kernels clamp to [0, 1], `sixth` weights whichever family runs it; the pair, the stage-0 fusion and the tail ask for it
+    bool rw_capable = false;
     RwPlan rw;
-    float* ptab = nullptr;       // folded BN tables for the rw kernel (stage_table) ...
+    GenericPlan gen;
+    bool sixth = false;          // conv weights stored / 6, folded BN scale x 6 (pack2_relu6_sixth in the stage's kernel)
+    i32x4* wfrag = nullptr;      // fragments in the generic order: Generic, RegWeights, the tail, the back end, the round-2 pair
+    i32x4* family_wfrag = nullptr;   // ... in its own family's order (Conv16 .. Row6x), without the constant input channels the handle folds
+    float* ptab = nullptr;       // folded BN tables for every family but Generic (stage_table) ...
     std::vector<float> tab;      // ... and their host copy
     std::vector<float> wq;       // the conv weights every pack of the stage reads (host, HWIO: / 6 when `sixth`, refined rounding)
-    int variant = -1;            // index into the dispatch table
-    int ctw = 1;                 // cout tiles per workgroup
-    int npt = 1;                 // pixel tiles (= waves) per workgroup
-    int n_colblocks = 1;
-    size_t lds_bytes = 0;
-    i32x4* wfrag = nullptr;
+    // the launch arguments, bound at rn_create: all but the bands of a batch size (rows_per_band, n_bands), stamp_buf and the image s0_bgr
+    bool conv16() const { return family == Family::Conv16 || family == Family::Conv16P; }    // `c16` is the live member, else `args`
+    union {
+        StageArgs args{};
+        Conv16Args c16;
+    };
 };
-
-using LaunchFn = int (*)(hipStream_t, const StageArgs&, dim3, dim3, size_t);
-
-template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int CTW>
-int launch_variant(hipStream_t s, const StageArgs& a, dim3 grid, dim3 block, size_t lds) {
-    constexpr auto kern = stage_mfma_kernel<DT, CIN, COUT, PK, PS, RES, CTW>;
-    if (int rc = rn_allow_big_lds<kern>()) return rc;
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-    RN_CHECK_LAUNCH();
-    return RN_OK;
-}
-
-struct Variant {
-    int cin, cout, pk, ps, res, ctw;
-    LaunchFn fn[2];   // [bf16, f16]
-};
-
-#define RN_VARIANT(CIN, COUT, PK, PS, RES, CTW)                                                   \
-    {                                                                                             \
-        CIN, COUT, PK, PS, RES, CTW, {                                                            \
-            launch_variant<RN_DTYPE_BF16, CIN, COUT, PK, PS, RES != 0, CTW>,                      \
-                launch_variant<RN_DTYPE_F16, CIN, COUT, PK, PS, RES != 0, CTW>                    \
-        }                                                                                         \
-    }
-
-const Variant kVariants[] = {
-    RN_VARIANT(8, 32, 4, 1, 0, 1),    // stage 1
-    RN_VARIANT(32, 32, 4, 1, 0, 1),   // stage 2
-    RN_VARIANT(32, 32, 4, 1, 1, 1),   // stage 3 (+ residual)
-    RN_VARIANT(32, 64, 4, 2, 0, 2),   // stage 4
-    RN_VARIANT(64, 64, 4, 2, 1, 2),   // stage 5 (+ residual)
-    RN_VARIANT(64, 128, 0, 1, 0, 2),  // stage 6 (no pool; cout tiles split over 2 workgroups)
-    RN_VARIANT(128, 16, 4, 2, 0, 1),  // stage 7
-    RN_VARIANT(16, 16, 4, 2, 0, 1),   // stage 8
-    RN_VARIANT(16, 16, 4, 2, 1, 1),   // stage 9 (+ residual)
-};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 struct FusedState {
     std::vector<FusedStage> st;
-    // cross-stage fusion: launch_rep[i] = the stage under which the launch that computes stage i reports its time
-    // (== i for a launch of its own)
+    // cross-stage fusion: launch_rep[i] = the stage under which the launch that computes stage i reports its time (== i: its own)
     std::vector<int> launch_rep;
     bool fuse_s0 = false;        // stage 0 is computed inside stage 1's kernel (rn_stage_rw.hip, S0F)
     bool use_tail = false;       // last two stages + head in one launch (rn_tail.hip)
@@ -498,46 +47,29 @@ struct FusedState {
     // batch fills at least half the chip; smaller batches keep the launches that cut an image into bands
     bool use_backend = false;
     bool last_backend = false;   // the last forward pass ran it: stages 6 and 7 were not written
-    // cross-stage fused pair (rn_stage23.hip): stages pair_first, pair_first + 1 run as one launch
+    // cross-stage fused pair (rn_stage23.hip): stages pair_first, pair_first + 1 run as one launch with `pair_args`
     int pair_first = -1;
-    float* pair_ptab = nullptr;  // [5][32]: the first stage's scale, shift | the second stage's scale', shift', scale2
-    bool pair_x16 = false;       // the pair runs on 16x16x32 tiles (rn_stage23x.hip) with the fragments below
-    i32x4* pair_wfrag_a = nullptr;
-    i32x4* pair_wfrag_b = nullptr;
-    // frozen first-BN channels of the 64 -> 64 residual stage (fold16): its index (or -1) and the 16-cout quarters whose
-    // convolution still runs (the channel relabelling of the tensors it touches: rn_handle::node_perm)
+    bool pair_x16 = false;       // the pair runs on 16x16x32 tiles (rn_stage23x.hip) with fragments and a table of its own
+    int pair_frozen = 0;         // how many channels of its on-chip tensor are frozen on this handle
+    Stage23Args pair_args{};     // bound at rn_create like FusedStage::args
+    // frozen first-BN channels of the 64 -> 64 residual stage (fold16): its index (or -1); the convolution of two of its four 16-cout
+    // quarters still runs (live_q; the channel relabelling of the tensors it touches: rn_handle::node_perm)
     int fold5_stage = -1;
-    int fold5_live_q = 4;
-    // constant channels of the stage in front of it (round 6; fold16, prepare_const_channels): the relabelling puts 16 channels
-    // whose 16-BIT STORE is one number for every input into the last cout quarter of that stage -- all of them frozen channels of the residual
-    // stage too, so the same positions of the residual stage's output are constants as well.  Neither kernel computes them: both
-    // tensors are filled once (rn_fused_post_alloc), the residual stage contracts 48 input channels and starts its accumulators
-    // from the constants' contribution.
     // round 6: refined rounding of the 16-bit handles (default; off under RN_FLAG_NO_DITHER and on the legacy comparison arms):
     // `refine` = conv weights rounded with the residual carried from tap to tap (diffuse_taps), `dither` (bf16 only) = the stores of
     // the large stage outputs go through v_cvt_sr_bf16_f32 with a seed that depends on the output row (rn_stage.h)
     bool refine = false;
-    bool dither = false;
     std::vector<char> dither_out;    // per conv stage: its output rows are dithered
     int relabel_stage = -1;          // the residual stage whose channels (and its neighbours') are stored relabelled -- also on the
                                      // arm that computes every channel (same channel order in both arms: same MFMA summation order)
     bool const_layout = false;       // positions 48..63 of the two relabelled tensors hold the constant channels (both arms)
     int const4_proven = 0;           // channels of that stage with a constant 16-bit store on this handle
-    bool const4 = false;             // 16 of them sit in positions 48..63 and are not computed
-    unsigned short const4_val[16] = {};   // their stored values (s4.bn positions 48..63)
-    unsigned short const5_val[16] = {};   // ... and of the residual stage's output (s5.bn2 positions 48..63)
-    unsigned short* const_vals_dev = nullptr;   // [2][16] on the device: const4_val | const5_val (StageArgs::cvals)
-    i32x4* s6_wfrag48 = nullptr;     // the stage behind the residual stage without ITS constant input channels (rn_stage6x_pack48) ...
-    float* s6_cstart = nullptr;      // ... and their contribution [128]
-    float* s5_cstart = nullptr;      // [64] what the 16 constant input channels add to every conv output of the residual stage
-    i32x4* s5_wfrag48 = nullptr;     // the residual stage's fragments without them (rn_stage5x_pack48)
-    float* pair_ptab_x = nullptr;    // rn_stage23x.hip's table: pair_ptab with the first stage's channels in the B ring's order
-    int pair_producer_halves = 2;    // 1: 16 channels of the pair's on-chip tensor are frozen and not computed (Stage23Args)
-    int pair_narrow = 0;             // with it: 1 = the ring holds 16 channels, 2 = eight (24 constant channels; round 6)
-    int pair_frozen = 0;             // how many channels of it are frozen on this handle
-    // stage 0
-    i32x4* s0_wfrag = nullptr;
-    float* s0_ptab = nullptr;
+    // 16 of them sit in positions 48..63 and no kernel computes them (prepare_const_channels): all are frozen channels of the residual
+    // stage too, so its output has constants there as well.  Both tensors are filled once (rn_fused_post_alloc); the stages around
+    // them are told through live_q, cvals, cstart and fragments of 48 input channels.
+    bool const4 = false;
+    unsigned short const_val[2][16] = {};   // their stored values (s4.bn positions 48..63) | those of the residual stage's output (s5.bn2)
+    Stage0Args s0_args{};            // stage 0 as a launch of its own; its fragments and table also feed the fusion into stage 1
 };
 
 }  // namespace
@@ -633,10 +165,10 @@ static int upload16(rn_handle* h, const std::vector<unsigned short>& v, i32x4** 
 // output is the pair's on-chip tensor; the frozen-channel fold relies on its plain rounding)
 static void plan_dither(const rn_handle* h, FusedState* fs) {
     fs->refine = !(h->flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32 | RN_FLAG_NO_DITHER));
-    fs->dither = fs->refine && h->dtype == RN_DTYPE_BF16;
+    const bool dither = fs->refine && h->dtype == RN_DTYPE_BF16;
     fs->dither_out.assign(h->stages.size(), 0);
     const int ns = static_cast<int>(h->stages.size());
-    for (int i = 1; i + 4 < ns && fs->dither; ++i) {
+    for (int i = 1; i + 4 < ns && dither; ++i) {
         const StagePlan& s = h->stages[i];
         const bool pair_first = i + 1 < ns && s.cin == 32 && s.cout == 32 && s.pool_k == 4 && s.pool_s == 1 && s.skip_stage < 0 &&
                                 h->stages[i + 1].cin == 32 && h->stages[i + 1].cout == 32 && h->stages[i + 1].skip_stage == i - 1;
@@ -716,7 +248,7 @@ static void fold16(rn_handle* h, FusedState* fs, const rn_weights* w_in, Relabel
         for (int p = 0; p < 32; ++p) pi[p] = live[p];
         for (int p = 0; p < 32; ++p) pi[32 + p] = frozen[p];
         if (fs->const_layout)
-            for (int p = 0; p < 16; ++p) fs->const4_val[p] = cst_val[pi[48 + p]];
+            for (int p = 0; p < 16; ++p) fs->const_val[0][p] = cst_val[pi[48 + p]];
         rw->permute_couts(r - 1, pi);
         rw->permute_couts(r, pi);
         rw->permute_cins(r, pi);
@@ -724,7 +256,6 @@ static void fold16(rn_handle* h, FusedState* fs, const rn_weights* w_in, Relabel
         fs->relabel_stage = r;
         if (fold_ok) {
             fs->fold5_stage = r;
-            fs->fold5_live_q = 2;
         }
         h->node_perm[h->stages[r - 1].node_bn] = pi;
         h->node_perm[h->stages[r].node_bn2] = pi;
@@ -777,149 +308,192 @@ static int prepare_stage0(rn_handle* h, FusedState* fs, const rn_weights* w) {
         tab[c] = inv / 9.0f / S0_WSCALE;
         tab[8 + c] = rn_bn_shift(ws.beta[c], ws.mean[c], inv);
     }
+    i32x4* d_frag = nullptr;
+    float* d_tab = nullptr;
     int rc;
-    if ((rc = upload16(h, frag, &fs->s0_wfrag)) != RN_OK) return rc;
-    return upload(h, tab.data(), tab.size(), &fs->s0_ptab);
+    if ((rc = upload16(h, frag, &d_frag)) != RN_OK || (rc = upload(h, tab.data(), tab.size(), &d_tab)) != RN_OK) return rc;
+    Stage0Args& a0 = fs->s0_args;
+    a0.wfrag = d_frag;
+    a0.ptab = d_tab;
+    a0.S = h->stages[0].in_side;
+    a0.So = h->stages[0].out_side;
+    const int tiles = (a0.So + S0_TSTRIDE - 1) / S0_TSTRIDE;
+    a0.npt = tiles >= 8 ? 8 : tiles;
+    a0.n_colblocks = (tiles + a0.npt - 1) / a0.npt;
+    return RN_OK;
 }
 
-// conv stage i >= 1: the kernel family that runs it, its launch geometry, its folded BN table and its weight fragments
+// The one family of conv stage i >= 1.  Derived from the two chains this replaces -- six flags set one after the other, then a priority
+// chain over them in the forward pass.  With  rw = rn_rw_supported && !GENERIC_KERNELS  and  row = rw && !PAIR_32X32  they set
+//   use_rw = rw;  use_s6x = row && 6x;  use_c16 = rw && conv16 && !use_s6x;  use_s4x = row && 4x;  use_s5x = row && 5x;  use_c16p = rw && conv16p
+// (4x, 5x, 6x, conv16, conv16p: the families' own *_supported predicates; 5x also needs the skip tensor to be the stage's own input,
+// a first BN output: the kernel interpolates it from its input ring), and the forward pass took the first that held of
+//   use_c16 | use_s5x, use_s4x, use_s6x (in this order: launch_rowreg's) | use_c16p | use_rw | generic.
+// Without rw every flag is false: Generic.  With it, reading the priority chain from the top gives the lines below; RegWeights is what
+// is left.  (The predicates accept disjoint shapes except conv16 / 6x, both the 64 -> 128 stage: the row-blocked kernel wins wherever its
+// geometry allows.)
+static Family choose_family(const rn_handle* h, size_t i, bool rw_capable) {
+    const StagePlan& s = h->stages[i];
+    const bool res = s.skip_stage >= 0;
+    if (!rw_capable) return Family::Generic;
+    const bool row = !(h->flags & RN_FLAG_PAIR_32X32);
+    const bool s6x = row && rn_stage6x_supported(s.cin, s.cout, s.pool_k, res, s.in_side);
+    if (rn_conv16_supported(s.cin, s.cout, s.pool_k, res) && !s6x) return Family::Conv16;
+    if (row && res && rn_stage5x_supported(s.cin, s.cout, s.pool_k, s.pool_s, true, s.in_side, s.skip_side) &&
+        s.skip_stage == static_cast<int>(i) - 1 && h->stages[s.skip_stage].node_bn2 < 0)
+        return Family::Row5x;
+    if (row && rn_stage4x_supported(s.cin, s.cout, s.pool_k, s.pool_s, res, s.in_side)) return Family::Row4x;
+    if (s6x) return Family::Row6x;
+    if (rn_conv16p_supported(s.cin, s.cout, s.pool_k, s.pool_s, res)) return Family::Conv16P;
+    return Family::RegWeights;
+}
+
+// The family's own fragments, and what the launch of stage i is told and rn_create knows without the activation buffers
+// (rn_fused_post_alloc adds those): BN, skip and resize tables, rounding, the family's fragments, table and geometry.
+static int bind_stage_args(rn_handle* h, const FusedState* fs, size_t i, FusedStage* f) {
+    const StagePlan& s = h->stages[i];
+    const int r = fs->relabel_stage - static_cast<int>(i);
+    const float* wq = f->wq.data();
+    // the skip source is the first BN output of the block (network.py:195-196)
+    if (s.skip_stage >= 0 && h->stages[s.skip_stage].node_bn2 >= 0) {
+        rn_set_error("16-bit path: skip source with its own residual is not supported");
+        return RN_E_INVALID;
+    }
+    StageArgs& a = f->args;
+    std::vector<unsigned short> frag;
+    bool (*row_plan)(int, int*, int*, int*) = nullptr;
+    switch (f->family) {
+    case Family::Conv16: rn_conv16_pack(wq, h->dtype, &frag); break;
+    case Family::Conv16P: rn_conv16p_pack(wq, h->dtype, &frag); break;
+    case Family::Row4x: rn_stage4x_pack(wq, h->dtype, &frag), row_plan = rn_stage4x_plan; break;
+    case Family::Row5x: rn_stage5x_pack(wq, h->dtype, &frag), row_plan = rn_stage5x_plan; break;
+    case Family::Row6x: rn_stage6x_pack(wq, h->dtype, &frag), row_plan = rn_stage6x_plan; break;
+    case Family::Generic:
+        a.n_colblocks = f->gen.n_colblocks;
+        a.n_ctg = f->gen.n_ctg;
+        a.npt = f->gen.npt;
+        break;
+    case Family::RegWeights:
+        // `sixth` weights (/ 6, BN scale x 6) are only right for kernels that clamp to [0, 1]: the pool 4/1 variants of the
+        // register-weights kernel and rn_stage4x / 5x.  Its stride-2 (DPP) variants clamp at 6.
+        if (f->sixth && !(s.pool_k == 4 && s.pool_s == 1)) {
+            rn_set_error("16-bit path: stage %zu has weights / 6 but would run a kernel that applies ReLU6 at 6", i);
+            return RN_E_STATE;
+        }
+        a.skipcols = f->rw.skipcols;
+        a.n_colblocks = f->rw.n_colblocks;
+        a.npt = f->rw.npt;
+        a.n_ctg = 1;
+        break;
+    }
+    if (int rc = frag.empty() ? RN_OK : upload16(h, frag, &f->family_wfrag)) return rc;
+    if (f->conv16()) {
+        f->c16 = Conv16Args{nullptr, nullptr, f->family_wfrag, f->ptab, s.in_side, s.in_side, s.out_side, s.out_side, 0, 0,
+                            f->family == Family::Conv16P ? rn_conv16p_colblocks(s.out_side) : rn_conv16_colblocks(s.out_side)};
+        return RN_OK;
+    }
+    a.wfrag = f->wfrag;
+    a.ptab = f->ptab;
+    a.bn_mean = s.bn.mean;
+    a.bn_inv = s.bn.inv;
+    a.bn_beta = s.bn.beta;
+    if (s.skip_stage >= 0) {
+        a.bn2_mean = s.bn2.mean;
+        a.bn2_inv = s.bn2.inv;
+        a.bn2_beta = s.bn2.beta;
+        a.rlo = s.rt.lo;
+        a.rhi = s.rt.hi;
+        a.rlerp = s.rt.lerp;
+        a.Ss = s.skip_side;
+        a.rscale = static_cast<float>(s.skip_side) / static_cast<float>(s.out_side);
+    }
+    a.H = a.W = s.in_side;
+    a.Ho = a.Wo = s.out_side;
+    a.dither = fs->dither_out[i];
+    // (both arms: the constant channels sit in the last quarter of the two relabelled tensors and keep the plain rounding)
+    a.plain_q = fs->const_layout && (r == 0 || r == 1) ? 3 : -1;
+    if (!row_plan) return RN_OK;
+    if (!row_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)) {
+        rn_set_error("stage %zu: no column-block plan for output side %d", i, s.out_side);
+        return RN_E_STATE;
+    }
+    a.wfrag = f->family_wfrag;
+    a.live_q = (f->family == Family::Row5x && static_cast<int>(i) == fs->fold5_stage) ? 2 : 4;
+    return RN_OK;
+}
+
+// conv stage i >= 1: the kernel family that runs it, its folded BN table, its weight fragments and its launch arguments
 static int prepare_stage(rn_handle* h, FusedState* fs, const rn_weights* w, size_t i) {
     StagePlan& s = h->stages[i];
     FusedStage& f = fs->st[i];
-    for (int v = 0; v < kNumVariants; ++v) {
-        const Variant& k = kVariants[v];
-        if (k.cin == s.cin && k.cout == s.cout && k.pk == s.pool_k && (s.pool_k == 0 || k.ps == s.pool_s) &&
-            k.res == (s.skip_stage >= 0 ? 1 : 0)) {
-            f.variant = v;
-            break;
-        }
-    }
-    if (f.variant < 0) {
-        rn_set_error("16-bit path: no kernel variant for stage %zu (cin %d cout %d pool %d/%d res %d)", i, s.cin,
-                     s.cout, s.pool_k, s.pool_s, s.skip_stage >= 0);
+    const bool res = s.skip_stage >= 0;
+    if (!rn_generic_plan(s.cin, s.cout, s.pool_k, s.pool_s, res, s.out_side, &f.gen)) {
+        rn_set_error("16-bit path: no kernel variant for stage %zu (cin %d cout %d pool %d/%d res %d)", i, s.cin, s.cout, s.pool_k, s.pool_s, res);
         return RN_E_INVALID;
     }
-    f.use_rw = rn_rw_supported(s.cin, s.cout, s.pool_k, s.pool_s, s.skip_stage >= 0, s.out_side, s.skip_side,
-                               &f.rw) && !(h->flags & RN_FLAG_GENERIC_KERNELS);
+    f.rw_capable = rn_rw_supported(s.cin, s.cout, s.pool_k, s.pool_s, res, s.out_side, s.skip_side, &f.rw) && !(h->flags & RN_FLAG_GENERIC_KERNELS);
+    f.family = choose_family(h, i, f.rw_capable);
+    if (f.family == Family::Generic && f.gen.lds_bytes > 160 * 1024) {
+        rn_set_error("16-bit path: stage %zu needs %zu bytes of LDS", i, f.gen.lds_bytes);
+        return RN_E_INVALID;
+    }
     // Stages whose kernel pools fp16 ReLU6 outputs on the matrix cores (the pool 4/1 register-weights variants and the
     // cross-stage kernels built on them; rn_stage4x / rn_stage5x) store their conv weights divided by 6: the ReLU6 is
     // then the free [0, 1] clamp of the fp16 conversion (pack2_relu6_sixth) and the folded BN scale carries the 6.
-    const bool want_s4x = f.use_rw && !(h->flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32)) &&
-                          rn_stage4x_supported(s.cin, s.cout, s.pool_k, s.pool_s, s.skip_stage >= 0, s.in_side);
-    const bool want_s5x = f.use_rw && !(h->flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32)) && s.skip_stage >= 0 &&
-                          rn_stage5x_supported(s.cin, s.cout, s.pool_k, s.pool_s, true, s.in_side, s.skip_side) &&
-                          s.skip_stage == static_cast<int>(i) - 1 && h->stages[s.skip_stage].node_bn2 < 0;
-    f.sixth = f.use_rw && ((s.pool_k == 4 && s.pool_s == 1) || want_s4x || want_s5x);
+    f.sixth = f.rw_capable && ((s.pool_k == 4 && s.pool_s == 1) || f.family == Family::Row4x || f.family == Family::Row5x);
     int rc;
-    if (f.use_rw) {
+    if (f.rw_capable) {
         f.tab = stage_table(w->stages[i], w->bn_epsilon, f.sixth);
         if ((rc = upload(h, f.tab.data(), f.tab.size(), &f.ptab)) != RN_OK) return rc;
     }
-    const Variant& k = kVariants[f.variant];
-    f.ctw = k.ctw;
-    const int tstride = tile_stride(s.pool_k, s.pool_s), nout_t = tile_nout(s.pool_k, s.pool_s);
-    const int tiles = (s.out_side + nout_t - 1) / nout_t;
-    const int kc = (9 * s.cin + 15) / 16;
-    // generic kernel: as many pixel tiles per workgroup as fit the LDS next to the weights
-    f.npt = tiles >= 8 ? 8 : tiles;
-    for (;;) {
-        const int ringcols = (f.npt - 1) * tstride + 34;
-        f.lds_bytes = static_cast<size_t>(kc) * f.ctw * 1024 + static_cast<size_t>(NSLOT) * ringcols * s.cin * 2;
-        if (f.lds_bytes <= 160 * 1024 || f.npt == 1) break;
-        --f.npt;
-    }
-    f.n_colblocks = (tiles + f.npt - 1) / f.npt;
-    if (!f.use_rw && f.lds_bytes > 160 * 1024) {
-        rn_set_error("16-bit path: stage %zu needs %zu bytes of LDS", i, f.lds_bytes);
-        return RN_E_INVALID;
-    }
     // the weights every pack of this stage reads: HWIO == [k = tap*cin + c][cout], / 6 for `sixth` stages, with the refined rounding
     // when it is on (every pack below then converts exactly)
-    const int K = 9 * s.cin;
-    f.wq.assign(w->stages[i].kernel, w->stages[i].kernel + static_cast<size_t>(K) * s.cout);
+    f.wq.assign(w->stages[i].kernel, w->stages[i].kernel + static_cast<size_t>(9) * s.cin * s.cout);
     if (f.sixth)
         for (float& v : f.wq) v /= 6.0f;
     if (fs->refine) diffuse_taps(f.wq.data(), s.cin, s.cout, h->dtype);
-    const float* wsrc = f.wq.data();
-    // pack weights: frag[kc][ct][lane][j] = W[k = kc*16 + 8*(lane>>5) + j][cout = ct*32 + (lane&31)]
-    const int ct_n = (s.cout + 31) / 32;
-    std::vector<unsigned short> frag(static_cast<size_t>(kc) * ct_n * 64 * 8, 0);
-    for (int c = 0; c < kc; ++c)
-        for (int t = 0; t < ct_n; ++t)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int kk = c * 16 + 8 * (l >> 5) + j, co = t * 32 + (l & 31);
-                    float v = 0.f;
-                    if (kk < K && co < s.cout) v = wsrc[static_cast<size_t>(kk) * s.cout + co];
-                    frag[((static_cast<size_t>(c) * ct_n + t) * 64 + l) * 8 + j] = rn_to16(v, h->dtype);
-                }
+    std::vector<unsigned short> frag;
+    rn_generic_pack(f.wq.data(), s.cin, s.cout, h->dtype, &frag);
     if ((rc = upload16(h, frag, &f.wfrag)) != RN_OK) return rc;
-    std::vector<unsigned short> f16;
-    // the un-pooled 64 -> 128 stage runs on 16x16x32 tiles (rn_conv16.hip) unless the comparison flags ask for the
-    // one-kernel-family paths
-    if (f.use_rw && rn_conv16_supported(s.cin, s.cout, s.pool_k, s.skip_stage >= 0) && !(h->flags & RN_FLAG_GENERIC_KERNELS)) {
-        rn_conv16_pack(wsrc, h->dtype, &f16);
-        if ((rc = upload16(h, f16, &f.wfrag16)) != RN_OK) return rc;
-        f.use_c16 = true;
-    }
-    if (f.use_rw && !(h->flags & (RN_FLAG_GENERIC_KERNELS | RN_FLAG_PAIR_32X32)) &&
-        rn_stage6x_supported(s.cin, s.cout, s.pool_k, s.skip_stage >= 0, s.in_side)) {
-        rn_stage6x_pack(wsrc, h->dtype, &f16);
-        if ((rc = upload16(h, f16, &f.wfrag16)) != RN_OK) return rc;
-        f.use_s6x = true;
-        f.use_c16 = false;
-    }
-    if (want_s4x) {
-        rn_stage4x_pack(wsrc, h->dtype, &f16);
-        if ((rc = upload16(h, f16, &f.wfrag16)) != RN_OK) return rc;
-        f.use_s4x = true;
-    }
-    if (want_s5x) {
-        // (the skip tensor must be the stage's own input: the kernel interpolates it from its input ring)
-        rn_stage5x_pack(wsrc, h->dtype, &f16);
-        if ((rc = upload16(h, f16, &f.wfrag16)) != RN_OK) return rc;
-        f.use_s5x = true;
-    }
-    if (f.use_rw && rn_conv16p_supported(s.cin, s.cout, s.pool_k, s.pool_s, s.skip_stage >= 0) && !(h->flags & RN_FLAG_GENERIC_KERNELS)) {
-        rn_conv16p_pack(wsrc, h->dtype, &f16);
-        if ((rc = upload16(h, f16, &f.wfrag16)) != RN_OK) return rc;
-        f.use_c16p = true;
-    }
-    return RN_OK;
+    return bind_stage_args(h, fs, i, &f);
 }
 
 // ---- the 16 constant channels (const4) the relabelling put last: neither the stage in front of the residual stage nor the residual
 // stage computes them, when both run on their row-blocked kernels (any other kernel family computes every channel)
 static int prepare_const_channels(rn_handle* h, FusedState* fs) {
     const int r = fs->fold5_stage;
-    if (fs->const4 && !(r >= 1 && fs->st[r - 1].use_s4x && fs->st[r].use_s5x)) fs->const4 = false;
+    if (fs->const4 && !(r >= 1 && r + 1 < static_cast<int>(fs->st.size()) && fs->st[r - 1].family == Family::Row4x && fs->st[r].family == Family::Row5x)) fs->const4 = false;
     if (!fs->const4) return RN_OK;
-    const FusedStage& f5 = fs->st[r];
+    FusedStage &f4 = fs->st[r - 1], &f5 = fs->st[r], &f6 = fs->st[r + 1];
     // the residual stage's output at the positions of the constant channels: y1 = fma(0, sc1', sh1') = sh1' (frozen first BN), the
     // bilinear resize of a constant channel is the constant (its two weights are exact 16-bit numbers that sum to 1, the products are
     // exact in float32), y = fma(v, sc2, y1) -- what rn_stage5x.hip computes for them
     for (int p = 0; p < 16; ++p)
-        fs->const5_val[p] = cv_store(std::fmaf(rn_from16(fs->const4_val[p], h->dtype), f5.tab[2 * 64 + 48 + p], f5.tab[64 + 48 + p]), h->dtype);
-    // the residual stage without the 16 constant input channels (positions 48..63): 15 fragments per cout quarter instead of 18, and
-    // what those channels add to every conv output
-    std::vector<unsigned short> f16;
-    rn_stage5x_pack48(f5.wq.data(), h->dtype, &f16);
+        fs->const_val[1][p] = cv_store(std::fmaf(rn_from16(fs->const_val[0][p], h->dtype), f5.tab[2 * 64 + 48 + p], f5.tab[64 + 48 + p]), h->dtype);
+    unsigned short* d_vals = nullptr;                // [2][16] on the device (StageArgs::cvals)
     int rc;
-    if ((rc = upload16(h, f16, &fs->s5_wfrag48)) != RN_OK) return rc;
-    std::vector<float> cst = const_sum48(f5.wq.data(), 64, fs->const4_val, h->dtype);
-    if ((rc = upload(h, cst.data(), cst.size(), &fs->s5_cstart)) != RN_OK) return rc;
+    if ((rc = upload(h, fs->const_val[0], 32, &d_vals)) != RN_OK) return rc;
+    // a stage without its 16 constant input channels (positions 48..63; the residual stage: 15 fragments per cout quarter instead of
+    // 18): fragments that leave them out -- they replace prepare_stage's, which stay allocated until rn_destroy: whether the fold
+    // holds is known only when every stage has its family -- and what they add to every conv output, the accumulators' start value
+    auto drop_inputs = [&](FusedStage& f, int cout, const unsigned short* vals, auto pack48) {
+        std::vector<unsigned short> f16;
+        pack48(f.wq.data(), h->dtype, &f16);
+        if (int e = upload16(h, f16, &f.family_wfrag)) return e;
+        const std::vector<float> cst = const_sum48(f.wq.data(), cout, vals, h->dtype);
+        float* d_cst = nullptr;
+        if (int e = upload(h, cst.data(), cst.size(), &d_cst)) return e;
+        f.args.wfrag = f.family_wfrag;
+        f.args.cstart = d_cst;
+        return static_cast<int>(RN_OK);
+    };
+    f4.args.live_q = 3;                  // its last cout quarter is constant
+    f4.args.cvals = d_vals;
+    if ((rc = drop_inputs(f5, 64, fs->const_val[0], rn_stage5x_pack48)) != RN_OK) return rc;
+    f5.args.cvals = d_vals + 16;
     // the stage behind it likewise: the residual stage's output channels 48..63 are constants (const5_val)
-    const StagePlan& s6 = h->stages[r + 1];
-    if (fs->st[r + 1].use_s6x && s6.cin == 64 && s6.cout == 128) {
-        rn_stage6x_pack48(fs->st[r + 1].wq.data(), h->dtype, &f16);
-        if ((rc = upload16(h, f16, &fs->s6_wfrag48)) != RN_OK) return rc;
-        cst = const_sum48(fs->st[r + 1].wq.data(), 128, fs->const5_val, h->dtype);
-        if ((rc = upload(h, cst.data(), cst.size(), &fs->s6_cstart)) != RN_OK) return rc;
-    }
-    unsigned short both[32];
-    std::memcpy(both, fs->const4_val, 32);
-    std::memcpy(both + 16, fs->const5_val, 32);
-    return upload(h, both, 32, &fs->const_vals_dev);
+    if (f6.family == Family::Row6x) return drop_inputs(f6, 128, fs->const_val[1], rn_stage6x_pack48);
+    return RN_OK;
 }
 
 // ---- cross-stage fusion: the last two steps of a depth-3 block (network.py:183-203 with block_depth = 3):
@@ -932,7 +506,7 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
         const StagePlan& s2 = h->stages[i + 1];
         auto is3232 = [](const StagePlan& s) { return s.cin == 32 && s.cout == 32 && s.pool_k == 4 && s.pool_s == 1; };
         if (!is3232(s1) || !is3232(s2) || s1.skip_stage >= 0 || s2.skip_stage != static_cast<int>(i) - 1) continue;
-        if (!fs->st[i].use_rw || !fs->st[i + 1].use_rw || !rn_stage23_supported(s1.in_side)) continue;
+        if (!fs->st[i].rw_capable || !fs->st[i + 1].rw_capable || !rn_stage23_supported(s1.in_side)) continue;
         bool feeds_others = false;      // stage i's output must have no other consumer
         for (size_t k = i + 2; k < h->stages.size(); ++k) feeds_others |= h->stages[k].skip_stage == static_cast<int>(i);
         if (feeds_others) continue;
@@ -941,10 +515,30 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
         std::vector<float> tab(5 * 32);
         std::copy(t1.begin(), t1.begin() + 64, tab.begin());
         std::copy(t2.begin(), t2.begin() + 96, tab.begin() + 64);
+        // the launch arguments: what both kernels of the pair are told; the round-2 kernel (rn_stage23.hip) takes the stages' own
+        // fragments and computes every channel ...
+        Stage23Args& fa = fs->pair_args;
+        fa.dither = fs->dither_out[i + 1];
+        fa.rlo = s2.rt.lo;
+        fa.rhi = s2.rt.hi;
+        fa.rlerp = s2.rt.lerp;
+        fa.rscale = static_cast<float>(s2.skip_side) / static_cast<float>(s2.out_side);
+        fa.W = s1.in_side;
+        fa.Wo = s2.out_side;
+        if (!rn_stage23_plan(s1.in_side, &fa.n_cblocks, fa.cb_x0, fa.cb_wo)) {
+            rn_set_error("fused stage pair: no column-block plan for input side %d", s1.in_side);
+            return RN_E_STATE;
+        }
+        float* d_tab = nullptr;
         int rc;
-        if ((rc = upload(h, tab.data(), tab.size(), &fs->pair_ptab)) != RN_OK) return rc;
+        if ((rc = upload(h, tab.data(), tab.size(), &d_tab)) != RN_OK) return rc;
+        fa.wfrag2 = fs->st[i].wfrag;
+        fa.wfrag3 = fs->st[i + 1].wfrag;
+        fa.ptab = d_tab;
+        fa.producer_halves = 2;
         fs->pair_first = static_cast<int>(i);
         if (h->flags & RN_FLAG_PAIR_32X32) return RN_OK;
+        // ... rn_stage23x.hip: fragments and a table of its own, frozen channels left out
         // ---- frozen channels of the pair's on-chip tensor B (the first stage's output).  The epilogue stores
         // to16(fma(H, sc, sh)) with H = a sum of 16 ReLU6 / 6 values in [0, 16]: where |sc| * 16 < 2^-25 |sh| the fma
         // returns sh EXACTLY in float32 for every H the convolution can produce -- the channel is the constant to16(sh)
@@ -972,11 +566,11 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
             }
             fs->pair_frozen = static_cast<int>(frozen.size());
             const bool fold_pair = !(h->flags & RN_FLAG_COMPUTE_FROZEN);
-            fs->pair_producer_halves = (frozen.size() >= 16 && fold_pair) ? 1 : 2;
-            fs->pair_narrow = fs->pair_producer_halves == 1 ? (frozen.size() >= 24 ? 2 : 1) : 0;
-            const int n_fold = fs->pair_narrow == 2 ? 24 : 16;
-            const auto live_pos = [&](int p) { return fs->pair_narrow == 2 ? ((p & 7) < 4 && p < 16) : (p & 7) < 4; };
-            if (fs->pair_producer_halves == 1) {
+            fa.producer_halves = (frozen.size() >= 16 && fold_pair) ? 1 : 2;
+            fa.narrow_b = fa.producer_halves == 1 ? (frozen.size() >= 24 ? 2 : 1) : 0;
+            const int n_fold = fa.narrow_b == 2 ? 24 : 16;
+            const auto live_pos = [&](int p) { return fa.narrow_b == 2 ? ((p & 7) < 4 && p < 16) : (p & 7) < 4; };
+            if (fa.producer_halves == 1) {
                 while (static_cast<int>(frozen.size()) > n_fold) {             // the spare constant channels are computed like live ones
                     live.push_back(frozen.back());
                     frozen.pop_back();
@@ -993,7 +587,7 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
                 tabx[p] = t1[perm[p]];
                 tabx[32 + p] = t1[32 + perm[p]];
             }
-            if (fs->pair_producer_halves == 1) {
+            if (fa.producer_halves == 1) {
                 // row 5: what the 16 frozen channels (B positions (p & 7) >= 4) add to every output of the second conv, channel by
                 // channel (the stored value: the kernels' own store)
                 std::vector<ConstTerm> terms;
@@ -1005,7 +599,8 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
                 const std::vector<float> cst = const_sum(wq[1]->data(), 32, terms, h->dtype);
                 std::copy(cst.begin(), cst.end(), tabx.begin() + 160);
             }
-            if ((rc = upload(h, tabx.data(), tabx.size(), &fs->pair_ptab_x)) != RN_OK) return rc;
+            if ((rc = upload(h, tabx.data(), tabx.size(), &d_tab)) != RN_OK) return rc;
+            fa.ptab = d_tab;
         }
         for (int which = 0; which < 2; ++which) {
             std::vector<unsigned short> f16;
@@ -1017,16 +612,18 @@ static int prepare_pair(rn_handle* h, FusedState* fs) {
                         w6[(static_cast<size_t>(tap) * 32 + ci) * 32 + co] =
                             which == 0 ? wsrc6[(static_cast<size_t>(tap) * 32 + ci) * 32 + perm[co]]        // B's channels = the first conv's couts
                                        : wsrc6[(static_cast<size_t>(tap) * 32 + perm[ci]) * 32 + co];       // ... and the second conv's cins
-            if (which == 1 && fs->pair_producer_halves == 1) {
+            if (which == 1 && fa.producer_halves == 1) {
                 int ring_cin[16];
                 for (int r = 0; r < 16; ++r) ring_cin[r] = perm[8 * (r >> 2) + (r & 3)];       // (eight-channel ring: r < 8)
-                if (fs->pair_narrow == 2)
+                if (fa.narrow_b == 2)
                     rn_stage23x_pack_narrow8(wsrc6, ring_cin, h->dtype, &f16);
                 else
                     rn_stage23x_pack_narrow(wsrc6, ring_cin, h->dtype, &f16);
             } else
                 rn_stage23x_pack(w6.data(), h->dtype, &f16);
-            if ((rc = upload16(h, f16, which ? &fs->pair_wfrag_b : &fs->pair_wfrag_a)) != RN_OK) return rc;
+            i32x4* d_frag = nullptr;
+            if ((rc = upload16(h, f16, &d_frag)) != RN_OK) return rc;
+            (which ? fa.wfrag3 : fa.wfrag2) = d_frag;
         }
         fs->pair_x16 = true;
         return RN_OK;
@@ -1042,20 +639,21 @@ static void plan_fusion(const rn_handle* h, FusedState* fs) {
         // the 8-channel register-weights variant computes stage 0 for its own ring columns
         bool feeds_others = false;
         for (size_t k = 2; k < ns; ++k) feeds_others |= h->stages[k].skip_stage == 0;
-        fs->fuse_s0 = fs->st[1].use_rw && fs->st[1].rw.variant == 0 && h->stages[1].skip_stage < 0 && !feeds_others;
+        FusedStage& f1 = fs->st[1];
+        fs->fuse_s0 = f1.family == Family::RegWeights && f1.rw.variant == 0 && h->stages[1].skip_stage < 0 && !feeds_others;
+        if (fs->fuse_s0) {
+            StageArgs& a = f1.args;      // (s0_bgr is the call's image batch)
+            a.s0_wfrag = fs->s0_args.wfrag;
+            a.s0_ptab = fs->s0_args.ptab;
+            a.s0_S = h->stages[0].in_side;
+            a.s0_private = (h->flags & RN_FLAG_PAIR_32X32) ? 1 : 0;
+            // the shared-ring form of the fused stages 0 + 1 cuts rows into 227-column blocks (eight 29-column tiles - 5 halo columns)
+            if (!a.s0_private && f1.rw.npt == 8) a.n_colblocks = rn_rw_s0sh_colblocks(h->stages[1].out_side);
+        }
     }
     fs->use_tail = !(h->flags & (RN_FLAG_STAGE_LAUNCHES | RN_FLAG_GENERIC_KERNELS)) && rn_tail_supported(h);
-    fs->use_backend = fs->use_tail && !(h->flags & RN_FLAG_PAIR_32X32) && ns >= 5 && rn_backend_supported(h) && fs->st[ns - 4].use_s6x &&
-                      fs->st[ns - 3].use_c16p;
-}
-
-static void plan_launch_rep(const rn_handle* h, FusedState* fs) {
-    const int ns = static_cast<int>(h->stages.size());
-    fs->launch_rep.resize(ns);
-    for (int i = 0; i < ns; ++i) fs->launch_rep[i] = i;
-    if (fs->fuse_s0) fs->launch_rep[0] = 1;
-    if (fs->use_tail) fs->launch_rep[ns - 2] = ns - 1;
-    if (fs->pair_first >= 0) fs->launch_rep[fs->pair_first] = fs->pair_first + 1;
+    fs->use_backend = fs->use_tail && !(h->flags & RN_FLAG_PAIR_32X32) && ns >= 5 && rn_backend_supported(h) &&
+                      fs->st[ns - 4].family == Family::Row6x && fs->st[ns - 3].family == Family::Conv16P;
 }
 
 int rn_fused_prepare(rn_handle* h, const rn_weights* w_in) {
@@ -1073,7 +671,11 @@ int rn_fused_prepare(rn_handle* h, const rn_weights* w_in) {
     if ((rc = prepare_const_channels(h, fs)) != RN_OK) return rc;
     if ((rc = prepare_pair(h, fs)) != RN_OK) return rc;
     plan_fusion(h, fs);
-    plan_launch_rep(h, fs);
+    const int ns = static_cast<int>(h->stages.size());
+    for (int i = 0; i < ns; ++i) fs->launch_rep.push_back(i);
+    if (fs->fuse_s0) fs->launch_rep[0] = 1;
+    if (fs->use_tail) fs->launch_rep[ns - 2] = ns - 1;
+    if (fs->pair_first >= 0) fs->launch_rep[fs->pair_first] = fs->pair_first + 1;
     return RN_OK;
 }
 
@@ -1083,10 +685,10 @@ void rn_fused_frozen_info(const rn_handle* h, int info[4]) {
     info[2] = -1;
     info[3] = 4;
     if (!fs) return;
-    info[0] = fs->pair_x16 && fs->pair_producer_halves == 1 ? (fs->pair_narrow == 2 ? 24 : 16) : 0;
+    info[0] = fs->pair_x16 && fs->pair_args.producer_halves == 1 ? (fs->pair_args.narrow_b == 2 ? 24 : 16) : 0;
     info[1] = fs->pair_frozen;
     info[2] = fs->fold5_stage;
-    info[3] = fs->fold5_stage >= 0 ? fs->fold5_live_q : 4;
+    info[3] = fs->fold5_stage >= 0 ? 2 : 4;
 }
 
 void rn_fused_const_info(const rn_handle* h, int info[4]) {
@@ -1112,16 +714,30 @@ __global__ void fill_channels16_kernel(unsigned short* base, int64_t npix, int c
 }
 }  // namespace
 
-// After alloc_buffers: the constant channels of the two tensors nobody computes (const4) are written once, for every image slot
-// of the handle; the kernels never touch these positions again, rn_tap and the consumers read complete tensors.
+// After alloc_buffers, which fixes the node pointers: the launch arguments get their tensors; the constant channels of the two tensors
+// nobody computes (const4) are written once, for every image slot of the handle; the kernels never touch these positions again, rn_tap
+// and the consumers read complete tensors.
 int rn_fused_post_alloc(rn_handle* h) {
     FusedState* fs = static_cast<FusedState*>(h->fused);
-    if (!fs || !fs->const4) return RN_OK;
+    if (!fs) return RN_OK;
+    auto out_of = [&](const StagePlan& s) { return static_cast<unsigned short*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr); };
+    fs->s0_args.out = out_of(h->stages[0]);
+    for (size_t i = 1; i < h->stages.size(); ++i) {
+        const StagePlan& s = h->stages[i];
+        FusedStage& f = fs->st[i];
+        const bool c16 = f.conv16();
+        (c16 ? f.c16.in : f.args.in) = out_of(h->stages[i - 1]);
+        (c16 ? f.c16.out : f.args.out) = out_of(s);
+        if (!c16 && s.skip_stage >= 0) f.args.skip = static_cast<const unsigned short*>(h->nodes[h->stages[s.skip_stage].node_bn].ptr);
+        if (static_cast<int>(i) == fs->pair_first) fs->pair_args.in = f.args.in;
+        if (static_cast<int>(i) == fs->pair_first + 1 && fs->pair_first >= 0) fs->pair_args.out = f.args.out;
+    }
+    if (!fs->const4) return RN_OK;
     const int r = fs->fold5_stage;
     const StagePlan& s4 = h->stages[r - 1];
     const StagePlan& s5 = h->stages[r];
     struct Job { int node; int side; const unsigned short* vals; };
-    const Job jobs[2] = {{s4.node_bn, s4.out_side, fs->const4_val}, {s5.node_bn2, s5.out_side, fs->const5_val}};
+    const Job jobs[2] = {{s4.node_bn, s4.out_side, fs->const_val[0]}, {s5.node_bn2, s5.out_side, fs->const_val[1]}};
     for (const Job& j : jobs) {
         unsigned short* base = static_cast<unsigned short*>(h->nodes[j.node].ptr);
         if (!base) {
@@ -1155,32 +771,20 @@ int rn_fused_launch_rep(const rn_handle* h, int stage) {
     return fs->launch_rep[stage];
 }
 
-// ---- the launch steps of a forward pass: each builds its kernel's arguments, asks the band picker (rn_bands.h), launches and
-// returns a status.  rn_fused_forward below decides which one runs and records the events.
+// ---- the launch steps of a forward pass: each copies its bound arguments with what depends on the call -- the bands of this batch size
+// from the band picker (rn_bands.h), the clock region, the image pointer -- and launches.  rn_fused_forward decides which one runs.
 namespace {
 
+template <class Args> Args with_bands(Args a, const Bands& b) {      // the copy of bound arguments a launch works on
+    a.rows_per_band = b.rows_per_band;
+    a.n_bands = b.n_bands;
+    return a;
+}
+
 int launch_stage0(const rn_handle* h, const FusedState* fs, const uint8_t* d_bgr, int n) {
-    const StagePlan& s = h->stages[0];
-    Stage0Args a0{};
+    Stage0Args a0 = with_bands(fs->s0_args, rn_bands_stage0(n, fs->s0_args.So, fs->s0_args.n_colblocks));
     a0.bgr = d_bgr;
-    a0.wfrag = fs->s0_wfrag;
-    a0.ptab = fs->s0_ptab;
-    a0.out = static_cast<unsigned short*>(h->nodes[s.node_bn].ptr);
-    a0.S = s.in_side;
-    a0.So = s.out_side;
-    const int tiles = (s.out_side + S0_TSTRIDE - 1) / S0_TSTRIDE;
-    a0.npt = tiles >= 8 ? 8 : tiles;
-    a0.n_colblocks = (tiles + a0.npt - 1) / a0.npt;
-    const Bands b = rn_bands_stage0(n, s.out_side, a0.n_colblocks);
-    a0.rows_per_band = b.rows_per_band;
-    a0.n_bands = b.n_bands;
-    dim3 grid(a0.n_bands * a0.n_colblocks, n);
-    if (h->dtype == RN_DTYPE_BF16)
-        hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_BF16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
-    else
-        hipLaunchKernelGGL(stage0_kernel<RN_DTYPE_F16>, grid, dim3(64 * a0.npt), 0, h->stream, a0);
-    RN_CHECK_LAUNCH();
-    return RN_OK;
+    return rn_stage0_launch(h->dtype, h->stream, a0, n);
 }
 
 // stage 6 .. head in one launch
@@ -1188,9 +792,9 @@ int launch_backend(rn_handle* h, const FusedState* fs, int n, float* d_probs, in
     const size_t ns = h->stages.size();
     HeadArgs head;
     rn_fill_head_args(h, &head);
-    const bool k48_6 = fs->s6_cstart && static_cast<int>(ns) - 4 == fs->fold5_stage + 1;
-    return rn_backend_launch(h, k48_6 ? fs->s6_wfrag48 : fs->st[ns - 4].wfrag16, fs->st[ns - 4].ptab, k48_6 ? fs->s6_cstart : nullptr,
-                             fs->st[ns - 3].wfrag16, fs->st[ns - 3].ptab, fs->st[ns - 2].wfrag, fs->st[ns - 1].wfrag, head, n, d_probs, d_ids);
+    const StageArgs& a6 = fs->st[ns - 4].args;      // (plan_fusion sets use_backend only where stage 6 is Row6x, stage 7 Conv16P)
+    const Conv16Args& a7 = fs->st[ns - 3].c16;
+    return rn_backend_launch(h, a6.wfrag, a6.ptab, a6.cstart, a7.wfrag, a7.ptab, fs->st[ns - 2].wfrag, fs->st[ns - 1].wfrag, head, n, d_probs, d_ids);
 }
 
 // the last two stages (i, i + 1), the flatten, the dense head, softmax and argmax in one launch
@@ -1200,31 +804,9 @@ int launch_tail(rn_handle* h, const FusedState* fs, size_t i, int n, float* d_pr
     return rn_tail_launch(h, fs->st[i].wfrag, fs->st[i + 1].wfrag, head, n, d_probs, d_ids);
 }
 
-// both stages of the pair (i, i + 1) in one launch
-int launch_pair(const rn_handle* h, const FusedState* fs, size_t i, int n) {
-    const StagePlan &prev = h->stages[i - 1], &s = h->stages[i], &s2 = h->stages[i + 1];
-    Stage23Args fa{};
-    fa.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
-    fa.out = static_cast<unsigned short*>(h->nodes[s2.node_bn2].ptr);
-    fa.wfrag2 = fs->pair_x16 ? fs->pair_wfrag_a : fs->st[i].wfrag;
-    fa.wfrag3 = fs->pair_x16 ? fs->pair_wfrag_b : fs->st[i + 1].wfrag;
-    fa.ptab = fs->pair_x16 ? fs->pair_ptab_x : fs->pair_ptab;
-    fa.producer_halves = fs->pair_x16 ? fs->pair_producer_halves : 2;
-    fa.dither = fs->dither_out[i + 1];
-    fa.narrow_b = fa.producer_halves == 1 ? fs->pair_narrow : 0;
-    fa.rlo = s2.rt.lo;
-    fa.rhi = s2.rt.hi;
-    fa.rlerp = s2.rt.lerp;
-    fa.rscale = static_cast<float>(s2.skip_side) / static_cast<float>(s2.out_side);
-    fa.W = s.in_side;
-    fa.Wo = s2.out_side;
-    if (!rn_stage23_plan(s.in_side, &fa.n_cblocks, fa.cb_x0, fa.cb_wo)) {
-        rn_set_error("fused stage pair: no column-block plan for input side %d", s.in_side);
-        return RN_E_STATE;
-    }
-    const Bands b = rn_bands_pair(n, h->n_cu, s2.out_side, fa.n_cblocks);
-    fa.rows_per_band = b.rows_per_band;
-    fa.n_bands = b.n_bands;
+// both stages of the pair in one launch
+int launch_pair(const rn_handle* h, const FusedState* fs, int n) {
+    Stage23Args fa = with_bands(fs->pair_args, rn_bands_pair(n, h->n_cu, fs->pair_args.Wo, fs->pair_args.n_cblocks));
     if (fs->pair_x16) fa.stamp_buf = rn_clock_region("stages 2+3", static_cast<size_t>(fa.n_bands) * fa.n_cblocks * n);
 #ifdef RN_ROUND2_ARMS
     return fs->pair_x16 ? rn_stage23x_launch(h->dtype, h->stream, fa, n) : rn_stage23_launch(h->dtype, h->stream, fa, n);
@@ -1234,125 +816,31 @@ int launch_pair(const rn_handle* h, const FusedState* fs, size_t i, int n) {
 #endif
 }
 
-// what every kernel of a single stage i >= 1 is told: input and output tensor, BN, skip and resize tables, rounding
-int fill_stage_args(const rn_handle* h, const FusedState* fs, size_t i, StageArgs* out) {
-    const StagePlan &prev = h->stages[i - 1], &s = h->stages[i];
-    StageArgs& a = *out;
-    a.in = static_cast<const unsigned short*>(h->nodes[prev.node_bn2 >= 0 ? prev.node_bn2 : prev.node_bn].ptr);
-    a.out = static_cast<unsigned short*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr);
-    a.wfrag = fs->st[i].wfrag;
-    a.bn_mean = s.bn.mean;
-    a.bn_inv = s.bn.inv;
-    a.bn_beta = s.bn.beta;
-    if (s.skip_stage >= 0) {
-        const StagePlan& sk = h->stages[s.skip_stage];
-        // the skip source is the first BN output of the block (network.py:195-196)
-        if (sk.node_bn2 >= 0) {
-            rn_set_error("16-bit path: skip source with its own residual is not supported");
-            return RN_E_INVALID;
-        }
-        a.skip = static_cast<const unsigned short*>(h->nodes[sk.node_bn].ptr);
-        a.bn2_mean = s.bn2.mean;
-        a.bn2_inv = s.bn2.inv;
-        a.bn2_beta = s.bn2.beta;
-        a.rlo = s.rt.lo;
-        a.rhi = s.rt.hi;
-        a.rlerp = s.rt.lerp;
-        a.Ss = s.skip_side;
-        a.rscale = static_cast<float>(s.skip_side) / static_cast<float>(s.out_side);
-    }
-    a.H = a.W = s.in_side;
-    a.Ho = a.Wo = s.out_side;
-    a.dither = fs->dither_out[i];
-    a.plain_q = -1;
-    // (both arms: the constant channels sit in the last quarter of the two relabelled tensors and keep the plain rounding)
-    if (fs->const_layout && (static_cast<int>(i) == fs->relabel_stage || static_cast<int>(i) + 1 == fs->relabel_stage)) a.plain_q = 3;
-    return RN_OK;
-}
-
-// rn_conv16 (the un-pooled 64 -> 128 stage) and, `pooled`, rn_conv16p (128 -> 16 with avg-pool 4/2)
-int launch_conv16(const rn_handle* h, const FusedState* fs, size_t i, const StageArgs& a, int n, bool pooled) {
-    const StagePlan& s = h->stages[i];
-    Conv16Args ca{};
-    ca.in = a.in;
-    ca.out = a.out;
-    ca.wfrag = fs->st[i].wfrag16;
-    ca.ptab = fs->st[i].ptab;
-    ca.H = ca.W = s.in_side;
-    ca.Ho = ca.Wo = s.out_side;
-    ca.n_colblocks = pooled ? rn_conv16p_colblocks(s.out_side) : rn_conv16_colblocks(s.out_side);
-    const Bands b = rn_bands_conv16(n, h->n_cu, s.out_side, ca.n_colblocks, pooled ? rn_conv16p_wgs_per_cu(s.out_side) : 2, pooled);
-    ca.rows_per_band = b.rows_per_band;
-    ca.n_bands = b.n_bands;
+// rn_conv16 (the un-pooled 64 -> 128 stage) and its pooled sibling rn_conv16p (128 -> 16 with avg-pool 4/2)
+int launch_conv16(const rn_handle* h, const FusedStage& f, int n) {
+    const bool pooled = f.family == Family::Conv16P;
+    const Bands b = rn_bands_conv16(n, h->n_cu, f.c16.Ho, f.c16.n_colblocks, pooled ? rn_conv16p_wgs_per_cu(f.c16.Ho) : 2, pooled);
+    const Conv16Args ca = with_bands(f.c16, b);
     return pooled ? rn_conv16p_launch(h->dtype, h->stream, ca, n) : rn_conv16_launch(h->dtype, h->stream, ca, n);
 }
 
 // the row-register kernels: rn_stage4x (32 -> 64), rn_stage5x (64 -> 64 residual), rn_stage6x (64 -> 128)
-int launch_rowreg(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, int n) {
-    const StagePlan& s = h->stages[i];
-    const FusedStage& f = fs->st[i];
-    a.wfrag = f.wfrag16;
-    a.ptab = f.ptab;
-    const bool planned = f.use_s5x   ? rn_stage5x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
-                         : f.use_s4x ? rn_stage4x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo)
-                                     : rn_stage6x_plan(s.out_side, &a.n_cb, a.cb_xo0, a.cb_wo);
-    if (!planned) {
-        rn_set_error("stage %zu: no column-block plan for output side %d", i, s.out_side);
-        return RN_E_STATE;
-    }
-    const Bands b = rn_bands_rowreg(n, h->n_cu, s.out_side, a.n_cb, s.pool_k != 0);
-    a.rows_per_band = b.rows_per_band;
-    a.n_bands = b.n_bands;
+int launch_rowreg(const rn_handle* h, const FusedStage& f, size_t i, int n) {
+    StageArgs a = with_bands(f.args, rn_bands_rowreg(n, h->n_cu, f.args.Ho, f.args.n_cb, h->stages[i].pool_k != 0));
     char what[32];
     snprintf(what, sizeof what, "stage %d", static_cast<int>(i));
     a.stamp_buf = rn_clock_region(what, static_cast<size_t>(a.n_bands) * a.n_cb * n);
-    a.live_q = (f.use_s5x && static_cast<int>(i) == fs->fold5_stage) ? fs->fold5_live_q : 4;
-    if (fs->const4 && f.use_s4x && static_cast<int>(i) + 1 == fs->fold5_stage) {      // its last cout quarter is constant
-        a.live_q = 3;
-        a.cvals = fs->const_vals_dev;
-    }
-    if (fs->s6_cstart && f.use_s6x && static_cast<int>(i) == fs->fold5_stage + 1) {
-        a.wfrag = fs->s6_wfrag48;
-        a.cstart = fs->s6_cstart;
-    }
-    if (fs->const4 && f.use_s5x && static_cast<int>(i) == fs->fold5_stage) {
-        a.wfrag = fs->s5_wfrag48;
-        a.cstart = fs->s5_cstart;
-        a.cvals = fs->const_vals_dev + 16;
-    }
-    return f.use_s5x   ? rn_stage5x_launch(h->dtype, h->stream, a, n)
-           : f.use_s4x ? rn_stage4x_launch(h->dtype, h->stream, a, n)
-                       : rn_stage6x_launch(h->dtype, h->stream, a, n);
+    if (f.family == Family::Row5x) return rn_stage5x_launch(h->dtype, h->stream, a, n);
+    if (f.family == Family::Row4x) return rn_stage4x_launch(h->dtype, h->stream, a, n);
+    return rn_stage6x_launch(h->dtype, h->stream, a, n);
 }
 
 // the register-weights kernels (rn_stage_rw.hip); stage 1 computes stage 0 too when the handle fuses them
-int launch_regweights(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, const uint8_t* d_bgr, int n) {
+int launch_regweights(const rn_handle* h, const FusedState* fs, size_t i, const uint8_t* d_bgr, int n) {
     const StagePlan& s = h->stages[i];
     const FusedStage& f = fs->st[i];
-    // `sixth` weights (/ 6, BN scale x 6) are only right for kernels that clamp to [0, 1]: the pool 4/1 variants of the
-    // register-weights kernel and rn_stage4x / 5x (launch_rowreg).  Its stride-2 (DPP) variants clamp at 6.
-    if (f.sixth && !(s.pool_k == 4 && s.pool_s == 1)) {
-        rn_set_error("16-bit path: stage %zu has weights / 6 but would run a kernel that applies ReLU6 at 6", i);
-        return RN_E_STATE;
-    }
-    if (i == 1 && fs->fuse_s0) {
-        a.s0_bgr = d_bgr;
-        a.s0_wfrag = fs->s0_wfrag;
-        a.s0_ptab = fs->s0_ptab;
-        a.s0_S = h->stages[0].in_side;
-        a.s0_private = (h->flags & RN_FLAG_PAIR_32X32) ? 1 : 0;
-    }
-    a.ptab = f.ptab;
-    a.skipcols = f.rw.skipcols;
-    a.n_colblocks = f.rw.n_colblocks;
-    // the shared-ring form of the fused stages 0 + 1 cuts rows into 227-column blocks (eight 29-column tiles minus the
-    // 5 halo columns of the last one)
-    if (a.s0_bgr && !a.s0_private && f.rw.variant == 0 && f.rw.npt == 8) a.n_colblocks = rn_rw_s0sh_colblocks(s.out_side);
-    a.npt = f.rw.npt;
-    a.n_ctg = 1;
-    const Bands b = rn_bands_rw(n, h->n_cu, s.out_side, a.n_colblocks, f.rw.wgs_per_cu, s.pool_k, s.pool_s);
-    a.rows_per_band = b.rows_per_band;
-    a.n_bands = b.n_bands;
+    StageArgs a = with_bands(f.args, rn_bands_rw(n, h->n_cu, s.out_side, f.args.n_colblocks, f.rw.wgs_per_cu, s.pool_k, s.pool_s));
+    if (i == 1 && fs->fuse_s0) a.s0_bgr = d_bgr;
     dim3 grid(a.n_bands * a.n_colblocks, n);
     char what[32];
     snprintf(what, sizeof what, a.s0_bgr ? "stages 0+%zu" : "stage %zu", i);
@@ -1360,17 +848,9 @@ int launch_regweights(const rn_handle* h, const FusedState* fs, size_t i, StageA
     return rn_rw_launch(f.rw, h->dtype, h->stream, a, grid);
 }
 
-int launch_generic(const rn_handle* h, const FusedState* fs, size_t i, StageArgs a, int n) {
-    const StagePlan& s = h->stages[i];
-    const FusedStage& f = fs->st[i];
-    a.n_colblocks = f.n_colblocks;
-    a.n_ctg = ((s.cout + 31) / 32) / f.ctw;
-    a.npt = f.npt;
-    const Bands b = rn_bands_generic(n, s.out_side, a.n_colblocks * a.n_ctg);
-    a.rows_per_band = b.rows_per_band;
-    a.n_bands = b.n_bands;
-    dim3 grid(a.n_bands * a.n_colblocks * a.n_ctg, n);
-    return kVariants[f.variant].fn[h->dtype == RN_DTYPE_BF16 ? 0 : 1](h->stream, a, grid, dim3(64 * f.npt), f.lds_bytes);
+int launch_generic(const rn_handle* h, const FusedStage& f, int n) {
+    const StageArgs a = with_bands(f.args, rn_bands_generic(n, f.args.Ho, f.args.n_colblocks * f.args.n_ctg));
+    return rn_generic_launch(f.gen, h->dtype, h->stream, a, n);
 }
 
 }  // namespace
@@ -1416,22 +896,19 @@ int rn_fused_forward(rn_handle* h, const uint8_t* d_bgr, const float* d_rgb, int
         }
         if (static_cast<int>(i) == fs->pair_first) {
             event(i);
-            if ((rc = launch_pair(h, fs, i, n)) != RN_OK) return rc;
+            if ((rc = launch_pair(h, fs, n)) != RN_OK) return rc;
             event(++i);
             continue;
         }
-        StageArgs a{};
-        if ((rc = fill_stage_args(h, fs, i, &a)) != RN_OK) return rc;
-        if (f.use_c16)
-            rc = launch_conv16(h, fs, i, a, n, false);
-        else if (f.use_s5x || f.use_s4x || f.use_s6x)
-            rc = launch_rowreg(h, fs, i, a, n);
-        else if (f.use_c16p)
-            rc = launch_conv16(h, fs, i, a, n, true);
-        else if (f.use_rw)
-            rc = launch_regweights(h, fs, i, a, d_bgr, n);
-        else
-            rc = launch_generic(h, fs, i, a, n);
+        switch (f.family) {
+        case Family::Conv16:
+        case Family::Conv16P: rc = launch_conv16(h, f, n); break;
+        case Family::Row4x:
+        case Family::Row5x:
+        case Family::Row6x: rc = launch_rowreg(h, f, i, n); break;
+        case Family::RegWeights: rc = launch_regweights(h, fs, i, d_bgr, n); break;
+        case Family::Generic: rc = launch_generic(h, f, n); break;
+        }
         if (rc != RN_OK) return rc;
         event(i);
     }

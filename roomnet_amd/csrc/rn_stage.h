@@ -182,7 +182,7 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
 
 __device__ __forceinline__ float relu6f(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, 6.f); }
 
-// ---- stage-0 operands (stage0_kernel in rn_fused.hip and the stage-0 fusion of stage_rw_kernel use the same sequence)
+// ---- stage-0 operands (stage0_kernel in rn_generic.hip and the stage-0 fusion of stage_rw_kernel use the same sequence)
 // Stage 0 is the one stage whose input is EXACT in 16 bits: the uint8 pixel values themselves.  The pre-processing
 // ((x / 255.) * 2) - 1 of network.py:129 is folded into the weights and a per-cout constant,
 //     conv(x') = sum w (2 x / 255 - 1) = sum (2 w / 255) x - sum w,
@@ -293,6 +293,18 @@ __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N <= 63, "vmcnt range");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+
+// ------------------------------------------------------------------------ stage 0 as a launch of its own (rn_generic.hip)
+constexpr int S0_CO = 8;
+constexpr int S0_TSTRIDE = 29;      // output columns per 32-column tile: 32 - (3 - 1) - 1
+struct Stage0Args {
+    const uint8_t* bgr;             // [N, S, S, 3]
+    const i32x4* wfrag;             // [3 (ky)][64 lanes] A fragments, 8 x fp16: cout rows 0..7 hi, 8..15 lo
+    const float* ptab;              // [2][8] folded BN: scale (inv / 9 / 2^8), shift
+    unsigned short* out;            // [N, So, So, 8]
+    int S, So;
+    int rows_per_band, n_bands, n_colblocks, npt;
+};
 
 // ------------------------------------------------------------------------ MFMA stage
 struct StageArgs {

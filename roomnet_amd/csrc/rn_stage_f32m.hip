@@ -8,7 +8,7 @@
 // differs from the per-node path (within the 1e-4-of-abs-max per-node tolerance of BASELINE config 2; tests/test_hip_f32.py).
 // The per-node path stays what RN_FLAG_TAPS handles run: every graph node tappable.
 //
-// Kernel: the row-streaming implicit GEMM of stage_mfma_kernel (rn_fused.hip) with v_mfma_f32_32x32x2_f32 -- fp32 in, fp32
+// Kernel: the row-streaming implicit GEMM of stage_mfma_kernel (rn_generic.hip) with v_mfma_f32_32x32x2_f32 -- fp32 in, fp32
 // accumulate, bitwise an fmaf chain, 64 FLOP / clock / SIMD = 1/16 of the bf16 rate (MI355X_MICROARCH.md): the stage is bound by
 // the matrix pipe, not by memory (fp32 is priced against the 157 TFLOP/s matrix-fp32 roofline).
 //   * workgroup = image x band of output rows x block of columns x group of 32 couts; one wave = one tile of 32 conv columns;

@@ -321,7 +321,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     };
 
     // ---- stage-0 fusion (S0F): this wave computes stage 0 for its own 34 ring columns, one row per call, on the matrix
-    // cores with the im2col in registers exactly like stage0_kernel (rn_fused.hip; same instruction sequence, so the
+    // cores with the im2col in registers exactly like stage0_kernel (rn_generic.hip; same instruction sequence, so the
     // ring holds bit for bit what the two-launch path reads back from HBM).  34 output columns = 36 conv columns = two
     // 32-column MFMA tiles: tile 0 at the ring origin gives output columns 0..28 (conv column 31 of a tile is not
     // computable: its right neighbour pixel sits in the other half-wave), tile 1 at +29 gives 29..33.

@@ -6,7 +6,7 @@
 //
 // One 256-thread workgroup per image.  The stage input (and residual skip tensor) is staged in LDS once; each wave
 // streams the conv rows of its share of pooled rows through the matrix cores exactly like the generic stage kernel
-// (stage_mfma_kernel, rn_fused.hip: same MFMA sequence, same DPP / register-ring pooling order, same un-folded BN
+// (stage_mfma_kernel, rn_generic.hip: same MFMA sequence, same DPP / register-ring pooling order, same un-folded BN
 // expression), so the results are those of the three-launch path; the stage outputs are still written to HBM (a few KB:
 // rn_tap keeps working) and kept in LDS for the next phase; wave 0 finishes with the dense chain of head_kernel
 // (rn_kernels_f32.hip) on dense kernels that were staged in LDS while the conv phases ran.

@@ -1025,3 +1025,69 @@ def test_frozen_channel_fold_on_other_checkpoints(weights, parity_images, case):
             assert np.abs(probs - ref["probs"]).max() <= 0.05
         finally:
             e.close()
+
+
+@pytest.mark.parametrize("compute_frozen", [False, True])
+def test_bound_launch_arguments_do_not_go_stale_between_calls(weights, parity_images, compute_frozen):
+    """A handle's launch arguments are filled once at rn_create; a call copies them and sets only what depends on it (the bands of
+    its batch size, the image pointer).  A field that a call left behind in the reused struct would show as a result that depends
+    on the calls before it: one handle runs image buffer A at n = 1, buffer B at ceil(n_cu / 2) images (the back end in one
+    launch), a grad-CAM (the back end split), A at n = 3 and B at n = 1, and every result is, byte for byte, that of a fresh
+    handle given that one call."""
+    import torch
+    n_big = (torch.cuda.get_device_properties(0).multi_processor_count + 1) // 2
+    g = build_graph(6, 224)
+    kw = dict(device=0, dtype="bf16", max_batch=n_big, compute_frozen=compute_frozen)
+    buf = {"A": parity_images[(np.arange(n_big) * 3) % len(parity_images)], "B": parity_images[(np.arange(n_big) * 5 + 1) % len(parity_images)]}
+    assert not np.array_equal(buf["A"][:3], buf["B"][:3])
+    taps = ("s3.bn2", "s5.bn2", "s9.bn2")          # (at the large batch the last one only: the others are ~100 MB as float32)
+
+    def forward(e, d_im, n):
+        d_probs, d_ids = e.device_malloc(n * 6 * 4), e.device_malloc(n * 8)
+        try:
+            e.forward_u8_device(d_im, n, d_probs, d_ids)
+            e.sync()
+            probs, ids = np.empty((n, 6), np.float32), np.empty((n,), np.int64)
+            e.d2h(probs, d_probs)
+            e.d2h(ids, d_ids)
+            return [probs, ids] + [e.tap(t, n) for t in (taps if n <= 3 else taps[-1:])]
+        finally:
+            e.device_free(d_probs)
+            e.device_free(d_ids)
+
+    def upload(e):
+        d = {}
+        for k, v in buf.items():
+            d[k] = e.device_malloc(v.nbytes)
+            e.h2d(d[k], v)
+        return d
+
+    def release(e, d):
+        for p in d.values():
+            e.device_free(p)
+        e.close()
+
+    calls = [("A", 1), ("B", n_big), ("cam", 2), ("A", 3), ("B", 1)]
+    reused = _capi.Engine(g, weights, **kw)
+    d_reused = upload(reused)
+    got = []
+    try:
+        for which, n in calls:
+            if which == "cam":
+                got.append(list(reused.grad_cam(buf["B"][:n])))
+            else:
+                got.append(forward(reused, d_reused[which], n))
+                if n == n_big:
+                    assert reused.launch_groups()[-1] == [6, 7, 8, 9]
+    finally:
+        release(reused, d_reused)
+    for (which, n), have in zip(calls, got):
+        fresh = _capi.Engine(g, weights, **kw)
+        d_fresh = upload(fresh)
+        try:
+            want = list(fresh.grad_cam(buf["B"][:n])) if which == "cam" else forward(fresh, d_fresh[which], n)
+        finally:
+            release(fresh, d_fresh)
+        assert len(have) == len(want)
+        for k, (a, b) in enumerate(zip(have, want)):
+            assert a.tobytes() == b.tobytes(), (which, n, compute_frozen, k)

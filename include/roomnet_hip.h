@@ -252,6 +252,70 @@ RN_API int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images, con
                                  float* probs, int64_t* ids);
 RN_API int rn_sync(rn_handle* h);
 
+/* ---- baseline JPEG files, decoded where each half of the work belongs ------------------------------
+ * cv2.imread of infer.py:81 for the files a camera writes.  A JPEG decode is serial up to the end of its Huffman pass and
+ * per-pixel behind it, so it is split there: the host walks the markers and runs the Huffman pass into int16 coefficients
+ * (rn_jpeg_probe, rn_jpeg_entropy_decode: pure functions, no device, safe on arbitrary bytes), the GPU dequantises, runs the
+ * inverse DCT, upsamples the chroma and converts YCbCr to BGR (rn_jpeg_decode_batch_device), and the full-size BGR image never
+ * exists in host memory.  The pixels are byte for byte those of libjpeg's default decode path (what Pillow and OpenCV return):
+ * jpeg_idct_islow on coef * q (CONST_BITS 13, PASS1_BITS 2: columns descaled by 11, then rows by 18, then range_limit[v & 1023]),
+ * "fancy" triangle upsampling of h2v1 / h2v2 chroma on the component's downsampled extent (plain replication when that is at most
+ * 2 columns wide), the 16-bit fixed-point YCbCr -> RGB tables; roomnet_amd/jpegdec.py restates it in NumPy.
+ *
+ * rn_jpeg_probe           fills *out from the file's headers: size, 1 or 3 components, the luma sampling (1x1, 2x1 or 2x2; chroma
+ *                         1x1), the restart interval, each component's padded block grid (whole MCUs), its quantisation table in
+ *                         natural order, and `supported`.  Supported: SOF0, 8 bits, ONE interleaved Huffman scan of all
+ *                         components, 8-bit tables, grey or component ids 1,2,3, no Adobe APP14 segment, EXIF orientation (APP1,
+ *                         IFD0 tag 0x0112, either byte order) absent or 1, no orientation in an XMP packet.  Anything else that
+ *                         is a JPEG -- progressive, arithmetic, 12-bit, CMYK, 1x2 / 4:1:1, several scans, DNL, orientation 2-8 --
+ *                         is RN_OK with supported = 0 and the reason in `reason`: a file for the general decoder.  RN_E_INVALID:
+ *                         not a JPEG, or its headers are truncated.
+ * rn_jpeg_entropy_decode  the Huffman pass of a supported file (table-lookup decoder; DC prediction, EOB / ZRL, FF 00 stuffing,
+ *                         RSTn with predictor reset): quantised coefficients [component][block_y][block_x][64], natural order,
+ *                         into coeffs; cap = int16 elements available (rn_jpeg_coeff_count of them are written; fewer:
+ *                         RN_E_RANGE).  Truncated scan data, an invalid code, a run past the block, or a dequantised coefficient
+ *                         |coef * q| > RN_JPEG_COEF_LIMIT: RN_E_INVALID, with nothing read or written out of range.
+ * RN_JPEG_COEF_LIMIT      the pixel stage keeps 32-bit intermediates.  Every intermediate of a 1-D pass of jpeg_idct_islow is a
+ *                         linear form of its 8 inputs whose absolute coefficients sum to at most 61214 (an output), so with
+ *                         |coef * q| <= B no value of the column pass exceeds 61214 B + 2^10, its results are at most
+ *                         W = (61214 B + 2^10) >> 11, and no value of the row pass exceeds 61214 W + 2^17: below 2^31 for
+ *                         B <= 1173.  The SIMD code libjpeg-turbo really runs keeps the column pass's results in 16 bits and
+ *                         saturates them, so parity with it is defined while W <= 32767: B <= 1096, the smaller of the two and
+ *                         the limit.  An 8-bit image's own coefficients stay below 1016 + q / 2.
+ * rn_jpeg_decode_batch_device  the pixel stage of n images of individual sizes and samplings: the coefficients (host memory;
+ *                         from rn_host_alloc memory the upload is asynchronous, and the buffers then stay unchanged until
+ *                         rn_sync) go up on the handle's copy stream, then TWO launches for the whole batch on the handle's
+ *                         stream -- inverse DCT into planar Y / Cb / Cr scratch, then upsampling + colour + interleave -- write image
+ *                         i as BGR uint8 HWC, height x width x 3 tightly packed, to d_bgr[i]: the layout
+ *                         rn_crop_resize_batch_u8_device takes.  Asynchronous.  n outside [1, max_batch]: RN_E_RANGE; an image
+ *                         whose info is not a supported one as rn_jpeg_probe fills it: RN_E_INVALID; the handle stays usable.
+ * rn_classify_jpegs       rn_classify_images_u8 for coefficient images: decoded into scratch the handle owns (allocated by the
+ *                         first call, grown as needed, freed by rn_destroy), centre-cropped, resized and classified; probs and
+ *                         ids are bit-identical to rn_classify_images_u8 of the same files decoded by libjpeg.  Synchronous.
+ * rn_jpeg_last_decode_ms  device time of the last call's two pixel-stage launches (events on the handle's stream); waits for them. */
+#define RN_JPEG_COEF_LIMIT 1096
+#define RN_JPEG_REASON_LEN 48
+typedef struct rn_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;                    /* 1 (grey) or 3 (YCbCr)                      */
+    int32_t hsamp, vsamp;             /* luma sampling: 1x1, 2x1 or 2x2             */
+    int32_t restart_interval;         /* MCUs between RSTn markers, 0: none         */
+    int32_t blocks_w[3], blocks_h[3]; /* per component: 8x8 blocks, whole MCUs      */
+    int32_t supported;
+    uint16_t qt[3][64];               /* per component, natural (row-major) order   */
+    char reason[RN_JPEG_REASON_LEN];  /* why supported == 0                         */
+} rn_jpeg_info;
+typedef struct rn_jpeg_image {
+    rn_jpeg_info info;
+    const int16_t* coeffs;            /* host: what rn_jpeg_entropy_decode wrote    */
+} rn_jpeg_image;
+RN_API int rn_jpeg_probe(const uint8_t* data, size_t len, rn_jpeg_info* out);
+RN_API size_t rn_jpeg_coeff_count(const rn_jpeg_info* info);
+RN_API int rn_jpeg_entropy_decode(const uint8_t* data, size_t len, const rn_jpeg_info* info, int16_t* coeffs, size_t cap);
+RN_API int rn_jpeg_decode_batch_device(rn_handle* h, const rn_jpeg_image* ims, int n, uint8_t* const* d_bgr);
+RN_API int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, float* probs, int64_t* ids);
+RN_API int rn_jpeg_last_decode_ms(rn_handle* h, float* ms);
+
 /* Run on a caller-provided hipStream_t (e.g. the framework's current stream)
  * instead of the handle's own; NULL restores the handle's stream (a non-blocking stream,
  * NOT ordered against the HIP null stream).  rn_set_stream_null selects the HIP null

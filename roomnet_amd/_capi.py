@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "rn_features_depth_shape", "rn_features_depth_u8", "rn_features_depth_u8_device",
     "rn_ft_create", "rn_ft_create_depth", "rn_ft_depth", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
+    "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
+    "rn_jpeg_last_decode_ms",
 )
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
@@ -96,6 +98,20 @@ class rn_node_info(C.Structure):
 class rn_ft_config(C.Structure):
     _fields_ = [("learn_rate", C.c_float), ("decay_rate", C.c_float), ("num_steps", C.c_int32), ("start_step", C.c_int32),
                 ("l2_coeff", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float)]
+
+
+RN_JPEG_REASON_LEN = 48
+
+
+class rn_jpeg_info(C.Structure):
+    """What ``rn_jpeg_probe`` reads from a JPEG file's headers (include/roomnet_hip.h: baseline JPEG files)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hsamp", C.c_int32), ("vsamp", C.c_int32),
+                ("restart_interval", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
+                ("supported", C.c_int32), ("qt", (C.c_uint16 * 64) * 3), ("reason", C.c_char * RN_JPEG_REASON_LEN)]
+
+
+class rn_jpeg_image(C.Structure):
+    _fields_ = [("info", rn_jpeg_info), ("coeffs", C.c_void_p)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -254,6 +270,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_ft_create_depth.restype = i32
         lib.rn_ft_depth.argtypes = [vp]
         lib.rn_ft_depth.restype = i32
+    if hasattr(lib, "rn_jpeg_probe"):
+        lib.rn_jpeg_probe.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info)]
+        lib.rn_jpeg_probe.restype = i32
+        lib.rn_jpeg_coeff_count.argtypes = [C.POINTER(rn_jpeg_info)]
+        lib.rn_jpeg_coeff_count.restype = sz
+        lib.rn_jpeg_entropy_decode.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info), vp, sz]
+        lib.rn_jpeg_entropy_decode.restype = i32
+        lib.rn_jpeg_decode_batch_device.argtypes = [vp, C.POINTER(rn_jpeg_image), i32, C.POINTER(vp)]
+        lib.rn_jpeg_decode_batch_device.restype = i32
+        lib.rn_classify_jpegs.argtypes = [vp, C.POINTER(rn_jpeg_image), i32, vp, vp]
+        lib.rn_classify_jpegs.restype = i32
+        lib.rn_jpeg_last_decode_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_jpeg_last_decode_ms.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -354,6 +383,10 @@ class Engine:
     # -- lifetime
     def close(self) -> None:
         if getattr(self, "_h", None):
+            for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0)):      # (jpegs_to_batch's device buffers)
+                if p:
+                    self.lib.rn_device_free(self._h, C.c_void_p(p))
+            self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = 0
             self.lib.rn_destroy(self._h)
             self._h = None
 
@@ -405,6 +438,91 @@ class Engine:
                                                 ids[i:i + m].ctypes.data)
             _check(self.lib, rc, "rn_classify_images_u8")
         return ids, probs
+
+    @staticmethod
+    def _jpeg_images(items):
+        """``[(rn_jpeg_info, coefficient address or int16 array)]`` -> the C array ``rn_jpeg_image[n]`` (the arrays stay the caller's)."""
+        arr = (rn_jpeg_image * len(items))()
+        for k, (info, coeffs) in enumerate(items):
+            arr[k].info = info
+            arr[k].coeffs = coeffs.ctypes.data if isinstance(coeffs, np.ndarray) else int(coeffs)
+        return arr
+
+    def classify_jpegs(self, items) -> Tuple[np.ndarray, np.ndarray]:
+        """``items``: ``[(rn_jpeg_info, coeffs)]`` of supported baseline JPEG files as ``jpegdec.probe`` / ``entropy_decode`` give
+        them (``coeffs``: an int16 array or the address of one, e.g. inside a ``PinnedArray``).  Pixel stage, centre crop, resize
+        and forward pass on the GPU (``rn_classify_jpegs``); returns ``(ids [n], probs [n, C])``, bit-identical to
+        ``classify_images`` of the decoded files."""
+        items = list(items)
+        n = len(items)
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        for i in range(0, n, self.max_batch):
+            arr = self._jpeg_images(items[i:i + self.max_batch])
+            m = len(arr)
+            _check(self.lib, self.lib.rn_classify_jpegs(self.handle, arr, m, probs[i:i + m].ctypes.data, ids[i:i + m].ctypes.data),
+                   "rn_classify_jpegs")
+        return ids, probs
+
+    def jpeg_decode_batch(self, items, repeat: int = 1):
+        """One ``rn_jpeg_decode_batch_device`` call over ``items`` (as ``classify_jpegs`` takes them, at most ``max_batch``): the
+        list of decoded BGR uint8 ``[h, w, 3]`` images, read back (parity tests, timing; ``repeat`` > 1 issues the call that often)."""
+        items = list(items)
+        n = len(items)
+        arr = self._jpeg_images(items)
+        shapes = [(int(info.height), int(info.width), 3) for info, _c in items]
+        d_out = [self.device_malloc(max(1, h * w * 3)) for h, w, _ in shapes]
+        try:
+            ptrs = (C.c_void_p * max(n, 1))(*d_out)
+            for _ in range(max(1, repeat)):
+                _check(self.lib, self.lib.rn_jpeg_decode_batch_device(self.handle, arr, n, ptrs), "rn_jpeg_decode_batch_device")
+            self.sync()
+            outs = []
+            for d, shape in zip(d_out, shapes):
+                a = np.empty(shape, np.uint8)
+                self.d2h(a, d)
+                outs.append(a)
+            return outs
+        finally:
+            for d in d_out:
+                self.device_free(d)
+
+    def jpegs_to_batch(self, items) -> np.ndarray:
+        """``items`` as ``classify_jpegs`` takes them -> their centre-cropped, resized images, uint8 BGR ``[n, S, S, 3]`` on the
+        host: pixel stage (``rn_jpeg_decode_batch_device``) into a device buffer this engine keeps and grows, ONE crop + resize
+        launch (``rn_crop_resize_batch_u8_device``), and only the ``S x S`` results come back."""
+        items = list(items)
+        s = self.graph.im_side
+        out = np.empty((len(items), s, s, 3), np.uint8)
+        if not getattr(self, "_jpeg_dst", 0):
+            self._jpeg_dst, self._jpeg_src, self._jpeg_src_cap = self.device_malloc(self.max_batch * s * s * 3), 0, 0
+        for i in range(0, len(items), self.max_batch):
+            chunk = items[i:i + self.max_batch]
+            m = len(chunk)
+            sizes = [(int(info.height) * int(info.width) * 3 + 15) & ~15 for info, _c in chunk]
+            if sum(sizes) > self._jpeg_src_cap:
+                self.sync()
+                if self._jpeg_src:
+                    self.device_free(self._jpeg_src)
+                self._jpeg_src_cap = sum(sizes) + sum(sizes) // 4
+                self._jpeg_src = self.device_malloc(self._jpeg_src_cap)
+            offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+            ptrs = (C.c_void_p * m)(*[self._jpeg_src + int(o) for o in offs])
+            arr = self._jpeg_images(chunk)
+            _check(self.lib, self.lib.rn_jpeg_decode_batch_device(self.handle, arr, m, ptrs), "rn_jpeg_decode_batch_device")
+            hs = (C.c_int * m)(*[int(info.height) for info, _c in chunk])
+            ws = (C.c_int * m)(*[int(info.width) for info, _c in chunk])
+            _check(self.lib, self.lib.rn_crop_resize_batch_u8_device(self.handle, ptrs, hs, ws, m, C.c_void_p(self._jpeg_dst)),
+                   "rn_crop_resize_batch_u8_device")
+            self.sync()
+            self.d2h(out[i:i + m], self._jpeg_dst)
+        return out
+
+    def jpeg_last_decode_ms(self) -> float:
+        """Device time of the last JPEG batch's pixel stage (``rn_jpeg_last_decode_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_jpeg_last_decode_ms(self.handle, C.byref(ms)), "rn_jpeg_last_decode_ms")
+        return float(ms.value)
 
     def crop_resize(self, im_bgr_u8: np.ndarray) -> np.ndarray:
         """One image through the device crop + resize; returns the ``[S, S, 3]`` uint8 result (parity tests)."""

@@ -724,6 +724,7 @@ extern "C" void rn_destroy(rn_handle* h) {
     rn_f32m_release(h);
     rn_gradcam_release(h);
     rn_bnstats_release(h);
+    rn_jpeg_release(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -798,7 +799,7 @@ extern "C" int rn_forward_u8_device(rn_handle* h, const uint8_t* d_bgr, int n, f
 }
 
 // the tail of the host entry points: the call's probabilities and classes (h->d_probs, h->d_ids) to the caller, one synchronisation
-static int results_to_host(rn_handle* h, int n, float* probs, int64_t* ids) {
+int rn_results_to_host(rn_handle* h, int n, float* probs, int64_t* ids) {
     RN_HIP(hipMemcpyAsync(probs, h->d_probs, static_cast<size_t>(n) * h->num_classes * 4, hipMemcpyDeviceToHost, h->stream));
     RN_HIP(hipMemcpyAsync(ids, h->d_ids, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, h->stream));
     RN_HIP(hipStreamSynchronize(h->stream));
@@ -812,7 +813,7 @@ extern "C" int rn_forward_u8(rn_handle* h, const uint8_t* bgr, int n, float* pro
     const size_t in_bytes = static_cast<size_t>(n) * h->im_side * h->im_side * 3;
     RN_HIP(hipMemcpyAsync(h->d_in_u8, bgr, in_bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    return results_to_host(h, n, probs, ids);
+    return rn_results_to_host(h, n, probs, ids);
 }
 
 // ---- grad-CAM class-evidence maps (rn_gradcam.hip): the forward pass of the call (16-bit handles: the back end as its split
@@ -914,7 +915,7 @@ int gradcam_host(rn_handle* h, const uint8_t* bgr, const float* rgb, int n, cons
     const rn_node_info& li = h->nodes[layer_node].info;
     RN_HIP(hipMemcpyAsync(cam, d_cam, static_cast<size_t>(n) * li.h * li.w * 4, hipMemcpyDeviceToHost, h->stream));
     if (alpha) RN_HIP(hipMemcpyAsync(alpha, d_alpha, static_cast<size_t>(n) * li.c * 4, hipMemcpyDeviceToHost, h->stream));
-    return results_to_host(h, n, probs, ids);
+    return rn_results_to_host(h, n, probs, ids);
 }
 }  // namespace
 
@@ -1169,6 +1170,10 @@ static int ensure_items(rn_handle* h) {
     return RN_OK;
 }
 
+// (for rn_jpeg.hip, whose decoded images take the same crop + resize launch)
+void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side) { center_crop_window(hh, ww, x0, y0, side); }
+int rn_ensure_resize_items(rn_handle* h) { return ensure_items(h); }
+
 extern "C" int rn_crop_resize_batch_u8_device(rn_handle* h, const uint8_t* const* d_srcs, const int* heights, const int* widths, int n,
                                               uint8_t* d_dst_batch) {
     if (!h || !d_srcs || !heights || !widths || !d_dst_batch || n < 1 || n > h->max_batch) {
@@ -1249,7 +1254,7 @@ extern "C" int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images,
     RN_HIP(hipMemcpyAsync(h->d_items, h->items_host.data(), static_cast<size_t>(n) * sizeof(rn_resize_item), hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_launch_resize_batch_u8(h->stream, h->d_items, n, h->d_in_u8, S)) != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    return results_to_host(h, n, probs, ids);
+    return rn_results_to_host(h, n, probs, ids);
 }
 
 extern "C" int rn_forward_f32(rn_handle* h, const float* rgb, int n, float* probs, int64_t* ids) {
@@ -1264,7 +1269,7 @@ extern "C" int rn_forward_f32(rn_handle* h, const float* rgb, int n, float* prob
     const size_t in_bytes = static_cast<size_t>(n) * h->im_side * h->im_side * 3 * 4;
     RN_HIP(hipMemcpyAsync(in_node, rgb, in_bytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = rn_forward_f32_device(h, in_node, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    return results_to_host(h, n, probs, ids);
+    return rn_results_to_host(h, n, probs, ids);
 }
 
 extern "C" int rn_node_count(const rn_handle* h) { return h ? static_cast<int>(h->nodes.size()) : 0; }

@@ -152,6 +152,7 @@ struct rn_handle {
     float* d_feat = nullptr;     // rn_features_u8: float32 staging of s7.bn, [max_batch, S7, S7, 16] (allocated by the first call)
     float* d_feat6 = nullptr;    // rn_features_depth_u8, depth 3: float32 staging of s6.bn, [max_batch, S6, S6, 128] (the same)
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
+    void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch and the batch table (rn_jpeg.hip; allocated by the first call)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
     // couts whose convolution still runs
@@ -217,6 +218,13 @@ void rn_bnstats_release(rn_handle* h);
 // moments of x [npix, cout] on the handle's stream -> the (mean, inv) table of stage `stage`'s first / second BN
 int rn_bnstats_conv(rn_handle* h, int stage, bool second, const float* x, int64_t npix);
 int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
+
+// ---- baseline JPEG pixel stage (rn_jpeg.hip)
+void rn_jpeg_release(rn_handle* h);
+// (rn_api.hip) the centred square window of network.py:137-146, the batched resize's device table, the tail of a host entry point
+void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side);
+int rn_ensure_resize_items(rn_handle* h);
+int rn_results_to_host(rn_handle* h, int n, float* probs, int64_t* ids);
 
 // ---- host helpers (rn_api.hip) -----------------------------------------------------------
 // Makes `dev` the current HIP device and puts the caller's back on scope exit; `ok` = the device could be set.  Without an

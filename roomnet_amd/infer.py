@@ -127,10 +127,20 @@ def _decode_files(fpaths, batch_size, decode_threads=None):
             yield i, fpath, im
 
 
-def _infer_files(nn, fpaths, batch_size, decode_threads=None):
+def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False):
     """Yield ``(index, image_bgr, idx, conf)`` per readable file, in list order.  Files are decoded on a small thread
     pool (Pillow releases the GIL while it decodes) that runs up to two batches ahead of the GPU; the GPU gets the
-    decoded images in batches of ``batch_size``."""
+    decoded images in batches of ``batch_size``.  ``gpu_decode``: ``RoomNet.infer_files`` instead -- baseline JPEG files
+    only pass their Huffman stage on the pool and become pixels on the GPU; ``image_bgr`` is then None (the decoded image
+    never exists on the host); same ids and confidences."""
+    if gpu_decode:
+        ids, probs, ok = nn.infer_files(fpaths, decode_threads=decode_threads, batch_size=batch_size)
+        for i, fpath in enumerate(fpaths):
+            if not ok[i]:
+                print(fpath, '---> unreadable image, skipped')
+                continue
+            yield i, None, int(ids[i]), probs[i][ids[i]]
+        return
     pending = []
 
     def flush():
@@ -157,15 +167,16 @@ def _infer_files(nn, fpaths, batch_size, decode_threads=None):
         yield r
 
 
-def groundtruth_validation(nn, list_fpath=None, batch_size=64):
+def groundtruth_validation(nn, list_fpath=None, batch_size=64, gpu_decode=False):
     """infer.py:41-57, with the list file it reads made an argument (the reference's global is
     commented out, infer.py:28).  Prints and returns accuracy and per-class precision / recall /
-    f-score, computed like ``train.py:146-152``."""
+    f-score, computed like ``train.py:146-152``.  ``gpu_decode``: baseline JPEG files are decoded on the GPU
+    (``RoomNet.infer_files``); same predictions."""
     from sklearn.metrics import accuracy_score, precision_recall_fscore_support
     fpaths, labels, num_fpaths = read_fpaths(list_fpath or INPUT_IMG_PATH_LIST_FILE)
     print('Inferring Images...')
     y_preds, y_truths = [], []
-    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size):
+    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size, gpu_decode=gpu_decode):
         y_preds.append(idx)
         y_truths.append(labels[i])
     acc = accuracy_score(y_truths, y_preds)
@@ -193,12 +204,17 @@ def _overlay_and_write(im, pred_label, pred_conf, out_fpath):
     return imwrite(out_fpath, im)
 
 
-def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64):
+def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
-    returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order."""
+    returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
+    ``gpu_decode`` (with ``overlay=False`` only: the overlay needs the pixels on the host): baseline JPEG files are decoded on
+    the GPU (``RoomNet.infer_files``); the workbook is the same, byte for byte."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
+    if gpu_decode and overlay:
+        raise ValueError("classify_im_dir: gpu_decode=True needs overlay=False (the overlay is drawn on the decoded image, "
+                         "which the GPU decode path never brings to the host)")
     print('Classifying images in', imgs_dir)
     all_im_paths = glob(imgs_dir + '/*')
     out_dir = imgs_dir + '_classified'
@@ -215,7 +231,7 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64):
     writers = ThreadPoolExecutor(max_workers=DECODE_THREADS) if overlay else None
     writing = deque()
     try:
-        for i, im, idx, pred_conf in _infer_files(nn, all_im_paths, batch_size):
+        for i, im, idx, pred_conf in _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode):
             fpath = all_im_paths[i]
             row += 1
             pred_label = CLASS_LABELS[idx]
@@ -240,12 +256,25 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64):
     return xl_fpath
 
 
-def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None):
+def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=False):
     """Re-estimate the model's BN statistics on the images of a directory (``RoomNet.recalibrate_bn``; not in the reference,
     whose statistics only move while it trains, network.py:64-67): the files are decoded as ``classify_im_dir`` decodes them
     and fed in batches of ``batch_size`` (at most the model's ``max_batch``; a last batch of ONE image is dropped: its variance is 0).
-    ``momentum=None``: the statistics become the average over the batches.  Returns the new statistics."""
+    ``momentum=None``: the statistics become the average over the batches.  Returns the new statistics.  ``gpu_decode``: baseline
+    JPEG files are decoded, cropped and resized on the GPU (``RoomNet.prepare_files``); the batches are the same bytes."""
     all_im_paths = sorted(glob(imgs_dir + '/*'))
+
+    def gpu_batches():
+        pending = np.zeros((0, nn.im_side, nn.im_side, 3), np.uint8)
+        for _at, batch, bad in nn.prepare_files(all_im_paths, batch_size=batch_size):
+            for i in bad:
+                print(all_im_paths[i], '---> unreadable image, skipped')
+            pending = np.concatenate([pending, batch], 0)
+            while len(pending) >= batch_size:
+                yield pending[:batch_size]
+                pending = pending[batch_size:]
+        if len(pending) > 1:
+            yield pending
 
     def batches():
         pending = []
@@ -260,18 +289,30 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None):
         if len(pending) > 1:
             yield pending
 
-    return nn.recalibrate_bn(batches(), momentum=momentum)
+    return nn.recalibrate_bn(gpu_batches() if gpu_decode else batches(), momentum=momentum)
 
 
-def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2):
+def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2,
+                        gpu_decode=False):
     """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
     infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
     batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
     features.  ``val_list_fpath``: a second list evaluated after the last step.  ``depth=3`` trains the whole last conv block on
-    cached ``s6.bn`` (1.08 MB per image at 224, against 28 KB at depth 2).  Returns what ``fine_tune`` returns."""
+    cached ``s6.bn`` (1.08 MB per image at 224, against 28 KB at depth 2).  Returns what ``fine_tune`` returns.  ``gpu_decode``:
+    the feature extraction decodes baseline JPEG files on the GPU (``RoomNet.prepare_files``); same features."""
     def features_of(path):
         fpaths, labels, _n = read_fpaths(path)
         feats, kept, pending = [], [], []
+        if gpu_decode:
+            for at, batch, bad in nn.prepare_files(fpaths, batch_size=extract_batch):
+                for i in bad:
+                    print(fpaths[i], '---> unreadable image, skipped')
+                if at:
+                    feats.append(nn.extract_features(batch, depth=depth))
+                    kept.extend(labels[i] for i in at)
+            if not feats:
+                raise ValueError("fine_tune_from_list: no readable image in %r" % path)
+            return np.concatenate(feats, 0), np.asarray(kept, np.int32)
 
         def flush():
             if pending:

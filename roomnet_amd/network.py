@@ -325,6 +325,87 @@ class RoomNet:
             prepared.append(np.ascontiguousarray(im))
         return self.infer(np.stack(prepared, 0))
 
+    def infer_files(self, paths, decode_threads=None, batch_size=64):
+        """Classify image FILES, decoding baseline JPEG on the GPU: ``(ids int64[N], probs float32[N,C], ok bool[N])`` in list
+        order; ``ok[i]`` False (id -1, zero probabilities) marks a file that is not a readable image.  A pool of
+        ``decode_threads`` threads (default ``infer.DECODE_THREADS``, at most 16) reads each file, walks its markers and runs its
+        Huffman pass into a ring of reused page-locked buffers (``roomnet_amd.jpegdec``); dequantisation, inverse DCT, chroma
+        upsampling, colour conversion, crop, resize and the forward pass run on the GPU, ``batch_size`` files (at most
+        ``max_batch``) per call (``rn_classify_jpegs``) while the pool works on the next batch.  Files the split decoder does
+        not take -- progressive, CMYK, rotated by EXIF, damaged, not JPEG at all -- are decoded by ``imageio.imread`` on the same
+        pool and classified by ``infer_images`` in the same call.  Every result equals ``infer_images`` of the ``imread``
+        images bit for bit.  Not in the reference (infer.py:79-82 decodes with ``cv2.imread``)."""
+        paths = list(paths)
+        n = len(paths)
+        ids = np.full((n,), -1, np.int64)
+        probs = np.zeros((n, self.num_classes), np.float32)
+        ok = np.zeros((n,), bool)
+        eng = self._engine() if n else None
+        for lo, loaded in self._file_chunks(paths, batch_size, decode_threads):
+            jp = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "jpeg"]
+            im = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "image"]
+            if jp:
+                a, b = eng.classify_jpegs([(r[1], r[2]) for _i, r in jp])
+                at = [i for i, _r in jp]
+                ids[at], probs[at], ok[at] = a, b, True
+            if im:
+                a, b = eng.classify_images([r[1] for _i, r in im])
+                at = [i for i, _r in im]
+                ids[at], probs[at], ok[at] = a, b, True
+        return ids, probs, ok
+
+    def _file_chunks(self, paths, batch_size, decode_threads=None):
+        """Yield ``(lo, [jpegdec.load_file result of paths[lo + j]])`` chunk by chunk (``batch_size``, at most ``max_batch``, files
+        each): the pool decodes chunk k + 1 into the other half of the coefficient ring while the consumer works on chunk k.  A
+        chunk's coefficient buffers are valid until the consumer asks for the next chunk."""
+        from concurrent.futures import ThreadPoolExecutor
+        from . import jpegdec
+        from .infer import DECODE_THREADS
+        n = len(paths)
+        if not n:
+            return
+        chunk = max(1, min(int(batch_size), self._engine().max_batch))
+        nthreads = max(1, min(16, int(decode_threads or DECODE_THREADS)))
+        ring = getattr(self, "_jpeg_ring", None)
+        if ring is None or len(ring) < 2 * chunk:
+            if ring is not None:
+                ring.close()
+            ring = self._jpeg_ring = jpegdec.CoeffRing(2 * chunk)
+        n_chunks = (n + chunk - 1) // chunk
+        with ThreadPoolExecutor(max_workers=nthreads) as pool:
+            def submit(k):
+                # chunk k decodes into bank k % 2 of the ring: that bank was chunk k - 2's, which the consumer was done with when it asked for chunk k - 1
+                lo = k * chunk
+                return [pool.submit(jpegdec.load_file, paths[i], ring, (k % 2) * chunk + i - lo) for i in range(lo, min(n, lo + chunk))]
+            ahead = submit(0)
+            for k in range(n_chunks):
+                cur, ahead = ahead, (submit(k + 1) if k + 1 < n_chunks else [])
+                yield k * chunk, [f.result() for f in cur]
+
+    def prepare_files(self, paths, decode_threads=None, batch_size=64):
+        """Image files -> the batches ``infer`` takes, decoding baseline JPEG on the GPU: yields ``(indices, batch, unreadable)`` per
+        chunk of ``batch_size`` files: ``batch`` the uint8 BGR ``[m, S, S, 3]`` centre-cropped, resized images of the readable files
+        ``paths[indices]``, ``unreadable`` the indices of the chunk's files that are no readable image -- byte for byte ``center_crop`` + the ``cv2.resize`` restatement of their ``imread`` images.  JPEG
+        files the split decoder takes become pixels, are cropped and resized on the GPU and only the ``S x S`` result comes back;
+        other files are prepared on the host.  For the callers that need a batch and not a classification: ``recalibrate_bn``
+        (its statistics are the whole batch's) and ``extract_features``."""
+        eng = self._engine() if len(paths) else None
+        for lo, loaded in self._file_chunks(list(paths), batch_size, decode_threads):
+            at = [lo + j for j, r in enumerate(loaded) if r is not None]
+            bad = [lo + j for j, r in enumerate(loaded) if r is None]
+            if not at:
+                yield at, np.zeros((0, self.im_side, self.im_side, 3), np.uint8), bad
+                continue
+            batch = np.empty((len(at), self.im_side, self.im_side, 3), np.uint8)
+            live = [r for r in loaded if r is not None]
+            jp = [k for k, r in enumerate(live) if r[0] == "jpeg"]
+            if jp:
+                batch[jp] = eng.jpegs_to_batch([(live[k][1], live[k][2]) for k in jp])
+            for k, r in enumerate(live):
+                if r[0] == "image":
+                    batch[k] = self._batch_from([r[1]], "prepare_files")[0]
+            yield at, batch, bad
+
     def grad_cam(self, im_in, class_ids=None, layer="s6.bn"):
         """Grad-CAM class-evidence maps (not in the reference): where in each image the network saw its class.
         ``im_in`` is an ``[N,S,S,3]`` BGR batch (the feed rules of ``infer``), or one BGR ``[H,W,3]`` image or a list of

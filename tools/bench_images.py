@@ -5,6 +5,9 @@
   python tools/bench_images.py --dir [--threads=T] [H W [N]]    a generated directory of N JPEG files of that size through
         classify_im_dir(overlay=False) and groundtruth_validation (decode on the thread pool, crop + resize + forward on
         the GPU), next to decode alone and to the one-image-at-a-time loop of the reference's caller (infer.py:79-82)
+  python tools/bench_images.py --dir --gpu-decode [--threads=T] [H W [N]]    then, in the same session and on the same files, the
+        gpu_decode=True arm of both drivers (baseline JPEG split: Huffman pass on the pool, pixel stage on the GPU), the host
+        entropy pass alone on one thread, and the device time of the pixel stage per batch; a second line with the ratios
 """
 import contextlib
 import io
@@ -112,7 +115,51 @@ def directory():
           'classify_im_dir(overlay=True) %.1f img/s (overlay + write alone, one thread: %.1f img/s)   '
           'groundtruth_validation %.1f img/s   decode alone, one thread %.1f img/s   one image per call (reference loop) %.1f img/s'
           % (N, W, H, mb, infer.DECODE_THREADS, os.cpu_count() or 1, N / t_dir, N / t_ovl, 1.0 / t_ow, N / t_val, N / t_dec1, 1.0 / t_one))
+    if '--gpu-decode' in sys.argv:
+        gpu_decode_arm(nn, infer, d, lst, paths, N / t_dir, N / t_val, N / t_dec1)
     shutil.rmtree(root, ignore_errors=True)
+
+
+def gpu_decode_arm(nn, infer, d, lst, paths, dir_ips, val_ips, dec1_ips):
+    """The gpu_decode=True arm on the files the default arm has just been timed on (same session, same box)."""
+    from roomnet_amd import jpegdec
+    with open(d + '_classified_results.xls', 'rb') as f:
+        xls_host = f.read()
+    nn.infer_files(paths[:2])                                  # first-use allocations (ring, device scratch) stay out of the times
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):
+        t0 = time.perf_counter()
+        xl = infer.classify_im_dir(nn, d, overlay=False, batch_size=64, gpu_decode=True)
+        t_dir = time.perf_counter() - t0
+        with open(xl, 'rb') as f:
+            same = f.read() == xls_host
+        t0 = time.perf_counter()
+        infer.groundtruth_validation(nn, lst, batch_size=64, gpu_decode=True)
+        t_val = time.perf_counter() - t0
+    # the host's share: file read + marker walk + Huffman pass, one thread, into one reused buffer
+    datas = [open(p, 'rb').read() for p in paths]
+    infos = [jpegdec.probe(b) for b in datas]
+    buf = np.empty(max(jpegdec.coeff_count(i) for i in infos), np.int16)
+    t0 = time.perf_counter()
+    for b in datas:
+        info = jpegdec.probe(b)
+        assert info.supported and jpegdec.entropy_decode_rc(b, info, buf) == 0
+    t_ent = time.perf_counter() - t0
+    # the device's share: the pixel stage of one batch (two launches; events on the handle's stream), median of 5 calls
+    eng = nn._engine()
+    n = min(len(paths), eng.max_batch)
+    items = [jpegdec.entropy_decode(b, i) for b, i in zip(datas[:n], infos[:n])]
+    ms = []
+    for _ in range(5):
+        eng.classify_jpegs(items)
+        ms.append(eng.jpeg_last_decode_ms())
+    ms = sorted(ms)[len(ms) // 2]
+    N_ = len(paths)
+    print('gpu_decode=True, same files, same session: classify_im_dir(overlay=False) %.1f img/s (x%.2f)   groundtruth_validation '
+          '%.1f img/s (x%.2f)   workbook identical: %s   host entropy pass alone, one thread %.1f img/s (x%.2f of the one-thread '
+          'decode)   pixel stage on the device %.3f ms per batch of %d (%.1f us per image)'
+          % (N_ / t_dir, (N_ / t_dir) / dir_ips, N_ / t_val, (N_ / t_val) / val_ips, same, N_ / t_ent, (N_ / t_ent) / dec1_ips, ms, n,
+             1e3 * ms / n))
 
 
 if '--dir' in sys.argv:

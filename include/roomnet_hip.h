@@ -316,6 +316,64 @@ RN_API int rn_jpeg_decode_batch_device(rn_handle* h, const rn_jpeg_image* ims, i
 RN_API int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, float* probs, int64_t* ids);
 RN_API int rn_jpeg_last_decode_ms(rn_handle* h, float* ms);
 
+/* ---- the overlay and the output JPEG, written where the image already is --------------------------
+ * cv2.putText and cv2.imwrite of infer.py:89-93 for an image the GPU holds.  An encode is the decode
+ * above mirrored and splits at the same place: colour conversion, chroma downsampling, forward DCT and quantisation are per pixel
+ * or per block and run on the GPU; only the Huffman pass is serial and runs on the host, on the int16 coefficients the GPU sends
+ * back (1.5 x 2 B per pixel, and no BGR image in host memory).  The file is byte for byte the one libjpeg's default path writes
+ * for quality q at 4:2:0 (what Pillow's save(format="JPEG", quality=q) and cv2.imwrite write): the fixed-point RGB -> YCbCr of
+ * jccolor.c, h2v2_downsample with its alternating bias and expand_right_edge, jpeg_fdct_islow (CONST_BITS 13, PASS1_BITS 2) on
+ * sample - 128, the quantiser sign(c) * ((|c| + 4 q) / (8 q)); roomnet_amd/jpegenc.py restates it in NumPy.  Edge rules: rows are
+ * extended to the luma block grid by their last column BEFORE downsampling, one row is added below only when the height is odd,
+ * each downsampled component is then extended to its block grid by its own last row; luma blocks beyond ceil(w / 8) x
+ * ceil(h / 8) are not transformed: their AC is 0 and their DC is that of the block before them in MCU order.
+ * 32-bit intermediates are exact: |sample - 128| <= 128, a 1-D pass of jpeg_fdct_islow before its descale is a linear form whose
+ * absolute coefficients sum to at most 8 * 8192 * 1.39 < 2^17 (outputs 0 and 4 sum to 8), so the row pass stays below
+ * 128 * 2^17 = 2^24 and its results below 2^13 + 1; the column pass then stays below 2^13 * 2^17 + 2^14 < 2^31.
+ *
+ * rn_jpeg_encode_info     fills *out for a width x height file of quality 1..100 as rn_jpeg_probe would for that file: 3 components,
+ *                         luma 2x2, whole-MCU block grids, libjpeg's scaling of the Annex K tables, supported = 1.  Sizes outside
+ *                         1..65535 or another quality: RN_E_INVALID.
+ * rn_jpeg_encoded_bound   bytes that always suffice for the file of such an info (0 for another info).
+ * rn_jpeg_entropy_encode  writes the whole file into out[0 .. cap): SOI, APP0 (JFIF 1.01), two DQT, SOF0, the four Annex K DHT
+ *                         (DC0, AC0, DC1, AC1), one interleaved SOS, the scan (DC differences per component, ZRL / EOB runs, FF
+ *                         stuffing, the last byte padded with 1-bits, no restart markers), EOI.  coeffs: the layout
+ *                         rn_jpeg_entropy_decode writes.  *len = the file's size; more than cap: RN_E_RANGE with nothing stored
+ *                         past cap.  A DC difference above category 11, an AC value above category 10, or an info that
+ *                         rn_jpeg_encode_info does not fill (grey, other samplings, inconsistent grids): RN_E_INVALID.
+ * rn_jpeg_overlay_batch_device  draws each image's overlays in place, IN ORDER: per pixel of a box and per channel, in float32
+ *                         without contraction, v = v + (colour - v) * coverage, then round-half-even, clamp, store as uint8 --
+ *                         what hershey.put_text computes from the same coverage.  One launch per overlay rank for the whole
+ *                         batch.  The coverage arrays are copied before the call returns.  Asynchronous.
+ * rn_jpeg_encode_batch_device  the same, then the pixel stage of the encode in two launches for the whole batch (colour +
+ *                         padding + downsampling into planar scratch; forward DCT + quantisation), then the coefficients go to
+ *                         `coeffs` on the handle's copy stream (from rn_host_alloc memory that is asynchronous): rn_sync before
+ *                         reading them.  Scratch belongs to the handle, grows as needed and is freed by rn_destroy; back-to-back
+ *                         calls without a sync are fine (the batch tables are double-buffered behind events).
+ *                         n outside [1, max_batch]: RN_E_RANGE.  An info that rn_jpeg_encode_info does not fill, a null image or
+ *                         coefficient pointer, more than RN_JPEG_MAX_OVERLAYS overlays, an empty box, one not inside the image or
+ *                         one without coverage: RN_E_INVALID.  In both cases nothing is enqueued and the handle stays usable.
+ * rn_jpeg_last_encode_ms  device time of the last rn_jpeg_encode_batch_device call's launches; waits for them. */
+#define RN_JPEG_MAX_OVERLAYS 8
+typedef struct rn_jpeg_overlay {      /* one putText line, rasterised by the caller */
+    int32_t x, y, w, h;               /* box inside the image                      */
+    uint8_t color_bgr[3];
+    const float* coverage;            /* host, [h, w] float32 in [0, 1]            */
+} rn_jpeg_overlay;
+typedef struct rn_jpeg_source {
+    uint8_t* d_bgr;                   /* device, HWC, tightly packed: what rn_jpeg_decode_batch_device wrote */
+    rn_jpeg_info info;                /* rn_jpeg_encode_info of its size           */
+    const rn_jpeg_overlay* overlays;  /* applied IN ORDER, in place                */
+    int32_t n_overlays;
+    int16_t* coeffs;                  /* host (rn_host_alloc: the download is asynchronous) */
+} rn_jpeg_source;
+RN_API int rn_jpeg_encode_info(int width, int height, int quality, rn_jpeg_info* out);
+RN_API size_t rn_jpeg_encoded_bound(const rn_jpeg_info* info);
+RN_API int rn_jpeg_entropy_encode(const rn_jpeg_info* info, const int16_t* coeffs, uint8_t* out, size_t cap, size_t* len);
+RN_API int rn_jpeg_overlay_batch_device(rn_handle* h, const rn_jpeg_source* srcs, int n);
+RN_API int rn_jpeg_encode_batch_device(rn_handle* h, const rn_jpeg_source* srcs, int n);
+RN_API int rn_jpeg_last_encode_ms(rn_handle* h, float* ms);
+
 /* Run on a caller-provided hipStream_t (e.g. the framework's current stream)
  * instead of the handle's own; NULL restores the handle's stream (a non-blocking stream,
  * NOT ordered against the HIP null stream).  rn_set_stream_null selects the HIP null

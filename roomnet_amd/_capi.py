@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
     "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
     "rn_jpeg_last_decode_ms",
+    "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
+    "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
 )
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
@@ -112,6 +114,21 @@ class rn_jpeg_info(C.Structure):
 
 class rn_jpeg_image(C.Structure):
     _fields_ = [("info", rn_jpeg_info), ("coeffs", C.c_void_p)]
+
+
+RN_JPEG_MAX_OVERLAYS = 8
+
+
+class rn_jpeg_overlay(C.Structure):
+    """One rasterised text line for ``rn_jpeg_overlay_batch_device`` / ``rn_jpeg_encode_batch_device``: its box inside the image, its
+    colour and the host address of its float32 ``[h, w]`` coverage (``hershey.coverage``)."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("color_bgr", C.c_uint8 * 3),
+                ("coverage", C.c_void_p)]
+
+
+class rn_jpeg_source(C.Structure):
+    _fields_ = [("d_bgr", C.c_void_p), ("info", rn_jpeg_info), ("overlays", C.POINTER(rn_jpeg_overlay)), ("n_overlays", C.c_int32),
+                ("coeffs", C.c_void_p)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -283,6 +300,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_classify_jpegs.restype = i32
         lib.rn_jpeg_last_decode_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_jpeg_last_decode_ms.restype = i32
+    if hasattr(lib, "rn_jpeg_encode_info"):
+        lib.rn_jpeg_encode_info.argtypes = [i32, i32, i32, C.POINTER(rn_jpeg_info)]
+        lib.rn_jpeg_encode_info.restype = i32
+        lib.rn_jpeg_encoded_bound.argtypes = [C.POINTER(rn_jpeg_info)]
+        lib.rn_jpeg_encoded_bound.restype = sz
+        lib.rn_jpeg_entropy_encode.argtypes = [C.POINTER(rn_jpeg_info), vp, vp, sz, C.POINTER(sz)]
+        lib.rn_jpeg_entropy_encode.restype = i32
+        for name in ("rn_jpeg_overlay_batch_device", "rn_jpeg_encode_batch_device"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(rn_jpeg_source), i32]
+            getattr(lib, name).restype = i32
+        lib.rn_jpeg_last_encode_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_jpeg_last_encode_ms.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -383,10 +412,10 @@ class Engine:
     # -- lifetime
     def close(self) -> None:
         if getattr(self, "_h", None):
-            for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0)):      # (jpegs_to_batch's device buffers)
+            for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0), getattr(self, "_jpeg_res", 0)):      # (jpegs_to_batch's / classify_resident's device buffers)
                 if p:
                     self.lib.rn_device_free(self._h, C.c_void_p(p))
-            self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = 0
+            self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = self._jpeg_res = 0
             self.lib.rn_destroy(self._h)
             self._h = None
 
@@ -487,6 +516,35 @@ class Engine:
             for d in d_out:
                 self.device_free(d)
 
+    def _stage_resident(self, jpegs, images):
+        """``jpegs`` ``[(rn_jpeg_info, coeffs)]`` decoded (``rn_jpeg_decode_batch_device``) and ``images`` (BGR uint8 HWC arrays)
+        uploaded into a device buffer this engine keeps and grows, then ONE crop + resize launch
+        (``rn_crop_resize_batch_u8_device``) into ``self._jpeg_dst``.  Returns ``(addresses, shapes)`` of the full-size images,
+        jpegs first; they stay valid until the next call.  Asynchronous; at most ``max_batch`` files."""
+        shapes = [(int(info.height), int(info.width)) for info, _c in jpegs] + [im.shape[:2] for im in images]
+        m, s = len(shapes), self.graph.im_side
+        if not getattr(self, "_jpeg_dst", 0):
+            self._jpeg_dst, self._jpeg_src, self._jpeg_src_cap = self.device_malloc(self.max_batch * s * s * 3), 0, 0
+        sizes = [(h * w * 3 + 15) & ~15 for h, w in shapes]
+        if sum(sizes) > self._jpeg_src_cap:
+            self.sync()
+            if self._jpeg_src:
+                self.device_free(self._jpeg_src)
+            self._jpeg_src_cap = sum(sizes) + sum(sizes) // 4
+            self._jpeg_src = self.device_malloc(self._jpeg_src_cap)
+        addrs = [self._jpeg_src + int(o) for o in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
+        ptrs = (C.c_void_p * m)(*addrs)
+        if jpegs:
+            _check(self.lib, self.lib.rn_jpeg_decode_batch_device(self.handle, self._jpeg_images(jpegs), len(jpegs), ptrs),
+                   "rn_jpeg_decode_batch_device")
+        for a, im in zip(addrs[len(jpegs):], images):
+            self.h2d(a, im)
+        hs = (C.c_int * m)(*[h for h, _w in shapes])
+        ws = (C.c_int * m)(*[w for _h, w in shapes])
+        _check(self.lib, self.lib.rn_crop_resize_batch_u8_device(self.handle, ptrs, hs, ws, m, C.c_void_p(self._jpeg_dst)),
+               "rn_crop_resize_batch_u8_device")
+        return addrs, shapes
+
     def jpegs_to_batch(self, items) -> np.ndarray:
         """``items`` as ``classify_jpegs`` takes them -> their centre-cropped, resized images, uint8 BGR ``[n, S, S, 3]`` on the
         host: pixel stage (``rn_jpeg_decode_batch_device``) into a device buffer this engine keeps and grows, ONE crop + resize
@@ -494,34 +552,78 @@ class Engine:
         items = list(items)
         s = self.graph.im_side
         out = np.empty((len(items), s, s, 3), np.uint8)
-        if not getattr(self, "_jpeg_dst", 0):
-            self._jpeg_dst, self._jpeg_src, self._jpeg_src_cap = self.device_malloc(self.max_batch * s * s * 3), 0, 0
         for i in range(0, len(items), self.max_batch):
             chunk = items[i:i + self.max_batch]
-            m = len(chunk)
-            sizes = [(int(info.height) * int(info.width) * 3 + 15) & ~15 for info, _c in chunk]
-            if sum(sizes) > self._jpeg_src_cap:
-                self.sync()
-                if self._jpeg_src:
-                    self.device_free(self._jpeg_src)
-                self._jpeg_src_cap = sum(sizes) + sum(sizes) // 4
-                self._jpeg_src = self.device_malloc(self._jpeg_src_cap)
-            offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-            ptrs = (C.c_void_p * m)(*[self._jpeg_src + int(o) for o in offs])
-            arr = self._jpeg_images(chunk)
-            _check(self.lib, self.lib.rn_jpeg_decode_batch_device(self.handle, arr, m, ptrs), "rn_jpeg_decode_batch_device")
-            hs = (C.c_int * m)(*[int(info.height) for info, _c in chunk])
-            ws = (C.c_int * m)(*[int(info.width) for info, _c in chunk])
-            _check(self.lib, self.lib.rn_crop_resize_batch_u8_device(self.handle, ptrs, hs, ws, m, C.c_void_p(self._jpeg_dst)),
-                   "rn_crop_resize_batch_u8_device")
+            self._stage_resident(chunk, [])
             self.sync()
-            self.d2h(out[i:i + m], self._jpeg_dst)
+            self.d2h(out[i:i + len(chunk)], self._jpeg_dst)
         return out
+
+    def classify_resident(self, jpegs, images):
+        """Classify a chunk and KEEP its full-size images on the device: ``jpegs`` are decoded there and ``images`` uploaded
+        (``_stage_resident``), then ``rn_forward_u8_device`` on the cropped, resized batch -- the launches of ``classify_jpegs`` /
+        ``classify_images``, so the same bits.  Returns ``(ids, probs, addresses, shapes)``, jpegs first; the addresses stay valid
+        until the next ``classify_resident`` / ``jpegs_to_batch`` call (``jpeg_encode_batch`` takes them).  At most ``max_batch``."""
+        jpegs, images = list(jpegs), [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        m, nc = len(jpegs) + len(images), self.graph.num_classes
+        if not 1 <= m <= self.max_batch:
+            raise ValueError("classify_resident: %d files (1..%d)" % (m, self.max_batch))
+        addrs, shapes = self._stage_resident(jpegs, images)
+        if not getattr(self, "_jpeg_res", 0):
+            self._jpeg_res = self.device_malloc(self.max_batch * (nc * 4 + 8))
+        d_probs, d_ids = self._jpeg_res, self._jpeg_res + self.max_batch * nc * 4
+        self.forward_u8_device(self._jpeg_dst, m, d_probs, d_ids)
+        self.sync()
+        probs, ids = np.empty((m, nc), np.float32), np.empty((m,), np.int64)
+        self.d2h(probs, d_probs)
+        self.d2h(ids, d_ids)
+        return ids, probs, addrs, shapes
 
     def jpeg_last_decode_ms(self) -> float:
         """Device time of the last JPEG batch's pixel stage (``rn_jpeg_last_decode_ms``)."""
         ms = C.c_float(0)
         _check(self.lib, self.lib.rn_jpeg_last_decode_ms(self.handle, C.byref(ms)), "rn_jpeg_last_decode_ms")
+        return float(ms.value)
+
+    @staticmethod
+    def _jpeg_sources(items):
+        """``[(device image address, rn_jpeg_info of jpegenc.encode_info, overlays, coefficient address / int16 array / None)]``
+        with ``overlays`` a list of ``(x, y, coverage float32 [h, w], color_bgr)`` -> ``(rn_jpeg_source[n], what it points into)``."""
+        arr = (rn_jpeg_source * max(len(items), 1))()
+        keep = []
+        for k, (d_bgr, info, overlays, coeffs) in enumerate(items):
+            ovs = (rn_jpeg_overlay * max(len(overlays), 1))()
+            for j, (x, y, cov, color) in enumerate(overlays):
+                cov = np.ascontiguousarray(cov, dtype=np.float32)
+                ovs[j].x, ovs[j].y, ovs[j].h, ovs[j].w = int(x), int(y), int(cov.shape[0]), int(cov.shape[1])
+                ovs[j].color_bgr[:] = [int(c) for c in color]
+                ovs[j].coverage = cov.ctypes.data
+                keep.append(cov)
+            keep.append(ovs)
+            arr[k].d_bgr = int(d_bgr)
+            arr[k].info = info
+            arr[k].overlays = C.cast(ovs, C.POINTER(rn_jpeg_overlay))
+            arr[k].n_overlays = len(overlays)
+            arr[k].coeffs = 0 if coeffs is None else (coeffs.ctypes.data if isinstance(coeffs, np.ndarray) else int(coeffs))
+        return arr, keep
+
+    def jpeg_overlay_batch(self, items) -> None:
+        """``rn_jpeg_overlay_batch_device`` over ``items`` (as ``_jpeg_sources`` takes them, at most ``max_batch``): the overlays are
+        drawn into the device images, in order.  Asynchronous; the coverages are copied before it returns."""
+        arr, _keep = self._jpeg_sources(items)
+        _check(self.lib, self.lib.rn_jpeg_overlay_batch_device(self.handle, arr, len(items)), "rn_jpeg_overlay_batch_device")
+
+    def jpeg_encode_batch(self, items) -> None:
+        """``rn_jpeg_encode_batch_device`` over ``items``: overlays, then the pixel stage of the JPEG encode; each image's quantised
+        coefficients arrive in its coefficient buffer (``jpegenc.entropy_encode`` writes the file from them).  ``sync()`` before
+        reading them."""
+        arr, _keep = self._jpeg_sources(items)
+        _check(self.lib, self.lib.rn_jpeg_encode_batch_device(self.handle, arr, len(items)), "rn_jpeg_encode_batch_device")
+
+    def jpeg_last_encode_ms(self) -> float:
+        """Device time of the last encoded batch's launches (``rn_jpeg_last_encode_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_jpeg_last_encode_ms(self.handle, C.byref(ms)), "rn_jpeg_last_encode_ms")
         return float(ms.value)
 
     def crop_resize(self, im_bgr_u8: np.ndarray) -> np.ndarray:

@@ -153,6 +153,7 @@ struct rn_handle {
     float* d_feat6 = nullptr;    // rn_features_depth_u8, depth 3: float32 staging of s6.bn, [max_batch, S6, S6, 128] (the same)
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
     void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch and the batch table (rn_jpeg.hip; allocated by the first call)
+    void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the double-buffered batch tables (rn_jpeg_enc.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
     // couts whose convolution still runs
@@ -221,6 +222,8 @@ int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
 
 // ---- baseline JPEG pixel stage (rn_jpeg.hip)
 void rn_jpeg_release(rn_handle* h);
+// ---- overlay + the encode's pixel stage (rn_jpeg_enc.hip)
+void rn_jpeg_enc_release(rn_handle* h);
 // (rn_api.hip) the centred square window of network.py:137-146, the batched resize's device table, the tail of a host entry point
 void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side);
 int rn_ensure_resize_items(rn_handle* h);
@@ -258,6 +261,28 @@ int rn_owned_zeroed(std::vector<void*>& owner, size_t min_bytes, size_t count, T
     if (rc != RN_OK) return rc;
     RN_HIP(hipMemset(p, 0, count * sizeof(T)));
     *out = static_cast<T*>(p);
+    return RN_OK;
+}
+// grow-only device scratch of a lazily created stage (rn_jpeg.hip, rn_jpeg_enc.hip): the handle's streams are drained first, so
+// nothing still reads the old block; a quarter is added to what is asked for
+template <typename T>
+int rn_grow_scratch(rn_handle* h, T** p, size_t* cap, size_t need, const char* what) {
+    if (need <= *cap) return RN_OK;
+    RN_HIP(hipStreamSynchronize(h->stream));
+    if (h->copy_stream) RN_HIP(hipStreamSynchronize(h->copy_stream));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 4;
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, want * sizeof(T));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rn_set_error("hipMalloc(%zu bytes of %s) failed: %s", want * sizeof(T), what, hipGetErrorString(e));
+        return RN_E_NOMEM;
+    }
+    *p = static_cast<T*>(q);
+    *cap = want;
     return RN_OK;
 }
 // ... by the handle (an empty request gets 16 bytes)

@@ -243,28 +243,6 @@ int jpeg_state(rn_handle* h, JpegState** out) {
     return RN_OK;
 }
 
-// grow-only scratch; the streams are drained first, so nothing still reads the old block
-template <typename T>
-int grow(rn_handle* h, T** p, size_t* cap, size_t need, const char* what) {
-    if (need <= *cap) return RN_OK;
-    RN_HIP(hipStreamSynchronize(h->stream));
-    RN_HIP(hipStreamSynchronize(h->copy_stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 4;
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, want * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rn_set_error("hipMalloc(%zu bytes of %s) failed: %s", want * sizeof(T), what, hipGetErrorString(e));
-        return RN_E_NOMEM;
-    }
-    *p = static_cast<T*>(q);
-    *cap = want;
-    return RN_OK;
-}
-
 // a supported image as rn_jpeg_probe fills it: every size the kernels index with is recomputed from width, height and sampling
 bool info_ok(const rn_jpeg_info& f) {
     if (f.supported != 1 || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
@@ -294,9 +272,9 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n,
         max_h = std::max(max_h, f.height);
     }
     int rc;
-    if ((rc = grow(h, &st->d_coef, &st->coef_cap, coef_total, "JPEG coefficients")) != RN_OK) return rc;
-    if ((rc = grow(h, &st->d_planes, &st->planes_cap, plane_total, "JPEG planes")) != RN_OK) return rc;
-    if (!d_bgr && (rc = grow(h, &st->d_bgr, &st->bgr_cap, bgr_total, "decoded images")) != RN_OK) return rc;
+    if ((rc = rn_grow_scratch(h, &st->d_coef, &st->coef_cap, coef_total, "JPEG coefficients")) != RN_OK) return rc;
+    if ((rc = rn_grow_scratch(h, &st->d_planes, &st->planes_cap, plane_total, "JPEG planes")) != RN_OK) return rc;
+    if (!d_bgr && (rc = rn_grow_scratch(h, &st->d_bgr, &st->bgr_cap, bgr_total, "decoded images")) != RN_OK) return rc;
     // the previous call's launches read the coefficient scratch: the copy stream starts behind them
     RN_HIP(hipStreamWaitEvent(h->copy_stream, st->done, 0));
     size_t coef_off = 0, plane_off = 0, bgr_off = 0;

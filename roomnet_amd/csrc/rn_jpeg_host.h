@@ -4,6 +4,9 @@
 // header, no device, no allocation; every read of `data` and every coefficient index is bounded, so arbitrary bytes give RN_OK or
 // a negative code and nothing else.  Included by rn_jpeg.hip (which exports the two entry points) and by
 // tools/jpeg_corrupt_main.cpp (the host-sanitizer corpus run).
+// Further down, the host half of the split ENCODE: the description of the output file
+// (rn_jpeg_encode_info) and its Huffman pass (rn_jpeg_entropy_encode), with the same properties; exported by rn_jpeg_enc.hip and
+// run stand-alone by tools/jpeg_encode_main.cpp.
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -436,6 +439,259 @@ inline int entropy_decode(const uint8_t* data, size_t len, const rn_jpeg_info* i
             }
             --until_restart;
         }
+    }
+    return RN_OK;
+}
+
+// ---- the encoder's host half: the decode above, mirrored -----------------------------------------------
+// rn_jpeg_encode_info describes the file imwrite writes for a .jpg name (4:2:0, libjpeg's quality scaling of the standard
+// tables), the GPU turns pixels into the quantised coefficients of that file (rn_jpeg_enc.hip), and entropy_encode writes the
+// file: its headers, the Huffman pass with the standard tables of JPEG Annex K, EOI.  Same properties as the decoder: no device,
+// no allocation, every write of `out` bounded by `cap`.
+
+// Annex K.1 in natural order
+static const uint8_t kStdLumaQ[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                                      14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                                      18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                      49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+static const uint8_t kStdChromaQ[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                        99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                        99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// Annex K.3: code counts per length 1..16, then the symbols in code order
+static const uint8_t kStdDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+static const uint8_t kStdDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const uint8_t kStdAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+static const uint8_t kStdAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+
+// libjpeg's jpeg_set_quality: the standard tables scaled by 5000 / q below 50, else 200 - 2 q; entries clamped to 1..255
+inline void quality_table(const uint8_t (&std_table)[64], int quality, uint16_t* out) {
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int k = 0; k < 64; ++k) {
+        const int v = (std_table[k] * scale + 50) / 100;
+        out[k] = static_cast<uint16_t>(v < 1 ? 1 : (v > 255 ? 255 : v));
+    }
+}
+
+inline int encode_info(int width, int height, int quality, rn_jpeg_info* out) {
+    if (!out || quality < 1 || quality > 100 || width < 1 || height < 1 || width > 65535 || height > 65535) return RN_E_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->width = width;
+    out->height = height;
+    out->ncomp = 3;
+    out->hsamp = out->vsamp = 2;
+    const int mcus_x = (width + 15) / 16, mcus_y = (height + 15) / 16;
+    for (int c = 0; c < 3; ++c) {
+        out->blocks_w[c] = mcus_x * (c == 0 ? 2 : 1);
+        out->blocks_h[c] = mcus_y * (c == 0 ? 2 : 1);
+    }
+    quality_table(kStdLumaQ, quality, out->qt[0]);
+    quality_table(kStdChromaQ, quality, out->qt[1]);
+    std::memcpy(out->qt[2], out->qt[1], sizeof(out->qt[2]));
+    out->supported = 1;
+    return RN_OK;
+}
+
+// an info as encode_info fills it (whatever the quality was): the only kind of file the encoder writes
+inline bool encode_info_ok(const rn_jpeg_info& f) {
+    if (f.supported != 1 || f.ncomp != 3 || f.hsamp != 2 || f.vsamp != 2 || f.restart_interval != 0) return false;
+    if (f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
+    const int mcus_x = (f.width + 15) / 16, mcus_y = (f.height + 15) / 16;
+    for (int c = 0; c < 3; ++c)
+        if (f.blocks_w[c] != mcus_x * (c == 0 ? 2 : 1) || f.blocks_h[c] != mcus_y * (c == 0 ? 2 : 1)) return false;
+    for (int k = 0; k < 64; ++k) {
+        if (f.qt[0][k] < 1 || f.qt[0][k] > 255 || f.qt[1][k] < 1 || f.qt[1][k] > 255) return false;
+        if (f.qt[2][k] != f.qt[1][k]) return false;       // (Cb and Cr share table 1 of the file)
+    }
+    return true;
+}
+
+constexpr size_t kEncHeaderBytes = 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 14;      // SOI .. SOS, as entropy_encode writes them
+// Worst case of one block: a DC code of at most 9 bits + 11 magnitude bits, 63 AC codes of at most 16 + 10 bits = 1658 bits,
+// every byte of them FF and stuffed.
+constexpr size_t kEncBlockBytes = 2 * ((9 + 11 + 63 * 26 + 7) / 8);
+
+inline size_t encoded_bound(const rn_jpeg_info& f) {
+    return kEncHeaderBytes + (coeff_count(f) / 64) * kEncBlockBytes + 2 /* padding byte, stuffed */ + 2 /* EOI */;
+}
+
+struct EncTable {
+    uint16_t code[256];
+    uint8_t size[256];       // 0: the table has no code for the symbol
+};
+
+inline void build_enc_table(const uint8_t* bits, const uint8_t* vals, EncTable& t) {
+    std::memset(&t, 0, sizeof(t));
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < bits[l - 1]; ++i, ++code, ++k) {
+            t.code[vals[k]] = static_cast<uint16_t>(code);
+            t.size[vals[k]] = static_cast<uint8_t>(l);
+        }
+        code <<= 1;
+    }
+}
+
+// Bytes into out[0 .. cap): past cap nothing is stored, the count goes on (the caller learns the size it needed).
+struct ByteWriter {
+    uint8_t* out;
+    size_t cap, pos = 0;
+    uint64_t acc = 0;        // pending bits, right-aligned
+    int cnt = 0;
+    inline void byte(uint32_t b) {
+        if (pos < cap) out[pos] = static_cast<uint8_t>(b);
+        ++pos;
+    }
+    inline void u16(uint32_t v) {
+        byte(v >> 8);
+        byte(v & 255);
+    }
+    inline void bits(uint32_t v, int n) {       // n <= 26, v < 2^n
+        acc = (acc << n) | v;
+        cnt += n;
+        while (cnt >= 8) {
+            const uint32_t b = static_cast<uint32_t>(acc >> (cnt - 8)) & 255u;
+            byte(b);
+            if (b == 0xFF) byte(0);
+            cnt -= 8;
+        }
+    }
+    inline void flush() {                       // the last byte is padded with 1-bits
+        if (cnt) bits((1u << (8 - cnt)) - 1u, 8 - cnt);
+    }
+};
+
+inline int bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+// The whole file for the quantised coefficients `coeffs` ([component][block_y][block_x][64], natural order: the layout
+// entropy_decode writes).  *len: the file's size, also when it is more than cap (RN_E_RANGE; out[0 .. cap) is then its beginning).
+inline int entropy_encode(const rn_jpeg_info* info, const int16_t* coeffs, uint8_t* out, size_t cap, size_t* len, const char** why) {
+    static thread_local EncTable dc[2], ac[2];
+    static thread_local bool built = false;
+    *why = "";
+    if (!info || !coeffs || !len || (!out && cap)) {
+        *why = "null argument";
+        return RN_E_INVALID;
+    }
+    *len = 0;
+    if (!encode_info_ok(*info)) {
+        *why = "the info is not one rn_jpeg_encode_info fills (3 components, 4:2:0, whole-MCU grids, 8-bit tables)";
+        return RN_E_INVALID;
+    }
+    if (!built) {
+        for (int t = 0; t < 2; ++t) {
+            build_enc_table(kStdDcBits[t], kStdDcVals, dc[t]);
+            build_enc_table(kStdAcBits[t], kStdAcVals[t], ac[t]);
+        }
+        built = true;
+    }
+    const rn_jpeg_info& f = *info;
+    ByteWriter w{out, cap};
+    w.u16(0xFFD8);
+    w.u16(0xFFE0);                                           // APP0: JFIF 1.01, no units, 1:1, no thumbnail
+    w.u16(16);
+    for (const uint8_t b : {0x4A, 0x46, 0x49, 0x46, 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00}) w.byte(b);
+    for (int t = 0; t < 2; ++t) {                            // DQT, zigzag order
+        w.u16(0xFFDB);
+        w.u16(67);
+        w.byte(t);
+        for (int k = 0; k < 64; ++k) w.byte(f.qt[t][kNatural[k]]);
+    }
+    w.u16(0xFFC0);                                           // SOF0
+    w.u16(17);
+    w.byte(8);
+    w.u16(static_cast<uint32_t>(f.height));
+    w.u16(static_cast<uint32_t>(f.width));
+    w.byte(3);
+    for (const uint8_t b : {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) w.byte(b);
+    for (int t = 0; t < 2; ++t)                              // DHT: DC0, AC0, DC1, AC1
+        for (int cls = 0; cls < 2; ++cls) {
+            const uint8_t* bits = cls ? kStdAcBits[t] : kStdDcBits[t];
+            const uint8_t* vals = cls ? kStdAcVals[t] : kStdDcVals;
+            const int count = cls ? 162 : 12;
+            w.u16(0xFFC4);
+            w.u16(static_cast<uint32_t>(2 + 1 + 16 + count));
+            w.byte(static_cast<uint32_t>((cls << 4) | t));
+            for (int l = 0; l < 16; ++l) w.byte(bits[l]);
+            for (int k = 0; k < count; ++k) w.byte(vals[k]);
+        }
+    w.u16(0xFFDA);                                           // SOS: one interleaved scan
+    w.u16(12);
+    for (const uint8_t b : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) w.byte(b);
+
+    const int16_t* base[3];
+    size_t off = 0;
+    for (int c = 0; c < 3; ++c) {
+        base[c] = coeffs + off;
+        off += static_cast<size_t>(f.blocks_w[c]) * f.blocks_h[c] * 64;
+    }
+    const int mcus_x = f.blocks_w[1], mcus_y = f.blocks_h[1];
+    int pred[3] = {0, 0, 0};
+    for (int my = 0; my < mcus_y; ++my)
+        for (int mx = 0; mx < mcus_x; ++mx)
+            for (int c = 0; c < 3; ++c) {
+                const int s = c == 0 ? 2 : 1;
+                const EncTable& dct = dc[c ? 1 : 0];
+                const EncTable& act = ac[c ? 1 : 0];
+                for (int v = 0; v < s; ++v)
+                    for (int hh = 0; hh < s; ++hh) {
+                        const size_t by = static_cast<size_t>(my) * s + v, bx = static_cast<size_t>(mx) * s + hh;
+                        const int16_t* blk = base[c] + (by * f.blocks_w[c] + bx) * 64;
+                        // encode_one_block of jchuff.c
+                        const int diff = blk[0] - pred[c];
+                        pred[c] = blk[0];
+                        int nbits = bit_length(static_cast<uint32_t>(diff < 0 ? -diff : diff));
+                        if (nbits > 11) {
+                            *why = "DC difference beyond category 11";
+                            return RN_E_INVALID;
+                        }
+                        w.bits(dct.code[nbits], dct.size[nbits]);
+                        if (nbits) w.bits(static_cast<uint32_t>(diff < 0 ? diff - 1 : diff) & ((1u << nbits) - 1u), nbits);
+                        int run = 0;
+                        for (int k = 1; k < 64; ++k) {
+                            const int val = blk[kNatural[k]];
+                            if (val == 0) {
+                                ++run;
+                                continue;
+                            }
+                            while (run > 15) {
+                                w.bits(act.code[0xF0], act.size[0xF0]);      // ZRL
+                                run -= 16;
+                            }
+                            nbits = bit_length(static_cast<uint32_t>(val < 0 ? -val : val));
+                            if (nbits > 10) {
+                                *why = "AC coefficient beyond category 10";
+                                return RN_E_INVALID;
+                            }
+                            const int sym = (run << 4) | nbits;
+                            w.bits(act.code[sym], act.size[sym]);
+                            w.bits(static_cast<uint32_t>(val < 0 ? val - 1 : val) & ((1u << nbits) - 1u), nbits);
+                            run = 0;
+                        }
+                        if (run > 0) w.bits(act.code[0x00], act.size[0x00]);      // EOB
+                    }
+            }
+    w.flush();
+    w.u16(0xFFD9);
+    *len = w.pos;
+    if (w.pos > cap) {
+        *why = "output buffer too small";
+        return RN_E_RANGE;
     }
     return RN_OK;
 }

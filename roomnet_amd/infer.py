@@ -195,26 +195,55 @@ def force_makedir(dir):
         os.makedirs(dir)
 
 
+def _overlay_lines(h, w, pred_label, pred_conf):
+    """infer.py:87-92: the two overlay lines of an ``h x w`` image as ``(text, org, font_scale, color_bgr)``."""
+    return [("Predicted Class: " + pred_label, (int(.5 * w), int(.90 * h)), (h / 720.) * .85, (0, 255, 0)),
+            ("Confidence: " + str(round(pred_conf * 100, 2)) + " %", (int(.5 * w), int(.95 * h)), (h / 720.) * .85, (255, 0, 0))]
+
+
 def _overlay_and_write(im, pred_label, pred_conf, out_fpath):
     """infer.py:87-93 for one image: the two overlay lines, then the file."""
     h, w, _ = im.shape
-    put_text(im, "Predicted Class: " + pred_label, (int(.5 * w), int(.90 * h)), (h / 720.) * .85, (0, 255, 0))
-    put_text(im, "Confidence: " + str(round(pred_conf * 100, 2)) + " %", (int(.5 * w), int(.95 * h)),
-             (h / 720.) * .85, (255, 0, 0))
+    for text, org, font_scale, color in _overlay_lines(h, w, pred_label, pred_conf):
+        put_text(im, text, org, font_scale, color)
     return imwrite(out_fpath, im)
 
 
-def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False):
+def _in_batches_of_readable(results, batch_size):
+    """``RoomNet.classify_files_to_dir``'s results in the order ``_infer_files`` reports on files: an unreadable file at once, the
+    readable ones when ``batch_size`` of them have come together -- so the printed lines of both arms are the same sequence."""
+    pending = []
+    for r in results:
+        if r[1] is None:
+            yield r
+            continue
+        pending.append(r)
+        if len(pending) >= batch_size:
+            yield from pending
+            pending.clear()
+    yield from pending
+
+
+def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
-    ``gpu_decode`` (with ``overlay=False`` only: the overlay needs the pixels on the host): baseline JPEG files are decoded on
-    the GPU (``RoomNet.infer_files``); the workbook is the same, byte for byte."""
+    ``gpu_decode`` (with ``overlay=False``, or with ``gpu_encode``): baseline JPEG files are decoded on the GPU
+    (``RoomNet.infer_files``); the workbook is the same, byte for byte.  ``gpu_encode`` (with ``overlay=True`` and ``gpu_decode``):
+    the overlay is drawn and the output JPEG's pixel stage runs on the GPU as well (``RoomNet.classify_files_to_dir``): a file
+    stays on the device from decode to encode and only the Huffman passes run on the host; files ``imread`` decodes are uploaded
+    when their output is a JPEG file and go the host way otherwise.  Output files, workbook and printed lines are the same,
+    byte for byte."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
-    if gpu_decode and overlay:
+    if gpu_encode and not overlay:
+        raise ValueError("classify_im_dir: gpu_encode=True needs overlay=True (without the overlay the files are copied: there is "
+                         "nothing to encode)")
+    if gpu_encode and not gpu_decode:
+        raise ValueError("classify_im_dir: gpu_encode=True needs gpu_decode=True (it encodes the image the GPU decode left on the device)")
+    if gpu_decode and overlay and not gpu_encode:
         raise ValueError("classify_im_dir: gpu_decode=True needs overlay=False (the overlay is drawn on the decoded image, "
-                         "which the GPU decode path never brings to the host)")
+                         "which the GPU decode path never brings to the host) or gpu_encode=True")
     print('Classifying images in', imgs_dir)
     all_im_paths = glob(imgs_dir + '/*')
     out_dir = imgs_dir + '_classified'
@@ -230,14 +259,27 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False)
     row = 0      # unreadable files are skipped (the reference crashes on them): rows stay contiguous
     writers = ThreadPoolExecutor(max_workers=DECODE_THREADS) if overlay else None
     writing = deque()
+    if gpu_encode:
+        results = _in_batches_of_readable(
+            nn.classify_files_to_dir(all_im_paths,
+                                     lambda i, idx: out_dir + os.sep + CLASS_LABELS[idx] + os.sep + all_im_paths[i].split(os.sep)[-1],
+                                     lambda h, w, idx, conf: _overlay_lines(h, w, CLASS_LABELS[idx], conf),
+                                     writers, batch_size=batch_size), batch_size)
+    else:
+        results = ((i, idx, conf, im, None) for i, im, idx, conf in _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode))
     try:
-        for i, im, idx, pred_conf in _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode):
+        for i, idx, pred_conf, im, written in results:
             fpath = all_im_paths[i]
+            if idx is None:
+                print(fpath, '---> unreadable image, skipped')
+                continue
             row += 1
             pred_label = CLASS_LABELS[idx]
             out_fpath_dir = out_dir + os.sep + pred_label
             print(fpath, '--->', pred_label, pred_conf)
-            if overlay:
+            if written is not None:
+                writing.append(written)
+            elif overlay:
                 writing.append(writers.submit(_overlay_and_write, im, pred_label, pred_conf,
                                               out_fpath_dir + os.sep + fpath.split(os.sep)[-1]))
                 while len(writing) > 4 * DECODE_THREADS:      # (a bound on the decoded images held for the writers)

@@ -382,6 +382,77 @@ class RoomNet:
                 cur, ahead = ahead, (submit(k + 1) if k + 1 < n_chunks else [])
                 yield k * chunk, [f.result() for f in cur]
 
+    def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64):
+        """Classify image FILES and write each with its overlay as a JPEG file, decode to encode on the GPU.  Yields, in list
+        order, ``(index, id, conf, image, future)``: ``future`` is the pending write (on the ``writers`` pool) of a file that went
+        through the device; ``image`` (BGR) is set instead for a file whose output name ``out_path_of(index, id)`` has no JPEG
+        extension -- the caller writes those; an unreadable file yields ``(index, None, None, None, None)``.
+
+        Per chunk of ``batch_size`` files (at most ``max_batch``): the pool of ``_file_chunks`` runs the Huffman pass of baseline
+        JPEG files (others are decoded by ``imageio.imread`` and uploaded), the GPU decodes, crops, resizes and classifies
+        (``Engine.classify_resident``: the bits of ``infer_files``), the text lines ``lines_of(h, w, id, conf)`` -- ``put_text``
+        argument tuples -- are rasterised to coverages on the ``writers`` pool, the GPU draws them and runs the encode's pixel
+        stage (``rn_jpeg_encode_batch_device``), and the ``writers`` pool runs the Huffman pass of the output and writes the
+        file while the GPU works on the next chunk.  The coefficients come back into a second ring of page-locked buffers,
+        two banks like the decode's; a bank is reused once its files are written.  The full-size image never exists on the host.
+        Every file equals ``imageio.imwrite`` of the ``put_text`` image byte for byte."""
+        import os
+        from . import hershey, jpegdec, jpegenc
+        paths = list(paths)
+        if not paths:
+            return
+        eng = self._engine()
+        chunk = max(1, min(int(batch_size), eng.max_batch))
+        ring = getattr(self, "_jpeg_enc_ring", None)
+        if ring is None or len(ring) < 2 * chunk:
+            if ring is not None:
+                ring.close()
+            ring = self._jpeg_enc_ring = jpegdec.CoeffRing(2 * chunk)
+        pending = [[], []]                      # the writes that still read each bank's buffers
+
+        def write(info, coeffs, out_path):
+            try:
+                data = jpegenc.entropy_encode(info, coeffs)
+                with open(out_path, "wb") as f:
+                    f.write(data)
+            except (OSError, ValueError):
+                return False
+            return True
+
+        def rasterise(shape, lines):
+            boxes = [(hershey.coverage(text, org, scale, shape, 1), color) for text, org, scale, color in lines]
+            return [(b[0], b[1], b[2], color) for b, color in boxes if b is not None]
+
+        for k, (lo, loaded) in enumerate(self._file_chunks(paths, chunk, decode_threads)):
+            bank = k % 2
+            for f in pending[bank]:
+                f.result()
+            pending[bank] = []
+            jp = [j for j, r in enumerate(loaded) if r is not None and r[0] == "jpeg"]
+            up = [j for j, r in enumerate(loaded) if r is not None and r[0] == "image"
+                  and os.path.splitext(paths[lo + j])[1].lower() in jpegenc.JPEG_EXTENSIONS]
+            host = [j for j, r in enumerate(loaded) if r is not None and r[0] == "image" and j not in up]
+            out = {}
+            if jp or up:
+                ids, probs, addrs, shapes = eng.classify_resident([(loaded[j][1], loaded[j][2]) for j in jp],
+                                                                  [loaded[j][1] for j in up])
+                confs = [probs[m][ids[m]] for m in range(len(ids))]
+                overlays = list(writers.map(rasterise, shapes, [lines_of(h, w, int(ids[m]), confs[m]) for m, (h, w) in enumerate(shapes)]))
+                infos = [jpegenc.encode_info(h, w) for h, w in shapes]
+                bufs = [ring.buffer(bank * chunk + m, jpegdec.coeff_count(info)) for m, info in enumerate(infos)]
+                eng.jpeg_encode_batch([(addrs[m], infos[m], overlays[m], bufs[m]) for m in range(len(infos))])
+                eng.sync()
+                for m, j in enumerate(jp + up):
+                    fut = writers.submit(write, infos[m], bufs[m], out_path_of(lo + j, int(ids[m])))
+                    pending[bank].append(fut)
+                    out[j] = (int(ids[m]), confs[m], None, fut)
+            if host:
+                ids, probs = eng.classify_images([loaded[j][1] for j in host])
+                for m, j in enumerate(host):
+                    out[j] = (int(ids[m]), probs[m][ids[m]], loaded[j][1], None)
+            for j in range(len(loaded)):
+                yield (lo + j,) + out.get(j, (None, None, None, None))
+
     def prepare_files(self, paths, decode_threads=None, batch_size=64):
         """Image files -> the batches ``infer`` takes, decoding baseline JPEG on the GPU: yields ``(indices, batch, unreadable)`` per
         chunk of ``batch_size`` files: ``batch`` the uint8 BGR ``[m, S, S, 3]`` centre-cropped, resized images of the readable files

@@ -8,6 +8,10 @@
   python tools/bench_images.py --dir --gpu-decode [--threads=T] [H W [N]]    then, in the same session and on the same files, the
         gpu_decode=True arm of both drivers (baseline JPEG split: Huffman pass on the pool, pixel stage on the GPU), the host
         entropy pass alone on one thread, and the device time of the pixel stage per batch; a second line with the ratios
+  python tools/bench_images.py --dir --gpu-encode [--threads=T] [H W [N]]    then classify_im_dir(overlay=True) as it was (host
+        decode, host overlay and re-encode on the pool) against overlay=True, gpu_decode=True, gpu_encode=True on the same files,
+        alternating, three times each after a warm-up of both; the host Huffman-encode pass alone on one thread and the device time
+        of the overlay + encode launches per batch; a line with the rates, the ratio and whether the files are identical
 """
 import contextlib
 import io
@@ -117,6 +121,8 @@ def directory():
           % (N, W, H, mb, infer.DECODE_THREADS, os.cpu_count() or 1, N / t_dir, N / t_ovl, 1.0 / t_ow, N / t_val, N / t_dec1, 1.0 / t_one))
     if '--gpu-decode' in sys.argv:
         gpu_decode_arm(nn, infer, d, lst, paths, N / t_dir, N / t_val, N / t_dec1)
+    if '--gpu-encode' in sys.argv:
+        gpu_encode_arm(nn, infer, d, paths, 1.0 / t_ow)
     shutil.rmtree(root, ignore_errors=True)
 
 
@@ -160,6 +166,72 @@ def gpu_decode_arm(nn, infer, d, lst, paths, dir_ips, val_ips, dec1_ips):
           'decode)   pixel stage on the device %.3f ms per batch of %d (%.1f us per image)'
           % (N_ / t_dir, (N_ / t_dir) / dir_ips, N_ / t_val, (N_ / t_val) / val_ips, same, N_ / t_ent, (N_ / t_ent) / dec1_ips, ms, n,
              1e3 * ms / n))
+
+
+def gpu_encode_arm(nn, infer, d, paths, overlay_write_ips):
+    """overlay=True on the host against the gpu_decode + gpu_encode arm: same files, same session, alternating."""
+    from roomnet_amd import jpegdec, jpegenc
+
+    def outputs():
+        out = {}
+        for dirpath, _dirs, names in os.walk(d + '_classified'):
+            for name in names:
+                with open(os.path.join(dirpath, name), 'rb') as f:
+                    out[name] = f.read()
+        return out
+
+    arms = {'host': dict(), 'gpu': dict(gpu_decode=True, gpu_encode=True)}
+    times = {'host': [], 'gpu': []}
+    files = {}
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):
+        for rep in range(4):                              # (the first round is the warm-up of both arms)
+            for arm, kw in arms.items():
+                t0 = time.perf_counter()
+                infer.classify_im_dir(nn, d, overlay=True, batch_size=64, **kw)
+                if rep:
+                    times[arm].append(time.perf_counter() - t0)
+                files[arm] = outputs()
+    same = files['host'] == files['gpu'] and len(files['gpu']) == len(paths)
+    # the host's share of the encode: the Huffman pass of each output file, one thread (coefficients of the host restatement's source:
+    # the decode of the file itself)
+    eng = nn._engine()
+    n = min(len(paths), eng.max_batch)
+    ims = [imageio.imread(p) for p in paths[:n]]
+    infos = [jpegenc.encode_info(im.shape[0], im.shape[1]) for im in ims]
+    pinned = [_capi.PinnedArray((jpegdec.coeff_count(i),), np.int16) for i in infos]
+    d_ims = [eng.device_malloc(im.nbytes) for im in ims]
+    for p, im in zip(d_ims, ims):
+        eng.h2d(p, im)
+    lines = [infer._overlay_lines(im.shape[0], im.shape[1], 'LivingRoom', np.float32(0.9987)) for im in ims]
+    from roomnet_amd import hershey
+    ovs = [[(b[0], b[1], b[2], color) for b, color in ((hershey.coverage(t, o, s_, im.shape, 1), c) for t, o, s_, c in ln) if b is not None]
+           for im, ln in zip(ims, lines)]
+    items = [(p, i, o, c.array) for p, i, o, c in zip(d_ims, infos, ovs, pinned)]
+    ms = []
+    for _ in range(6):
+        eng.jpeg_encode_batch(items)
+        eng.sync()
+        ms.append(eng.jpeg_last_encode_ms())
+    ms = sorted(ms[1:])[2]
+    t0 = time.perf_counter()
+    total = 0
+    for i, c in zip(infos, pinned):
+        total += len(jpegenc.entropy_encode(i, c.array))
+    t_huff = (time.perf_counter() - t0) / n
+    for p in d_ims:
+        eng.device_free(p)
+    for c in pinned:
+        c.close()
+    N_ = len(paths)
+    med = {a: sorted(t)[len(t) // 2] for a, t in times.items()}
+    print('overlay=True, same files, same session, alternating, 3 runs each after a warm-up: host decode + overlay + write %.1f img/s '
+          '(runs %s)   gpu_decode + gpu_encode %.1f img/s (runs %s)   x%.2f   output files identical: %s   host Huffman-encode pass '
+          'alone, one thread %.1f img/s (%.2f MB per file; overlay + write alone, one thread: %.1f img/s)   overlay + encode launches on '
+          'the device %.3f ms per batch of %d (%.1f us per image)'
+          % (N_ / med['host'], ' '.join('%.1f' % (N_ / t) for t in times['host']), N_ / med['gpu'],
+             ' '.join('%.1f' % (N_ / t) for t in times['gpu']), med['host'] / med['gpu'], same, 1.0 / t_huff, total / n / 1e6,
+             overlay_write_ips, ms, n, 1e3 * ms / n))
 
 
 if '--dir' in sys.argv:

@@ -420,7 +420,7 @@ RN_API int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n,
  * those features with the handle's fast forward pass; an rn_ft trainer then runs Adam steps on the resident cache with no
  * trunk pass, no host round trip and no inference handle.  Mathematics (forward, loss, TensorFlow's gradient rules, Adam, the
  * learning-rate schedule): the header of csrc/rn_finetune.hip.  In short: every BN is the inference BN with trainable gamma and
- * beta and fixed moving statistics (train.py:40-41), no dropout; loss = mean CE(softmax(relu6(z)), y) + l2_coeff sum(v^2) / 2 over
+ * beta and fixed moving statistics (train.py:40-41), dropout only where rn_ft_set_dropout switches it on; loss = mean CE(softmax(relu6(z)), y) + l2_coeff sum(v^2) / 2 over
  * the TRAINED variables; tf.train.AdamOptimizer in float32 with lr(step) = learn_rate * decay_rate^(step / num_steps).
  *
  * rn_features_shape     side and channels of one feature ([side, side, channels] float32 per image)
@@ -496,6 +496,45 @@ RN_API int64_t rn_ft_step_count(const rn_ft* ft);
 RN_API int rn_ft_last_run_ms(rn_ft* ft, float* ms);
 RN_API int rn_ft_upload(rn_ft* ft, const void* src, size_t bytes, void** d_ptr);
 RN_API int rn_ft_free(rn_ft* ft, void* d_ptr);
+
+/* ---- dropout while fine-tuning ------------------------------------------------------------------
+ * The reference's other regulariser (RoomNet(dropout_enabled=True, dropout_rate=...), network.py:204-206 and :219-221; train.py:37-38
+ * carries DROPOUT_RATE = .35): tf.nn.dropout behind every conv block and every dense block.  A trainer applies it at every site
+ * at or behind the cached feature; the dropout behind conv blocks 0-2 (and, at depth 2, behind block 3) acts on frozen stages
+ * upstream of the cache and cannot be applied to cached features.  No mask is stored: every mask bit is recomputed where it is
+ * needed, forward and adjoint, from a counter-based generator, so that with dropout on the same calls still give the same bits, one
+ * call of k steps equals k calls of one step, and a run resumed with start_step reproduces the same masks.
+ *
+ * Generator: Philox4x32-10 as published (multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants 0x9E3779B9 and 0xBB67AE85, ten rounds).
+ * For element e of site `site`, minibatch slot b (the position in the minibatch, not the item: an item that occurs twice in a step
+ * gets two masks) and global step t (what rn_ft_step_count returned before the step):
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (e >> 2, b, (uint32) t, site | ((uint32)(t >> 32) << 8))
+ *   word    = out[e & 3];   k = word >> 8, a 24-bit value
+ * The element is kept iff k >= thr, thr = ceil((double) rate * 2^24): exactly k 2^-24 >= rate, TensorFlow's random_uniform >= rate.
+ * A kept value becomes x * scale, one float32 product with scale = 1.0f / (1.0f - rate) (one float32 division); a dropped value
+ * becomes +0.0f; the adjoint is g * scale where kept and 0 where dropped.
+ *
+ *   site   tensor                                                                      element index e
+ *   0      "s6.bn", the output of conv block 3 and the input of stage 7; depth 3 only  (y * S6 + x) * 128 + c within the item
+ *   1      the last conv block's output, the flattened tensor dense 0 reads            (y * S9 + x) * 16 + c
+ *   2 + d  the output of dense block d: behind its BN for d < n_dense - 1; the last     unit j
+ *          block's logits relu6(z) have no BN and are dropped too, as the reference drops them
+ * With dropout on, a depth-3 step is five launches: site 0 is a pre-pass that writes the minibatch's dropped s6.bn to a workspace
+ * [max_batch, S6, S6, 128] float32, allocated when dropout is first switched on at depth 3.
+ *
+ * rn_ft_set_dropout   rate in [0, 1): else (NaN included) RN_E_RANGE, trainer unchanged.  rate 0: off -- the trainer runs launch for
+ *                     launch what it runs without this call.  Takes effect from the next rn_ft_run; rn_ft_eval never drops (the
+ *                     reference's infer feeds rate 0).  A failed workspace allocation is RN_E_NOMEM, trainer unchanged.
+ * rn_ft_dropout       the current rate and seed (0 and 0 on a new trainer); either pointer may be NULL.
+ * rn_ft_dropout_mask  the mask a step would use, at the trainer's current rate and seed, computed on the device: keep[0 .. count)
+ *                     on the host, 0 or 1, of elements [0, count) of `site` in `slot` at global step `step`.
+ *                     Errors: site 0 on a depth-2 trainer, or a site the graph lacks: RN_E_INVALID.
+ *                             count < 1 or beyond the site's size, slot outside [0, max_batch), or step < 0: RN_E_RANGE.
+ *                     rate 0: all ones. */
+RN_API int rn_ft_set_dropout(rn_ft* ft, float rate, uint64_t seed);
+RN_API int rn_ft_dropout(const rn_ft* ft, float* rate, uint64_t* seed);
+RN_API int rn_ft_dropout_mask(rn_ft* ft, int site, int64_t step, int slot, int64_t count, uint8_t* keep);
 
 /* ---- introspection -----------------------------------------------------------
  * rn_tap copies graph node `node_id` of the last forward call to host float32

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "rn_features_depth_shape", "rn_features_depth_u8", "rn_features_depth_u8_device",
     "rn_ft_create", "rn_ft_create_depth", "rn_ft_depth", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
+    "rn_ft_set_dropout", "rn_ft_dropout", "rn_ft_dropout_mask",
     "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
     "rn_jpeg_last_decode_ms",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
@@ -287,6 +288,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_ft_create_depth.restype = i32
         lib.rn_ft_depth.argtypes = [vp]
         lib.rn_ft_depth.restype = i32
+    if hasattr(lib, "rn_ft_set_dropout"):
+        lib.rn_ft_set_dropout.argtypes = [vp, C.c_float, C.c_uint64]
+        lib.rn_ft_set_dropout.restype = i32
+        lib.rn_ft_dropout.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        lib.rn_ft_dropout.restype = i32
+        lib.rn_ft_dropout_mask.argtypes = [vp, i32, C.c_int64, i32, C.c_int64, vp]
+        lib.rn_ft_dropout_mask.restype = i32
     if hasattr(lib, "rn_jpeg_probe"):
         lib.rn_jpeg_probe.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info)]
         lib.rn_jpeg_probe.restype = i32
@@ -924,12 +932,15 @@ class Trainer:
     GPU (include/roomnet_hip.h: fine-tuning).  Trains on features that stay resident in device memory: ``upload`` the
     ``[n_items, side, side, 16]`` float32 features of ``Engine.features_u8`` and the int32 labels once, then ``run``.
     ``depth=3`` (``rn_ft_create_depth``) trains the whole last conv block, stage 7 included, on the ``[n_items, side, side, 128]``
-    features of ``Engine.features_u8(..., depth=3)``: 1.08 MB per image at 224 against 28 KB at depth 2."""
+    features of ``Engine.features_u8(..., depth=3)``: 1.08 MB per image at 224 against 28 KB at depth 2.
+    ``dropout_rate`` in ``[0, 1)`` and ``dropout_seed`` (``rn_ft_set_dropout``) switch on dropout at every site at or behind the cached
+    feature (``finetune.dropout_sites``); the dropout behind the frozen stages upstream of the cache cannot be applied to cached
+    features.  ``eval`` never drops."""
 
     def __init__(self, graph: Graph, weights: Dict[str, np.ndarray], device: int = 0, max_batch: int = 64, learn_rate: float = 1e-4,
                  num_steps: int = 10000, start_step: int = 0, l2_coeff: float = 1e-2, decay_rate: float = 0.068,
                  beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, lib_path: Optional[str] = None,
-                 depth: int = 2):
+                 depth: int = 2, dropout_rate: float = 0.0, dropout_seed: int = 0):
         self.lib = load_library(lib_path)
         self.graph = graph
         self.depth = int(depth)
@@ -946,6 +957,12 @@ class Trainer:
                                                          C.byref(h)), "rn_ft_create_depth")
         self._h = h
         self._vars: Optional[List[Tuple[str, int]]] = None
+        if dropout_rate or dropout_seed:
+            try:
+                self.set_dropout(dropout_rate, dropout_seed)
+            except Exception:
+                self.close()
+                raise
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -1038,6 +1055,25 @@ class Trainer:
 
     def step_count(self) -> int:
         return int(self.lib.rn_ft_step_count(self.handle))
+
+    def set_dropout(self, rate: float, seed: int = 0) -> None:
+        """Dropout from the next ``run`` on (``rn_ft_set_dropout``): ``rate`` in ``[0, 1)``, 0 switches it off; ``seed``: 64 bits."""
+        _check(self.lib, self.lib.rn_ft_set_dropout(self.handle, C.c_float(rate), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)),
+               "rn_ft_set_dropout")
+
+    def dropout(self) -> Tuple[float, int]:
+        """``(rate, seed)`` as set (``rn_ft_dropout``); ``(0.0, 0)`` on a new trainer."""
+        rate, seed = C.c_float(0), C.c_uint64(0)
+        _check(self.lib, self.lib.rn_ft_dropout(self.handle, C.byref(rate), C.byref(seed)), "rn_ft_dropout")
+        return float(rate.value), int(seed.value)
+
+    def dropout_mask(self, site: int, step: int, slot: int, count: int) -> np.ndarray:
+        """The keep mask (uint8 ``[count]``, 0 or 1) that global step ``step`` would use for the first ``count`` elements of ``site``
+        in minibatch slot ``slot``, computed on the device (``rn_ft_dropout_mask``); ``finetune.dropout_keep`` states the same."""
+        keep = np.empty((max(int(count), 1),), np.uint8)
+        _check(self.lib, self.lib.rn_ft_dropout_mask(self.handle, int(site), int(step), int(slot), int(count), keep.ctypes.data),
+               "rn_ft_dropout_mask")
+        return keep[:count]
 
     def last_run_ms(self) -> float:
         """Device time of the last ``run``'s step loop (``rn_ft_last_run_ms``)."""

@@ -8,7 +8,8 @@
 // kernel, its BN's gamma and beta, gamma and beta of the BN behind the residual add; per dense block its kernel and its BN's gamma and
 // beta; the last dense layer's kernel and bias.  moving_mean / moving_variance are read and never written: every BN is the inference
 // BN y = (x - mean) rsqrt(var + eps) gamma + beta with trainable gamma and beta (the reference's shipped training configuration,
-// train.py:40-41: COMPUTE_BN_MEAN_VAR = False, UPDATE_BATCHNORM_MOVING_VARS = False).  No dropout.
+// train.py:40-41: COMPUTE_BN_MEAN_VAR = False, UPDATE_BATCHNORM_MOVING_VARS = False).  Dropout only where
+// rn_ft_set_dropout switches it on (rn_dropout.h: the generator and the sites; the end of this header: where it enters a step).
 //
 // Forward, per item, float32:  stage 8 (conv 3x3 VALID -> ReLU6 -> avg-pool 4/2 -> BN), stage 9 (the same, + legacy-bilinear
 // resize of x7 -> add -> BN), flatten, dense blocks x @ W [+ b] -> ReLU6 -> [BN]; the last block's ReLU6 is applied to the logits
@@ -53,6 +54,14 @@
 // Both depths pass the same FtItemArgs / FtUpdateArgs: the depth-3 fields are null or zero at depth 2, and the one variable list has
 // conv 7's three variables in front at depth 3.  The kernels are templates on the depth; the depth-2 instantiations run the code they
 // always did.
+//
+// Dropout (rn_ft_set_dropout, rate > 0; a trainer at rate 0 launches exactly the above).  The item kernel's third template parameter
+// DROP: fl is dropped where it is written (site 1), every hidden block's output behind its BN (site 2 + d), and the softmax, the CE
+// term and the argmax read the dropped relu6(z) (site 2 + L).  Adjoint: dL/dz_j = keep_j scale (p_j - [j == y]) where 0 < z_j < 6;
+// a hidden layer's dense adjoint is multiplied by keep scale BEFORE it feeds the d gamma / d beta partials and the ReLU6 mask; dL/dfl
+// gets site 1's factor before stage 9.  The partials' input vectors are the dropped ones.  At depth 3 ft7_drop_kernel writes the
+// minibatch's dropped s6.bn (site 0) in slot order in front of ft7_fwd_kernel: five launches.  rn_ft_eval never drops.
+#include "rn_dropout.h"
 #include "rn_finetune7.h"
 #include "rn_internal.h"
 #include "rn_lastblock.h"
@@ -104,6 +113,8 @@ struct FtItemArgs {
     float* dpool7;                   // [batch, S7, S7, 16] dL/dpool7 for ft7_bwd_kernel
     int64_t off_gadd;                // workspace: dL/d(stage 9's add), which the skip branch carries back to x7
     int o_g7, f_bn7, p_bn7;
+    // dropout (read by the DROP instantiation alone)
+    RnDropout drop;
 };
 
 // sum of `val` over the 32 threads that share channel tid & 15, in a fixed order; the result is valid for tid < 16
@@ -153,8 +164,11 @@ __device__ __forceinline__ void wgrad16(const float* in, int S, const float* dou
     __syncthreads();
 }
 
-template <bool TRAIN, bool D3>
+// DROP (training only): dropout at sites 1 and 2 + d of rn_dropout.h, every mask bit recomputed from the generator where it is read.
+// hx[0] (dense layer 0 reads fl) holds the dropped logits and hxh[L] (the last layer has no BN) their keep * scale.
+template <bool TRAIN, bool D3, bool DROP = false>
 __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
+    static_assert(TRAIN || !DROP, "evaluation never drops");
     __shared__ float w8[FT_W];
     __shared__ float w9[FT_W];
     __shared__ float tab[3 * 4 * LB_C];                  // bn8 | bn9 | bn9b, each [mean | rsq | gamma | beta]
@@ -231,7 +245,10 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
             xh9[i] = xh;
             xh9b[i] = xhb;
         }
-        fl[i] = fmaf(xhb, tab[160 + co], tab[176 + co]);
+        if constexpr (DROP)
+            fl[i] = rn_dropout_apply(a.drop, RN_DROP_SITE_FLAT, b, i, fmaf(xhb, tab[160 + co], tab[176 + co]));
+        else
+            fl[i] = fmaf(xhb, tab[160 + co], tab[176 + co]);
     }
     __syncthreads();
     // ---- dense head forward: each layer's dot products split over FT_NT / 64 groups of k, summed in a fixed order
@@ -248,7 +265,12 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
                     hxh[d][tid] = xh;
                     r = fmaf(xh, P[a.o_dg[d] + tid], P[a.o_dbeta[d] + tid]);
                 }
+                if constexpr (DROP) r = rn_dropout_apply(a.drop, RN_DROP_SITE_DENSE + d, b, tid, r);
                 hx[d + 1][tid] = r;
+            } else if constexpr (DROP) {
+                const bool keep = rn_dropout_keep(a.drop, RN_DROP_SITE_DENSE + d, b, tid);
+                hx[0][tid] = keep ? relu6f(t) * a.drop.scale : 0.f;
+                hxh[d][tid] = keep ? a.drop.scale : 0.f;
             }
         }
         __syncthreads();
@@ -258,22 +280,31 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
     if (tid == 0) {
         const int nc = a.nc;
         const float* z = hmm[L];
-        float mx = relu6f(z[0]);
+        // the logits the softmax, the CE term and the argmax read: relu6(z), behind the last block's dropout with DROP
+        auto logit = [&](int j) {
+            if constexpr (DROP)
+                return hx[0][j];
+            else
+                return relu6f(z[j]);
+        };
+        float mx = logit(0);
         int best = 0;
         for (int j = 1; j < nc; ++j) {
-            const float r = relu6f(z[j]);
+            const float r = logit(j);
             if (r > mx) {
                 mx = r;
                 best = j;
             }
         }
         double se = 0.0;
-        for (int j = 0; j < nc; ++j) se += exp(static_cast<double>(relu6f(z[j])) - static_cast<double>(mx));
+        for (int j = 0; j < nc; ++j) se += exp(static_cast<double>(logit(j)) - static_cast<double>(mx));
         const int y = a.labels ? a.labels[item] : -1;
-        if (y >= 0) a.item_loss[b] = log(se) - (static_cast<double>(relu6f(z[y])) - static_cast<double>(mx));
+        if (y >= 0) a.item_loss[b] = log(se) - (static_cast<double>(logit(y)) - static_cast<double>(mx));
         for (int j = 0; j < nc; ++j) {
-            const float p = static_cast<float>(exp(static_cast<double>(relu6f(z[j])) - static_cast<double>(mx)) / se);
-            if (TRAIN)
+            const float p = static_cast<float>(exp(static_cast<double>(logit(j)) - static_cast<double>(mx)) / se);
+            if constexpr (DROP)
+                hg[L & 1][j] = relu6_passes(z[j]) && hxh[L][j] != 0.f ? (p - (j == y ? 1.f : 0.f)) * hxh[L][j] : 0.f;
+            else if (TRAIN)
                 hg[L & 1][j] = relu6_passes(z[j]) ? p - (j == y ? 1.f : 0.f) : 0.f;
             else
                 a.probs[b * nc + j] = p;
@@ -295,6 +326,7 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
             for (int k = tid; k < nin; k += FT_NT) {
                 prt[a.p_x[d] + k] = xin[k];
                 float v = dense_adjoint_at(W, nout, gz, k);
+                if constexpr (DROP) v = rn_dropout_apply(a.drop, d == 0 ? RN_DROP_SITE_FLAT : RN_DROP_SITE_DENSE + d - 1, b, k, v);
                 if (d == 0) {
                     gfl[k] = v;
                 } else {
@@ -413,6 +445,42 @@ __global__ __launch_bounds__(FT_NT) void ft_item_kernel(const FtItemArgs a) {
     }
 }
 
+// Site 0 of rn_dropout.h, the pre-pass of a depth-3 step with dropout: slot b's dropped copy of item index[base + b] of the resident
+// cache, x6d[b] [S6, S6, 128].  ft7_fwd_kernel and ft7_bwd_kernel then read x6d in slot order: each x6 element is read by nine taps
+// in both, and the generator at every read would cost more than this copy.  One thread handles four consecutive floats (one generator
+// call, one 16-byte load, one 16-byte store); an item is a whole number of such quads.
+struct Ft7DropArgs {
+    const float* feats;              // the resident cache [n_items, S6, S6, 128]
+    const int32_t* index;            // item of slot b = index[base + b]
+    int64_t base;
+    int64_t item_quads;              // S6 * S6 * 128 / 4
+    int64_t total_quads;             // batch * item_quads
+    float* x6d;                      // [batch, S6, S6, 128]
+    RnDropout drop;
+};
+
+__global__ __launch_bounds__(256) void ft7_drop_kernel(const Ft7DropArgs a) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+    for (int64_t q = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; q < a.total_quads; q += stride) {
+        const int64_t b = q / a.item_quads, qi = q - b * a.item_quads;
+        const int64_t item = a.index[a.base + b];
+        const f32x4 x = reinterpret_cast<const f32x4*>(a.feats)[item * a.item_quads + qi];
+        uint32_t w[4];
+        rn_dropout_words(a.drop, RN_DROP_SITE_X6, static_cast<uint32_t>(b), static_cast<uint32_t>(qi), w);
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = rn_dropout_word_keeps(a.drop, w[k]) ? x[k] * a.drop.scale : 0.f;
+        reinterpret_cast<f32x4*>(a.x6d)[q] = y;
+    }
+}
+
+// keep bytes of elements [0, count) of (site, slot) for rn_ft_dropout_mask
+__global__ __launch_bounds__(256) void ft_mask_kernel(const RnDropout drop, int site, int slot, int64_t count, uint8_t* keep) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < count; e += stride)
+        keep[e] = rn_dropout_keep(drop, static_cast<uint32_t>(site), static_cast<uint32_t>(slot), static_cast<uint32_t>(e)) ? 1 : 0;
+}
+
 // how the update kernel forms one variable's gradient from the items' partials
 enum { FT_SUM = 0, FT_OUTER = 1, FT_BANDS = 2 };
 struct FtVarDev {
@@ -517,6 +585,11 @@ struct rn_ft {
     int64_t steps_done = 0;                        // t of the next step is steps_done + 1; global step = start_step + steps_done
     std::vector<void*> allocs;                     // trainer-owned device memory (freed by rn_ft_destroy)
     std::vector<void*> user;                       // rn_ft_upload buffers not yet freed
+    // dropout (rn_ft_set_dropout): rate 0 is off and runs the launches a trainer without it runs
+    float drop_rate = 0.f;
+    uint64_t drop_seed = 0;
+    RnDropout drop{};                              // key, threshold and scale; the step is set per launch
+    float* d_x6d = nullptr;                        // depth 3: [max_batch, S6, S6, 128], allocated when dropout is first switched on
 };
 
 namespace {
@@ -955,6 +1028,17 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
     const int ublocks = (ft->n_param + 255) / 256;
     const bool d3 = ft->depth == 3;
+    const bool dropping = ft->drop.thr != 0;
+    Ft7DropArgs dr{};
+    int dblocks = 0;
+    if (d3 && dropping) {
+        dr.feats = d_feats;
+        dr.index = d_index;
+        dr.item_quads = static_cast<int64_t>(ft->sd.S6) * ft->sd.S6 * (LB_CIN7 / 4);
+        dr.total_quads = dr.item_quads * batch;
+        dr.x6d = ft->d_x6d;
+        dblocks = static_cast<int>(std::min<int64_t>((dr.total_quads + 255) / 256, 8192));
+    }
     ft->timed = false;
     RN_HIP(hipEventRecord(ft->ev0, ft->stream));
     for (int s = 0; s < steps; ++s) {
@@ -963,7 +1047,33 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
         u.lr_t = static_cast<float>(lr * std::sqrt(1.0 - std::pow(b2, static_cast<double>(t))) / (1.0 - std::pow(b1, static_cast<double>(t))));
         u.loss_out = ft->d_losses + s;
         a.base = static_cast<int64_t>(s) * batch;
-        if (d3) {
+        if (dropping) {
+            const uint64_t gstep = static_cast<uint64_t>(ft->cfg.start_step + ft->steps_done);
+            a.drop = ft->drop;
+            a.drop.step_lo = static_cast<uint32_t>(gstep);
+            a.drop.step_hi = static_cast<uint32_t>(gstep >> 32);
+        }
+        if (d3 && dropping) {
+            // five launches: the dropped copy of the step's s6.bn, then the four of a depth-3 step on it in slot order
+            int rc;
+            dr.base = a.base;
+            dr.drop = a.drop;
+            hipLaunchKernelGGL(ft7_drop_kernel, dim3(dblocks), dim3(256), 0, ft->stream, dr);
+            RN_CHECK_LAUNCH();
+            const Ft7Args s7 = ft7_call(ft, ft->d_x6d, nullptr, 0, batch);
+            if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
+            hipLaunchKernelGGL((ft_item_kernel<true, true, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
+            RN_CHECK_LAUNCH();
+            if ((rc = rn_ft7_backward(ft->stream, s7, batch)) != RN_OK) return rc;
+            u.bands = s7.bands_b;
+            hipLaunchKernelGGL(ft_update_kernel<true>, dim3(ublocks), dim3(256), 0, ft->stream, u);
+            RN_CHECK_LAUNCH();
+        } else if (dropping) {
+            hipLaunchKernelGGL((ft_item_kernel<true, false, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
+            RN_CHECK_LAUNCH();
+            hipLaunchKernelGGL(ft_update_kernel<false>, dim3(ublocks), dim3(256), 0, ft->stream, u);
+            RN_CHECK_LAUNCH();
+        } else if (d3) {
             int rc;
             const Ft7Args s7 = ft7_call(ft, d_feats, d_index, a.base, batch);
             if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
@@ -1108,3 +1218,89 @@ extern "C" int rn_ft_last_run_ms(rn_ft* ft, float* ms) {
 }
 
 extern "C" int64_t rn_ft_step_count(const rn_ft* ft) { return ft ? ft->cfg.start_step + ft->steps_done : -1; }
+
+// ---- dropout
+extern "C" int rn_ft_set_dropout(rn_ft* ft, float rate, uint64_t seed) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    if (!(rate >= 0.f && rate < 1.f)) {
+        rn_set_error("rn_ft_set_dropout: rate = %g outside [0, 1)", static_cast<double>(rate));
+        return RN_E_RANGE;
+    }
+    if (rate > 0.f && ft->depth == 3 && !ft->d_x6d) {
+        DeviceGuard guard(ft->device);
+        const size_t n6 = static_cast<size_t>(ft->sd.S6) * ft->sd.S6 * LB_CIN7;
+        int rc = ft_zeroed(ft, static_cast<size_t>(ft->max_batch) * n6, &ft->d_x6d);
+        if (rc != RN_OK) {
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    ft->drop_rate = rate;
+    ft->drop_seed = seed;
+    ft->drop = RnDropout{};
+    ft->drop.key0 = static_cast<uint32_t>(seed);
+    ft->drop.key1 = static_cast<uint32_t>(seed >> 32);
+    ft->drop.thr = static_cast<uint32_t>(std::ceil(static_cast<double>(rate) * 16777216.0));
+    ft->drop.scale = 1.0f / (1.0f - rate);
+    return RN_OK;
+}
+
+extern "C" int rn_ft_dropout(const rn_ft* ft, float* rate, uint64_t* seed) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    if (rate) *rate = ft->drop_rate;
+    if (seed) *seed = ft->drop_seed;
+    return RN_OK;
+}
+
+extern "C" int rn_ft_dropout_mask(rn_ft* ft, int site, int64_t step, int slot, int64_t count, uint8_t* keep) {
+    if (!ft || !keep) {
+        rn_set_error("rn_ft_dropout_mask: null argument");
+        return RN_E_INVALID;
+    }
+    const int n_dense = ft->item.n_dense;
+    if (site < (ft->depth == 3 ? 0 : 1) || site >= RN_DROP_SITE_DENSE + n_dense) {
+        rn_set_error("rn_ft_dropout_mask: a depth-%d trainer with %d dense blocks has no site %d", ft->depth, n_dense, site);
+        return RN_E_INVALID;
+    }
+    const int64_t size = site == RN_DROP_SITE_X6     ? static_cast<int64_t>(ft->sd.S6) * ft->sd.S6 * LB_CIN7
+                         : site == RN_DROP_SITE_FLAT ? static_cast<int64_t>(ft->sd.S9) * ft->sd.S9 * LB_C
+                                                     : ft->item.nout[site - RN_DROP_SITE_DENSE];
+    if (count < 1 || count > size) {
+        rn_set_error("rn_ft_dropout_mask: count = %lld outside [1, %lld] of site %d", static_cast<long long>(count),
+                     static_cast<long long>(size), site);
+        return RN_E_RANGE;
+    }
+    if (slot < 0 || slot >= ft->max_batch) {
+        rn_set_error("rn_ft_dropout_mask: slot = %d outside [0, %d)", slot, ft->max_batch);
+        return RN_E_RANGE;
+    }
+    if (step < 0) {
+        rn_set_error("rn_ft_dropout_mask: step = %lld", static_cast<long long>(step));
+        return RN_E_RANGE;
+    }
+    DeviceGuard guard(ft->device);
+    (void)hipGetLastError();
+    RnDropout d = ft->drop;
+    d.step_lo = static_cast<uint32_t>(static_cast<uint64_t>(step));
+    d.step_hi = static_cast<uint32_t>(static_cast<uint64_t>(step) >> 32);
+    uint8_t* d_keep = nullptr;
+    RN_HIP(hipMalloc(reinterpret_cast<void**>(&d_keep), static_cast<size_t>(count)));
+    const int blocks = static_cast<int>(std::min<int64_t>((count + 255) / 256, 4096));
+    hipLaunchKernelGGL(ft_mask_kernel, dim3(blocks), dim3(256), 0, ft->stream, d, site, slot, count, d_keep);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, static_cast<size_t>(count), hipMemcpyDeviceToHost, ft->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ft->stream);
+    (void)hipFree(d_keep);
+    if (e != hipSuccess) {
+        rn_set_error("rn_ft_dropout_mask: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
+        return RN_E_HIP;
+    }
+    return RN_OK;
+}

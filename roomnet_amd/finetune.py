@@ -1,6 +1,7 @@
 """Host side of fine-tuning the last conv stages and the dense head (``RoomNet.fine_tune``, C ABI ``rn_ft_*``): which variables are
-trained, the learning-rate schedule, the minibatch order and a NumPy statement of the Adam rule.  Pure host code; the
-mathematics is stated once in the headers of ``csrc/rn_finetune.hip`` and ``csrc/rn_finetune7.hip``.
+trained, the learning-rate schedule, the minibatch order and a NumPy statement of the Adam rule, and the dropout stream (``philox4x32``, ``dropout_keep``): the product's statement of the masks the kernels
+recompute, as ``jpegenc.py`` is for the encoder.  Pure host code; the mathematics is stated once in the headers of
+``csrc/rn_finetune.hip``, ``csrc/rn_finetune7.hip`` and ``csrc/rn_dropout.h``.
 
 The *depth* of a trainer or a feature is its number of trained conv stages: 2 trains stages 8-9 on cached ``s7.bn`` (28 KB per
 image at 224), 3 trains the whole last block, stages 7-9, on cached ``s6.bn`` (1.08 MB per image at 224)."""
@@ -97,3 +98,77 @@ def adam_update(param, grad, m, v, t, lr, beta1=ADAM_BETA1, beta2=ADAM_BETA2, ep
     m = np.asarray(m, dt) + (g - np.asarray(m, dt)) * dt.type(1.0 - beta1)
     v = np.asarray(v, dt) + (g * g - np.asarray(v, dt)) * dt.type(1.0 - beta2)
     return param - lr_t * m / (np.sqrt(v) + dt.type(epsilon)), m, v
+
+
+# ---- dropout (csrc/rn_dropout.h, include/roomnet_hip.h: dropout while fine-tuning)
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key, rounds=10):
+    """Philox4x32-10 as published (Salmon et al., SC'11).  ``counter``: four 32-bit words, or an array ``[..., 4]`` of them;
+    ``key``: two 32-bit words.  Returns uint32 of ``counter``'s shape."""
+    c = np.asarray(counter, np.uint64) & _M32
+    if c.shape[-1] != 4:
+        raise ValueError("philox4x32: the counter has four words, got shape %s" % (c.shape,))
+    c0, c1, c2, c3 = (c[..., i].copy() for i in range(4))
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(rounds):
+        p0 = np.uint64(PHILOX_M0) * c0                       # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & _M32
+        k0, k1 = (k0 + PHILOX_W0) & 0xFFFFFFFF, (k1 + PHILOX_W1) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _checked_rate(rate) -> np.float32:
+    r = np.float32(rate)
+    if not (r >= 0 and r < 1):
+        raise ValueError("dropout_rate = %r outside [0, 1)" % (rate,))
+    return r
+
+
+def dropout_threshold(rate) -> int:
+    """``ceil(float32(rate) * 2^24)``: an element is kept iff its 24-bit value ``k >= threshold``, i.e. ``k * 2^-24 >= rate``."""
+    return int(np.ceil(np.float64(_checked_rate(rate)) * 16777216.0))
+
+
+def dropout_scale(rate) -> np.float32:
+    """``1 / (1 - rate)`` as one float32 division: what a kept value is multiplied by."""
+    return np.float32(1.0) / (np.float32(1.0) - _checked_rate(rate))
+
+
+def dropout_sites(graph: Graph, depth: int = 2):
+    """``{site: (name, size)}`` of the dropout sites of a trainer: every site at or behind the cached feature.  Site 0 (depth 3
+    only) is ``s6.bn``, NHWC within the item; site 1 the last conv block's output as dense 0 reads it; site ``2 + d`` the output of
+    dense block ``d`` (the last block's logits included).  The reference's dropout behind the frozen conv blocks upstream of the
+    cache cannot be applied to cached features and is not there."""
+    depth = _checked_depth(depth)
+    sites = {}
+    if depth == 3:
+        s6 = graph.stages[-4]
+        sites[0] = ("s%d.bn" % s6.index, s6.out_side * s6.out_side * s6.cout)
+    s9 = graph.stages[-1]
+    sites[1] = ("flat", s9.out_side * s9.out_side * s9.cout)
+    for d, layer in enumerate(graph.dense):
+        sites[2 + d] = (layer.name, int(layer.nout))
+    return sites
+
+
+def dropout_keep(seed, step, slot, site, count, rate) -> np.ndarray:
+    """The keep mask (bool ``[count]``) of elements ``0 .. count - 1`` of ``site`` in minibatch slot ``slot`` at global step
+    ``step``: key ``(seed & 0xffffffff, seed >> 32)``, counter ``(e >> 2, slot, step & 0xffffffff, site | (step >> 32) << 8)``,
+    word ``e & 3`` of the output, kept iff ``word >> 8 >= dropout_threshold(rate)``."""
+    seed, step, count = int(seed), int(step), int(count)
+    if seed < 0 or seed >> 64 or step < 0 or count < 0:
+        raise ValueError("dropout_keep: seed %d, step %d, count %d" % (seed, step, count))
+    thr = dropout_threshold(rate)
+    quads = (count + 3) // 4
+    ctr = np.empty((quads, 4), np.uint64)
+    ctr[:, 0] = np.arange(quads, dtype=np.uint64)
+    ctr[:, 1] = int(slot)
+    ctr[:, 2] = step & 0xFFFFFFFF
+    ctr[:, 3] = (int(site) | ((step >> 32) << 8)) & 0xFFFFFFFF
+    words = philox4x32(ctr, (seed & 0xFFFFFFFF, seed >> 32)).reshape(-1)[:count]
+    return (words >> np.uint32(8)) >= np.uint32(thr)

@@ -123,6 +123,7 @@ class RoomNet:
         self.l2_regularizer_coeff = l2_regularizer_coeff
         self.num_steps = num_steps
         self.dropout_enabled = False if optimized_inference else dropout_enabled
+        self.dropout_rate = dropout_rate          # what fine_tune(..., dropout_rate=nn.dropout_rate) passes on
         self.model_folder = 'all_trained_models/trained_models'
         self.model_fpath_prefix = self.model_folder + '/' + 'roomnet-'
         if compute_bn_mean_var:
@@ -614,7 +615,7 @@ class RoomNet:
                 raise ValueError("extract_features takes uint8 images (or integral values in [0, 255]), got %s" % im.dtype)
         return self._engine().features_u8(im, depth=depth)
 
-    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None):
+    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None, dropout_rate=None):
         """Train stages 8 and 9 and the dense head on cached features, on the GPU (``rn_ft_*``; not the reference's whole-network
         ``train_step``): stages 0-7 stay as loaded, every BN keeps its moving statistics and trains gamma and beta (the
         reference's shipped configuration, train.py:40-41), Adam with the constructor's ``learn_rate``, ``num_steps`` (decay),
@@ -626,11 +627,27 @@ class RoomNet:
         depth, or one that contradicts an explicit ``depth``, raises ``ValueError``.
         The trained variables are written back through ``set_variables`` (the next ``infer`` builds its engine on them, ``save()``
         writes them) and ``self.step`` advances.  Returns ``{"losses": float32[steps] (each before its update), "step",
-        "learn_rate" (at the new step), "val": (loss, accuracy) or None}``.  Adam's slots start at zero in every call."""
+        "learn_rate" (at the new step), "val": (loss, accuracy) or None}``.  Adam's slots start at zero in every call.
+        ``dropout_rate``: a float in ``[0, 1)`` trains with dropout at every site at or behind the cached feature
+        (``finetune.dropout_sites``: the last conv block's output and every dense block's, at depth 3 the cached ``s6.bn`` as well),
+        whatever the constructor's ``dropout_enabled``, with ``seed`` as the dropout seed.  The reference's dropout behind the frozen
+        conv blocks upstream of the cache cannot be applied to cached features, which is why the opt-in is explicit: a net
+        constructed with ``dropout_enabled=True`` raises ``ValueError`` unless the argument is given, e.g.
+        ``nn.fine_tune(f, y, steps, dropout_rate=nn.dropout_rate)``.  ``val`` and inference never drop."""
         from . import finetune
         from ._capi import Trainer
-        if self.dropout_enabled:
-            raise ValueError("fine_tune: dropout is not implemented on the GPU path; construct with dropout_enabled=False")
+        if dropout_rate is None:
+            if self.dropout_enabled:
+                raise ValueError("fine_tune: dropout on the GPU path covers the sites at or behind the cached feature only and is "
+                                 "asked for explicitly: pass dropout_rate= (e.g. dropout_rate=nn.dropout_rate), or construct "
+                                 "with dropout_enabled=False")
+        else:
+            try:
+                dropout_rate = float(dropout_rate)
+            except (TypeError, ValueError):
+                raise ValueError("fine_tune: dropout_rate = %r is not a number" % (dropout_rate,)) from None
+            if not (0.0 <= dropout_rate < 1.0):
+                raise ValueError("fine_tune: dropout_rate = %r outside [0, 1)" % (dropout_rate,))
         if not self.sess:
             raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
         feats = np.ascontiguousarray(features, np.float32)
@@ -654,7 +671,8 @@ class RoomNet:
         index = finetune.epoch_indices(feats.shape[0], batch_size, steps, seed=[int(seed), int(self.step)])
         tr = Trainer(self.graph, self.sess.variables, device=self.device, max_batch=max(index.shape[1], min(self.max_batch, 256)),
                      learn_rate=self.learn_rate, num_steps=self.num_steps, start_step=self.step,
-                     l2_coeff=self.l2_regularizer_coeff, depth=depth)
+                     l2_coeff=self.l2_regularizer_coeff, depth=depth, dropout_rate=dropout_rate or 0.0,
+                     dropout_seed=int(seed) if dropout_rate else 0)
         try:
             losses = tr.run_host(feats, labels, index)
             out_val = None

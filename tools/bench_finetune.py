@@ -8,7 +8,13 @@
 items at 224 and 48 at 600 -- an item is 1.08 MB and 10 MB) against the float32 torch restatement tests/finetune7_ref.py, and states
 each step against its arithmetic floor.  --lib PATH measures another build of the library (depth 2 of the commit before, say).
 
+--dropout RATE measures, at batch 45 / 224 and both depths in one session with the arms alternating run by run, the step with
+dropout off beside the step with dropout on (rn_ft_set_dropout) -- and, with --lib PATH, beside the dropout-off step of that other
+build, a parent-commit build for instance -- and states whether this build's dropout-off range overlaps the other build's.  With
+--trace-run / --summarise it is the five launches of a depth-3 step with dropout (ft7_drop_kernel in front) that are traced.
+
     python tools/bench_finetune.py [--depth 3] [--steps 200] [--runs 5] [--steps-only] [--lib PATH]
+    python tools/bench_finetune.py --dropout 0.35 [--lib PARENT_BUILD.so] [--steps 200] [--runs 7]
     rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py [--depth 3] --trace-run
     python tools/bench_finetune.py [--depth 3] --summarise DIR/.../kt_kernel_trace.csv [--out profiles/finetune_kernel_stats.txt]
 """
@@ -28,6 +34,8 @@ sys.path.insert(0, ROOT)
 CASES = ((224, 45), (224, 256), (600, 45))
 N_ITEMS = 512
 KERNELS = {2: ("ft_item_kernel", "ft_update_kernel"), 3: ("ft7_fwd_kernel", "ft_item_kernel", "ft7_bwd_kernel", "ft_update_kernel")}
+DROP_KERNEL = "ft7_drop_kernel"                  # depth 3 with dropout: the pre-pass in front of the four
+DROP_CASES = ((224, 45),)
 F32_MFMA_TFLOPS = 155.0                          # float32 MFMA = the float32 vector rate (measured peak of the part)
 HBM_TBPS = 6.0
 
@@ -67,7 +75,48 @@ def step_floor(g, batch):
             "cache_read_mb": round(cache / 1e6, 1), "hbm_floor_us": round(cache / HBM_TBPS / 1e6, 1)}
 
 
-def step_case(side, batch, steps, runs, depth=2, lib=None):
+def dropout_case(side, batch, steps, runs, depth, rate, lib=None):
+    """Dropout off, dropout on and (``lib``) the other build's dropout off on the same data: one trainer per arm, a warm-up run
+    each, then ``runs`` rounds in which every arm runs once, in an order that rotates from round to round, so that drift of the
+    clocks and whatever an arm inherits from the one before it hit all arms alike."""
+    from roomnet_amd import _capi, finetune
+    g, w = _weights(side)
+    n_items = n_items_of(side, depth)
+    feats, labels = _data(g, n_items, depth)
+    index = finetune.epoch_indices(n_items, batch, steps, seed=1)
+    arms = [("off", None, 0.0), ("on", None, rate)] + ([("other_off", lib, 0.0)] if lib else [])
+    trainers, us = {}, {name: [] for name, _, _ in arms}
+    try:
+        for name, path, r in arms:
+            tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06, lib_path=path, depth=depth)
+            trainers[name] = (tr, [tr.upload(feats), tr.upload(labels), tr.upload(index)])
+            if r:
+                tr.set_dropout(r, 1)
+        del feats
+        for r in range(runs + 1):                                   # the first round is the warm-up
+            k = r % len(arms)                                       # the order rotates, so that no arm always follows the same one
+            for name, _, _ in arms[k:] + arms[:k]:
+                tr, d = trainers[name]
+                tr.run(d[0], d[1], n_items, d[2], batch, steps)
+                us[name].append(tr.last_run_ms() * 1e3 / steps)
+        out = {"side": side, "batch": batch, "depth": depth, "steps_per_run": steps, "runs": runs, "rate": rate}
+        for name in us:
+            v = us[name][1:]
+            out[name] = {"us_per_step": round(statistics.median(v), 2), "us_per_step_min": round(min(v), 2),
+                         "us_per_step_max": round(max(v), 2)}
+        if lib:
+            a, b = out["off"], out["other_off"]
+            out["off_ranges_overlap"] = bool(a["us_per_step_min"] <= b["us_per_step_max"] and b["us_per_step_min"] <= a["us_per_step_max"])
+        out["on_inside_off_range"] = bool(out["off"]["us_per_step_min"] <= out["on"]["us_per_step"] <= out["off"]["us_per_step_max"])
+        if depth == 3:
+            out["ft7_drop_kernel_bytes"] = 2 * batch * g.stages[-4].out_side ** 2 * g.stages[-3].cin * 4
+        return out
+    finally:
+        for tr, _ in trainers.values():
+            tr.close()
+
+
+def step_case(side, batch, steps, runs, depth=2, lib=None, dropout=0.0):
     from roomnet_amd import _capi, finetune
     g, w = _weights(side)
     n_items = n_items_of(side, depth)
@@ -76,6 +125,8 @@ def step_case(side, batch, steps, runs, depth=2, lib=None):
     kw = {"depth": depth} if depth != 2 else {}
     tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06, lib_path=lib, **kw)
     try:
+        if dropout:
+            tr.set_dropout(dropout, 1)
         d = [tr.upload(feats), tr.upload(labels), tr.upload(index)]
         del feats
         tr.run(d[0], d[1], n_items, d[2], batch, steps)            # warm-up
@@ -147,16 +198,17 @@ def torch_case(batch=45, steps=5, threads=16, depth=2):
     return {"side": 224, "batch": batch, "threads": threads, "ms_per_step": round((time.perf_counter() - t0) * 1e3 / steps, 2)}
 
 
-def trace_run(depth=2):
-    for side, batch in CASES:
-        step_case(side, batch, TRACE_STEPS, 1, depth)
+def trace_run(depth=2, dropout=0.0):
+    for side, batch in (DROP_CASES if dropout else CASES):
+        step_case(side, batch, TRACE_STEPS, 1, depth, dropout=dropout)
 
 
 TRACE_STEPS = 20                                  # steps per rn_ft_run of --trace-run (a warm-up run and a measured one per case)
 
 
-def summarise(trace_csv, depth=2):
-    kernels = KERNELS[depth]
+def summarise(trace_csv, depth=2, dropout=0.0):
+    kernels = ((DROP_KERNEL,) if dropout and depth == 3 else ()) + KERNELS[depth]
+    cases = DROP_CASES if dropout else CASES
     rows = []
     for r in csv.DictReader(open(trace_csv)):
         for key in kernels:
@@ -166,21 +218,21 @@ def summarise(trace_csv, depth=2):
                              (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     rows.sort()
     per_case = 2 * len(kernels) * TRACE_STEPS     # the cases run one after the other: two runs x the launches of a step
-    if len(rows) != per_case * len(CASES):
-        raise SystemExit("expected %d ft_* launches (%d cases), found %d" % (per_case * len(CASES), len(CASES), len(rows)))
-    lines = ["# rocprofv3 --kernel-trace --stats -- python tools/bench_finetune.py%s --trace-run (one MI355X, its own run)"
-             % (" --depth 3" if depth == 3 else ""),
+    if len(rows) != per_case * len(cases):
+        raise SystemExit("expected %d ft_* launches (%d cases), found %d" % (per_case * len(cases), len(cases), len(rows)))
+    lines = ["# rocprofv3 --kernel-trace --stats -- python tools/bench_finetune.py%s%s --trace-run (one MI355X, its own run)"
+             % (" --depth 3" if depth == 3 else "", " --dropout %g" % dropout if dropout else ""),
              "# the %s launches of an Adam step per case: workgroups, calls, median / max duration in us, and the step's sum"
-             % ("two" if depth == 2 else "four"),
+             % {2: "two", 4: "four", 5: "five"}[len(kernels)],
              "%5s %6s  %-17s %6s %6s %11s %9s" % ("side", "batch", "kernel", "wgs", "calls", "median_us", "max_us")]
-    for ci, (side, batch) in enumerate(CASES):
+    for ci, (side, batch) in enumerate(cases):
         total = 0.0
         for key in kernels:
             sel = [r for r in rows[ci * per_case:(ci + 1) * per_case] if r[1] == key]
             us = [r[3] for r in sel]
             total += statistics.median(us)
             lines.append("%5d %6d  %-17s %6d %6d %11.1f %9.1f" % (side, batch, key, sel[0][2], len(us), statistics.median(us), max(us)))
-        lines.append("%5d %6d  %-17s %6s %6s %11.1f" % (side, batch, "both" if depth == 2 else "all four", "", "", total))
+        lines.append("%5d %6d  %-17s %6s %6s %11.1f" % (side, batch, {2: "both", 4: "all four", 5: "all five"}[len(kernels)], "", "", total))
     return "\n".join(lines) + "\n"
 
 
@@ -194,17 +246,28 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--depth", type=int, default=2, choices=(2, 3), help="trained conv stages: 2 (features s7.bn) or 3 (s6.bn)")
     ap.add_argument("--lib", help="measure this build of libroomnet_hip.so instead of the package's")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="RATE",
+                    help="the dropout-on arm beside the dropout-off arm (and beside --lib's dropout-off arm) at both depths")
     args = ap.parse_args()
     if not args.summarise:
         import torch  # noqa: F401  (before libroomnet_hip.so is loaded: one HIP runtime in the process, torch's)
     if args.summarise:
-        text = summarise(args.summarise, args.depth)
+        text = summarise(args.summarise, args.depth, args.dropout)
         if args.out:
             open(args.out, "w").write(text)
         print(text, end="")
         return
     if args.trace_run:
-        trace_run(args.depth)
+        trace_run(args.depth, args.dropout)
+        return
+    if args.dropout:
+        print(json.dumps({"what": "fine-tuning with dropout: us per Adam step at batch 45 / 224, dropout off, dropout on at rate %g and "
+                                  "(other_off) dropout off of the build given with --lib, the arms alternating run by run in one "
+                                  "session; ft7_drop_kernel moves ft7_drop_kernel_bytes per step (one read and one write of the "
+                                  "minibatch's s6.bn)" % args.dropout,
+                          "other_lib": args.lib,
+                          "cases": [dropout_case(s, b, args.steps, args.runs, depth, args.dropout, args.lib)
+                                    for depth in (2, 3) for s, b in DROP_CASES]}))
         return
     if args.steps_only:
         print(json.dumps({"depth": args.depth, "lib": args.lib,

@@ -1,0 +1,210 @@
+"""CPU evidence that the GPU tests of the backward passes on `live` (tests/test_hip_backward_live.py) can see what they claim to see.
+
+The three backward passes -- the trainers at depth 2 and 3 and grad-CAM -- share ``relu6_passes(v) = v > 0 && v < 6``, the pool
+adjoint and the BN factors.  From the shipped checkpoint (and from "fresh", which keeps its conv trunk) no pre-activation of conv 7,
+8, 9 or of the hidden dense blocks comes near 6 and no trained gamma is negative, so a mask without its upper end, or a BN adjoint
+that multiplies by |gamma|, changes no gradient there: by exactly 0, asserted below on the references.  On
+``CK.live(graph, 0, CK.LIVE_GAIN)`` the same two mutants move most of the 22 gradients by more than 1000 x the GPU tests' bound.
+
+Then every condition the GPU file puts on its inputs (tests/backward_ref.py states the cases once, for both files): both signs of
+gamma in every trained BN, a share at the clamp and a share inside (0, 6), no float64 pre-activation of conv 8, conv 9 or the head
+within DELTA[site] = 4 x the float32 torch yardstick's error of 0 or 6, conv 7's near-kink share under the project's cap, live
+gradients -- and, at one class, gradients that are exactly zero.  The yardstick's figures are printed."""
+import numpy as np
+import pytest
+import torch
+
+import backward_ref as BR
+import checkpoints as CK
+from conftest import parity_set_of
+from finetune7_ref import FineTune7Ref
+from gradcam_ref import GradCamRef
+from oracle import c_oracle, roomnet_ref as R
+from roomnet_amd.graph import build_graph
+from roomnet_amd.network import _initializer_values
+from test_checkpoints_host import AT_CLAMP_MIN, INSIDE_MIN
+from test_hip_other_checkpoints import TIE_EDGE
+
+ITEMS_32 = list(range(0, 8)) + list(range(40, 64))          # the 32 parity items of the shipped-checkpoint backward tests
+VISIBLE = 1000 * BR.GRAD_TOL                                # a change the GPU tests cannot miss
+
+
+@pytest.fixture(scope="module")
+def taps64(parity_images):
+    """The float64 oracle's taps of the four items on `live` (the conv trunk is the same at every head width)."""
+    return R.infer(BR.live_weights(6, 224), parity_images[BR.ITEMS], dtype=np.float64, taps=True)["taps"]
+
+
+@pytest.fixture(scope="module")
+def shipped32(weights, parity_images):
+    """s6.bn of the 32 items from the shipped checkpoint (the C oracle), their labels, and the two starts."""
+    x6 = c_oracle.infer(weights, np.ascontiguousarray(parity_images[ITEMS_32]), taps=True)["taps"]["s6.bn"]
+    g = build_graph(6, 224)
+    fresh = dict(weights)
+    init = _initializer_values(g, seed=1)
+    for d in g.dense:
+        for name in init:
+            if name.startswith(d.name + "/") or (d.bn_name and name.startswith(d.bn_name + "/")):
+                fresh[name] = init[name]
+    return x6, np.arange(32, dtype=np.int32) % 6, {"shipped": weights, "fresh": fresh}
+
+
+MUTANTS = {"open_masks": BR.open_masks, "abs_gamma_adjoint": BR.abs_gamma_adjoint}
+
+
+# ---------------------------------------------------------------------------------------------- the helpers themselves
+@pytest.mark.parametrize("depth,rate", [(2, 0.0), (3, 0.0), (2, BR.DROP_RATE), (3, BR.DROP_RATE)])
+def test_pre_activations_restate_the_reference_forward(taps64, depth, rate):
+    """``pre_activations`` walks the forward pass itself: its last step must be ``ref.logits`` bit for bit, in both arithmetics,
+    and each site's tensor has the site's shape."""
+    case = dict(BR.cases("one_step")[0], depth=depth, rate=rate, batch=3)
+    w, x, y, idx = BR.case_inputs(case, taps64)
+    r = BR.reference_of(case, w, x, y, idx)
+    for ref in (r["ref"], r["ref"].twin32):
+        pre, logits = BR._forward_pre(ref, r["xin"])
+        with torch.no_grad():
+            want = ref.logits(r["xin"]).to(torch.float64).numpy()
+        assert logits.tobytes() == want.tobytes()
+        assert sorted(pre) == sorted((("conv7",) if depth == 3 else ()) + BR.KINK_SITES)
+        assert pre["conv8"].shape == (3, 16, 19, 19) and pre["conv9"].shape == (3, 16, 6, 6) and pre["d3"].shape == (3, 6)
+        if depth == 3:
+            assert pre["conv7"].shape == (3, 16, 44, 44)
+
+
+@pytest.mark.parametrize("mutant", sorted(MUTANTS))
+def test_mutants_keep_every_forward_value(taps64, mutant):
+    w, x6 = BR.live_weights(6, 224), BR.features_224(taps64, 3)
+    a, b = FineTune7Ref(w, 6, 224), MUTANTS[mutant](FineTune7Ref)(w, 6, 224)
+    with torch.no_grad():
+        assert a.logits(x6).numpy().tobytes() == b.logits(x6).numpy().tobytes()
+    assert float(a.loss(x6, np.arange(4) % 6, 0.06).detach()) == float(b.loss(x6, np.arange(4) % 6, 0.06).detach())
+
+
+# ---------------------------------------------------------------------------------------------- 1. blindness contrast
+@pytest.mark.parametrize("start", ["shipped", "fresh"])
+def test_shipped_checkpoint_is_blind_to_both_mutants(shipped32, start):
+    """From both starts of the existing GPU tests, on their 32 items, at l2 = 0.06 and 0: neither mutant changes any of the 22
+    gradients, by exactly 0.0 -- because no pre-activation behind a masked ReLU6 reaches 6 and no trained gamma is negative."""
+    x6, y, starts = shipped32
+    w = starts[start]
+    ref = FineTune7Ref(w, 6, 224)
+    pre, _ = BR._forward_pre(ref, x6)
+    top = {s: float(v.max()) for s, v in pre.items()}
+    print(start, "largest pre-activations:", " ".join("%s=%.3g" % kv for kv in top.items()))
+    assert all(top[s] < 6.0 for s in BR.CONV_SITES + ("d0", "d1", "d2")), top
+    assert all((np.asarray(w[n]) >= 0).all() for n in ref.names if n.endswith("/gamma"))
+    for l2 in (0.06, 0.0):
+        _, G = ref.loss_and_grads(x6, y, l2)
+        assert len(G) == 22
+        for name, make in MUTANTS.items():
+            _, Gm = make(FineTune7Ref)(w, 6, 224).loss_and_grads(x6, y, l2)
+            change = BR.grad_change(G, Gm)
+            assert max(change.values()) == 0.0, (name, l2, change)
+
+
+@pytest.mark.parametrize("l2", [0.06, 0.0])
+def test_live_checkpoint_sees_both_mutants(taps64, l2):
+    """On `live`, on the four items of the GPU tests: the mask without its upper end moves at least 10 of the 22 gradients by more
+    than 1000 x GRAD_TOL of their largest entry; the |gamma| adjoint moves gradients by more than that as well."""
+    w = BR.live_weights(6, 224)
+    x6, y = BR.features_224(taps64, 3), np.arange(4) % 6
+    _, G = FineTune7Ref(w, 6, 224).loss_and_grads(x6, y, l2)
+    for name, make in MUTANTS.items():
+        _, Gm = make(FineTune7Ref)(w, 6, 224).loss_and_grads(x6, y, l2)
+        change = BR.grad_change(G, Gm)
+        moved = sorted(n for n, c in change.items() if c > VISIBLE)
+        print("l2=%g %s: %d of 22 gradients move by more than %g, the most by %.3g of its largest entry"
+              % (l2, name, len(moved), VISIBLE, max(change.values())))
+        assert len(moved) >= (10 if name == "open_masks" else 1), (name, change)
+
+
+# ---------------------------------------------------------------------------------------------- 2. live conditions
+def test_every_trained_bn_has_gammas_of_both_signs():
+    for nc, side in ((6, 224), (1, 224), (64, 224), (6, 300)):
+        w = BR.live_weights(nc, side)
+        gammas = [n for n in FineTune7Ref(w, nc, side).names if n.endswith("/gamma")]
+        assert len(gammas) == 7
+        for n in gammas:
+            assert (w[n] < 0).any() and (w[n] > 0).any(), n
+
+
+def test_live_saturates_relu6_behind_the_cached_features(taps64):
+    w, x6 = BR.live_weights(6, 224), BR.features_224(taps64, 3)
+    shares = BR.clamp_shares(BR._forward_pre(FineTune7Ref(w, 6, 224), x6)[0])
+    print("224:", " ".join("%s=%.3f/%.3f" % (s, a, b) for s, (a, b) in shares.items()))
+    for s in ("conv7", "conv8", "conv9", "d0", "d1"):
+        assert shares[s][0] >= AT_CLAMP_MIN, (s, shares)
+    for s in BR.CONV_SITES:
+        assert shares[s][1] >= INSIDE_MIN, (s, shares)
+    # side 300: random features, conv 7 saturates less but does, and has most of its values inside
+    w300 = BR.live_weights(6, 300)
+    s300 = BR.clamp_shares(BR._forward_pre(FineTune7Ref(w300, 6, 300), BR.features_300(3))[0])
+    print("300:", " ".join("%s=%.3f/%.3f" % (s, a, b) for s, (a, b) in s300.items()))
+    assert s300["conv7"][0] >= AT_CLAMP_MIN and s300["conv7"][1] >= INSIDE_MIN
+
+
+@pytest.mark.parametrize("case", [c for c in BR.ONE_STEP_CASES if c["l2"] == 0.06 or c["nc"] == 1], ids=lambda c: c["key"])
+def test_conditions_of_every_gpu_case(taps64, case):
+    """The kink condition at conv 8, conv 9 and d0 .. d3, conv 7's share at the derived delta, and live gradients, for every input
+    of the GPU file (pre-activations and conv 7's adjoint do not depend on l2, so each input is visited once, and its gradients at
+    l2 = 0).  The yardstick's figures are printed."""
+    w, x, y, idx = BR.case_inputs(case, taps64)
+    r = BR.reference_of(dict(case, l2=0.0), w, x, y, idx)
+    print("%s: float32 torch |dloss| %.3g, worst gradient %.3g; DELTA %s; kink distance %s%s"
+          % (case["key"], abs(r["L32"] - r["L"]), max(r["yard"].values()), " ".join("%s=%.2g" % kv for kv in r["delta"].items()),
+             " ".join("%s=%.2g" % kv for kv in r["kink_distance"].items() if kv[0] != "conv7"),
+             "; conv-7 share %.3g" % r["share"] if case["depth"] == 3 else ""))
+    assert not r["violations"], r["violations"]
+    if case["depth"] == 3:
+        assert r["share"] <= BR.SHARE_CAP
+    G = r["G"]
+    assert len(G) == (22 if case["depth"] == 3 else 19)
+    if case["nc"] == 1:
+        assert r["L"] == 0.0 and all(not g.any() for g in G.values())
+    else:
+        assert np.abs(G[BR.W_LAST]).max() > 0
+        if case["depth"] == 3:
+            assert np.abs(G[BR.W7]).max() > 0
+        print("   dead gradients:", [n for n, g in G.items() if not g.any()])
+    if case["side"] == 300 and case["depth"] == 3:
+        _, u = r["ref"].conv7_adjoint(r["xin"], y[idx])
+        assert u.shape[-1] == 63 and not u[:, :, -1, :].any() and not u[:, :, :, -1].any() and u[:, :, :-1, :-1].any()
+
+
+def test_gradcam_reference_maps_are_non_zero(taps64):
+    """Images 14 and 30 (items 0 and 1), both layers, the default class, at the float64 oracle's s6.bn; and the class the GPU test
+    asks for beside the default one exists: a logit that ReLU6 clamps to exactly 0 from a pre-activation further than TIE_EDGE
+    below 0.  Its score is d3.mm BEFORE the ReLU6 (include/roomnet_hip.h), so its map is the reference's, not zero."""
+    for nc in (6, 10):
+        gc = GradCamRef(BR.live_weights(nc, 224), nc, 224)
+        s6 = np.asarray(taps64["s6.bn"])[:2]
+        for layer in ("s6.bn", "s7.bn"):
+            r = gc.grad_cam(s6=s6, layer=layer)
+            top = np.abs(r["cam"]).reshape(2, -1).max(1)
+            print("nc=%d %s max|cam| %s max|alpha| %.3g" % (nc, layer, top, np.abs(r["alpha"]).max()))
+            assert (top > 0).all() and np.abs(r["alpha"]).reshape(2, -1).max(1).min() > 0
+        z = r["z"]
+        clamped = [int(np.flatnonzero(zi < -TIE_EDGE)[0]) if (zi < -TIE_EDGE).any() else -1 for zi in z]
+        print("nc=%d classes clamped to 0:" % nc, clamped)
+        assert max(clamped) >= 0
+
+
+def test_gradcam_conditions_at_side_300():
+    """The one-image side-300 grad-CAM case, at the float64 oracle's s6.bn and s7.bn (the GPU test recomputes this on the handle's
+    own): no pre-activation of conv 8, conv 9, d0 .. d2 within DELTA of a kink, conv 7's share under the cap, non-zero maps."""
+    w = BR.live_weights(6, 300)
+    taps = R.infer(w, parity_set_of(300)[CK.ONE_IMAGE_IDX], dtype=np.float64, taps=True)["taps"]
+    s6, s7 = np.asarray(taps["s6.bn"]).astype(np.float32), np.asarray(taps["s7.bn"]).astype(np.float32)
+    pre64, pre32 = BR.pre_activations(BR.make_ref(w, 6, 300, 2), s7)
+    c7 = BR.pre_activations(BR.make_ref(w, 6, 300, 3), s6)
+    pre64["conv7"], pre32["conv7"] = c7[0]["conv7"], c7[1]["conv7"]
+    delta = BR.deltas(pre64, pre32)
+    assert not BR.kink_violations(pre64, delta, BR.GRADCAM_KINK_SITES)
+    gc = GradCamRef(w, 6, 300)
+    for layer in ("s6.bn", "s7.bn"):
+        r = gc.grad_cam(s6=s6, s7=s7, layer=layer)
+        assert np.abs(r["cam"]).max() > 0 and np.abs(r["alpha"]).max() > 0
+    g7, _ = gc.grad_s7(s7, r["cls"])
+    share, room_alpha, room_cam = BR.gradcam_room6(gc, s6, g7, delta["conv7"])
+    print("300: DELTA %s, share %.3g, room_alpha max %.3g, room_cam max %.3g" % (delta, share, room_alpha.max(), room_cam.max()))
+    assert share <= BR.SHARE_CAP and room_alpha.shape == (1, 128) and room_cam.shape == (1, 65, 65)

@@ -331,7 +331,9 @@ static int prepare_stage0(rn_handle* h, FusedState* fs, const rn_weights* w) {
 //   use_c16 | use_s5x, use_s4x, use_s6x (in this order: launch_rowreg's) | use_c16p | use_rw | generic.
 // Without rw every flag is false: Generic.  With it, reading the priority chain from the top gives the lines below; RegWeights is what
 // is left.  (The predicates accept disjoint shapes except conv16 / 6x, both the 64 -> 128 stage: the row-blocked kernel wins wherever its
-// geometry allows.)
+// geometry allows.)  conv16 and conv16p take their one shape each (64 -> 128 unpooled, 128 -> 16) on shape alone, whatever the side and
+// the flags, so RegWeights is never reached with them: rw_plan still answers for both (variants 5 and 6; its answer is rw_capable),
+// and rn_rw_launch has no case for either.
 static Family choose_family(const rn_handle* h, size_t i, bool rw_capable) {
     const StagePlan& s = h->stages[i];
     const bool res = s.skip_stage >= 0;

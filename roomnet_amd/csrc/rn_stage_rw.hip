@@ -1,5 +1,9 @@
-// "rw" (register-weights) fused stage kernel: stages 1-7 of the 16-bit path
-// (conv3x3 -> ReLU6 -> [avg-pool 4x4 / s] -> BN [-> + legacy-bilinear(skip) -> BN]), one launch per stage.
+// "rw" (register-weights) fused stage kernel of the 16-bit path
+// (conv3x3 -> ReLU6 -> avg-pool 4x4 / s -> BN [-> + legacy-bilinear(skip) -> BN]), one launch per stage.
+// It runs stage 1 with stage 0 fused into it, and the 32- and 64-channel pooling stages (8->32, 32->32, 32->32 + residual,
+// 32->64, 64->64 + residual) where the fused pair and the row-blocked kernels are switched off or do not fit: eleven forms
+// per dtype, listed at rn_rw_launch (who launches which: DESIGN.md section 4).  The unpooled 64->128 stage and the 128->16
+// stage run rn_conv16.hip; rw_plan still answers for their shapes (variants 5 and 6), the launch has no case for them.
 //
 // Row-streaming implicit GEMM: a workgroup owns (image, band of output rows, block of columns) and walks
 // down its band one conv row per step.  What the counters and the ISA of the earlier versions led to
@@ -46,13 +50,13 @@ namespace {
 //            (wave_shl:1, three DPP operations per value instead of two).  203 conv columns = 7 tiles instead of 8.
 constexpr int rw_tile_nout(int pk, int ps, bool wide = false) { return pk ? (ps == 2 ? (wide ? 15 : 14) : 32 - pk + 1) : 32; }
 constexpr int rw_tile_stride(int pk, int ps, bool wide = false) { return pk ? rw_tile_nout(pk, ps, wide) * ps : 32; }
-#ifndef RN_SPREAD_DMA
-#define RN_SPREAD_DMA 1
-#endif
 constexpr int RW_SKIPBUF = 3;   // staged skip-row pairs (residual): 1 being read + 2 in flight
 
-template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS = 1, bool S0F_ = false, bool WIDE_ = false, int S0SH_ = 0>
+// Every form pools 4 x 4 (stride PS) and fills whole 32-channel cout tiles, one wave per (pixel tile, cout tile).
+template <int DT, int CIN, int COUT, int PS, bool RES, int NPT, bool S0F_ = false, bool WIDE_ = false, bool S0SH_ = false>
 struct RwCfg {
+    static constexpr int PK = 4;                               // pool window
+    static_assert(PS == 1 || PS == 2, "pool window 4, stride 1 or 2");
     // S0F: stage 0 (uint8 image -> conv 3->8 -> ReLU6 -> pool 3/1 -> BN) is computed by the SAME wave, row by row,
     // straight into its private ring: the 8-channel tensor between stages 0 and 1 never reaches HBM (see s0_feed)
     static constexpr bool S0F = S0F_;
@@ -61,16 +65,11 @@ struct RwCfg {
     // for 5 halo columns only and costs as much as the first) and reads its 34-column window once its neighbours are done.
     // The eight waves produce 232 stage-0 columns = the windows of 227 output columns: column blocks of this form are 227
     // wide (the eighth tile stores 24 of its 29 columns), one at 224 x 224, two at 420, three at 600.
-    static constexpr bool S0SH = S0SH_ != 0;
+    static constexpr bool S0SH = S0SH_;
     static constexpr int S0SH_BLKW = 227;
     static_assert(!S0SH || S0F, "shared stage-0 ring is a form of the stage-0 fusion");
-    // S0SH_ == 2 (S0HW): NPT / 2 extra "helper" waves compute the stage-0 rows (two 29-column tiles each) and the NPT tile
-    // waves run stage 1 only: 12 waves of <= 168 registers = three per SIMD instead of two, and the stage-0 row (a long
-    // dependent sequence: image bytes -> operand -> 3 MFMAs -> DPP sums -> BN -> LDS) runs beside the stage-1 chains of the
-    // SIMD's other waves instead of in front of them
-    static constexpr bool S0HW = S0SH_ == 2;
-    static constexpr int S0_TILES = S0HW ? 2 : (S0SH ? 1 : 2);
-    static_assert(!S0F || (CIN == 8 && !RES && KS == 1 && COUT == 32), "stage-0 fusion feeds the 8-channel private-ring variant");
+    static constexpr int S0_TILES = S0SH ? 1 : 2;
+    static_assert(!S0F || (CIN == 8 && !RES && COUT == 32), "stage-0 fusion feeds the 8-channel variant");
     // Ring depth: at step s the DMA for input row s + AHEAD is issued; NSLOT = AHEAD + 1 slots
     // (3 live rows + AHEAD - 2 in flight).  Rows of the 8-channel stage are only ~3.8 KB, so it
     // keeps 9 of them in flight to cover the HBM latency (Little's law), the others 3.
@@ -79,11 +78,11 @@ struct RwCfg {
     static constexpr int NSLOT = AHEAD + 1;
     static constexpr int CP = CIN / 8;
     static constexpr int KC = (9 * CIN + 15) / 16;
-    static constexpr int CT = (COUT + 31) / 32;
-    static constexpr int NG = COUT >= 32 ? 4 : COUT / 8;   // 4-channel groups per lane half-row
+    static constexpr int CT = COUT / 32;
+    static constexpr int NG = 4;                               // 4-channel groups per lane half-row of a cout tile
     static constexpr int CPO = COUT / 8;                       // 16-byte chunks per output/skip pixel
     static constexpr bool WIDE2 = WIDE_;                       // wide stride-2 tiles (see rw_tile_nout)
-    static_assert(!WIDE_ || (PK == 4 && PS == 2 && KS == 1), "wide tiles: the stride-2 DPP pooling variants");
+    static_assert(!WIDE_ || PS == 2, "wide tiles: the stride-2 DPP pooling variants");
     static constexpr int TSTRIDE = rw_tile_stride(PK, PS, WIDE2);
     static constexpr int NOUT_T = rw_tile_nout(PK, PS, WIDE2);
     // POOLM: the 4-wide horizontal window sums run on the matrix cores.  The conv MFMA is issued with its
@@ -93,14 +92,11 @@ struct RwCfg {
     // B operand -- no cross-lane movement at all, and H comes out in the usual cout-in-register /
     // pixel-on-lane layout for BN, residual and the stores.  Vertical pooling = fp32 pair sums before the
     // rounding, so a pooled row costs 4 MFMAs (2 pair-sum rows x K = 32) instead of 48 DPP instructions.
-    static constexpr bool POOLM = PK == 4 && PS == 1;
+    static constexpr bool POOLM = PS == 1;
     static constexpr bool RES_SPLIT = !POOLM;                  // residual interpolation weights as hi + lo 16-bit operands
-    static constexpr bool GAP = PK == 4 && PS == 2 && !WIDE2;  // gapped lane -> column map, DPP pooling (see rw_tile_nout)
-    static constexpr bool DPP2 = PK == 4 && PS == 2;           // stride-2 pooling by DPP (gapped or wide)
-    // KS = 3: the K dimension is split by kernel row over three waves per pixel tile (each keeps one
-    // kernel row's weight fragments in registers); partial accumulators meet in LDS (K = 1152 stage)
-    static constexpr int NTHREADS = 64 * NPT * CT * KS + (S0SH_ == 2 ? 64 * (NPT / 2) : 0);
-    static constexpr int KCW = KC / KS;                        // K-chunks per wave
+    static constexpr bool GAP = PS == 2 && !WIDE2;             // gapped lane -> column map, DPP pooling (see rw_tile_nout)
+    static constexpr bool DPP2 = PS == 2;                      // stride-2 pooling by DPP (gapped or wide)
+    static constexpr int NTHREADS = 64 * NPT * CT;
     // PRIV: every wave owns a private ring holding just its own 34-column input tile and fetches
     // it itself.  No wave ever reads another wave's LDS data, so the row loop needs NO workgroup
     // barrier: waves drift apart and the two waves sharing a SIMD overlap MFMA with epilogue
@@ -110,7 +106,7 @@ struct RwCfg {
     // Only for single-cout-tile stages: with several cout tiles the waves of one pixel tile would each
     // fetch the same input, and once they drift apart the duplicates miss L2 (measured on the 32->64
     // stage: 1.65x the algorithmic HBM bytes); those stages keep the workgroup-shared ring.
-    static constexpr bool PRIV = !RES && KS == 1 && CT == 1 && !S0SH;
+    static constexpr bool PRIV = !RES && CT == 1 && !S0SH;
     static constexpr int RINGCOLS = PRIV ? 34 : (NPT - 1) * TSTRIDE + 34;
     static constexpr int LOADERS = PRIV ? 64 : NTHREADS;       // lanes cooperating on one ring row
     static constexpr int NRINGS = PRIV ? NPT * CT : 1;
@@ -132,15 +128,13 @@ struct RwCfg {
     static constexpr bool STAGE_OUT = COUT == 32 && !RES;
     // folded-BN tables: persistent registers where the register file has room (one wave per SIMD, or the
     // small 8-channel stage); otherwise one batched LDS read at the start of every epilogue
-    static constexpr bool PTAB_REGS = (NTHREADS <= 256 || CIN == 8 || (CIN == 32 && COUT == 64)) && !S0HW;   // (S0HW: 168 registers per wave)
+    static constexpr bool PTAB_REGS = (NTHREADS <= 256 || CIN == 8 || (CIN == 32 && COUT == 64));
     // ... except the 8-wave 32->32 variant, which sits at the 256-register cap: it reads each group's
     // table entries late (right before use) so they never pin registers across the MFMA chain
     static constexpr bool PTAB_LATE = !PTAB_REGS && CIN == 32 && COUT == 32;
     static constexpr int STAGE_WAVE_B = 32 * 64;
     static constexpr int STAGE_OFF = SKIP_OFF + (RES ? RW_SKIPBUF * SKIPBUFB : 0);
-    static constexpr int PART_OFF = STAGE_OFF + (STAGE_OUT ? NPT * CT * STAGE_WAVE_B : 0);
-    static constexpr int PART_B = 16 * 64 * 4;                 // one wave's partial accumulator tile
-    static constexpr int LDS_BYTES = PART_OFF + (KS > 1 ? 2 * NPT * CT * (KS - 1) * PART_B : 0);
+    static constexpr int LDS_BYTES = STAGE_OFF + (STAGE_OUT ? NPT * CT * STAGE_WAVE_B : 0);
     // steady-state counted wait at the end of step s: everything up to input row s+3 and the
     // skip pair used by step s+1 has landed; what may stay in flight is what the wave issued
     // after them (the pieces of this step, plus one more row of input when there is no skip)
@@ -152,10 +146,8 @@ struct RwCfg {
     }
     static constexpr int VMCNT_STEADY = (RES ? 2 * LPT + 2 * SLPT : (AHEAD - 3) * LPT);   // upper bound (field-width check)
     static_assert(!RES || AHEAD == 5, "the residual wait counts are derived for AHEAD = 5");
-    static_assert(COUT % 32 == 0 || COUT == 16, "cout must be whole 32-channel tiles (or one half tile)");
-    static_assert(PK == 0 || PK == 4, "pool window 4 or none");
-    static_assert(KCW * 4 <= 80 || NTHREADS <= 256 || KS > 1, "weights need the whole register file: <= 1 wave per SIMD");
-    static_assert(KS == 1 || (KS == 3 && CIN >= 16 && KC % 3 == 0 && !RES), "K split = one kernel row per wave");
+    static_assert(COUT % 32 == 0, "cout must be whole 32-channel tiles");
+    static_assert(KC * 4 <= 80 || NTHREADS <= 256, "weights need the whole register file: <= 1 wave per SIMD");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     static_assert(NSLOT % 2 == 0, "pool-ring parity is tied to the unroll");
     static_assert(!PRIV || (LPT - 1) * 64 < RINGCOLS * CP, "every DMA piece must have at least one active lane");
@@ -163,9 +155,9 @@ struct RwCfg {
 };
 
 
-template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS, bool S0F, bool WIDE, int S0SH>
-__global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>::NTHREADS), 1) void stage_rw_kernel(const StageArgs a) {
-    using C = RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
+template <int DT, int CIN, int COUT, int PS, bool RES, int NPT, bool S0F, bool WIDE, bool S0SH>
+__global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>::NTHREADS), 1) void stage_rw_kernel(const StageArgs a) {
+    using C = RwCfg<DT, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>;
     constexpr int CP = C::CP, KC = C::KC, CT = C::CT, CPO = C::CPO, TSTRIDE = C::TSTRIDE, NOUT_T = C::NOUT_T;
     constexpr int RINGCOLS = C::RINGCOLS, ROWB = C::ROWB, NTHREADS = C::NTHREADS, LPT = C::LPT, SLPT = C::SLPT;
     constexpr int PIXB = CIN * 2, NG = C::NG;
@@ -177,10 +169,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pt = wave % NPT, ct = (wave / NPT) % CT;
-    const bool helper = C::S0HW && wave >= NPT;      // stage-0 helper wave (wave-uniform); tiles 2 hq, 2 hq + 1
-    const int hq = wave - NPT;
-    const int ks = __builtin_amdgcn_readfirstlane(wave / (NPT * CT));     // kernel row of this wave (K split)
-    constexpr int KCW = C::KCW;
     const int r = lane & 31, hh = lane >> 5;
 
     int bid = blockIdx.x;
@@ -196,13 +184,13 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     const int yo0 = band * a.rows_per_band;
     const int yo1 = min(a.Ho, yo0 + a.rows_per_band);
     const int nout_rows = yo1 - yo0;
-    const int yc0 = PK ? yo0 * PS : yo0;
-    const int nconv = PK ? (nout_rows - 1) * PS + 4 : nout_rows;
+    const int yc0 = yo0 * PS;
+    const int nconv = (nout_rows - 1) * PS + 4;
     const int nin = nconv + 2;
     constexpr int BLKC = C::S0SH ? C::S0SH_BLKW : NPT * TSTRIDE;           // conv columns per column block
     constexpr int BLKO = C::S0SH ? C::S0SH_BLKW : NPT * NOUT_T;            // output columns per column block
     const int x0c = cb * BLKC;
-    const int xo_blk0 = PK ? x0c / PS : x0c;
+    const int xo_blk0 = x0c / PS;
 
     // ---- folded BN tables -> LDS
     for (int i = tid; i < 4 * COUT; i += NTHREADS) ptab[i] = a.ptab[i];
@@ -210,13 +198,13 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     // the others (no barrier in their row loop; a finished wave is not waited for by the one barrier of the prologue):
     // it leaves after its share of the table copy.  (600 x 600: 21 tiles in 3 blocks of 8 -- three such waves.)
     if constexpr (C::PRIV) {
-        if ((PK ? (x0c + pt * TSTRIDE) / PS : x0c + pt * TSTRIDE) >= a.Wo) return;
+        if ((x0c + pt * TSTRIDE) / PS >= a.Wo) return;
     }
 
     // ---- this wave's weight fragments -> registers (lane-linear, coalesced)
-    i32x4 wreg[KCW];
+    i32x4 wreg[KC];
 #pragma unroll
-    for (int kc = 0; kc < KCW; ++kc) wreg[kc] = a.wfrag[((ks * KCW + kc) * CT + ct) * 64 + lane];
+    for (int kc = 0; kc < KC; ++kc) wreg[kc] = a.wfrag[(kc * CT + ct) * 64 + lane];
 
     // ---- input-row DMA: piece i of a row covers ring chunks [i*NTHREADS, (i+1)*NTHREADS); this
     // lane fills chunk q = tid + i*NTHREADS = (pixel p, slot c') and therefore fetches source
@@ -303,22 +291,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         if constexpr (RES)
             dma16(sr.r0 + (sk_goff[i] + (sk_hi[i] ? sr.hi_delta : 0u)), skipb + buf * C::SKIPBUFB + i * NTHREADS * 16 + piece_base);
     };
-    auto issue_skip = [&](int e, int buf) __attribute__((always_inline)) {               // skip rows of local output row e -> buffer
-        if constexpr (RES) {
-            const int yo = yo0 + min(max(e, 0), nout_rows - 1);
-            // TF-1.13 compute_interpolation_weights: src = yo * scale (fp32), lo = int(src), hi = min(lo+1, in-1)
-            const float src = mul_rounded(static_cast<float>(yo), a.rscale);
-            const int ylo = static_cast<int>(src);
-            const int yhi = min(ylo + 1, a.Ss - 1);
-            // uniform base = lo row; lanes of the hi row add the (uniform) row distance
-            const char* r0 = skip_img + static_cast<int64_t>(ylo) * skip_row_bytes;
-            const unsigned hi_delta = static_cast<unsigned>((yhi - ylo) * skip_row_bytes);
-#pragma unroll
-            for (int i = 0; i < SLPT; ++i)
-                dma16(r0 + (sk_goff[i] + (sk_hi[i] ? hi_delta : 0u)),
-                      skipb + buf * C::SKIPBUFB + i * NTHREADS * 16 + piece_base);
-        }
-    };
 
     // ---- stage-0 fusion (S0F): this wave computes stage 0 for its own 34 ring columns, one row per call, on the matrix
     // cores with the im2col in registers exactly like stage0_kernel (rn_generic.hip; same instruction sequence, so the
@@ -338,20 +310,19 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     float s0_h1[2][4], s0_h2[2][4];
     int s0_wr[2] = {0, 0};                 // byte offset of this lane's 8-byte piece inside a ring row, or -1
     const int s0_rows = nin + 4;           // image rows this band reads
-    if (C::S0F && (!C::S0HW || helper)) {
+    if constexpr (C::S0F) {
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) s0_w[ky] = a.s0_wfrag[ky * 64 + lane];
         s0_scale = *reinterpret_cast<const f32x4*>(a.s0_ptab + 4 * hh);
         s0_shift = *reinterpret_cast<const f32x4*>(a.s0_ptab + 8 + 4 * hh);
 #pragma unroll
         for (int u = 0; u < C::S0_TILES; ++u) {
-            const int tix = C::S0HW ? 2 * hq + u : pt;                   // shared ring: the 29-column tile this (wave, u) produces
-            const int xt0 = x0c + (C::S0HW ? tix * 29 : pt * TSTRIDE + 29 * u);   // first conv / image column of the tile
+            const int xt0 = x0c + pt * TSTRIDE + 29 * u;                // first conv / image column of the tile
             const int px = min(xt0 + r + 2 * hh, a.s0_S - 1);           // this lane's image column (clamped at the edge)
             s0_sh[u] = px == a.s0_S - 1 ? 8 : 0;                        // last column: load one byte early and shift
             s0_src[u] = a.s0_bgr + (static_cast<int64_t>(n) * a.s0_S * a.s0_S + static_cast<int64_t>(yc0) * a.s0_S + px) * 3 - (s0_sh[u] >> 3);
-            const int oc = C::S0HW ? tix * 29 + r : (C::S0SH ? pt * TSTRIDE : 0) + 29 * u + r;   // ring column of this lane's output pixel
-            s0_wr[u] = (r < (u == 0 || C::S0HW ? 29 : 5) && oc < RINGCOLS) ? oc * PIXB + 8 * hh : -1;
+            const int oc = (C::S0SH ? pt * TSTRIDE : 0) + 29 * u + r;   // ring column of this lane's output pixel
+            s0_wr[u] = (r < (u == 0 ? 29 : 5) && oc < RINGCOLS) ? oc * PIXB + 8 * hh : -1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) s0_h1[u][j] = s0_h2[u][j] = 0.f;
 #pragma unroll
@@ -460,7 +431,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
             }
         }
     };
-    // ---- prologue: rows 0 .. RW_AHEAD-1 in flight (clamped: a no-pool band can be shorter)
+    // ---- prologue: rows 0 .. RW_AHEAD-1 in flight (clamped: a short band of the 8-channel stage has fewer rows)
     if constexpr (C::S0F) {
         if constexpr (C::S0SH) {
             // ring columns 232 .. of every slot are written by nobody and feed discarded lanes only: finite values
@@ -470,19 +441,17 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                 *reinterpret_cast<i32x4*>(ring + (i / ZN) * ROWB + Z0 + (i % ZN) * 16) = i32x4{0, 0, 0, 0};
         }
         static_assert(!C::S0F || (RW_NSLOT == 4 && S0_AHEAD == 4 && RW_AHEAD == 3), "queue phase = ring phase");
-        if (!C::S0HW || helper) {
 #pragma unroll
-            for (int u = 0; u < C::S0_TILES; ++u)
+        for (int u = 0; u < C::S0_TILES; ++u)
 #pragma unroll
-                for (int k = 0; k < S0_AHEAD; ++k) s0_pw[u][k] = s0_load(u, k);
-            s0_feed(IC<0>{}, IC<0>{}, 0, 0);
-            s0_feed(IC<0>{}, IC<1>{}, 1, 0);
-            s0_feed(IC<0>{}, IC<2>{}, 2, 0);
-            s0_feed(IC<0>{}, IC<3>{}, 3, 0);
-            s0_feed(IC<1>{}, IC<0>{}, 4, 0);               // emits ring rows 0 .. RW_AHEAD-1
-            s0_feed(IC<1>{}, IC<1>{}, 5, 1);
-            s0_feed(IC<1>{}, IC<2>{}, 6, 2);
-        }
+            for (int k = 0; k < S0_AHEAD; ++k) s0_pw[u][k] = s0_load(u, k);
+        s0_feed(IC<0>{}, IC<0>{}, 0, 0);
+        s0_feed(IC<0>{}, IC<1>{}, 1, 0);
+        s0_feed(IC<0>{}, IC<2>{}, 2, 0);
+        s0_feed(IC<0>{}, IC<3>{}, 3, 0);
+        s0_feed(IC<1>{}, IC<0>{}, 4, 0);               // emits ring rows 0 .. RW_AHEAD-1
+        s0_feed(IC<1>{}, IC<1>{}, 5, 1);
+        s0_feed(IC<1>{}, IC<2>{}, 6, 2);
     } else {
 #pragma unroll
         for (int j = 0; j < RW_AHEAD; ++j) issue_row(min(j, nin - 1), j);
@@ -526,7 +495,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     i32x4 b8_pre[B8_ASM ? KC : 1];
     // output column of this lane: MFMA-pooled tiles deliver window i of the tile on lane i (see POOLM), gapped
     // tiles the window that starts at the lane's own conv column
-    const int xo = C::DPP2 ? (x0c + pt * TSTRIDE + pm) / PS : (PK ? (x0c + pt * TSTRIDE) / PS : x0c + pt * TSTRIDE) + r;
+    const int xo = C::DPP2 ? (x0c + pt * TSTRIDE + pm) / PS : (x0c + pt * TSTRIDE) / PS + r;
     // a window of the tile ends up on this lane (gapped / wide tiles: the window that starts at the lane's own, even, column)
     const bool lane_win = C::GAP ? ((r & 1) == 0 && (r & 15) <= 12) : (C::WIDE2 ? ((r & 1) == 0 && r <= 28) : r < NOUT_T);
     const bool lane_out = lane_win && xo < a.Wo && (xo - xo_blk0) < BLKO;
@@ -546,7 +515,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     }
     // staging: this lane's output pixel index inside the tile, number of valid pixels of the tile
     const int pr = r;
-    const int xo_t0s = PK ? (x0c + pt * TSTRIDE) / PS : (x0c + pt * TSTRIDE);     // first output column of the tile
+    const int xo_t0s = (x0c + pt * TSTRIDE) / PS;                               // first output column of the tile
     const int nvalid = max(0, min(NOUT_T, min(a.Wo, xo_blk0 + BLKO) - xo_t0s)); // wave-uniform
     // LDS byte addresses (as 32-bit LDS offsets, used by inline-asm DS ops):
     //   write: after the half-wave swap this lane holds 16-byte chunk (2k + hh) of pixel pr, stored at
@@ -658,7 +627,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
             for (int e2 = 0; e2 < 2; ++e2) {
                 const int j8 = 2 * d + e2;
                 const int x = (j8 & 3) + 8 * (j8 >> 2) + 16 * c + 4 * hh;
-                const bool in = PK && x >= PS * r && x < PS * r + 4;
+                const bool in = x >= PS * r && x < PS * r + 4;
                 w |= (in ? 0x3C00u : 0u) << (16 * e2);      // fp16 1.0
             }
             pmw[c][d] = static_cast<int>(w);
@@ -669,34 +638,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
 
     wait_vmcnt<0>();
     lds_barrier();
-
-    if constexpr (C::S0HW) {
-        if (helper) {
-            // stage-0 helper: one ring row per step, in step with the tile waves' barriers (nconv + 1 of them: the first
-            // step, nconv - 1 full steps, the drain step); step k produces ring row k + RW_AHEAD, read from step k + 1 on
-            auto hstep = [&](auto PC, int k) __attribute__((always_inline)) {
-                constexpr int P = decltype(PC)::value;
-                s0_front(IC<(P + RW_AHEAD + 4) % 4>{}, k + RW_AHEAD + 4);
-                s0_part(IC<0>{}, (P + RW_AHEAD) % RW_NSLOT);
-                s0_part(IC<1>{}, (P + RW_AHEAD) % RW_NSLOT);
-                s0_part(IC<2>{}, (P + RW_AHEAD) % RW_NSLOT);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                raw_barrier();
-            };
-            int k = 0;
-            for (; k + 3 < nconv; k += 4) {
-                hstep(IC<0>{}, k);
-                hstep(IC<1>{}, k + 1);
-                hstep(IC<2>{}, k + 2);
-                hstep(IC<3>{}, k + 3);
-            }
-            if (k < nconv) hstep(IC<0>{}, k++);
-            if (k < nconv) hstep(IC<1>{}, k++);
-            if (k < nconv) hstep(IC<2>{}, k++);
-            raw_barrier();          // the tile waves' drain step
-            return;
-        }
-    }
 
     // B fragment of K-chunk kc for the conv row whose first input row sits in ring slot P
     // (compiler-visible load; used by the 8-channel variant whose tap row is lane dependent)
@@ -767,21 +708,20 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
             }(std::make_integer_sequence<int, KC>{});
         }
     };
-    // MFMA chain of one conv row over the K-chunks [KB, KB + KCW) (KB = 0 unless K is split)
+    // MFMA chain of one conv row over its KC K-chunks
     // `slot(IC<I>)` runs right behind MFMA I: the epilogue micro-ops of that chain slot (see step())
-    auto mma_chain = [&](auto PC, auto KBC, f32x16& acc, auto&& slot) __attribute__((always_inline)) {
-        constexpr int KB = decltype(KBC)::value;
+    auto mma_chain = [&](auto PC, f32x16& acc, auto&& slot) __attribute__((always_inline)) {
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        i32x4 bq[KCW];
+        i32x4 bq[KC];
         if constexpr (CIN >= 16) {
             [&]<int... I>(std::integer_sequence<int, I...>) {
-                ((bq[I] = b_read_asm(PC, IC<KB + I>{}, 0.f)), ...);
+                ((bq[I] = b_read_asm(PC, IC<I>{}, 0.f)), ...);
             }(std::make_integer_sequence<int, BAHEAD>{});
             [&]<int... I>(std::integer_sequence<int, I...>) {
                 (([&] {
-                     if constexpr (I + BAHEAD < KCW)
-                         bq[I + BAHEAD] = b_read_asm(PC, IC<KB + (I + BAHEAD < KCW ? I + BAHEAD : 0)>{}, I == 0 ? 0.f : acc[0]);
-                     constexpr int newer = (KCW - 1 - I) < BAHEAD ? (KCW - 1 - I) : BAHEAD;   // my reads issued after chunk I
+                     if constexpr (I + BAHEAD < KC)
+                         bq[I + BAHEAD] = b_read_asm(PC, IC<(I + BAHEAD < KC ? I + BAHEAD : 0)>{}, I == 0 ? 0.f : acc[0]);
+                     constexpr int newer = (KC - 1 - I) < BAHEAD ? (KC - 1 - I) : BAHEAD;   // my reads issued after chunk I
                      asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bq[I]) : "n"(newer));
                      if constexpr (C::POOLM)
                          acc = mfma32<DT>(bq[I], wreg[I], I == 0 ? zero : acc);   // D'[pixel][cout]
@@ -790,7 +730,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                      slot(IC<I>{});
                  }()),
                  ...);
-            }(std::make_integer_sequence<int, KCW>{});
+            }(std::make_integer_sequence<int, KC>{});
         } else if constexpr (B8_ASM) {
             // fragments were issued by b8_issue() at the top of the step
             [&]<int... I>(std::integer_sequence<int, I...>) {
@@ -811,65 +751,6 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                   slot(IC<I>{})),
                  ...);
             }(std::make_integer_sequence<int, KC>{});
-        }
-    };
-    auto mma_row = [&](auto PC, f32x16& acc, auto&& slot) __attribute__((always_inline)) {
-        if constexpr (KS == 1) {
-            mma_chain(PC, IC<0>{}, acc, slot);
-        } else {
-            // wave-uniform dispatch on the kernel row: ring slot and tap offsets stay compile-time
-            if (ks == 0)
-                mma_chain(PC, IC<0>{}, acc, slot);
-            else if (ks == 1)
-                mma_chain(PC, IC<KCW>{}, acc, slot);
-            else
-                mma_chain(PC, IC<2 * KCW>{}, acc, slot);
-        }
-    };
-    // K split: LDS exchange of partial accumulators, double-buffered by step parity
-    const unsigned part_lds = static_cast<unsigned>(reinterpret_cast<uintptr_t>(
-        (__attribute__((address_space(3))) char*)(smem + C::PART_OFF))) + lane * 16;
-    auto part_addr = [&](int parity, int k1) __attribute__((always_inline)) -> unsigned {   // k1 = ks - 1 of the writer
-        return part_lds + static_cast<unsigned>(((parity * NPT * CT + (ct * NPT + pt)) * (KS - 1) + k1) * C::PART_B);
-    };
-    auto part_write = [&](int parity, const f32x16& acc_in) __attribute__((always_inline)) {
-        const unsigned ad = part_addr(parity, ks - 1);
-        // The DS writes below are inline asm and read registers the MFMA chain has just written:
-        // hipcc inserts no XDL-write -> DS-read wait states around asm, so spend them explicitly
-        // (16-pass MFMA: 18 states; two s_nop 15 are 32).  The "+v" operand ties the statement to the
-        // accumulator registers -- a memory clobber alone does not keep the MFMAs in front of it.
-        f32x16 acc = acc_in;
-        asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc));
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const i32x4 v = {__float_as_int(acc[4 * g]), __float_as_int(acc[4 * g + 1]), __float_as_int(acc[4 * g + 2]),
-                             __float_as_int(acc[4 * g + 3])};
-            switch (g) {
-                case 0: asm volatile("ds_write_b128 %0, %1\n\ts_nop 1" ::"v"(ad), "v"(v) : "memory"); break;
-                case 1: asm volatile("ds_write_b128 %0, %1 offset:1024\n\ts_nop 1" ::"v"(ad), "v"(v) : "memory"); break;
-                case 2: asm volatile("ds_write_b128 %0, %1 offset:2048\n\ts_nop 1" ::"v"(ad), "v"(v) : "memory"); break;
-                default: asm volatile("ds_write_b128 %0, %1 offset:3072\n\ts_nop 1" ::"v"(ad), "v"(v) : "memory"); break;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-    auto part_add = [&](int parity, f32x16& acc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k1 = 0; k1 < KS - 1; ++k1) {
-            const unsigned ad = part_addr(parity, k1);
-            i32x4 v0, v1, v2, v3;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(v0) : "v"(ad) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(v1) : "v"(ad) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(v2) : "v"(ad) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(v3) : "v"(ad) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[j] += __int_as_float(v0[j]);
-                acc[4 + j] += __int_as_float(v1[j]);
-                acc[8 + j] += __int_as_float(v2[j]);
-                acc[12 + j] += __int_as_float(v3[j]);
-            }
         }
     };
 
@@ -911,7 +792,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     // One pipeline step s (ring phase P = s mod RW_NSLOT): DMA for row s+RW_AHEAD, MFMA chain of conv row s,
     // epilogue of conv row s-1, counted wait, barrier.
     //
-    // The epilogue is cut into micro-ops and micro-op k runs right behind chain MFMA floor(k * KCW / NM) -- in
+    // The epilogue is cut into micro-ops and micro-op k runs right behind chain MFMA floor(k * KC / NM) -- in
     // SOURCE order, pinned by sched_barrier(0).  Explicit placement instead of scheduler hints because the
     // epilogue has MFMAs of its own (pooling, residual) in the middle of its dependency chain
     // (ReLU/pair sums -> pool MFMAs -> BN -> stores): left to sched_group_barrier they ended up behind the
@@ -922,19 +803,19 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         constexpr int P = decltype(PC)::value;
         constexpr bool MMA = decltype(MMAC)::value != 0, EPI = decltype(EPIC)::value != 0;
         constexpr int JP = (P + RW_NSLOT - 1) % RW_NSLOT;                     // phase of conv row s-1 (the epilogue's row)
-        constexpr bool emit_phase = PK == 0 || PS == 1 || (JP & 1) == 1;
+        constexpr bool emit_phase = PS == 1 || (JP & 1) == 1;
         constexpr bool RESW = RES && EPI && emit_phase;                        // this step adds a residual row
         f32x16& acc_new = (P & 1) == 0 ? acc0 : acc1;
         f32x16& acc_old = (P & 1) == 0 ? acc1 : acc0;
         const int j = s - 1;                         // conv row of the epilogue (local)
-        const bool emit = PK ? j >= 3 : true;
-        const int yo = yo0 + (PK ? (j - 3) / PS : j);   // emitted output row
+        const bool emit = j >= 3;
+        const int yo = yo0 + (j - 3) / PS;           // emitted output row
         // bf16 instantiations of the stages whose output can be dithered (32+ channels in and out, residual or stride-2 pooling: the
         // last step of the 32-channel block and the two steps of the 64-channel block) store through v_cvt_sr_bf16_f32 -- with the row's
         // dither seed (StageArgs::dither) or the plain one (round half up); no branch, one instruction per value (rn_stage.h).  Every
         // other instantiation rounds to nearest even with one v_cvt_pk per pair: the 1.5 M values per image of the first block's first
         // step cost the stage 0 + 1 launch 0.02 ms as SR stores (round 6: 0.198-0.21 -> 0.22-0.236 ms), more than their dither returned
-        constexpr bool SRP = DT == RN_DTYPE_BF16 && CIN >= 32 && COUT >= 32 && (RES || PS == 2);
+        constexpr bool SRP = DT == RN_DTYPE_BF16 && CIN >= 32 && (RES || PS == 2);
         [[maybe_unused]] const unsigned seed_out = a.dither ? rn_dither_seed(max(yo, 0)) : RN_SEED_PLAIN;
         float yl = 0.f;
         if constexpr (RESW) {
@@ -951,14 +832,12 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         constexpr int M_RES_RD = 0, M_FRONT = 1, NF = 8, M_RES_MM = M_FRONT + NF, M_POOL = M_RES_MM + 1, M_BN = M_POOL + 3,
                       M_STORE = M_BN + 2 * NG, NM = M_STORE + 1;
         float yv[16];
-        const bool epi_wave = KS == 1 || ks == 0;        // K split: only the wave of kernel row 0 owns the epilogue
         // explicit placement where the epilogue has MFMAs of its own; the plain VALU epilogue of the stride-2
         // non-residual stage does better under hipcc's own interleave (sched_group_barrier hints): 0.375 vs 0.39 ms
-        constexpr bool SLICED = KS == 1 && !(C::DPP2 && !RES);
+        constexpr bool SLICED = !(C::DPP2 && !RES);
         auto mop = [&](auto KK) __attribute__((always_inline)) {
             constexpr int k = decltype(KK)::value;
             if constexpr (k == M_RES_RD) {
-                if constexpr (KS > 1) part_add((P + 1) & 1, acc_old);
                 if constexpr (RESW) res_issue(sbuf_read, tq);
             } else if constexpr (k >= M_FRONT && k < M_FRONT + NF) {
                 if constexpr (C::DPP2) {
@@ -1033,7 +912,7 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                     }
 #pragma unroll
                     for (int jj = 2 * h2; jj < 2 * h2 + 2; ++jj) {
-                        const float S = PK ? H[4 * g + jj] : relu6f(acc_old[4 * g + jj]);
+                        const float S = H[4 * g + jj];
                         float y = fmaf(S, sc1[jj], sh1[jj]);
                         if constexpr (RES) {
                             const float lo = r_lo[4 * g + jj];
@@ -1085,22 +964,24 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                 }
             }
         };
-        // micro-ops of chain slot I (the ones with floor(k * KCW / NM) == I)
         // DMA pieces of this step (input row s + AHEAD, then the skip pair), spread over the chain slots: issued in
         // one burst at the top of the step -- every wave of the CU at once, next to the burst of fragment reads --
         // each global_load_lds held its wave for 100+ cycles
         constexpr bool SKIPW = RES && MMA && (PS == 1 || (P & 1) == 0);         // this step issues a skip pair
         constexpr int NPIECE = LPT + (SKIPW ? SLPT : 0);
-        constexpr int DSTEP = (KCW - 1) / NPIECE >= 1 ? (KCW - 1) / NPIECE : 1;
+        constexpr int DSTEP = (KC - 1) / NPIECE >= 1 ? (KC - 1) / NPIECE : 1;
         const int sbuf_now = sbuf_issue;
         const SkipRows skr = skip_rows((s - 2) / PS);
+        // (past the end of the band the last row is fetched again into a free slot: the number of
+        //  DMA pieces per step stays constant, so the counted waits and the code path do too)
         const char* const in_row_next = in_img + static_cast<int64_t>(yc0 + min(s + RW_AHEAD, nin - 1)) * in_row_bytes;
+        // chain slot I: its share of the DMA pieces, of the stage-0 row and of the micro-ops (the ones with floor(k * KC / NM) == I)
         auto slot = [&](auto II) __attribute__((always_inline)) {
             constexpr int I = decltype(II)::value;
-            if constexpr (MMA && RN_SPREAD_DMA && !C::S0F) {
+            if constexpr (MMA && !C::S0F) {
                 [&]<int... PI>(std::integer_sequence<int, PI...>) {
                     (([&] {
-                         constexpr int at = PI * DSTEP < KCW ? PI * DSTEP : KCW - 1;
+                         constexpr int at = PI * DSTEP < KC ? PI * DSTEP : KC - 1;
                          if constexpr (at == I) {
                              if constexpr (PI < LPT)
                                  issue_row_piece_at(IC<PI>{}, in_row_next, (P + RW_AHEAD) % RW_NSLOT);
@@ -1111,11 +992,11 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
                      ...);
                 }(std::make_integer_sequence<int, NPIECE>{});
             }
-            if constexpr (MMA && C::S0F && !C::S0HW && I < 3) s0_part(IC<(I < 3 ? I : 0)>{}, (P + RW_AHEAD) % RW_NSLOT);
+            if constexpr (MMA && C::S0F && I < 3) s0_part(IC<(I < 3 ? I : 0)>{}, (P + RW_AHEAD) % RW_NSLOT);
             if constexpr (EPI && SLICED) {
                 [&]<int... K>(std::integer_sequence<int, K...>) {
                     (([&] {
-                         if constexpr (K * KCW / NM == I) mop(IC<K>{});
+                         if constexpr (K * KC / NM == I) mop(IC<K>{});
                      }()),
                      ...);
                 }(std::make_integer_sequence<int, NM>{});
@@ -1124,35 +1005,23 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
         };
         if constexpr (MMA) b8_issue(PC);
         if constexpr (MMA) {
-            // (past the end of the band the last row is fetched again into a free slot: the number of
-            //  DMA pieces per step stays constant, so the counted waits and the code path do too)
-            if constexpr (!RN_SPREAD_DMA && !C::S0F) issue_row(min(s + RW_AHEAD, nin - 1), (P + RW_AHEAD) % RW_NSLOT);
             // S0F: image row s + RW_AHEAD + 4 completes stage-0 output row s + RW_AHEAD -> the slot the DMA would fill
-            if constexpr (C::S0F && !C::S0HW) s0_front(IC<(P + RW_AHEAD + 4) % 4>{}, s + RW_AHEAD + 4);      // the rest: chain slots 0..2
+            if constexpr (C::S0F) s0_front(IC<(P + RW_AHEAD + 4) % 4>{}, s + RW_AHEAD + 4);      // the rest: chain slots 0..2
             if constexpr (RES && (PS == 1 || (P & 1) == 0)) {
                 // pair for the epilogue of conv row s+1 (runs in step s+2): e = (s + 1 - 3) / PS
                 // (stride 2: only odd conv rows emit, so pairs are issued on even steps)
-                static_assert(!RES || PK == 4, "residual variant pools");
-                if constexpr (!RN_SPREAD_DMA) issue_skip((s - 2) / PS, sbuf_issue);
                 sbuf_issue = sbuf_issue == RW_SKIPBUF - 1 ? 0 : sbuf_issue + 1;
             }
-            mma_row(PC, acc_new, slot);
-            if constexpr (KS > 1) {
-                // waves of kernel rows 1, 2 publish their partial sums for the epilogue of the next step
-                if (ks > 0) part_write(P & 1, acc_new);
-            }
+            mma_chain(PC, acc_new, slot);
         }
         if constexpr (EPI && (!MMA || !SLICED)) {
-            // drain step (no chain to hang the micro-ops on), or the K-split variant (three chain bodies, only
-            // the wave of kernel row 0 finishes rows): the whole epilogue in one piece
-            if (epi_wave) {
-                [&]<int... K>(std::integer_sequence<int, K...>) { (mop(IC<K>{}), ...); }(std::make_integer_sequence<int, NM>{});
-            }
+            // drain step (no chain to hang the micro-ops on), or the epilogue left to hipcc's interleave: in one piece
+            [&]<int... K>(std::integer_sequence<int, K...>) { (mop(IC<K>{}), ...); }(std::make_integer_sequence<int, NM>{});
         }
-        if constexpr (MMA && EPI && !SLICED && KS == 1) {
+        if constexpr (MMA && EPI && !SLICED) {
             // software pipeline by hint: spread the VALU epilogue of row s-1 through the MFMA chain of row s
 #pragma unroll
-            for (int i = 0; i < KCW; ++i) {
+            for (int i = 0; i < KC; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
                 __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);   // VALU
             }
@@ -1189,20 +1058,20 @@ __global__ __launch_bounds__((RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WI
     RN_CLOCK_EXIT(a.stamp_buf, tid == 0);
 }
 
-template <int DT, int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS = 1, bool S0F = false, bool WIDE = false, int S0SH = 0>
+template <int DT, int CIN, int COUT, int PS, bool RES, int NPT, bool S0F = false, bool WIDE = false, bool S0SH = false>
 int launch_rw(hipStream_t s, const StageArgs& a, dim3 grid) {
-    using C = RwCfg<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
-    constexpr auto kern = stage_rw_kernel<DT, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>;
+    using C = RwCfg<DT, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>;
+    constexpr auto kern = stage_rw_kernel<DT, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>;
     if (int rc = rn_allow_big_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), C::LDS_BYTES, s, a);
     RN_CHECK_LAUNCH();
     return RN_OK;
 }
 
-template <int CIN, int COUT, int PK, int PS, bool RES, int NPT, int KS = 1, bool S0F = false, bool WIDE = false, int S0SH = 0>
+template <int CIN, int COUT, int PS, bool RES, int NPT, bool S0F = false, bool WIDE = false, bool S0SH = false>
 int launch_rw_dt(int dtype, hipStream_t s, const StageArgs& a, dim3 grid) {
-    if (dtype == RN_DTYPE_BF16) return launch_rw<RN_DTYPE_BF16, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>(s, a, grid);
-    return launch_rw<RN_DTYPE_F16, CIN, COUT, PK, PS, RES, NPT, KS, S0F, WIDE, S0SH>(s, a, grid);
+    if (dtype == RN_DTYPE_BF16) return launch_rw<RN_DTYPE_BF16, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>(s, a, grid);
+    return launch_rw<RN_DTYPE_F16, CIN, COUT, PS, RES, NPT, S0F, WIDE, S0SH>(s, a, grid);
 }
 
 }  // namespace
@@ -1227,8 +1096,10 @@ static bool rw_plan(int cin, int cout, int pool_k, int pool_s, bool res, int out
     // gapped tiles measured the same as 1- and 2-tile ones, so the decomposition itself is free)
     if (cin == 32 && cout == 64 && pool_k == 4 && ps == 2 && !res) variant = 3, npt = 1;
     if (cin == 64 && cout == 64 && pool_k == 4 && ps == 2 && res) variant = 4, npt = 2;
+    // variants 5 and 6 are plan answers only ("the register-weights kernel could run this shape": rw_capable);
+    // both shapes run the conv16 kernels and rn_rw_launch has no case for them
     if (cin == 64 && cout == 128 && pool_k == 0 && !res) variant = 5, npt = 1;
-    if (cin == 128 && cout == 16 && pool_k == 4 && ps == 2 && !res) variant = 6, npt = 2;   // K split over 3 waves
+    if (cin == 128 && cout == 16 && pool_k == 4 && ps == 2 && !res) variant = 6, npt = 2;
     if (variant < 0) return false;
     plan->variant = variant;
     plan->npt = npt;
@@ -1280,33 +1151,26 @@ bool rn_rw_supported(int cin, int cout, int pool_k, int pool_s, bool res, int ou
 // column blocks of the shared-ring form of the fused stages 0 + 1 (variant 0, 8 tiles) for `out_side` output columns
 int rn_rw_s0sh_colblocks(int out_side) { return (out_side + 226) / 227; }
 
-// 1: shared stage-0 ring, every wave computes its own stage-0 tile (0.216-0.22 ms at batch 256).
-// 2: + four stage-0 helper waves (12-wave workgroups, three waves per SIMD): bit-identical, but the stage-1 waves need ~200
-//    registers and get 168 -- 46 spilled -- 0.227-0.234 ms.  Kept as a build switch: the direction needs a stage-1 wave
-//    designed for 168 registers (NOTES.md).
-#ifndef RN_S0_MODE
-#define RN_S0_MODE 1
-#endif
+// The eleven forms per dtype (template arguments: CIN, COUT, pool stride, residual, pixel tiles per workgroup, then stage-0
+// fusion, wide tiles, shared stage-0 ring).  Variants 5 and 6 have no case: choose_family (rn_fused.hip) gives their shapes to
+// the conv16 kernels before it reaches this family.
 int rn_rw_launch(const RwPlan& p, int dtype, hipStream_t s, const StageArgs& a, dim3 grid) {
     switch (p.variant * 16 + p.npt) {
         case 0 * 16 + 4:
-            if (a.s0_bgr) return launch_rw_dt<8, 32, 4, 1, false, 4, 1, true>(dtype, s, a, grid);
-            return launch_rw_dt<8, 32, 4, 1, false, 4>(dtype, s, a, grid);
+            if (a.s0_bgr) return launch_rw_dt<8, 32, 1, false, 4, true>(dtype, s, a, grid);
+            return launch_rw_dt<8, 32, 1, false, 4>(dtype, s, a, grid);
         case 0 * 16 + 8:
             // shared stage-0 ring: column blocks of 227 output columns (the caller sized n_colblocks for that, rn_rw_s0sh_colblocks)
-            if (a.s0_bgr && !a.s0_private)
-                return launch_rw_dt<8, 32, 4, 1, false, 8, 1, true, false, RN_S0_MODE>(dtype, s, a, grid);
-            if (a.s0_bgr) return launch_rw_dt<8, 32, 4, 1, false, 8, 1, true>(dtype, s, a, grid);
-            return launch_rw_dt<8, 32, 4, 1, false, 8>(dtype, s, a, grid);
-        case 1 * 16 + 4: return launch_rw_dt<32, 32, 4, 1, false, 4>(dtype, s, a, grid);
-        case 1 * 16 + 8: return launch_rw_dt<32, 32, 4, 1, false, 8>(dtype, s, a, grid);
-        case 2 * 16 + 4: return launch_rw_dt<32, 32, 4, 1, true, 4>(dtype, s, a, grid);
-        case 3 * 16 + 1: return launch_rw_dt<32, 64, 4, 2, false, 1, 1, false, true>(dtype, s, a, grid);
+            if (a.s0_bgr && !a.s0_private) return launch_rw_dt<8, 32, 1, false, 8, true, false, true>(dtype, s, a, grid);
+            if (a.s0_bgr) return launch_rw_dt<8, 32, 1, false, 8, true>(dtype, s, a, grid);
+            return launch_rw_dt<8, 32, 1, false, 8>(dtype, s, a, grid);
+        case 1 * 16 + 4: return launch_rw_dt<32, 32, 1, false, 4>(dtype, s, a, grid);
+        case 1 * 16 + 8: return launch_rw_dt<32, 32, 1, false, 8>(dtype, s, a, grid);
+        case 2 * 16 + 4: return launch_rw_dt<32, 32, 1, true, 4>(dtype, s, a, grid);
+        case 3 * 16 + 1: return launch_rw_dt<32, 64, 2, false, 1, false, true>(dtype, s, a, grid);
         case 4 * 16 + 2:
-            if (p.wide) return launch_rw_dt<64, 64, 4, 2, true, 2, 1, false, true>(dtype, s, a, grid);
-            return launch_rw_dt<64, 64, 4, 2, true, 2>(dtype, s, a, grid);
-        case 5 * 16 + 1: return launch_rw_dt<64, 128, 0, 1, false, 1>(dtype, s, a, grid);
-        case 6 * 16 + 2: return launch_rw_dt<128, 16, 4, 2, false, 2, 3>(dtype, s, a, grid);
+            if (p.wide) return launch_rw_dt<64, 64, 2, true, 2, false, true>(dtype, s, a, grid);
+            return launch_rw_dt<64, 64, 2, true, 2>(dtype, s, a, grid);
         default:
             rn_set_error("rw kernel: no instantiation for variant %d npt %d", p.variant, p.npt);
             return RN_E_INVALID;

@@ -41,7 +41,7 @@ def _run(tool, listing, *args):
 def test_no_valu_write_right_behind_a_wide_store(listing):
     out = _run("asm_store_audit.py", listing, "1")
     summary = [l for l in out.splitlines() if l.endswith("VALU overwrites flagged")]
-    assert len(summary) >= 16, out[-2000:]                  # every instantiation (2 dtypes x 9 variants) was scanned
+    assert len(summary) == 22, out[-2000:]                  # every instantiation (2 dtypes x 11 forms) was scanned
     assert all(l.split()[-4] == "0" for l in summary), "\n".join(summary)
 
 

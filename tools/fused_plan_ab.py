@@ -6,10 +6,12 @@ every tensor rn_tap returns, case by case; under rocprofv3 the same run is the b
     rocprofv3 --kernel-trace -d DIR_A -o kt --output-format csv -- python tools/fused_plan_ab.py --trace-run --lib A.so --ab-lib A_ab.so --dump a.json
     rocprofv3 --kernel-trace -d DIR_B -o kt --output-format csv -- python tools/fused_plan_ab.py --trace-run --lib B.so --ab-lib B_ab.so --dump b.json
     python tools/fused_plan_ab.py --summarise a.json b.json A_kernel_trace.csv B_kernel_trace.csv [--rename OLD=NEW ...]
-        [--skip-prefix PREFIX ...] [--out profiles/fused_plan_launches.txt]
+        [--rename-re PATTERN=REPLACEMENT ...] [--skip-prefix PREFIX ...] [--out profiles/fused_plan_launches.txt]
 
 --rename: a substring of A's kernel names that build B spells differently (a parameter type that moved to another namespace, say); A's
-names are compared under the new spelling and the summary says how many launches that touched.  --skip-prefix: kernels left out of the
+names are compared under the new spelling and the summary says how many launches that touched.  --rename-re: the same with a regular
+expression and its replacement (re.sub; a template list that lost parameters in build B; the option is split at its first `=`, so
+the pattern itself cannot contain one: write `\\x3d`).  --skip-prefix: kernels left out of the
 launch comparison on both sides, counted in the summary (the HIP runtime's own copy kernels `__amd_rocclr_`, which are the uploads
 of rn_create and not launches of the forward pass).  The trace reports a kernel's static LDS only: dynamic LDS is not compared.
 
@@ -23,6 +25,7 @@ import functools
 import hashlib
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -101,20 +104,19 @@ def trace_run(lib, ab_lib, dump):
 
 
 def _launches(trace_csv, rename, skip):
-    """(launches in order, how many a rename touched, how many were skipped)"""
+    """(launches in order, how many launches each rename touched, how many were skipped)"""
     rows = list(csv.DictReader(open(trace_csv)))
     rows.sort(key=lambda r: (int(r["Start_Timestamp"]), int(r.get("Dispatch_Id") or 0)))
-    out, renamed, skipped = [], 0, 0
+    out, renamed, skipped = [], [0] * len(rename), 0
     for r in rows:
         name = r["Kernel_Name"]
         if name.startswith(tuple(skip)):
             skipped += 1
             continue
-        new_name = name
-        for old, new in rename:
-            new_name = new_name.replace(old, new)
-        renamed += new_name != name
-        name = new_name
+        for k, (old, new) in enumerate(rename):
+            new_name = re.sub(old, new, name) if isinstance(old, re.Pattern) else name.replace(old, new)
+            renamed[k] += new_name != name
+            name = new_name
         grid = tuple(int(r.get("Grid_Size_" + d) or r.get("Grid_Size") or 0) for d in "XYZ")
         wg = tuple(int(r.get("Workgroup_Size_" + d) or r.get("Workgroup_Size") or 0) for d in "XYZ")
         out.append((name, grid, wg, int(r.get("LDS_Block_Size") or r.get("LDS_Block_Size_v") or 0)))
@@ -140,8 +142,9 @@ def summarise(dump_a, dump_b, trace_a, trace_b, rename=(), skip=()):
     lines.append("launches (kernel name, grid, workgroup size, static LDS bytes), in order: %d against %d, %s" %
                  (len(la), len(lb), "identical line for line" if launches_same else "FIRST DIFFERENCE at line %s" % first))
     lines.append("  (the trace reports static LDS only: the dynamic LDS of a launch is not in this comparison)")
-    for old, new in rename:
-        lines.append("  (A's kernel names are compared with %r spelled %r, as B spells it: %d launches)" % (old, new, n_renamed))
+    for (old, new), k in zip(rename, n_renamed):
+        lines.append("  (A's kernel names are compared with '%s' spelled '%s', as B spells it: %d launches)"
+                     % (getattr(old, "pattern", old), new, k))
     for prefix in skip:
         lines.append("  (not compared: kernels named %s*, %d against %d)" % (prefix, ra, rb))
     if not launches_same and first is not None:
@@ -165,11 +168,15 @@ def main():
     ap.add_argument("--dump", default="fused_plan_digests.json")
     ap.add_argument("--summarise", nargs=4, metavar=("DUMP_A", "DUMP_B", "TRACE_A", "TRACE_B"))
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="A's kernel names are compared with OLD spelled NEW")
+    ap.add_argument("--rename-re", action="append", default=[], metavar="PATTERN=REPLACEMENT",
+                    help="the same, by re.sub; split at the first '=', so PATTERN cannot contain one (write \\x3d)")
     ap.add_argument("--skip-prefix", action="append", default=[], metavar="PREFIX", help="kernels left out of the launch comparison")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.summarise:
-        text, ok = summarise(*args.summarise, rename=[tuple(r.split("=", 1)) for r in args.rename], skip=args.skip_prefix)
+        rename = [tuple(r.split("=", 1)) for r in args.rename]
+        rename += [(re.compile(p), new) for p, new in (r.split("=", 1) for r in args.rename_re)]
+        text, ok = summarise(*args.summarise, rename=rename, skip=args.skip_prefix)
         if args.out:
             open(args.out, "w").write(text)
         print(text, end="")

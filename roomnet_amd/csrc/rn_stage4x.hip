@@ -109,8 +109,9 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
         const int p = q >> 2, c = q & 3;
         goff1 = static_cast<unsigned>(p * 64 + ((c ^ swz4x(p)) << 4));
     }
-    auto issue_row = [&](int y, int slot) __attribute__((always_inline)) {
-        const char* row = in_img + static_cast<int64_t>(y0 + min(y, nin - 1)) * row_bytes;
+    // (the row pointer is carried by the caller, the slot is an immediate: see the steady loop)
+    auto issue_row = [&](const char* row, auto SLOTC) __attribute__((always_inline)) {
+        constexpr int slot = decltype(SLOTC)::value;
         unsigned o0 = goff0, o1 = goff1;
         asm volatile("" : "+v"(o0), "+v"(o1));
         dma16(row + o0, ring + slot * U_ROW + wave * 1024);
@@ -155,33 +156,48 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
     const int out_row_bytes = Wo_full * 128;
     const char* const out_img = reinterpret_cast<const char*>(a.out + static_cast<int64_t>(n) * Ho * Wo_full * 64);
 
+    // ---- row state carried from step to step instead of being recomputed from the step number:
+    //  in_row   the input row the next step's DMA loads = band row min(s + U_AHEAD, nin - 1); it advances by row_bytes per step
+    //           until it stands on the band's last row (nin >= 6: the prologue's three rows exist)
+    //  orow     the output row the next emitting odd step stores (pooled row r = (s - 5) / 2: steps 1 and 3 emit nothing, and
+    //           r < nrows holds for every s < nin = 2 nrows + 4)
+    //  sd[]     the dither seeds of the period's odd steps: a period of 12 steps emits 6 rows, so the seed of the odd step 2 j + 1
+    //           of every period is rn_dither_seed(yo0 + 6 n + j - 2) = that of row yo0 + j + 1 -- three wave constants
+    const char* in_row = in_img + static_cast<int64_t>(y0) * row_bytes;
+    issue_row(in_row, IC<0>{});
+    issue_row(in_row + row_bytes, IC<1>{});
+    issue_row(in_row + 2 * static_cast<int64_t>(row_bytes), IC<2>{});
+    in_row += 3 * static_cast<int64_t>(row_bytes);
+    const char* orow = out_img + static_cast<int64_t>(yo0) * out_row_bytes;
+    [[maybe_unused]] unsigned sd[3];
 #pragma unroll
-    for (int j = 0; j < U_AHEAD; ++j) issue_row(j, j);
+    for (int t = 0; t < 3; ++t) sd[t] = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + t + 1);
     wait_vmcnt<0>();
 #pragma unroll
     for (int f = 0; f < 9; ++f) asm volatile("" : "+v"(wf[f]));
     lds_barrier();
 
-    int slot_cur = 0;
     // operand fragments double-buffered across tiles: tile k + 1's three reads go out before tile k's MFMAs (a tile's
     // chain is only 9 MFMAs long: the LDS round trip at its head was a bubble as long as the chain itself) -- and across STEPS:
     // the first tile's fragments of row s + 1 are read at the end of step s, in front of the barrier (round 4; the barrier of a
     // step publishes the row AFTER the one the step computes).  Read behind the barrier they left both waves of every SIMD
     // waiting for LDS at the same moment, ~350 cycles of a ~2 950-cycle step with an idle matrix pipe.
+    // The ring slot is part of the instruction's immediate (slot 3, tile 6: 46 080 < 2^16).
     i32x4 fq[2][3];
-    auto reads_at = [&](auto KC, const unsigned (&bcr)[3]) __attribute__((always_inline)) {
-        constexpr int k = decltype(KC)::value;
+    auto reads_at = [&](auto KC, auto SLOTC) __attribute__((always_inline)) {
+        constexpr int k = decltype(KC)::value, slot = decltype(SLOTC)::value;
         auto& dst = fq[k & 1];
+        auto& bcr = base;                                              // (named outside the asm: implicit capture)
 #pragma unroll
-        for (int f = 0; f < 3; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[f]) : "v"(bcr[f]), "n"(k * 1024));
+        for (int f = 0; f < 3; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[f]) : "v"(bcr[f]), "n"(slot * U_ROW + k * 1024));
     };
-    {
-        // row 0 is published by the prologue's barrier only after every wave's pieces have landed: wait_vmcnt<0> above
-        unsigned bc0[3] = {base[0], base[1], base[2]};
-        reads_at(IC<0>{}, bc0);
-    }
-    auto step = [&](auto RC, auto PARC, int s) __attribute__((always_inline)) {
-        constexpr int R = decltype(RC)::value, PAR = decltype(PARC)::value;
+    // One step = one input row s.  I = s mod 12 is compile time: the accumulator rotation (I mod 3), the row parity (I mod 2) and the
+    // ring slot (I mod 4) are all immediates or register names.  H7: the wave owns the longest run (U_NT tiles; the others one fewer).
+    // `early` (odd steps 1 and 3 only): OOB in the band's first period, whose steps 1 and 3 complete no pooled row, 0 afterwards.
+    auto step = [&](auto IDXC, auto H7C, unsigned in_adv, int early, unsigned early_adv) __attribute__((always_inline)) {
+        constexpr int I = decltype(IDXC)::value, R = I % 3, PAR = I % 2, SLOT = I % 4;
+        constexpr bool H7 = decltype(H7C)::value != 0;
+        constexpr int NTW = H7 ? U_NT : U_NT - 1;                      // this wave's tiles
         constexpr int iN = R, iM = (R + 2) % 3, iO = (R + 1) % 3;      // accumulators of conv rows s, s-1, s-2
         // row s + 1 has landed (row s was published by the previous step's barrier).  VM_CNT counts the output stores too and
         // retires in order: a step issues two DMA pieces behind its first MFMAs and, on odd rows, 3 (or 4: has7) stores at its
@@ -190,17 +206,15 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
         // (NQ = 3: two stores per odd step)
         wait_vmcnt<(NQ == 4 ? 5 : 4)>();
         raw_barrier();
-        const unsigned so = static_cast<unsigned>(slot_cur * U_ROW);
-        unsigned bc[3];
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) bc[kx] = base[kx] + so;
+        // (nothing moves across the top of a step: with the whole period in one block the scheduler stretched live ranges over step
+        //  borders until the twelve-wave form spilled)
+        __builtin_amdgcn_sched_barrier(0);
         i32x4 op[U_NT + 1];
         op[U_NT - 1] = op[U_NT] = i32x4{0, 0, 0, 0};
-        auto reads = [&](auto KC) __attribute__((always_inline)) { reads_at(KC, bc); };
         auto tile = [&](auto KC, auto NEXTC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
             constexpr bool NEXT = decltype(NEXTC)::value != 0;        // tile k + 1's reads are issued here (3 more in flight)
-            if constexpr (NEXT) reads(IC<k + 1>{});
+            if constexpr (NEXT) reads_at(IC<k + 1>{}, IC<SLOT>{});
             auto& cur = fq[k & 1];
             [&]<int... F>(std::integer_sequence<int, F...>) {
                 (([&] {
@@ -210,9 +224,8 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
                      acc[iO][k] = mfma16<DT>(cur[F], wf[2 * 3 + F], acc[iO][k]);
                      if constexpr (k == 0 && F == 0) {
                          // the row DMA rides behind the step's first MFMAs: into the slot of row s - 1 (everybody is past it)
-                         int sl = slot_cur + U_AHEAD;
-                         sl = sl >= U_NS ? sl - U_NS : sl;
-                         issue_row(s + U_AHEAD, sl);
+                         issue_row(in_row, IC<(SLOT + U_AHEAD) % U_NS>{});
+                         in_row += in_adv;
                      }
                  }()),
                  ...);
@@ -233,22 +246,14 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
             }
         };
         [&]<int... K>(std::integer_sequence<int, K...>) {
-            (tile(IC<K>{}, IC<(K + 2 < U_NT ? 1 : 0)>{}), ...);
-        }(std::make_integer_sequence<int, U_NT - 1>{});
-        if (has7) {                       // (the last tile's reads stay behind the branch: its tile code exists once)
-            reads(IC<U_NT - 1>{});
-            tile(IC<U_NT - 1>{}, IC<0>{});
-        }
+            (tile(IC<K>{}, IC<(K + 1 < NTW ? 1 : 0)>{}), ...);
+        }(std::make_integer_sequence<int, NTW>{});
         if constexpr (PAR == 1) {
-            // odd conv row j = s - 2 >= 3 completes pooled row r = (j - 3) / 2
-            const int r = (s - 5) >> 1;
-            const bool emit = s >= 5 && r < nrows;
-            const int rr = min(max(r, 0), nrows - 1);
-            const char* orow = out_img + static_cast<int64_t>(yo0 + rr) * out_row_bytes;
+            // odd conv row j = s - 2 >= 3 completes pooled row r = (j - 3) / 2: the row `orow` stands on
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(orow), 0, out_row_bytes, 0x00020000);
-            const int emask = emit ? 0 : OOB;
+            constexpr bool EARLY = I == 1 || I == 3;
             // bf16 handles: the row's stores are dithered by the output row (rn_stage.h); a constant quarter keeps the plain seed
-            [[maybe_unused]] const unsigned seed = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + rr);
+            [[maybe_unused]] const unsigned seed = sd[((I - 1) / 2) % 3];
             auto out = [&](auto UC) __attribute__((always_inline)) {
                 constexpr int u = decltype(UC)::value;
                 f32x4 H = mfma16<RN_DTYPE_F16>(op[2 * u], pmA, zero4);
@@ -262,46 +267,65 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
                     d = i32x2{static_cast<int>(pack2_sr_bf16(y[0], y[1], seed)), static_cast<int>(pack2_sr_bf16(y[2], y[3], seed))};
                 else
                     d = i32x2{static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
-                __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff[u] | emask, 0, 0);
+                const int vo = EARLY ? (voff[u] | early) : voff[u];
+                __builtin_amdgcn_raw_buffer_store_b64(d, rs, vo, 0, 0);
                 if constexpr (NQ == 3)
-                    if (cq == 2) __builtin_amdgcn_raw_buffer_store_b64(cq3v, rs, (voff[u] + 32) | emask, 0, 0);      // (wave-uniform; OOB stays OOB)
+                    if (cq == 2) __builtin_amdgcn_raw_buffer_store_b64(cq3v, rs, EARLY ? ((voff[u] + 32) | early) : voff[u] + 32, 0, 0);      // (wave-uniform; OOB stays OOB)
             };
             if constexpr (NQ == 4) {
                 out(IC<0>{});
                 out(IC<1>{});
                 out(IC<2>{});
-                if (has7) out(IC<3>{});
+                if constexpr (H7) out(IC<3>{});
             } else {
                 out(IC<0>{});
                 out(IC<1>{});         // (the shorter runs' second pair is their third tile alone: op[3] = 0)
             }
+            orow += EARLY ? early_adv : static_cast<unsigned>(out_row_bytes);
         }
-        slot_cur = slot_cur == U_NS - 1 ? 0 : slot_cur + 1;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        {
-            // first tile of the next row (published by this step's barrier)
-            const unsigned sn = static_cast<unsigned>(slot_cur * U_ROW);
-            unsigned bn[3];
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) bn[kx] = base[kx] + sn;
-            reads_at(IC<0>{}, bn);
+        // first tile of the next row (published by this step's barrier)
+        reads_at(IC<0>{}, IC<(SLOT + 1) % U_NS>{});
+    };
+    // The steady loop: periods of 12 steps = lcm(ring slots 4, accumulator rotation 3, row parity 2).  nin is even, so a band ends
+    // behind an odd step: the loop is left there (no tail code: its last period is cut short).  Per pair of steps one compare decides
+    // whether the row pointer still advances: even step s loads row s + 3 and moves on iff s + 4 <= nin - 1, odd step s + 1 iff
+    // s + 5 <= nin - 1 -- with left = nin - s even, both are left >= 6.
+    auto steady = [&](auto H7C) __attribute__((always_inline)) {
+        // row 0 is published by the prologue's barrier only after every wave's pieces have landed: wait_vmcnt<0> above.  (Read here,
+        // inside the instantiation: in front of the choice between the two the compiler copied the fragments' registers for one of
+        // them before the data had arrived -- it cannot know that the statement is a load still in flight.)
+        // The rule for every edit here: between a reads_at and the counted s_waitcnt that names its registers ("+v") there may be
+        // no control-flow join at which fq could live in different registers on the two sides.  The joins that exist -- `if (done)
+        // return` between pairs of steps and the loop's back edge -- have the same straight-line code (the previous step) on every
+        // path that reaches them, so fq is one set of registers there; a new branch AROUND a reads_at would break that.
+        reads_at(IC<0>{}, IC<0>{});
+        int left = nin;                   // steps still to run, this pair included
+        int early = OOB;
+        unsigned early_adv = 0;
+        for (;;) {
+            bool done = false;
+            [&]<int... P>(std::integer_sequence<int, P...>) {
+                (([&] {
+                     if (done) return;
+                     const unsigned in_adv = left >= 6 ? static_cast<unsigned>(row_bytes) : 0u;
+                     step(IC<2 * P>{}, H7C, in_adv, early, early_adv);
+                     step(IC<2 * P + 1>{}, H7C, in_adv, early, early_adv);
+                     left -= 2;
+                     done = left == 0;
+                 }()),
+                 ...);
+            }(std::make_integer_sequence<int, 6>{});
+            if (done) break;
+            early = 0;
+            early_adv = static_cast<unsigned>(out_row_bytes);
         }
     };
-    int s = 0;
-    for (; s + 5 < nin; s += 6) {
-        step(IC<0>{}, IC<0>{}, s);
-        step(IC<1>{}, IC<1>{}, s + 1);
-        step(IC<2>{}, IC<0>{}, s + 2);
-        step(IC<0>{}, IC<1>{}, s + 3);
-        step(IC<1>{}, IC<0>{}, s + 4);
-        step(IC<2>{}, IC<1>{}, s + 5);
-    }
-    const int rem = nin - s;
-    if (rem > 0) step(IC<0>{}, IC<0>{}, s);
-    if (rem > 1) step(IC<1>{}, IC<1>{}, s + 1);
-    if (rem > 2) step(IC<2>{}, IC<0>{}, s + 2);
-    if (rem > 3) step(IC<0>{}, IC<1>{}, s + 3);
-    if (rem > 4) step(IC<1>{}, IC<0>{}, s + 4);
+    // the longest run's waves and the others run two instantiations of the loop, chosen once (wave-uniform)
+    if (has7)
+        steady(IC<1>{});
+    else
+        steady(IC<0>{});
     wait_vmcnt<0>();
     RN_CLOCK_EXIT(a.stamp_buf, threadIdx.x == 256);
 }

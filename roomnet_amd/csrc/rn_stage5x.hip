@@ -115,12 +115,12 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
         const int p = q >> 3, c = q & 7;
         goff1 = static_cast<unsigned>(p * 128 + ((c ^ swz8(p)) << 4));
     }
-    auto issue_row = [&](int y, int slot) __attribute__((always_inline)) {
-        const char* row = in_img + static_cast<int64_t>(y0 + min(y, nin - 1)) * row_bytes;
+    // (the row pointer and the slot's byte offset are carried by the caller: see the steady loop)
+    auto issue_row = [&](const char* row, int slot_off) __attribute__((always_inline)) {
         unsigned o0 = goff0, o1 = goff1;
         asm volatile("" : "+v"(o0), "+v"(o1));
-        dma16(row + o0, ring + slot * V_ROW + wave * 1024);
-        dma16_masked(row + o1, ring + slot * V_ROW + (512 + wave * tailn) * 16, tail_mask);
+        dma16(row + o0, ring + slot_off + wave * 1024);
+        dma16_masked(row + o1, ring + slot_off + (512 + wave * tailn) * 16, tail_mask);
     };
 
     // ---- operand read bases (slot 0): tap column kx, channel half ch; tile k adds 16 pixels = 2048 bytes (same swizzle)
@@ -206,8 +206,25 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     const int out_row_bytes = Wo_full * 128;
     const char* const out_img = reinterpret_cast<const char*>(a.out + static_cast<int64_t>(n) * Ho * Wo_full * 64);
 
+    // ---- row state carried from step to step instead of being recomputed from the step number (as in rn_stage4x.hip):
+    //  in_row   the input row the next step's DMA loads = band row min(s + V_AHEAD, nin - 1) (nin >= 6: the prologue's rows exist)
+    //  rr, orow the pooled row the next emitting odd step stores (r = (s - 5) / 2: steps 1 and 3 emit nothing, and r < nrows holds
+    //           for every s < nin = 2 nrows + 4), and its place in the output
+    //  sd[]     the dither seeds of the period's odd steps: a period of 6 steps emits 3 rows, so the seed of the odd step 2 j + 1 of
+    //           every period is rn_dither_seed(yo0 + 3 n + j - 2) = that of row yo0 + j + 1 -- three wave constants
+    //  so, sl   byte offsets of the ring slots of row s and of the row the step's DMA loads (9 slots: run time, but no products)
+    //  slot_cur, s   the slot NUMBER of row s and the step number stay beside them for the residual epilogue, which picks the two
+    //           ring rows it interpolates by number (slo, shi).  The four advance together at the end of a step, sl at its top.
+    const char* in_row = in_img + static_cast<int64_t>(y0) * row_bytes;
+    issue_row(in_row, 0);
+    issue_row(in_row + row_bytes, V_ROW);
+    issue_row(in_row + 2 * static_cast<int64_t>(row_bytes), 2 * V_ROW);
+    in_row += 3 * static_cast<int64_t>(row_bytes);
+    const char* orow = out_img + static_cast<int64_t>(yo0) * out_row_bytes;
+    int rr = 0;
+    [[maybe_unused]] unsigned sd[3];
 #pragma unroll
-    for (int j = 0; j < V_AHEAD; ++j) issue_row(j, j);
+    for (int t = 0; t < 3; ++t) sd[t] = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + t + 1);
     wait_vmcnt<0>();
 #pragma unroll
     for (int f = 0; f < 3 * NF; ++f) asm volatile("" : "+v"(wf[f]));
@@ -220,21 +237,24 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     lds_barrier();
 
     int slot_cur = 0;             // ring slot of input row s
-    // One step = one input row s (band-relative).  R = s mod 3 and the parity of s are compile time (unrolled by 6).
-    auto step = [&](auto RC, auto PARC, int s) __attribute__((always_inline)) {
-        constexpr int R = decltype(RC)::value, PAR = decltype(PARC)::value;
+    int so_cur = 0, sl_cur = V_AHEAD * V_ROW;
+    int s = 0;
+    // One step = one input row s (band-relative).  I = s mod 6 is compile time: the accumulator rotation (I mod 3) and the row parity.
+    // CL, H4, EL: the wave's conv_live, has4 and epi_live (wave constants: the loop exists once per combination that occurs).
+    // `early` (odd steps 1 and 3 only): OOB in the band's first period, whose steps 1 and 3 complete no pooled row, 0 afterwards.
+    auto step = [&](auto IDXC, auto CLC, auto H4C, auto ELC, unsigned in_adv, int early, int early_adv) __attribute__((always_inline)) {
+        constexpr int I = decltype(IDXC)::value, R = I % 3, PAR = I % 2;
+        constexpr bool CL = decltype(CLC)::value != 0, H4 = decltype(H4C)::value != 0, EL = decltype(ELC)::value != 0;
         constexpr int iN = R, iM = (R + 2) % 3, iO = (R + 1) % 3;      // accumulators of conv rows s, s-1, s-2
         // row s has landed.  VM_CNT counts the output stores too and retires in order: a step issues two DMA pieces at its
         // top and, on odd rows, two stores at its end.  Younger than the DMA of row s (issued at step s - 3): even s: stores
         // of s - 3, DMA of s - 2, DMA + stores of s - 1 = 2 + 2 + 2 + 2; odd s: DMA + stores of s - 2, DMA of s - 1 = 2 + 2 + 2.
         wait_vmcnt<PAR == 0 ? 8 : 6>();
         raw_barrier();
-        {
-            int sl = slot_cur + V_AHEAD;
-            sl = sl >= V_NS ? sl - V_NS : sl;
-            issue_row(s + V_AHEAD, sl);                                 // into the slot of row s-6: nobody reads it any more
-        }
-        const unsigned so = static_cast<unsigned>(slot_cur * V_ROW);
+        issue_row(in_row, sl_cur);                                      // into the slot of row s-6: nobody reads it any more
+        in_row += in_adv;
+        sl_cur = sl_cur == (V_NS - 1) * V_ROW ? 0 : sl_cur + V_ROW;
+        const unsigned so = static_cast<unsigned>(so_cur);
         unsigned bc[3][2];
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx)
@@ -321,41 +341,34 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
                  ...);
             }(std::make_integer_sequence<int, 5>{});
         };
-        if constexpr (K48) {
-            if (conv_live) {              // (wave-uniform)
-                reads5(IC<0>{});
-                tile5(IC<0>{}, IC<1>{});
-                finish(IC<0>{});
-                tile5(IC<1>{}, IC<1>{});
-                finish(IC<1>{});
-                tile5(IC<2>{}, IC<0>{});
-                finish(IC<2>{});
-                if (has4) {               // (the fourth tile's reads stay behind the branch)
-                    reads5(IC<3>{});
-                    tile5(IC<3>{}, IC<0>{});
-                    finish(IC<3>{});
-                }
+        if constexpr (K48 && CL) {
+            reads5(IC<0>{});
+            tile5(IC<0>{}, IC<1>{});
+            finish(IC<0>{});
+            tile5(IC<1>{}, IC<1>{});
+            finish(IC<1>{});
+            tile5(IC<2>{}, IC<(H4 ? 1 : 0)>{});
+            finish(IC<2>{});
+            if constexpr (H4) {
+                tile5(IC<3>{}, IC<0>{});
+                finish(IC<3>{});
             }
-        } else
-        if (conv_live) {                  // (wave-uniform)
+        } else if constexpr (CL) {
             reads(IC<0>{});
             tile(IC<0>{}, IC<0>{});
             finish(IC<0>{});
             tile(IC<1>{}, IC<0>{});
             finish(IC<1>{});
-            tile(IC<2>{}, IC<1>{});
+            tile(IC<2>{}, IC<(H4 ? 0 : 1)>{});
             finish(IC<2>{});
-            if (has4) {                   // (the fourth tile's first reads stay behind the branch)
-                reads(IC<6>{});
+            if constexpr (H4) {
                 tile(IC<3>{}, IC<1>{});
                 finish(IC<3>{});
             }
         }
         if constexpr (PAR == 1) {
             // odd conv row j = s - 2 >= 3 completes pooled row r = (j - 3) / 2
-            const int r = (s - 5) >> 1;
-            const bool emit = s >= 5 && r < nrows;
-            const int rr = min(max(r, 0), nrows - 1);
+            constexpr bool EARLY = I == 1 || I == 3;
             const float src = mul_rounded(static_cast<float>(yo0 + rr), a.rscale);
             const int ylo_v = static_cast<int>(src);
             const int ylo = __builtin_amdgcn_readfirstlane(ylo_v);
@@ -369,11 +382,10 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
             slo = slo < 0 ? slo + V_NS : slo;
             shi = shi < 0 ? shi + V_NS : shi;
             const unsigned olo = static_cast<unsigned>(slo * V_ROW), ohi = static_cast<unsigned>(shi * V_ROW);
-            const char* orow = out_img + static_cast<int64_t>(yo0 + rr) * out_row_bytes;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(orow), 0, out_row_bytes, 0x00020000);
-            const int emask = emit ? 0 : OOB;
-            [[maybe_unused]] const unsigned seed = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + rr);      // (bf16 handles: rn_stage.h)
-            if (!epi_live) {
+            const int emask = EARLY ? early : 0;
+            [[maybe_unused]] const unsigned seed = sd[((I - 1) / 2) % 3];      // (bf16 handles: rn_stage.h)
+            if constexpr (!EL) {
                 // (K48, last quarter: nothing to compute -- its waves store the constants, so that the pixels leave as full lines and
                 //  VM_CNT counts two stores per odd step in every wave: the counted wait at the top of a step is one immediate)
                 const i32x2 cv = *reinterpret_cast<const i32x2*>(a.cvals + 4 * g);     // (the lane's channels 48 + 4 g .. + 3; full lines)
@@ -392,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
                         asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(tq[1][kh][t2]) : "v"(ahi));
                     }
                 f32x4 H = zero4;           // frozen quarters: fma(H, sc1, sh1) = sh1 for every H the convolution can produce
-                if (conv_live) {
+                if constexpr (CL) {
                     H = mfma16<RN_DTYPE_F16>(op[2 * u], pmA, zero4);
                     H = mfma16<RN_DTYPE_F16>(op[2 * u + 1], pmB, H);
                     if (u == 0) H = mfma16<RN_DTYPE_F16>(op[2], pmC, H);
@@ -423,25 +435,53 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
                     d = i32x2{static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
                 __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff[u] | emask, 0, 0);
             }
+            const int adv = EARLY ? early_adv : 1;
+            rr += adv;
+            orow += static_cast<unsigned>(adv ? out_row_bytes : 0);
         }
         slot_cur = slot_cur == V_NS - 1 ? 0 : slot_cur + 1;
+        so_cur = so_cur == (V_NS - 1) * V_ROW ? 0 : so_cur + V_ROW;
+        ++s;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-    int s = 0;
-    for (; s + 5 < nin; s += 6) {
-        step(IC<0>{}, IC<0>{}, s);
-        step(IC<1>{}, IC<1>{}, s + 1);
-        step(IC<2>{}, IC<0>{}, s + 2);
-        step(IC<0>{}, IC<1>{}, s + 3);
-        step(IC<1>{}, IC<0>{}, s + 4);
-        step(IC<2>{}, IC<1>{}, s + 5);
+    // The steady loop: periods of 6 steps (accumulator rotation 3 x row parity 2).  nin is even, so a band ends behind an odd step: the
+    // loop is left there (no tail code: its last period is cut short).  Per pair of steps one compare decides whether the row pointer
+    // still advances: even step s loads row s + 3 and moves on iff s + 4 <= nin - 1, odd step s + 1 iff s + 5 <= nin - 1 -- with
+    // left = nin - s even, both are left >= 6.
+    auto steady = [&](auto CLC, auto H4C, auto ELC) __attribute__((always_inline)) {
+        int left = nin;                   // steps still to run, this pair included
+        int early = OOB, early_adv = 0;
+#pragma nounroll      // (the compiler would peel the first period off for its constant `early`: twice the code in the instruction cache)
+        for (;;) {
+            bool done = false;
+            [&]<int... P>(std::integer_sequence<int, P...>) {
+                (([&] {
+                     if (done) return;
+                     const unsigned in_adv = left >= 6 ? static_cast<unsigned>(row_bytes) : 0u;
+                     step(IC<2 * P>{}, CLC, H4C, ELC, in_adv, early, early_adv);
+                     step(IC<2 * P + 1>{}, CLC, H4C, ELC, in_adv, early, early_adv);
+                     left -= 2;
+                     done = left == 0;
+                 }()),
+                 ...);
+            }(std::make_integer_sequence<int, 3>{});
+            if (done) break;
+            early = 0;
+            early_adv = 1;
+        }
+    };
+    // one instantiation of the loop per kind of wave, chosen once (wave-uniform): computing waves with four / three tiles, the frozen
+    // quarters' waves (residual epilogue only) and, K48, the constant quarter's (stores only)
+    if (conv_live) {
+        if (has4)
+            steady(IC<1>{}, IC<1>{}, IC<1>{});
+        else
+            steady(IC<1>{}, IC<0>{}, IC<1>{});
+    } else if (epi_live) {
+        steady(IC<0>{}, IC<0>{}, IC<1>{});
+    } else {
+        steady(IC<0>{}, IC<0>{}, IC<0>{});
     }
-    const int rem = nin - s;
-    if (rem > 0) step(IC<0>{}, IC<0>{}, s);
-    if (rem > 1) step(IC<1>{}, IC<1>{}, s + 1);
-    if (rem > 2) step(IC<2>{}, IC<0>{}, s + 2);
-    if (rem > 3) step(IC<0>{}, IC<1>{}, s + 3);
-    if (rem > 4) step(IC<1>{}, IC<0>{}, s + 4);
     wait_vmcnt<0>();
     RN_CLOCK_EXIT(a.stamp_buf, threadIdx.x == 256);
 }

@@ -974,6 +974,79 @@ static Ft7Args ft7_call(const rn_ft* ft, const float* feats, const int32_t* inde
     return s;
 }
 
+// Labels are read back and range-checked on the host before anything is enqueued: the `n_labels` of `d_labels`, or, through
+// `d_index` (rn_ft_run), its `n_index` indices and the label each one selects.  `who` is the entry point's name in the message.
+static int ft_check_labels(rn_ft* ft, const char* who, const int32_t* d_labels, int64_t n_labels, const int32_t* d_index, size_t n_index) {
+    std::vector<int32_t> idx(d_index ? n_index : 0), lab(static_cast<size_t>(n_labels));
+    RN_HIP(hipStreamSynchronize(ft->stream));
+    if (d_index) RN_HIP(hipMemcpy(idx.data(), d_index, idx.size() * 4, hipMemcpyDeviceToHost));
+    RN_HIP(hipMemcpy(lab.data(), d_labels, lab.size() * 4, hipMemcpyDeviceToHost));
+    const size_t count = d_index ? n_index : lab.size();
+    for (size_t k = 0; k < count; ++k) {
+        int64_t i = static_cast<int64_t>(k);
+        if (d_index) {
+            i = idx[k];
+            if (i < 0 || i >= n_labels) {
+                rn_set_error("%s: index[%zu] = %d outside [0, %lld)", who, k, idx[k], static_cast<long long>(n_labels));
+                return RN_E_RANGE;
+            }
+        }
+        if (lab[i] < 0 || lab[i] >= ft->nc) {
+            rn_set_error("%s: label[%lld] = %d outside [0, %d)", who, static_cast<long long>(i), lab[i], ft->nc);
+            return RN_E_RANGE;
+        }
+    }
+    return RN_OK;
+}
+
+// The kernels of one pass: the item kernel's six instantiations (evaluation never drops and has no update).  They are named in the
+// order this file has always first used them, which is the order the code object lays them out in.
+struct FtKernels {
+    void (*item)(FtItemArgs);
+    void (*update)(FtUpdateArgs);
+};
+static FtKernels ft_kernels_of(bool train, bool d3, bool drop) {
+    if (train && drop)
+        return d3 ? FtKernels{ft_item_kernel<true, true, true>, ft_update_kernel<true>}
+                  : FtKernels{ft_item_kernel<true, false, true>, ft_update_kernel<false>};
+    if (train) return d3 ? FtKernels{ft_item_kernel<true, true>, ft_update_kernel<true>} : FtKernels{ft_item_kernel<true, false>, ft_update_kernel<false>};
+    return d3 ? FtKernels{ft_item_kernel<false, true>, nullptr} : FtKernels{ft_item_kernel<false, false>, nullptr};
+}
+
+// One pass over `m` slots on the trainer's stream: the items `a` names, from a.base on.  With `u` a training step (the update
+// closes it; a.drop.thr != 0 drops), without it an evaluation.  Depth 2 is the item kernel [+ the update]; depth 3 puts stage 7's
+// forward pass in front of the item kernel and its backward pass behind it, and, when dropping, in front of all the pre-pass that
+// gathers the step's s6.bn into d_x6d, dropped -- stage 7 then reads that copy in slot order.
+static int ft_enqueue_pass(rn_ft* ft, const FtItemArgs& a, FtUpdateArgs* u, int m) {
+    const bool train = u != nullptr, d3 = ft->depth == 3, dropping = a.drop.thr != 0;
+    const FtKernels k = ft_kernels_of(train, d3, dropping);
+    const bool gathered = d3 && dropping;
+    int rc;
+    if (gathered) {
+        const int64_t quads = static_cast<int64_t>(ft->sd.S6) * ft->sd.S6 * (LB_CIN7 / 4);
+        const Ft7DropArgs dr{a.feats, a.index, a.base, quads, quads * m, ft->d_x6d, a.drop};
+        const int dblocks = static_cast<int>(std::min<int64_t>((dr.total_quads + 255) / 256, 8192));
+        hipLaunchKernelGGL(ft7_drop_kernel, dim3(dblocks), dim3(256), 0, ft->stream, dr);
+        RN_CHECK_LAUNCH();
+    }
+    Ft7Args s7{};
+    if (d3) {
+        // stage 7 reads the gathered copy in slot order, or the caller's items
+        s7 = ft7_call(ft, gathered ? ft->d_x6d : a.feats, gathered ? nullptr : a.index, gathered ? 0 : a.base, m);
+        if ((rc = rn_ft7_forward(ft->stream, s7, m)) != RN_OK) return rc;
+    }
+    hipLaunchKernelGGL(k.item, dim3(m), dim3(FT_NT), 0, ft->stream, a);
+    RN_CHECK_LAUNCH();
+    if (!train) return RN_OK;
+    if (d3) {
+        if ((rc = rn_ft7_backward(ft->stream, s7, m)) != RN_OK) return rc;
+        u->bands = s7.bands_b;
+    }
+    hipLaunchKernelGGL(k.update, dim3((ft->n_param + 255) / 256), dim3(256), 0, ft->stream, *u);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
 extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
                          int steps, float* losses) {
     if (!ft || !d_feats || !d_labels || !d_index || !losses) {
@@ -990,26 +1063,10 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     }
     DeviceGuard guard(ft->device);
     (void)hipGetLastError();
-    // every index and the label it selects are checked on the host before anything is enqueued
-    {
-        const size_t ni = static_cast<size_t>(steps) * batch;
-        std::vector<int32_t> idx(ni), lab(static_cast<size_t>(n_items));
-        RN_HIP(hipStreamSynchronize(ft->stream));
-        RN_HIP(hipMemcpy(idx.data(), d_index, ni * 4, hipMemcpyDeviceToHost));
-        RN_HIP(hipMemcpy(lab.data(), d_labels, lab.size() * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < ni; ++i) {
-            if (idx[i] < 0 || idx[i] >= n_items) {
-                rn_set_error("rn_ft_run: index[%zu] = %d outside [0, %lld)", i, idx[i], static_cast<long long>(n_items));
-                return RN_E_RANGE;
-            }
-            const int32_t y = lab[idx[i]];
-            if (y < 0 || y >= ft->nc) {
-                rn_set_error("rn_ft_run: label[%d] = %d outside [0, %d)", idx[i], y, ft->nc);
-                return RN_E_RANGE;
-            }
-        }
-    }
+    int rc;
+    if ((rc = ft_check_labels(ft, "rn_ft_run", d_labels, n_items, d_index, static_cast<size_t>(steps) * batch)) != RN_OK) return rc;
     if (steps > ft->losses_cap) {
+        // the old buffer and its size go before the allocation that may fail: a failed grow leaves no stale pointer
         if (ft->d_losses) RN_HIP(hipFree(ft->d_losses));
         ft->d_losses = nullptr;
         ft->losses_cap = 0;
@@ -1026,19 +1083,7 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     FtUpdateArgs u = ft->upd;
     u.n = batch;
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
-    const int ublocks = (ft->n_param + 255) / 256;
-    const bool d3 = ft->depth == 3;
     const bool dropping = ft->drop.thr != 0;
-    Ft7DropArgs dr{};
-    int dblocks = 0;
-    if (d3 && dropping) {
-        dr.feats = d_feats;
-        dr.index = d_index;
-        dr.item_quads = static_cast<int64_t>(ft->sd.S6) * ft->sd.S6 * (LB_CIN7 / 4);
-        dr.total_quads = dr.item_quads * batch;
-        dr.x6d = ft->d_x6d;
-        dblocks = static_cast<int>(std::min<int64_t>((dr.total_quads + 255) / 256, 8192));
-    }
     ft->timed = false;
     RN_HIP(hipEventRecord(ft->ev0, ft->stream));
     for (int s = 0; s < steps; ++s) {
@@ -1053,42 +1098,7 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
             a.drop.step_lo = static_cast<uint32_t>(gstep);
             a.drop.step_hi = static_cast<uint32_t>(gstep >> 32);
         }
-        if (d3 && dropping) {
-            // five launches: the dropped copy of the step's s6.bn, then the four of a depth-3 step on it in slot order
-            int rc;
-            dr.base = a.base;
-            dr.drop = a.drop;
-            hipLaunchKernelGGL(ft7_drop_kernel, dim3(dblocks), dim3(256), 0, ft->stream, dr);
-            RN_CHECK_LAUNCH();
-            const Ft7Args s7 = ft7_call(ft, ft->d_x6d, nullptr, 0, batch);
-            if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
-            hipLaunchKernelGGL((ft_item_kernel<true, true, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
-            RN_CHECK_LAUNCH();
-            if ((rc = rn_ft7_backward(ft->stream, s7, batch)) != RN_OK) return rc;
-            u.bands = s7.bands_b;
-            hipLaunchKernelGGL(ft_update_kernel<true>, dim3(ublocks), dim3(256), 0, ft->stream, u);
-            RN_CHECK_LAUNCH();
-        } else if (dropping) {
-            hipLaunchKernelGGL((ft_item_kernel<true, false, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
-            RN_CHECK_LAUNCH();
-            hipLaunchKernelGGL(ft_update_kernel<false>, dim3(ublocks), dim3(256), 0, ft->stream, u);
-            RN_CHECK_LAUNCH();
-        } else if (d3) {
-            int rc;
-            const Ft7Args s7 = ft7_call(ft, d_feats, d_index, a.base, batch);
-            if ((rc = rn_ft7_forward(ft->stream, s7, batch)) != RN_OK) return rc;
-            hipLaunchKernelGGL((ft_item_kernel<true, true>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
-            RN_CHECK_LAUNCH();
-            if ((rc = rn_ft7_backward(ft->stream, s7, batch)) != RN_OK) return rc;
-            u.bands = s7.bands_b;
-            hipLaunchKernelGGL(ft_update_kernel<true>, dim3(ublocks), dim3(256), 0, ft->stream, u);
-            RN_CHECK_LAUNCH();
-        } else {
-            hipLaunchKernelGGL((ft_item_kernel<true, false>), dim3(batch), dim3(FT_NT), 0, ft->stream, a);
-            RN_CHECK_LAUNCH();
-            hipLaunchKernelGGL(ft_update_kernel<false>, dim3(ublocks), dim3(256), 0, ft->stream, u);
-            RN_CHECK_LAUNCH();
-        }
+        if ((rc = ft_enqueue_pass(ft, a, &u, batch)) != RN_OK) return rc;
         ++ft->steps_done;
     }
     RN_HIP(hipEventRecord(ft->ev1, ft->stream));
@@ -1110,37 +1120,21 @@ extern "C" int rn_ft_eval(rn_ft* ft, const float* d_feats, const int32_t* d_labe
     }
     DeviceGuard guard(ft->device);
     (void)hipGetLastError();
-    if (d_labels) {
-        std::vector<int32_t> lab(static_cast<size_t>(n));
-        RN_HIP(hipStreamSynchronize(ft->stream));
-        RN_HIP(hipMemcpy(lab.data(), d_labels, lab.size() * 4, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < n; ++i)
-            if (lab[i] < 0 || lab[i] >= ft->nc) {
-                rn_set_error("rn_ft_eval: label[%lld] = %d outside [0, %d)", static_cast<long long>(i), lab[i], ft->nc);
-                return RN_E_RANGE;
-            }
-    }
+    int rc;
+    if (d_labels && (rc = ft_check_labels(ft, "rn_ft_eval", d_labels, n, nullptr, 0)) != RN_OK) return rc;
     FtItemArgs a = ft->item;
     a.feats = d_feats;
     a.labels = d_labels;
     a.index = nullptr;
     a.l2sum = nullptr;
+    a.probs = ft->d_probs;
+    a.ids = ft->d_ids;
     double ce = 0.0;
     std::vector<double> il(static_cast<size_t>(ft->max_batch));
     for (int64_t i = 0; i < n; i += ft->max_batch) {
         const int m = static_cast<int>(std::min<int64_t>(ft->max_batch, n - i));
         a.base = i;
-        a.probs = ft->d_probs;
-        a.ids = ft->d_ids;
-        if (ft->depth == 3) {
-            const Ft7Args s7 = ft7_call(ft, d_feats, nullptr, i, m);
-            int rc;
-            if ((rc = rn_ft7_forward(ft->stream, s7, m)) != RN_OK) return rc;
-            hipLaunchKernelGGL((ft_item_kernel<false, true>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
-        } else {
-            hipLaunchKernelGGL((ft_item_kernel<false, false>), dim3(m), dim3(FT_NT), 0, ft->stream, a);
-        }
-        RN_CHECK_LAUNCH();
+        if ((rc = ft_enqueue_pass(ft, a, nullptr, m)) != RN_OK) return rc;
         if (probs) RN_HIP(hipMemcpyAsync(probs + i * ft->nc, ft->d_probs, static_cast<size_t>(m) * ft->nc * 4, hipMemcpyDeviceToHost, ft->stream));
         if (ids) RN_HIP(hipMemcpyAsync(ids + i, ft->d_ids, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, ft->stream));
         if (mean_loss) RN_HIP(hipMemcpyAsync(il.data(), ft->d_item_loss, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, ft->stream));

@@ -1,8 +1,8 @@
 """Helpers for the backward-pass tests on a checkpoint that saturates ReLU6 (tests/test_backward_live_host.py on the CPU,
-tests/test_hip_backward_live.py on the GPU), on top of ``FineTuneRef``, ``FineTune7Ref``, ``GradCamRef`` and the dropout references,
-which stay as they are.
+tests/test_hip_backward_live.py on the GPU): what is specific to that checkpoint, on top of the one reference
+(tests/finetune_ref.py; ``make_ref`` gives a float64 reference with its float32 twin, the yardstick, as ``ref.twin32``), ``GradCamRef``
+and the one-step reference and bounds of tests/finetune_harness.py.
 
-* ``make_ref``: a float64 reference with its float32 twin (the yardstick: the same torch code in float32) as ``ref.twin32``.
 * ``pre_activations``: the pre-activation of every ReLU6 site -- conv 7 (depth 3), conv 8, conv 9, d0 .. d3 -- in float64 and in the
   yardstick; ``deltas``: 4 x max |pre32 - pre64| per site (4: a kernel sums in another order than torch does);
   ``kink_violations``: sites where a float64 pre-activation lies within its delta of 0 or 6.  At conv 8 and behind, a mask flipped
@@ -19,9 +19,8 @@ import torch
 import torch.nn.functional as F
 
 import checkpoints as CK
-from finetune7_ref import FineTune7Ref
-from finetune_dropout_ref import FineTune7DropRef, FineTuneDropRef, dropped_x6, host_masks
-from finetune_ref import FineTuneRef
+from finetune_harness import GRAD_TOL, LOSS_TOL, SHARE_CAP, W7, grad_errors, locate, one_step_reference  # noqa: F401  (BR.NAME)
+from finetune_ref import FineTune7Ref, make_ref  # noqa: F401
 from gradcam_ref import relu6
 from roomnet_amd.graph import build_graph
 
@@ -30,8 +29,7 @@ HEAD_SITES = ("d0", "d1", "d2", "d3")
 KINK_SITES = ("conv8", "conv9") + HEAD_SITES      # a flip here reaches every upstream gradient: no room, a condition instead
 GRADCAM_KINK_SITES = ("conv8", "conv9", "d0", "d1", "d2")      # grad-CAM's score is d3.mm: the last ReLU6 is not in its path
 ITEMS = CK.PARITY_IDX + [52]                      # the four parity images the forward tests on `live` use
-GRAD_TOL, LOSS_TOL, SHARE_CAP = 1e-5, 5e-6, 1e-4  # the project's bounds (test_hip_finetune.py, test_hip_finetune7.py)
-W7, W_LAST = "conv2d_7/kernel", "dense_3/kernel"
+W_LAST = "dense_3/kernel"
 DROP_RATE, DROP_SEED = 0.35, 2024
 
 
@@ -81,46 +79,17 @@ def case_inputs(case, taps64):
 
 
 def reference_of(case, w, x, y, idx):
-    """Everything the CPU and the GPU test of one case need from the references, computed once: float64 loss and gradients, the
-    yardstick's, the pre-activations, DELTA, the kink condition's violations, and at depth 3 conv 7's near-kink share and Amb."""
-    n, depth, rate = len(idx), case["depth"], case["rate"]
-    masks = host_masks(build_graph(case["nc"], case["side"]), depth, DROP_SEED, 0, n, rate) if rate else None
-    xin = x[idx]
-    if masks is not None and depth == 3:
-        xin = dropped_x6(xin, masks[0], rate)
-    ref = make_ref(w, case["nc"], case["side"], depth, masks, rate)
-    L, G = ref.loss_and_grads(xin, y[idx], case["l2"])
-    L32, G32 = ref.twin32.loss_and_grads(xin, y[idx], case["l2"])
-    pre64, pre32 = pre_activations(ref, xin)
+    """Everything the CPU and the GPU test of one case need from the references, computed once: the harness's one-step reference
+    (float64 loss and gradients, the yardstick's) and, on top, the pre-activations, DELTA, the kink condition's violations, the loss
+    bound and at depth 3 conv 7's near-kink share and Amb at DELTA["conv7"]."""
+    r = one_step_reference(w, x, y, idx, case["l2"], case["depth"], case["side"], case["nc"], case["rate"], DROP_SEED)
+    pre64, pre32 = pre_activations(r["ref"], r["xin"])
     delta = deltas(pre64, pre32)
-    out = {"ref": ref, "xin": xin, "masks": masks, "L": L, "G": G, "L32": L32, "G32": G32, "pre64": pre64, "delta": delta,
-           "violations": kink_violations(pre64, delta), "kink_distance": kink_distance(pre64),
-           "loss_bound": max(LOSS_TOL, 4.0 * abs(L32 - L)), "yard": grad_errors(G32, G)}
-    if depth == 3:
-        out["share"], out["amb"] = ref.conv7_ambiguity(xin, y[idx], case["l2"], delta["conv7"])
-    return out
-
-
-def grad_errors(got, ref):
-    """Per variable max |got - ref| / max |ref|."""
-    return {n: float(np.abs(np.asarray(got[n], np.float64) - ref[n]).max() / max(np.abs(ref[n]).max(), 1e-300)) for n in ref}
-
-
-# ---------------------------------------------------------------------------------------------- references with a twin
-def make_ref(weights, nc, side, depth, masks=None, rate=0.0, cls=None):
-    """The float64 reference of a trainer of ``depth`` with ``ref.twin32``, the same class in float32.  With ``masks`` (and
-    ``rate``) the dropout references, masks set on both.  ``cls`` overrides the class (a mutant)."""
-    if cls is None:
-        if masks is None:
-            cls = FineTuneRef if depth == 2 else FineTune7Ref
-        else:
-            cls = FineTuneDropRef if depth == 2 else FineTune7DropRef
-    ref, ref32 = cls(weights, nc, side), cls(weights, nc, side, dtype=torch.float32)
-    if masks is not None:
-        ref.set_masks(masks, rate)
-        ref32.set_masks(masks, rate)
-    ref.twin32 = ref32
-    return ref
+    r.update({"pre64": pre64, "delta": delta, "violations": kink_violations(pre64, delta), "kink_distance": kink_distance(pre64),
+              "loss_bound": max(LOSS_TOL, 4.0 * abs(r["L32"] - r["L"]))})
+    if case["depth"] == 3:
+        r["share"], r["amb"] = r["ref"].conv7_ambiguity(r["xin"], y[idx], case["l2"], delta["conv7"])
+    return r
 
 
 def _forward_pre(ref, x):
@@ -128,7 +97,7 @@ def _forward_pre(ref, x):
     restatement of ``ref.logits`` that keeps what feeds each ReLU6; tests/test_backward_live_host.py asserts that its logits are
     ``ref.logits``' bit for bit."""
     g, P = ref.graph, ref.params
-    masks = getattr(ref, "masks", None)
+    masks = ref.masks
     out = {}
     with torch.no_grad():
         x = ref._t(x) if not torch.is_tensor(x) else x
@@ -185,14 +154,6 @@ def kink_violations(pre64, delta, sites=KINK_SITES):
 def clamp_shares(pre):
     """Per site ``(share at or above 6, share strictly inside (0, 6))``."""
     return {s: (float((v >= 6.0).mean()), float(((v > 0.0) & (v < 6.0)).mean())) for s, v in pre.items()}
-
-
-def locate(got, want):
-    """Where a gradient tensor is wrong, in the style of test_hip_other_checkpoints._locate: the worst element and its values."""
-    d = np.abs(np.asarray(got, np.float64) - want)
-    i = np.unravel_index(int(d.argmax()), d.shape)
-    return {"at": [int(v) for v in i], "got": float(np.asarray(got)[i]), "want": float(want[i]), "abs_err": float(d[i]),
-            "max_abs_want": float(np.abs(want).max()), "elements_above_half_of_worst": int((d > 0.5 * d.max()).sum())}
 
 
 # ---------------------------------------------------------------------------------------------- grad-CAM room, layer s6.bn

@@ -17,13 +17,12 @@ import torch
 import backward_ref as BR
 import checkpoints as CK
 from conftest import parity_set_of
-from finetune7_ref import FineTune7Ref
+from finetune_ref import FineTune7Ref
 from gradcam_ref import GradCamRef
 from oracle import c_oracle, roomnet_ref as R
+from parity_bounds import AT_CLAMP_MIN, INSIDE_MIN, TIE_EDGE
 from roomnet_amd.graph import build_graph
 from roomnet_amd.network import _initializer_values
-from test_checkpoints_host import AT_CLAMP_MIN, INSIDE_MIN
-from test_hip_other_checkpoints import TIE_EDGE
 
 ITEMS_32 = list(range(0, 8)) + list(range(40, 64))          # the 32 parity items of the shipped-checkpoint backward tests
 VISIBLE = 1000 * BR.GRAD_TOL                                # a change the GPU tests cannot miss

@@ -10,9 +10,9 @@ import pytest
 import checkpoints as CK
 import stage_ref as SR
 from oracle import roomnet_ref as R
+from parity_bounds import AT_CLAMP_MIN, INSIDE_MIN
 from roomnet_amd.graph import build_graph
 
-AT_CLAMP_MIN, INSIDE_MIN = 0.005, 0.15      # live(gain 2.5): per stage 1-9, share at exactly 6 / strictly inside (0, 6)
 SHIPPED_AT_CLAMP_MAX = 1e-4                 # shipped checkpoint: no stage 1-9 above 0.01 % at the clamp
 
 

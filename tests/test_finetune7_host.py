@@ -1,11 +1,11 @@
 """Host side of depth-3 fine-tuning (roomnet_amd/finetune.py) and the float64 reference its GPU tests measure against
-(tests/finetune7_ref.py): the reference's gradients against finite differences, the trained-variable list and the feature shape of
+(tests/finetune_ref.py): the reference's gradients against finite differences, the trained-variable list and the feature shape of
 both depths, and the shapes ``RoomNet.fine_tune`` accepts.  No GPU."""
 import numpy as np
 import pytest
 import torch
 
-from finetune7_ref import FineTune7Ref
+from finetune_ref import FineTune7Ref
 from roomnet_amd import finetune
 from roomnet_amd.graph import build_graph
 

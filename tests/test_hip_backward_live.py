@@ -9,7 +9,7 @@ s7.bn / s6.bn of the four parity images ``CK.PARITY_IDX + [52]``, labels ``arang
 side 300 (conv 7 is 63 x 63: its last row and column lie in no pool window) seeded normal features; plus the handle's own features.
 
 Bounds -- the project's: per variable max|d| / max|g_ref| <= GRAD_TOL = 1e-5; exact zeros wherever float64 is exactly zero;
-conv2d_7/kernel elementwise |d| <= GRAD_TOL max|g| + Amb / n (finetune7_ref.conv7_ambiguity) with conv 7's near-kink share <= 1e-4;
+conv2d_7/kernel elementwise |d| <= GRAD_TOL max|g| + Amb / n (finetune_ref.conv7_ambiguity) with conv 7's near-kink share <= 1e-4;
 the loss within max(5e-6, 4 x |L32 - L64|) of the same call (on `live` with l2 = 0.06 the loss is 14 to 22 and float32 torch itself
 misses it by up to 3.8e-6; 4: another summation order).  DELTA[site] = 4 x max|pre32 - pre64| is computed per call from the float32
 torch yardstick; that no float64 pre-activation of conv 8, conv 9, d0 .. d3 lies within DELTA[site] of 0 or 6 is a CONDITION on
@@ -32,19 +32,18 @@ import torch
 
 import backward_ref as BR
 import checkpoints as CK
+import finetune_harness as H
 from conftest import parity_set_of
+from finetune_harness import LOSS_TOL, SHARE_CAP
 from gradcam_ref import GradCamRef
 from oracle import roomnet_ref as R
+from parity_bounds import MARGIN, TIE_EDGE, _tol
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
-from test_hip_bnstats import _tol
-from test_hip_fused import MARGIN
-from test_hip_other_checkpoints import TIE_EDGE
 
 pytestmark = pytest.mark.gpu
 
 SECTION = "backward_live"
-GRAD_TOL, LOSS_TOL, SHARE_CAP, W7 = BR.GRAD_TOL, BR.LOSS_TOL, BR.SHARE_CAP, BR.W7
 CAM_TOL = 1e-4
 LAYERS = ("s6.bn", "s7.bn")
 
@@ -72,8 +71,8 @@ def handle_feats(four):
 
 
 def _trainer(case, w, n, **kw):
-    return _capi.Trainer(build_graph(case["nc"], case["side"]), w, device=0, max_batch=max(n, 2), depth=case["depth"],
-                         l2_coeff=case["l2"], dropout_rate=case["rate"], dropout_seed=BR.DROP_SEED if case["rate"] else 0, **kw)
+    return H.trainer(w, case["side"], max(n, 2), case["depth"], case["nc"], l2_coeff=case["l2"], dropout_rate=case["rate"],
+                     dropout_seed=BR.DROP_SEED if case["rate"] else 0, **kw)
 
 
 def _condition(r, case):
@@ -84,50 +83,14 @@ def _condition(r, case):
         assert r["share"] <= SHARE_CAP, "FAILED CONDITION on the inputs (not a kernel error): conv-7 near-kink share %g" % r["share"]
 
 
-def _check_one_step(case, w, x, y, idx, record, key=None):
-    """One step of a trainer on slots ``idx`` of ``x`` against float64: the bounds of the module docstring."""
-    key = key or case["key"]
-    n = len(idx)
+def _check_one_step(case, w, x, y, idx, record):
+    """One step of a trainer on slots ``idx`` of ``x`` against float64: the harness's check with the bounds of the module docstring
+    (the loss bound and conv 7's DELTA from the yardstick of this very call) and the kink condition on the inputs."""
     r = BR.reference_of(case, w, x, y, idx)
-    L, G = r["L"], r["G"]
-    tr = _trainer(case, w, n, learn_rate=2e-4)
-    try:
-        assert len(tr.variables()) == len(G) and tr.lib.rn_ft_depth(tr.handle) == case["depth"]
-        losses = tr.run_host(x, y, idx.reshape(1, n))
-        got = tr.read(_capi.RN_FT_GRAD)
-    finally:
-        tr.close()
-    err, yard = BR.grad_errors(got, G), r["yard"]
-    dl, dl32 = abs(float(losses[0]) - L), abs(r["L32"] - L)
-    rec = {"loss": L, "loss_abs": dl, "loss_abs_float32_torch": dl32, "loss_bound": r["loss_bound"],
-           "grad_rel_worst": max(err.values()), "grad_rel_worst_float32_torch": max(yard.values()), "grad_bound": GRAD_TOL,
-           "grad_rel": err, "grad_rel_float32_torch": yard, "delta": r["delta"],
-           "kink_distance": {s: d for s, d in r["kink_distance"].items() if s != "conv7"}}
-    text = "%s: loss %.9g (ref %.9g) |dloss| %.3g (float32 torch %.3g, bound %.3g); worst grad %.3g (float32 torch %.3g)" \
-        % (key, losses[0], L, dl, dl32, r["loss_bound"], max(err.values()), max(yard.values()))
-    if case["depth"] == 3:
-        gmax = float(np.abs(G[W7]).max())
-        d7 = np.abs(got[W7].astype(np.float64) - G[W7])
-        room = GRAD_TOL * gmax + r["amb"] / n
-        over = float((d7 / room).max()) if gmax else 0.0
-        rec.update({"near_kink_share": r["share"], "share_cap": SHARE_CAP, "dw7_over_room_worst": over,
-                    "amb_over_n_max_rel": float(r["amb"].max() / n / max(gmax, 1e-300))})
-        text += "; dW7 %.3g (float32 torch %.3g), share %.3g at delta %.3g, worst dW7 / room %.3g" \
-            % (err[W7], yard[W7], r["share"], r["delta"]["conv7"], over)
-    print(text)
-    record(SECTION, key, rec)
-    _condition(r, case)
-    assert dl <= r["loss_bound"], (dl, r["loss_bound"])
-    if case["depth"] == 3:
-        assert np.all(d7 <= room), ("conv2d_7/kernel: %d elements outside 1e-5 max|g| + Amb / n" % int((d7 > room).sum()),
-                                    BR.locate(got[W7], G[W7]))
-    for name in G:
-        if name != W7:
-            assert err[name] <= GRAD_TOL, (name, err[name], BR.locate(got[name], G[name]))
-        zero = G[name] == 0
-        assert not got[name][zero].any(), "%s: %d entries are exactly zero in float64 and not on the GPU" \
-            % (name, int(got[name][zero].astype(bool).sum()))
-    return r, got, losses
+    return H.check_one_step(w, x, y, idx, case["l2"], record, SECTION, case["key"], case["depth"], case["side"], case["nc"],
+                            case["rate"], BR.DROP_SEED, reference=r, loss_bound=r["loss_bound"], delta=r["delta"].get("conv7"),
+                            condition=lambda: _condition(r, case),
+                            extra={"delta": r["delta"], "kink_distance": {s: d for s, d in r["kink_distance"].items() if s != "conv7"}})
 
 
 def _ids(kind):

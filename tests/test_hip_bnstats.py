@@ -17,6 +17,7 @@ import torch
 
 import bn_batch_ref
 from oracle import roomnet_ref as R
+from parity_bounds import _tol
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
 from roomnet_amd.network import RoomNet, _initializer_values
@@ -30,11 +31,6 @@ RN_E_INVALID, RN_E_STATE, RN_E_RANGE = -1, -4, -5
 
 def _refs(weights, ims):
     return bn_batch_ref.forward(weights, ims), bn_batch_ref.forward(weights, ims, dtype=torch.float32)
-
-
-def _tol(want64, got32, scale=None):
-    scale = float(np.abs(want64).max()) if scale is None else scale
-    return max(1e-4 * max(scale, 1e-3), 4.0 * float(np.abs(np.asarray(got32, np.float64) - want64).max()))
 
 
 def _check_call(eng, ims, r64, r32, record, key):

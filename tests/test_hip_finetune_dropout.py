@@ -1,13 +1,11 @@
 """Dropout while fine-tuning on the GPU (rn_ft_set_dropout, rn_ft_dropout, rn_ft_dropout_mask; RoomNet.fine_tune(dropout_rate=)):
 the device's masks against the host statement of the stream byte for byte, one step's loss and gradients at depth 2, at the 600
 geometry and at depth 3, and a 20-step Adam trajectory against the float64 reference with the host masks
-(tests/finetune_dropout_ref.py), determinism and the identities the step counter in the generator's counter buys, and the Python
+(tests/finetune_ref.py with ``set_masks``), determinism and the identities the step counter in the generator's counter buys, and the Python
 surface.
 
-Bounds: the project's existing ones, unchanged -- gradients per variable max|d| / max|g_ref| <= 1e-5, |d loss| <= 5e-6, entries that
-are exactly zero in float64 exactly zero on the GPU; conv2d_7/kernel elementwise within 1e-5 max|g_ref| + Amb / n on condition that at
-most 1e-4 of conv 7's pre-activations lie within 1e-6 of a ReLU6 kink (finetune7_ref.conv7_ambiguity, evaluated on the DROPPED s6.bn);
-trajectory: every parameter within max(0.01 learn_rate, 3 x the float32 torch run's drift) of float64 and every loss within 5e-6.
+Bounds: the project's existing ones, unchanged, stated with the checks in tests/finetune_harness.py; conv 7's room is evaluated on the
+DROPPED s6.bn; trajectory: every parameter within max(0.01 learn_rate, 3 x the float32 torch run's drift) of float64.
 Each test records the kernel's error beside the float32 torch run of the same masked mathematics through
 ``record("finetune_dropout", ...)``.
 
@@ -26,64 +24,22 @@ import numpy as np
 import pytest
 import torch
 
-from finetune_dropout_ref import FineTune7DropRef, FineTuneDropRef, dropped_x6, host_masks
+import finetune_harness as H
+from finetune_harness import LABELS, RN_E_INVALID, RN_E_RANGE, feats, images, starts  # noqa: F401  (fixtures)
+from finetune_ref import FineTuneRef, host_masks
 from roomnet_amd import _capi, finetune
 from roomnet_amd.graph import build_graph
-from roomnet_amd.network import RoomNet, _initializer_values
+from roomnet_amd.network import RoomNet
 
 pytestmark = pytest.mark.gpu
 
-ITEMS = list(range(0, 8)) + list(range(40, 64))          # the 32 parity items and labels of test_hip_finetune.py
-LABELS = np.arange(32, dtype=np.int32) % 6
-GRAD_TOL, LOSS_TOL = 1e-5, 5e-6
-DELTA, SHARE_CAP = 1e-6, 1e-4
-W7 = "conv2d_7/kernel"
-RN_E_INVALID, RN_E_RANGE = -1, -5
 SEED = 2024
 SEED_600 = 3
 SEED_HI = (0x9E3 << 32) | 0x5EED                         # above 2^32: the key's second word is not zero
 SITE0 = 46 * 46 * 128
+SECTION = "finetune_dropout"
 
-
-def _engine(weights, dtype, max_batch=32, **kw):
-    return _capi.Engine(build_graph(6, 224), weights, device=0, dtype=dtype, max_batch=max_batch, **kw)
-
-
-@pytest.fixture(scope="module")
-def images(parity_images):
-    return np.ascontiguousarray(parity_images[ITEMS])
-
-
-@pytest.fixture(scope="module")
-def feats(weights, images):
-    """The handle's own f32 features: ``{2: s7.bn [32, 21, 21, 16], 3: s6.bn [32, 46, 46, 128]}``."""
-    eng = _engine(weights, "f32")
-    try:
-        return {2: eng.features_u8(images), 3: eng.features_u8(images, depth=3)}
-    finally:
-        eng.close()
-
-
-@pytest.fixture(scope="module")
-def starts(weights):
-    """The shipped checkpoint, and the reference's load() state in training mode: the conv trunk restored, the dense head at its
-    initial values."""
-    g = build_graph(6, 224)
-    fresh = dict(weights)
-    init = _initializer_values(g, seed=1)
-    for d in g.dense:
-        for name in init:
-            if name.startswith(d.name + "/") or (d.bn_name and name.startswith(d.bn_name + "/")):
-                fresh[name] = init[name]
-    return {"shipped": weights, "fresh": fresh}
-
-
-def _trainer(w, side=224, max_batch=45, depth=2, **kw):
-    return _capi.Trainer(build_graph(6, side), w, device=0, max_batch=max_batch, depth=depth, **kw)
-
-
-def _grad_errors(got, ref):
-    return {n: float(np.abs(got[n].astype(np.float64) - ref[n]).max() / max(np.abs(ref[n]).max(), 1e-300)) for n in ref}
+_trainer, _state, _same = H.trainer, H.state, H.same_bytes
 
 
 def _batch_index(steps, batch, seed=11):
@@ -149,62 +105,15 @@ def test_mask_and_rate_errors(weights):
 
 
 # ---- 2.-4. one step's loss and gradients
-def _check_one_step(w, side, depth, x, y, idx, l2, rate, seed, record, key):
-    """One step of a trainer with dropout on slots ``idx`` of ``x`` against float64 with the host masks of step 0."""
-    n = len(idx)
-    g = build_graph(6, side)
-    masks = host_masks(g, depth, seed, 0, n, rate)
-    xin = x[idx] if depth == 2 else dropped_x6(x[idx], masks[0], rate)
-    cls = FineTuneDropRef if depth == 2 else FineTune7DropRef
-    ref, ref32 = cls(w, 6, side), cls(w, 6, side, dtype=torch.float32)
-    ref.set_masks(masks, rate)
-    ref32.set_masks(masks, rate)
-    L, G = ref.loss_and_grads(xin, y[idx], l2)
-    L32, G32 = ref32.loss_and_grads(xin, y[idx], l2)
-    if depth == 3:
-        share, amb = ref.conv7_ambiguity(xin, y[idx], l2, DELTA)
-    tr = _trainer(w, side=side, max_batch=max(n, 2), depth=depth, learn_rate=2e-4, l2_coeff=l2, dropout_rate=rate, dropout_seed=seed)
-    try:
-        assert tr.dropout() == (float(np.float32(rate)), seed)
-        losses = tr.run_host(x, y, np.asarray(idx, np.int32).reshape(1, n))
-        got = tr.read(_capi.RN_FT_GRAD)
-    finally:
-        tr.close()
-    err, yard = _grad_errors(got, G), _grad_errors(G32, G)
-    dl, dl32 = abs(float(losses[0]) - L), abs(L32 - L)
-    rec = {"loss_abs": dl, "loss_abs_float32_torch": dl32, "grad_rel_worst": max(err.values()),
-           "grad_rel_worst_float32_torch": max(yard.values()), "grad_rel": err}
-    text = "%s: loss %.9g (ref %.9g) |dloss| %.3g (float32 torch %.3g); worst grad %.3g (float32 torch %.3g)" \
-        % (key, losses[0], L, dl, dl32, max(err.values()), max(yard.values()))
-    if depth == 3:
-        d7 = np.abs(got[W7].astype(np.float64) - G[W7])
-        room = GRAD_TOL * np.abs(G[W7]).max() + amb / n
-        rec.update({"near_kink_share": share, "amb_over_n_max_rel": float(amb.max() / n / np.abs(G[W7]).max()),
-                    "dw7_over_room_worst": float((d7 / room).max()), "grad_rel_float32_torch": yard})
-        text += "; dW7 %.3g (float32 torch %.3g), share %.3g, worst dW7 / room %.3g" % (err[W7], yard[W7], share, float((d7 / room).max()))
-    print(text)
-    record("finetune_dropout", key, rec)
-    if depth == 3:
-        assert share <= SHARE_CAP
-        assert np.all(d7 <= room), "conv2d_7/kernel: %d elements outside 1e-5 max|g| + Amb / n" % int((d7 > room).sum())
-    assert dl <= LOSS_TOL
-    for name in G:
-        if name != W7:
-            assert err[name] <= GRAD_TOL, (name, err[name])
-        zero = G[name] == 0
-        assert not got[name][zero].any(), "%s: %d entries are exactly zero in float64 and not on the GPU" \
-            % (name, int(got[name][zero].astype(bool).sum()))
-    return masks, G
-
-
 @pytest.mark.parametrize("batch", [1, 3, 45])
 @pytest.mark.parametrize("l2", [0.06, 0.0])
 @pytest.mark.parametrize("start", ["shipped", "fresh"])
 @pytest.mark.parametrize("rate", [0.35, 0.2])
 def test_one_step_depth_2(starts, feats, record, rate, start, l2, batch):
     idx = np.arange(batch, dtype=np.int32) % 32             # batch 45: items 0-12 occur again in slots 32-44, under other masks
-    masks, G = _check_one_step(starts[start], 224, 2, feats[2], LABELS, idx, l2, rate, SEED, record,
-                               "one_step_rate_%g_%s_l2_%g_batch_%d" % (rate, start, l2, batch))
+    r, _, _ = H.check_one_step(starts[start], feats[2], LABELS, idx, l2, record, SECTION,
+                               "one_step_rate_%g_%s_l2_%g_batch_%d" % (rate, start, l2, batch), 2, rate=rate, seed=SEED)
+    masks, G = r["masks"], r["G"]
     if batch == 1 and l2 == 0.0:
         # the zero check above is not empty: a dropped input's whole kernel row has no gradient
         for site, name in ((1, "dense/kernel"), (2, "dense_1/kernel"), (3, "dense_2/kernel"), (4, "dense_3/kernel")):
@@ -221,83 +130,31 @@ def test_one_step_600_geometry(weights, record):
     rng = np.random.default_rng(68)
     x7 = (rng.standard_normal((2, 68, 68, 16)) * 0.5).astype(np.float32)
     y = np.array([2, 5], np.int32)
-    ref = FineTuneDropRef(w, 6, 600)
+    ref = FineTuneRef(w, 6, 600)
     ref.set_masks(host_masks(g, 2, SEED_600, 0, 2, 0.35), 0.35)
     with torch.no_grad():
         r = ref.logits(x7).numpy()
     assert (((r > 0) & (r < 6.0 * ref.scale)).sum(1) >= 1).all(), "an item without a live logit: its head gradient is zero"
-    _check_one_step(w, 600, 2, x7, y, np.arange(2), 0.06, 0.35, SEED_600, record, "one_step_600")
+    H.check_one_step(w, x7, y, np.arange(2), 0.06, record, SECTION, "one_step_600", 2, side=600, rate=0.35, seed=SEED_600)
 
 
 @pytest.mark.parametrize("batch", [1, 45])
 def test_one_step_depth_3(starts, feats, record, batch):
     idx = np.arange(batch, dtype=np.int32) % 32
-    _check_one_step(starts["shipped"], 224, 3, feats[3], LABELS, idx, 0.06, 0.35, SEED, record, "one_step_depth_3_batch_%d" % batch)
+    H.check_one_step(starts["shipped"], feats[3], LABELS, idx, 0.06, record, SECTION, "one_step_depth_3_batch_%d" % batch, 3, rate=0.35, seed=SEED)
 
 
 # ---- 5. trajectory
 def test_trajectory_20_steps(starts, feats, record):
-    w = starts["shipped"]
-    lr, l2, ns, rate = 2e-4, 0.06, 10000, 0.35
-    index = _batch_index(20, 45)
-    ref, ref32 = FineTuneDropRef(w, 6, 224), FineTuneDropRef(w, 6, 224, dtype=torch.float32)
-    Lref = ref.train_dropout(feats[2], LABELS, index, lr, ns, l2, SEED, rate)
-    L32 = ref32.train_dropout(feats[2], LABELS, index, lr, ns, l2, SEED, rate)
-    P, P32 = ref.values(), ref32.values()
-    tr = _trainer(w, learn_rate=lr, l2_coeff=l2, num_steps=ns, dropout_rate=rate, dropout_seed=SEED)
-    try:
-        losses = tr.run_host(feats[2], LABELS, index)
-        got = tr.read()
-        assert tr.step_count() == 20
-    finally:
-        tr.close()
-    drift = max(float(np.abs(got[n] - P[n]).max()) for n in P)
-    drift32 = max(float(np.abs(P32[n] - P[n]).max()) for n in P)
-    moved = max(float(np.abs(P[n] - np.asarray(w[n], np.float64)).max()) for n in P)
-    dl, dl32 = float(np.abs(losses - Lref).max()), float(np.abs(L32 - Lref).max())
-    bound = max(0.01 * lr, 3 * drift32)
-    print("trajectory: parameter drift %.3g (float32 torch %.3g, bound %.3g), parameters moved %.3g = %.1f lr; loss drift %.3g "
-          "(float32 torch %.3g)" % (drift, drift32, bound, moved, moved / lr, dl, dl32))
-    record("finetune_dropout", "trajectory", {"param_abs": drift, "param_abs_float32_torch": drift32, "param_moved": moved,
-                                              "loss_abs": dl, "loss_abs_float32_torch": dl32, "bound_param": bound})
-    assert drift <= bound
-    assert dl <= LOSS_TOL
+    H.check_trajectory(starts["shipped"], feats[2], _batch_index(20, 45), record, SECTION, "trajectory", 2, drift32_factor=3, rate=0.35,
+                       seed=SEED)
 
 
 # ---- 6. determinism and identity
-def _state(tr):
-    return [tr.read(), tr.read(_capi.RN_FT_ADAM_M), tr.read(_capi.RN_FT_ADAM_V)]
-
-
-def _same(a, b):
-    for x, y in zip(a, b):
-        assert x.keys() == y.keys()
-        for n in x:
-            assert x[n].tobytes() == y[n].tobytes(), n
-
-
 @pytest.mark.parametrize("depth", [2, 3])
 def test_same_calls_same_bytes_and_step_splitting(starts, feats, depth):
-    w = starts["fresh"]
     steps, batch = (20, 45) if depth == 2 else (4, 9)
-    index = _batch_index(steps, batch)
-
-    def run(split):
-        tr = _trainer(w, depth=depth, learn_rate=2e-4, l2_coeff=0.06, dropout_rate=0.35, dropout_seed=SEED_HI)
-        d = [tr.upload(feats[depth]), tr.upload(LABELS), tr.upload(index)]
-        try:
-            if split:
-                losses = np.concatenate([tr.run(d[0], d[1], 32, d[2] + batch * 4 * s, batch, 1) for s in range(steps)])
-            else:
-                losses = tr.run(d[0], d[1], 32, d[2], batch, steps)
-            return losses, _state(tr)
-        finally:
-            tr.close()
-
-    a, b, c = run(False), run(False), run(True)
-    for other in (b, c):
-        assert a[0].tobytes() == other[0].tobytes()
-        _same(a[1], other[1])
+    H.check_determinism(starts["fresh"], feats[depth], _batch_index(steps, batch), depth, dropout_rate=0.35, dropout_seed=SEED_HI)
 
 
 @pytest.mark.parametrize("depth", [2, 3])

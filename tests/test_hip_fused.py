@@ -10,6 +10,7 @@ import pytest
 
 from conftest import with_gammas
 from oracle import c_oracle
+from parity_bounds import FUSED_AWAY, MARGIN, STAGE_TOL, _downstream_same, _same_up_to_sum_order
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
 
@@ -21,10 +22,6 @@ TOL_LOGITS = 0.1          # SURVEY 8c's bound on |logit - fp64 truth| for 16-bit
 # (profiles/r6_parity.json; rounds 1-5: 0.080 / 0.022 and 0.126 / 0.014)
 TOL_LOGITS_224 = {"bf16": 0.06, "f16": 0.05}
 TOL_LOGITS_600 = {"bf16": 0.1, "f16": 0.05}
-MARGIN = 0.2
-# max |err| / absmax of the stage output.  Observed (profiles/r3_parity.json): bf16 <= 0.0067 at 224 and <= 0.0059 at 600,
-# f16 <= 0.0048 / 0.0024: the bounds sit at about twice that (round 2 carried 0.04 for bf16)
-STAGE_TOL = {"bf16": 0.0125, "f16": 0.006}
 
 
 @pytest.fixture(scope="module", params=["bf16", "f16"])
@@ -46,11 +43,6 @@ def engine_stagewise(request, weights):
 
 def _stage_out_names(g):
     return ["s%d.%s" % (s.index, "bn2" if s.residual else "bn") for s in g.stages]
-
-
-# never written to HBM on a default handle: s0.bn lives in the private LDS rings of stage 1's kernel (rn_stage_rw.hip,
-# S0F), s2.bn in the B ring of the fused stage pair (rn_stage23.hip)
-FUSED_AWAY = {"s0.bn", "s2.bn"}
 
 
 def _check_stage_outputs(engine, weights, parity_images, skip=(), record=None, label=""):
@@ -99,42 +91,6 @@ def test_stage0_is_exact_up_to_the_rounding_of_its_output(engine_stagewise, weig
     bound = 2.0 * half_ulp * np.abs(want) + 5e-6 * np.abs(want).max()
     bad = np.abs(got - want) > bound
     assert not bad.any(), (int(bad.sum()), float(np.abs(got - want).max()), float(np.abs(want).max()))
-
-def _same_up_to_sum_order(a, b, dtype, what, frac=1e-4, n_ulp=6):
-    """Equal up to the fp32 ORDER of sums, where it shows through the 16-bit rounding.  Two sources: (1) the fused pair adds
-    its fp16 pooling terms in 16x16x32 MFMAs, the stage kernels in 32x32x16 ones; (2) round 5: on the shipped checkpoint the
-    pair's second conv contracts 16 of the 32 channels of its input on the matrix cores and takes the other 16 -- FROZEN
-    channels, constants for every image (rn_fused_prepare proves it) -- as one per-cout constant summed on the host in double:
-    the same products, another summation order (and the channels sit in another order inside a tap).  Seen: 2-3e-5 of the
-    elements of s3.bn2 off by one 16-bit ulp (f16; bf16 5e-6), single elements near zero by up to 3 ulps of the 1 % floor;
-    downstream tensors inherit it (`frac`, `n_ulp` wider there).  The bound per element stays a few 16-bit ulps: a corrupted
-    tile is orders of magnitude outside it."""
-    bad = a != b
-    n = int(bad.sum())
-    if n == 0:
-        return
-    ulp = 2.0 ** (-8 if dtype == "bf16" else -11)
-    scale = float(np.abs(b).max())
-    # bounded PER ELEMENT: n_ulp 16-bit ulps of the element itself (values below 1 % of the tensor's abs-max are measured
-    # against that floor: a folded-BN output near zero is a difference of two larger numbers)
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    lim = n_ulp * ulp * np.maximum(np.abs(b.astype(np.float64)), 0.01 * scale)
-    worst = float((d / lim).max())
-    # (tensors of a few hundred elements -- s9.bn2 is 2 x 2 x 16 per image -- get a floor of 32 differing elements: every one of
-    #  them sums the whole image, a handful of one-ulp flips upstream moves more than `frac` of them)
-    assert n <= max(32 if a.size < 4096 else 2, frac * a.size) and worst <= 1.0, (what, dtype, n, a.size, worst, np.argwhere(bad)[:4].tolist())
-
-
-def _downstream_same(fused, plain, names, nb, dtype, probs_f, probs_p, ids_f, ids_p):
-    for name in names:
-        if name.startswith("d"):              # the fp32 logits: every element moves a little, none by much
-            np.testing.assert_allclose(fused.tap(name, nb), plain.tap(name, nb), rtol=0, atol=1e-2, err_msg=name)
-            continue
-        _same_up_to_sum_order(fused.tap(name, nb), plain.tap(name, nb), dtype, name, frac=6e-2, n_ulp=12)
-    np.testing.assert_allclose(probs_f, probs_p, rtol=0, atol=2e-3)
-    np.testing.assert_array_equal(ids_f, ids_p)
-
-
 
 
 @pytest.mark.parametrize("nb", [1, 5, 8, 33, 70])

@@ -21,17 +21,15 @@ import checkpoints as CK
 import stage_ref as SR
 from conftest import parity_set_of
 from oracle import c_oracle, roomnet_ref as R
+from parity_bounds import FUSED_AWAY, MARGIN, STAGE_TOL, TIE_EDGE, _downstream_same, _same_up_to_sum_order, _tol
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
-from test_hip_bnstats import _tol
-from test_hip_fused import FUSED_AWAY, MARGIN, STAGE_TOL, _downstream_same, _same_up_to_sum_order
 
 pytestmark = pytest.mark.gpu
 
 NOTHING_FOLDED = {"pair_channels_not_convolved": 0, "pair_channels_proven_frozen": 0, "residual_stage_folded": -1,
                   "residual_stage_live_quarters": 4}
 WHOLE_CHAIN_MARGIN = 0.5      # (f): ids must agree with float64 wherever its top-2 logit margin exceeds this
-TIE_EDGE = 1e-3               # (d): an exact float64 tie counts only if every tied pre-activation is this far from 0 and 6
 SECTION = "other_checkpoints"
 
 

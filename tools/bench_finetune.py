@@ -5,7 +5,7 @@
   - ms per step of the float32 torch restatement (tests/finetune_ref.py) on 16 CPU threads, batch 45 at 224: what a user has today.
 
 --depth 3 measures the trainer of the whole last conv block on cached s6.bn (rn_ft_create_depth: four launches per step, 256 resident
-items at 224 and 48 at 600 -- an item is 1.08 MB and 10 MB) against the float32 torch restatement tests/finetune7_ref.py, and states
+items at 224 and 48 at 600 -- an item is 1.08 MB and 10 MB) against the float32 torch restatement tests/finetune_ref.py, and states
 each step against its arithmetic floor.  --lib PATH measures another build of the library (depth 2 of the commit before, say).
 
 --dropout RATE measures, at batch 45 / 224 and both depths in one session with the arms alternating run by run, the step with
@@ -183,8 +183,7 @@ def features_case(steps=20, warmup=5):
 def torch_case(batch=45, steps=5, threads=16, depth=2):
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from finetune_ref import FineTuneRef
-    from finetune7_ref import FineTune7Ref
+    from finetune_ref import FineTune7Ref, FineTuneRef
     from roomnet_amd import finetune
     torch.set_num_threads(threads)
     g, w = _weights(224)

@@ -672,6 +672,31 @@ RN_API int rn_group_plan(int n, int ndev, int max_batch_per_device, int num_clas
 RN_API int rn_band_plan(int family, int n, int n_cu, int out_side, int n_colblocks, int wgs_per_cu, int pool_k, int pool_s,
                         int* rows_per_band, int* n_bands);
 
+/* ---- plan of one conv stage on the float32 matrix-core path, as a pure function (no handle, no device) ---------------------
+ * What rn_create decides for a stage of an RN_DTYPE_F32 handle without RN_FLAG_TAPS from its shape alone: the kernel, the row
+ * of its variant table and the launch geometry (the dynamic LDS included, which no kernel trace shows).
+ *   live_cin      input channels the stage contracts (cin, or fewer where its producer's BN freezes the last ones; where no
+ *                 variant contracts that count the plan contracts all of them and says so in live_cin)
+ *   frozen_couts  couts not convolved: of a residual stage, whole 32-cout tiles left to the residual-only launch (n_ctg
+ *                 shrinks); otherwise constants written beside 16 live couts by the 16-cout kernel (without such a variant the
+ *                 plan convolves every cout and says so in frozen_couts)
+ * pinned by tests/test_f32m_plan.py.  A bad argument is RN_E_INVALID. */
+#define RN_F32M_OFF 0       /* not covered: the per-node kernels run the stage */
+#define RN_F32M_WIDE 1      /* 32-cout tiles, v_mfma_f32_32x32x2_f32 */
+#define RN_F32M_16 2        /* 16 couts, v_mfma_f32_16x16x4_f32 */
+typedef struct rn_f32m_stage_plan {
+    int kind;               /* RN_F32M_* */
+    int variant;            /* row of the kind's variant table (-1: none) */
+    int live_cin, frozen_couts;
+    int npt;                /* pixel tiles per workgroup */
+    int ringcols;           /* columns of a ring row in LDS */
+    int lds;                /* dynamic LDS bytes of the launch */
+    int n_colblocks, n_ctg; /* column blocks; workgroups the cout tiles are split over */
+    int threads;            /* threads per workgroup */
+} rn_f32m_stage_plan;
+RN_API int rn_f32m_plan(int cin, int cout, int pool_k, int pool_s, int residual, int in_side, int out_side, int live_cin,
+                        int frozen_couts, rn_f32m_stage_plan* plan);
+
 /* ---- simple device memory helpers (so a host language without a HIP binding
  * can keep batches resident in HBM) ---------------------------------------- */
 RN_API int rn_device_malloc(rn_handle* h, size_t bytes, void** d_ptr);

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "rn_crop_resize_u8_device", "rn_crop_resize_batch_u8_device", "rn_classify_images_u8", "rn_host_alloc", "rn_host_free", "rn_frozen_info", "rn_const_info",
     "rn_group_create", "rn_group_destroy", "rn_group_size", "rn_group_handle", "rn_group_forward_u8",
     "rn_group_forward_u8_device", "rn_group_result_buffer", "rn_group_sync", "rn_group_plan",
-    "rn_band_plan",
+    "rn_band_plan", "rn_f32m_plan",
     "rn_grad_cam_u8", "rn_grad_cam_f32", "rn_grad_cam_u8_device",
     "rn_bn_count", "rn_bn_info", "rn_bn_batch_stats",
     "rn_features_shape", "rn_features_u8", "rn_features_u8_device",
@@ -87,6 +87,10 @@ class rn_weights(C.Structure):
     _fields_ = [("im_side", C.c_int32), ("num_classes", C.c_int32), ("n_stages", C.c_int32),
                 ("n_dense", C.c_int32), ("bn_epsilon", C.c_float),
                 ("stages", C.POINTER(rn_conv_stage)), ("dense", C.POINTER(rn_dense_layer))]
+
+
+class rn_f32m_stage_plan(C.Structure):
+    _fields_ = [(name, C.c_int) for name in ("kind", "variant", "live_cin", "frozen_couts", "npt", "ringcols", "lds", "n_colblocks", "n_ctg", "threads")]
 
 
 class rn_stage_ms(C.Structure):
@@ -233,6 +237,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "rn_group_plan"):
         lib.rn_group_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(sz)]
         lib.rn_group_plan.restype = i32
+    if hasattr(lib, "rn_f32m_plan"):
+        lib.rn_f32m_plan.argtypes = [i32] * 9 + [C.POINTER(rn_f32m_stage_plan)]
+        lib.rn_f32m_plan.restype = i32
     if hasattr(lib, "rn_band_plan"):
         lib.rn_band_plan.argtypes = [i32] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.rn_band_plan.restype = i32
@@ -1129,6 +1136,23 @@ def band_plan(family, n: int, n_cu: int, out_side: int, n_colblocks: int, wgs_pe
     rows, bands = C.c_int(0), C.c_int(0)
     _check(lib, lib.rn_band_plan(fam, n, n_cu, out_side, n_colblocks, wgs_per_cu, pool_k, pool_s, C.byref(rows), C.byref(bands)), "rn_band_plan")
     return int(rows.value), int(bands.value)
+
+
+# kernel kinds of rn_f32m_plan (include/roomnet_hip.h: RN_F32M_*)
+F32M_KINDS = ("off", "wide", "m16")
+
+
+def f32m_plan(cin: int, cout: int, pool_k: int, pool_s: int, residual: bool, in_side: int, out_side: int, live_cin: Optional[int] = None,
+              frozen_couts: int = 0, lib_path: Optional[str] = None) -> Dict[str, object]:
+    """``rn_f32m_plan``: what a float32 handle decides for a conv stage of this shape (kernel kind, variant, launch geometry,
+    dynamic LDS) -- no GPU needed."""
+    lib = load_library(lib_path)
+    p = rn_f32m_stage_plan()
+    _check(lib, lib.rn_f32m_plan(cin, cout, pool_k, pool_s, int(residual), in_side, out_side, cin if live_cin is None else live_cin, frozen_couts,
+                                 C.byref(p)), "rn_f32m_plan")
+    out = {name: int(getattr(p, name)) for name, _ in rn_f32m_stage_plan._fields_}
+    out["kind"] = F32M_KINDS[out["kind"]]
+    return out
 
 
 class Group:

@@ -119,6 +119,29 @@ void RelabelledWeights::permute_cins(int stage, const std::vector<int>& pi) {
     st.kernel = owned.back().data();
 }
 
+void RelabelledWeights::permute_block(int r, const std::vector<int>& pi) {
+    permute_couts(r - 1, pi);
+    permute_couts(r, pi);
+    permute_cins(r, pi);
+    permute_cins(r + 1, pi);
+}
+
+bool rn_fold_block_at(const rn_weights* w, int r) {
+    if (r < 1 || r + 1 >= w->n_stages) return false;
+    const rn_conv_stage &s4 = w->stages[r - 1], &s5 = w->stages[r], &s6 = w->stages[r + 1];
+    if (!(s5.cin == 64 && s5.cout == 64 && s5.pool_k == 4 && s5.pool_s == 2 && s5.skip_stage == r - 1 && s5.gamma2 && s4.cout == 64 &&
+          s4.skip_stage < 0 && s6.cin == 64 && s6.skip_stage < 0))
+        return false;
+    bool other_use = false;          // nobody else may pair with the relabelled tensors
+    for (int k = 0; k < w->n_stages; ++k) other_use |= (k != r && w->stages[k].skip_stage == r - 1) || w->stages[k].skip_stage == r;
+    return !other_use;
+}
+
+void rn_fold_block_register(rn_handle* h, int r, const std::vector<int>& pi) {
+    h->node_perm[h->stages[r - 1].node_bn] = pi;
+    h->node_perm[h->stages[r].node_bn2] = pi;
+}
+
 namespace {
 
 int upload_bn(rn_handle* h, int c, const float* gamma, const float* beta, const float* mean, const float* var,
@@ -339,7 +362,7 @@ int alloc_buffers(rn_handle* h) {
     }
     size_t scratch_elems = 0;
     for (auto& s : h->stages) {
-        const int out_node = s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn;
+        const int out_node = rn_stage_out_node(s);
         for (int id : {s.node_conv, s.node_pool, s.node_bn, s.node_add, s.node_bn2}) {
             if (id < 0) continue;
             NodeBuf& n = h->nodes[id];
@@ -374,7 +397,7 @@ int alloc_buffers(rn_handle* h) {
     // flat aliases the last stage output
     {
         const StagePlan& last = h->stages.back();
-        const NodeBuf& src = h->nodes[last.node_bn2 >= 0 ? last.node_bn2 : last.node_bn];
+        const NodeBuf& src = h->nodes[rn_stage_out_node(last)];
         h->nodes[h->node_flat].ptr = src.ptr;
         h->nodes[h->node_flat].dtype = src.dtype;
     }
@@ -432,8 +455,8 @@ int forward_unfused(rn_handle* h, const float* d_rgb, int n, float* d_probs, int
         StagePlan& s = h->stages[i];
         if (rn_f32m_covers(h, static_cast<int>(i))) {
             // the whole stage in one launch on the matrix cores; only its output node is written
-            if ((rc = rn_f32m_launch(h, static_cast<int>(i), cur, n)) != RN_OK) return rc;
-            cur = static_cast<const float*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr);
+            if ((rc = rn_f32m_launch(h, static_cast<int>(i), n)) != RN_OK) return rc;
+            cur = static_cast<const float*>(h->nodes[rn_stage_out_node(s)].ptr);
             record(h, 2 + static_cast<int>(i));
             continue;
         }
@@ -523,94 +546,6 @@ int check_device(int device, int* n_cu) {
     return RN_OK;
 }
 
-// The frozen-channel folds of a float32 handle (rn_create): the stage each applies to (-1: none) and its channel relabelling.
-struct F32Folds {
-    int fold_r = -1;                 // the 64 -> 64 residual stage whose second 32-cout tile is all frozen
-    std::vector<int> fold_pi;
-    int kfold_r = -1;                // the stage whose last input channels are frozen
-    std::vector<int> kfold_pi;
-    int kfold_live = 0, kfold_proven = 0;
-};
-
-// relabelling of `n` channels that puts the first `keep` of `frozen` behind all the others, those in ascending order
-std::vector<int> frozen_last(int n, std::vector<int> frozen, size_t keep) {
-    frozen.resize(keep);
-    std::vector<int> pi;
-    for (int c = 0; c < n; ++c)
-        if (std::find(frozen.begin(), frozen.end(), c) == frozen.end()) pi.push_back(c);
-    pi.insert(pi.end(), frozen.begin(), frozen.end());
-    return pi;
-}
-
-// ---- float32 handles on the matrix-core path: frozen first-BN channels of a 64 -> 64 residual stage (stage 5).  The stage
-// kernels form y1 = ((x * 1/16 - mean) * inv + beta) un-contracted: where |inv| * max(|mean|, |6 - mean|) < 2^-25 |beta| the
-// product vanishes against beta and y1 IS beta for every input (the reference's float32 computes the same expression).  With
-// >= 32 such channels the stage's channels are relabelled on a copy of the weights (stage 4's couts, stage 5's cins + couts,
-// stage 6's cins: the residual pairs channel c of stage 4's output with channel c of stage 5's) so that the second 32-cout
-// tile is all frozen: it is not convolved (rn_f32m_launch runs the residual for it alone).  rn_tap un-relabels.
-F32Folds plan_f32_folds(const rn_weights* w, int dtype, unsigned flags, RelabelledWeights& rw) {
-    F32Folds f;
-    if (dtype != RN_DTYPE_F32 || (flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_BATCH_STATS))) return f;
-    auto frozen_couts = [&](const rn_conv_stage& st) {
-        std::vector<int> frozen;
-        for (int c = 0; c < st.cout; ++c) {
-            const float inv = rn_bn_inv(st.variance[c], st.gamma[c], w->bn_epsilon);
-            const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
-            if (std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8)
-                frozen.push_back(c);
-        }
-        return frozen;
-    };
-    for (int r = 2; r + 1 < w->n_stages && f.fold_r < 0; ++r) {
-        const rn_conv_stage& s5 = w->stages[r];
-        const rn_conv_stage& s4 = w->stages[r - 1];
-        const rn_conv_stage& s6 = w->stages[r + 1];
-        if (!(s5.cin == 64 && s5.cout == 64 && s5.pool_k == 4 && s5.pool_s == 2 && s5.skip_stage == r - 1 && s5.gamma2 && s4.cout == 64 &&
-              s4.skip_stage < 0 && s6.cin == 64 && s6.skip_stage < 0 && s5.gamma && s5.beta && s5.mean && s5.variance))
-            continue;
-        bool other_use = false;
-        for (int k = 0; k < w->n_stages; ++k) other_use |= (k != r && w->stages[k].skip_stage == r - 1) || w->stages[k].skip_stage == r;
-        if (other_use) continue;
-        const std::vector<int> frozen = frozen_couts(s5);
-        if (frozen.size() < 32) continue;
-        f.fold_pi = frozen_last(64, frozen, 32);
-        f.fold_r = r;
-    }
-    if (f.fold_r >= 0) {
-        rw.permute_couts(f.fold_r - 1, f.fold_pi);
-        rw.permute_couts(f.fold_r, f.fold_pi);
-        rw.permute_cins(f.fold_r, f.fold_pi);
-        rw.permute_cins(f.fold_r + 1, f.fold_pi);
-    }
-    // ---- ... and frozen INPUT channels: a pooled stage p without a second BN whose output only feeds the convolution of stage
-    // p + 1 (nobody's residual) and whose BN freezes >= 8 channels (same inequality).  Its couts / the consumer's cins are
-    // relabelled so that the last 8 k channels are all frozen; the consumer contracts the others and starts its accumulators
-    // from the frozen ones' contribution (rn_f32m_prepare: a variant of the stage kernel must exist for that channel count)
-    for (int r = 1; r < w->n_stages && f.kfold_r < 0; ++r) {
-        const int p = r - 1;
-        const rn_conv_stage& sp = rw.stages[p];
-        const rn_conv_stage& sc = rw.stages[r];
-        if (f.fold_r >= 0 && (p == f.fold_r - 1 || p == f.fold_r)) continue;          // (those channels are relabelled already)
-        if (sp.skip_stage >= 0 || sp.gamma2 || sp.pool_k != 4 || !sp.gamma || !sp.beta || !sp.mean || !sp.variance) continue;
-        if (sc.cin != sp.cout || sp.cout % 8 != 0 || sp.cout > 64) continue;
-        bool other_use = false;
-        for (int k = 0; k < w->n_stages; ++k) other_use |= w->stages[k].skip_stage == p;
-        if (other_use) continue;
-        const std::vector<int> frozen = frozen_couts(sp);
-        const int proven = static_cast<int>(frozen.size()), nf = proven / 8 * 8;
-        if (nf < 8 || nf >= sp.cout) continue;
-        f.kfold_pi = frozen_last(sp.cout, frozen, nf);
-        f.kfold_r = r;
-        f.kfold_live = sp.cout - nf;
-        f.kfold_proven = proven;
-    }
-    if (f.kfold_r >= 0) {
-        rw.permute_couts(f.kfold_r - 1, f.kfold_pi);
-        rw.permute_cins(f.kfold_r, f.kfold_pi);
-    }
-    return f;
-}
-
 }  // namespace
 
 int rn_run_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids) { return run_head(h, n, d_probs, d_ids); }
@@ -657,23 +592,11 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     }
     h->stream = h->own_stream;
     RelabelledWeights rw(w);
-    const F32Folds folds = plan_f32_folds(w, dtype, flags, rw);
+    const auto folds = rn_f32m_plan_folds(w, dtype, flags, &rw);      // (float32 handles: the frozen-channel folds, relabelled on rw)
     // (the grad-CAM adjoint keeps its host copies from the caller's weights, in the reference's channel order)
     if ((rc = rn_gradcam_keep(h, w)) != RN_OK) return fail(rc);
     w = &rw.w;
     if ((rc = build_plan(h, w)) != RN_OK) return fail(rc);
-    if (folds.fold_r >= 0) {
-        h->f32_fold_stage = folds.fold_r;
-        h->f32_fold_live = 32;
-        h->node_perm[h->stages[folds.fold_r - 1].node_bn] = folds.fold_pi;
-        h->node_perm[h->stages[folds.fold_r].node_bn2] = folds.fold_pi;
-    }
-    if (folds.kfold_r >= 0) {
-        h->f32_kfold_stage = folds.kfold_r;     // (rn_f32m_prepare takes it back if no kernel variant contracts that channel count)
-        h->f32_kfold_live = folds.kfold_live;
-        h->f32_kfold_proven = folds.kfold_proven;
-        h->node_perm[h->stages[folds.kfold_r - 1].node_bn] = folds.kfold_pi;
-    }
     // uint8 -> float32 table, evaluated in float64 like the reference's NumPy expression
     {
         float lut[256];
@@ -683,10 +606,11 @@ extern "C" int rn_create(const rn_weights* w, int device, int dtype, int max_bat
     if (fused_mode(h) && (rc = rn_fused_prepare(h, w)) != RN_OK) return fail(rc);
     // float32 handles without per-node taps run their conv stages on the matrix cores (rn_stage_f32m.hip)
     // (not the batch-statistics handles: their BN tables do not exist before the stage's input has been reduced)
-    if (!fused_mode(h) && !(h->flags & (RN_FLAG_TAPS | RN_FLAG_BATCH_STATS)) && (rc = rn_f32m_prepare(h, w)) != RN_OK) return fail(rc);
+    if (!fused_mode(h) && !(h->flags & (RN_FLAG_TAPS | RN_FLAG_BATCH_STATS)) && (rc = rn_f32m_prepare(h, w, folds)) != RN_OK)
+        return fail(rc);
     if ((h->flags & RN_FLAG_BATCH_STATS) && (rc = rn_bnstats_prepare(h, w)) != RN_OK) return fail(rc);
     if ((rc = alloc_buffers(h)) != RN_OK) return fail(rc);
-    if (fused_mode(h) && (rc = rn_fused_post_alloc(h)) != RN_OK) return fail(rc);
+    if ((rc = fused_mode(h) ? rn_fused_post_alloc(h) : rn_f32m_post_alloc(h)) != RN_OK) return fail(rc);
     h->events.resize(3 + h->stages.size());
     for (auto& e : h->events)
         if (hipEventCreate(&e) != hipSuccess) {
@@ -1509,20 +1433,6 @@ extern "C" int rn_frozen_info(const rn_handle* h, int info[4]) {
         rn_set_error("rn_frozen_info: bad argument");
         return RN_E_INVALID;
     }
-    info[0] = info[1] = 0;
-    info[2] = -1;
-    info[3] = 4;
-    if (fused_mode(h)) {
-        rn_fused_frozen_info(h, info);
-    } else {
-        if (h->f32_fold_stage >= 0 && rn_f32m_covers(h, h->f32_fold_stage)) {
-            info[2] = h->f32_fold_stage;
-            info[3] = h->f32_fold_live / 16;
-        }
-        if (h->f32_kfold_stage >= 0 && rn_f32m_covers(h, h->f32_kfold_stage)) {
-            info[0] = h->stages[h->f32_kfold_stage].cin - h->f32_kfold_live;
-            info[1] = h->f32_kfold_proven;
-        }
-    }
+    fused_mode(h) ? rn_fused_frozen_info(h, info) : rn_f32m_frozen_info(h, info);
     return RN_OK;
 }

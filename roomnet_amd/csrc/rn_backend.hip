@@ -408,7 +408,7 @@ int rn_backend_launch(rn_handle* h, const i32x4* wfrag6, const float* ptab6, con
     const StagePlan& s6 = h->stages[ns - 4];
     const StagePlan& s7 = h->stages[ns - 3];
     BackendArgs a{};
-    a.in = static_cast<const unsigned short*>(h->nodes[s5.node_bn2 >= 0 ? s5.node_bn2 : s5.node_bn].ptr);
+    a.in = static_cast<const unsigned short*>(h->nodes[rn_stage_out_node(s5)].ptr);
     a.wfrag6 = wfrag6;
     a.ptab6 = ptab6;
     a.cstart6 = cstart6;

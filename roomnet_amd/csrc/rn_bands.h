@@ -11,6 +11,12 @@ struct Bands {
     int rows_per_band, n_bands;
 };
 
+template <class Args> Args with_bands(Args a, const Bands& b) {      // the copy of bound arguments a launch works on
+    a.rows_per_band = b.rows_per_band;
+    a.n_bands = b.n_bands;
+    return a;
+}
+
 // `bands` bands of equal height (at least min_rows rows each) that cover out_side rows
 inline Bands rn_bands_from_count(int out_side, int bands, int min_rows = 1) {
     Bands r;

@@ -103,10 +103,24 @@ void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned shor
 int rn_stage6x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 
 // ---- float32 conv stages on the matrix cores (rn_stage_f32m.hip): the throughput path of RN_DTYPE_F32 handles without RN_FLAG_TAPS
-int rn_f32m_prepare(rn_handle* h, const rn_weights* w);
+// The frozen-channel folds rn_create proposes for a float32 handle, found on the caller's weights and applied to the copy `rw`
+// in front of everything that uploads weights: the stage each applies to (-1: none) and its channel relabelling
+struct F32Folds {
+    int fold_r = -1;                 // the 64 -> 64 residual stage whose second 32-cout tile is all frozen
+    std::vector<int> fold_pi;
+    int kfold_r = -1;                // the stage whose last input channels are frozen
+    std::vector<int> kfold_pi;
+    int kfold_live = 0, kfold_proven = 0;
+};
+F32Folds rn_f32m_plan_folds(const rn_weights* w, int dtype, unsigned flags, RelabelledWeights* rw);
+// plans every stage, keeps what the handle really folds, uploads; registers the folds' relabellings in rn_handle::node_perm
+int rn_f32m_prepare(rn_handle* h, const rn_weights* w, const F32Folds& folds);
+// after the activation buffers exist: every launch argument but the bands
+int rn_f32m_post_alloc(rn_handle* h);
 void rn_f32m_release(rn_handle* h);
 bool rn_f32m_covers(const rn_handle* h, int stage);
-int rn_f32m_launch(rn_handle* h, int stage, const float* in, int n);      // writes the stage's output node
+int rn_f32m_launch(rn_handle* h, int stage, int n);      // reads the output node of stage - 1, writes the stage's
+void rn_f32m_frozen_info(const rn_handle* h, int info[4]);
 
 // ---- the back end in one launch: stage 6 -> 7 -> 8 -> 9 -> head (rn_backend.hip)
 bool rn_backend_supported(const rn_handle* h);

@@ -195,15 +195,8 @@ static void fold16(rn_handle* h, FusedState* fs, const rn_weights* w_in, Relabel
     for (int r = 2; r + 1 < w_in->n_stages; ++r) {
         const rn_conv_stage& s5 = w_in->stages[r];
         const rn_conv_stage& s4 = w_in->stages[r - 1];
-        const rn_conv_stage& s6 = w_in->stages[r + 1];
         const StagePlan& p5 = h->stages[r];
-        if (!(s5.cin == 64 && s5.cout == 64 && s5.pool_k == 4 && s5.pool_s == 2 && s5.skip_stage == r - 1 && s5.gamma2 && s4.cout == 64 &&
-              s4.skip_stage < 0 && s6.cin == 64 && s6.skip_stage < 0 &&
-              rn_stage5x_supported(s5.cin, s5.cout, s5.pool_k, s5.pool_s, true, p5.in_side, p5.skip_side)))
-            continue;
-        bool other_use = false;          // nobody else may pair with the relabelled tensors
-        for (int k = 0; k < w_in->n_stages; ++k) other_use |= (k != r && w_in->stages[k].skip_stage == r - 1) || w_in->stages[k].skip_stage == r;
-        if (other_use) continue;
+        if (!rn_fold_block_at(w_in, r) || !rn_stage5x_supported(s5.cin, s5.cout, s5.pool_k, s5.pool_s, true, p5.in_side, p5.skip_side)) continue;
         std::vector<int> frozen, live;
         const std::vector<float> t5 = stage_table(s5, w_in->bn_epsilon, true);
         for (int c = 0; c < 64; ++c) {
@@ -249,16 +242,12 @@ static void fold16(rn_handle* h, FusedState* fs, const rn_weights* w_in, Relabel
         for (int p = 0; p < 32; ++p) pi[32 + p] = frozen[p];
         if (fs->const_layout)
             for (int p = 0; p < 16; ++p) fs->const_val[0][p] = cst_val[pi[48 + p]];
-        rw->permute_couts(r - 1, pi);
-        rw->permute_couts(r, pi);
-        rw->permute_cins(r, pi);
-        rw->permute_cins(r + 1, pi);
+        rw->permute_block(r, pi);
         fs->relabel_stage = r;
         if (fold_ok) {
             fs->fold5_stage = r;
         }
-        h->node_perm[h->stages[r - 1].node_bn] = pi;
-        h->node_perm[h->stages[r].node_bn2] = pi;
+        rn_fold_block_register(h, r, pi);
         return;
     }
 }
@@ -722,7 +711,7 @@ __global__ void fill_channels16_kernel(unsigned short* base, int64_t npix, int c
 int rn_fused_post_alloc(rn_handle* h) {
     FusedState* fs = static_cast<FusedState*>(h->fused);
     if (!fs) return RN_OK;
-    auto out_of = [&](const StagePlan& s) { return static_cast<unsigned short*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr); };
+    auto out_of = [&](const StagePlan& s) { return static_cast<unsigned short*>(h->nodes[rn_stage_out_node(s)].ptr); };
     fs->s0_args.out = out_of(h->stages[0]);
     for (size_t i = 1; i < h->stages.size(); ++i) {
         const StagePlan& s = h->stages[i];
@@ -776,12 +765,6 @@ int rn_fused_launch_rep(const rn_handle* h, int stage) {
 // ---- the launch steps of a forward pass: each copies its bound arguments with what depends on the call -- the bands of this batch size
 // from the band picker (rn_bands.h), the clock region, the image pointer -- and launches.  rn_fused_forward decides which one runs.
 namespace {
-
-template <class Args> Args with_bands(Args a, const Bands& b) {      // the copy of bound arguments a launch works on
-    a.rows_per_band = b.rows_per_band;
-    a.n_bands = b.n_bands;
-    return a;
-}
 
 int launch_stage0(const rn_handle* h, const FusedState* fs, const uint8_t* d_bgr, int n) {
     Stage0Args a0 = with_bands(fs->s0_args, rn_bands_stage0(n, fs->s0_args.So, fs->s0_args.n_colblocks));

@@ -94,6 +94,9 @@ struct DensePlan {
     int node_mm = -1, node_relu = -1, node_bn = -1;
 };
 
+// the node a stage's output lives in
+inline int rn_stage_out_node(const StagePlan& s) { return s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn; }
+
 struct NodeBuf {
     rn_node_info info;
     void* ptr = nullptr;         // device buffer [max_batch, h, w, c] (null: not materialised)
@@ -155,16 +158,7 @@ struct rn_handle {
     void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch and the batch table (rn_jpeg.hip; allocated by the first call)
     void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the double-buffered batch tables (rn_jpeg_enc.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
-    // float32 handles: frozen first-BN channels of the 64 -> 64 residual stage folded (rn_create): the stage's index (or -1) and the
-    // couts whose convolution still runs
-    int f32_fold_stage = -1;
-    int f32_fold_live = 0;
-    // ... and frozen INPUT channels of a stage (its producer's BN freezes them; relabelled to the end): the stage's index (or -1),
-    // the input channels it still contracts (a multiple of 8), how many channels were proven constant
-    int f32_kfold_stage = -1;
-    int f32_kfold_live = 0;
-    int f32_kfold_proven = 0;
-    // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_create) and 16-bit (rn_fused_prepare) alike:
+    // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
     // node id -> position p of the stored tensor holds the reference's channel perm[p] (rn_tap puts them back in order)
     std::map<int, std::vector<int>> node_perm;
     // profiling
@@ -325,7 +319,12 @@ struct RelabelledWeights {
     RelabelledWeights& operator=(const RelabelledWeights&) = delete;
     void permute_couts(int stage, const std::vector<int>& pi);     // its kernel's couts, its BN (and the second BN of a residual stage)
     void permute_cins(int stage, const std::vector<int>& pi);      // its kernel's cins
+    void permute_block(int r, const std::vector<int>& pi);         // residual stage r pairs its channels with stage r - 1's: couts of r - 1, r; cins of r, r + 1
 };
+// Stage r is the 64 -> 64 residual stage (pool 4/2) of a depth-2 block between a 64-cout stage and a 64-cin stage without skips, and
+// nobody else pairs with the block's two tensors: the block both frozen-channel folds relabel (each adds a condition of its own)
+bool rn_fold_block_at(const rn_weights* w, int r);
+void rn_fold_block_register(rn_handle* h, int r, const std::vector<int>& pi);      // its two tensors' entries in rn_handle::node_perm
 
 // ---- the 16-bit storage types on the host: round to nearest even, and back
 inline unsigned short f32_to_bf16(float f) {

@@ -569,20 +569,6 @@ __global__ __launch_bounds__(256) void f32_frozen_residual_kernel(const float* _
     *reinterpret_cast<f32x4*>(out + p * cout + c0) = y;
 }
 
-struct F32mStage {
-    bool on = false;
-    bool m16 = false;             // stage_f32m16_kernel (16 couts): ks / lpt16 below
-    int ks16 = 1;
-    f32x4* wfrag = nullptr;
-    float* cinit = nullptr;       // per cout: the frozen input channels' contribution (variants with live_cin < cin)
-    int variant = -1, npt = 1, n_colblocks = 1, n_ctg = 1, nsl = 4, ringcols = 34;
-    size_t lds = 0;
-};
-
-struct F32mState {
-    std::vector<F32mStage> st;
-};
-
 using F32LaunchFn = int (*)(const F32StageArgs&, dim3, dim3, size_t, hipStream_t);
 
 template <int CIN, int COUT, int PK, int PS, bool RES, int NSL, int LPT, int KS, int KQL = CIN / 8>
@@ -632,202 +618,336 @@ const F32Variant16 kF32Variants16[] = {
     {32, 1, 2, 1, 16, 4, 4, launch_f32m16<32, 1, 2, 1, 16>},
 };
 
+// ---- the plan of one stage: a pure function of its shape (exported as rn_f32m_plan)
+int find_variant(int cin, int cout, int pk, int ps, bool res, int live_cin) {
+    for (const F32Variant& k : kF32Variants)
+        if (k.cin == cin && k.cout == cout && k.pk == pk && (pk == 0 || k.ps == ps) && k.res == (res ? 1 : 0) && k.live_cin == live_cin)
+            return static_cast<int>(&k - kF32Variants);
+    return -1;
+}
+
+int find_variant16(int cin, int ps, int frozen) {
+    for (const F32Variant16& k : kF32Variants16)
+        if (k.cin == cin && k.ps == ps && k.frozen == frozen) return static_cast<int>(&k - kF32Variants16);
+    return -1;
+}
+
+// stage_f32m_kernel: pixel tiles (= waves) per workgroup, as many as fit the LDS next to the weights, at most 8.  false: not coverable
+bool geometry(const F32Variant& k, int cin, int cout, int pk, int ps, int in_side, int out_side, rn_f32m_stage_plan* p) {
+    const int tiles = (out_side + tile_nout(pk, ps) - 1) / tile_nout(pk, ps);
+    for (p->npt = std::min(tiles, 8); p->npt >= 1; --p->npt) {
+        p->ringcols = std::min((p->npt - 1) * tile_stride(pk, ps) + 34, in_side);
+        p->lds = 9 * (cin / 8) * 1024 + 1024 + k.nsl * p->ringcols * cin * 4 + (k.ks == 2 ? p->npt * 4096 : 0);
+        const bool fits = p->lds <= 160 * 1024 && p->ringcols * (cin / 4) <= k.lpt * 64 * p->npt * k.ks;
+        if (fits && (p->npt * k.ks <= 8 || p->npt == 1)) break;
+    }
+    if (p->npt < 1) return false;
+    p->n_colblocks = (tiles + p->npt - 1) / p->npt;
+    p->n_ctg = (cout + 31) / 32;
+    p->threads = 64 * p->npt * k.ks;
+    return true;
+}
+
+// stage_f32m16_kernel: even column blocks of at most max_tiles tiles
+bool geometry16(const F32Variant16& k, int cin, int in_side, int out_side, rn_f32m_stage_plan* p) {
+    const int tstride = k.ps == 2 ? 14 : 13, nout_t = k.ps == 2 ? 7 : 13;
+    const int tiles = (out_side + nout_t - 1) / nout_t;
+    p->npt = std::min(tiles, k.max_tiles);
+    p->npt = std::min(p->npt, (tiles + (tiles + p->npt - 1) / p->npt - 1) / ((tiles + p->npt - 1) / p->npt));
+    for (; p->npt >= 1; --p->npt) {
+        p->ringcols = std::min((p->npt - 1) * tstride + 18, in_side);
+        p->lds = 9 * (cin / 16) * 1024 + 256 + k.nsl * p->ringcols * cin * 4 + (k.ks == 3 ? 2 * p->npt * 1024 : 0);
+        if (p->lds <= 160 * 1024 && p->ringcols * (cin / 4) <= k.lpt * 64 * p->npt * k.ks) break;
+    }
+    if (p->npt < 1) return false;
+    p->n_colblocks = (tiles + p->npt - 1) / p->npt;
+    p->n_ctg = 1;
+    p->threads = 64 * p->npt * k.ks;
+    return true;
+}
+
+rn_f32m_stage_plan stage_off(int cin) { return rn_f32m_stage_plan{RN_F32M_OFF, -1, cin, 0, 1, 0, 0, 1, 1, 0}; }
+
+// live_cin < cin: the stage's frozen input channels are relabelled to the end -- the variant that contracts the others only, if there
+// is one (otherwise every channel is contracted: the relabelling alone changes nothing).  frozen > 0: couts that are not convolved -- of
+// a residual stage whole 32-cout tiles (f32_frozen_residual_kernel forms their outputs); of any other stage constants the 16-cout
+// kernel writes beside its 16 live ones (a producer without such a variant convolves every channel like any other stage)
+rn_f32m_stage_plan plan_stage(int cin, int cout, int pk, int ps, bool res, int in_side, int out_side, int live_cin, int frozen) {
+    rn_f32m_stage_plan p = stage_off(cin);
+    const bool producer16 = frozen > 0 && !res;
+    int v = producer16 ? -1 : find_variant(cin, cout, pk, ps, res, live_cin);
+    if (v >= 0) p.live_cin = live_cin;
+    if (v < 0 && !producer16 && live_cin != cin) v = find_variant(cin, cout, pk, ps, res, cin);
+    if (v < 0 && (producer16 || (cout == 16 && pk == 4 && ps == 2 && !res))) {
+        const int v16 = find_variant16(cin, ps, producer16 ? frozen : 0);
+        if (v16 >= 0 && geometry16(kF32Variants16[v16], cin, in_side, out_side, &p)) {
+            p.kind = RN_F32M_16;
+            p.variant = v16;
+            p.frozen_couts = producer16 ? frozen : 0;
+            return p;
+        }
+        if (!producer16) return stage_off(cin);
+        v = find_variant(cin, cout, pk, ps, false, cin);
+    }
+    if (v < 0 || !geometry(kF32Variants[v], cin, cout, pk, ps, in_side, out_side, &p)) return stage_off(cin);
+    p.kind = RN_F32M_WIDE;
+    p.variant = v;
+    if (res && frozen > 0 && frozen < cout && (cout - frozen) % 32 == 0) {
+        p.frozen_couts = frozen;
+        p.n_ctg = (cout - frozen) / 32;
+    }
+    return p;
+}
+
+// ---- the plan of a handle from the folds rn_f32m_plan_folds proposed (and relabelled the weights for).  The stage with frozen input
+// channels is planned first: only if it is covered AND contracts fewer channels may its producer leave the frozen ones out (16 live
+// couts on the 16 x 16 x 4 tiles, the others written as constants)
+std::vector<rn_f32m_stage_plan> plan_stages(const std::vector<StagePlan>& stages, const F32Folds& folds) {
+    std::vector<rn_f32m_stage_plan> plan(stages.size());
+    const auto plan_of = [&](int si, int live_cin, int frozen) {
+        const StagePlan& s = stages[si];
+        if (s.skip_stage >= 0 && stages[s.skip_stage].node_bn2 >= 0) return stage_off(s.cin);      // skip source = a first BN output
+        return plan_stage(s.cin, s.cout, s.pool_k, s.pool_s, s.skip_stage >= 0, s.in_side, s.out_side, live_cin, frozen);
+    };
+    const int kf = folds.kfold_r;
+    if (kf >= 0) plan[kf] = plan_of(kf, folds.kfold_live, 0);
+    const bool kfold = kf >= 0 && plan[kf].kind != RN_F32M_OFF && plan[kf].live_cin < stages[kf].cin;
+    for (int si = 0; si < static_cast<int>(stages.size()); ++si) {
+        const StagePlan& s = stages[si];
+        if (si == kf) continue;
+        const bool producer16 = kfold && si + 1 == kf && folds.kfold_live == 16 && s.cout == 32 && s.pool_k == 4 && s.pool_s == 1 && s.skip_stage < 0;
+        plan[si] = plan_of(si, s.cin, producer16 ? 16 : si == folds.fold_r ? s.cout - 32 : 0);
+    }
+    return plan;
+}
+
+struct F32mStage {
+    rn_f32m_stage_plan plan{};
+    f32x4* wfrag = nullptr;
+    float* cinit = nullptr;       // per cout: the frozen input channels' contribution (plan.live_cin < cin)
+    F32StageArgs args{};          // everything but the bands (rn_f32m_post_alloc)
+};
+
+struct F32mState {
+    std::vector<F32mStage> st;
+    // what the handle really folds (-1: nothing): the residual stage's frozen cout tiles, a stage's frozen input channels
+    int fold_stage = -1, kfold_stage = -1, kfold_proven = 0;
+};
+
+// frag[tap * CIN / 8 + q][cout tile][lane][i] = W[tap][channel 8 q + 4 (lane / 32) + i][cout 32 tile + lane % 32]; w = HWIO = [tap][cin][cout]
+std::vector<float> pack(const float* w, int cin, int cout) {
+    const int kq = cin / 8, ct_n = (cout + 31) / 32;
+    std::vector<float> frag(static_cast<size_t>(9 * kq) * ct_n * 64 * 4, 0.f);
+    for (int tap = 0; tap < 9; ++tap)
+        for (int q = 0; q < kq; ++q)
+            for (int t = 0; t < ct_n; ++t)
+                for (int l = 0; l < 64; ++l)
+                    for (int i = 0; i < 4; ++i) {
+                        const int c = 8 * q + 4 * (l >> 5) + i, co = 32 * t + (l & 31);
+                        if (co < cout) frag[((static_cast<size_t>(tap * kq + q) * ct_n + t) * 64 + l) * 4 + i] = w[(static_cast<size_t>(tap) * cin + c) * cout + co];
+                    }
+    return frag;
+}
+
+// 16-cout stages: frag[tap * CIN / 16 + q][lane][i] = W[tap][channel 16 q + 4 (lane / 16) + i][cout lane % 16] (the first 16 couts)
+std::vector<float> pack16(const float* w, int cin, int cout) {
+    const int kg = cin / 16;
+    std::vector<float> frag(static_cast<size_t>(9 * kg) * 64 * 4, 0.f);
+    for (int tap = 0; tap < 9; ++tap)
+        for (int q = 0; q < kg; ++q)
+            for (int l = 0; l < 64; ++l)
+                for (int i = 0; i < 4; ++i)
+                    frag[((static_cast<size_t>(tap) * kg + q) * 64 + l) * 4 + i] = w[(static_cast<size_t>(tap) * cin + 16 * q + 4 * (l >> 4) + i) * cout + (l & 15)];
+    return frag;
+}
+
+// the producer writes beta[c] for its frozen channel c at every pixel: per cout, the sum over the nine taps, in double
+std::vector<float> cinit(const float* w, const float* beta, int cin, int cout, int live_cin) {
+    std::vector<float> ci(static_cast<size_t>((cout + 31) / 32) * 32, 0.f);
+    for (int co = 0; co < cout; ++co) {
+        double acc = 0.0;
+        for (int tap = 0; tap < 9; ++tap)
+            for (int c = live_cin; c < cin; ++c) acc += static_cast<double>(w[(static_cast<size_t>(tap) * cin + c) * cout + co]) * static_cast<double>(beta[c]);
+        ci[co] = static_cast<float>(acc);
+    }
+    return ci;
+}
+
+// relabelling of `n` channels that puts the first `keep` of `frozen` behind all the others, those in ascending order
+std::vector<int> frozen_last(int n, std::vector<int> frozen, size_t keep) {
+    frozen.resize(keep);
+    std::vector<int> pi;
+    for (int c = 0; c < n; ++c)
+        if (std::find(frozen.begin(), frozen.end(), c) == frozen.end()) pi.push_back(c);
+    pi.insert(pi.end(), frozen.begin(), frozen.end());
+    return pi;
+}
+
+// The stage kernels form y1 = ((x * 1/16 - mean) * inv + beta) un-contracted: where |inv| * max(|mean|, |6 - mean|) < 2^-25 |beta| the
+// product vanishes against beta and y1 IS beta for every input (the reference's float32 computes the same expression)
+std::vector<int> frozen_couts(const rn_conv_stage& st, float eps) {
+    std::vector<int> frozen;
+    for (int c = 0; c < st.cout; ++c) {
+        const float inv = rn_bn_inv(st.variance[c], st.gamma[c], eps);
+        const double reach = std::max(std::fabs(static_cast<double>(st.mean[c])), std::fabs(6.0 - static_cast<double>(st.mean[c])));
+        if (std::fabs(static_cast<double>(inv)) * reach * (1.0 + 1e-6) < std::fabs(static_cast<double>(st.beta[c])) * 2.98023223876953125e-8)
+            frozen.push_back(c);
+    }
+    return frozen;
+}
+
 }  // namespace
+
+// ---- frozen first-BN channels of a 64 -> 64 residual stage (stage 5).  With >= 32 of them the block's channels are relabelled on a
+// copy of the weights (rn_fold_block_at) so that the stage's second 32-cout tile is all frozen: it is not convolved (rn_f32m_launch
+// runs the residual for it alone).  rn_tap un-relabels.
+F32Folds rn_f32m_plan_folds(const rn_weights* w, int dtype, unsigned flags, RelabelledWeights* rw) {
+    F32Folds f;
+    if (dtype != RN_DTYPE_F32 || (flags & (RN_FLAG_TAPS | RN_FLAG_COMPUTE_FROZEN | RN_FLAG_BATCH_STATS))) return f;
+    for (int r = 2; r + 1 < w->n_stages && f.fold_r < 0; ++r) {
+        const rn_conv_stage& s5 = w->stages[r];
+        if (!rn_fold_block_at(w, r) || !s5.gamma || !s5.beta || !s5.mean || !s5.variance) continue;
+        const std::vector<int> frozen = frozen_couts(s5, w->bn_epsilon);
+        if (frozen.size() < 32) continue;
+        f.fold_pi = frozen_last(64, frozen, 32);
+        f.fold_r = r;
+    }
+    if (f.fold_r >= 0) rw->permute_block(f.fold_r, f.fold_pi);
+    // ---- ... and frozen INPUT channels: a pooled stage p without a second BN whose output only feeds the convolution of stage
+    // p + 1 (nobody's residual) and whose BN freezes >= 8 channels (same inequality).  Its couts / the consumer's cins are
+    // relabelled so that the last 8 k channels are all frozen; the consumer contracts the others and starts its accumulators
+    // from the frozen ones' contribution (plan_stages: a variant of the stage kernel must exist for that channel count)
+    for (int r = 1; r < w->n_stages && f.kfold_r < 0; ++r) {
+        const int p = r - 1;
+        const rn_conv_stage& sp = rw->stages[p];
+        const rn_conv_stage& sc = rw->stages[r];
+        if (f.fold_r >= 0 && (p == f.fold_r - 1 || p == f.fold_r)) continue;          // (those channels are relabelled already)
+        if (sp.skip_stage >= 0 || sp.gamma2 || sp.pool_k != 4 || !sp.gamma || !sp.beta || !sp.mean || !sp.variance) continue;
+        if (sc.cin != sp.cout || sp.cout % 8 != 0 || sp.cout > 64) continue;
+        bool other_use = false;
+        for (int k = 0; k < w->n_stages; ++k) other_use |= w->stages[k].skip_stage == p;
+        if (other_use) continue;
+        const std::vector<int> frozen = frozen_couts(sp, w->bn_epsilon);
+        const int proven = static_cast<int>(frozen.size()), nf = proven / 8 * 8;
+        if (nf < 8 || nf >= sp.cout) continue;
+        f.kfold_pi = frozen_last(sp.cout, frozen, nf);
+        f.kfold_r = r;
+        f.kfold_live = sp.cout - nf;
+        f.kfold_proven = proven;
+    }
+    if (f.kfold_r >= 0) {
+        rw->permute_couts(f.kfold_r - 1, f.kfold_pi);
+        rw->permute_cins(f.kfold_r, f.kfold_pi);
+    }
+    return f;
+}
 
 void rn_f32m_release(rn_handle* h) {
     delete static_cast<F32mState*>(h->f32m);
     h->f32m = nullptr;
 }
 
-// Pack the weights of every stage the kernel covers: frag[tap * CIN / 8 + q][cout tile][lane][i] =
-// W[tap][channel 8 q + 4 (lane / 32) + i][cout 32 tile + lane % 32]
-int rn_f32m_prepare(rn_handle* h, const rn_weights* w) {
+int rn_f32m_prepare(rn_handle* h, const rn_weights* w, const F32Folds& folds) {
     auto* fs = new F32mState();
     fs->st.resize(h->stages.size());
     h->f32m = fs;
-    auto prepare_stage = [&](size_t si) -> int {
+    // (a fold that is not taken keeps its relabelling: the weights are relabelled already, and rn_tap undoes it)
+    if (folds.fold_r >= 0) rn_fold_block_register(h, folds.fold_r, folds.fold_pi);
+    if (folds.kfold_r >= 0) h->node_perm[h->stages[folds.kfold_r - 1].node_bn] = folds.kfold_pi;
+    const std::vector<rn_f32m_stage_plan> plan = plan_stages(h->stages, folds);
+    const int fr = folds.fold_r, kf = folds.kfold_r;
+    if (fr >= 0 && plan[fr].kind != RN_F32M_OFF && plan[fr].frozen_couts > 0) fs->fold_stage = fr;
+    if (kf >= 0 && plan[kf].kind != RN_F32M_OFF && plan[kf].live_cin < h->stages[kf].cin) fs->kfold_stage = kf;
+    fs->kfold_proven = folds.kfold_proven;
+    for (size_t si = 0; si < plan.size(); ++si) {
         const StagePlan& s = h->stages[si];
         F32mStage& f = fs->st[si];
-        // the producer of a stage that does not contract its frozen input channels need not convolve them either: 16 live couts on
-        // the 16 x 16 x 4 tiles, the frozen ones written as constants (only once the consumer's variant is in place)
-        const bool live16 = static_cast<int>(si) + 1 == h->f32_kfold_stage && fs->st[si + 1].on && fs->st[si + 1].cinit && h->f32_kfold_live == 16 &&
-                            s.cout == 32 && s.pool_k == 4 && s.pool_s == 1 && s.skip_stage < 0;
-        // (rn_create relabelled a stage's frozen input channels to the end: the variant that contracts the others only, if there is one)
-        int want_live = static_cast<int>(si) == h->f32_kfold_stage ? h->f32_kfold_live : s.cin;
-        for (int pass = 0; pass < 2 && f.variant < 0 && !live16; ++pass) {
-            for (size_t v = 0; v < sizeof(kF32Variants) / sizeof(kF32Variants[0]); ++v) {
-                const F32Variant& k = kF32Variants[v];
-                if (k.cin == s.cin && k.cout == s.cout && k.pk == s.pool_k && (s.pool_k == 0 || k.ps == s.pool_s) &&
-                    k.res == (s.skip_stage >= 0 ? 1 : 0) && k.live_cin == want_live)
-                    f.variant = static_cast<int>(v);
-            }
-            if (f.variant < 0 && want_live != s.cin) {
-                h->f32_kfold_stage = -1;          // no such variant: every channel is contracted (the relabelling alone changes nothing)
-                want_live = s.cin;
-            }
-        }
-        if (f.variant < 0 && (live16 || (s.cout == 16 && s.pool_k == 4 && s.pool_s == 2 && s.skip_stage < 0))) {
-            // 16-cout stages: stage_f32m16_kernel; frag[tap * CIN / 16 + q][lane][i] = W[tap][channel 16 q + 4 (lane / 16) + i][cout lane % 16]
-            const int frozen = live16 ? 16 : 0;
-            for (size_t v = 0; v < sizeof(kF32Variants16) / sizeof(kF32Variants16[0]); ++v) {
-                const F32Variant16& k = kF32Variants16[v];
-                if (k.cin != s.cin || k.ps != s.pool_s || k.frozen != frozen) continue;
-                const int tstride = k.ps == 2 ? 14 : 13, nout_t = k.ps == 2 ? 7 : 13;
-                const int kg = s.cin / 16, tiles = (s.out_side + nout_t - 1) / nout_t;
-                int npt = std::min(tiles, k.max_tiles);
-                npt = std::min(npt, (tiles + (tiles + npt - 1) / npt - 1) / ((tiles + npt - 1) / npt));      // even column blocks
-                size_t lds = 0;
-                int ringcols = 0;
-                for (; npt >= 1; --npt) {
-                    ringcols = std::min((npt - 1) * tstride + 18, s.in_side);
-                    lds = static_cast<size_t>(9 * kg) * 1024 + 256 + static_cast<size_t>(k.nsl) * ringcols * s.cin * 4 + (k.ks == 3 ? 2 * npt * 1024 : 0);
-                    if (lds <= 160 * 1024 && ringcols * (s.cin / 4) <= k.lpt * 64 * npt * k.ks) break;
-                }
-                if (npt < 1) continue;
-                std::vector<float> frag(static_cast<size_t>(9 * kg) * 64 * 4, 0.f);
-                const float* wsrc = w->stages[si].kernel;      // HWIO = [tap][cin][cout]: the first 16 couts
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int q = 0; q < kg; ++q)
-                        for (int l = 0; l < 64; ++l)
-                            for (int i = 0; i < 4; ++i)
-                                frag[((static_cast<size_t>(tap) * kg + q) * 64 + l) * 4 + i] =
-                                    wsrc[(static_cast<size_t>(tap) * s.cin + 16 * q + 4 * (l >> 4) + i) * s.cout + (l & 15)];
-                const int rc = upload(h, reinterpret_cast<const f32x4*>(frag.data()), frag.size() / 4, &f.wfrag);
-                if (rc != RN_OK) return rc;
-                f.m16 = true;
-                f.variant = static_cast<int>(v);
-                f.ks16 = k.ks;
-                f.npt = npt;
-                f.ringcols = ringcols;
-                f.lds = lds;
-                f.n_colblocks = (tiles + npt - 1) / npt;
-                f.n_ctg = 1;
-                f.on = true;
-                break;
-            }
-            if (f.on || !live16) return RN_OK;
-            // (no 16-cout variant for this producer: it convolves every channel like any other stage)
-            for (size_t v = 0; v < sizeof(kF32Variants) / sizeof(kF32Variants[0]); ++v) {
-                const F32Variant& k = kF32Variants[v];
-                if (k.cin == s.cin && k.cout == s.cout && k.pk == s.pool_k && k.ps == s.pool_s && k.res == 0 && k.live_cin == s.cin) f.variant = static_cast<int>(v);
-            }
-        }
-        if (f.variant < 0) return RN_OK;
-        if (s.skip_stage >= 0 && h->stages[s.skip_stage].node_bn2 >= 0) return RN_OK;      // skip source = a first BN output
-        const int kq = s.cin / 8, kc = 9 * kq, ct_n = (s.cout + 31) / 32;
-        f.nsl = kF32Variants[f.variant].nsl;
-        // pixel tiles (= waves) per workgroup: as many as fit the LDS next to the weights, at most 8
-        const int tstride = tile_stride(s.pool_k, s.pool_s), nout_t = tile_nout(s.pool_k, s.pool_s);
-        const int tiles = (s.out_side + nout_t - 1) / nout_t;
-        f.npt = std::min(tiles, 8);
-        for (;;) {
-            f.ringcols = std::min((f.npt - 1) * tstride + 34, s.in_side);
-            const int ks = kF32Variants[f.variant].ks;
-            f.lds = static_cast<size_t>(kc) * 1024 + 1024 + static_cast<size_t>(f.nsl) * f.ringcols * s.cin * 4 + (ks == 2 ? f.npt * 4096 : 0);
-            const int chunks = f.ringcols * (s.cin / 4);
-            if ((f.lds <= 160 * 1024 && chunks <= kF32Variants[f.variant].lpt * 64 * f.npt * ks && f.npt * ks <= 8) || f.npt == 1) break;
-            --f.npt;
-        }
-        if (f.lds > 160 * 1024 || f.ringcols * (s.cin / 4) > kF32Variants[f.variant].lpt * 64 * f.npt * kF32Variants[f.variant].ks)
-            return RN_OK;      // not coverable
-        f.n_colblocks = (tiles + f.npt - 1) / f.npt;
-        f.n_ctg = ct_n;
-        std::vector<float> frag(static_cast<size_t>(kc) * ct_n * 64 * 4, 0.f);
-        const float* wsrc = w->stages[si].kernel;      // HWIO = [tap][cin][cout]
-        for (int tap = 0; tap < 9; ++tap)
-            for (int q = 0; q < kq; ++q)
-                for (int t = 0; t < ct_n; ++t)
-                    for (int l = 0; l < 64; ++l)
-                        for (int i = 0; i < 4; ++i) {
-                            const int c = 8 * q + 4 * (l >> 5) + i, co = 32 * t + (l & 31);
-                            if (co < s.cout)
-                                frag[((static_cast<size_t>(tap * kq + q) * ct_n + t) * 64 + l) * 4 + i] =
-                                    wsrc[(static_cast<size_t>(tap) * s.cin + c) * s.cout + co];
-                        }
-        int rc = upload(h, reinterpret_cast<const f32x4*>(frag.data()), frag.size() / 4, &f.wfrag);
-        if (rc != RN_OK) return rc;
-        if (want_live < s.cin) {
-            // the producer writes beta[c] for its frozen channel c at every pixel: sum over the nine taps, in double
-            const float* beta = w->stages[si - 1].beta;
-            std::vector<float> ci(static_cast<size_t>(ct_n) * 32, 0.f);
-            for (int co = 0; co < s.cout; ++co) {
-                double acc = 0.0;
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int c = want_live; c < s.cin; ++c)
-                        acc += static_cast<double>(wsrc[(static_cast<size_t>(tap) * s.cin + c) * s.cout + co]) * static_cast<double>(beta[c]);
-                ci[co] = static_cast<float>(acc);
-            }
-            if ((rc = upload(h, ci.data(), ci.size(), &f.cinit)) != RN_OK) return rc;
-        }
-        f.on = true;
-        return RN_OK;
-    };
-    // the stage with frozen input channels first: whether its producer may leave them out depends on it
-    const int kf = h->f32_kfold_stage;
-    if (kf >= 0) {
-        const int rc = prepare_stage(static_cast<size_t>(kf));
-        if (rc != RN_OK) return rc;
-        if (!fs->st[kf].cinit) h->f32_kfold_stage = -1;      // (the stage is not covered, or has no variant for that channel count)
+        f.plan = plan[si];
+        if (f.plan.kind == RN_F32M_OFF) continue;
+        const float* wsrc = w->stages[si].kernel;
+        const std::vector<float> frag = f.plan.kind == RN_F32M_16 ? pack16(wsrc, s.cin, s.cout) : pack(wsrc, s.cin, s.cout);
+        if (int rc = upload(h, reinterpret_cast<const f32x4*>(frag.data()), frag.size() / 4, &f.wfrag)) return rc;
+        if (f.plan.live_cin == s.cin) continue;
+        const std::vector<float> ci = cinit(wsrc, w->stages[si - 1].beta, s.cin, s.cout, f.plan.live_cin);
+        if (int rc = upload(h, ci.data(), ci.size(), &f.cinit)) return rc;
     }
-    for (size_t si = 0; si < h->stages.size(); ++si) {
-        if (static_cast<int>(si) == kf) continue;
-        const int rc = prepare_stage(si);
-        if (rc != RN_OK) return rc;
+    return RN_OK;
+}
+
+int rn_f32m_post_alloc(rn_handle* h) {
+    F32mState* fs = static_cast<F32mState*>(h->f32m);
+    for (size_t si = 1; fs && si < fs->st.size(); ++si) {
+        const StagePlan& s = h->stages[si];
+        F32mStage& f = fs->st[si];
+        if (f.plan.kind == RN_F32M_OFF) continue;
+        F32StageArgs& a = f.args;
+        a.in = static_cast<const float*>(h->nodes[rn_stage_out_node(h->stages[si - 1])].ptr);
+        a.out = static_cast<float*>(h->nodes[rn_stage_out_node(s)].ptr);
+        a.wfrag = f.wfrag;
+        a.cinit = f.cinit;
+        a.bn_mean = s.bn.mean;
+        a.bn_inv = s.bn.inv;
+        a.bn_beta = s.bn.beta;
+        if (s.skip_stage >= 0) {
+            a.skip = static_cast<const float*>(h->nodes[h->stages[s.skip_stage].node_bn].ptr);
+            a.bn2_mean = s.bn2.mean;
+            a.bn2_inv = s.bn2.inv;
+            a.bn2_beta = s.bn2.beta;
+            a.rlo = s.rt.lo;
+            a.rhi = s.rt.hi;
+            a.rlerp = s.rt.lerp;
+            a.Ss = s.skip_side;
+        }
+        a.H = a.W = s.in_side;
+        a.Ho = a.Wo = s.out_side;
+        a.npt = f.plan.npt;
+        a.ringcols = f.plan.ringcols;
+        a.n_colblocks = f.plan.n_colblocks;
+        a.n_ctg = f.plan.n_ctg;      // (without the frozen cout tiles of the residual fold)
     }
     return RN_OK;
 }
 
 bool rn_f32m_covers(const rn_handle* h, int stage) {
     const F32mState* fs = static_cast<const F32mState*>(h->f32m);
-    return fs && stage >= 0 && stage < static_cast<int>(fs->st.size()) && fs->st[stage].on;
+    return fs && stage >= 0 && stage < static_cast<int>(fs->st.size()) && fs->st[stage].plan.kind != RN_F32M_OFF;
 }
 
-int rn_f32m_launch(rn_handle* h, int stage, const float* in, int n) {
+void rn_f32m_frozen_info(const rn_handle* h, int info[4]) {
     const F32mState* fs = static_cast<const F32mState*>(h->f32m);
-    const F32mStage& f = fs->st[stage];
+    const int fr = fs ? fs->fold_stage : -1, kf = fs ? fs->kfold_stage : -1;
+    info[0] = kf >= 0 ? h->stages[kf].cin - fs->st[kf].plan.live_cin : 0;
+    info[1] = kf >= 0 ? fs->kfold_proven : 0;
+    info[2] = fr;
+    info[3] = fr >= 0 ? (h->stages[fr].cout - fs->st[fr].plan.frozen_couts) / 16 : 4;
+}
+
+int rn_f32m_launch(rn_handle* h, int stage, int n) {
+    const F32mStage& f = static_cast<const F32mState*>(h->f32m)->st[stage];
     const StagePlan& s = h->stages[stage];
-    F32StageArgs a{};
-    a.in = in;
-    a.out = static_cast<float*>(h->nodes[s.node_bn2 >= 0 ? s.node_bn2 : s.node_bn].ptr);
-    a.wfrag = f.wfrag;
-    a.cinit = f.cinit;
-    a.bn_mean = s.bn.mean;
-    a.bn_inv = s.bn.inv;
-    a.bn_beta = s.bn.beta;
-    if (s.skip_stage >= 0) {
-        a.skip = static_cast<const float*>(h->nodes[h->stages[s.skip_stage].node_bn].ptr);
-        a.bn2_mean = s.bn2.mean;
-        a.bn2_inv = s.bn2.inv;
-        a.bn2_beta = s.bn2.beta;
-        a.rlo = s.rt.lo;
-        a.rhi = s.rt.hi;
-        a.rlerp = s.rt.lerp;
-        a.Ss = s.skip_side;
+    const F32StageArgs a = with_bands(f.args, rn_bands_f32m(n, h->n_cu, s.out_side, f.plan.n_colblocks * f.plan.n_ctg, s.pool_k, s.pool_s));
+    const F32LaunchFn fn = f.plan.kind == RN_F32M_16 ? kF32Variants16[f.plan.variant].fn : kF32Variants[f.plan.variant].fn;
+    const int rc = fn(a, dim3(a.n_bands * a.n_colblocks * a.n_ctg, n), dim3(f.plan.threads), f.plan.lds, h->stream);
+    if (rc != RN_OK || f.plan.frozen_couts == 0 || f.plan.kind != RN_F32M_WIDE) return rc;
+    // the frozen cout tiles of the residual fold (y1 = beta for their channels, relabelled to the end): the residual alone
+    const int c_begin = s.cout - f.plan.frozen_couts;
+    const int64_t n_pix = static_cast<int64_t>(n) * s.out_side * s.out_side;
+    const int64_t threads = n_pix * (f.plan.frozen_couts / 4);
+    hipLaunchKernelGGL(f32_frozen_residual_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, h->stream, a.skip, a.out, a.bn_beta,
+                       a.bn2_mean, a.bn2_inv, a.bn2_beta, a.rlo, a.rhi, a.rlerp, n_pix, s.out_side, s.out_side, s.skip_side, s.cout, c_begin, f.plan.frozen_couts);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
+// the planner of one stage, exported for tests
+extern "C" int rn_f32m_plan(int cin, int cout, int pool_k, int pool_s, int residual, int in_side, int out_side, int live_cin, int frozen_couts,
+                            rn_f32m_stage_plan* plan) {
+    if (!plan || cin < 8 || cin % 8 != 0 || cout < 8 || cout % 8 != 0 || pool_k < 0 || pool_s < 1 || in_side < 3 || out_side < 1 || live_cin < 1 ||
+        live_cin > cin || frozen_couts < 0 || frozen_couts >= cout) {
+        rn_set_error("rn_f32m_plan: bad argument (%d -> %d, pool %d/%d, sides %d -> %d, live_cin %d, frozen_couts %d)", cin, cout, pool_k, pool_s, in_side,
+                     out_side, live_cin, frozen_couts);
+        return RN_E_INVALID;
     }
-    a.H = a.W = s.in_side;
-    a.Ho = a.Wo = s.out_side;
-    a.npt = f.npt;
-    a.ringcols = f.ringcols;
-    a.n_colblocks = f.n_colblocks;
-    a.n_ctg = f.n_ctg;
-    // frozen cout tiles of this stage (rn_create proved y1 = beta for their channels and relabelled them to the end): not convolved
-    const bool fold = !f.m16 && stage == h->f32_fold_stage && s.skip_stage >= 0 && h->f32_fold_live > 0 && h->f32_fold_live < s.cout &&
-                      h->f32_fold_live % 32 == 0;
-    if (fold) a.n_ctg = h->f32_fold_live / 32;
-    const Bands bands = rn_bands_f32m(n, h->n_cu, s.out_side, f.n_colblocks * a.n_ctg, s.pool_k, s.pool_s);
-    a.rows_per_band = bands.rows_per_band;
-    a.n_bands = bands.n_bands;
-    const int rc = f.m16 ? kF32Variants16[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * f.npt * f.ks16), f.lds, h->stream)
-                         : kF32Variants[f.variant].fn(a, dim3(a.n_bands * a.n_colblocks * a.n_ctg, n), dim3(64 * f.npt * kF32Variants[f.variant].ks),
-                                                      f.lds, h->stream);
-    if (rc != RN_OK) return rc;
-    if (fold) {
-        const int c_begin = h->f32_fold_live, c_count = s.cout - c_begin;
-        const int64_t n_pix = static_cast<int64_t>(n) * s.out_side * s.out_side;
-        const int64_t threads = n_pix * (c_count / 4);
-        hipLaunchKernelGGL(f32_frozen_residual_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, h->stream, a.skip, a.out, a.bn_beta,
-                           a.bn2_mean, a.bn2_inv, a.bn2_beta, a.rlo, a.rhi, a.rlerp, n_pix, s.out_side, s.out_side, s.skip_side, s.cout, c_begin, c_count);
-        RN_CHECK_LAUNCH();
-    }
+    *plan = plan_stage(cin, cout, pool_k, pool_s, residual != 0, in_side, out_side, live_cin, frozen_couts);
     return RN_OK;
 }

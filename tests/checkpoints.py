@@ -51,3 +51,39 @@ def clamp_shares(taps, n_stages=10):
         c = np.asarray(taps["s%d.conv" % k])
         out.append((float((c == 6).mean()), float(((c > 0) & (c < 6)).mean())))
     return out
+
+
+def with_bn_gammas(weights, bn_name, frozen, seed):
+    """``weights`` with every gamma of the BN ``bn_name`` set to a trained-looking value and the channels ``frozen`` to 1e-24
+    (their betas to a visible constant): conftest.with_gammas' recipe for any one BN of the graph."""
+    rng = np.random.default_rng(seed)
+    w = dict(weights)
+    n = len(w[bn_name + "/gamma"])
+    g = rng.uniform(0.05, 0.4, n).astype(np.float32) * rng.choice([-1.0, 1.0], n).astype(np.float32)
+    b = w[bn_name + "/beta"].copy()
+    for c in frozen:
+        g[c] = np.float32(1e-24)
+        b[c] = np.float32(rng.uniform(0.002, 0.02))
+    w[bn_name + "/gamma"] = g
+    w[bn_name + "/beta"] = b
+    w[bn_name + "/moving_variance"] = np.maximum(w[bn_name + "/moving_variance"], np.float32(0.05))
+    return w
+
+
+def f32_frozen_channels(weights, bn_name, eps=1e-3):
+    """Channels of a stage's first BN the float32 stage kernels need not compute: y1 = ((x / 16 - mean) * inv + beta) is beta for
+    every x in [0, 6] where |inv| max(|mean|, |6 - mean|) < 2^-25 |beta| (the inequality of rn_stage_f32m.hip, inv in float32)."""
+    gamma, beta, mean, var = (weights[bn_name + "/" + leaf] for leaf in ("gamma", "beta", "moving_mean", "moving_variance"))
+    inv = ((np.float32(1) / np.sqrt(var + np.float32(eps), dtype=np.float32)) * gamma).astype(np.float64)
+    reach = np.maximum(np.abs(mean.astype(np.float64)), np.abs(6.0 - mean.astype(np.float64)))
+    return [int(c) for c in np.nonzero(np.abs(inv) * reach * (1.0 + 1e-6) < np.abs(beta.astype(np.float64)) * 2.0 ** -25)[0]]
+
+
+def take_back_stage9(graph, weights):
+    """The shipped checkpoint with the float32 input-channel fold landing where no kernel variant exists at all: stages 2, 4 and 5 with
+    no frozen channel (so no fold takes their place) and 11 of stage 8's 16 -- whole groups of 8 -> the fold is proposed for residual
+    stage 9, whose channels are relabelled, and is taken back."""
+    from conftest import with_gammas
+    w = with_gammas(weights, [], [], 5)
+    w = with_bn_gammas(w, graph.stages[4].bn_name, [], 6)
+    return with_bn_gammas(w, graph.stages[8].bn_name, np.random.default_rng(8).choice(16, 11, replace=False), 7)

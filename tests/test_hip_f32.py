@@ -6,6 +6,7 @@ probs abs <= 1e-5, ids identical where the top-2 margin > 1e-3; per-node max err
 import numpy as np
 import pytest
 
+import checkpoints
 from conftest import sample_positions, with_gammas
 from oracle import c_oracle, roomnet_ref as R
 from roomnet_amd import _capi
@@ -312,11 +313,14 @@ def test_matrix_core_f32_folds_stage_5_frozen_channels(weights, parity_images):
         full.close()
 
 
-@pytest.mark.parametrize("case", ["none", "nine_and_31", "other_sets", "everything"])
+@pytest.mark.parametrize("case", ["none", "nine_and_31", "other_sets", "everything", "lands_on_stage_9"])
 def test_matrix_core_f32_fold_on_other_checkpoints(weights, parity_images, case):
     """The float32 folds are a property of the CHECKPOINT too: frozen channels elsewhere, too few of them for a kernel variant
     (9 in stage 2: the relabelling happens, every channel is still contracted), or all of them (a stage needs live input
-    channels) -- the handle folds what it can and agrees with the oracle on every stage output."""
+    channels) -- the handle folds what it can and agrees with the oracle on every stage output.  lands_on_stage_9: frozen channels
+    in stage 8 only, so the input-channel fold is proposed for a stage no kernel covers and taken back after its relabelling
+    (tests/test_f32m_plan.py checks on the CPU that the checkpoint gets there).  "none" is also the take-back that cannot happen:
+    stage 4 of the shipped checkpoint freezes 11 channels, but its output is stage 5's skip tensor, so nothing folds into stage 5."""
     g = build_graph(6, 224)
     rng = np.random.default_rng(6)
     if case == "none":
@@ -326,8 +330,10 @@ def test_matrix_core_f32_fold_on_other_checkpoints(weights, parity_images, case)
     elif case == "other_sets":
         w, want = with_gammas(weights, rng.choice(32, 17, replace=False), rng.choice(64, 40, replace=False), 3), {
             "pair_channels_not_convolved": 16, "pair_channels_proven_frozen": 17, "residual_stage_folded": 5, "residual_stage_live_quarters": 2}
-    else:
+    elif case == "everything":
         w, want = with_gammas(weights, range(32), range(64), 4), {"pair_channels_not_convolved": 0, "residual_stage_folded": 5}
+    else:
+        w, want = checkpoints.take_back_stage9(g, weights), {"pair_channels_not_convolved": 0, "residual_stage_folded": -1}
     ims = parity_images[[14, 30, 2, 52]]
     ref = c_oracle.infer(w, ims, taps=True)
     e = _capi.Engine(g, w, device=0, dtype="f32", max_batch=4)

@@ -1,6 +1,6 @@
-"""Two builds of the library held to each other on the 16-bit path: every output byte and every launch.
+"""Two builds of the library held to each other on the 16-bit path and the float32 path: every output byte and every launch.
 
-For a refactor of the host side (rn_fused.hip) that must change neither.  One run per build writes a digest of probs, ids and of
+For a refactor of the host side (rn_fused.hip, rn_stage_f32m.hip) that must change neither.  One run per build writes a digest of probs, ids and of
 every tensor rn_tap returns, case by case; under rocprofv3 the same run is the build's launch sequence.  --summarise compares the two.
 
     rocprofv3 --kernel-trace -d DIR_A -o kt --output-format csv -- python tools/fused_plan_ab.py --trace-run --lib A.so --ab-lib A_ab.so --dump a.json
@@ -18,6 +18,10 @@ of rn_create and not launches of the forward pass).  The trace reports a kernel'
 Cases: bf16 and f16; sides 190 (no fused pair), 224, 300, 420, 600 at batch 3 and side 224 at ceil(n_cu / 2) images (the back end in
 one launch); the default handle, stage_launches, generic_kernels, compute_frozen, no_dither and pair32 (the A/B library); the shipped
 checkpoint, and at 224 the `live` recipe of tests/checkpoints.py, which folds nothing.
+Float32 cases: the same sides and batches; the default handle (the matrix-core stages of rn_stage_f32m.hip), compute_frozen, taps and
+batch_stats (the per-node kernels); the shipped checkpoint, `live`, and at 224 the four `with_gammas` checkpoints of
+tests/test_hip_f32.py::test_matrix_core_f32_fold_on_other_checkpoints (folds elsewhere, taken back, none).  The float32 stage
+kernels' LDS is all dynamic: tests/test_f32m_plan.py pins it on the CPU.
 """
 import argparse
 import csv
@@ -35,6 +39,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HANDLES = ("default", "stage_launches", "generic_kernels", "compute_frozen", "no_dither", "pair32")
+F32_HANDLES = ("default", "compute_frozen", "taps", "batch_stats")
+# tests/test_hip_f32.py::test_matrix_core_f32_fold_on_other_checkpoints: frozen channels of stage 2's BN and stage 5's first BN, seed
+GAMMAS = {"none": (0, 0, 1), "nine_and_31": (9, 31, 2), "other_sets": (17, 40, 3), "everything": (32, 64, 4)}
 SIDES = (190, 224, 300, 420, 600)
 BATCH = 3
 
@@ -47,6 +54,12 @@ def case_list(n_big):
                 cases.append(("shipped", dtype, handle, side, BATCH))
             cases.append(("shipped", dtype, handle, 224, n_big))
             cases.append(("live", dtype, handle, 224, BATCH))
+    for handle in F32_HANDLES:
+        for side in SIDES:
+            cases.append(("shipped", "f32", handle, side, BATCH))
+        cases.append(("shipped", "f32", handle, 224, n_big))
+        for kind in ("live",) + tuple("gammas_" + k for k in GAMMAS):
+            cases.append((kind, "f32", handle, 224, BATCH))
     return cases
 
 
@@ -59,6 +72,12 @@ def _weights(kind, side):
         import checkpoints
         return g, checkpoints.live(g, 1, checkpoints.LIVE_GAIN)
     w = dict(BundleReader(os.path.join(ROOT, "roomnet_amd", "final_model", "roomnet")).load_all())
+    if kind.startswith("gammas_"):
+        from conftest import with_gammas
+        n2, n5, seed = GAMMAS[kind[len("gammas_"):]]
+        rng = np.random.default_rng(6)
+        bn2 = range(32) if n2 == 32 else rng.choice(32, n2, replace=False) if n2 else []
+        return g, with_gammas(w, bn2, range(64) if n5 == 64 else rng.choice(64, n5, replace=False) if n5 else [], seed)
     if side != 224:
         w["dense/kernel"] = np.random.default_rng(side).uniform(-0.04, 0.04, (g.flat_len, 32)).astype(np.float32)
     return g, w
@@ -132,6 +151,8 @@ def summarise(dump_a, dump_b, trace_a, trace_b, rename=(), skip=()):
     n_tensors = sum(len(v) for v in a["cases"].values())
     lines.append("outputs (probs, ids, every rn_tap tensor, frozen / constant channel info; %d digests): %d cases, %d identical"
                  % (n_tensors, len(a["cases"]), len(same)))
+    for name, part in (("16-bit", [c for c in a["cases"] if c.split()[1] != "f32"]), ("float32", [c for c in a["cases"] if c.split()[1] == "f32"])):
+        lines.append("  %s: %d of %d cases identical" % (name, len([c for c in part if c in same]), len(part)))
     for c in sorted(a["cases"]):
         if c not in same:
             diff = [k for k in a["cases"][c] if b["cases"].get(c, {}).get(k) != a["cases"][c][k]]

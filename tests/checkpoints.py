@@ -9,7 +9,14 @@ import numpy as np
 from roomnet_amd.network import _initializer_values
 
 PARITY_IDX = [14, 30, 2]      # the parity images the stage-output tests of the shipped checkpoint use
-ONE_IMAGE_IDX = [30]         # the one of them that reaches the clamp in EVERY stage 1-9 on its own (the side-240 case)
+ONE_IMAGE_IDX = [30]         # the one of them that reaches the clamp in EVERY stage 1-9 on its own; a checkerboard of period 32:
+                             # its stage outputs are constant over whole regions (tests/test_seam_cases_host.py)
+# the clamp image plus the textured one (low-pass noise on an 8-pixel grid: neighbouring columns and rows differ at every stage
+# output): together they reach the clamp in every stage AND show an error of indexing (the side-240 and the seam cases)
+SEAM_IDX = [30, 14]
+# sides at which the tuned 16-bit kernels cut their rows into two or three column blocks (tests/block_plans.py); 600 is the
+# reference's own default side
+SEAM_SIDES = (409, 420, 600)
 LIVE_GAIN = 2.5               # conv-kernel gain at which every stage 1-9 has values at the clamp AND strictly inside (0, 6)
 
 

@@ -3,17 +3,16 @@
 ``stage_local`` computes ONE conv stage from a given input (and, for the residual stages, a given skip tensor): fed the
 tensors a handle itself stored, it judges every stage on exact inputs and nothing compounds.  ``head_local`` does the same
 for everything behind the last conv stage.  ``stage_local_emulated`` is the same stage with the roundings include/roomnet_hip.h
-documents for 16-bit handles applied by NumPy casts: a reference-side number that says how much of an error is rounding."""
+documents for 16-bit handles applied by NumPy casts: a reference-side number that says how much of an error is rounding.
+``check_stage_local`` and ``_check_nodes`` at the end are the checks the GPU test files share (a test module imports from here, never
+from another test module)."""
 import numpy as np
 
+import block_plans as BP
 from oracle import roomnet_ref as R
+from parity_bounds import STAGE_TOL, _tol
 
 F64 = np.float64
-
-
-def _colblock_plan_exists(out_side, wo_min, wo_max):
-    """csrc/rn_stage.h, rn_colblock_plan: one to four column blocks of wo_min .. wo_max pooled columns each."""
-    return any(-(-out_side // nb) <= wo_max and out_side // nb >= wo_min for nb in range(1, 5))
 
 
 def fp16_pool_stages(graph, tuned=True):
@@ -21,16 +20,11 @@ def fp16_pool_stages(graph, tuned=True):
     (include/roomnet_hip.h): the pool 4 / stride 1 stages 1-3 always; the stride-2 stages 4 and 5 where the row-blocked kernels
     run -- rows that can be cut into column blocks of 194-206 (stage 4) / 66-110 (stage 5) input columns, restated here from
     rn_stage4x_supported / rn_stage5x_supported: at 224 both, at 240 stage 5 only.  The generic kernels (``tuned=False``) pool in
-    float32.  On its row-blocked kernel stage 5 also rounds the lerp fraction of its horizontal interpolation, as stage 3 does."""
+    float32.  On its row-blocked kernel stage 5 also rounds the lerp fraction of its horizontal interpolation, as stage 3 does.
+    The plans themselves are restated in tests/block_plans.py."""
     if not tuned:
         return ()
-    out = [1, 2, 3]
-    s4, s5 = graph.stages[4], graph.stages[5]
-    if s4.in_side >= 193 and _colblock_plan_exists(s4.out_side, 95, 101):
-        out.append(4)
-    if s5.in_side >= 66 and s5.in_side - 2 * s5.out_side <= 5 and _colblock_plan_exists(s5.out_side, 31, 53):
-        out.append(5)
-    return tuple(out)
+    return (1, 2, 3) + tuple(k for k in (4, 5) if BP.stage_plan(graph, k))
 
 
 def stage_out_name(stage):
@@ -167,3 +161,68 @@ def rel_err(got, want):
     """max |got - want| relative to the abs-max of the float64 tensor ``want``."""
     want = np.asarray(want, F64)
     return float(np.abs(np.asarray(got, F64) - want).max() / max(float(np.abs(want).max()), 1e-6))
+
+
+# ---- the checks tests/test_hip_other_checkpoints.py and tests/test_hip_seams_live.py share ----------------------------------
+NOTHING_FOLDED = {"pair_channels_not_convolved": 0, "pair_channels_proven_frozen": 0, "residual_stage_folded": -1,
+                  "residual_stage_live_quarters": 4}
+STAGE_OUT = ["s0.bn", "s1.bn", "s2.bn", "s3.bn2", "s4.bn", "s5.bn2", "s6.bn", "s7.bn", "s8.bn", "s9.bn2"]
+SECTION = "other_checkpoints"       # the parity report's section of both files
+
+
+def _locate(got, want):
+    """Where a tensor is wrong: the worst element, its values, whether it sits at a clamp end, the three worst channels."""
+    d = np.abs(np.asarray(got, np.float64) - want)
+    i = np.unravel_index(int(d.argmax()), d.shape)
+    per_c = d.reshape(-1, d.shape[-1]).max(0)
+    worst_c = np.argsort(per_c)[::-1][:3]
+    return {"at [n, y, x, c]": [int(v) for v in i], "got": float(np.asarray(got)[i]), "want": float(want[i]),
+            "want_negative": bool(want[i] < 0), "worst_channels": {int(c): float(per_c[c]) for c in worst_c},
+            "elements_above_half_of_worst": int((d > 0.5 * d.max()).sum())}
+
+
+def check_stage_local(eng, w, ims, dtype, record=None, key="", tuned=True, lazy_emulation=False):
+    """Every stage of a handle that materialises all ten stage outputs, judged on the handle's own stored inputs: stage k's
+    stored output against ``stage_local`` of the stored output of stage k - 1 (and skip tensor).  Bound per tensor:
+    max(STAGE_TOL, 2 x the error of ``stage_local_emulated``).  ``lazy_emulation``: the emulation (as costly as the reference
+    itself) is computed only for a stage whose error exceeds STAGE_TOL -- the bound is the same, a passing stage's row then
+    carries no emulated error."""
+    g, n = eng.graph, len(ims)
+    eng.forward_u8(ims)
+    taps = [eng.tap(stage_out_name(s), n).astype(np.float64) for s in g.stages]
+    rows, bad = {}, []
+    for k, s in enumerate(g.stages):
+        x_in = preprocess64(ims) if k == 0 else taps[k - 1]
+        skip = taps[s.skip_stage] if s.residual else None
+        want = stage_local(g, w, k, x_in, skip)
+        assert taps[k].shape == want.shape, k
+        err = rel_err(taps[k], want)
+        bound, emu = STAGE_TOL[dtype], None
+        if not (lazy_emulation and err <= bound):
+            emu = rel_err(stage_local_emulated(g, w, k, x_in, skip, dtype, tuned=tuned), want)
+            bound = max(STAGE_TOL[dtype], 2.0 * emu)
+        rows[stage_out_name(s)] = {"rel_err": err, "emulated_rel_err": emu, "bound": bound}
+        print("%s %-7s stage-local %.3e   emulated %s   bound %.3e" % (dtype, stage_out_name(s), err,
+                                                                      "not needed" if emu is None else "%.3e" % emu, bound))
+        if not err <= bound:
+            bad.append((stage_out_name(s), err, bound, _locate(taps[k], want)))
+    if record:
+        record(SECTION, key, rows)
+    assert not bad, bad
+    return rows
+
+
+def _check_nodes(eng, names, n, r64, r32, record, key):
+    """Float32 handles: the named nodes against the float64 oracle run ``r64``, tolerance _tol with the float32 C oracle run ``r32``."""
+    rows, bad = {}, []
+    for name in names:
+        want = np.asarray(r64["taps"][name], np.float64)
+        got = eng.tap(name, n)
+        assert got.shape == want.shape, name
+        err, tol = float(np.abs(got - want).max()), _tol(want, r32["taps"][name])
+        rows[name] = {"err": err, "tol": tol}
+        if not err <= tol:
+            bad.append((name, err, tol))
+    print(key, " ".join("%s=%.2g/%.2g" % (k, v["err"], v["tol"]) for k, v in rows.items()))
+    record(SECTION, key, rows)
+    assert not bad, bad

@@ -84,13 +84,16 @@ def test_live_recipe_saturates_relu6_in_every_stage(live_ref):
 
 
 def test_live_recipe_saturates_relu6_at_side_240():
-    """The one-image side-240 case of the stage-local GPU test."""
+    """The two-image side-240 case of the stage-local GPU test (the clamp image and the textured one: tests/test_seam_cases_host.py
+    asserts what each of them is there for), and the clamp image on its own."""
     from conftest import parity_set_of
     g = build_graph(6, 240)
-    ref = R.infer(CK.live(g, 0, CK.LIVE_GAIN), parity_set_of(240)[CK.ONE_IMAGE_IDX], dtype=np.float64, taps=True)
-    shares = CK.clamp_shares(ref["taps"])
-    for k in range(1, 10):
-        assert shares[k][0] >= AT_CLAMP_MIN and shares[k][1] >= INSIDE_MIN, (k, shares)
+    w = CK.live(g, 0, CK.LIVE_GAIN)
+    for idx in (CK.SEAM_IDX, CK.ONE_IMAGE_IDX):
+        ref = R.infer(w, parity_set_of(240)[idx], dtype=np.float64, taps=True)
+        shares = CK.clamp_shares(ref["taps"])
+        for k in range(1, 10):
+            assert shares[k][0] >= AT_CLAMP_MIN and shares[k][1] >= INSIDE_MIN, (idx, k, shares)
 
 
 def test_init_scale_recipe_is_o1_and_does_not_saturate(graph, ims):

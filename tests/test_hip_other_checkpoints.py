@@ -24,13 +24,11 @@ from oracle import c_oracle, roomnet_ref as R
 from parity_bounds import FUSED_AWAY, MARGIN, STAGE_TOL, TIE_EDGE, _downstream_same, _same_up_to_sum_order, _tol
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
+from stage_ref import NOTHING_FOLDED, SECTION, STAGE_OUT, _check_nodes, check_stage_local
 
 pytestmark = pytest.mark.gpu
 
-NOTHING_FOLDED = {"pair_channels_not_convolved": 0, "pair_channels_proven_frozen": 0, "residual_stage_folded": -1,
-                  "residual_stage_live_quarters": 4}
 WHOLE_CHAIN_MARGIN = 0.5      # (f): ids must agree with float64 wherever its top-2 logit margin exceeds this
-SECTION = "other_checkpoints"
 
 
 @pytest.fixture(scope="module")
@@ -61,41 +59,6 @@ def refs(checkpoints, ims):
     return get
 
 
-def _locate(got, want):
-    """Where a tensor is wrong: the worst element, its values, whether it sits at a clamp end, the three worst channels."""
-    d = np.abs(np.asarray(got, np.float64) - want)
-    i = np.unravel_index(int(d.argmax()), d.shape)
-    per_c = d.reshape(-1, d.shape[-1]).max(0)
-    worst_c = np.argsort(per_c)[::-1][:3]
-    return {"at [n, y, x, c]": [int(v) for v in i], "got": float(np.asarray(got)[i]), "want": float(want[i]),
-            "want_negative": bool(want[i] < 0), "worst_channels": {int(c): float(per_c[c]) for c in worst_c},
-            "elements_above_half_of_worst": int((d > 0.5 * d.max()).sum())}
-
-
-def check_stage_local(eng, w, ims, dtype, record=None, key="", tuned=True):
-    """(a): every stage of a handle that materialises all ten stage outputs, judged on the handle's own stored inputs."""
-    g, n = eng.graph, len(ims)
-    eng.forward_u8(ims)
-    taps = [eng.tap(SR.stage_out_name(s), n).astype(np.float64) for s in g.stages]
-    rows, bad = {}, []
-    for k, s in enumerate(g.stages):
-        x_in = SR.preprocess64(ims) if k == 0 else taps[k - 1]
-        skip = taps[s.skip_stage] if s.residual else None
-        want = SR.stage_local(g, w, k, x_in, skip)
-        assert taps[k].shape == want.shape, k
-        err = SR.rel_err(taps[k], want)
-        emu = SR.rel_err(SR.stage_local_emulated(g, w, k, x_in, skip, dtype, tuned=tuned), want)
-        bound = max(STAGE_TOL[dtype], 2.0 * emu)
-        rows[SR.stage_out_name(s)] = {"rel_err": err, "emulated_rel_err": emu, "bound": bound}
-        print("%s %-7s stage-local %.3e   emulated %.3e   bound %.3e" % (dtype, SR.stage_out_name(s), err, emu, bound))
-        if not err <= bound:
-            bad.append((SR.stage_out_name(s), err, bound, _locate(taps[k], want)))
-    if record:
-        record(SECTION, key, rows)
-    assert not bad, bad
-    return rows
-
-
 # ---------------------------------------------------------------------------------------------- a. 16-bit, stage-local
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
 @pytest.mark.parametrize("ckpt", ["live", "init_scale"])
@@ -112,11 +75,12 @@ def test_16bit_stages_locally_vs_fp64(graph, checkpoints, ims, record, ckpt, dty
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
 def test_16bit_stages_locally_vs_fp64_at_side_240(record, dtype):
     """Side 240: stage 4's rows are too wide for its row-blocked kernel (the register-weights kernel runs, float32 pooling), the
-    stage pair and stages 5-6 keep theirs: another kernel mix, one image that reaches the clamp in every stage on its own."""
+    stage pair and stages 5-6 keep theirs: another kernel mix.  Two images: the one that reaches the clamp in every stage on its
+    own, whose stage outputs are constant over whole regions, and the textured one, on which a wrong index shows."""
     g = build_graph(6, 240)
     w = CK.live(g, 0, CK.LIVE_GAIN)
-    im = parity_set_of(240)[CK.ONE_IMAGE_IDX]
-    e = _capi.Engine(g, w, device=0, dtype=dtype, max_batch=1, stage_launches=True)
+    im = parity_set_of(240)[CK.SEAM_IDX]
+    e = _capi.Engine(g, w, device=0, dtype=dtype, max_batch=len(im), stage_launches=True)
     try:
         assert e.frozen_info() == NOTHING_FOLDED and e.const_info()["stage"] == -1
         check_stage_local(e, w, im, dtype, record, "stage_local_240_live_%s" % dtype)
@@ -252,24 +216,6 @@ def test_head_width_head_locally_vs_fp64(parity_images, record, nc, dtype):
 
 
 # ---------------------------------------------------------------------------------------------- e. float32 handles
-STAGE_OUT = ["s0.bn", "s1.bn", "s2.bn", "s3.bn2", "s4.bn", "s5.bn2", "s6.bn", "s7.bn", "s8.bn", "s9.bn2"]
-
-
-def _check_nodes(eng, names, n, r64, r32, record, key):
-    rows, bad = {}, []
-    for name in names:
-        want = np.asarray(r64["taps"][name], np.float64)
-        got = eng.tap(name, n)
-        assert got.shape == want.shape, name
-        err, tol = float(np.abs(got - want).max()), _tol(want, r32["taps"][name])
-        rows[name] = {"err": err, "tol": tol}
-        if not err <= tol:
-            bad.append((name, err, tol))
-    print(key, " ".join("%s=%.2g/%.2g" % (k, v["err"], v["tol"]) for k, v in rows.items()))
-    record(SECTION, key, rows)
-    assert not bad, bad
-
-
 @pytest.mark.parametrize("ckpt", ["live", "init_scale"])
 def test_f32_handles_vs_fp64(graph, checkpoints, ims, refs, record, ckpt):
     w = checkpoints[ckpt]

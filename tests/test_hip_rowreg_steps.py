@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 import torch              # (in front of the first load of the project's library, as in the other test files that use both)
 
+import block_plans as BP
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
 
@@ -42,22 +43,14 @@ GENERIC_BATCHES = {side: tuple(n for n in b if n <= 3) for side, b in BATCHES.it
 N_CU = 256                            # MI355X: the planner's chip (the GPU tests ask the device)
 
 
-def _colblocks(out_side, lo, hi):
-    """rn_colblock_plan's block count (rn_stage.h)."""
-    for nb in range(1, 5):
-        if (out_side + nb - 1) // nb <= hi and out_side // nb >= lo:
-            return nb
-    raise AssertionError(out_side)
-
-
 def _bands(side, n, n_cu):
     """(first output row, row steps) of every band of the stage 4 and of the stage 5 launch of `n` images of `side`; a band of r
     output rows runs 2 r + 4 steps (input rows)."""
     g = build_graph(6, side)
     out = []
-    for stage, lo, hi in ((g.stages[4], (193 + 1 - 4 + 1) // 2, (206 - 4) // 2), (g.stages[5], (66 - 4 + 1) // 2, (110 - 4) // 2)):
+    for stage in (g.stages[4], g.stages[5]):
         assert stage.pool_k == 4 and stage.pool_s == 2
-        rpb, nb = _capi.band_plan("rowreg", n, n_cu, stage.out_side, _colblocks(stage.out_side, lo, hi), pool_k=4, pool_s=2)
+        rpb, nb = _capi.band_plan("rowreg", n, n_cu, stage.out_side, len(BP.stage_plan(g, stage.index)), pool_k=4, pool_s=2)
         rows = [min(stage.out_side, (b + 1) * rpb) - b * rpb for b in range(nb)]
         assert sum(rows) == stage.out_side and min(rows) >= 1
         out.append([(b * rpb, 2 * r + 4) for b, r in enumerate(rows)])
@@ -80,7 +73,7 @@ def _check_coverage(n_cu):
                 seen[st] |= {steps for _, steps in only_one}
         # every side is compared under two different plans of either stage
         assert differs == [True, True], (side, differs)
-        blocks.add(_colblocks(build_graph(6, side).stages[4].out_side, (193 + 1 - 4 + 1) // 2, (206 - 4) // 2))
+        blocks.add(len(BP.stage_plan(build_graph(6, side), 4)))
     # a band's step count is even (two input rows per output row + 4): every even residue must be walked
     assert {x % S4_PERIOD for x in seen[0]} == set(range(0, S4_PERIOD, 2)), sorted(seen[0])
     assert {x % S5_PERIOD for x in seen[1]} == set(range(0, S5_PERIOD, 2)), sorted(seen[1])

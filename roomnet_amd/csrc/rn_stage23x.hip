@@ -29,6 +29,25 @@
 // 288 products of one convolution output tap by tap, 32 channels at a time, where the 32x32x16 form adds them 16 at a
 // time.  On gfx950 the two orders give the SAME bits: every test that compares the fused pair with one launch per stage
 // bit for bit (224, 420 and 600 inputs, 1-4 column blocks, 1-73 bands) passes unchanged with this kernel.
+//
+// How the kernel body is laid out:
+//
+//  * ONE operand pipeline, `pipe`: AHEAD ds_read_b128 operand reads in flight, the read AHEAD chunks further on issued behind an
+//    accumulator register, one counted s_waitcnt lgkmcnt per chunk, the chunk's MFMAs, the hooks.  Every convolution chain is a
+//    description handed to it (where the operand comes from, which register a read is ordered behind, the chunk's MFMAs and hook
+//    slots): `chain` (nine taps from a 32-channel ring: the producers' full form and the consumers' wide form), `chainA_half` (the
+//    producers' half form: two tiles side by side as two operand streams under one wait, or a single tile) and the two narrow arms
+//    of `cchain` (five two-tap chunks; three four-tap chunks).  A change to the pipeline is made in `pipe`, once.
+//  * The pooled tiles: finish_part is one of six slices of a tile's ReLU6 / pack / vertical pair sums; finish and finish1 run a tile's
+//    slices at once, finish_behind hangs a run of them behind the MFMA pairs of the next chain (with_finish: a whole tile behind pairs
+//    1 .. 6; the half form nests two of them, half 0 of two tiles behind pairs 1 .. 3 and 4 .. 6).  The history they carry from row
+//    to row (hp, q0, q1) is declared and zeroed by either role and reaches them as references to one tile's part: every way of
+//    declaring it once, or of reaching it through a tile index, moved the register allocation of the 256-register instantiations
+//    (NOTES.md, "Fused pair: one operand pipeline").
+//  * The roles.  Producer: per row step one of two bodies, step_half (PH == 1: two two-tile chains) or step_full (a chain per tile),
+//    which share the DMA / skip-row hooks, and `out`, the one B-ring store routine (pooling MFMA -> folded BN -> pack -> ds_write of
+//    PH halves).  Consumer: cchain per tile, out_reads / out_rest (pooling, residual interpolation on the matrix cores, the last BN,
+//    the output store).
 #include "rn_fused.h"
 #include "rn_stage.h"
 
@@ -38,11 +57,10 @@ using namespace rnk;
 
 namespace {
 
-// the on-chip tensor's 16-bit store: never dithered, round to nearest even (one v_cvt_pk per pair) -- like the stage-launch arm's
-// store of the same tensor (rn_stage_rw.hip: only the instantiations whose output can be dithered use the SR conversion)
-template <int DT>
-__device__ __forceinline__ unsigned pack2p(float a, float b) {
-    return pack2<DT>(a, b);
+// f(IC<0>{}) ... f(IC<N - 1>{}): a loop whose index is a compile-time constant of every pass (immediate offsets, wait counts)
+template <int N, class F>
+__device__ __forceinline__ void unrolled(F&& f) {
+    [&]<int... I>(std::integer_sequence<int, I...>) __attribute__((always_inline)) { (f(IC<I>{}), ...); }(std::make_integer_sequence<int, N>{});
 }
 
 // Cache policy (aux operand of the buffer store / LDS-DMA; 2 = nt): the output rows and the residual's second read of an A row are
@@ -95,6 +113,7 @@ template <int DT, int PH, bool NB, bool N8 = false>
 __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
     static_assert(!NB || PH == 1, "the narrow B ring holds the computed half only");
     static_assert(!N8 || NB, "the eight-channel ring is a narrow ring");
+    static_assert(PH == 2 || NB, "a producer that computes one half stores into a narrow ring (rn_stage23x_launch refuses the rest)");
     constexpr int ROWB = N8 ? X_ROWB_8 : NB ? X_ROWB_N : X_ROWB;
 // Registers: the kernel sits at 256 VGPRs with six spilled dwords, two of them reloaded inside the consumer's loop.  A build that
 // keeps four of the consumers' weight fragments in LDS instead has no scratch access at all and is 3 % SLOWER (0.490 against
@@ -144,34 +163,64 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
     }
     asm volatile("" : "+v"(pm), "+v"(pmx));
 
-    // two interleaved accumulation chains (the tile's two 16-cout halves) over the nine taps; the tap's operand is ONE
-    // ds_read_b128 (16 pixels x 32 channels), issued AHEAD taps early and retired by a counted wait
-    // `hook(IC<tap>)` runs behind the tap's MFMA pair: DMA issue and scalar bookkeeping ride in the MFMAs' shadow
-    auto chain = [&](auto S0C, auto ROWC, auto KC, const unsigned (&base)[3], const i32x4 (&wr)[2 * X_KT], f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {
-        constexpr int S0 = decltype(S0C)::value, ROW = decltype(ROWC)::value, k = decltype(KC)::value;
-        i32x4 fq[X_KT];
-        auto rd = [&](auto TC, float dep) __attribute__((always_inline)) -> i32x4 {
-            constexpr int tap = decltype(TC)::value, ky = tap / 3, kx = tap % 3;
-            constexpr int off = ((S0 + ky) % 4) * ROW + k * 1024;
-            i32x4 v;
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base[kx]), "n"(off), "v"(dep));
-            return v;
-        };
-        [&]<int... I>(std::integer_sequence<int, I...>) { ((fq[I] = rd(IC<I>{}, 0.f)), ...); }(std::make_integer_sequence<int, AHEAD>{});
-        [&]<int... I>(std::integer_sequence<int, I...>) {
-            (([&] {
-                 if constexpr (I + AHEAD < X_KT) fq[I + AHEAD] = rd(IC<(I + AHEAD < X_KT ? I + AHEAD : 0)>{}, I == 0 ? 0.f : acc[0][0]);
-                 // one counted wait per tap (one per PAIR of taps measured slower, 0.48-0.50 against 0.475 ms: a wait that
-                 // stalls costs more than its issue slot)
-                 constexpr int newer = (X_KT - 1 - I) < AHEAD ? (X_KT - 1 - I) : AHEAD;
-                 asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fq[I]) : "n"(newer));
-                 acc[0] = mfma16<DT>(fq[I], wr[2 * I], I == 0 ? zero4 : acc[0]);          // D'[pixel][cout], couts of half 0
-                 acc[1] = mfma16<DT>(fq[I], wr[2 * I + 1], I == 0 ? zero4 : acc[1]);
-                 hook(IC<I>{});
-             }()),
-             ...);
-        }(std::make_integer_sequence<int, X_KT>{});
+    // ---- THE operand pipeline of every convolution chain in this kernel.  A chain is NC chunks of K = 32; the operand of a chunk is
+    // one ds_read_b128 per stream (NS = 1, or 2: two tiles side by side), issued AHEAD chunks early and retired by one counted wait
+    // in front of the chunk's MFMAs.  A chain describes itself with three callables:
+    //   rd(IC<stream>, IC<chunk>, dep) -> operand    the read; `dep` is a register the read is ordered behind (below)
+    //   dep(IC<stream>) -> float                      an accumulator of the stream: a read issued inside the chain waits for it
+    //   mm(IC<chunk>, operands[NS])                   the chunk's MFMAs and whatever rides in their shadow (the hooks)
+    auto pipe = [&](auto NCC, auto NSC, auto&& rd, auto&& dep, auto&& mm) __attribute__((always_inline)) {
+        constexpr int NC = decltype(NCC)::value, NS = decltype(NSC)::value;
+        static_assert(NS == 1 || NS == 2, "one wait covers the operands of one chunk");
+        i32x4 fq[NC][NS];
+        unrolled<(NC < AHEAD ? NC : AHEAD)>([&](auto CC) __attribute__((always_inline)) {
+            unrolled<NS>([&](auto SC) __attribute__((always_inline)) { fq[decltype(CC)::value][decltype(SC)::value] = rd(SC, CC, 0.f); });
+        });
+        unrolled<NC>([&](auto CC) __attribute__((always_inline)) {
+            constexpr int I = decltype(CC)::value;
+            if constexpr (I + AHEAD < NC)
+                unrolled<NS>([&](auto SC) __attribute__((always_inline)) {
+                    fq[I + AHEAD][decltype(SC)::value] = rd(SC, IC<I + AHEAD>{}, I == 0 ? 0.f : dep(SC));
+                });
+            // one counted wait per chunk (one per PAIR of chunks measured slower, 0.48-0.50 against 0.475 ms: a wait that
+            // stalls costs more than its issue slot)
+            constexpr int newer = (NC - 1 - I) < AHEAD ? (NC - 1 - I) : AHEAD;
+            if constexpr (NS == 1)
+                asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fq[I][0]) : "n"(newer));
+            else
+                asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fq[I][0]), "+v"(fq[I][1]) : "n"(2 * newer));
+            mm(CC, fq[I]);
+        });
     };
+    auto lds_rd = [](auto OFFC, unsigned addr, float dep) __attribute__((always_inline)) -> i32x4 {
+        i32x4 v;
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(decltype(OFFC)::value), "v"(dep));
+        return v;
+    };
+    // the operand of tap TC (16 pixels x 32 channels) of tile k from a four-row ring of 64-byte pixels whose row S0 is the tap row ky = 0
+    auto rd_tap = [&](auto S0C, auto ROWC, auto KC, auto TC, const unsigned (&base)[3], float dep) __attribute__((always_inline)) -> i32x4 {
+        constexpr int tap = decltype(TC)::value, ky = tap / 3, kx = tap % 3;
+        return lds_rd(IC<((decltype(S0C)::value + ky) % 4) * decltype(ROWC)::value + decltype(KC)::value * 1024>{}, base[kx], dep);
+    };
+    // chunk I of a tile's two interleaved accumulation chains (its two 16-cout halves: no dependent-issue stall), started from `init`
+    auto mma2 = [&](auto CC, const i32x4& f, const i32x4 (&wr)[2 * X_KT], const f32x4 (&init)[2], f32x4 (&acc)[2]) __attribute__((always_inline)) {
+        constexpr int I = decltype(CC)::value;
+        acc[0] = mfma16<DT>(f, wr[2 * I], I == 0 ? init[0] : acc[0]);          // D'[pixel][cout], couts of half 0
+        acc[1] = mfma16<DT>(f, wr[2 * I + 1], I == 0 ? init[1] : acc[1]);
+    };
+    // a tile's nine taps from a 32-channel ring; `hook(IC<tap>)` runs behind the tap's MFMA pair: DMA issue and scalar bookkeeping
+    // ride in the MFMAs' shadow
+    auto chain = [&](auto S0C, auto ROWC, auto KC, const unsigned (&base)[3], const i32x4 (&wr)[2 * X_KT], const f32x4 (&init)[2], f32x4 (&acc)[2],
+                     auto&& hook) __attribute__((always_inline)) {
+        pipe(IC<X_KT>{}, IC<1>{},
+             [&](auto, auto TC, float dep) __attribute__((always_inline)) { return rd_tap(S0C, ROWC, KC, TC, base, dep); },
+             [&](auto) __attribute__((always_inline)) { return acc[0][0]; },
+             [&](auto TC, const i32x4 (&f)[1]) __attribute__((always_inline)) {
+                 mma2(TC, f[0], wr, init, acc);
+                 hook(TC);
+             });
+    };
+
     // ReLU6 -> fp16 pairs -> vertical pair sums; the pooling operand of the tile half = [pair sums two rows back | current]
     // Cut into six slices (per 16-cout half: pack rows 0-1, pack rows 2-3, pair sums + operand), so that the slices of tile k
     // can ride behind the MFMA pairs of tile k + 1's chain (the wave's other accumulator pair): with_finish() below.
@@ -205,14 +254,19 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
         int vt[2][2];
         [&]<int... I>(std::integer_sequence<int, I...>) { (finish_part(IC<I>{}, PRC, acc, hp, q0, q1, op, vt), ...); }(std::make_integer_sequence<int, 6>{});
     };
-    // chain hook = `base` (DMA / bookkeeping) + slice i - 1 of the previous tile's finish behind MFMA pair i = 1 .. 6
-    auto with_finish = [&](auto&& base, auto PRC, const f32x4 (&acc)[2], int (&hp)[2][2], auto& q0, auto& q1, i32x4 (&op)[2],
-                           int (&vt)[2][2]) __attribute__((always_inline)) {
-        return [&, PRC](auto IC_) __attribute__((always_inline)) {
-            constexpr int i = decltype(IC_)::value;
+    // chain hook = `base` (DMA / bookkeeping, or another hook of this kind) + slice j of a finished tile's first NH halves behind MFMA
+    // pair FIRST + j of the next chain; with_finish: the whole tile behind pairs 1 .. 6
+    auto finish_behind = [&](auto base, auto FIRSTC, auto NHC, auto PRC, const f32x4 (&acc)[2], int (&hp)[2][2], auto& q0, auto& q1, i32x4 (&op)[2],
+                             int (&vt)[2][2]) __attribute__((always_inline)) {
+        return [&, base, PRC](auto IC_) __attribute__((always_inline)) {
+            constexpr int j = decltype(IC_)::value - decltype(FIRSTC)::value;
             base(IC_);
-            if constexpr (i >= 1 && i <= 6) finish_part(IC<(i >= 1 && i <= 6 ? i - 1 : 0)>{}, PRC, acc, hp, q0, q1, op, vt);
+            if constexpr (j >= 0 && j < 3 * decltype(NHC)::value) finish_part(IC<j>{}, PRC, acc, hp, q0, q1, op, vt);
         };
+    };
+    auto with_finish = [&](auto base, auto PRC, const f32x4 (&acc)[2], int (&hp)[2][2], auto& q0, auto& q1, i32x4 (&op)[2],
+                           int (&vt)[2][2]) __attribute__((always_inline)) {
+        return finish_behind(base, IC<1>{}, IC<2>{}, PRC, acc, hp, q0, q1, op, vt);
     };
 
     // ---- residual skip rows: schedule as in rn_stage23.hip (the partner producer fetches the regular new row during the
@@ -233,10 +287,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
         __builtin_amdgcn_global_load_lds(row + i * 1024 + off, (lds_void_ptr)(skw + slot * X_SKROW + i * 1024), 16, 0, RN_NT_SKIP);
     };
     auto issue_skip_row = [&](int y, int slot) __attribute__((always_inline)) {
-        issue_skip_piece(IC<0>{}, y, slot);
-        issue_skip_piece(IC<1>{}, y, slot);
-        issue_skip_piece(IC<2>{}, y, slot);
-        issue_skip_piece(IC<3>{}, y, slot);
+        unrolled<4>([&](auto IC_) __attribute__((always_inline)) { issue_skip_piece(IC_, y, slot); });
     };
     auto no_hook = [](auto) __attribute__((always_inline)) {};
     struct VLerp {
@@ -292,10 +343,7 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
             }
         };
         auto issue_A_pieces = [&](const char* row, int slot) __attribute__((always_inline)) {
-            issue_A_piece(IC<0>{}, row, slot);
-            issue_A_piece(IC<1>{}, row, slot);
-            issue_A_piece(IC<2>{}, row, slot);
-            issue_A_piece(IC<3>{}, row, slot);
+            unrolled<4>([&](auto IC_) __attribute__((always_inline)) { issue_A_piece(IC_, row, slot); });
         };
         const char* a_next = in_blk + static_cast<int64_t>(yo0) * (Win * 64);
         unsigned baseA[3], wbB[4];
@@ -346,120 +394,130 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
             if (PH == 2 || !(f & 1)) asm volatile("" : "+v"(w2[f]));
         lds_barrier();
         // PH == 1: the frozen channels of the lane's group (positions 8 g + 4 .. 8 g + 7) as the two dwords every store carries
-        [[maybe_unused]] const int cdead0 = static_cast<int>(pack2p<DT>(shv[1][0], shv[1][1])), cdead1 = static_cast<int>(pack2p<DT>(shv[1][2], shv[1][3]));
 
+        const f32x4 zero2[2] = {zero4, zero4};
+        auto chainA = [&](auto PC, auto KC, f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {      // conv row t-2: A rows t-2 .. t
+            chain(IC<(decltype(PC)::value + 2) % 4>{}, IC<X_ROWA>{}, KC, baseA, w2, zero2, acc, hook);
+        };
         // ---- PH == 1: two adjacent tiles share a chain (one accumulator each: two independent MFMA chains, as the two halves of a
-        // tile are in the full form); a tap costs two operand reads and two MFMAs
-        [[maybe_unused]] auto chain2 = [&](auto S0C, auto K0C, auto K1C, f32x4& acc0, f32x4& acc1, auto&& hook) __attribute__((always_inline)) {
-            constexpr int S0 = decltype(S0C)::value, k0 = decltype(K0C)::value, k1 = decltype(K1C)::value;
-            i32x4 fa[X_KT], fb[X_KT];
-            auto rd = [&](auto TC, auto KC_, float dep) __attribute__((always_inline)) -> i32x4 {
-                constexpr int tap = decltype(TC)::value, ky = tap / 3, kx = tap % 3, k = decltype(KC_)::value;
-                constexpr int off = ((S0 + ky) % 4) * X_ROWA + k * 1024;
-                i32x4 v;
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(baseA[kx]), "n"(off), "v"(dep));
-                return v;
-            };
-            [&]<int... I>(std::integer_sequence<int, I...>) { ((fa[I] = rd(IC<I>{}, IC<k0>{}, 0.f), fb[I] = rd(IC<I>{}, IC<k1>{}, 0.f)), ...); }(std::make_integer_sequence<int, AHEAD>{});
-            [&]<int... I>(std::integer_sequence<int, I...>) {
-                (([&] {
-                     if constexpr (I + AHEAD < X_KT) {
-                         fa[I + AHEAD] = rd(IC<(I + AHEAD < X_KT ? I + AHEAD : 0)>{}, IC<k0>{}, I == 0 ? 0.f : acc0[0]);
-                         fb[I + AHEAD] = rd(IC<(I + AHEAD < X_KT ? I + AHEAD : 0)>{}, IC<k1>{}, I == 0 ? 0.f : acc1[0]);
-                     }
-                     constexpr int newer = (X_KT - 1 - I) < AHEAD ? (X_KT - 1 - I) : AHEAD;
-                     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(fa[I]), "+v"(fb[I]) : "n"(2 * newer));
-                     acc0 = mfma16<DT>(fa[I], w2[2 * I], I == 0 ? zero4 : acc0);
-                     acc1 = mfma16<DT>(fb[I], w2[2 * I], I == 0 ? zero4 : acc1);
-                     hook(IC<I>{});
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, X_KT>{});
+        // tile are in the full form); a tap costs two operand reads and two MFMAs.  K1 < 0: a single tile (the third tile of a
+        // three-tile wave), one dependent chain
+        auto chainA_half = [&](auto PC, auto K0C, auto K1C, f32x4& acc0, f32x4& acc1, auto&& hook) __attribute__((always_inline)) {
+            constexpr int NS = decltype(K1C)::value < 0 ? 1 : 2;
+            pipe(IC<X_KT>{}, IC<NS>{},
+                 [&](auto SC, auto TC, float dep) __attribute__((always_inline)) {
+                     return rd_tap(IC<(decltype(PC)::value + 2) % 4>{}, IC<X_ROWA>{}, IC<(decltype(SC)::value ? decltype(K1C)::value : decltype(K0C)::value)>{}, TC, baseA, dep);
+                 },
+                 [&](auto SC) __attribute__((always_inline)) { return decltype(SC)::value ? acc1[0] : acc0[0]; },
+                 [&](auto TC, const i32x4 (&f)[NS]) __attribute__((always_inline)) {
+                     constexpr int I = decltype(TC)::value;
+                     acc0 = mfma16<DT>(f[0], w2[2 * I], I == 0 ? zero4 : acc0);
+                     if constexpr (NS == 2) acc1 = mfma16<DT>(f[1], w2[2 * I], I == 0 ? zero4 : acc1);
+                     hook(TC);
+                 });
         };
-        // ... and a single tile (the third tile of a three-tile wave): one dependent chain
-        [[maybe_unused]] auto chain1 = [&](auto S0C, auto KC_, f32x4& acc0, auto&& hook) __attribute__((always_inline)) {
-            constexpr int S0 = decltype(S0C)::value, k = decltype(KC_)::value;
-            i32x4 fa[X_KT];
-            auto rd = [&](auto TC, float dep) __attribute__((always_inline)) -> i32x4 {
-                constexpr int tap = decltype(TC)::value, ky = tap / 3, kx = tap % 3;
-                constexpr int off = ((S0 + ky) % 4) * X_ROWA + k * 1024;
-                i32x4 v;
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(baseA[kx]), "n"(off), "v"(dep));
-                return v;
-            };
-            [&]<int... I>(std::integer_sequence<int, I...>) { ((fa[I] = rd(IC<I>{}, 0.f)), ...); }(std::make_integer_sequence<int, AHEAD>{});
-            [&]<int... I>(std::integer_sequence<int, I...>) {
-                (([&] {
-                     if constexpr (I + AHEAD < X_KT) fa[I + AHEAD] = rd(IC<(I + AHEAD < X_KT ? I + AHEAD : 0)>{}, I == 0 ? 0.f : acc0[0]);
-                     constexpr int newer = (X_KT - 1 - I) < AHEAD ? (X_KT - 1 - I) : AHEAD;
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fa[I]) : "n"(newer));
-                     acc0 = mfma16<DT>(fa[I], w2[2 * I], I == 0 ? zero4 : acc0);
-                     hook(IC<I>{});
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, X_KT>{});
-        };
-        // the first-half finish of two tiles behind MFMA pairs 1 .. 6 of the next chain
-        [[maybe_unused]] auto with_finish2 = [&](auto&& base, auto PRC, const f32x4 (&accx)[2], int (&hpx)[2][2], auto& q0x, auto& q1x, i32x4 (&opx)[2],
-                                const f32x4 (&accy)[2], int (&hpy)[2][2], auto& q0y, auto& q1y, i32x4 (&opy)[2], int (&vt)[2][2]) __attribute__((always_inline)) {
-            return [&, PRC](auto IC_) __attribute__((always_inline)) {
-                constexpr int i = decltype(IC_)::value;
-                base(IC_);
-                if constexpr (i >= 1 && i <= 3) finish_part(IC<(i >= 1 && i <= 3 ? i - 1 : 0)>{}, PRC, accx, hpx, q0x, q1x, opx, vt);
-                if constexpr (i >= 4 && i <= 6) finish_part(IC<(i >= 4 && i <= 6 ? i - 4 : 0)>{}, PRC, accy, hpy, q0y, q1y, opy, vt);
-            };
-        };
-        [[maybe_unused]] auto finish1 = [&](auto PRC, const f32x4 (&acc)[2], int (&hpx)[2][2], auto& q0x, auto& q1x, i32x4 (&opx)[2]) __attribute__((always_inline)) {
+        auto finish1 = [&](auto PRC, const f32x4 (&acc)[2], int (&hpx)[2][2], auto& q0x, auto& q1x, i32x4 (&opx)[2]) __attribute__((always_inline)) {
             int vt[2][2];
             finish_part(IC<0>{}, PRC, acc, hpx, q0x, q1x, opx, vt);
             finish_part(IC<1>{}, PRC, acc, hpx, q0x, q1x, opx, vt);
             finish_part(IC<2>{}, PRC, acc, hpx, q0x, q1x, opx, vt);
         };
-        [[maybe_unused]] auto out1 = [&](auto KC, auto PC, const i32x4 (&opk)[2], const i32x4 (&opn)[2], bool cross) __attribute__((always_inline)) {
-            constexpr int k = decltype(KC)::value, P = decltype(PC)::value;
-            constexpr int off = ((P + 3) % X_NB) * ROWB;         // B row t-5
-            f32x4 H = mfma16<RN_DTYPE_F16>(opk[0], pm, zero4);
-            if (cross) H = mfma16<RN_DTYPE_F16>(opn[0], pmx, H);
-            float y[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[i] = __builtin_fmaf(H[i], scv[0][i], shv[0][i]);
-            auto& wb = wbB;
-            if constexpr (NB) {
-                const i32x2 d = {static_cast<int>(pack2p<DT>(y[0], y[1])), static_cast<int>(pack2p<DT>(y[2], y[3]))};
-                asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(wb[k]), "v"(d), "n"(off) : "memory");
-            } else {
-                const i32x4 d = {static_cast<int>(pack2p<DT>(y[0], y[1])), static_cast<int>(pack2p<DT>(y[2], y[3])), cdead0, cdead1};
-                asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(wb[k]), "v"(d), "n"(off) : "memory");
-            }
-        };
-
+        // B row t-5 of tile k, PH halves: pooling MFMAs (the windows of columns 13..15 end in tile k + 1: `cross`) -> folded BN -> 16 bit -> B ring.
+        // The on-chip tensor's 16-bit store is never dithered: round to nearest even (one v_cvt_pk per pair), like the stage-launch arm's
+        // store of the same tensor (rn_stage_rw.hip: only the instantiations whose output can be dithered use the SR conversion)
         auto out = [&](auto KC, auto PC, const i32x4 (&opk)[2], const i32x4 (&opn)[2], bool cross) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value, P = decltype(PC)::value;
-            constexpr int off = ((P + 3) % X_NB) * X_ROWB;       // B row t-5
-            f32x4 H[2];
+            constexpr int off = ((P + 3) % X_NB) * ROWB;
+            f32x4 H[PH];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) H[h] = mfma16<RN_DTYPE_F16>(opk[h], pm, zero4);
+            for (int h = 0; h < PH; ++h) H[h] = mfma16<RN_DTYPE_F16>(opk[h], pm, zero4);
             if (cross) {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) H[h] = mfma16<RN_DTYPE_F16>(opn[h], pmx, H[h]);
+                for (int h = 0; h < PH; ++h) H[h] = mfma16<RN_DTYPE_F16>(opn[h], pmx, H[h]);
             }
-            float y[8];
+            float y[4 * PH];
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+            for (int h = 0; h < PH; ++h)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) y[4 * h + i] = __builtin_fmaf(H[h][i], scv[h][i], shv[h][i]);
-            const i32x4 d = {static_cast<int>(pack2p<DT>(y[0], y[1])), static_cast<int>(pack2p<DT>(y[2], y[3])),
-                             static_cast<int>(pack2p<DT>(y[4], y[5])), static_cast<int>(pack2p<DT>(y[6], y[7]))};
-            auto& wb = wbB;
-            asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(wb[k]), "v"(d), "n"(off) : "memory");
+            int d[2 * PH];
+#pragma unroll
+            for (int j = 0; j < 2 * PH; ++j) d[j] = static_cast<int>(pack2<DT>(y[2 * j], y[2 * j + 1]));
+            const unsigned wb = wbB[k];             // (read here: an asm operand inside `if constexpr` does not capture wbB by itself)
+            if constexpr (NB)       // ds_write_b64: the lane's 4 computed couts
+                asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(wb), "v"(i32x2{d[0], d[1]}), "n"(off) : "memory");
+            else
+                asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(wb), "v"(i32x4{d[0], d[1], d[2], d[3]}), "n"(off) : "memory");
+        };
+        // ---- a row step.  A row t+1 goes out as four DMA pieces behind MFMA pairs of the first chains.  Skip rows of the partner
+        // consumer: decided behind the first chain's MFMAs (hook0's slots 3 and 7), fetched behind a later chain's (hook2); when no
+        // new row is due the newest one is fetched again into its own slot (same bytes), so there is no branch around a DMA.
+        // The half form (PH == 1): two chains of two tiles each
+        auto step_half = [&](auto PC, auto&& hook0, auto&& hook2) __attribute__((always_inline)) {
+            constexpr int P = decltype(PC)::value;
+            // the DMA pieces of A row t + 1 and the skip bookkeeping behind the first chain's MFMA pairs, the partner
+            // consumer's skip pieces and the two tiles' finish slices behind the second's
+            auto hookA = [&](auto IC_) __attribute__((always_inline)) {
+                constexpr int i = decltype(IC_)::value;
+                if constexpr (i % 2 == 0 && i <= 6) issue_A_piece(IC<(i <= 6 ? i / 2 : 0)>{}, a_next, (P + 1) % X_NA);      // pieces 0 .. 3 behind pairs 0, 2, 4, 6
+                if constexpr (i == 3 || i == 7) hook0(IC_);              // (hook0's bookkeeping slots)
+            };
+            f32x4 ac0[2], ac1[2], ac2[2], ac3[2];
+            int vt[2][2];
+            i32x4 op[4][2];
+            op[3][0] = op[3][1] = i32x4{0, 0, 0, 0};
+            // (half 0 of tile 0 behind pairs 1 .. 3 of the second chain, of tile 1 behind pairs 4 .. 6)
+            auto hook2f = finish_behind(finish_behind(hook2, IC<1>{}, IC<1>{}, IC<(P & 3)>{}, ac0, hp[0], q0[0], q1[0], op[0], vt), IC<4>{}, IC<1>{}, IC<(P & 3)>{},
+                                        ac1, hp[1], q0[1], q1[1], op[1], vt);
+            chainA_half(PC, IC<0>{}, IC<1>{}, ac0[0], ac1[0], hookA);
+            if (has4) {
+                chainA_half(PC, IC<2>{}, IC<3>{}, ac2[0], ac3[0], hook2f);
+                out(IC<0>{}, PC, op[0], op[1], true);
+                finish1(IC<(P & 3)>{}, ac2, hp[2], q0[2], q1[2], op[2]);
+                out(IC<1>{}, PC, op[1], op[2], true);
+                finish1(IC<(P & 3)>{}, ac3, hp[3], q0[3], q1[3], op[3]);
+                out(IC<2>{}, PC, op[2], op[3], true);
+                out(IC<3>{}, PC, op[3], op[3], false);
+            } else {
+                chainA_half(PC, IC<2>{}, IC<-1>{}, ac2[0], ac2[0], hook2f);
+                out(IC<0>{}, PC, op[0], op[1], true);
+                finish1(IC<(P & 3)>{}, ac2, hp[2], q0[2], q1[2], op[2]);
+                out(IC<1>{}, PC, op[1], op[2], true);
+                out(IC<2>{}, PC, op[2], op[3], true);         // op[3] = 0, and columns 13..15 of the third tile go to the dummy column
+            }
+        };
+        // The full form: a chain per tile, A pieces behind the first two (hook0, hook1)
+        auto step_full = [&](auto PC, auto&& hook0, auto&& hook2) __attribute__((always_inline)) {
+            constexpr int P = decltype(PC)::value;
+            auto hook1 = [&](auto IC_) __attribute__((always_inline)) {
+                constexpr int i = decltype(IC_)::value;
+                if constexpr (i == 1) issue_A_piece(IC<2>{}, a_next, (P + 1) % X_NA);
+                if constexpr (i == 5) issue_A_piece(IC<3>{}, a_next, (P + 1) % X_NA);
+            };
+            // tile k's ReLU6 / pack / pair sums ride behind the MFMAs of tile k + 1's chain (two accumulator pairs alternate)
+            f32x4 accA[2], accB[2];
+            int vt[2][2];
+            i32x4 op[4][2];
+            op[3][0] = op[3][1] = i32x4{0, 0, 0, 0};
+            chainA(PC, IC<0>{}, accA, hook0);      // conv row t-2: A rows t-2 .. t
+            chainA(PC, IC<1>{}, accB, with_finish(hook1, IC<(P & 3)>{}, accA, hp[0], q0[0], q1[0], op[0], vt));
+            chainA(PC, IC<2>{}, accA, with_finish(hook2, IC<(P & 3)>{}, accB, hp[1], q0[1], q1[1], op[1], vt));
+            out(IC<0>{}, PC, op[0], op[1], true);
+            if (has4) {
+                chainA(PC, IC<3>{}, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2], vt));
+                out(IC<1>{}, PC, op[1], op[2], true);
+                finish(IC<(P & 3)>{}, accB, hp[3], q0[3], q1[3], op[3]);
+                out(IC<2>{}, PC, op[2], op[3], true);
+                out(IC<3>{}, PC, op[3], op[3], false);
+            } else {
+                finish(IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2]);
+                out(IC<1>{}, PC, op[1], op[2], true);
+                out(IC<2>{}, PC, op[2], op[3], true);         // op[3] = 0, and columns 13..15 of the third tile go to the dummy column
+            }
         };
         auto step = [&](auto PC, int t) __attribute__((always_inline)) {
             constexpr int P = decltype(PC)::value;
-            [[maybe_unused]] constexpr int PR = P & 1;
             if (t < nrows + 9) a_next += Win * 64;
-            // A row t+1: two DMA pieces behind MFMA pairs of the first tile's chain, two behind the second's.  Skip rows of the
-            // partner consumer: decided behind the first chain's MFMAs, fetched behind the third tile's; when no new row is
-            // due the newest one is fetched again into its own slot (same bytes), so there is no branch around a DMA
             auto hook0 = [&](auto IC_) __attribute__((always_inline)) {
                 constexpr int i = decltype(IC_)::value;
                 if constexpr (i == 1) issue_A_piece(IC<0>{}, a_next, (P + 1) % X_NA);
@@ -480,76 +538,14 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
                     }
                 }
             };
-            auto hook1 = [&](auto IC_) __attribute__((always_inline)) {
-                constexpr int i = decltype(IC_)::value;
-                if constexpr (i == 1) issue_A_piece(IC<2>{}, a_next, (P + 1) % X_NA);
-                if constexpr (i == 5) issue_A_piece(IC<3>{}, a_next, (P + 1) % X_NA);
-            };
             auto hook2 = [&](auto IC_) __attribute__((always_inline)) {
                 constexpr int i = decltype(IC_)::value;
-                if constexpr (i == 0) issue_skip_piece(IC<0>{}, sk_f, sk_slot);
-                if constexpr (i == 2) issue_skip_piece(IC<1>{}, sk_f, sk_slot);
-                if constexpr (i == 4) issue_skip_piece(IC<2>{}, sk_f, sk_slot);
-                if constexpr (i == 6) issue_skip_piece(IC<3>{}, sk_f, sk_slot);
+                if constexpr (i % 2 == 0 && i <= 6) issue_skip_piece(IC<(i <= 6 ? i / 2 : 0)>{}, sk_f, sk_slot);         // pieces 0 .. 3 behind pairs 0, 2, 4, 6
             };
-            if constexpr (PH == 1) {
-                // the DMA pieces of A row t + 1 and the skip bookkeeping behind the first chain's MFMA pairs, the partner
-                // consumer's skip pieces and the two tiles' finish slices behind the second's
-                auto hookA = [&](auto IC_) __attribute__((always_inline)) {
-                    constexpr int i = decltype(IC_)::value;
-                    if constexpr (i == 0) issue_A_piece(IC<0>{}, a_next, (P + 1) % X_NA);
-                    if constexpr (i == 2) issue_A_piece(IC<1>{}, a_next, (P + 1) % X_NA);
-                    if constexpr (i == 4) issue_A_piece(IC<2>{}, a_next, (P + 1) % X_NA);
-                    if constexpr (i == 6) issue_A_piece(IC<3>{}, a_next, (P + 1) % X_NA);
-                    if constexpr (i == 3 || i == 7) hook0(IC_);              // (hook0's bookkeeping slots)
-                };
-                f32x4 ac0[2], ac1[2], ac2[2], ac3[2];
-                int vt[2][2];
-                i32x4 op[4][2];
-                op[3][0] = op[3][1] = i32x4{0, 0, 0, 0};
-                chain2(IC<(P + 2) % 4>{}, IC<0>{}, IC<1>{}, ac0[0], ac1[0], hookA);
-                if (has4) {
-                    chain2(IC<(P + 2) % 4>{}, IC<2>{}, IC<3>{}, ac2[0], ac3[0],
-                           with_finish2(hook2, IC<(P & 3)>{}, ac0, hp[0], q0[0], q1[0], op[0], ac1, hp[1], q0[1], q1[1], op[1], vt));
-                    out1(IC<0>{}, PC, op[0], op[1], true);
-                    finish1(IC<(P & 3)>{}, ac2, hp[2], q0[2], q1[2], op[2]);
-                    out1(IC<1>{}, PC, op[1], op[2], true);
-                    finish1(IC<(P & 3)>{}, ac3, hp[3], q0[3], q1[3], op[3]);
-                    out1(IC<2>{}, PC, op[2], op[3], true);
-                    out1(IC<3>{}, PC, op[3], op[3], false);
-                } else {
-                    chain1(IC<(P + 2) % 4>{}, IC<2>{}, ac2[0],
-                           with_finish2(hook2, IC<(P & 3)>{}, ac0, hp[0], q0[0], q1[0], op[0], ac1, hp[1], q0[1], q1[1], op[1], vt));
-                    out1(IC<0>{}, PC, op[0], op[1], true);
-                    finish1(IC<(P & 3)>{}, ac2, hp[2], q0[2], q1[2], op[2]);
-                    out1(IC<1>{}, PC, op[1], op[2], true);
-                    out1(IC<2>{}, PC, op[2], op[3], true);         // op[3] = 0, and columns 13..15 of the third tile go to the dummy column
-                }
-                wait_vmcnt<0>();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                raw_barrier();
-                return;
-            }
-            // tile k's ReLU6 / pack / pair sums ride behind the MFMAs of tile k + 1's chain (two accumulator pairs alternate)
-            f32x4 accA[2], accB[2];
-            int vt[2][2];
-            i32x4 op[4][2];
-            op[3][0] = op[3][1] = i32x4{0, 0, 0, 0};
-            chain(IC<(P + 2) % 4>{}, IC<X_ROWA>{}, IC<0>{}, baseA, w2, accA, hook0);      // conv row t-2: A rows t-2 .. t
-            chain(IC<(P + 2) % 4>{}, IC<X_ROWA>{}, IC<1>{}, baseA, w2, accB, with_finish(hook1, IC<(P & 3)>{}, accA, hp[0], q0[0], q1[0], op[0], vt));
-            chain(IC<(P + 2) % 4>{}, IC<X_ROWA>{}, IC<2>{}, baseA, w2, accA, with_finish(hook2, IC<(P & 3)>{}, accB, hp[1], q0[1], q1[1], op[1], vt));
-            out(IC<0>{}, PC, op[0], op[1], true);
-            if (has4) {
-                chain(IC<(P + 2) % 4>{}, IC<X_ROWA>{}, IC<3>{}, baseA, w2, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2], vt));
-                out(IC<1>{}, PC, op[1], op[2], true);
-                finish(IC<(P & 3)>{}, accB, hp[3], q0[3], q1[3], op[3]);
-                out(IC<2>{}, PC, op[2], op[3], true);
-                out(IC<3>{}, PC, op[3], op[3], false);
-            } else {
-                finish(IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2]);
-                out(IC<1>{}, PC, op[1], op[2], true);
-                out(IC<2>{}, PC, op[2], op[3], true);         // op[3] = 0, and columns 13..15 of the third tile go to the dummy column
-            }
+            if constexpr (PH == 1)
+                step_half(PC, hook0, hook2);
+            else
+                step_full(PC, hook0, hook2);
             wait_vmcnt<0>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             raw_barrier();
@@ -690,69 +686,55 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
 #pragma unroll
     for (int f = 0; f < NW3; ++f) asm volatile("" : "+v"(w3[f]));
     lds_barrier();
-    // the narrow second conv: five two-tap chunks, one accumulator pair started from the frozen channels' constant
-    [[maybe_unused]] auto chainN = [&](auto S0C, auto KC, f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {
-        constexpr int S0 = decltype(S0C)::value, k = decltype(KC)::value;
-        i32x4 fq[5];
-        auto rd = [&](auto CC, float dep) __attribute__((always_inline)) -> i32x4 {
-            constexpr int c = decltype(CC)::value;
-            constexpr int row0 = S0 % 4, row1 = (S0 + 1) % 4, row2 = (S0 + 2) % 4;
-            i32x4 v;
-            if constexpr (c == 1) {
-                if constexpr (row0 == 3)
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(baseMixW), "n"(k * 512), "v"(dep));
-                else
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(baseMix), "n"(row0 * X_ROWB_N + k * 512), "v"(dep));
-            } else {
-                constexpr int off = (c == 0 ? row0 * X_ROWB_N : c == 2 ? row1 * X_ROWB_N + 32 : c == 3 ? row2 * X_ROWB_N : row2 * X_ROWB_N + 64) + k * 512;
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(baseN0), "n"(off), "v"(dep));
-            }
-            return v;
-        };
-        [&]<int... I>(std::integer_sequence<int, I...>) { ((fq[I] = rd(IC<I>{}, 0.f)), ...); }(std::make_integer_sequence<int, AHEAD>{});
-        [&]<int... I>(std::integer_sequence<int, I...>) {
-            (([&] {
-                 if constexpr (I + AHEAD < 5) fq[I + AHEAD] = rd(IC<(I + AHEAD < 5 ? I + AHEAD : 0)>{}, I == 0 ? 0.f : acc[0][0]);
-                 constexpr int newer = (4 - I) < AHEAD ? (4 - I) : AHEAD;
-                 asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fq[I]) : "n"(newer));
-                 acc[0] = mfma16<DT>(fq[I], w3[2 * I], I == 0 ? cinit[0] : acc[0]);
-                 acc[1] = mfma16<DT>(fq[I], w3[2 * I + 1], I == 0 ? cinit[1] : acc[1]);
-                 hook(IC<I + 1>{});                         // (the hooks count MFMA pairs 1 .. 6 of a nine-tap chain:
-                 if constexpr (I == 4) hook(IC<6>{});       //  the last pair of this one carries two of their slices)
-             }()),
-             ...);
-        }(std::make_integer_sequence<int, 5>{});
-        hook(IC<7>{});
-    };
-    // the eight-channel second conv: three four-tap chunks; the lane's three operand addresses of this step's ring phase are formed
-    // once per chain (ring row (S0 + ky) mod 4 of the lane's tap)
-    [[maybe_unused]] auto chainN8 = [&](auto S0C, auto KC, f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {
-        constexpr int S0 = decltype(S0C)::value, k = decltype(KC)::value;
-        unsigned ad[3];
+    // ---- the second conv's chain of tile k over ring phase P (conv row t-8: B rows t-8 .. t-6), one accumulator pair started from
+    // cinit.  The hooks count the MFMA pairs 0 .. 8 of a nine-tap chain in every form:
+    auto cchain = [&](auto PC, auto KC, f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {
+        constexpr int S0 = decltype(PC)::value, k = decltype(KC)::value;
+        auto dep = [&](auto) __attribute__((always_inline)) { return acc[0][0]; };
+        if constexpr (N8) {
+            // three four-tap chunks; the lane's three operand addresses of this step's ring phase are formed once per chain (ring row
+            // (S0 + ky) mod 4 of the lane's tap), and all three reads go out in front of the chain.  Pair I carries slots 2 I + 1, 2 I + 2
+            unsigned ad[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) ad[c] = col8[c] + static_cast<unsigned>(((S0 + ky8[c]) & 3) * X_ROWB_8);
-        i32x4 fq[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fq[c]) : "v"(ad[c]), "n"(k * 256));
-        [&]<int... I>(std::integer_sequence<int, I...>) {
-            (([&] {
-                 asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fq[I]) : "n"(2 - I));
-                 acc[0] = mfma16<DT>(fq[I], w3[2 * I], I == 0 ? cinit[0] : acc[0]);
-                 acc[1] = mfma16<DT>(fq[I], w3[2 * I + 1], I == 0 ? cinit[1] : acc[1]);
-                 hook(IC<2 * I + 1>{});                     // (the hooks count MFMA pairs 1 .. 7 of a nine-tap chain: two of
-                 hook(IC<2 * I + 2>{});                     //  their slices behind every pair of this one)
-             }()),
-             ...);
-        }(std::make_integer_sequence<int, 3>{});
-        hook(IC<7>{});
-    };
-    auto cchain = [&](auto PC_, auto KC, f32x4 (&acc)[2], auto&& hook) __attribute__((always_inline)) {
-        if constexpr (N8)
-            chainN8(PC_, KC, acc, hook);
-        else if constexpr (NB)
-            chainN(PC_, KC, acc, hook);
-        else
-            chain(PC_, IC<X_ROWB>{}, KC, baseB, w3, acc, hook);
+            for (int c = 0; c < 3; ++c) ad[c] = col8[c] + static_cast<unsigned>(((S0 + ky8[c]) & 3) * X_ROWB_8);
+            pipe(IC<3>{}, IC<1>{},
+                 [&](auto, auto CC, float) __attribute__((always_inline)) {
+                     i32x4 v;
+                     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(ad[decltype(CC)::value]), "n"(k * 256));
+                     return v;
+                 },
+                 dep,
+                 [&](auto CC, const i32x4 (&f)[1]) __attribute__((always_inline)) {
+                     constexpr int I = decltype(CC)::value;
+                     mma2(CC, f[0], w3, cinit, acc);
+                     hook(IC<2 * I + 1>{});
+                     hook(IC<2 * I + 2>{});
+                 });
+            hook(IC<7>{});
+        } else if constexpr (NB) {
+            // five two-tap chunks.  Pair I carries slot I + 1, the last one slot 6 as well
+            pipe(IC<5>{}, IC<1>{},
+                 [&](auto, auto CC, float dep) __attribute__((always_inline)) {
+                     constexpr int c = decltype(CC)::value;
+                     constexpr int row0 = S0 % 4, row1 = (S0 + 1) % 4, row2 = (S0 + 2) % 4;
+                     if constexpr (c == 1 && row0 == 3)
+                         return lds_rd(IC<k * 512>{}, baseMixW, dep);
+                     else if constexpr (c == 1)
+                         return lds_rd(IC<row0 * X_ROWB_N + k * 512>{}, baseMix, dep);
+                     else
+                         return lds_rd(IC<(c == 0 ? row0 * X_ROWB_N : c == 2 ? row1 * X_ROWB_N + 32 : c == 3 ? row2 * X_ROWB_N : row2 * X_ROWB_N + 64) + k * 512>{},
+                                       baseN0, dep);
+                 },
+                 dep,
+                 [&](auto CC, const i32x4 (&f)[1]) __attribute__((always_inline)) {
+                     constexpr int I = decltype(CC)::value;
+                     mma2(CC, f[0], w3, cinit, acc);
+                     hook(IC<I + 1>{});
+                     if constexpr (I == 4) hook(IC<6>{});
+                 });
+            hook(IC<7>{});
+        } else
+            chain(PC, IC<X_ROWB>{}, KC, baseB, w3, cinit, acc, hook);
     };
 
     // The LDS reads of a tile's epilogue (8 transposed reads of the skip rows, 6 table reads) are issued in FRONT of the next
@@ -784,17 +766,11 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
         auto& tsc2 = R.tsc2;
         // BN tables of the lane's 8 couts: read here, behind the skip reads and in front of the eight pooling / residual MFMAs
         // (a chain earlier they cost 24 registers across the chain)
-        {
-            const unsigned ta = tabl_lds;
-            auto& t1 = R.tsc1;
-            auto& t2 = R.tsh1;
-            auto& t3 = R.tsc2;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t1[h]) : "v"(ta), "n"(16 * h));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t2[h]) : "v"(ta), "n"(128 + 16 * h));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t3[h]) : "v"(ta), "n"(256 + 16 * h));
-            }
+        for (int h = 0; h < 2; ++h) {
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tsc1[h]) : "v"(tabl_lds), "n"(16 * h));
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tsh1[h]) : "v"(tabl_lds), "n"(128 + 16 * h));
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tsc2[h]) : "v"(tabl_lds), "n"(256 + 16 * h));
         }
         f32x4 H[2];
 #pragma unroll
@@ -835,7 +811,6 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
     };
     auto step = [&](auto PC, int t) __attribute__((always_inline)) {
         constexpr int P = decltype(PC)::value;
-        [[maybe_unused]] constexpr int PR = P & 1;
         const int jo = t - X_LAG;
         cx.yl = vl_cur.yl;
         cx.sk_lo = static_cast<unsigned>(slot_cur * X_SKROW);
@@ -869,15 +844,15 @@ __global__ __launch_bounds__(512, 2) void stage23x_kernel(const Stage23Args a) {
         auto hook_c2 = [&](auto IC_) __attribute__((always_inline)) {
             if constexpr (decltype(IC_)::value == 7) vl_pre = vlerp_of(yo0 + min(max(jo + 2, 0), nrows - 1));
         };
-        cchain(IC<P>{}, IC<0>{}, accA, no_hook);           // conv row t-8: B rows t-8 .. t-6
-        cchain(IC<P>{}, IC<1>{}, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[0], q0[0], q1[0], op[0], vt));
+        cchain(PC, IC<0>{}, accA, no_hook);           // conv row t-8: B rows t-8 .. t-6
+        cchain(PC, IC<1>{}, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[0], q0[0], q1[0], op[0], vt));
         wait_vmcnt<0>();                                       // a skip row fetched at the top of this step has landed
         out_reads(IC<0>{}, R);
-        cchain(IC<P>{}, IC<2>{}, accA, with_finish(hook_c2, IC<(P & 3)>{}, accB, hp[1], q0[1], q1[1], op[1], vt));
+        cchain(PC, IC<2>{}, accA, with_finish(hook_c2, IC<(P & 3)>{}, accB, hp[1], q0[1], q1[1], op[1], vt));
         out_rest(IC<0>{}, R, op[0], op[1], true);
         if (has4) {
             out_reads(IC<1>{}, R);
-            cchain(IC<P>{}, IC<3>{}, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2], vt));
+            cchain(PC, IC<3>{}, accB, with_finish(no_hook, IC<(P & 3)>{}, accA, hp[2], q0[2], q1[2], op[2], vt));
             out_rest(IC<1>{}, R, op[1], op[2], true);
             out_reads(IC<2>{}, R);
             finish(IC<(P & 3)>{}, accB, hp[3], q0[3], q1[3], op[3]);
@@ -940,74 +915,59 @@ bool rn_stage23_plan(int in_side, int* n_cblocks, int* x0, int* wo) {
 
 bool rn_stage23_supported(int in_side) { return rn_stage23_plan(in_side, nullptr, nullptr, nullptr); }
 
-// B-operand fragments of the 16x16x32 form: frag[tap][half][lane][j] = W[k = 32 tap + 8 (lane / 16) + j][cout(half, lane % 16)]
-// with cout(h, n) = 8 (n / 4) + 4 h + n % 4 (so that a lane's pooled rows 4 g + i of the two halves are couts 8 g .. 8 g + 7)
-void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(2 * X_KT) * 64 * 8, 0);
-    for (int tap = 0; tap < X_KT; ++tap)
+// B-operand fragments of the 16x16x32 form, `nchunks` K chunks of 32: frag[chunk][half][lane][j] = W[tap_of(chunk, lane)][cin_of(lane, j)][cout(half, lane % 16)]
+// with cout(h, n) = 8 (n / 4) + 4 h + n % 4 (so that a lane's pooled rows 4 g + i of the two halves are couts 8 g .. 8 g + 7); a tap past
+// the kernel's nine carries zero weights.  `w_hwio` is a [tap][cin][cout] kernel.
+template <class Tap, class Cin>
+static void pack_frags(const float* w_hwio, int dtype, int nchunks, Tap tap_of, Cin cin_of, std::vector<unsigned short>* out) {
+    out->assign(static_cast<size_t>(2 * nchunks) * 64 * 8, 0);
+    for (int c = 0; c < nchunks; ++c)
         for (int h = 0; h < 2; ++h)
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * tap + 8 * (l >> 4) + j, nn = l & 15;
+                    const int tap = tap_of(c, l), nn = l & 15;
+                    if (tap >= X_KT) continue;
                     const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
-                    const float v = w_hwio[static_cast<size_t>(k) * 32 + co];
-                    (*out)[((static_cast<size_t>(tap) * 2 + h) * 64 + l) * 8 + j] = rn_to16(v, dtype);
+                    const float v = w_hwio[(static_cast<size_t>(tap) * 32 + cin_of(l, j)) * 32 + co];
+                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + j] = rn_to16(v, dtype);
                 }
 }
 
-// Narrow second conv (NB): frag[(2 ky + j)][half][lane][jj] = W[ky][kx = 2 j + (lane / 32)][cin = ring_cin[8 ((lane / 16) & 1) + jj]][cout(half, lane % 16)]
-// (kx = 3: zero); ring_cin[r] = the stage-2 channel at ring channel r (16 entries).  `w_hwio` is the UNpermuted [tap][cin][cout] kernel.
+// The 32-channel ring: chunk = tap, lane group g = channels 8 g .. 8 g + 7 (both convs; the caller has permuted the kernel's B channels)
+void rn_stage23x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
+    pack_frags(w_hwio, dtype, X_KT, [](int c, int) { return c; }, [](int l, int j) { return 8 * (l >> 4) + j; }, out);
+}
+
+// Narrow second conv (NB): chunk c = taps 2 c, 2 c + 1 (tap = 3 ky + kx; tap 9: zeros) in the lane halves, channels ring_cin[8 (g & 1) + j];
+// ring_cin[r] = the stage-2 channel at ring channel r (16 entries).  `w_hwio` is the UNpermuted kernel.
 void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(10) * 64 * 8, 0);
-    for (int c = 0; c < 5; ++c)
-        for (int h = 0; h < 2; ++h)
-            for (int l = 0; l < 64; ++l)
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int tap = 2 * c + (l >> 5), nn = l & 15;          // chunk c = taps 2 c, 2 c + 1 (tap = 3 ky + kx; tap 9: zeros)
-                    if (tap > 8) continue;
-                    const int cin = ring_cin[8 * ((l >> 4) & 1) + jj];
-                    const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
-                    const float v = w_hwio[(static_cast<size_t>(tap) * 32 + cin) * 32 + co];
-                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = rn_to16(v, dtype);
-                }
+    pack_frags(w_hwio, dtype, 5, [](int c, int l) { return 2 * c + (l >> 5); }, [&](int l, int j) { return ring_cin[8 * ((l >> 4) & 1) + j]; }, out);
 }
 
-// Eight-channel second conv (N8): frag[c][half][lane][jj] = W[tap 4 c + lane / 16][cin = ring_cin[jj]][cout(half, lane % 16)] (taps > 8: zero);
-// ring_cin[r] = the stage-2 channel at ring channel r (8 entries).  `w_hwio` is the UNpermuted [tap][cin][cout] kernel.
+// Eight-channel second conv (N8): chunk c = taps 4 c + g, channels ring_cin[j] (8 entries).  `w_hwio` is the UNpermuted kernel.
 void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(6) * 64 * 8, 0);
-    for (int c = 0; c < 3; ++c)
-        for (int h = 0; h < 2; ++h)
-            for (int l = 0; l < 64; ++l)
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int tap = 4 * c + (l >> 4), nn = l & 15;
-                    if (tap > 8) continue;
-                    const int cin = ring_cin[jj];
-                    const int co = 8 * (nn >> 2) + 4 * h + (nn & 3);
-                    const float v = w_hwio[(static_cast<size_t>(tap) * 32 + cin) * 32 + co];
-                    (*out)[((static_cast<size_t>(c) * 2 + h) * 64 + l) * 8 + jj] = rn_to16(v, dtype);
-                }
+    pack_frags(w_hwio, dtype, 3, [](int c, int l) { return 4 * c + (l >> 4); }, [&](int, int j) { return ring_cin[j]; }, out);
 }
+
+namespace {
+template <int DT, int PH, bool NB, bool N8>
+int launch_form(hipStream_t s, const Stage23Args& a, int n) {
+    constexpr auto kern = stage23x_kernel<DT, PH, NB, N8>;
+    if (int rc = rn_allow_big_lds<kern>()) return rc;
+    hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), X_LDS, s, a);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+}  // namespace
 
 int rn_stage23x_launch(int dtype, hipStream_t s, const Stage23Args& a, int n) {
-    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
-        if (int rc = rn_allow_big_lds<Kern>()) return rc;
-        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cblocks, n), dim3(512), X_LDS, s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
-    if (a.producer_halves == 1 && a.narrow_b == 2) {
-        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 1, true, true>>{});
-        return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 1, true, true>>{});
-    }
-    if (a.producer_halves == 1 && a.narrow_b) {
-        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 1, true>>{});
-        return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 1, true>>{});
-    }
-    if (a.producer_halves == 1) {
+    if (a.producer_halves == 1 && !a.narrow_b) {
         rn_set_error("stage23x: producer_halves == 1 runs in the narrow form only");
         return RN_E_STATE;
     }
-    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage23x_kernel<RN_DTYPE_BF16, 2, false>>{});
-    return launch(rn_kernel<stage23x_kernel<RN_DTYPE_F16, 2, false>>{});
+    // [16-bit type][form of the B ring: all 32 channels, the 16 computed ones, the 8 computed ones]
+    static constexpr int (*const forms[2][3])(hipStream_t, const Stage23Args&, int) = {
+        {launch_form<RN_DTYPE_BF16, 2, false, false>, launch_form<RN_DTYPE_BF16, 1, true, false>, launch_form<RN_DTYPE_BF16, 1, true, true>},
+        {launch_form<RN_DTYPE_F16, 2, false, false>, launch_form<RN_DTYPE_F16, 1, true, false>, launch_form<RN_DTYPE_F16, 1, true, true>}};
+    return forms[dtype == RN_DTYPE_BF16 ? 0 : 1][a.producer_halves != 1 ? 0 : a.narrow_b == 2 ? 2 : 1](s, a, n);
 }

@@ -17,7 +17,9 @@ of rn_create and not launches of the forward pass).  The trace reports a kernel'
 
 Cases: bf16 and f16; sides 190 (no fused pair), 224, 300, 420, 600 at batch 3 and side 224 at ceil(n_cu / 2) images (the back end in
 one launch); the default handle, stage_launches, generic_kernels, compute_frozen, no_dither and pair32 (the A/B library); the shipped
-checkpoint, and at 224 the `live` recipe of tests/checkpoints.py, which folds nothing.
+checkpoint, and at 224 the `live` recipe of tests/checkpoints.py, which folds nothing.  The fused pair runs in its eight-channel form on the
+shipped checkpoint (24 constant channels of stage 2) and in its full form on `live` and compute_frozen; its 16-channel form needs a
+checkpoint that freezes 16 to 23: `gammas_other_sets` (17), default handle, both types, sides 224 and 420 (one column block and two).
 Float32 cases: the same sides and batches; the default handle (the matrix-core stages of rn_stage_f32m.hip), compute_frozen, taps and
 batch_stats (the per-node kernels); the shipped checkpoint, `live`, and at 224 the four `with_gammas` checkpoints of
 tests/test_hip_f32.py::test_matrix_core_f32_fold_on_other_checkpoints (folds elsewhere, taken back, none).  The float32 stage
@@ -44,6 +46,7 @@ F32_HANDLES = ("default", "compute_frozen", "taps", "batch_stats")
 GAMMAS = {"none": (0, 0, 1), "nine_and_31": (9, 31, 2), "other_sets": (17, 40, 3), "everything": (32, 64, 4)}
 SIDES = (190, 224, 300, 420, 600)
 BATCH = 3
+PAIR16_SIDES = (224, 420)       # the 16-bit cases of gammas_other_sets: one column block and two
 
 
 def case_list(n_big):
@@ -54,6 +57,8 @@ def case_list(n_big):
                 cases.append(("shipped", dtype, handle, side, BATCH))
             cases.append(("shipped", dtype, handle, 224, n_big))
             cases.append(("live", dtype, handle, 224, BATCH))
+        for side in PAIR16_SIDES:
+            cases.append(("gammas_other_sets", dtype, "default", side, BATCH))
     for handle in F32_HANDLES:
         for side in SIDES:
             cases.append(("shipped", "f32", handle, side, BATCH))
@@ -72,14 +77,14 @@ def _weights(kind, side):
         import checkpoints
         return g, checkpoints.live(g, 1, checkpoints.LIVE_GAIN)
     w = dict(BundleReader(os.path.join(ROOT, "roomnet_amd", "final_model", "roomnet")).load_all())
+    if side != 224:
+        w["dense/kernel"] = np.random.default_rng(side).uniform(-0.04, 0.04, (g.flat_len, 32)).astype(np.float32)
     if kind.startswith("gammas_"):
         from conftest import with_gammas
         n2, n5, seed = GAMMAS[kind[len("gammas_"):]]
         rng = np.random.default_rng(6)
         bn2 = range(32) if n2 == 32 else rng.choice(32, n2, replace=False) if n2 else []
         return g, with_gammas(w, bn2, range(64) if n5 == 64 else rng.choice(64, n5, replace=False) if n5 else [], seed)
-    if side != 224:
-        w["dense/kernel"] = np.random.default_rng(side).uniform(-0.04, 0.04, (g.flat_len, 32)).astype(np.float32)
     return g, w
 
 

@@ -413,6 +413,42 @@ RN_API int rn_grad_cam_f32(rn_handle* h, const float* rgb_nhwc, int n, const int
 RN_API int rn_grad_cam_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, const int32_t* d_class_ids, int layer_node,
                                  float* d_cam, float* d_alpha, float* d_probs, int64_t* d_ids);
 
+/* ---- grad-CAM heat maps drawn on the images the GPU holds ------------------------------------------
+ * roomnet_amd/cam.py's overlay_image for images in device memory: what turns a map of rn_grad_cam_* into a
+ * picture, between rn_jpeg_decode_batch_device and rn_jpeg_encode_batch_device, without the full-size image visiting the host.
+ * The heat goes on the square the network saw, the centred window of rn_crop_resize_*: side c = min(height, width), offset
+ * abs((width - height) // 2) along the longer axis with Python's floor division (a portrait image with an odd difference rounds
+ * the offset UP); the rest of the image is untouched.  Per window pixel (y, x) and per channel, in float64, every product, sum and
+ * quotient rounded on its own (no contraction), in cam.py's order:
+ *   src  = (i + 0.5) * (n_in / double(c)) - 0.5 clipped to [0, n_in - 1], lo = floor(src), hi = min(lo + 1, n_in - 1),
+ *          frac = src - lo                                   per axis (n_in = cam_h for i = y, cam_w for i = x)
+ *   up   = max((a (1 - xl) + b xl) (1 - yl) + (c (1 - xl) + d xl) yl, 0)   from the four map neighbours
+ *   v    = float32(up / mx), mx = the maximum of up over the window; mx = 0 (no positive entry): v = 0, the ramp's first anchor
+ *   heat = rint(A[i] (1 - t) + A[i + 1] t), i = min(floor(4 v), 3), t = 4 v - i, A = the five BGR anchors (128,0,0) (255,255,0)
+ *          (0,255,0) (0,255,255) (0,0,255)
+ *   out  = clip(rint((1 - weight) * image + weight * heat), 0, 255), stored as uint8 in place; rint rounds half to even.
+ * The bytes are those of cam.overlay_image of the same image, map and weight.  c = 1 and c < cam_h (the map is sampled down) are
+ * ordinary cases.  Map entries are taken as finite.
+ *
+ * rn_cam_overlay_batch_device  n images of individual sizes, each with a map of its own size, in two launches for the whole batch
+ *                         (the maxima -- an order-free maximum, the same bits in every schedule; then upsampling again, colour and
+ *                         blend).  Asynchronous on the handle's stream, so ordered behind the calls that wrote the images and the
+ *                         maps and in front of a following rn_jpeg_overlay_batch_device / rn_jpeg_encode_batch_device (the heat is
+ *                         under the text); the targets are copied before the call returns.  The maxima and the batch tables belong
+ *                         to the handle (allocated by the first call, double-buffered behind events, freed by rn_destroy):
+ *                         back-to-back calls without a sync are fine.
+ *                         n outside [1, max_batch]: RN_E_RANGE.  A null image or map pointer, a size outside 1..65535, a weight
+ *                         outside [0, 1] or NaN: RN_E_INVALID.  In both cases nothing is enqueued and the handle stays usable.
+ * rn_cam_last_overlay_ms  device time of the last rn_cam_overlay_batch_device call's launches; waits for them. */
+typedef struct rn_cam_target {
+    uint8_t* d_bgr;                   /* device, HWC, tightly packed                */
+    int32_t height, width;
+    const float* d_cam;               /* device map, e.g. one image's slice of rn_grad_cam_u8_device's d_cam */
+    int32_t cam_h, cam_w;
+} rn_cam_target;
+RN_API int rn_cam_overlay_batch_device(rn_handle* h, const rn_cam_target* targets, int n, double weight);
+RN_API int rn_cam_last_overlay_ms(rn_handle* h, float* ms);
+
 /* ---- fine-tuning stages 8-9 and the dense head on cached features ------------------------------
  * What the reference's RoomNet(optimized_inference=False).load() prepares (network.py:242, restore_excluded_vars: the conv trunk
  * restored, the dense head left at its initial values, to be trained), cut where it is cheap: stages 0-7 stay frozen, and

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "rn_jpeg_last_decode_ms",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
     "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
+    "rn_cam_overlay_batch_device", "rn_cam_last_overlay_ms",
 )
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
@@ -134,6 +135,12 @@ class rn_jpeg_overlay(C.Structure):
 class rn_jpeg_source(C.Structure):
     _fields_ = [("d_bgr", C.c_void_p), ("info", rn_jpeg_info), ("overlays", C.POINTER(rn_jpeg_overlay)), ("n_overlays", C.c_int32),
                 ("coeffs", C.c_void_p)]
+
+
+class rn_cam_target(C.Structure):
+    """One image of ``rn_cam_overlay_batch_device``: a BGR image in device memory and the device map to draw on its crop window."""
+    _fields_ = [("d_bgr", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("d_cam", C.c_void_p), ("cam_h", C.c_int32),
+                ("cam_w", C.c_int32)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -327,6 +334,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             getattr(lib, name).restype = i32
         lib.rn_jpeg_last_encode_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_jpeg_last_encode_ms.restype = i32
+    if hasattr(lib, "rn_cam_overlay_batch_device"):
+        lib.rn_cam_overlay_batch_device.argtypes = [vp, C.POINTER(rn_cam_target), i32, C.c_double]
+        lib.rn_cam_overlay_batch_device.restype = i32
+        lib.rn_cam_last_overlay_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_cam_last_overlay_ms.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -427,10 +439,11 @@ class Engine:
     # -- lifetime
     def close(self) -> None:
         if getattr(self, "_h", None):
-            for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0), getattr(self, "_jpeg_res", 0)):      # (jpegs_to_batch's / classify_resident's device buffers)
+            for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0), getattr(self, "_jpeg_res", 0),
+                      getattr(self, "_cam_maps", 0)):      # (jpegs_to_batch's / classify_resident's / explain_resident's device buffers)
                 if p:
                     self.lib.rn_device_free(self._h, C.c_void_p(p))
-            self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = self._jpeg_res = 0
+            self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = self._jpeg_res = self._cam_maps = 0
             self.lib.rn_destroy(self._h)
             self._h = None
 
@@ -593,6 +606,53 @@ class Engine:
         self.d2h(probs, d_probs)
         self.d2h(ids, d_ids)
         return ids, probs, addrs, shapes
+
+    def explain_resident(self, jpegs, images, layer, class_ids=None):
+        """``classify_resident`` with the evidence: the chunk is staged the same way, then ``rn_grad_cam_u8_device`` runs on the
+        cropped, resized batch instead of the forward pass and its maps STAY on the device.  ``class_ids``: int per file or None
+        (each file's argmax).  Returns ``(ids, probs, addresses, shapes, d_cams, (mh, mw))``: ``ids`` / ``probs`` are
+        ``classify_resident``'s bits (the grad-CAM contract), ``d_cams[k]`` the device address of file k's float32 ``[mh, mw]`` map,
+        valid like the image addresses until the next ``explain_resident`` (``cam_overlay_batch`` takes both)."""
+        if layer not in GRAD_CAM_LAYERS:
+            raise ValueError("grad_cam: layer must be one of %s, got %r" % (GRAD_CAM_LAYERS, layer))
+        jpegs, images = list(jpegs), [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        m, nc = len(jpegs) + len(images), self.graph.num_classes
+        if not 1 <= m <= self.max_batch:
+            raise ValueError("explain_resident: %d files (1..%d)" % (m, self.max_batch))
+        addrs, shapes = self._stage_resident(jpegs, images)
+        if not getattr(self, "_jpeg_res", 0):
+            self._jpeg_res = self.device_malloc(self.max_batch * (nc * 4 + 8))
+        per_map = max(h * w for _id, (h, w, _c) in (self.nodes()[name] for name in GRAD_CAM_LAYERS)) * 4
+        if not getattr(self, "_cam_maps", 0):
+            self._cam_maps = self.device_malloc(self.max_batch * (per_map + 4))         # the maps, then the class ids
+        d_probs, d_ids = self._jpeg_res, self._jpeg_res + self.max_batch * nc * 4
+        d_cls = None
+        if class_ids is not None:
+            d_cls = self._cam_maps + self.max_batch * per_map
+            self.h2d(d_cls, np.ascontiguousarray(np.broadcast_to(np.asarray(class_ids), (m,)), dtype=np.int32))
+        self.grad_cam_u8_device(self._jpeg_dst, m, d_cls, layer, self._cam_maps, None, d_probs, d_ids)
+        self.sync()
+        probs, ids = np.empty((m, nc), np.float32), np.empty((m,), np.int64)
+        self.d2h(probs, d_probs)
+        self.d2h(ids, d_ids)
+        mh, mw, _c = self.nodes()[layer][1]
+        return ids, probs, addrs, shapes, [self._cam_maps + k * mh * mw * 4 for k in range(m)], (mh, mw)
+
+    def cam_overlay_batch(self, items, weight: float = 0.5) -> None:
+        """``rn_cam_overlay_batch_device`` over ``items`` ``[(device image address, (height, width), device map address, (mh, mw))]``
+        (at most ``max_batch``): each map is drawn as a heat map on its image's crop window, in place -- the bytes of
+        ``cam.overlay_image``.  Asynchronous, ordered in front of a following ``jpeg_overlay_batch`` / ``jpeg_encode_batch``."""
+        arr = (rn_cam_target * max(len(items), 1))()
+        for k, (d_bgr, (h, w), d_cam, (mh, mw)) in enumerate(items):
+            arr[k].d_bgr, arr[k].height, arr[k].width = int(d_bgr), int(h), int(w)
+            arr[k].d_cam, arr[k].cam_h, arr[k].cam_w = int(d_cam), int(mh), int(mw)
+        _check(self.lib, self.lib.rn_cam_overlay_batch_device(self.handle, arr, len(items), float(weight)), "rn_cam_overlay_batch_device")
+
+    def cam_last_overlay_ms(self) -> float:
+        """Device time of the last heat-map batch's two launches (``rn_cam_last_overlay_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_cam_last_overlay_ms(self.handle, C.byref(ms)), "rn_cam_last_overlay_ms")
+        return float(ms.value)
 
     def jpeg_last_decode_ms(self) -> float:
         """Device time of the last JPEG batch's pixel stage (``rn_jpeg_last_decode_ms``)."""

@@ -59,3 +59,23 @@ def overlay(im_bgr_u8: np.ndarray, cam: np.ndarray, weight: float = 0.5) -> np.n
     heat = colormap(upsample(cam, im.shape[0]))
     out = (1.0 - weight) * im.astype(np.float64) + weight * heat.astype(np.float64)
     return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
+def crop_window(h: int, w: int):
+    """``(y0, x0, side)`` of the centred square ``RoomNet.center_crop`` cuts from an ``h x w`` image: side ``min(h, w)``, offset
+    ``abs((w - h) // 2)`` along the longer axis (Python's floor division: a portrait image with an odd difference rounds UP)."""
+    offset = abs((w - h) // 2)
+    return (0, offset, h) if h < w else (offset, 0, w)
+
+
+def overlay_image(im_bgr_u8: np.ndarray, cam: np.ndarray, weight: float = 0.5) -> np.ndarray:
+    """``overlay`` for a whole photograph ``[h, w, 3]`` of any shape: the heat goes on the square the network saw
+    (``crop_window``), the rest of the image is untouched.  Returns a new BGR uint8 image.  The definition of what
+    ``rn_cam_overlay_batch_device`` draws on the GPU, byte for byte."""
+    im = np.asarray(im_bgr_u8)
+    if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape[0] < 1 or im.shape[1] < 1:
+        raise ValueError("expected a [h, w, 3] BGR uint8 image, got %s %s" % (im.dtype, im.shape))
+    y0, x0, c = crop_window(im.shape[0], im.shape[1])
+    out = im.copy()
+    out[y0:y0 + c, x0:x0 + c] = overlay(im[y0:y0 + c, x0:x0 + c], cam, weight)
+    return out

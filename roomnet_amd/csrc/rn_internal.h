@@ -157,6 +157,7 @@ struct rn_handle {
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
     void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch and the batch table (rn_jpeg.hip; allocated by the first call)
     void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the double-buffered batch tables (rn_jpeg_enc.hip; the same)
+    void* cam_overlay = nullptr; // rn_cam_overlay_*: the per-image maxima and the double-buffered batch tables (rn_cam_overlay.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
     // node id -> position p of the stored tensor holds the reference's channel perm[p] (rn_tap puts them back in order)
@@ -218,6 +219,8 @@ int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
 void rn_jpeg_release(rn_handle* h);
 // ---- overlay + the encode's pixel stage (rn_jpeg_enc.hip)
 void rn_jpeg_enc_release(rn_handle* h);
+// ---- grad-CAM heat maps on resident images (rn_cam_overlay.hip)
+void rn_cam_overlay_release(rn_handle* h);
 // (rn_api.hip) the centred square window of network.py:137-146, the batched resize's device table, the tail of a host entry point
 void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side);
 int rn_ensure_resize_items(rn_handle* h);

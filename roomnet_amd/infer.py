@@ -224,7 +224,36 @@ def _in_batches_of_readable(results, batch_size):
     yield from pending
 
 
-def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False):
+def _explain_files(nn, fpaths, batch_size, layer):
+    """``_infer_files`` with the evidence: yields ``(index, image_bgr, idx, conf, cam)``, the grad-CAM map of each file's predicted
+    class from ``nn.grad_cam`` on the same batches; ids and confidences are ``_infer_files``'s (the grad-CAM contract)."""
+    pending = []
+
+    def flush():
+        if not pending:
+            return []
+        cams, ids, probs = nn.grad_cam([p[1] for p in pending], layer=layer)
+        res = [(p[0], p[1], int(ids[k]), probs[k][ids[k]], cams[k]) for k, p in enumerate(pending)]
+        pending.clear()
+        return res
+
+    for i, fpath, im in _decode_files(fpaths, batch_size):
+        if im is None:
+            print(fpath, '---> unreadable image, skipped')
+            continue
+        pending.append((i, im))
+        if len(pending) >= batch_size:
+            yield from flush()
+    yield from flush()
+
+
+def _heat_overlay_and_write(im, cam_map, weight, pred_label, pred_conf, out_fpath):
+    """``_overlay_and_write`` on the image with its heat map: the heat is under the text."""
+    from .cam import overlay_image
+    return _overlay_and_write(overlay_image(im, cam_map, weight), pred_label, pred_conf, out_fpath)
+
+
+def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
@@ -244,6 +273,13 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     if gpu_decode and overlay and not gpu_encode:
         raise ValueError("classify_im_dir: gpu_decode=True needs overlay=False (the overlay is drawn on the decoded image, "
                          "which the GPU decode path never brings to the host) or gpu_encode=True")
+    if heatmap is not None and not overlay:
+        raise ValueError("classify_im_dir: heatmap=%r needs overlay=True (without the overlay the files are copied: there is "
+                         "nothing to draw on)" % (heatmap,))
+    if heatmap is not None and heatmap not in ('s6.bn', 's7.bn'):
+        raise ValueError("classify_im_dir: heatmap must be None, 's6.bn' or 's7.bn', got %r" % (heatmap,))
+    if heatmap is not None and not 0.0 <= heatmap_weight <= 1.0:
+        raise ValueError("classify_im_dir: heatmap_weight must be in [0, 1], got %r" % (heatmap_weight,))
     print('Classifying images in', imgs_dir)
     all_im_paths = glob(imgs_dir + '/*')
     out_dir = imgs_dir + '_classified'
@@ -259,12 +295,15 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     row = 0      # unreadable files are skipped (the reference crashes on them): rows stay contiguous
     writers = ThreadPoolExecutor(max_workers=DECODE_THREADS) if overlay else None
     writing = deque()
+    heat = {} if heatmap is None else dict(heatmap=heatmap, heatmap_weight=heatmap_weight)      # (a model object without the arguments still works without a heat map)
     if gpu_encode:
         results = _in_batches_of_readable(
             nn.classify_files_to_dir(all_im_paths,
                                      lambda i, idx: out_dir + os.sep + CLASS_LABELS[idx] + os.sep + all_im_paths[i].split(os.sep)[-1],
                                      lambda h, w, idx, conf: _overlay_lines(h, w, CLASS_LABELS[idx], conf),
-                                     writers, batch_size=batch_size), batch_size)
+                                     writers, batch_size=batch_size, **heat), batch_size)
+    elif heatmap is not None:
+        results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap))
     else:
         results = ((i, idx, conf, im, None) for i, im, idx, conf in _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode))
     try:
@@ -280,8 +319,8 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
             if written is not None:
                 writing.append(written)
             elif overlay:
-                writing.append(writers.submit(_overlay_and_write, im, pred_label, pred_conf,
-                                              out_fpath_dir + os.sep + fpath.split(os.sep)[-1]))
+                draw = (_heat_overlay_and_write, im[0], im[1], heatmap_weight) if isinstance(im, tuple) else (_overlay_and_write, im)
+                writing.append(writers.submit(*draw, pred_label, pred_conf, out_fpath_dir + os.sep + fpath.split(os.sep)[-1]))
                 while len(writing) > 4 * DECODE_THREADS:      # (a bound on the decoded images held for the writers)
                     writing.popleft().result()
             else:

@@ -383,7 +383,8 @@ class RoomNet:
                 cur, ahead = ahead, (submit(k + 1) if k + 1 < n_chunks else [])
                 yield k * chunk, [f.result() for f in cur]
 
-    def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64):
+    def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64, heatmap=None,
+                              heatmap_weight=0.5):
         """Classify image FILES and write each with its overlay as a JPEG file, decode to encode on the GPU.  Yields, in list
         order, ``(index, id, conf, image, future)``: ``future`` is the pending write (on the ``writers`` pool) of a file that went
         through the device; ``image`` (BGR) is set instead for a file whose output name ``out_path_of(index, id)`` has no JPEG
@@ -396,9 +397,20 @@ class RoomNet:
         stage (``rn_jpeg_encode_batch_device``), and the ``writers`` pool runs the Huffman pass of the output and writes the
         file while the GPU works on the next chunk.  The coefficients come back into a second ring of page-locked buffers,
         two banks like the decode's; a bank is reused once its files are written.  The full-size image never exists on the host.
-        Every file equals ``imageio.imwrite`` of the ``put_text`` image byte for byte."""
+        Every file equals ``imageio.imwrite`` of the ``put_text`` image byte for byte.
+
+        ``heatmap`` ("s6.bn" or "s7.bn"; None: off): each file also gets the grad-CAM map of its predicted class, drawn on the
+        square the network saw with ``heatmap_weight``, UNDER the text.  The chunk then runs ``Engine.explain_resident`` (the
+        forward pass and its adjoint; the same ids and confidences) and ``Engine.cam_overlay_batch`` in front of the text and the
+        encode, all on the device; a file the caller writes comes back with its heat map drawn on the host (``grad_cam``,
+        ``cam.overlay_image``: the same bytes)."""
         import os
-        from . import hershey, jpegdec, jpegenc
+        from . import cam, hershey, jpegdec, jpegenc
+        from ._capi import GRAD_CAM_LAYERS
+        if heatmap is not None and heatmap not in GRAD_CAM_LAYERS:
+            raise ValueError("classify_files_to_dir: heatmap must be None or one of %s, got %r" % (GRAD_CAM_LAYERS, heatmap))
+        if not 0.0 <= heatmap_weight <= 1.0:
+            raise ValueError("classify_files_to_dir: heatmap_weight must be in [0, 1]")
         paths = list(paths)
         if not paths:
             return
@@ -435,8 +447,12 @@ class RoomNet:
             host = [j for j, r in enumerate(loaded) if r is not None and r[0] == "image" and j not in up]
             out = {}
             if jp or up:
-                ids, probs, addrs, shapes = eng.classify_resident([(loaded[j][1], loaded[j][2]) for j in jp],
-                                                                  [loaded[j][1] for j in up])
+                staged = [(loaded[j][1], loaded[j][2]) for j in jp], [loaded[j][1] for j in up]
+                if heatmap is None:
+                    ids, probs, addrs, shapes = eng.classify_resident(*staged)
+                else:
+                    ids, probs, addrs, shapes, d_cams, map_shape = eng.explain_resident(*staged, heatmap)
+                    eng.cam_overlay_batch([(addrs[m], shapes[m], d_cams[m], map_shape) for m in range(len(addrs))], heatmap_weight)
                 confs = [probs[m][ids[m]] for m in range(len(ids))]
                 overlays = list(writers.map(rasterise, shapes, [lines_of(h, w, int(ids[m]), confs[m]) for m, (h, w) in enumerate(shapes)]))
                 infos = [jpegenc.encode_info(h, w) for h, w in shapes]
@@ -447,10 +463,14 @@ class RoomNet:
                     fut = writers.submit(write, infos[m], bufs[m], out_path_of(lo + j, int(ids[m])))
                     pending[bank].append(fut)
                     out[j] = (int(ids[m]), confs[m], None, fut)
-            if host:
+            if host and heatmap is None:
                 ids, probs = eng.classify_images([loaded[j][1] for j in host])
                 for m, j in enumerate(host):
                     out[j] = (int(ids[m]), probs[m][ids[m]], loaded[j][1], None)
+            elif host:
+                cams, ids, probs = self.grad_cam([loaded[j][1] for j in host], layer=heatmap)
+                for m, j in enumerate(host):
+                    out[j] = (int(ids[m]), probs[m][ids[m]], cam.overlay_image(loaded[j][1], cams[m], heatmap_weight), None)
             for j in range(len(loaded)):
                 yield (lo + j,) + out.get(j, (None, None, None, None))
 

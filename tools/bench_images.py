@@ -12,6 +12,10 @@
         decode, host overlay and re-encode on the pool) against overlay=True, gpu_decode=True, gpu_encode=True on the same files,
         alternating, three times each after a warm-up of both; the host Huffman-encode pass alone on one thread and the device time
         of the overlay + encode launches per batch; a line with the rates, the ratio and whether the files are identical
+  python tools/bench_images.py --heatmap [--threads=T] [H W [N]]    a generated directory again, nothing of the above: the device time
+        of the two heat-map launches (rn_cam_last_overlay_ms) for one batch and both layers, next to the decode's and the encode's
+        pixel stages of the same batch; then classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True) with heatmap="s6.bn",
+        the same call with heatmap=None and the host arm with the heat map, alternating, twice each after a warm-up round
 """
 import contextlib
 import io
@@ -64,7 +68,8 @@ def decoded_images():
               N, W, H, N / t_gpu, 1e3 * t_gpu / N, N * min(H, W) ** 2 * 3 / 1e6, N / t_host, 1e3 * t_host / N))
 
 
-def directory():
+def generated_directory():
+    """``(root, d, nn, paths, MB)``: N generated JPEG files of H x W under ``d`` and the bf16 model."""
     from roomnet_amd import infer
     from roomnet_amd.network import RoomNet
     if THREADS:
@@ -85,6 +90,12 @@ def directory():
     nn.load(os.path.join('roomnet_amd', 'final_model', 'roomnet'))
     paths = sorted(os.path.join(d, f) for f in os.listdir(d))
     nn.infer_images([imageio.imread(paths[0])])
+    return root, d, nn, paths, mb
+
+
+def directory():
+    from roomnet_amd import infer
+    root, d, nn, paths, mb = generated_directory()
     t0 = time.perf_counter()
     for p in paths:
         imageio.imread(p)
@@ -234,7 +245,58 @@ def gpu_encode_arm(nn, infer, d, paths, overlay_write_ips):
              overlay_write_ips, ms, n, 1e3 * ms / n))
 
 
-if '--dir' in sys.argv:
+def heatmap_arm():
+    """The heat map's launches against the decode's and the encode's pixel stages, and the directory driver with and without it."""
+    from roomnet_amd import infer, jpegdec, jpegenc
+    root, d, nn, paths, mb = generated_directory()
+    eng = nn._engine()
+    n = min(len(paths), eng.max_batch)
+    items = [jpegdec.entropy_decode(open(p, 'rb').read()) for p in paths[:n]]
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    cam_ms, dec_ms = {}, []
+    for layer in ('s6.bn', 's7.bn'):
+        ms = []
+        for _ in range(6):
+            _ids, _probs, addrs, shapes, d_cams, map_shape = eng.explain_resident(items, [], layer)
+            dec_ms.append(eng.jpeg_last_decode_ms())
+            eng.cam_overlay_batch([(addrs[k], shapes[k], d_cams[k], map_shape) for k in range(n)], 0.5)
+            eng.sync()
+            ms.append(eng.cam_last_overlay_ms())
+        cam_ms[layer] = med(ms[1:])
+    infos = [jpegenc.encode_info(h, w) for h, w in shapes]
+    pinned = [_capi.PinnedArray((jpegdec.coeff_count(i),), np.int16) for i in infos]
+    enc_ms = []
+    for _ in range(6):
+        eng.jpeg_encode_batch([(a, i, [], c.array) for a, i, c in zip(addrs, infos, pinned)])
+        eng.sync()
+        enc_ms.append(eng.jpeg_last_encode_ms())
+    for c in pinned:
+        c.close()
+    side = min(H, W)
+    print('%d JPEG files %dx%d (%.0f MB), one batch of %d, window %dx%d: heat map launches %.3f ms (s6.bn, 46x46 maps; %.1f us per image, '
+          '%.0f GB/s of the 6 B per window pixel)  %.3f ms (s7.bn, 21x21 maps)   decode pixel stage %.3f ms   encode pixel stage %.3f ms'
+          % (len(paths), W, H, mb, n, side, side, cam_ms['s6.bn'], 1e3 * cam_ms['s6.bn'] / n, n * side * side * 6 / cam_ms['s6.bn'] / 1e6,
+             cam_ms['s7.bn'], med(dec_ms[1:]), med(enc_ms[1:])))
+    arms = {'gpu + heat map': dict(gpu_decode=True, gpu_encode=True, heatmap='s6.bn'), 'gpu': dict(gpu_decode=True, gpu_encode=True),
+            'host + heat map': dict(heatmap='s6.bn')}
+    times = {a: [] for a in arms}
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):
+        for rep in range(3):                              # (the first round is the warm-up of every arm)
+            for arm, kw in arms.items():
+                t0 = time.perf_counter()
+                infer.classify_im_dir(nn, d, overlay=True, batch_size=64, **kw)
+                if rep:
+                    times[arm].append(time.perf_counter() - t0)
+    N_ = len(paths)
+    print('classify_im_dir(overlay=True), same files, same session, alternating, 2 runs each after a warm-up, %d decode threads:   '
+          % infer.DECODE_THREADS + '   '.join('%s %s img/s' % (a, ' / '.join('%.1f' % (N_ / x) for x in t)) for a, t in times.items()))
+    shutil.rmtree(root, ignore_errors=True)
+
+
+if '--heatmap' in sys.argv:
+    heatmap_arm()
+elif '--dir' in sys.argv:
     directory()
 else:
     decoded_images()

@@ -533,6 +533,38 @@ RN_API int rn_ft_last_run_ms(rn_ft* ft, float* ms);
 RN_API int rn_ft_upload(rn_ft* ft, const void* src, size_t bytes, void** d_ptr);
 RN_API int rn_ft_free(rn_ft* ft, void* d_ptr);
 
+/* ---- validation inside a training run ------------------------------------------------------------
+ * The other half of the reference's loop (train.py:134-155): every SAVE_FREQ steps the validation set is run and accuracy and the
+ * per-class figures are recorded.  rn_ft_run_validated is rn_ft_run with evaluation passes over a second resident set enqueued
+ * between steps on the trainer's stream; the run keeps its one synchronisation.
+ * Points: with g0 = rn_ft_step_count at the call, one after the step that brings the global step to g, for every g in
+ *               (g0, g0 + steps] with g % val_every == 0 (the reference's rule), and one more at g0 + steps if that is none.
+ * rn_ft_val_points  the number of points of such a call (host only); their global steps to point_steps[0 .. min(points, cap))
+ *               when point_steps is given.  steps < 1 or val_every < 1: RN_E_RANGE.
+ * rn_ft_run_validated  losses [steps] as rn_ft_run; val_losses [points]: the training loss of the validation set at each point
+ *               (mean cross-entropy + l2_coeff sum(v^2) / 2, what rn_ft_eval reports); val_confusion [points][nc][nc] int32,
+ *               row = label, column = predicted class.  d_val_feats [n_val, ...] and d_val_labels [n_val] are device memory as
+ *               the training set is; n_val may exceed max_batch (chunks of max_batch inside).  Validation never drops.
+ *               The confusion matrix and the loss are reduced on the device (float64 sums in a fixed order, no floating-point
+ *               atomics); the device decides whether a point has strictly more correct predictions than the best so far -- the
+ *               earliest of equal points stays -- and then copies the master parameters aside.  Losses, parameters, gradients
+ *               and Adam slots are byte for byte those of rn_ft_run with the same arguments, and a point with
+ *               g % val_every == 0 gives the same bits however the run is split over calls.
+ *               Errors, checked on the host before anything is enqueued, trainer unchanged: those of rn_ft_run; a null
+ *               argument: RN_E_INVALID; val_every < 1, n_val < 1 or a validation label outside [0, num_classes): RN_E_RANGE;
+ *               a failed allocation of the tables or of the second parameter slab: RN_E_NOMEM.
+ * rn_ft_best    the best point so far: its global step, its number of correct predictions and the size of its validation set
+ *               (each pointer may be NULL).  Trainer state: it lasts across calls.  RN_E_STATE before any point was taken; so
+ *               is rn_ft_read(RN_FT_BEST, ...), which otherwise reads the variable as it was at that point.
+ * rn_ft_last_run_ms covers the whole loop of the last run, validation included. */
+#define RN_FT_BEST 4   /* rn_ft_read: the master parameters as they were at the best validation point */
+RN_API int rn_ft_val_points(const rn_ft* ft, int steps, int val_every, int64_t* point_steps, int cap);
+RN_API int rn_ft_run_validated(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items,
+                               const int32_t* d_index, int batch, int steps, float* losses,
+                               const float* d_val_feats, const int32_t* d_val_labels, int64_t n_val, int val_every,
+                               float* val_losses, int32_t* val_confusion);
+RN_API int rn_ft_best(const rn_ft* ft, int64_t* step, int64_t* correct, int64_t* n_val);
+
 /* ---- dropout while fine-tuning ------------------------------------------------------------------
  * The reference's other regulariser (RoomNet(dropout_enabled=True, dropout_rate=...), network.py:204-206 and :219-221; train.py:37-38
  * carries DROPOUT_RATE = .35): tf.nn.dropout behind every conv block and every dense block.  A trainer applies it at every site

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "rn_ft_create", "rn_ft_create_depth", "rn_ft_depth", "rn_ft_destroy", "rn_ft_run", "rn_ft_eval", "rn_ft_var_count", "rn_ft_var_info", "rn_ft_read",
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
     "rn_ft_set_dropout", "rn_ft_dropout", "rn_ft_dropout_mask",
+    "rn_ft_val_points", "rn_ft_run_validated", "rn_ft_best",
     "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
     "rn_jpeg_last_decode_ms",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
@@ -60,6 +61,7 @@ EXPORTED_SYMBOLS = (
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
 RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V = 0, 1, 2, 3
+RN_FT_BEST = 4                           # the master parameters as they were at the best validation point
 
 # the layers rn_grad_cam_* explains (include/roomnet_hip.h: grad-CAM)
 GRAD_CAM_LAYERS = ("s6.bn", "s7.bn")
@@ -309,6 +311,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_ft_dropout.restype = i32
         lib.rn_ft_dropout_mask.argtypes = [vp, i32, C.c_int64, i32, C.c_int64, vp]
         lib.rn_ft_dropout_mask.restype = i32
+    if hasattr(lib, "rn_ft_run_validated"):
+        lib.rn_ft_val_points.argtypes = [vp, i32, i32, vp, i32]
+        lib.rn_ft_val_points.restype = i32
+        lib.rn_ft_run_validated.argtypes = [vp, vp, vp, C.c_int64, vp, i32, i32, vp, vp, vp, C.c_int64, i32, vp, vp]
+        lib.rn_ft_run_validated.restype = i32
+        lib.rn_ft_best.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.rn_ft_best.restype = i32
     if hasattr(lib, "rn_jpeg_probe"):
         lib.rn_jpeg_probe.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info)]
         lib.rn_jpeg_probe.restype = i32
@@ -1079,6 +1088,41 @@ class Trainer:
             for p in d:
                 self.free(p)
 
+    def val_points(self, steps: int, val_every: int) -> np.ndarray:
+        """The global steps at which ``run_validated(..., steps, ..., val_every)`` would validate from the trainer's current step
+        (``rn_ft_val_points``; ``finetune.validation_steps`` states the same): int64 ``[points]``."""
+        n = self.lib.rn_ft_val_points(self.handle, int(steps), int(val_every), None, 0)
+        _check(self.lib, min(n, 0), "rn_ft_val_points")
+        out = np.empty((n,), np.int64)
+        _check(self.lib, min(self.lib.rn_ft_val_points(self.handle, int(steps), int(val_every), out.ctypes.data, n), 0),
+               "rn_ft_val_points")
+        return out
+
+    def run_validated(self, d_feats: int, d_labels: int, n_items: int, d_index: int, batch: int, steps: int, d_val_feats: int,
+                      d_val_labels: int, n_val: int, val_every: int):
+        """``run`` with the device-resident validation set ``d_val_feats`` / ``d_val_labels`` evaluated on the GPU every
+        ``val_every`` global steps and after the last step, inside the run's one synchronisation (``rn_ft_run_validated``).
+        Returns ``(losses float32 [steps], point_steps int64 [points], val_losses float32 [points], confusion int32 [points, C, C])``;
+        confusion: row = label, column = predicted class.  The best point so far is kept on the trainer (``best``,
+        ``read(RN_FT_BEST)``)."""
+        nc = self.graph.num_classes
+        points = self.val_points(steps, val_every)
+        losses = np.empty((int(steps),), np.float32)
+        val_losses = np.empty((points.size,), np.float32)
+        confusion = np.empty((points.size, nc, nc), np.int32)
+        _check(self.lib, self.lib.rn_ft_run_validated(
+            self.handle, C.c_void_p(d_feats), C.c_void_p(d_labels), int(n_items), C.c_void_p(d_index), int(batch), int(steps),
+            losses.ctypes.data, C.c_void_p(d_val_feats), C.c_void_p(d_val_labels), int(n_val), int(val_every), val_losses.ctypes.data,
+            confusion.ctypes.data), "rn_ft_run_validated")
+        return losses, points, val_losses, confusion
+
+    def best(self) -> Tuple[int, int, int]:
+        """``(step, correct, n_val)`` of the best validation point so far on this trainer (``rn_ft_best``): the earliest point with
+        the most correct predictions.  Raises ``RoomNetLibraryError`` before any point has been taken."""
+        step, correct, n_val = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(self.lib, self.lib.rn_ft_best(self.handle, C.byref(step), C.byref(correct), C.byref(n_val)), "rn_ft_best")
+        return int(step.value), int(correct.value), int(n_val.value)
+
     def eval(self, d_feats: int, n: int, d_labels: Optional[int] = None):
         """Forward only from the current parameters (``rn_ft_eval``): ``(mean_loss or None, probs [n, C], ids [n])``."""
         probs = np.empty((n, self.graph.num_classes), np.float32)
@@ -1111,7 +1155,8 @@ class Trainer:
         return self._vars
 
     def read(self, what: int = RN_FT_PARAM) -> Dict[str, np.ndarray]:
-        """Every trained variable's parameters, last gradient or Adam slot (``rn_ft_read``), in its checkpoint shape."""
+        """Every trained variable's parameters, last gradient or Adam slot, or (``RN_FT_BEST``) its parameters at the best validation
+        point (``rn_ft_read``), in its checkpoint shape."""
         shapes = self.graph.variable_shapes()
         out = {}
         for i, (name, cnt) in enumerate(self.variables()):

@@ -61,6 +61,12 @@
 // a hidden layer's dense adjoint is multiplied by keep scale BEFORE it feeds the d gamma / d beta partials and the ReLU6 mask; dL/dfl
 // gets site 1's factor before stage 9.  The partials' input vectors are the dropped ones.  At depth 3 ft7_drop_kernel writes the
 // minibatch's dropped s6.bn (site 0) in slot order in front of ft7_fwd_kernel: five launches.  rn_ft_eval never drops.
+//
+// Validation inside a run (rn_ft_run_validated; rn_ft_run is the same loop, ft_run_loop, with no points).  Behind every step the
+// schedule names (ft_is_point) the resident validation set goes through the forward-only pass in chunks of max_batch, and on the
+// device ft_val_chunk_kernel adds each chunk to the point's confusion matrix and float64 cross-entropy sum, ft_val_close_kernel
+// writes the point's loss, counts the correct predictions and decides whether the point beats the best so far (strictly more
+// correct), and ft_val_snapshot_kernel then copies the parameter slab aside.  Nothing is synchronised until the run's one read-back.
 #include "rn_dropout.h"
 #include "rn_finetune7.h"
 #include "rn_internal.h"
@@ -554,6 +560,90 @@ __global__ __launch_bounds__(256) void ft_update_kernel(const FtUpdateArgs a) {
     a.P[e] = p - a.lr_t * m / (sqrtf(v) + a.eps);
 }
 
+// ---- validation inside a run (rn_ft_run_validated).  A point is one evaluation of the resident validation set between two steps:
+// per chunk of max_batch items the forward-only item kernel and ft_val_chunk_kernel, then ft_val_close_kernel and
+// ft_val_snapshot_kernel once.  The point's tables are zeroed by one memset at the head of the run.
+constexpr int FT_VAL_NT = 256;
+
+// the best point so far; lives on the device, where the closer decides, and is mirrored to the host after a run's synchronisation
+struct FtBestDev {
+    long long step, correct, n_val;
+    int valid, pad;
+};
+
+// Chunk reducer, one workgroup: the chunk's m items add to the point's confusion matrix (integer atomics) and its cross-entropy sum
+// (float64: thread t sums items t, t + FT_VAL_NT, ... in order, a fixed tree joins the threads, and the chunks are chained in order
+// through *ce -- the same call gives the same bits).
+struct FtValChunkArgs {
+    const int64_t* ids;              // [m] the chunk's argmax (ft_item_kernel, forward only)
+    const double* item_loss;         // [m] its CE terms
+    const int32_t* labels;           // the chunk's labels (checked on the host: inside [0, nc))
+    int m, nc;
+    int32_t* conf;                   // the point's [nc, nc], row = label, column = predicted
+    double* ce;                      // the point's sum so far
+};
+
+__global__ __launch_bounds__(FT_VAL_NT) void ft_val_chunk_kernel(const FtValChunkArgs a) {
+    __shared__ double dred[FT_VAL_NT];
+    const int tid = threadIdx.x;
+    double t = 0.0;
+    for (int i = tid; i < a.m; i += FT_VAL_NT) {
+        t += a.item_loss[i];
+        const int y = a.labels[i], p = static_cast<int>(a.ids[i]);
+        if (y >= 0 && y < a.nc && p >= 0 && p < a.nc) atomicAdd(a.conf + y * a.nc + p, 1);
+    }
+    dred[tid] = t;
+    __syncthreads();
+    for (int s = FT_VAL_NT / 2; s > 0; s >>= 1) {
+        if (tid < s) dred[tid] += dred[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) *a.ce += dred[0];
+}
+
+// Point closer, one workgroup: sum v^2 over the parameter slab in float64 (a fixed strided sum per thread and a fixed tree, as the
+// item kernel forms it), the point's float32 loss, its number of correct predictions (the trace), and whether it beats the best so
+// far: strictly more correct, so the earliest of equal points stays.  *flag tells the snapshot launch behind it.
+struct FtValCloseArgs {
+    const float* P;
+    int n_param, nc;
+    float l2;
+    long long n_val, step;
+    const double* ce;
+    const int32_t* conf;
+    float* loss;
+    int32_t* flag;
+    FtBestDev* best;
+};
+
+__global__ __launch_bounds__(FT_NT) void ft_val_close_kernel(const FtValCloseArgs a) {
+    __shared__ double dred[FT_NT];
+    const int tid = threadIdx.x;
+    double t = 0.0;
+    for (int i = tid; i < a.n_param; i += FT_NT) t += static_cast<double>(a.P[i]) * static_cast<double>(a.P[i]);
+    dred[tid] = t;
+    __syncthreads();
+    for (int s = FT_NT / 2; s > 0; s >>= 1) {
+        if (tid < s) dred[tid] += dred[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *a.loss = static_cast<float>(*a.ce / static_cast<double>(a.n_val) + 0.5 * static_cast<double>(a.l2) * dred[0]);
+        long long correct = 0;
+        for (int c = 0; c < a.nc; ++c) correct += a.conf[c * a.nc + c];
+        const bool beats = !a.best->valid || correct > a.best->correct;
+        *a.flag = beats ? 1 : 0;
+        if (beats) *a.best = FtBestDev{a.step, correct, a.n_val, 1, 0};
+    }
+}
+
+// Snapshot: where the closer in front of it set the point's flag, the parameter slab (a whole number of quads) goes to d_P_best
+__global__ __launch_bounds__(256) void ft_val_snapshot_kernel(const int32_t* flag, const float* P, float* best, int quads) {
+    if (!*flag) return;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < quads) reinterpret_cast<f32x4*>(best)[q] = reinterpret_cast<const f32x4*>(P)[q];
+}
+
 struct FtVarHost {
     std::string name;
     int off = 0, count = 0;
@@ -590,6 +680,12 @@ struct rn_ft {
     uint64_t drop_seed = 0;
     RnDropout drop{};                              // key, threshold and scale; the step is set per launch
     float* d_x6d = nullptr;                        // depth 3: [max_batch, S6, S6, 128], allocated when dropout is first switched on
+    // validation inside a run (rn_ft_run_validated): allocated when the first validated run needs them
+    float* d_P_best = nullptr;                     // the parameter slab at the best point
+    FtBestDev* d_best = nullptr;                   // the best point, decided on the device ...
+    FtBestDev best{};                              // ... and its host copy, read back behind every validated run
+    void* d_val = nullptr;                         // the per-point tables of a run: [cap] ce | [cap] loss | [cap] flag | [cap, nc, nc]
+    int val_cap = 0;
 };
 
 namespace {
@@ -919,6 +1015,7 @@ extern "C" void rn_ft_destroy(rn_ft* ft) {
     for (void* p : ft->allocs) (void)hipFree(p);
     for (void* p : ft->user) (void)hipFree(p);
     if (ft->d_losses) (void)hipFree(ft->d_losses);
+    if (ft->d_val) (void)hipFree(ft->d_val);
     if (ft->ev0) (void)hipEventDestroy(ft->ev0);
     if (ft->ev1) (void)hipEventDestroy(ft->ev1);
     if (ft->stream) (void)hipStreamDestroy(ft->stream);
@@ -1047,24 +1144,131 @@ static int ft_enqueue_pass(rn_ft* ft, const FtItemArgs& a, FtUpdateArgs* u, int 
     return RN_OK;
 }
 
-extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
-                         int steps, float* losses) {
-    if (!ft || !d_feats || !d_labels || !d_index || !losses) {
-        rn_set_error("rn_ft_run: null argument");
-        return RN_E_INVALID;
+// The validation of a run: the resident set, the schedule, and where the results go on the host (rn_ft_run_validated)
+struct FtValidation {
+    const float* d_feats;
+    const int32_t* d_labels;
+    int64_t n;
+    int every;
+    float* losses;                   // [points]
+    int32_t* confusion;              // [points, nc, nc]
+};
+
+// whether a point is taken behind the step that brings the global step to `g`, the last of the run or not
+static bool ft_is_point(int64_t g, int every, bool last) { return last || g % every == 0; }
+
+static int ft_count_points(int64_t g0, int steps, int every, int64_t* point_steps, int cap) {
+    int points = 0;
+    for (int s = 0; s < steps; ++s) {
+        const int64_t g = g0 + s + 1;
+        if (!ft_is_point(g, every, s == steps - 1)) continue;
+        if (point_steps && points < cap) point_steps[points] = g;
+        ++points;
     }
+    return points;
+}
+
+// the pieces of the per-point tables, for `cap` points
+struct FtValTables {
+    double* ce;
+    float* loss;
+    int32_t* flag;
+    int32_t* conf;
+    size_t bytes;
+};
+static FtValTables ft_val_tables(const rn_ft* ft, void* base, int cap) {
+    const size_t n = static_cast<size_t>(cap), cc = static_cast<size_t>(ft->nc) * ft->nc;
+    FtValTables t;
+    char* p = static_cast<char*>(base);
+    t.ce = reinterpret_cast<double*>(p);
+    t.loss = reinterpret_cast<float*>(p + 8 * n);
+    t.flag = reinterpret_cast<int32_t*>(p + 12 * n);
+    t.conf = reinterpret_cast<int32_t*>(p + 16 * n);
+    t.bytes = 16 * n + 4 * n * cc;
+    return t;
+}
+
+// what a validated run needs beside the trainer's own memory; a failed allocation leaves the trainer as it was
+static int ft_val_reserve(rn_ft* ft, int points) {
+    int rc;
+    if (!ft->d_P_best && (rc = ft_zeroed(ft, static_cast<size_t>(ft->n_param), &ft->d_P_best)) != RN_OK) return rc;
+    if (!ft->d_best && (rc = ft_zeroed(ft, 1, &ft->d_best)) != RN_OK) return rc;
+    if (points > ft->val_cap) {
+        void* p = nullptr;
+        const size_t bytes = ft_val_tables(ft, nullptr, points).bytes;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rn_set_error("rn_ft_run_validated: hipMalloc(%zu bytes of validation tables) failed: %s", bytes, hipGetErrorString(e));
+            return RN_E_NOMEM;
+        }
+        if (ft->d_val) (void)hipFree(ft->d_val);   // (ft_check_labels has drained the stream: nothing still reads it)
+        ft->d_val = p;
+        ft->val_cap = points;
+    }
+    return RN_OK;
+}
+
+// One validation point on the trainer's stream, behind the step that made the global step `step`: the set in chunks of max_batch
+// through the forward-only pass, each chunk reduced into the point's tables, then the closer and the snapshot.
+static int ft_enqueue_point(rn_ft* ft, const FtValidation& v, const FtValTables& t, int point, int64_t step) {
+    FtItemArgs a = ft->item;
+    a.feats = v.d_feats;
+    a.labels = v.d_labels;
+    a.index = nullptr;
+    a.l2sum = nullptr;
+    a.probs = ft->d_probs;
+    a.ids = ft->d_ids;
+    int32_t* conf = t.conf + static_cast<size_t>(point) * ft->nc * ft->nc;
+    int rc;
+    for (int64_t i = 0; i < v.n; i += ft->max_batch) {
+        const int m = static_cast<int>(std::min<int64_t>(ft->max_batch, v.n - i));
+        a.base = i;
+        if ((rc = ft_enqueue_pass(ft, a, nullptr, m)) != RN_OK) return rc;
+        const FtValChunkArgs c{ft->d_ids, ft->d_item_loss, v.d_labels + i, m, ft->nc, conf, t.ce + point};
+        hipLaunchKernelGGL(ft_val_chunk_kernel, dim3(1), dim3(FT_VAL_NT), 0, ft->stream, c);
+        RN_CHECK_LAUNCH();
+    }
+    const FtValCloseArgs c{ft->d_P, ft->n_param, ft->nc, ft->cfg.l2_coeff, static_cast<long long>(v.n), static_cast<long long>(step),
+                           t.ce + point, conf, t.loss + point, t.flag + point, ft->d_best};
+    hipLaunchKernelGGL(ft_val_close_kernel, dim3(1), dim3(FT_NT), 0, ft->stream, c);
+    RN_CHECK_LAUNCH();
+    const int quads = ft->n_param / 4;
+    hipLaunchKernelGGL(ft_val_snapshot_kernel, dim3((quads + 255) / 256), dim3(256), 0, ft->stream, t.flag + point, ft->d_P, ft->d_P_best,
+                       quads);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
+// The step loop of rn_ft_run and rn_ft_run_validated (`who` in the messages): the checks, `steps` training passes enqueued back to
+// back, with `v` a validation point behind every step the schedule names, and one synchronisation at the end.
+static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index,
+                       int batch, int steps, float* losses, const FtValidation* v) {
     if (batch < 1 || batch > ft->max_batch) {
-        rn_set_error("rn_ft_run: batch = %d out of range (1..%d)", batch, ft->max_batch);
+        rn_set_error("%s: batch = %d out of range (1..%d)", who, batch, ft->max_batch);
         return RN_E_RANGE;
     }
     if (steps < 1 || n_items < 1) {
-        rn_set_error("rn_ft_run: steps = %d, n_items = %lld", steps, static_cast<long long>(n_items));
+        rn_set_error("%s: steps = %d, n_items = %lld", who, steps, static_cast<long long>(n_items));
+        return RN_E_RANGE;
+    }
+    if (v && (v->every < 1 || v->n < 1)) {
+        rn_set_error("%s: val_every = %d, n_val = %lld", who, v->every, static_cast<long long>(v->n));
         return RN_E_RANGE;
     }
     DeviceGuard guard(ft->device);
     (void)hipGetLastError();
     int rc;
-    if ((rc = ft_check_labels(ft, "rn_ft_run", d_labels, n_items, d_index, static_cast<size_t>(steps) * batch)) != RN_OK) return rc;
+    if ((rc = ft_check_labels(ft, who, d_labels, n_items, d_index, static_cast<size_t>(steps) * batch)) != RN_OK) return rc;
+    FtValTables t{};
+    int points = 0;
+    if (v) {
+        const std::string vwho = std::string(who) + ": validation";
+        if ((rc = ft_check_labels(ft, vwho.c_str(), v->d_labels, v->n, nullptr, 0)) != RN_OK) return rc;
+        points = ft_count_points(ft->cfg.start_step + ft->steps_done, steps, v->every, nullptr, 0);
+        if ((rc = ft_val_reserve(ft, points)) != RN_OK) return rc;
+        t = ft_val_tables(ft, ft->d_val, points);
+    }
     if (steps > ft->losses_cap) {
         // the old buffer and its size go before the allocation that may fail: a failed grow leaves no stale pointer
         if (ft->d_losses) RN_HIP(hipFree(ft->d_losses));
@@ -1086,10 +1290,12 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
     const bool dropping = ft->drop.thr != 0;
     ft->timed = false;
     RN_HIP(hipEventRecord(ft->ev0, ft->stream));
+    if (v) RN_HIP(hipMemsetAsync(ft->d_val, 0, t.bytes, ft->stream));
+    int point = 0;
     for (int s = 0; s < steps; ++s) {
-        const int64_t t = ft->steps_done + 1;
+        const int64_t t1 = ft->steps_done + 1;
         const double lr = ft_learn_rate(ft->cfg, ft->cfg.start_step + ft->steps_done);
-        u.lr_t = static_cast<float>(lr * std::sqrt(1.0 - std::pow(b2, static_cast<double>(t))) / (1.0 - std::pow(b1, static_cast<double>(t))));
+        u.lr_t = static_cast<float>(lr * std::sqrt(1.0 - std::pow(b2, static_cast<double>(t1))) / (1.0 - std::pow(b1, static_cast<double>(t1))));
         u.loss_out = ft->d_losses + s;
         a.base = static_cast<int64_t>(s) * batch;
         if (dropping) {
@@ -1100,11 +1306,68 @@ extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_label
         }
         if ((rc = ft_enqueue_pass(ft, a, &u, batch)) != RN_OK) return rc;
         ++ft->steps_done;
+        if (v) {
+            const int64_t g = ft->cfg.start_step + ft->steps_done;
+            if (ft_is_point(g, v->every, s == steps - 1) && (rc = ft_enqueue_point(ft, *v, t, point++, g)) != RN_OK) return rc;
+        }
     }
     RN_HIP(hipEventRecord(ft->ev1, ft->stream));
     RN_HIP(hipMemcpyAsync(losses, ft->d_losses, static_cast<size_t>(steps) * 4, hipMemcpyDeviceToHost, ft->stream));
+    if (v) {
+        const size_t cc = static_cast<size_t>(ft->nc) * ft->nc;
+        RN_HIP(hipMemcpyAsync(v->losses, t.loss, static_cast<size_t>(points) * 4, hipMemcpyDeviceToHost, ft->stream));
+        RN_HIP(hipMemcpyAsync(v->confusion, t.conf, static_cast<size_t>(points) * cc * 4, hipMemcpyDeviceToHost, ft->stream));
+        RN_HIP(hipMemcpyAsync(&ft->best, ft->d_best, sizeof(FtBestDev), hipMemcpyDeviceToHost, ft->stream));
+    }
     RN_HIP(hipStreamSynchronize(ft->stream));
     ft->timed = true;
+    return RN_OK;
+}
+
+extern "C" int rn_ft_run(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index, int batch,
+                         int steps, float* losses) {
+    if (!ft || !d_feats || !d_labels || !d_index || !losses) {
+        rn_set_error("rn_ft_run: null argument");
+        return RN_E_INVALID;
+    }
+    return ft_run_loop(ft, "rn_ft_run", d_feats, d_labels, n_items, d_index, batch, steps, losses, nullptr);
+}
+
+extern "C" int rn_ft_run_validated(rn_ft* ft, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index,
+                                   int batch, int steps, float* losses, const float* d_val_feats, const int32_t* d_val_labels,
+                                   int64_t n_val, int val_every, float* val_losses, int32_t* val_confusion) {
+    if (!ft || !d_feats || !d_labels || !d_index || !losses || !d_val_feats || !d_val_labels || !val_losses || !val_confusion) {
+        rn_set_error("rn_ft_run_validated: null argument");
+        return RN_E_INVALID;
+    }
+    const FtValidation v{d_val_feats, d_val_labels, n_val, val_every, val_losses, val_confusion};
+    return ft_run_loop(ft, "rn_ft_run_validated", d_feats, d_labels, n_items, d_index, batch, steps, losses, &v);
+}
+
+extern "C" int rn_ft_val_points(const rn_ft* ft, int steps, int val_every, int64_t* point_steps, int cap) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    if (steps < 1 || val_every < 1) {
+        rn_set_error("rn_ft_val_points: steps = %d, val_every = %d", steps, val_every);
+        return RN_E_RANGE;
+    }
+    return ft_count_points(ft->cfg.start_step + ft->steps_done, steps, val_every, point_steps, cap);
+}
+
+extern "C" int rn_ft_best(const rn_ft* ft, int64_t* step, int64_t* correct, int64_t* n_val) {
+    if (!ft) {
+        rn_set_error("null trainer");
+        return RN_E_INVALID;
+    }
+    if (!ft->best.valid) {
+        rn_set_error("rn_ft_best: no validation point has been taken on this trainer");
+        return RN_E_STATE;
+    }
+    if (step) *step = ft->best.step;
+    if (correct) *correct = ft->best.correct;
+    if (n_val) *n_val = ft->best.n_val;
     return RN_OK;
 }
 
@@ -1180,10 +1443,14 @@ extern "C" int rn_ft_read(rn_ft* ft, int what, int var, float* out, size_t cap) 
         rn_set_error("rn_ft_read: bad argument (variable %d)", var);
         return RN_E_RANGE;
     }
+    if (what == RN_FT_BEST && !ft->best.valid) {
+        rn_set_error("rn_ft_read: RN_FT_BEST before any validation point has been taken on this trainer");
+        return RN_E_STATE;
+    }
     const float* src = what == RN_FT_PARAM ? ft->d_P : what == RN_FT_GRAD ? ft->d_G : what == RN_FT_ADAM_M ? ft->d_M :
-                       what == RN_FT_ADAM_V ? ft->d_V : nullptr;
+                       what == RN_FT_ADAM_V ? ft->d_V : what == RN_FT_BEST ? ft->d_P_best : nullptr;
     if (!src) {
-        rn_set_error("rn_ft_read: what = %d is none of RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V", what);
+        rn_set_error("rn_ft_read: what = %d is none of RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V, RN_FT_BEST", what);
         return RN_E_INVALID;
     }
     const FtVarHost& v = ft->vars[var];

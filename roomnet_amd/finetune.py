@@ -1,5 +1,5 @@
 """Host side of fine-tuning the last conv stages and the dense head (``RoomNet.fine_tune``, C ABI ``rn_ft_*``): which variables are
-trained, the learning-rate schedule, the minibatch order and a NumPy statement of the Adam rule, and the dropout stream (``philox4x32``, ``dropout_keep``): the product's statement of the masks the kernels
+trained, the learning-rate schedule, the minibatch order, the validation points of a run and a NumPy statement of the Adam rule, and the dropout stream (``philox4x32``, ``dropout_keep``): the product's statement of the masks the kernels
 recompute, as ``jpegenc.py`` is for the encoder.  Pure host code; the mathematics is stated once in the headers of
 ``csrc/rn_finetune.hip``, ``csrc/rn_finetune7.hip`` and ``csrc/rn_dropout.h``.
 
@@ -85,6 +85,19 @@ def epoch_indices(n_items, batch, steps, seed):
             rng.shuffle(order)
         out[s] = order[k * batch:(k + 1) * batch]
     return out
+
+
+def validation_steps(step, steps, val_every) -> List[int]:
+    """The global steps at which a run of ``steps`` steps that starts at global step ``step`` validates (``rn_ft_val_points``):
+    every ``g`` in ``(step, step + steps]`` with ``g % val_every == 0`` -- the reference's ``train_iter % SAVE_FREQ == 0 and
+    train_iter > start_step`` (train.py:134) -- and ``step + steps`` itself if that is none of them."""
+    step, steps, val_every = int(step), int(steps), int(val_every)
+    if step < 0 or steps < 1 or val_every < 1:
+        raise ValueError("validation_steps: step %d, steps %d, val_every %d" % (step, steps, val_every))
+    points = [g for g in range(step + 1, step + steps + 1) if g % val_every == 0]
+    if not points or points[-1] != step + steps:
+        points.append(step + steps)
+    return points
 
 
 def adam_update(param, grad, m, v, t, lr, beta1=ADAM_BETA1, beta2=ADAM_BETA2, epsilon=ADAM_EPSILON):

@@ -374,14 +374,20 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=
 
 
 def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2,
-                        gpu_decode=False, dropout_rate=None):
+                        gpu_decode=False, dropout_rate=None, val_every=None, keep="last", stats_fpath=None):
     """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
     infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
     batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
     features.  ``val_list_fpath``: a second list evaluated after the last step.  ``depth=3`` trains the whole last conv block on
     cached ``s6.bn`` (1.08 MB per image at 224, against 28 KB at depth 2).  Returns what ``fine_tune`` returns.  ``gpu_decode``:
     the feature extraction decodes baseline JPEG files on the GPU (``RoomNet.prepare_files``); same features.
-    ``dropout_rate``: passed to ``fine_tune`` (dropout at every site at or behind the cached feature)."""
+    ``dropout_rate``: passed to ``fine_tune`` (dropout at every site at or behind the cached feature).
+    ``val_every``, ``keep``: passed to ``fine_tune`` (validation on the GPU every ``val_every`` steps; ``keep="best"`` keeps the best
+    point's variables).  ``stats_fpath``: every point's ``step``, ``accuracy``, ``precisions``, ``recalls`` and ``f-scores`` are
+    appended to that JSON file as train.py:129-155 keeps ``all_train_stats.json`` (``metrics.append_stats``), so the reference's
+    ``plotter.py`` reads it as it is; needs ``val_every``."""
+    if stats_fpath is not None and val_every is None:
+        raise ValueError("fine_tune_from_list: stats_fpath records validation points: pass val_every= (and val_list_fpath=)")
     def features_of(path):
         fpaths, labels, _n = read_fpaths(path)
         feats, kept, pending = [], [], []
@@ -416,7 +422,12 @@ def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_f
 
     feats, labels = features_of(list_fpath)
     val = features_of(val_list_fpath) if val_list_fpath else None
-    return nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val, depth=depth, dropout_rate=dropout_rate)
+    out = nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val, depth=depth, dropout_rate=dropout_rate,
+                       val_every=val_every, keep=keep)
+    if stats_fpath is not None:
+        from . import metrics
+        metrics.append_stats(stats_fpath, out["val_history"])
+    return out
 
 
 if __name__ == '__main__':

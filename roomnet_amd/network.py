@@ -635,7 +635,8 @@ class RoomNet:
                 raise ValueError("extract_features takes uint8 images (or integral values in [0, 255]), got %s" % im.dtype)
         return self._engine().features_u8(im, depth=depth)
 
-    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None, dropout_rate=None):
+    def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None, dropout_rate=None, val_every=None,
+                  keep="last"):
         """Train stages 8 and 9 and the dense head on cached features, on the GPU (``rn_ft_*``; not the reference's whole-network
         ``train_step``): stages 0-7 stay as loaded, every BN keeps its moving statistics and trains gamma and beta (the
         reference's shipped configuration, train.py:40-41), Adam with the constructor's ``learn_rate``, ``num_steps`` (decay),
@@ -653,9 +654,26 @@ class RoomNet:
         whatever the constructor's ``dropout_enabled``, with ``seed`` as the dropout seed.  The reference's dropout behind the frozen
         conv blocks upstream of the cache cannot be applied to cached features, which is why the opt-in is explicit: a net
         constructed with ``dropout_enabled=True`` raises ``ValueError`` unless the argument is given, e.g.
-        ``nn.fine_tune(f, y, steps, dropout_rate=nn.dropout_rate)``.  ``val`` and inference never drop."""
-        from . import finetune
-        from ._capi import Trainer
+        ``nn.fine_tune(f, y, steps, dropout_rate=nn.dropout_rate)``.  ``val`` and inference never drop.
+        ``val_every=k`` (needs ``val``) validates on the GPU inside the training run, as the reference's loop does every
+        ``SAVE_FREQ`` steps (train.py:134-155): after every global step that is a multiple of ``k`` and after the last step
+        (``finetune.validation_steps``), with no host synchronisation in between (``rn_ft_run_validated``).  The result then also
+        holds ``"val_history"``, one dict per point with the reference's ``'step'``, ``'accuracy'``, ``'precisions'``,
+        ``'recalls'``, ``'f-scores'`` (``metrics.stats_from_confusion``) plus ``'loss'`` and ``'confusion'`` (int32 ``[C, C]``, row =
+        label), and ``"best_step"``: the earliest point with the most correct predictions; ``"val"`` is the last point's.
+        ``keep="best"`` writes that point's variables back instead of the last step's (``self.step`` advances by ``steps`` either
+        way); any other ``keep`` than ``"last"`` or ``"best"`` raises ``ValueError``."""
+        from . import finetune, metrics
+        from ._capi import RN_FT_BEST, RN_FT_PARAM, Trainer
+        if keep not in ("last", "best"):
+            raise ValueError("fine_tune: keep = %r is neither 'last' nor 'best'" % (keep,))
+        if val_every is not None:
+            if isinstance(val_every, bool) or not isinstance(val_every, (int, np.integer)) or val_every < 1:
+                raise ValueError("fine_tune: val_every = %r is not a positive number of steps" % (val_every,))
+            if val is None:
+                raise ValueError("fine_tune: val_every = %d needs a validation set: pass val=(features, labels)" % val_every)
+        elif keep == "best":
+            raise ValueError("fine_tune: keep='best' needs validation points: pass val= and val_every=")
         if dropout_rate is None:
             if self.dropout_enabled:
                 raise ValueError("fine_tune: dropout on the GPU path covers the sites at or behind the cached feature only and is "
@@ -693,22 +711,42 @@ class RoomNet:
                      learn_rate=self.learn_rate, num_steps=self.num_steps, start_step=self.step,
                      l2_coeff=self.l2_regularizer_coeff, depth=depth, dropout_rate=dropout_rate or 0.0,
                      dropout_seed=int(seed) if dropout_rate else 0)
+        extra = {}
         try:
-            losses = tr.run_host(feats, labels, index)
             out_val = None
-            if val is not None:
-                vf, vl = val
-                vl = np.ascontiguousarray(vl, np.int32).reshape(-1)
-                loss, _probs, ids = tr.eval_host(vf, vl)
-                out_val = (loss, float(np.mean(ids == vl)))
-            new = tr.read()
+            if val_every is not None:
+                vf = np.ascontiguousarray(val[0], np.float32)
+                vl = np.ascontiguousarray(val[1], np.int32).reshape(-1)
+                if vf.ndim != 4 or vf.shape[1:] != shape or vf.shape[0] != vl.shape[0] or vf.shape[0] < 1:
+                    raise ValueError("fine_tune: validation features %s and labels %s do not form [N, %d, %d, %d] and [N] (depth %d)"
+                                     % (vf.shape, vl.shape, shape[0], shape[1], shape[2], depth))
+                d = [tr.upload(feats), tr.upload(labels), tr.upload(index), tr.upload(vf), tr.upload(vl)]
+                losses, points, val_losses, confusion = tr.run_validated(d[0], d[1], feats.shape[0], d[2], index.shape[1],
+                                                                         index.shape[0], d[3], d[4], vf.shape[0], val_every)
+                history = []
+                for g, vloss, cm in zip(points, val_losses, confusion):
+                    entry = {"step": int(g), "loss": float(vloss), "confusion": cm.copy()}
+                    entry.update((k, v) for k, v in metrics.stats_from_confusion(cm).items() if k != "support")
+                    history.append(entry)
+                extra = {"val_history": history, "best_step": tr.best()[0]}
+                out_val = (history[-1]["loss"], history[-1]["accuracy"])
+            else:
+                losses = tr.run_host(feats, labels, index)
+                if val is not None:
+                    vf, vl = val
+                    vl = np.ascontiguousarray(vl, np.int32).reshape(-1)
+                    loss, _probs, ids = tr.eval_host(vf, vl)
+                    out_val = (loss, float(np.mean(ids == vl)))
+            new = tr.read(RN_FT_BEST if keep == "best" else RN_FT_PARAM)
             step = tr.step_count()
         finally:
             tr.close()
         self.set_variables(new)
         self.step = step
-        return {"losses": losses, "step": step, "val": out_val,
-                "learn_rate": finetune.learn_rate_at(step, self.learn_rate, self.num_steps)}
+        out = {"losses": losses, "step": step, "val": out_val,
+               "learn_rate": finetune.learn_rate_at(step, self.learn_rate, self.num_steps)}
+        out.update(extra)
+        return out
 
     def train_step(self, x_in, y):
         raise NotImplementedError("training (network.py:158-170) is out of scope of the MI355X inference path")

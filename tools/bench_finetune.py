@@ -13,8 +13,12 @@ dropout off beside the step with dropout on (rn_ft_set_dropout) -- and, with --l
 build, a parent-commit build for instance -- and states whether this build's dropout-off range overlaps the other build's.  With
 --trace-run / --summarise it is the five launches of a depth-3 step with dropout (ft7_drop_kernel in front) that are traced.
 
+--val-every K measures what a validation point costs at batch 45 / 224, both depths and validation sets of 256 and 2048 items: inside
+the run (rn_ft_run_validated) and the way there was before, K steps of rn_ft_run and an rn_ft_eval from the host in turn.
+
     python tools/bench_finetune.py [--depth 3] [--steps 200] [--runs 5] [--steps-only] [--lib PATH]
     python tools/bench_finetune.py --dropout 0.35 [--lib PARENT_BUILD.so] [--steps 200] [--runs 7]
+    python tools/bench_finetune.py --val-every 10 [--steps 200] [--runs 5] [--out profiles/finetune_validate_timing.json]
     rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py [--depth 3] --trace-run
     python tools/bench_finetune.py [--depth 3] --summarise DIR/.../kt_kernel_trace.csv [--out profiles/finetune_kernel_stats.txt]
 """
@@ -110,6 +114,69 @@ def dropout_case(side, batch, steps, runs, depth, rate, lib=None):
         out["on_inside_off_range"] = bool(out["off"]["us_per_step_min"] <= out["on"]["us_per_step"] <= out["off"]["us_per_step_max"])
         if depth == 3:
             out["ft7_drop_kernel_bytes"] = 2 * batch * g.stages[-4].out_side ** 2 * g.stages[-3].cin * 4
+        return out
+    finally:
+        for tr, _ in trainers.values():
+            tr.close()
+
+
+VAL_SIZES = (256, 2048)
+VAL_MAX_BATCH = 256                              # the chunk of an evaluation pass: what RoomNet.fine_tune gives its trainer
+
+
+def validate_case(side, batch, steps, runs, depth, n_val, val_every):
+    """What a validation point costs at ``val_every``: (a) inside the run (rn_ft_run_validated) and (b) the only way there was
+    before, ``val_every`` steps of rn_ft_run and an rn_ft_eval from the host in turn -- each as the host's wall time of the whole
+    arm minus that of the same steps in one plain rn_ft_run, per point.  One trainer per arm on the same data, a warm-up round,
+    then ``runs`` rounds in which every arm runs once, in an order that rotates."""
+    from roomnet_amd import _capi, finetune
+    steps -= steps % val_every                                      # every run then has steps / val_every points, wherever it starts
+    points = steps // val_every
+    g, w = _weights(side)
+    n_items = n_items_of(side, depth)
+    feats, labels = _data(g, n_items, depth)
+    index = finetune.epoch_indices(n_items, batch, steps, seed=1)
+    reps = -(-n_val // n_items)
+    vfeats, vlabels = np.concatenate([feats] * reps)[:n_val], np.concatenate([labels] * reps)[:n_val]
+    arms = ("plain", "validated", "alternating")
+    trainers, ms, dev = {}, {a: [] for a in arms}, {a: [] for a in ("plain", "validated")}
+    try:
+        for name in arms:
+            tr = _capi.Trainer(g, w, device=0, max_batch=VAL_MAX_BATCH, learn_rate=2e-4, l2_coeff=0.06, depth=depth)
+            d = [tr.upload(feats), tr.upload(labels), tr.upload(index)]
+            d += [] if name == "plain" else [tr.upload(vfeats), tr.upload(vlabels)]
+            trainers[name] = (tr, d)
+        del feats, vfeats
+
+        def run(name):
+            tr, d = trainers[name]
+            t0 = time.perf_counter()
+            if name == "plain":
+                tr.run(d[0], d[1], n_items, d[2], batch, steps)
+            elif name == "validated":
+                tr.run_validated(d[0], d[1], n_items, d[2], batch, steps, d[3], d[4], n_val, val_every)
+            else:
+                for p in range(points):
+                    tr.run(d[0], d[1], n_items, d[2] + 4 * batch * val_every * p, batch, val_every)
+                    tr.eval(d[3], n_val, d[4])
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            if name in dev:
+                dev[name].append(tr.last_run_ms())
+
+        for r in range(runs + 1):                                   # the first round is the warm-up
+            k = r % len(arms)
+            for name in arms[k:] + arms[:k]:
+                run(name)
+        med = {a: statistics.median(v[1:]) for a, v in ms.items()}
+        out = {"side": side, "batch": batch, "depth": depth, "n_val": n_val, "val_every": val_every, "steps_per_run": steps,
+               "points_per_run": points, "runs": runs, "eval_chunk": VAL_MAX_BATCH}
+        for a in arms:
+            out[a + "_wall_ms"] = {"median": round(med[a], 3), "min": round(min(ms[a][1:]), 3), "max": round(max(ms[a][1:]), 3)}
+        out["inside_run_us_per_point"] = round((med["validated"] - med["plain"]) * 1e3 / points, 1)
+        out["alternating_us_per_point"] = round((med["alternating"] - med["plain"]) * 1e3 / points, 1)
+        out["inside_run_device_us_per_point"] = round((statistics.median(dev["validated"][1:]) - statistics.median(dev["plain"][1:]))
+                                                      * 1e3 / points, 1)
+        out["inside_run_below_alternating"] = bool(out["inside_run_us_per_point"] < out["alternating_us_per_point"])
         return out
     finally:
         for tr, _ in trainers.values():
@@ -247,6 +314,8 @@ def main():
     ap.add_argument("--lib", help="measure this build of libroomnet_hip.so instead of the package's")
     ap.add_argument("--dropout", type=float, default=0.0, metavar="RATE",
                     help="the dropout-on arm beside the dropout-off arm (and beside --lib's dropout-off arm) at both depths")
+    ap.add_argument("--val-every", type=int, default=0, metavar="K",
+                    help="what a validation point costs inside the run (rn_ft_run_validated) and from the host (rn_ft_run / rn_ft_eval)")
     args = ap.parse_args()
     if not args.summarise:
         import torch  # noqa: F401  (before libroomnet_hip.so is loaded: one HIP runtime in the process, torch's)
@@ -258,6 +327,18 @@ def main():
         return
     if args.trace_run:
         trace_run(args.depth, args.dropout)
+        return
+    if args.val_every:
+        doc = {"what": "validation inside a fine-tuning run at batch 45 / 224, val_every %d, both depths, n_val 256 and 2048, the arms "
+                       "alternating run by run in one session: host wall time of (a) rn_ft_run_validated and of (b) rn_ft_run(%d "
+                       "steps) and rn_ft_eval in turn from the host, each minus the same steps in one plain rn_ft_run, per point"
+                       % (args.val_every, args.val_every),
+               "cases": [validate_case(s, b, args.steps, args.runs, depth, n_val, args.val_every)
+                         for depth in (2, 3) for s, b in DROP_CASES for n_val in VAL_SIZES]}
+        text = json.dumps(doc, indent=1)
+        if args.out:
+            open(args.out, "w").write(text + "\n")
+        print(json.dumps(doc))
         return
     if args.dropout:
         print(json.dumps({"what": "fine-tuning with dropout: us per Adam step at batch 45 / 224, dropout off, dropout on at rate %g and "

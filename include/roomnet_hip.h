@@ -17,6 +17,12 @@
  *   - a handle is bound to one device and one stream; calls on one handle must
  *     be serialised by the caller (the reference is single-threaded,
  *     infer.py:79-82); distinct handles are independent.
+ *   - the asynchronous calls of one handle that are in flight together share one
+ *     stream: after rn_set_stream / rn_set_stream_null, rn_sync (on the old stream)
+ *     comes before the next call.  The image stages (batched resize, JPEG decode,
+ *     overlay + encode, heat maps) double-buffer their per-batch tables behind
+ *     events, but their plane and coefficient scratch is single and ordered by the
+ *     stream alone.
  *   - tensors are NHWC, C-contiguous.  Images are [n, S, S, 3].
  */
 #ifndef ROOMNET_HIP_H
@@ -243,7 +249,8 @@ RN_API int rn_forward_f32_device(rn_handle* h, const float* d_rgb_nhwc, int n, f
 RN_API int rn_crop_resize_u8_device(rn_handle* h, const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst_batch, int index);
 /* The same for a BATCH of device-resident images in ONE launch: image i (d_srcs[i], heights[i] x widths[i] BGR uint8, HWC, any
  * sizes) is centre-cropped and resized into slot i of d_dst_batch ([n, S, S, 3]).  Asynchronous on the handle's stream;
- * n <= max_batch.  network.py:149-152 for a whole directory's worth of decoded images at once. */
+ * n <= max_batch.  The arrays are copied before the call returns; back-to-back calls without a sync are fine (the batch table
+ * is double-buffered behind events).  network.py:149-152 for a whole directory's worth of decoded images at once. */
 RN_API int rn_crop_resize_batch_u8_device(rn_handle* h, const uint8_t* const* d_srcs, const int* heights, const int* widths, int n,
                                           uint8_t* d_dst_batch);
 /* infer.py:79-82 for a whole batch: n host images of individual sizes heights[i] x widths[i] (BGR uint8 HWC) are
@@ -287,7 +294,9 @@ RN_API int rn_sync(rn_handle* h);
  *                         rn_sync) go up on the handle's copy stream, then TWO launches for the whole batch on the handle's
  *                         stream -- inverse DCT into planar Y / Cb / Cr scratch, then upsampling + colour + interleave -- write image
  *                         i as BGR uint8 HWC, height x width x 3 tightly packed, to d_bgr[i]: the layout
- *                         rn_crop_resize_batch_u8_device takes.  Asynchronous.  n outside [1, max_batch]: RN_E_RANGE; an image
+ *                         rn_crop_resize_batch_u8_device takes.  Asynchronous; back-to-back calls without a sync are fine (the
+ *                         batch table is double-buffered behind events, the scratch is ordered by the streams).
+ *                         n outside [1, max_batch]: RN_E_RANGE; an image
  *                         whose info is not a supported one as rn_jpeg_probe fills it: RN_E_INVALID; the handle stays usable.
  * rn_classify_jpegs       rn_classify_images_u8 for coefficient images: decoded into scratch the handle owns (allocated by the
  *                         first call, grown as needed, freed by rn_destroy), centre-cropped, resized and classified; probs and

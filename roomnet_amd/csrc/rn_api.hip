@@ -633,7 +633,6 @@ extern "C" void rn_destroy(rn_handle* h) {
         if (e) (void)hipEventDestroy(e);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->d_raw) (void)hipFree(h->d_raw);
-    if (h->d_items) (void)hipFree(h->d_items);
     for (auto& sl : h->slots) {
         if (sl.d_in) (void)hipFree(sl.d_in);
         if (sl.d_probs) (void)hipFree(sl.d_probs);
@@ -1048,9 +1047,8 @@ extern "C" int rn_collect(rn_handle* h, int slot, float* probs, int64_t* ids) {
 }
 
 // ---- caller-side image pipeline on the device (network.py:137-156)
-namespace {
 // network.py:137-146: the centred square window of an h x w image (abs((w - h) // 2) with Python floor division)
-void center_crop_window(int hh, int ww, int* x0, int* y0, int* side) {
+void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side) {
     if (hh == ww) {
         *x0 = *y0 = 0;
         *side = hh;
@@ -1065,7 +1063,12 @@ void center_crop_window(int hh, int ww, int* x0, int* y0, int* side) {
         *side = ww;
     }
 }
-}  // namespace
+// ... of a packed BGR image at `src`
+rn_window rn_center_window(const uint8_t* src, int hh, int ww) {
+    int x0, y0, side;
+    rn_center_crop_window(hh, ww, &x0, &y0, &side);
+    return {src + (static_cast<int64_t>(y0) * ww + x0) * 3, side, static_cast<int64_t>(ww) * 3};
+}
 
 extern "C" int rn_crop_resize_u8_device(rn_handle* h, const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst_batch,
                                         int index) {
@@ -1075,30 +1078,40 @@ extern "C" int rn_crop_resize_u8_device(rn_handle* h, const uint8_t* d_src, int 
         return RN_E_INVALID;
     }
     DeviceGuard guard(h->device);
-    int x0, y0, side;
-    center_crop_window(src_h, src_w, &x0, &y0, &side);
+    const rn_window w = rn_center_window(d_src, src_h, src_w);
     const int S = h->im_side;
-    return rn_launch_resize_u8(h->stream, d_src + (static_cast<int64_t>(y0) * src_w + x0) * 3, side, side,
-                               static_cast<int64_t>(src_w) * 3, d_dst_batch + static_cast<int64_t>(index) * S * S * 3, S, S);
+    return rn_launch_resize_u8(h->stream, w.src, w.side, w.side, w.row_bytes, d_dst_batch + static_cast<int64_t>(index) * S * S * 3, S, S);
 }
 
-// the device table of a batched resize (max_batch entries), allocated at the first use
-static int ensure_items(rn_handle* h) {
-    if (h->d_items) return RN_OK;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, static_cast<size_t>(h->max_batch) * sizeof(rn_resize_item));
-    if (e != hipSuccess) {
-        rn_set_error("hipMalloc(resize table) failed: %s", hipGetErrorString(e));
-        return RN_E_NOMEM;
+int rn_check_batch(const char* who, const rn_handle* h, const void* ptr, int n) {
+    if (!h || !ptr) {
+        rn_set_error("%s: null argument", who);
+        return RN_E_INVALID;
     }
-    h->d_items = static_cast<rn_resize_item*>(p);
-    h->items_host.resize(static_cast<size_t>(h->max_batch));
+    if (n < 1 || n > h->max_batch) {
+        rn_set_error("%s: %d images out of range (1..%d)", who, n, h->max_batch);
+        return RN_E_RANGE;
+    }
     return RN_OK;
 }
 
-// (for rn_jpeg.hip, whose decoded images take the same crop + resize launch)
-void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side) { center_crop_window(hh, ww, x0, y0, side); }
-int rn_ensure_resize_items(rn_handle* h) { return ensure_items(h); }
+int rn_enqueue_resize_batch(rn_handle* h, int n, uint8_t* d_dst_batch, const std::function<rn_window(int)>& window) {
+    int rc, set;
+    if (!h->items_turn.done[0]) {      // the first use: two sets of max_batch entries (a failure here leaves what rn_destroy frees)
+        for (auto& t : h->items)
+            if (!t.cap && (rc = t.alloc(static_cast<size_t>(h->max_batch))) != RN_OK) return rc;
+        if ((rc = h->items_turn.create()) != RN_OK) return rc;
+    }
+    if ((rc = h->items_turn.acquire(&set)) != RN_OK) return rc;
+    const rn_table<rn_resize_item>& t = h->items[set];
+    for (int i = 0; i < n; ++i) {
+        const rn_window w = window(i);
+        rn_resize_item_fill(&t.host[i], w.src, w.side, w.side, w.row_bytes, h->im_side);
+    }
+    if ((rc = t.upload(static_cast<size_t>(n), h->stream)) != RN_OK) return rc;
+    if ((rc = rn_launch_resize_batch_u8(h->stream, t.dev, n, d_dst_batch, h->im_side)) != RN_OK) return rc;
+    return h->items_turn.retire(h->stream);
+}
 
 extern "C" int rn_crop_resize_batch_u8_device(rn_handle* h, const uint8_t* const* d_srcs, const int* heights, const int* widths, int n,
                                               uint8_t* d_dst_batch) {
@@ -1106,23 +1119,13 @@ extern "C" int rn_crop_resize_batch_u8_device(rn_handle* h, const uint8_t* const
         rn_set_error("rn_crop_resize_batch_u8_device: bad argument (%d images, max_batch %d)", n, h ? h->max_batch : 0);
         return RN_E_INVALID;
     }
-    DeviceGuard guard(h->device);
-    int rc = ensure_items(h);
-    if (rc != RN_OK) return rc;
-    // (the host copy of the table may be rewritten at once: a hipMemcpyAsync out of pageable memory returns when its source has been
-    //  read into the runtime's staging buffer -- the property rn_group_forward_u8's upload threads rely on too)
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (!d_srcs[i] || heights[i] < 1 || widths[i] < 1) {
             rn_set_error("rn_crop_resize_batch_u8_device: image %d is empty", i);
             return RN_E_INVALID;
         }
-        int x0, y0, side;
-        center_crop_window(heights[i], widths[i], &x0, &y0, &side);
-        rn_resize_item_fill(&h->items_host[i], d_srcs[i] + (static_cast<int64_t>(y0) * widths[i] + x0) * 3, side, side,
-                            static_cast<int64_t>(widths[i]) * 3, h->im_side);
-    }
-    RN_HIP(hipMemcpyAsync(h->d_items, h->items_host.data(), static_cast<size_t>(n) * sizeof(rn_resize_item), hipMemcpyHostToDevice, h->stream));
-    return rn_launch_resize_batch_u8(h->stream, h->d_items, n, d_dst_batch, h->im_side);
+    DeviceGuard guard(h->device);
+    return rn_enqueue_resize_batch(h, n, d_dst_batch, [&](int i) { return rn_center_window(d_srcs[i], heights[i], widths[i]); });
 }
 
 extern "C" int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images, const int* heights, const int* widths, int n,
@@ -1134,7 +1137,7 @@ extern "C" int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images,
         return RN_E_INVALID;
     }
     DeviceGuard guard(h->device);
-    // one staging buffer for the raw images, grown to the batch's total size: uploads and resize launches are queued
+    // one staging buffer for the raw images, grown to the batch's total size: uploads and the resize launch are queued
     // on the handle's stream back to back
     // (only the centred square window of each image crosses PCIe: a 1920x1080 frame uploads 1080x1080)
     size_t total = 0;
@@ -1146,39 +1149,26 @@ extern "C" int rn_classify_images_u8(rn_handle* h, const uint8_t* const* images,
         const size_t side = static_cast<size_t>(heights[i] < widths[i] ? heights[i] : widths[i]);
         total += side * side * 3;
     }
-    if (total > h->raw_cap) {
-        if (h->d_raw) (void)hipFree(h->d_raw);
-        h->d_raw = nullptr;
-        h->raw_cap = 0;
-        void* p = nullptr;
-        const size_t cap = total + total / 4;
-        hipError_t e = hipMalloc(&p, cap);
-        if (e != hipSuccess) {
-            rn_set_error("hipMalloc(%zu bytes of image staging) failed: %s", cap, hipGetErrorString(e));
-            return RN_E_NOMEM;
-        }
-        h->d_raw = static_cast<uint8_t*>(p);
-        h->raw_cap = cap;
-    }
+    if ((rc = rn_grow_scratch(h, &h->d_raw, &h->raw_cap, total, "image staging")) != RN_OK) return rc;
     size_t off = 0;
-    const int S = h->im_side;
-    if ((rc = ensure_items(h)) != RN_OK) return rc;
     for (int i = 0; i < n; ++i) {
-        int x0, y0, side;
-        center_crop_window(heights[i], widths[i], &x0, &y0, &side);
-        const size_t row = static_cast<size_t>(side) * 3, bytes = row * side;
-        const uint8_t* win = images[i] + (static_cast<size_t>(y0) * widths[i] + x0) * 3;
-        if (side == widths[i])
-            RN_HIP(hipMemcpyAsync(h->d_raw + off, win, bytes, hipMemcpyHostToDevice, h->stream));
+        const rn_window w = rn_center_window(images[i], heights[i], widths[i]);
+        const size_t row = static_cast<size_t>(w.side) * 3;
+        if (w.side == widths[i])
+            RN_HIP(hipMemcpyAsync(h->d_raw + off, w.src, row * w.side, hipMemcpyHostToDevice, h->stream));
         else
-            RN_HIP(hipMemcpy2DAsync(h->d_raw + off, row, win, static_cast<size_t>(widths[i]) * 3, row, side,
-                                    hipMemcpyHostToDevice, h->stream));
-        rn_resize_item_fill(&h->items_host[i], h->d_raw + off, side, side, static_cast<int64_t>(row), S);
-        off += bytes;
+            RN_HIP(hipMemcpy2DAsync(h->d_raw + off, row, w.src, static_cast<size_t>(w.row_bytes), row, w.side, hipMemcpyHostToDevice, h->stream));
+        off += row * w.side;
     }
-    // ONE resize launch for the batch (the crop windows' table goes up behind the images)
-    RN_HIP(hipMemcpyAsync(h->d_items, h->items_host.data(), static_cast<size_t>(n) * sizeof(rn_resize_item), hipMemcpyHostToDevice, h->stream));
-    if ((rc = rn_launch_resize_batch_u8(h->stream, h->d_items, n, h->d_in_u8, S)) != RN_OK) return rc;
+    // ONE resize launch for the batch (the packed windows' table goes up behind the images)
+    off = 0;
+    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) {
+        const int side = heights[i] < widths[i] ? heights[i] : widths[i];
+        const rn_window w = {h->d_raw + off, side, static_cast<int64_t>(side) * 3};
+        off += static_cast<size_t>(side) * side * 3;
+        return w;
+    });
+    if (rc != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
     return rn_results_to_host(h, n, probs, ids);
 }

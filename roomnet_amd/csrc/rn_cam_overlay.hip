@@ -101,21 +101,13 @@ __global__ __launch_bounds__(256) void cam_blend_kernel(const CamDev* __restrict
     }
 }
 
-// One set of the per-batch tables and maxima.  A call fills the set the call before the previous one used, after waiting for that
-// call's launches (`done`), as the encode's sets are (rn_jpeg_enc.hip).
-struct CamSlot {
-    CamDev* h_desc = nullptr;          // page-locked, [max_batch]
-    CamDev* d_desc = nullptr;
-    unsigned long long* d_max = nullptr;      // [max_batch]
-    hipEvent_t done = nullptr;
-    bool used = false;
-};
-
+// The per-batch tables and maxima, two sets behind one rotation (rn_batch_table.h).
 struct CamState {
-    CamSlot slot[2];
-    int next = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool ready = false, timed = false;
+    rn_table<CamDev> desc[2];                 // [max_batch]
+    unsigned long long* d_max[2] = {nullptr, nullptr};      // [max_batch]
+    rn_rotation turn;
+    rn_timer timer;
+    bool ready = false;
 };
 
 int cam_state(rn_handle* h, CamState** out) {
@@ -123,14 +115,12 @@ int cam_state(rn_handle* h, CamState** out) {
         CamState* s = new CamState();
         h->cam_overlay = s;            // (rn_cam_overlay_release frees whatever of it exists)
         const size_t nb = static_cast<size_t>(h->max_batch);
-        for (CamSlot& sl : s->slot) {
-            RN_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_desc), nb * sizeof(CamDev), hipHostMallocDefault));
-            RN_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_desc), nb * sizeof(CamDev)));
-            RN_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_max), nb * sizeof(unsigned long long)));
-            RN_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        int rc;
+        for (int k = 0; k < 2; ++k) {
+            if ((rc = s->desc[k].alloc(nb)) != RN_OK) return rc;
+            RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_max[k]), nb * sizeof(unsigned long long)));
         }
-        RN_HIP(hipEventCreate(&s->t0));
-        RN_HIP(hipEventCreate(&s->t1));
+        if ((rc = s->turn.create()) != RN_OK || (rc = s->timer.create()) != RN_OK) return rc;
         s->ready = true;
     }
     *out = static_cast<CamState*>(h->cam_overlay);
@@ -143,14 +133,8 @@ int cam_state(rn_handle* h, CamState** out) {
 
 int check_targets(rn_handle* h, const rn_cam_target* t, int n, double weight) {
     const char* who = "rn_cam_overlay_batch_device";
-    if (!h || !t) {
-        rn_set_error("%s: null argument", who);
-        return RN_E_INVALID;
-    }
-    if (n < 1 || n > h->max_batch) {
-        rn_set_error("%s: %d images out of range (1..%d)", who, n, h->max_batch);
-        return RN_E_RANGE;
-    }
+    const int rc = rn_check_batch(who, h, t, n);
+    if (rc != RN_OK) return rc;
     if (!(weight >= 0.0 && weight <= 1.0)) {
         rn_set_error("%s: weight %g is not in [0, 1]", who, weight);
         return RN_E_INVALID;
@@ -171,19 +155,21 @@ int check_targets(rn_handle* h, const rn_cam_target* t, int n, double weight) {
 }
 
 int enqueue(rn_handle* h, CamState* st, const rn_cam_target* targets, int n, double weight) {
-    CamSlot& sl = st->slot[st->next];
-    if (sl.used) RN_HIP(hipEventSynchronize(sl.done));
+    int rc, set;
+    if ((rc = st->turn.acquire(&set)) != RN_OK) return rc;
+    const rn_table<CamDev>& tab = st->desc[set];
+    unsigned long long* d_max = st->d_max[set];
     int max_side = 0;
     for (int i = 0; i < n; ++i) {
         const rn_cam_target& t = targets[i];
         int x0, y0, side;
         rn_center_crop_window(t.height, t.width, &x0, &y0, &side);
-        CamDev& d = sl.h_desc[i];
+        CamDev& d = tab.host[i];
         std::memset(&d, 0, sizeof(d));
         d.row_bytes = static_cast<int64_t>(t.width) * 3;
         d.bgr = t.d_bgr + y0 * d.row_bytes + static_cast<int64_t>(x0) * 3;
         d.cam = t.d_cam;
-        d.mx = sl.d_max + i;
+        d.mx = d_max + i;
         d.side = side;
         d.mh = t.cam_h;
         d.mw = t.cam_w;
@@ -191,22 +177,18 @@ int enqueue(rn_handle* h, CamState* st, const rn_cam_target* targets, int n, dou
         d.sx = t.cam_w / static_cast<double>(side);
         max_side = std::max(max_side, side);
     }
-    RN_HIP(hipMemcpyAsync(sl.d_desc, sl.h_desc, static_cast<size_t>(n) * sizeof(CamDev), hipMemcpyHostToDevice, h->stream));
-    RN_HIP(hipEventRecord(st->t0, h->stream));
-    sl.used = true;                    // (from here on the stream may read the slot: the next user waits for `done`)
-    st->next ^= 1;
-    RN_HIP(hipMemsetAsync(sl.d_max, 0, static_cast<size_t>(n) * sizeof(unsigned long long), h->stream));
+    if ((rc = tab.upload(static_cast<size_t>(n), h->stream)) != RN_OK) return rc;
+    if ((rc = st->timer.start(h->stream)) != RN_OK) return rc;
+    RN_HIP(hipMemsetAsync(d_max, 0, static_cast<size_t>(n) * sizeof(unsigned long long), h->stream));
     (void)hipGetLastError();
-    hipLaunchKernelGGL(cam_max_kernel, dim3((max_side + 63) / 64, (max_side + kMaxRows - 1) / kMaxRows, n), dim3(256), 0, h->stream, sl.d_desc);
+    hipLaunchKernelGGL(cam_max_kernel, dim3((max_side + 63) / 64, (max_side + kMaxRows - 1) / kMaxRows, n), dim3(256), 0, h->stream, tab.dev);
     RN_CHECK_LAUNCH();
     // (groups of 4 pixels: at most 3 pixels in front of the first aligned one, so (side + 3) / 4 + 1 groups reach the row's end)
-    hipLaunchKernelGGL(cam_blend_kernel, dim3(((max_side + 3) / 4 + 1 + 63) / 64, (max_side + 3) / 4, n), dim3(256), 0, h->stream, sl.d_desc,
+    hipLaunchKernelGGL(cam_blend_kernel, dim3(((max_side + 3) / 4 + 1 + 63) / 64, (max_side + 3) / 4, n), dim3(256), 0, h->stream, tab.dev,
                        weight, 1.0 - weight);
     RN_CHECK_LAUNCH();
-    RN_HIP(hipEventRecord(st->t1, h->stream));
-    st->timed = true;
-    RN_HIP(hipEventRecord(sl.done, h->stream));
-    return RN_OK;
+    if ((rc = st->timer.stop(h->stream)) != RN_OK) return rc;
+    return st->turn.retire(h->stream);
 }
 
 }  // namespace
@@ -214,15 +196,9 @@ int enqueue(rn_handle* h, CamState* st, const rn_cam_target* targets, int n, dou
 void rn_cam_overlay_release(rn_handle* h) {
     CamState* s = static_cast<CamState*>(h->cam_overlay);
     if (!s) return;
-    for (CamSlot& sl : s->slot) {
-        if (sl.h_desc) (void)hipHostFree(sl.h_desc);
-        if (sl.d_desc) (void)hipFree(sl.d_desc);
-        if (sl.d_max) (void)hipFree(sl.d_max);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    for (hipEvent_t e : {s->t0, s->t1})
-        if (e) (void)hipEventDestroy(e);
-    delete s;
+    for (unsigned long long* p : s->d_max)
+        if (p) (void)hipFree(p);
+    delete s;                          // (the tables, their rotation and the timer free themselves)
     h->cam_overlay = nullptr;
 }
 
@@ -236,17 +212,7 @@ extern "C" int rn_cam_overlay_batch_device(rn_handle* h, const rn_cam_target* ta
 }
 
 extern "C" int rn_cam_last_overlay_ms(rn_handle* h, float* ms) {
-    if (!h || !ms) {
-        rn_set_error("rn_cam_last_overlay_ms: null argument");
-        return RN_E_INVALID;
-    }
-    CamState* st = static_cast<CamState*>(h->cam_overlay);
-    if (!st || !st->timed) {
-        rn_set_error("rn_cam_last_overlay_ms: no heat map has been drawn on this handle");
-        return RN_E_STATE;
-    }
-    DeviceGuard guard(h->device);
-    RN_HIP(hipEventSynchronize(st->t1));
-    RN_HIP(hipEventElapsedTime(ms, st->t0, st->t1));
-    return RN_OK;
+    const CamState* st = h ? static_cast<const CamState*>(h->cam_overlay) : nullptr;
+    return rn_timer::read("rn_cam_last_overlay_ms", h, st ? &st->timer : nullptr, "no heat map has been drawn on this handle",
+                          h ? h->device : 0, ms);
 }

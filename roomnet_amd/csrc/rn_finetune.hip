@@ -670,8 +670,7 @@ struct rn_ft {
     int losses_cap = 0;
     float* d_probs = nullptr;                      // eval staging [max_batch, nc]
     int64_t* d_ids = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the step loop of the last rn_ft_run
-    bool timed = false;
+    rn_timer timer;                                // around the step loop of the last rn_ft_run
     int64_t steps_done = 0;                        // t of the next step is steps_done + 1; global step = start_step + steps_done
     std::vector<void*> allocs;                     // trainer-owned device memory (freed by rn_ft_destroy)
     std::vector<void*> user;                       // rn_ft_upload buffers not yet freed
@@ -972,11 +971,7 @@ int ft_create(const rn_weights* w, int device, int max_batch, const rn_ft_config
         rn_set_error("rn_ft_create: hipStreamCreate failed");
         rc = RN_E_HIP;
     }
-    if (rc == RN_OK && (hipEventCreate(&ft->ev0) != hipSuccess || hipEventCreate(&ft->ev1) != hipSuccess)) {
-        (void)hipGetLastError();
-        rn_set_error("rn_ft_create: hipEventCreate failed");
-        rc = RN_E_HIP;
-    }
+    if (rc == RN_OK) rc = ft->timer.create();
     if (rc == RN_OK) rc = ft_build(ft, w);
     if (rc != RN_OK) {
         rn_ft_destroy(ft);
@@ -1016,8 +1011,6 @@ extern "C" void rn_ft_destroy(rn_ft* ft) {
     for (void* p : ft->user) (void)hipFree(p);
     if (ft->d_losses) (void)hipFree(ft->d_losses);
     if (ft->d_val) (void)hipFree(ft->d_val);
-    if (ft->ev0) (void)hipEventDestroy(ft->ev0);
-    if (ft->ev1) (void)hipEventDestroy(ft->ev1);
     if (ft->stream) (void)hipStreamDestroy(ft->stream);
     (void)hipGetLastError();
     delete ft;
@@ -1288,8 +1281,7 @@ static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const i
     u.n = batch;
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
     const bool dropping = ft->drop.thr != 0;
-    ft->timed = false;
-    RN_HIP(hipEventRecord(ft->ev0, ft->stream));
+    if ((rc = ft->timer.start(ft->stream)) != RN_OK) return rc;
     if (v) RN_HIP(hipMemsetAsync(ft->d_val, 0, t.bytes, ft->stream));
     int point = 0;
     for (int s = 0; s < steps; ++s) {
@@ -1311,7 +1303,7 @@ static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const i
             if (ft_is_point(g, v->every, s == steps - 1) && (rc = ft_enqueue_point(ft, *v, t, point++, g)) != RN_OK) return rc;
         }
     }
-    RN_HIP(hipEventRecord(ft->ev1, ft->stream));
+    if ((rc = ft->timer.stop(ft->stream)) != RN_OK) return rc;
     RN_HIP(hipMemcpyAsync(losses, ft->d_losses, static_cast<size_t>(steps) * 4, hipMemcpyDeviceToHost, ft->stream));
     if (v) {
         const size_t cc = static_cast<size_t>(ft->nc) * ft->nc;
@@ -1320,7 +1312,6 @@ static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const i
         RN_HIP(hipMemcpyAsync(&ft->best, ft->d_best, sizeof(FtBestDev), hipMemcpyDeviceToHost, ft->stream));
     }
     RN_HIP(hipStreamSynchronize(ft->stream));
-    ft->timed = true;
     return RN_OK;
 }
 
@@ -1465,17 +1456,8 @@ extern "C" int rn_ft_read(rn_ft* ft, int what, int var, float* out, size_t cap) 
 }
 
 extern "C" int rn_ft_last_run_ms(rn_ft* ft, float* ms) {
-    if (!ft || !ms) {
-        rn_set_error("rn_ft_last_run_ms: null argument");
-        return RN_E_INVALID;
-    }
-    if (!ft->timed) {
-        rn_set_error("rn_ft_last_run_ms: no rn_ft_run has completed on this trainer");
-        return RN_E_STATE;
-    }
-    DeviceGuard guard(ft->device);
-    RN_HIP(hipEventElapsedTime(ms, ft->ev0, ft->ev1));
-    return RN_OK;
+    return rn_timer::read("rn_ft_last_run_ms", ft, ft ? &ft->timer : nullptr, "no rn_ft_run has completed on this trainer",
+                          ft ? ft->device : 0, ms);
 }
 
 extern "C" int64_t rn_ft_step_count(const rn_ft* ft) { return ft ? ft->cfg.start_step + ft->steps_done : -1; }

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -58,6 +59,20 @@ int rn_allow_big_lds() {
 // names a kernel instantiation as a value, for launch lambdas:  launch(rn_kernel<my_kernel<RN_DTYPE_BF16>>{})
 template <auto Kern>
 struct rn_kernel {};
+
+// Makes `dev` the current HIP device and puts the caller's back on scope exit; `ok` = the device could be set.  Without an
+// argument it only restores (the group entry points walk several devices).
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    DeviceGuard();
+    explicit DeviceGuard(int dev);
+    ~DeviceGuard();
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+#include "rn_batch_table.h"
 
 // per-channel affine form of an inference BN: y = (x - mean) * inv + beta
 struct BnDev {
@@ -129,10 +144,10 @@ struct rn_handle {
     float* lut = nullptr;        // 256-entry uint8 -> float32 table
     // staging for host-buffer calls
     uint8_t* d_in_u8 = nullptr;
-    uint8_t* d_raw = nullptr;      // staging for raw (un-resized) images, rn_classify_images_u8
-    rn_resize_item* d_items = nullptr;           // [max_batch] crop windows of a batched resize (device) ...
-    std::vector<rn_resize_item> items_host;      // ... and their host copy (kept until the next call: the upload is asynchronous)
+    uint8_t* d_raw = nullptr;      // staging for raw (un-resized) images, rn_classify_images_u8 (grow-only, rn_grow_scratch)
     size_t raw_cap = 0;
+    rn_table<rn_resize_item> items[2];     // [max_batch] crop windows of a batched resize, two sets (rn_enqueue_resize_batch allocates them)
+    rn_rotation items_turn;
     float* d_probs = nullptr;
     int64_t* d_ids = nullptr;
     // two-slot host pipeline (rn_submit_u8 / rn_collect): allocated by the first submit
@@ -155,9 +170,10 @@ struct rn_handle {
     float* d_feat = nullptr;     // rn_features_u8: float32 staging of s7.bn, [max_batch, S7, S7, 16] (allocated by the first call)
     float* d_feat6 = nullptr;    // rn_features_depth_u8, depth 3: float32 staging of s6.bn, [max_batch, S6, S6, 128] (the same)
     void* bnstats = nullptr;     // RN_FLAG_BATCH_STATS: the 16 BNs' gamma / moment buffers and the partials' slab (rn_bnstats.hip)
-    void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch and the batch table (rn_jpeg.hip; allocated by the first call)
-    void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the double-buffered batch tables (rn_jpeg_enc.hip; the same)
-    void* cam_overlay = nullptr; // rn_cam_overlay_*: the per-image maxima and the double-buffered batch tables (rn_cam_overlay.hip; the same)
+    // the image stages' lazily allocated state: single stream-ordered scratch, two sets of batch tables (rn_batch_table.h), a timer
+    void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch, the JpegDev tables (rn_jpeg.hip; allocated by the first call)
+    void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the EncDev / OverlayDev / coverage tables (rn_jpeg_enc.hip; the same)
+    void* cam_overlay = nullptr; // rn_cam_overlay_*: the CamDev tables and the per-image maxima (rn_cam_overlay.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
     // node id -> position p of the stored tensor holds the reference's channel perm[p] (rn_tap puts them back in order)
@@ -221,24 +237,22 @@ void rn_jpeg_release(rn_handle* h);
 void rn_jpeg_enc_release(rn_handle* h);
 // ---- grad-CAM heat maps on resident images (rn_cam_overlay.hip)
 void rn_cam_overlay_release(rn_handle* h);
-// (rn_api.hip) the centred square window of network.py:137-146, the batched resize's device table, the tail of a host entry point
+// (rn_api.hip) the centred square window of network.py:137-146 (of a packed BGR image: its top left, side and row bytes), the tail
+// of a host entry point, the null-argument (RN_E_INVALID) / n in 1..max_batch (RN_E_RANGE) check the batched image stages open with
+struct rn_window {
+    const uint8_t* src;
+    int side;
+    int64_t row_bytes;
+};
 void rn_center_crop_window(int hh, int ww, int* x0, int* y0, int* side);
-int rn_ensure_resize_items(rn_handle* h);
+rn_window rn_center_window(const uint8_t* src, int hh, int ww);
 int rn_results_to_host(rn_handle* h, int n, float* probs, int64_t* ids);
+int rn_check_batch(const char* who, const rn_handle* h, const void* ptr, int n);
+// One batched crop + resize of n <= max_batch windows (device memory) into d_dst_batch [n, im_side, im_side, 3] on the handle's stream:
+// acquires a set of h->items, fills it from window(0) .. window(n - 1) (asked once each, in order), uploads, launches, retires.
+int rn_enqueue_resize_batch(rn_handle* h, int n, uint8_t* d_dst_batch, const std::function<rn_window(int)>& window);
 
 // ---- host helpers (rn_api.hip) -----------------------------------------------------------
-// Makes `dev` the current HIP device and puts the caller's back on scope exit; `ok` = the device could be set.  Without an
-// argument it only restores (the group entry points walk several devices).
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    DeviceGuard();
-    explicit DeviceGuard(int dev);
-    ~DeviceGuard();
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
 // device memory owned through a list (freed by the list's owner: rn_destroy, rn_ft_destroy); a failure is RN_E_NOMEM with
 // "hipMalloc(N bytes) failed: ...".  An empty request gets `min_bytes`.
 int rn_owned_alloc(std::vector<void*>& owner, size_t bytes, size_t min_bytes, void** out);
@@ -260,7 +274,7 @@ int rn_owned_zeroed(std::vector<void*>& owner, size_t min_bytes, size_t count, T
     *out = static_cast<T*>(p);
     return RN_OK;
 }
-// grow-only device scratch of a lazily created stage (rn_jpeg.hip, rn_jpeg_enc.hip): the handle's streams are drained first, so
+// grow-only device scratch (h->d_raw, the JPEG stages' planes and coefficients): the handle's streams are drained first, so
 // nothing still reads the old block; a quarter is added to what is asked for
 template <typename T>
 int rn_grow_scratch(rn_handle* h, T** p, size_t* cap, size_t need, const char* what) {

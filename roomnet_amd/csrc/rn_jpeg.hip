@@ -207,7 +207,8 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDev* __restri
     }
 }
 
-// what a handle keeps for the stage: scratch that only grows, the batch table, the events that order the copy stream
+// what a handle keeps for the stage: scratch that only grows, two sets of the batch table (rn_batch_table.h), the events that order
+// the copy stream against the single coefficient scratch
 struct JpegState {
     int16_t* d_coef = nullptr;
     size_t coef_cap = 0;          // int16 elements
@@ -215,27 +216,29 @@ struct JpegState {
     size_t planes_cap = 0;
     uint8_t* d_bgr = nullptr;     // rn_classify_jpegs: the decoded images
     size_t bgr_cap = 0;
-    JpegDev* d_desc = nullptr;    // [max_batch]
-    std::vector<JpegDev> desc;    // its host copy (kept until the next call: the upload is asynchronous)
+    rn_table<JpegDev> desc[2];    // [max_batch]
+    rn_rotation turn;
     std::vector<uint8_t*> bgr_ptrs;
-    hipEvent_t uploaded = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr;
-    bool timed = false;
+    hipEvent_t uploaded = nullptr, done = nullptr;
+    rn_timer timer;
+    bool ready = false;
 };
 
 int jpeg_state(rn_handle* h, JpegState** out) {
     if (!h->jpeg) {
         JpegState* s = new JpegState();
         h->jpeg = s;               // (rn_jpeg_release frees whatever of it exists)
-        s->desc.resize(static_cast<size_t>(h->max_batch));
         s->bgr_ptrs.resize(static_cast<size_t>(h->max_batch));
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_desc), static_cast<size_t>(h->max_batch) * sizeof(JpegDev)));
+        int rc;
+        for (auto& t : s->desc)
+            if ((rc = t.alloc(static_cast<size_t>(h->max_batch))) != RN_OK) return rc;
+        if ((rc = s->turn.create()) != RN_OK || (rc = s->timer.create()) != RN_OK) return rc;
         RN_HIP(hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
         RN_HIP(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
-        RN_HIP(hipEventCreate(&s->t0));
-        RN_HIP(hipEventCreate(&s->t1));
+        s->ready = true;
     }
     *out = static_cast<JpegState*>(h->jpeg);
-    if (!(*out)->d_desc || !(*out)->t1) {
+    if (!(*out)->ready) {
         rn_set_error("rn_jpeg: the stage's state could not be allocated earlier");
         return RN_E_STATE;
     }
@@ -271,7 +274,9 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n,
         max_w = std::max(max_w, f.width);
         max_h = std::max(max_h, f.height);
     }
-    int rc;
+    int rc, set;
+    if ((rc = st->turn.acquire(&set)) != RN_OK) return rc;
+    const rn_table<JpegDev>& tab = st->desc[set];
     if ((rc = rn_grow_scratch(h, &st->d_coef, &st->coef_cap, coef_total, "JPEG coefficients")) != RN_OK) return rc;
     if ((rc = rn_grow_scratch(h, &st->d_planes, &st->planes_cap, plane_total, "JPEG planes")) != RN_OK) return rc;
     if (!d_bgr && (rc = rn_grow_scratch(h, &st->d_bgr, &st->bgr_cap, bgr_total, "decoded images")) != RN_OK) return rc;
@@ -280,7 +285,7 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n,
     size_t coef_off = 0, plane_off = 0, bgr_off = 0;
     for (int i = 0; i < n; ++i) {
         const rn_jpeg_info& f = ims[i].info;
-        JpegDev& d = st->desc[i];
+        JpegDev& d = tab.host[i];
         std::memset(&d, 0, sizeof(d));
         size_t count = 0;
         for (int c = 0; c < f.ncomp; ++c) {
@@ -308,29 +313,22 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n,
         }
     }
     RN_HIP(hipEventRecord(st->uploaded, h->copy_stream));
-    RN_HIP(hipMemcpyAsync(st->d_desc, st->desc.data(), static_cast<size_t>(n) * sizeof(JpegDev), hipMemcpyHostToDevice, h->stream));
+    if ((rc = tab.upload(static_cast<size_t>(n), h->stream)) != RN_OK) return rc;
     RN_HIP(hipStreamWaitEvent(h->stream, st->uploaded, 0));
-    RN_HIP(hipEventRecord(st->t0, h->stream));
+    if ((rc = st->timer.start(h->stream)) != RN_OK) return rc;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, 3, n), dim3(256), 0, h->stream, st->d_desc);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, 3, n), dim3(256), 0, h->stream, tab.dev);
     RN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((max_w + 255) / 256, (max_h + 3) / 4, n), dim3(256), 0, h->stream, st->d_desc);
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((max_w + 255) / 256, (max_h + 3) / 4, n), dim3(256), 0, h->stream, tab.dev);
     RN_CHECK_LAUNCH();
-    RN_HIP(hipEventRecord(st->t1, h->stream));
+    if ((rc = st->timer.stop(h->stream)) != RN_OK) return rc;
     RN_HIP(hipEventRecord(st->done, h->stream));
-    st->timed = true;
-    return RN_OK;
+    return st->turn.retire(h->stream);
 }
 
 int check_images(const char* who, rn_handle* h, const rn_jpeg_image* ims, int n) {
-    if (!h || !ims) {
-        rn_set_error("%s: null argument", who);
-        return RN_E_INVALID;
-    }
-    if (n < 1 || n > h->max_batch) {
-        rn_set_error("%s: %d images out of range (1..%d)", who, n, h->max_batch);
-        return RN_E_RANGE;
-    }
+    const int rc = rn_check_batch(who, h, ims, n);
+    if (rc != RN_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (!ims[i].coeffs || !info_ok(ims[i].info)) {
             rn_set_error("%s: image %d is not a supported JPEG as rn_jpeg_probe describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
@@ -349,10 +347,9 @@ void rn_jpeg_release(rn_handle* h) {
     if (s->d_coef) (void)hipFree(s->d_coef);
     if (s->d_planes) (void)hipFree(s->d_planes);
     if (s->d_bgr) (void)hipFree(s->d_bgr);
-    if (s->d_desc) (void)hipFree(s->d_desc);
-    for (hipEvent_t e : {s->uploaded, s->done, s->t0, s->t1})
+    for (hipEvent_t e : {s->uploaded, s->done})
         if (e) (void)hipEventDestroy(e);
-    delete s;
+    delete s;                      // (the tables, their rotation and the timer free themselves)
     h->jpeg = nullptr;
 }
 
@@ -411,35 +408,16 @@ extern "C" int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, 
     DeviceGuard guard(h->device);
     JpegState* st = nullptr;
     if ((rc = jpeg_state(h, &st)) != RN_OK) return rc;
-    if ((rc = rn_ensure_resize_items(h)) != RN_OK) return rc;
     if ((rc = enqueue_decode(h, st, ims, n, nullptr)) != RN_OK) return rc;
     // from here on it is rn_crop_resize_batch_u8_device + rn_forward_u8_device, as rn_classify_images_u8 runs them
-    const int S = h->im_side;
-    for (int i = 0; i < n; ++i) {
-        const int hh = ims[i].info.height, ww = ims[i].info.width;
-        int x0, y0, side;
-        rn_center_crop_window(hh, ww, &x0, &y0, &side);
-        rn_resize_item_fill(&h->items_host[i], st->bgr_ptrs[i] + (static_cast<int64_t>(y0) * ww + x0) * 3, side, side,
-                            static_cast<int64_t>(ww) * 3, S);
-    }
-    RN_HIP(hipMemcpyAsync(h->d_items, h->items_host.data(), static_cast<size_t>(n) * sizeof(rn_resize_item), hipMemcpyHostToDevice, h->stream));
-    if ((rc = rn_launch_resize_batch_u8(h->stream, h->d_items, n, h->d_in_u8, S)) != RN_OK) return rc;
+    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) { return rn_center_window(st->bgr_ptrs[i], ims[i].info.height, ims[i].info.width); });
+    if (rc != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
     return rn_results_to_host(h, n, probs, ids);
 }
 
 extern "C" int rn_jpeg_last_decode_ms(rn_handle* h, float* ms) {
-    if (!h || !ms) {
-        rn_set_error("rn_jpeg_last_decode_ms: null argument");
-        return RN_E_INVALID;
-    }
-    JpegState* st = static_cast<JpegState*>(h->jpeg);
-    if (!st || !st->timed) {
-        rn_set_error("rn_jpeg_last_decode_ms: no JPEG batch has been decoded on this handle");
-        return RN_E_STATE;
-    }
-    DeviceGuard guard(h->device);
-    RN_HIP(hipEventSynchronize(st->t1));
-    RN_HIP(hipEventElapsedTime(ms, st->t0, st->t1));
-    return RN_OK;
+    const JpegState* st = h ? static_cast<const JpegState*>(h->jpeg) : nullptr;
+    return rn_timer::read("rn_jpeg_last_decode_ms", h, st ? &st->timer : nullptr, "no JPEG batch has been decoded on this handle",
+                          h ? h->device : 0, ms);
 }

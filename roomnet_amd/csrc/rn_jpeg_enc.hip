@@ -214,30 +214,24 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const EncDev* __restrict
         *reinterpret_cast<uint4*>(d.coef[comp] + static_cast<int64_t>(blk) * 64 + j * 8) = *reinterpret_cast<const uint4*>(s_out + b * 64 + j * 8);
 }
 
-// One set of the per-batch tables.  A call fills the set the call before the previous one used, after waiting for that call's
-// launches (`done`): the next call never overwrites a table, or a coverage array, that a launch still reads.
-struct EncSlot {
-    EncDev* h_desc = nullptr;          // page-locked, [max_batch]
-    OverlayDev* h_ov = nullptr;        // page-locked, [RN_JPEG_MAX_OVERLAYS][max_batch]
-    float* h_cov = nullptr;            // page-locked
-    size_t h_cov_cap = 0;
-    EncDev* d_desc = nullptr;
-    OverlayDev* d_ov = nullptr;
-    float* d_cov = nullptr;
-    size_t d_cov_cap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
+// One set of the per-batch tables (rn_batch_table.h): the next call never overwrites a table, or a coverage array, that a launch
+// still reads.
+struct EncSet {
+    rn_table<EncDev> desc;             // [max_batch]
+    rn_table<OverlayDev> ov;           // [RN_JPEG_MAX_OVERLAYS][max_batch]
+    rn_table<float> cov;               // grows with the batch's boxes
 };
 
 struct EncState {
-    EncSlot slot[2];
-    int next = 0;
+    EncSet set[2];
+    rn_rotation turn;
     uint8_t* d_planes = nullptr;
     size_t planes_cap = 0;
     int16_t* d_coef = nullptr;
     size_t coef_cap = 0;               // int16 elements
-    hipEvent_t encoded = nullptr, downloaded = nullptr, t0 = nullptr, t1 = nullptr;
-    bool ready = false, timed = false;
+    hipEvent_t encoded = nullptr, downloaded = nullptr;
+    rn_timer timer;
+    bool ready = false;
 };
 
 int enc_state(rn_handle* h, EncState** out) {
@@ -245,17 +239,12 @@ int enc_state(rn_handle* h, EncState** out) {
         EncState* s = new EncState();
         h->jpeg_enc = s;               // (rn_jpeg_enc_release frees whatever of it exists)
         const size_t nb = static_cast<size_t>(h->max_batch);
-        for (EncSlot& sl : s->slot) {
-            RN_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_desc), nb * sizeof(EncDev), hipHostMallocDefault));
-            RN_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_ov), nb * RN_JPEG_MAX_OVERLAYS * sizeof(OverlayDev), hipHostMallocDefault));
-            RN_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_desc), nb * sizeof(EncDev)));
-            RN_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_ov), nb * RN_JPEG_MAX_OVERLAYS * sizeof(OverlayDev)));
-            RN_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        }
+        int rc;
+        for (EncSet& e : s->set)
+            if ((rc = e.desc.alloc(nb)) != RN_OK || (rc = e.ov.alloc(nb * RN_JPEG_MAX_OVERLAYS)) != RN_OK) return rc;
+        if ((rc = s->turn.create()) != RN_OK || (rc = s->timer.create()) != RN_OK) return rc;
         RN_HIP(hipEventCreateWithFlags(&s->encoded, hipEventDisableTiming));
         RN_HIP(hipEventCreateWithFlags(&s->downloaded, hipEventDisableTiming));
-        RN_HIP(hipEventCreate(&s->t0));
-        RN_HIP(hipEventCreate(&s->t1));
         s->ready = true;
     }
     *out = static_cast<EncState*>(h->jpeg_enc);
@@ -267,34 +256,9 @@ int enc_state(rn_handle* h, EncState** out) {
     return RN_OK;
 }
 
-// the slot's coverage staging, host and device, for `need` floats; the slot is idle (its `done` has been waited for)
-int grow_coverage(EncSlot& sl, size_t need) {
-    if (need > sl.h_cov_cap) {
-        if (sl.h_cov) (void)hipHostFree(sl.h_cov);
-        sl.h_cov = nullptr;
-        sl.h_cov_cap = 0;
-        RN_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_cov), (need + need / 4) * sizeof(float), hipHostMallocDefault));
-        sl.h_cov_cap = need + need / 4;
-    }
-    if (need > sl.d_cov_cap) {
-        if (sl.d_cov) (void)hipFree(sl.d_cov);
-        sl.d_cov = nullptr;
-        sl.d_cov_cap = 0;
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&sl.d_cov), (need + need / 4) * sizeof(float)));
-        sl.d_cov_cap = need + need / 4;
-    }
-    return RN_OK;
-}
-
 int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool encode) {
-    if (!h || !srcs) {
-        rn_set_error("%s: null argument", who);
-        return RN_E_INVALID;
-    }
-    if (n < 1 || n > h->max_batch) {
-        rn_set_error("%s: %d images out of range (1..%d)", who, n, h->max_batch);
-        return RN_E_RANGE;
-    }
+    const int rc = rn_check_batch(who, h, srcs, n);
+    if (rc != RN_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const rn_jpeg_source& s = srcs[i];
         if (!rn_jpeg::encode_info_ok(s.info)) {
@@ -323,8 +287,9 @@ int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int
 }
 
 int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool encode) {
-    EncSlot& sl = st->slot[st->next];
-    if (sl.used) RN_HIP(hipEventSynchronize(sl.done));
+    int rc, set;
+    if ((rc = st->turn.acquire(&set)) != RN_OK) return rc;
+    EncSet& sl = st->set[set];
     size_t cov_total = 0, plane_total = 0;
     int ranks = 0, max_ow = 0, max_oh = 0, max_blocks = 0, max_cw = 0, max_ch = 0;
     for (int i = 0; i < n; ++i) {
@@ -340,8 +305,7 @@ int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool 
         max_cw = std::max(max_cw, s.info.blocks_w[1] * 8);
         max_ch = std::max(max_ch, s.info.blocks_h[1] * 8);
     }
-    int rc;
-    if (cov_total && (rc = grow_coverage(sl, cov_total)) != RN_OK) return rc;
+    if ((rc = sl.cov.grow(cov_total)) != RN_OK) return rc;
     if (encode) {
         if ((rc = rn_grow_scratch(h, &st->d_planes, &st->planes_cap, plane_total, "JPEG encode planes")) != RN_OK) return rc;
         if ((rc = rn_grow_scratch(h, &st->d_coef, &st->coef_cap, plane_total, "JPEG encode coefficients")) != RN_OK) return rc;
@@ -351,14 +315,14 @@ int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool 
     for (int i = 0; i < n; ++i) {
         const rn_jpeg_source& s = srcs[i];
         for (int k = 0; k < ranks; ++k) {
-            OverlayDev& o = sl.h_ov[k * nb + i];
+            OverlayDev& o = sl.ov.host[k * nb + i];
             std::memset(&o, 0, sizeof(o));
             if (k >= s.n_overlays) continue;
             const rn_jpeg_overlay& src = s.overlays[k];
             const size_t count = static_cast<size_t>(src.w) * src.h;
-            std::memcpy(sl.h_cov + cov_off, src.coverage, count * sizeof(float));
+            std::memcpy(sl.cov.host + cov_off, src.coverage, count * sizeof(float));
             o.bgr = s.d_bgr;
-            o.cov = sl.d_cov + cov_off;
+            o.cov = sl.cov.dev + cov_off;
             o.x = src.x;
             o.y = src.y;
             o.w = src.w;
@@ -368,7 +332,7 @@ int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool 
             cov_off += count;
         }
         if (!encode) continue;
-        EncDev& d = sl.h_desc[i];
+        EncDev& d = sl.desc.host[i];
         std::memset(&d, 0, sizeof(d));
         d.bgr = s.d_bgr;
         d.width = s.info.width;
@@ -387,38 +351,34 @@ int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool 
                 d.recip[t][k] = static_cast<uint32_t>(((1ull << 32) + q8 - 1) / q8);
             }
     }
-    if (cov_total) RN_HIP(hipMemcpyAsync(sl.d_cov, sl.h_cov, cov_total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (ranks) RN_HIP(hipMemcpyAsync(sl.d_ov, sl.h_ov, ranks * nb * sizeof(OverlayDev), hipMemcpyHostToDevice, h->stream));
+    if (cov_total && (rc = sl.cov.upload(cov_total, h->stream)) != RN_OK) return rc;
+    if (ranks && (rc = sl.ov.upload(ranks * nb, h->stream)) != RN_OK) return rc;
     if (encode) {
-        RN_HIP(hipMemcpyAsync(sl.d_desc, sl.h_desc, static_cast<size_t>(n) * sizeof(EncDev), hipMemcpyHostToDevice, h->stream));
-        RN_HIP(hipEventRecord(st->t0, h->stream));
+        if ((rc = sl.desc.upload(static_cast<size_t>(n), h->stream)) != RN_OK) return rc;
+        if ((rc = st->timer.start(h->stream)) != RN_OK) return rc;
     }
-    sl.used = true;                    // (from here on the stream may read the slot: the next user waits for `done`)
-    st->next ^= 1;
     (void)hipGetLastError();
     for (int k = 0; k < ranks; ++k) {
-        hipLaunchKernelGGL(jpeg_overlay_kernel, dim3((max_ow + 63) / 64, (max_oh + 3) / 4, n), dim3(256), 0, h->stream, sl.d_ov + k * nb);
+        hipLaunchKernelGGL(jpeg_overlay_kernel, dim3((max_ow + 63) / 64, (max_oh + 3) / 4, n), dim3(256), 0, h->stream, sl.ov.dev + k * nb);
         RN_CHECK_LAUNCH();
     }
     if (encode) {
-        hipLaunchKernelGGL(jpeg_ycc_kernel, dim3((max_cw / 2 + 63) / 64, max_ch / 4, n), dim3(256), 0, h->stream, sl.d_desc);
+        hipLaunchKernelGGL(jpeg_ycc_kernel, dim3((max_cw / 2 + 63) / 64, max_ch / 4, n), dim3(256), 0, h->stream, sl.desc.dev);
         RN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, 3, n), dim3(256), 0, h->stream, sl.d_desc);
+        hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, 3, n), dim3(256), 0, h->stream, sl.desc.dev);
         RN_CHECK_LAUNCH();
-        RN_HIP(hipEventRecord(st->t1, h->stream));
-        st->timed = true;
+        if ((rc = st->timer.stop(h->stream)) != RN_OK) return rc;
         // the coefficients go down on the copy stream; the handle's stream continues behind the download, so rn_sync covers it
         // and the next call's launches do not overwrite the scratch under it
         RN_HIP(hipEventRecord(st->encoded, h->stream));
         RN_HIP(hipStreamWaitEvent(h->copy_stream, st->encoded, 0));
         for (int i = 0; i < n; ++i)
-            RN_HIP(hipMemcpyAsync(srcs[i].coeffs, sl.h_desc[i].coef[0], rn_jpeg::coeff_count(srcs[i].info) * sizeof(int16_t),
+            RN_HIP(hipMemcpyAsync(srcs[i].coeffs, sl.desc.host[i].coef[0], rn_jpeg::coeff_count(srcs[i].info) * sizeof(int16_t),
                                   hipMemcpyDeviceToHost, h->copy_stream));
         RN_HIP(hipEventRecord(st->downloaded, h->copy_stream));
         RN_HIP(hipStreamWaitEvent(h->stream, st->downloaded, 0));
     }
-    RN_HIP(hipEventRecord(sl.done, h->stream));
-    return RN_OK;
+    return st->turn.retire(h->stream);
 }
 
 int run(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool encode) {
@@ -435,20 +395,11 @@ int run(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool e
 void rn_jpeg_enc_release(rn_handle* h) {
     EncState* s = static_cast<EncState*>(h->jpeg_enc);
     if (!s) return;
-    for (EncSlot& sl : s->slot) {
-        if (sl.h_desc) (void)hipHostFree(sl.h_desc);
-        if (sl.h_ov) (void)hipHostFree(sl.h_ov);
-        if (sl.h_cov) (void)hipHostFree(sl.h_cov);
-        if (sl.d_desc) (void)hipFree(sl.d_desc);
-        if (sl.d_ov) (void)hipFree(sl.d_ov);
-        if (sl.d_cov) (void)hipFree(sl.d_cov);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
     if (s->d_planes) (void)hipFree(s->d_planes);
     if (s->d_coef) (void)hipFree(s->d_coef);
-    for (hipEvent_t e : {s->encoded, s->downloaded, s->t0, s->t1})
+    for (hipEvent_t e : {s->encoded, s->downloaded})
         if (e) (void)hipEventDestroy(e);
-    delete s;
+    delete s;                          // (the tables, their rotation and the timer free themselves)
     h->jpeg_enc = nullptr;
 }
 
@@ -479,17 +430,7 @@ extern "C" int rn_jpeg_encode_batch_device(rn_handle* h, const rn_jpeg_source* s
 }
 
 extern "C" int rn_jpeg_last_encode_ms(rn_handle* h, float* ms) {
-    if (!h || !ms) {
-        rn_set_error("rn_jpeg_last_encode_ms: null argument");
-        return RN_E_INVALID;
-    }
-    EncState* st = static_cast<EncState*>(h->jpeg_enc);
-    if (!st || !st->timed) {
-        rn_set_error("rn_jpeg_last_encode_ms: no batch has been encoded on this handle");
-        return RN_E_STATE;
-    }
-    DeviceGuard guard(h->device);
-    RN_HIP(hipEventSynchronize(st->t1));
-    RN_HIP(hipEventElapsedTime(ms, st->t0, st->t1));
-    return RN_OK;
+    const EncState* st = h ? static_cast<const EncState*>(h->jpeg_enc) : nullptr;
+    return rn_timer::read("rn_jpeg_last_encode_ms", h, st ? &st->timer : nullptr, "no batch has been encoded on this handle",
+                          h ? h->device : 0, ms);
 }

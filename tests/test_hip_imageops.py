@@ -104,3 +104,39 @@ def test_batched_crop_resize_is_one_launch_and_byte_identical(engine):
             np.testing.assert_array_equal(got[k], _host(im), err_msg=str(im.shape))
     with pytest.raises((ValueError, _capi.RoomNetLibraryError)):
         engine.crop_resize_batch([ims[0]] * 9)           # more than max_batch
+
+
+def test_back_to_back_batched_resizes_without_a_sync(engine):
+    """The contract include/roomnet_hip.h states for rn_crop_resize_batch_u8_device: back-to-back calls without a sync are fine.
+    Four calls with four different tables and three different n into four destinations, no sync between them (the third reuses the
+    first call's table set, the fourth the second's), one sync at the end; every slot is the host restatement byte for byte.
+    A contract, not a regression trap: a library whose single table happened to be copied in time passes it too."""
+    import ctypes as C
+    first = [(97, 131), (1, 1), (40, 17)]
+    calls = [first, [(224, 224), (33, 65)], [(65, 33)], first[::-1]]
+    rng = np.random.default_rng(20)
+    ims = [[rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in shapes] for shapes in calls]
+    s = 224
+    d_srcs = [[engine.device_malloc(im.nbytes) for im in batch] for batch in ims]
+    d_dsts = [engine.device_malloc(len(batch) * s * s * 3) for batch in ims]
+    try:
+        for batch, ds in zip(ims, d_srcs):
+            for im, d in zip(batch, ds):
+                engine.h2d(d, im)
+        engine.sync()
+        for batch, ds, d_dst in zip(ims, d_srcs, d_dsts):
+            n = len(batch)
+            ptrs = (C.c_void_p * n)(*ds)
+            hs = (C.c_int * n)(*[im.shape[0] for im in batch])
+            ws = (C.c_int * n)(*[im.shape[1] for im in batch])
+            _capi._check(engine.lib, engine.lib.rn_crop_resize_batch_u8_device(engine.handle, ptrs, hs, ws, n, C.c_void_p(d_dst)),
+                         "rn_crop_resize_batch_u8_device")
+        engine.sync()
+        for k, (batch, d_dst) in enumerate(zip(ims, d_dsts)):
+            got = np.empty((len(batch), s, s, 3), np.uint8)
+            engine.d2h(got, d_dst)
+            for i, im in enumerate(batch):
+                np.testing.assert_array_equal(got[i], _host(im), err_msg="call %d, image %d %s" % (k + 1, i, im.shape))
+    finally:
+        for d in [d for ds in d_srcs for d in ds] + d_dsts:
+            engine.device_free(d)

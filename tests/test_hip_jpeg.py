@@ -58,6 +58,34 @@ def test_mixed_batch_is_byte_identical_to_imread_and_to_the_host_restatement(eng
     assert engine.jpeg_last_decode_ms() > 0
 
 
+def test_back_to_back_decodes_without_a_sync(engine, mixed):
+    """The contract include/roomnet_hip.h states for rn_jpeg_decode_batch_device: back-to-back calls without a sync are fine.
+    Three calls with three different tables into separate destinations -- the first half of the mixed files, the second half, the
+    first half reversed (on the first call's table set) -- no sync between them, one at the end; every image as the mixed-batch test
+    checks it.  A contract, not a regression trap: a library whose single table happened to be copied in time passes it too."""
+    import ctypes as C
+    half = len(mixed) // 2
+    calls = [mixed[:half], mixed[half:], mixed[:half][::-1]]
+    d_outs = [[engine.device_malloc(ref.nbytes) for _info, _coeffs, ref in call] for call in calls]
+    try:
+        for call, ds in zip(calls, d_outs):
+            arr = engine._jpeg_images([(info, coeffs) for info, coeffs, _ref in call])
+            _capi._check(engine.lib, engine.lib.rn_jpeg_decode_batch_device(engine.handle, arr, len(call), (C.c_void_p * len(call))(*ds)),
+                         "rn_jpeg_decode_batch_device")
+        engine.sync()
+        for k, (call, ds) in enumerate(zip(calls, d_outs)):
+            for i, ((info, coeffs, ref), d) in enumerate(zip(call, ds)):
+                got = np.empty(ref.shape, np.uint8)
+                engine.d2h(got, d)
+                what = "call %d, image %d (%dx%d)" % (k + 1, i, info.width, info.height)
+                np.testing.assert_array_equal(got, ref, err_msg=what)
+                np.testing.assert_array_equal(got, jpegdec.pixels_from_coeffs(info, coeffs), err_msg=what)
+        assert engine.jpeg_last_decode_ms() > 0
+    finally:
+        for d in [d for ds in d_outs for d in ds]:
+            engine.device_free(d)
+
+
 @pytest.mark.parametrize("n", [1, MAX_BATCH])
 def test_batch_of_one_and_of_max_batch(engine, mixed, n):
     pick = [mixed[-1]] if n == 1 else [mixed[(3 * k) % len(mixed)] for k in range(n)]

@@ -79,3 +79,18 @@ def test_distinct_handles_run_concurrently_from_two_host_threads(weights, parity
     finally:
         for e in engines:
             e.close()
+
+
+def test_stage_timers_of_a_fresh_handle_have_nothing_to_report(weights):
+    """rn_jpeg_last_decode_ms, rn_jpeg_last_encode_ms and rn_cam_last_overlay_ms before any call of their stage: RN_E_STATE with
+    the text each entry has always given (the three share one interval timer; the stage's state does not exist yet)."""
+    e = _capi.Engine(build_graph(6, 224), weights, device=0, dtype="bf16", max_batch=2)
+    try:
+        for read, text in ((e.jpeg_last_decode_ms, "rn_jpeg_last_decode_ms: no JPEG batch has been decoded on this handle"),
+                           (e.jpeg_last_encode_ms, "rn_jpeg_last_encode_ms: no batch has been encoded on this handle"),
+                           (e.cam_last_overlay_ms, "rn_cam_last_overlay_ms: no heat map has been drawn on this handle")):
+            with pytest.raises(_capi.RoomNetLibraryError) as err:
+                read()
+            assert text in str(err.value)
+    finally:
+        e.close()

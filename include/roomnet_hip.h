@@ -325,6 +325,81 @@ RN_API int rn_jpeg_decode_batch_device(rn_handle* h, const rn_jpeg_image* ims, i
 RN_API int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, float* probs, int64_t* ids);
 RN_API int rn_jpeg_last_decode_ms(rn_handle* h, float* ms);
 
+/* ---- the Huffman pass of those files on the GPU --------------------------------------------------
+ * DESIGN.md section 18.  A Huffman bit stream can be decoded from many speculative start points whose decoder states converge
+ * after a few symbols, so the pass above is not serial: the host keeps the marker walk, the file's scan bytes go up as they are,
+ * and the coefficients are produced in device memory in the layout the pixel stage reads.  The scan is cut into subsequences of
+ * RN_JPEG_SUBSEQ_BYTES raw bytes; per batch: (1) one lane per subsequence decodes from a guessed state and stores its exit state;
+ * (2) lanes decode again from their left neighbour's stored state until nothing changes, inside groups of 256 subsequences and
+ * then across groups; (3) the coefficients are zeroed, the block counts scanned, and every lane decodes from its entry state
+ * with the coefficient writer and CHECKS that its exit state is the next lane's entry state; (4) the DC differences are summed
+ * per component with the predictor reset at every restart interval.  A chain of states that is consistent from subsequence 0
+ * is the sequential decode, so the check of (3) makes the result exact whatever (2) did.  Opt-in: nothing above changes.
+ *
+ * The status of an image (int32):
+ *   RN_JPEG_ST_OK              the coefficients equal rn_jpeg_entropy_decode's byte for byte
+ *   RN_JPEG_ST_INVALID_CODE .. RN_JPEG_ST_COEF_LIMIT   what rn_jpeg_entropy_decode refuses: a code no table has, an AC run past
+ *                              the block, scan data that ends before the last block, a restart marker that is missing, early or
+ *                              misnumbered, |coef * q| > RN_JPEG_COEF_LIMIT
+ *   RN_JPEG_ST_NOT_SYNCED      the chain of states was not consistent (or more than 16 fill bytes precede a restart marker)
+ *   RN_JPEG_ST_TOO_LARGE       a scan of more than 16 MiB
+ * Every file rn_jpeg_entropy_decode refuses gets a non-zero status; the two last ones are the only ones a file it accepts may
+ * get, and the caller then runs rn_jpeg_entropy_decode for that file.  With several findings the largest code is reported.  The
+ * coefficients of an image with a non-zero status are unspecified (inside its buffer).
+ *
+ * rn_jpeg_scan_probe      rn_jpeg_probe's walk again, for what rn_jpeg_info does not hold: the byte range of the scan (to the
+ *                         end of the data; the decoders stop at the marker that ends it) and the built lookup tables of each
+ *                         component's DC / AC Huffman table.  Returns what rn_jpeg_probe returns; *out is zero for a file that
+ *                         is not supported.
+ * rn_jpeg_huffman_model   the four phases on the host, lanes one after another through the same code (csrc/rn_jpeg_huff.h), for
+ *                         any subsequence length 4 .. 4096 (else RN_E_RANGE): the CPU statement of the algorithm.  Arguments and
+ *                         refusals as rn_jpeg_entropy_decode; RN_OK with the image's status in *status otherwise.
+ * rn_jpeg_huffman_batch_device  n files (info and scan as the two probes filled them, bytes = the scan's bytes in host memory,
+ *                         data + scan_begin; from rn_host_alloc memory the upload is asynchronous): the scan bytes go up on the
+ *                         handle's copy stream, then the launches of the four phases for the whole batch on the handle's stream
+ *                         write image i's coefficients to d_coeffs[i] (device, rn_jpeg_coeff_count elements), or into the
+ *                         handle's coefficient scratch when d_coeffs is NULL.  Waits for its own launches and fills status[n].
+ *                         n outside [1, max_batch]: RN_E_RANGE; an info that is not a supported one, a null pointer: RN_E_INVALID;
+ *                         the handle stays usable.
+ * rn_jpeg_huffman_batch   the same into host buffers (coefficients of images with status 0 are copied).  Synchronous.
+ * rn_classify_jpeg_files  rn_classify_jpegs from the files' bytes: the Huffman launches, the two pixel-stage launches on the
+ *                         device coefficients, crop + resize + forward pass.  An image with a non-zero status gets id -1 and
+ *                         zero probabilities and does not disturb the others.  Synchronous.
+ * rn_jpeg_last_huffman_ms device time of the last call's Huffman launches; waits for them.
+ * rn_jpeg_last_huffman_rounds  for the n images of the last call: the rounds phase 2 took inside groups (the most of any group)
+ *                         and across groups; waits for them. */
+#define RN_JPEG_ST_OK 0
+#define RN_JPEG_ST_INVALID_CODE 1
+#define RN_JPEG_ST_RUN_PAST_BLOCK 2
+#define RN_JPEG_ST_TRUNCATED 3
+#define RN_JPEG_ST_RESTART 4
+#define RN_JPEG_ST_COEF_LIMIT 5
+#define RN_JPEG_ST_NOT_SYNCED 6
+#define RN_JPEG_ST_TOO_LARGE 7
+typedef struct rn_jpeg_hufftab {
+    uint16_t look[512];               /* (length << 8) | symbol of the code that is a prefix of the 9-bit index; 0: longer */
+    int32_t maxcode[18];              /* largest code of length l, -1: none         */
+    int32_t valoff[17];               /* vals index of the first code of length l minus that code */
+    uint8_t vals[256];
+} rn_jpeg_hufftab;
+typedef struct rn_jpeg_scan {
+    uint64_t scan_begin, scan_len;    /* bytes of the file: [scan_begin, scan_begin + scan_len) */
+    rn_jpeg_hufftab dc[3], ac[3];     /* per component                              */
+} rn_jpeg_scan;
+typedef struct rn_jpeg_file {
+    rn_jpeg_info info;
+    rn_jpeg_scan scan;
+    const uint8_t* bytes;             /* host, the scan's bytes                     */
+} rn_jpeg_file;
+RN_API int rn_jpeg_scan_probe(const uint8_t* data, size_t len, rn_jpeg_scan* out);
+RN_API int rn_jpeg_huffman_model(const uint8_t* data, size_t len, const rn_jpeg_info* info, int16_t* coeffs, size_t cap,
+                                 int subseq_bytes, int32_t* status);
+RN_API int rn_jpeg_huffman_batch_device(rn_handle* h, const rn_jpeg_file* files, int n, int16_t* const* d_coeffs, int32_t* status);
+RN_API int rn_jpeg_huffman_batch(rn_handle* h, const rn_jpeg_file* files, int n, int16_t* const* coeffs_host, int32_t* status);
+RN_API int rn_classify_jpeg_files(rn_handle* h, const rn_jpeg_file* files, int n, float* probs, int64_t* ids, int32_t* status);
+RN_API int rn_jpeg_last_huffman_ms(rn_handle* h, float* ms);
+RN_API int rn_jpeg_last_huffman_rounds(rn_handle* h, int n, int32_t* inside, int32_t* across);
+
 /* ---- the overlay and the output JPEG, written where the image already is --------------------------
  * cv2.putText and cv2.imwrite of infer.py:89-93 for an image the GPU holds.  An encode is the decode
  * above mirrored and splits at the same place: colour conversion, chroma downsampling, forward DCT and quantisation are per pixel

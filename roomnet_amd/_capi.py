@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = (
     "rn_ft_val_points", "rn_ft_run_validated", "rn_ft_best",
     "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
     "rn_jpeg_last_decode_ms",
+    "rn_jpeg_scan_probe", "rn_jpeg_huffman_model", "rn_jpeg_huffman_batch_device", "rn_jpeg_huffman_batch", "rn_classify_jpeg_files",
+    "rn_jpeg_last_huffman_ms", "rn_jpeg_last_huffman_rounds",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
     "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
     "rn_cam_overlay_batch_device", "rn_cam_last_overlay_ms",
@@ -123,6 +125,24 @@ class rn_jpeg_info(C.Structure):
 class rn_jpeg_image(C.Structure):
     _fields_ = [("info", rn_jpeg_info), ("coeffs", C.c_void_p)]
 
+
+class rn_jpeg_hufftab(C.Structure):
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 17), ("vals", C.c_uint8 * 256)]
+
+
+class rn_jpeg_scan(C.Structure):
+    """What ``rn_jpeg_scan_probe`` adds to ``rn_jpeg_info``: the scan's byte range and the components' Huffman lookup tables."""
+    _fields_ = [("scan_begin", C.c_uint64), ("scan_len", C.c_uint64), ("dc", rn_jpeg_hufftab * 3), ("ac", rn_jpeg_hufftab * 3)]
+
+
+class rn_jpeg_file(C.Structure):
+    _fields_ = [("info", rn_jpeg_info), ("scan", rn_jpeg_scan), ("bytes", C.c_void_p)]
+
+
+# the status of an image after the GPU Huffman pass (include/roomnet_hip.h)
+(RN_JPEG_ST_OK, RN_JPEG_ST_INVALID_CODE, RN_JPEG_ST_RUN_PAST_BLOCK, RN_JPEG_ST_TRUNCATED, RN_JPEG_ST_RESTART, RN_JPEG_ST_COEF_LIMIT,
+ RN_JPEG_ST_NOT_SYNCED, RN_JPEG_ST_TOO_LARGE) = range(8)
+RN_JPEG_SUBSEQ_BYTES = 128
 
 RN_JPEG_MAX_OVERLAYS = 8
 
@@ -331,6 +351,20 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_classify_jpegs.restype = i32
         lib.rn_jpeg_last_decode_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_jpeg_last_decode_ms.restype = i32
+    if hasattr(lib, "rn_jpeg_scan_probe"):
+        lib.rn_jpeg_scan_probe.argtypes = [vp, sz, C.POINTER(rn_jpeg_scan)]
+        lib.rn_jpeg_scan_probe.restype = i32
+        lib.rn_jpeg_huffman_model.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info), vp, sz, i32, C.POINTER(i32)]
+        lib.rn_jpeg_huffman_model.restype = i32
+        for name in ("rn_jpeg_huffman_batch_device", "rn_jpeg_huffman_batch"):
+            getattr(lib, name).argtypes = [vp, C.POINTER(rn_jpeg_file), i32, C.POINTER(vp), vp]
+            getattr(lib, name).restype = i32
+        lib.rn_classify_jpeg_files.argtypes = [vp, C.POINTER(rn_jpeg_file), i32, vp, vp, vp]
+        lib.rn_classify_jpeg_files.restype = i32
+        lib.rn_jpeg_last_huffman_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_jpeg_last_huffman_ms.restype = i32
+        lib.rn_jpeg_last_huffman_rounds.argtypes = [vp, i32, vp, vp]
+        lib.rn_jpeg_last_huffman_rounds.restype = i32
     if hasattr(lib, "rn_jpeg_encode_info"):
         lib.rn_jpeg_encode_info.argtypes = [i32, i32, i32, C.POINTER(rn_jpeg_info)]
         lib.rn_jpeg_encode_info.restype = i32
@@ -529,6 +563,62 @@ class Engine:
             _check(self.lib, self.lib.rn_classify_jpegs(self.handle, arr, m, probs[i:i + m].ctypes.data, ids[i:i + m].ctypes.data),
                    "rn_classify_jpegs")
         return ids, probs
+
+    @staticmethod
+    def _jpeg_files(items):
+        """``[(rn_jpeg_info, rn_jpeg_scan, scan bytes)]`` -> the C array ``rn_jpeg_file[n]``; the scan bytes are a uint8 array that
+        holds exactly them, or the address of their first one (the buffers stay the caller's)."""
+        arr = (rn_jpeg_file * max(len(items), 1))()
+        for k, (info, scan, data) in enumerate(items):
+            arr[k].info = info
+            arr[k].scan = scan
+            arr[k].bytes = data.ctypes.data if isinstance(data, np.ndarray) else int(data)
+        return arr
+
+    def jpeg_huffman_batch(self, items):
+        """One ``rn_jpeg_huffman_batch`` call over ``items`` (as ``_jpeg_files`` takes them, at most ``max_batch``): the Huffman pass
+        on the GPU.  Returns ``(status int32 [n], [int16 coefficient array per image])``; the array of an image whose status is not
+        0 is left as zeros."""
+        items = list(items)
+        n = len(items)
+        arr = self._jpeg_files(items)
+        outs = [np.zeros(max(1, sum(int(info.blocks_w[c]) * int(info.blocks_h[c]) * 64 for c in range(min(max(info.ncomp, 0), 3)))),
+                         np.int16) for info, _s, _d in items]
+        ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        status = np.full((max(n, 1),), -1, np.int32)
+        _check(self.lib, self.lib.rn_jpeg_huffman_batch(self.handle, arr, n, ptrs, status.ctypes.data), "rn_jpeg_huffman_batch")
+        return status[:n], outs
+
+    def classify_jpeg_files(self, items) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``items``: ``[(rn_jpeg_info, rn_jpeg_scan, scan bytes)]`` of supported baseline JPEG files as ``jpegdec.load_file_bytes``
+        gives them.  Huffman pass, pixel stage, centre crop, resize and forward pass on the GPU (``rn_classify_jpeg_files``);
+        returns ``(ids [n], probs [n, C], status [n])``: where ``status`` is 0 the results are bit-identical to ``classify_jpegs``,
+        elsewhere the id is -1 and the file is one for the host's Huffman pass."""
+        items = list(items)
+        n = len(items)
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        status = np.empty((n,), np.int32)
+        for i in range(0, n, self.max_batch):
+            chunk = items[i:i + self.max_batch]
+            m = len(chunk)
+            _check(self.lib, self.lib.rn_classify_jpeg_files(self.handle, self._jpeg_files(chunk), m, probs[i:i + m].ctypes.data,
+                                                             ids[i:i + m].ctypes.data, status[i:i + m].ctypes.data),
+                   "rn_classify_jpeg_files")
+        return ids, probs, status
+
+    def jpeg_last_huffman_ms(self) -> float:
+        """Device time of the last batch's Huffman launches (``rn_jpeg_last_huffman_ms``)."""
+        ms = C.c_float(0.0)
+        _check(self.lib, self.lib.rn_jpeg_last_huffman_ms(self.handle, C.byref(ms)), "rn_jpeg_last_huffman_ms")
+        return float(ms.value)
+
+    def jpeg_last_huffman_rounds(self, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Synchronisation rounds of the last Huffman batch's ``n`` images: ``(inside groups, across groups)``."""
+        inside, across = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(self.lib, self.lib.rn_jpeg_last_huffman_rounds(self.handle, n, inside.ctypes.data, across.ctypes.data),
+               "rn_jpeg_last_huffman_rounds")
+        return inside, across
 
     def jpeg_decode_batch(self, items, repeat: int = 1):
         """One ``rn_jpeg_decode_batch_device`` call over ``items`` (as ``classify_jpegs`` takes them, at most ``max_batch``): the

@@ -11,21 +11,12 @@
 //                      is dword-aligned.
 // Both are ONE launch per batch (blockIdx.z = image, a device table of per-image descriptors), as the batched resize is.
 // HBM-bound byte work (2 B of coefficients in, 1 B of plane out and in again, 3 B of BGR out per sample); no MFMA.
-#include "rn_internal.h"
+#include "rn_jpeg_dev.h"
 #include "rn_jpeg_host.h"
 
 #include <algorithm>
 
 namespace {
-
-struct JpegDev {
-    const int16_t* coef[3];   // [blocks_h][blocks_w][64] per component
-    uint8_t* plane[3];        // [blocks_h * 8][blocks_w * 8] per component
-    uint8_t* bgr;             // [height][width][3]
-    int32_t width, height, ncomp, hsamp, vsamp;
-    int32_t bw[3], bh[3];
-    uint16_t qt[3][64];
-};
 
 // One 1-D pass of jpeg_idct_islow (jidctint.c, CONST_BITS = 13) before its descale: o[k] = sum of the even and odd parts.
 __device__ __forceinline__ void idct_islow_1d(const int (&x)[8], int (&o)[8]) {
@@ -207,24 +198,10 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDev* __restri
     }
 }
 
-// what a handle keeps for the stage: scratch that only grows, two sets of the batch table (rn_batch_table.h), the events that order
-// the copy stream against the single coefficient scratch
-struct JpegState {
-    int16_t* d_coef = nullptr;
-    size_t coef_cap = 0;          // int16 elements
-    uint8_t* d_planes = nullptr;
-    size_t planes_cap = 0;
-    uint8_t* d_bgr = nullptr;     // rn_classify_jpegs: the decoded images
-    size_t bgr_cap = 0;
-    rn_table<JpegDev> desc[2];    // [max_batch]
-    rn_rotation turn;
-    std::vector<uint8_t*> bgr_ptrs;
-    hipEvent_t uploaded = nullptr, done = nullptr;
-    rn_timer timer;
-    bool ready = false;
-};
+}  // namespace
 
-int jpeg_state(rn_handle* h, JpegState** out) {
+// the stage's state (rn_jpeg_dev.h), allocated by the first call
+int rn_jpeg_state(rn_handle* h, JpegState** out) {
     if (!h->jpeg) {
         JpegState* s = new JpegState();
         h->jpeg = s;               // (rn_jpeg_release frees whatever of it exists)
@@ -247,7 +224,7 @@ int jpeg_state(rn_handle* h, JpegState** out) {
 }
 
 // a supported image as rn_jpeg_probe fills it: every size the kernels index with is recomputed from width, height and sampling
-bool info_ok(const rn_jpeg_info& f) {
+bool rn_jpeg_info_ok(const rn_jpeg_info& f) {
     if (f.supported != 1 || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
     if (f.ncomp != 1 && f.ncomp != 3) return false;
     const bool s11 = f.hsamp == 1 && f.vsamp == 1, s21 = f.hsamp == 2 && f.vsamp == 1, s22 = f.hsamp == 2 && f.vsamp == 2;
@@ -258,15 +235,18 @@ bool info_ok(const rn_jpeg_info& f) {
     return true;
 }
 
-// Upload + the two launches for n checked images.  d_bgr == nullptr: into the handle's own image scratch (st->bgr_ptrs).
-int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n, uint8_t* const* d_bgr) {
+namespace {
+
+// Upload + the two launches for n checked images, all with host coefficients or all with coefficients a launch on the handle's stream
+// left in device memory.  d_bgr == nullptr: into the handle's own image scratch (st->bgr_ptrs).
+int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, uint8_t* const* d_bgr) {
     size_t coef_total = 0, plane_total = 0, bgr_total = 0;
     int max_blocks = 0, max_w = 0, max_h = 0;
     for (int i = 0; i < n; ++i) {
-        const rn_jpeg_info& f = ims[i].info;
+        const rn_jpeg_info& f = *jobs[i].info;
         for (int c = 0; c < f.ncomp; ++c) {
             const int nb = f.blocks_w[c] * f.blocks_h[c];          // <= 8192 * 8192
-            coef_total += static_cast<size_t>(nb) * 64;
+            if (!jobs[i].on_device) coef_total += static_cast<size_t>(nb) * 64;
             plane_total += static_cast<size_t>(nb) * 64;
             max_blocks = std::max(max_blocks, nb);
         }
@@ -284,21 +264,23 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_image* ims, int n,
     RN_HIP(hipStreamWaitEvent(h->copy_stream, st->done, 0));
     size_t coef_off = 0, plane_off = 0, bgr_off = 0;
     for (int i = 0; i < n; ++i) {
-        const rn_jpeg_info& f = ims[i].info;
+        const rn_jpeg_info& f = *jobs[i].info;
         JpegDev& d = tab.host[i];
         std::memset(&d, 0, sizeof(d));
         size_t count = 0;
         for (int c = 0; c < f.ncomp; ++c) {
             const size_t nb = static_cast<size_t>(f.blocks_w[c]) * f.blocks_h[c] * 64;
-            d.coef[c] = st->d_coef + coef_off + count;
+            d.coef[c] = (jobs[i].on_device ? jobs[i].coeffs : st->d_coef + coef_off) + count;
             d.plane[c] = st->d_planes + plane_off + count;
             d.bw[c] = f.blocks_w[c];
             d.bh[c] = f.blocks_h[c];
             std::memcpy(d.qt[c], f.qt[c], sizeof(d.qt[c]));
             count += nb;
         }
-        RN_HIP(hipMemcpyAsync(st->d_coef + coef_off, ims[i].coeffs, count * sizeof(int16_t), hipMemcpyHostToDevice, h->copy_stream));
-        coef_off += count;
+        if (!jobs[i].on_device) {
+            RN_HIP(hipMemcpyAsync(st->d_coef + coef_off, jobs[i].coeffs, count * sizeof(int16_t), hipMemcpyHostToDevice, h->copy_stream));
+            coef_off += count;
+        }
         plane_off += count;
         d.width = f.width;
         d.height = f.height;
@@ -330,7 +312,7 @@ int check_images(const char* who, rn_handle* h, const rn_jpeg_image* ims, int n)
     const int rc = rn_check_batch(who, h, ims, n);
     if (rc != RN_OK) return rc;
     for (int i = 0; i < n; ++i)
-        if (!ims[i].coeffs || !info_ok(ims[i].info)) {
+        if (!ims[i].coeffs || !rn_jpeg_info_ok(ims[i].info)) {
             rn_set_error("%s: image %d is not a supported JPEG as rn_jpeg_probe describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
                          who, i, ims[i].info.width, ims[i].info.height, ims[i].info.ncomp, ims[i].info.hsamp, ims[i].info.vsamp,
                          ims[i].info.supported);
@@ -339,7 +321,23 @@ int check_images(const char* who, rn_handle* h, const rn_jpeg_image* ims, int n)
     return RN_OK;
 }
 
+std::vector<rn_jpeg_job> host_jobs(const rn_jpeg_image* ims, int n) {
+    std::vector<rn_jpeg_job> jobs(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) jobs[static_cast<size_t>(i)] = rn_jpeg_job{&ims[i].info, ims[i].coeffs, false};
+    return jobs;
+}
+
 }  // namespace
+
+int rn_jpeg_classify_jobs(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, float* probs, int64_t* ids) {
+    int rc = enqueue_decode(h, st, jobs, n, nullptr);
+    if (rc != RN_OK) return rc;
+    // from here on it is rn_crop_resize_batch_u8_device + rn_forward_u8_device, as rn_classify_images_u8 runs them
+    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) { return rn_center_window(st->bgr_ptrs[i], jobs[i].info->height, jobs[i].info->width); });
+    if (rc != RN_OK) return rc;
+    if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
+    return rn_results_to_host(h, n, probs, ids);
+}
 
 void rn_jpeg_release(rn_handle* h) {
     JpegState* s = static_cast<JpegState*>(h->jpeg);
@@ -347,7 +345,9 @@ void rn_jpeg_release(rn_handle* h) {
     if (s->d_coef) (void)hipFree(s->d_coef);
     if (s->d_planes) (void)hipFree(s->d_planes);
     if (s->d_bgr) (void)hipFree(s->d_bgr);
-    for (hipEvent_t e : {s->uploaded, s->done})
+    if (s->d_scan) (void)hipFree(s->d_scan);
+    if (s->d_chain) (void)hipFree(s->d_chain);
+    for (hipEvent_t e : {s->uploaded, s->done, s->scan_done})
         if (e) (void)hipEventDestroy(e);
     delete s;                      // (the tables, their rotation and the timer free themselves)
     h->jpeg = nullptr;
@@ -369,7 +369,7 @@ extern "C" int rn_jpeg_probe(const uint8_t* data, size_t len, rn_jpeg_info* out)
 }
 
 extern "C" size_t rn_jpeg_coeff_count(const rn_jpeg_info* info) {
-    if (!info || !info_ok(*info)) return 0;
+    if (!info || !rn_jpeg_info_ok(*info)) return 0;
     return rn_jpeg::coeff_count(*info);
 }
 
@@ -394,8 +394,8 @@ extern "C" int rn_jpeg_decode_batch_device(rn_handle* h, const rn_jpeg_image* im
         }
     DeviceGuard guard(h->device);
     JpegState* st = nullptr;
-    if ((rc = jpeg_state(h, &st)) != RN_OK) return rc;
-    return enqueue_decode(h, st, ims, n, d_bgr);
+    if ((rc = rn_jpeg_state(h, &st)) != RN_OK) return rc;
+    return enqueue_decode(h, st, host_jobs(ims, n).data(), n, d_bgr);
 }
 
 extern "C" int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, float* probs, int64_t* ids) {
@@ -407,13 +407,8 @@ extern "C" int rn_classify_jpegs(rn_handle* h, const rn_jpeg_image* ims, int n, 
     }
     DeviceGuard guard(h->device);
     JpegState* st = nullptr;
-    if ((rc = jpeg_state(h, &st)) != RN_OK) return rc;
-    if ((rc = enqueue_decode(h, st, ims, n, nullptr)) != RN_OK) return rc;
-    // from here on it is rn_crop_resize_batch_u8_device + rn_forward_u8_device, as rn_classify_images_u8 runs them
-    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) { return rn_center_window(st->bgr_ptrs[i], ims[i].info.height, ims[i].info.width); });
-    if (rc != RN_OK) return rc;
-    if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
-    return rn_results_to_host(h, n, probs, ids);
+    if ((rc = rn_jpeg_state(h, &st)) != RN_OK) return rc;
+    return rn_jpeg_classify_jobs(h, st, host_jobs(ims, n).data(), n, probs, ids);
 }
 
 extern "C" int rn_jpeg_last_decode_ms(rn_handle* h, float* ms) {

@@ -127,14 +127,18 @@ def _decode_files(fpaths, batch_size, decode_threads=None):
             yield i, fpath, im
 
 
-def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False):
+def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False, gpu_huffman=False):
     """Yield ``(index, image_bgr, idx, conf)`` per readable file, in list order.  Files are decoded on a small thread
     pool (Pillow releases the GIL while it decodes) that runs up to two batches ahead of the GPU; the GPU gets the
     decoded images in batches of ``batch_size``.  ``gpu_decode``: ``RoomNet.infer_files`` instead -- baseline JPEG files
     only pass their Huffman stage on the pool and become pixels on the GPU; ``image_bgr`` is then None (the decoded image
-    never exists on the host); same ids and confidences."""
+    never exists on the host); same ids and confidences.  ``gpu_huffman`` (with ``gpu_decode``): their Huffman stage runs on the GPU
+    too and the pool only reads the files."""
+    if gpu_huffman and not gpu_decode:
+        raise ValueError("gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
     if gpu_decode:
-        ids, probs, ok = nn.infer_files(fpaths, decode_threads=decode_threads, batch_size=batch_size)
+        # (a model object without the argument still works while it is off)
+        ids, probs, ok = nn.infer_files(fpaths, decode_threads=decode_threads, batch_size=batch_size, **(dict(gpu_huffman=True) if gpu_huffman else {}))
         for i, fpath in enumerate(fpaths):
             if not ok[i]:
                 print(fpath, '---> unreadable image, skipped')
@@ -167,16 +171,18 @@ def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False):
         yield r
 
 
-def groundtruth_validation(nn, list_fpath=None, batch_size=64, gpu_decode=False):
+def groundtruth_validation(nn, list_fpath=None, batch_size=64, gpu_decode=False, gpu_huffman=False):
     """infer.py:41-57, with the list file it reads made an argument (the reference's global is
     commented out, infer.py:28).  Prints and returns accuracy and per-class precision / recall /
     f-score, computed like ``train.py:146-152``.  ``gpu_decode``: baseline JPEG files are decoded on the GPU
-    (``RoomNet.infer_files``); same predictions."""
+    (``RoomNet.infer_files``); same predictions.  ``gpu_huffman`` (with ``gpu_decode``): their Huffman pass too."""
+    if gpu_huffman and not gpu_decode:
+        raise ValueError("groundtruth_validation: gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
     from sklearn.metrics import accuracy_score, precision_recall_fscore_support
     fpaths, labels, num_fpaths = read_fpaths(list_fpath or INPUT_IMG_PATH_LIST_FILE)
     print('Inferring Images...')
     y_preds, y_truths = [], []
-    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size, gpu_decode=gpu_decode):
+    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman):
         y_preds.append(idx)
         y_truths.append(labels[i])
     acc = accuracy_score(y_truths, y_preds)
@@ -253,7 +259,8 @@ def _heat_overlay_and_write(im, cam_map, weight, pred_label, pred_conf, out_fpat
     return _overlay_and_write(overlay_image(im, cam_map, weight), pred_label, pred_conf, out_fpath)
 
 
-def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5):
+def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5,
+                    gpu_huffman=False):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
@@ -262,9 +269,12 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     the overlay is drawn and the output JPEG's pixel stage runs on the GPU as well (``RoomNet.classify_files_to_dir``): a file
     stays on the device from decode to encode and only the Huffman passes run on the host; files ``imread`` decodes are uploaded
     when their output is a JPEG file and go the host way otherwise.  Output files, workbook and printed lines are the same,
-    byte for byte."""
+    byte for byte.  ``gpu_huffman`` (with ``gpu_decode``): the Huffman pass of the input files runs on the GPU too (DESIGN.md
+    section 18; with ``gpu_encode`` the input's Huffman pass stays on the host); same outputs."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
+    if gpu_huffman and not gpu_decode:
+        raise ValueError("classify_im_dir: gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
     if gpu_encode and not overlay:
         raise ValueError("classify_im_dir: gpu_encode=True needs overlay=True (without the overlay the files are copied: there is "
                          "nothing to encode)")
@@ -305,7 +315,8 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     elif heatmap is not None:
         results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap))
     else:
-        results = ((i, idx, conf, im, None) for i, im, idx, conf in _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode))
+        results = ((i, idx, conf, im, None) for i, im, idx, conf in
+                   _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman))
     try:
         for i, idx, pred_conf, im, written in results:
             fpath = all_im_paths[i]

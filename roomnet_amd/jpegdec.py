@@ -6,10 +6,13 @@ the pixel stage -- dequantisation, ``jpeg_idct_islow``, "fancy" chroma upsamplin
 GPU kernels of ``csrc/rn_jpeg.hip`` are compared against byte for byte, and which itself equals libjpeg's default decode path
 (what Pillow returns) byte for byte: the host half of the parity argument, as ``imageops.py`` is for the resize.
 ``decode_bgr`` composes them: the bytes of a supported file -> what ``imageio.imread`` returns for it.
+``scan_probe_rc``, ``huffman_model_rc`` and ``load_file_bytes`` belong to the second opt-in, the Huffman pass on the GPU (DESIGN.md
+section 18): the scan's byte range and lookup tables, the host model of the parallel decode, and the loader that leaves the pass out.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -76,6 +79,27 @@ def entropy_decode(data, info: Optional[rn_jpeg_info] = None, lib_path: Optional
     out = np.empty(coeff_count(info), np.int16)
     _capi._check(_capi.load_library(lib_path), entropy_decode_rc(data, info, out, lib_path=lib_path), "rn_jpeg_entropy_decode")
     return info, out
+
+
+def scan_probe_rc(data, lib_path: Optional[str] = None) -> Tuple[int, _capi.rn_jpeg_scan]:
+    """``rn_jpeg_scan_probe`` as it returns: ``(code, scan)`` -- the scan's byte range and the components' Huffman lookup tables."""
+    lib = _capi.load_library(lib_path)
+    b, n = _as_buffer(data)
+    scan = _capi.rn_jpeg_scan()
+    return int(lib.rn_jpeg_scan_probe(b, n, C.byref(scan))), scan
+
+
+def huffman_model_rc(data, info: rn_jpeg_info, out: np.ndarray, subseq_bytes: int = _capi.RN_JPEG_SUBSEQ_BYTES,
+                     cap: Optional[int] = None, lib_path: Optional[str] = None) -> Tuple[int, int]:
+    """``rn_jpeg_huffman_model`` -- the GPU's parallel Huffman decode run lane by lane on the host -- into
+    the int16 array ``out``: ``(code, status)``; the status is -1 when the call was refused."""
+    lib = _capi.load_library(lib_path)
+    b, n = _as_buffer(data)
+    assert out.dtype == np.int16 and out.flags["C_CONTIGUOUS"]
+    status = C.c_int32(-1)
+    rc = lib.rn_jpeg_huffman_model(b, n, C.byref(info), out.ctypes.data, out.size if cap is None else int(cap), int(subseq_bytes),
+                                   C.byref(status))
+    return int(rc), int(status.value)
 
 
 def _idct_pass(x, axis, itype):
@@ -218,6 +242,56 @@ class CoeffRing:
             if b is not None:
                 b.close()
         self._bufs = [None] * len(self._bufs)
+
+
+class ByteRing:
+    """``slots`` page-locked byte buffers for the FILES in flight when the Huffman pass runs on the GPU (``load_file_bytes``): kept
+    and reused from file to file like ``CoeffRing``'s."""
+
+    def __init__(self, slots: int):
+        self._bufs = [None] * int(slots)
+
+    def __len__(self):
+        return len(self._bufs)
+
+    def buffer(self, slot: int, count: int) -> np.ndarray:
+        b = self._bufs[slot]
+        if b is None or b.array.size < count:
+            if b is not None:
+                b.close()
+            b = self._bufs[slot] = _capi.PinnedArray((count + count // 8 + 64,), np.uint8)
+        return b.array
+
+    def close(self) -> None:
+        for b in self._bufs:
+            if b is not None:
+                b.close()
+        self._bufs = [None] * len(self._bufs)
+
+
+def load_file_bytes(path: str, ring: ByteRing, slot: int):
+    """One file for the classifier when the GPU runs the Huffman pass too: ``("file", info, scan, bytes)``
+    -- a supported baseline JPEG, read into the ring's slot and only its markers walked (``rn_jpeg_probe``,
+    ``rn_jpeg_scan_probe``); ``bytes`` is the view of the scan's bytes inside the slot; ``("image", bgr)`` -- anything else
+    ``imageio.imread`` reads; ``None`` -- not a readable image.  Runs on a pool thread; the file read and both probes release the GIL."""
+    from .imageio import imread
+    lib = _capi.load_library()
+    try:
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            buf = ring.buffer(slot, max(size, 1))
+            got = f.readinto(memoryview(buf)[:size]) if size else 0
+    except OSError:
+        return None
+    if got == size and size:
+        info = rn_jpeg_info()
+        if lib.rn_jpeg_probe(C.cast(buf.ctypes.data, C.c_char_p), size, C.byref(info)) == 0 and info.supported and \
+                coeff_count(info) <= MAX_COEFFS:
+            scan = _capi.rn_jpeg_scan()
+            if lib.rn_jpeg_scan_probe(buf.ctypes.data, size, C.byref(scan)) == 0 and scan.scan_len:
+                return ("file", info, scan, buf[int(scan.scan_begin):int(scan.scan_begin) + int(scan.scan_len)])
+    im = imread(path)
+    return None if im is None else ("image", im)
 
 
 def load_file(path: str, ring: CoeffRing, slot: int):

@@ -326,7 +326,7 @@ class RoomNet:
             prepared.append(np.ascontiguousarray(im))
         return self.infer(np.stack(prepared, 0))
 
-    def infer_files(self, paths, decode_threads=None, batch_size=64):
+    def infer_files(self, paths, decode_threads=None, batch_size=64, gpu_huffman=False):
         """Classify image FILES, decoding baseline JPEG on the GPU: ``(ids int64[N], probs float32[N,C], ok bool[N])`` in list
         order; ``ok[i]`` False (id -1, zero probabilities) marks a file that is not a readable image.  A pool of
         ``decode_threads`` threads (default ``infer.DECODE_THREADS``, at most 16) reads each file, walks its markers and runs its
@@ -335,14 +335,22 @@ class RoomNet:
         ``max_batch``) per call (``rn_classify_jpegs``) while the pool works on the next batch.  Files the split decoder does
         not take -- progressive, CMYK, rotated by EXIF, damaged, not JPEG at all -- are decoded by ``imageio.imread`` on the same
         pool and classified by ``infer_images`` in the same call.  Every result equals ``infer_images`` of the ``imread``
-        images bit for bit.  Not in the reference (infer.py:79-82 decodes with ``cv2.imread``)."""
+        images bit for bit.  Not in the reference (infer.py:79-82 decodes with ``cv2.imread``).
+
+        ``gpu_huffman``: the Huffman pass runs on the GPU as well.  The pool then only reads each file
+        into page-locked memory and walks its markers; the file's bytes go up as they are (``rn_classify_jpeg_files``).  A file
+        whose status comes back non-zero is decoded by the host's Huffman pass on the same pool and classified in the same call
+        (``self.huffman_fallbacks`` counts them); the results are the same bits either way."""
         paths = list(paths)
         n = len(paths)
         ids = np.full((n,), -1, np.int64)
         probs = np.zeros((n, self.num_classes), np.float32)
         ok = np.zeros((n,), bool)
         eng = self._engine() if n else None
-        for lo, loaded in self._file_chunks(paths, batch_size, decode_threads):
+        self.huffman_fallbacks = 0
+        for lo, loaded, pool in self._file_chunks(paths, batch_size, decode_threads, gpu_huffman=gpu_huffman):
+            if gpu_huffman:
+                loaded = self._classify_file_bytes(eng, paths, lo, loaded, pool, ids, probs, ok)
             jp = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "jpeg"]
             im = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "image"]
             if jp:
@@ -355,10 +363,36 @@ class RoomNet:
                 ids[at], probs[at], ok[at] = a, b, True
         return ids, probs, ok
 
-    def _file_chunks(self, paths, batch_size, decode_threads=None):
+    def _classify_file_bytes(self, eng, paths, lo, loaded, pool, ids, probs, ok):
+        """The ``gpu_huffman`` half of ``infer_files`` for one chunk of ``jpegdec.load_file_bytes`` results: the ``"file"`` entries
+        are classified from their bytes (``rn_classify_jpeg_files``) and their results stored; returns the chunk with them taken
+        out (None in their place, already counted) and every file whose status is not 0 replaced by what ``jpegdec.load_file``
+        gives for it -- the host's Huffman pass, run on the same pool -- for the caller to classify as before."""
+        from . import jpegdec
+        loaded = list(loaded)
+        fl = [(j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "file"]
+        if not fl:
+            return loaded
+        a, b, status = eng.classify_jpeg_files([(r[1], r[2], r[3]) for _j, r in fl])
+        good = [k for k in range(len(fl)) if status[k] == 0]
+        at = [lo + fl[k][0] for k in good]
+        if good:
+            ids[at], probs[at], ok[at] = a[good], b[good], True
+        for j, _r in fl:
+            loaded[j] = None
+        again = [fl[k][0] for k in range(len(fl)) if status[k] != 0]
+        self.huffman_fallbacks += len(again)
+        # (the coefficient ring is free in this mode: the slots of the chunk's first bank take the fallbacks)
+        futures = [(j, pool.submit(jpegdec.load_file, paths[lo + j], self._jpeg_ring, j)) for j in again]
+        for j, f in futures:
+            loaded[j] = f.result()
+        return loaded
+
+    def _file_chunks(self, paths, batch_size, decode_threads=None, gpu_huffman=None):
         """Yield ``(lo, [jpegdec.load_file result of paths[lo + j]])`` chunk by chunk (``batch_size``, at most ``max_batch``, files
         each): the pool decodes chunk k + 1 into the other half of the coefficient ring while the consumer works on chunk k.  A
-        chunk's coefficient buffers are valid until the consumer asks for the next chunk."""
+        chunk's coefficient buffers are valid until the consumer asks for the next chunk.  ``gpu_huffman`` not None (``infer_files``):
+        yields ``(lo, results, pool)``, and when it is true the results are ``jpegdec.load_file_bytes``'s, in a ring of byte buffers."""
         from concurrent.futures import ThreadPoolExecutor
         from . import jpegdec
         from .infer import DECODE_THREADS
@@ -372,16 +406,25 @@ class RoomNet:
             if ring is not None:
                 ring.close()
             ring = self._jpeg_ring = jpegdec.CoeffRing(2 * chunk)
+        loader = jpegdec.load_file
+        if gpu_huffman:
+            ring = getattr(self, "_jpeg_byte_ring", None)
+            if ring is None or len(ring) < 2 * chunk:
+                if ring is not None:
+                    ring.close()
+                ring = self._jpeg_byte_ring = jpegdec.ByteRing(2 * chunk)
+            loader = jpegdec.load_file_bytes
         n_chunks = (n + chunk - 1) // chunk
         with ThreadPoolExecutor(max_workers=nthreads) as pool:
             def submit(k):
                 # chunk k decodes into bank k % 2 of the ring: that bank was chunk k - 2's, which the consumer was done with when it asked for chunk k - 1
                 lo = k * chunk
-                return [pool.submit(jpegdec.load_file, paths[i], ring, (k % 2) * chunk + i - lo) for i in range(lo, min(n, lo + chunk))]
+                return [pool.submit(loader, paths[i], ring, (k % 2) * chunk + i - lo) for i in range(lo, min(n, lo + chunk))]
             ahead = submit(0)
             for k in range(n_chunks):
                 cur, ahead = ahead, (submit(k + 1) if k + 1 < n_chunks else [])
-                yield k * chunk, [f.result() for f in cur]
+                res = [f.result() for f in cur]
+                yield (k * chunk, res) if gpu_huffman is None else (k * chunk, res, pool)
 
     def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64, heatmap=None,
                               heatmap_weight=0.5):

@@ -12,6 +12,10 @@
         decode, host overlay and re-encode on the pool) against overlay=True, gpu_decode=True, gpu_encode=True on the same files,
         alternating, three times each after a warm-up of both; the host Huffman-encode pass alone on one thread and the device time
         of the overlay + encode launches per batch; a line with the rates, the ratio and whether the files are identical
+  python tools/bench_images.py --dir --gpu-huffman [--threads=T] [H W [N]]    a generated directory again, nothing of the above: both
+        drivers with gpu_decode=True against gpu_decode=True, gpu_huffman=True (the Huffman pass on the GPU too)
+        on the same files, alternating, three runs each after a warm-up of both; the ratio, the host's share per file and thread in
+        both arms, the device time of the Huffman launches per batch, the synchronisation rounds, the count of host fallbacks
   python tools/bench_images.py --heatmap [--threads=T] [H W [N]]    a generated directory again, nothing of the above: the device time
         of the two heat-map launches (rn_cam_last_overlay_ms) for one batch and both layers, next to the decode's and the encode's
         pixel stages of the same batch; then classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True) with heatmap="s6.bn",
@@ -294,8 +298,82 @@ def heatmap_arm():
     shutil.rmtree(root, ignore_errors=True)
 
 
+def gpu_huffman_arm():
+    """gpu_decode=True against gpu_decode=True, gpu_huffman=True: same files, same session, alternating."""
+    from roomnet_amd import infer, jpegdec
+    root, d, nn, paths, mb = generated_directory()
+    lst = os.path.join(root, 'list.txt')
+    with open(lst, 'w') as f:
+        f.writelines('%s %d\n' % (p, 0) for p in paths)
+    import sklearn.metrics  # noqa: F401
+    arms = {'host Huffman': dict(gpu_decode=True), 'GPU Huffman': dict(gpu_decode=True, gpu_huffman=True)}
+    t_dir = {a: [] for a in arms}
+    t_val = {a: [] for a in arms}
+    xls, fallbacks = {}, 0
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):
+        for rep_ in range(4):                                  # round 0 is the warm-up of both arms
+            for arm, kw in arms.items():
+                t0 = time.perf_counter()
+                xl = infer.classify_im_dir(nn, d, overlay=False, batch_size=64, **kw)
+                t1 = time.perf_counter()
+                fallbacks += getattr(nn, 'huffman_fallbacks', 0) if 'gpu_huffman' in kw else 0
+                with open(xl, 'rb') as f:
+                    xls[arm] = f.read()
+                t2 = time.perf_counter()
+                infer.groundtruth_validation(nn, lst, batch_size=64, **kw)
+                t3 = time.perf_counter()
+                fallbacks += getattr(nn, 'huffman_fallbacks', 0) if 'gpu_huffman' in kw else 0
+                if rep_:
+                    t_dir[arm].append(t1 - t0)
+                    t_val[arm].append(t3 - t2)
+    # the host's share per file, one thread: read + marker walk + Huffman pass against read + marker walks
+    ring_c, ring_b = jpegdec.CoeffRing(1), jpegdec.ByteRing(1)
+    t0 = time.perf_counter()
+    for p in paths:
+        assert jpegdec.load_file(p, ring_c, 0)[0] == 'jpeg'
+    t_host = (time.perf_counter() - t0) / len(paths)
+    t0 = time.perf_counter()
+    for p in paths:
+        assert jpegdec.load_file_bytes(p, ring_b, 0)[0] == 'file'
+    t_bytes = (time.perf_counter() - t0) / len(paths)
+    # the device's share: the Huffman launches of one batch, median of 5 calls, and the rounds phase 2 took
+    eng = nn._engine()
+    n = min(len(paths), eng.max_batch)
+    rings = jpegdec.ByteRing(n)
+    items = [jpegdec.load_file_bytes(p, rings, k)[1:] for k, p in enumerate(paths[:n])]
+    ms, px = [], []
+    for _ in range(5):
+        _ids, _probs, status = eng.classify_jpeg_files(items)
+        assert not status.any()
+        ms.append(eng.jpeg_last_huffman_ms())
+        px.append(eng.jpeg_last_decode_ms())
+    inside, across = eng.jpeg_last_huffman_rounds(n)
+    ms, px = sorted(ms)[2], sorted(px)[2]
+    med = lambda t: sorted(t)[len(t) // 2]
+    N_ = len(paths)
+    scan_mb = sum(int(it[1].scan_len) for it in items) / 1e6
+    coef_mb = sum(jpegdec.coeff_count(it[0]) for it in items) * 2 / 1e6
+    print('%d JPEG files %dx%d (%.0f MB), %d decode threads of %d host cores, same files, same session, alternating, 3 runs each after a '
+          'warm-up of both:' % (N_, W, H, mb, infer.DECODE_THREADS, os.cpu_count() or 1))
+    for arm in arms:
+        print('  %-12s classify_im_dir(overlay=False) %s img/s   groundtruth_validation %s img/s' % (
+            arm + ':', ' / '.join('%.1f' % (N_ / x) for x in t_dir[arm]), ' / '.join('%.1f' % (N_ / x) for x in t_val[arm])))
+    print('  ratio GPU Huffman / host Huffman (medians): classify_im_dir x%.2f   groundtruth_validation x%.2f   workbook identical: %s   '
+          'host fallbacks: %d' % (med(t_dir['host Huffman']) / med(t_dir['GPU Huffman']), med(t_val['host Huffman']) / med(t_val['GPU Huffman']),
+                                  xls['host Huffman'] == xls['GPU Huffman'], fallbacks))
+    print('  host share per file, one thread: %.3f ms with the Huffman pass, %.3f ms without (file read + marker walks)   upload per batch '
+          'of %d: %.1f MB of scan bytes instead of %.1f MB of coefficients' % (1e3 * t_host, 1e3 * t_bytes, n, scan_mb, coef_mb))
+    print('  Huffman launches on the device: %.3f ms per batch of %d (%.1f us per image; pixel stage %.3f ms)   sync rounds per image: '
+          'inside groups median %d, most %d; across groups median %d, most %d'
+          % (ms, n, 1e3 * ms / n, px, int(np.median(inside)), int(inside.max()), int(np.median(across)), int(across.max())))
+    shutil.rmtree(root, ignore_errors=True)
+
+
 if '--heatmap' in sys.argv:
     heatmap_arm()
+elif '--dir' in sys.argv and '--gpu-huffman' in sys.argv:
+    gpu_huffman_arm()
 elif '--dir' in sys.argv:
     directory()
 else:

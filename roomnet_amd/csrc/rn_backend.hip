@@ -52,12 +52,12 @@ static_assert(B_LDS <= 160 * 1024, "LDS budget");
 struct BackendArgs {
     // stage 6
     const unsigned short* in;     // [N, W, W, 64]
-    const i32x4* wfrag6;          // rn_stage6x_pack
+    const i32x4* wfrag6;          // rn_pack_k32: [18][8][64 lanes]
     const float* ptab6;           // folded BN: scale[128], shift[128]
-    const float* cstart6;         // K48 (null otherwise): wfrag6 = rn_stage6x_pack48's fragments, cstart6[cout] = the constant input channels' sum
+    const float* cstart6;         // K48 (null otherwise): wfrag6 = rn_pack_k48's fragments, cstart6[cout] = the constant input channels' sum
     int W, Wo;                    // stage-6 input / output side
     // stage 7
-    const i32x4* wfrag7;          // rn_conv16p_pack: [36][64 lanes]
+    const i32x4* wfrag7;          // rn_pack_k32: [36][64 lanes]
     const float* ptab7;           // folded BN: scale[16] (inv / 16), shift[16]
     int So7;
     TailArgs tail;

@@ -375,28 +375,9 @@ bool rn_conv16_supported(int cin, int cout, int pool_k, bool res) { return cin =
 
 int rn_conv16_colblocks(int out_side) { return (out_side + C16_BLKW - 1) / C16_BLKW; }
 
-// A-operand fragments: frag[chunk c][cout tile t][lane][j] = W[k = 32 c + 8 (lane / 16) + j][cout = 16 t + lane % 16]
-// (k = tap * 64 + channel, the HWIO order of the checkpoint)
-void rn_conv16_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(C16_KC) * 8 * 64 * 8, 0);
-    for (int c = 0; c < C16_KC; ++c)
-        for (int t = 0; t < 8; ++t)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * c + 8 * (l >> 4) + j, co = 16 * t + (l & 15);
-                    const float v = w_hwio[static_cast<size_t>(k) * C16_COUT + co];
-                    (*out)[((static_cast<size_t>(c) * 8 + t) * 64 + l) * 8 + j] = rn_to16(v, dtype);
-                }
-}
-
+// (A-operand fragments: rn_pack_k32, 18 chunks x 8 cout tiles)
 int rn_conv16_launch(int dtype, hipStream_t s, const Conv16Args& a, int n) {
-    auto launch = [&](auto kern) -> int {
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_colblocks, n), dim3(256), C16_LDS, s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
-    if (dtype == RN_DTYPE_BF16) return launch(conv16_kernel<RN_DTYPE_BF16>);
-    return launch(conv16_kernel<RN_DTYPE_F16>);
+    return rn_launch16<conv16_kernel<RN_DTYPE_BF16>, conv16_kernel<RN_DTYPE_F16>, false>(dtype, dim3(a.n_bands * a.n_colblocks, n), 256, C16_LDS, s, a);
 }
 
 bool rn_conv16p_supported(int cin, int cout, int pool_k, int pool_s, bool res) {
@@ -411,30 +392,9 @@ int rn_conv16p_colblocks(int out_side) {
     return (out_side + blko - 1) / blko;
 }
 
-// A-operand fragments: frag[chunk c][lane][j] = W[k = 32 c + 8 (lane / 16) + j][cout = lane % 16]
-void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(P16_KC) * 64 * 8, 0);
-    for (int c = 0; c < P16_KC; ++c)
-        for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-                const int k = 32 * c + 8 * (l >> 4) + j, co = l & 15;
-                const float v = w_hwio[static_cast<size_t>(k) * P16_COUT + co];
-                (*out)[(static_cast<size_t>(c) * 64 + l) * 8 + j] = rn_to16(v, dtype);
-            }
-}
-
+// (A-operand fragments: rn_pack_k32, 36 chunks x 1 cout tile)
 int rn_conv16p_launch(int dtype, hipStream_t s, const Conv16Args& a, int n) {
-    const int nt = conv16p_nt(a.Wo);
-    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
-        if (int rc = rn_allow_big_lds<Kern>()) return rc;
-        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_colblocks, n), dim3(64 * nt), static_cast<size_t>(nt == 3 ? P16<3>::LDS : P16<5>::LDS), s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
-    if (nt == 3) {
-        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<conv16p_kernel<RN_DTYPE_BF16, 3>>{});
-        return launch(rn_kernel<conv16p_kernel<RN_DTYPE_F16, 3>>{});
-    }
-    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<conv16p_kernel<RN_DTYPE_BF16, 5>>{});
-    return launch(rn_kernel<conv16p_kernel<RN_DTYPE_F16, 5>>{});
+    const dim3 grid(a.n_bands * a.n_colblocks, n);
+    if (conv16p_nt(a.Wo) == 3) return rn_launch16<conv16p_kernel<RN_DTYPE_BF16, 3>, conv16p_kernel<RN_DTYPE_F16, 3>, true>(dtype, grid, 64 * 3, P16<3>::LDS, s, a);
+    return rn_launch16<conv16p_kernel<RN_DTYPE_BF16, 5>, conv16p_kernel<RN_DTYPE_F16, 5>, true>(dtype, grid, 64 * 5, P16<5>::LDS, s, a);
 }

@@ -70,36 +70,27 @@ void rn_stage23x_pack_narrow(const float* w_hwio, const int* ring_cin, int dtype
 void rn_stage23x_pack_narrow8(const float* w_hwio, const int* ring_cin, int dtype, std::vector<unsigned short>* out);
 int rn_stage23x_launch(int dtype, hipStream_t s, const rnk::Stage23Args& a, int n);
 
-// ---- 16x16x32 matrix tiles without row-register blocking (rn_conv16.hip): the un-pooled 64 -> 128 stage ...
+// ---- 16x16x32 matrix tiles (weight fragments: rn_pack.h) without row-register blocking (rn_conv16.hip): the un-pooled 64 -> 128 stage ...
 bool rn_conv16_supported(int cin, int cout, int pool_k, bool res);
 int rn_conv16_colblocks(int out_side);
-void rn_conv16_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_conv16_launch(int dtype, hipStream_t s, const rnk::Conv16Args& a, int n);
 // ... and the 128 -> 16 stage with avg-pool 4/2 (one wave = one 16-pixel tile x all 16 couts, no K split)
 bool rn_conv16p_supported(int cin, int cout, int pool_k, int pool_s, bool res);
 int rn_conv16p_colblocks(int out_side);
 int rn_conv16p_wgs_per_cu(int out_side);
-void rn_conv16p_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_conv16p_launch(int dtype, hipStream_t s, const rnk::Conv16Args& a, int n);
 
-// ---- 16x16x32 tiles with row-register blocking.  rn_stage4x.hip: the 32 -> 64 stage with pool 4/2
+// ---- 16x16x32 tiles with row-register blocking (shared device pieces: rn_rowreg.h).  rn_stage4x.hip: the 32 -> 64 stage with pool 4/2
 bool rn_stage4x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side);
 bool rn_stage4x_plan(int out_side, int* n_cb, int* xo0, int* wo);       // column blocks (xo0, wo: 4 entries)
-void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage4x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // rn_stage5x.hip: the 64 -> 64 residual stage with pool 4/2
 bool rn_stage5x_supported(int cin, int cout, int pool_k, int pool_s, bool res, int in_side, int skip_side);
 bool rn_stage5x_plan(int out_side, int* n_cb, int* xo0, int* wo);
-void rn_stage5x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-// ... without its input channels 48..63 (constants on the handle): 15 fragments per cout quarter (StageArgs::cstart carries their sum)
-void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage5x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 // rn_stage6x.hip: the un-pooled 64 -> 128 stage
 bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side);
 bool rn_stage6x_plan(int out_side, int* n_cb, int* xo0, int* wo);
-void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
-// ... without its input channels 48..63 (constants of the handle): StageArgs::cstart carries their sum
-void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out);
 int rn_stage6x_launch(int dtype, hipStream_t s, const rnk::StageArgs& a, int n);
 
 // ---- float32 conv stages on the matrix cores (rn_stage_f32m.hip): the throughput path of RN_DTYPE_F32 handles without RN_FLAG_TAPS

@@ -3,6 +3,7 @@
 // walks the stages, adds what depends on the call (the bands of this batch size, the image pointer) and launches.
 #include "rn_fused.h"
 #include "rn_clock.h"
+#include "rn_pack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -354,11 +355,11 @@ static int bind_stage_args(rn_handle* h, const FusedState* fs, size_t i, FusedSt
     std::vector<unsigned short> frag;
     bool (*row_plan)(int, int*, int*, int*) = nullptr;
     switch (f->family) {
-    case Family::Conv16: rn_conv16_pack(wq, h->dtype, &frag); break;
-    case Family::Conv16P: rn_conv16p_pack(wq, h->dtype, &frag); break;
-    case Family::Row4x: rn_stage4x_pack(wq, h->dtype, &frag), row_plan = rn_stage4x_plan; break;
-    case Family::Row5x: rn_stage5x_pack(wq, h->dtype, &frag), row_plan = rn_stage5x_plan; break;
-    case Family::Row6x: rn_stage6x_pack(wq, h->dtype, &frag), row_plan = rn_stage6x_plan; break;
+    case Family::Row4x: row_plan = rn_stage4x_plan; break;
+    case Family::Row5x: row_plan = rn_stage5x_plan; break;
+    case Family::Row6x: row_plan = rn_stage6x_plan; break;
+    case Family::Conv16:
+    case Family::Conv16P: break;
     case Family::Generic:
         a.n_colblocks = f->gen.n_colblocks;
         a.n_ctg = f->gen.n_ctg;
@@ -377,6 +378,8 @@ static int bind_stage_args(rn_handle* h, const FusedState* fs, size_t i, FusedSt
         a.n_ctg = 1;
         break;
     }
+    // the families on 16x16x32 tiles: K chunks of 32 (rn_pack.h)
+    if (row_plan || f->conv16()) rn_pack_k32(wq, 9 * s.cin / 32, s.cout, h->dtype, &frag);
     if (int rc = frag.empty() ? RN_OK : upload16(h, frag, &f->family_wfrag)) return rc;
     if (f->conv16()) {
         f->c16 = Conv16Args{nullptr, nullptr, f->family_wfrag, f->ptab, s.in_side, s.in_side, s.out_side, s.out_side, 0, 0,
@@ -467,9 +470,9 @@ static int prepare_const_channels(rn_handle* h, FusedState* fs) {
     // a stage without its 16 constant input channels (positions 48..63; the residual stage: 15 fragments per cout quarter instead of
     // 18): fragments that leave them out -- they replace prepare_stage's, which stay allocated until rn_destroy: whether the fold
     // holds is known only when every stage has its family -- and what they add to every conv output, the accumulators' start value
-    auto drop_inputs = [&](FusedStage& f, int cout, const unsigned short* vals, auto pack48) {
+    auto drop_inputs = [&](FusedStage& f, int cout, const unsigned short* vals) {
         std::vector<unsigned short> f16;
-        pack48(f.wq.data(), h->dtype, &f16);
+        rn_pack_k48(f.wq.data(), cout, h->dtype, &f16);
         if (int e = upload16(h, f16, &f.family_wfrag)) return e;
         const std::vector<float> cst = const_sum48(f.wq.data(), cout, vals, h->dtype);
         float* d_cst = nullptr;
@@ -480,10 +483,10 @@ static int prepare_const_channels(rn_handle* h, FusedState* fs) {
     };
     f4.args.live_q = 3;                  // its last cout quarter is constant
     f4.args.cvals = d_vals;
-    if ((rc = drop_inputs(f5, 64, fs->const_val[0], rn_stage5x_pack48)) != RN_OK) return rc;
+    if ((rc = drop_inputs(f5, 64, fs->const_val[0])) != RN_OK) return rc;
     f5.args.cvals = d_vals + 16;
     // the stage behind it likewise: the residual stage's output channels 48..63 are constants (const5_val)
-    if (f6.family == Family::Row6x) return drop_inputs(f6, 128, fs->const_val[1], rn_stage6x_pack48);
+    if (f6.family == Family::Row6x) return drop_inputs(f6, 128, fs->const_val[1]);
     return RN_OK;
 }
 

@@ -59,6 +59,19 @@ int rn_allow_big_lds() {
 // names a kernel instantiation as a value, for launch lambdas:  launch(rn_kernel<my_kernel<RN_DTYPE_BF16>>{})
 template <auto Kern>
 struct rn_kernel {};
+// Launches the instantiation of a 16-bit kernel for the handle's storage type (RN_DTYPE_BF16: KernBF16, otherwise KernF16) with one
+// argument block.  BIG_LDS: the kernel's dynamic LDS can exceed 64 KB (rn_allow_big_lds first).
+template <auto KernBF16, auto KernF16, bool BIG_LDS, class Args>
+int rn_launch16(int dtype, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args& a) {
+    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
+        if constexpr (BIG_LDS)
+            if (int rc = rn_allow_big_lds<Kern>()) return rc;
+        hipLaunchKernelGGL(Kern, grid, block, lds_bytes, s, a);
+        RN_CHECK_LAUNCH();
+        return RN_OK;
+    };
+    return dtype == RN_DTYPE_BF16 ? launch(rn_kernel<KernBF16>{}) : launch(rn_kernel<KernF16>{});
+}
 
 // Makes `dev` the current HIP device and puts the caller's back on scope exit; `ok` = the device could be set.  Without an
 // argument it only restores (the group entry points walk several devices).
@@ -343,68 +356,5 @@ struct RelabelledWeights {
 bool rn_fold_block_at(const rn_weights* w, int r);
 void rn_fold_block_register(rn_handle* h, int r, const std::vector<int>& pi);      // its two tensors' entries in rn_handle::node_perm
 
-// ---- the 16-bit storage types on the host: round to nearest even, and back
-inline unsigned short f32_to_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<unsigned short>((u >> 16) | 0x40);   // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return static_cast<unsigned short>(u >> 16);
-}
-
-inline unsigned short f32_to_f16(float f) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return static_cast<unsigned short>(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0));
-    if (x >= 0x477ff000u) return static_cast<unsigned short>(sign | 0x7c00u);          // overflow -> inf
-    if (x < 0x33000001u) return static_cast<unsigned short>(sign);                     // underflow -> 0
-    int e = static_cast<int>(x >> 23) - 127;
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;
-    int shift;
-    if (e < -14) {
-        shift = 13 + (-14 - e);
-        e = -15;
-    } else {
-        shift = 13;
-    }
-    uint32_t half = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (half & 1))) ++half;
-    uint32_t out;
-    if (e == -15)
-        out = half;                                   // subnormal (may carry into exponent 1)
-    else
-        out = (static_cast<uint32_t>(e + 15) << 10) + (half - 0x400u);
-    return static_cast<unsigned short>(sign | out);
-}
-
-inline float bf16_bits_to_f32(unsigned short u) {
-    const unsigned bits = static_cast<unsigned>(u) << 16;
-    float f;
-    std::memcpy(&f, &bits, 4);
-    return f;
-}
-
-inline float f16_to_f32(unsigned short h) {
-    const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16;
-    const int e = (h >> 10) & 0x1f;
-    const uint32_t m = h & 0x3ffu;
-    float mag;
-    if (e == 0)
-        mag = std::ldexp(static_cast<float>(m), -24);                    // zero / subnormal
-    else if (e == 31)
-        mag = m ? std::nanf("") : INFINITY;
-    else
-        mag = std::ldexp(static_cast<float>(m | 0x400u), e - 25);
-    uint32_t u;
-    std::memcpy(&u, &mag, 4);
-    u |= sign;
-    std::memcpy(&mag, &u, 4);
-    return mag;
-}
-
-// a handle's storage type (RN_DTYPE_BF16 / RN_DTYPE_F16)
-inline unsigned short rn_to16(float v, int dtype) { return dtype == RN_DTYPE_BF16 ? f32_to_bf16(v) : f32_to_f16(v); }
-inline float rn_from16(unsigned short u, int dtype) { return dtype == RN_DTYPE_BF16 ? bf16_bits_to_f32(u) : f16_to_f32(u); }
+// ---- the 16-bit storage types on the host (rn_to16, rn_from16 and the four conversions under them): rn_host16.h
+#include "rn_host16.h"

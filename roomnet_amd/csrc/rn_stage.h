@@ -346,7 +346,7 @@ struct StageArgs {
     // rn_stage4x.hip: 3 = the channels of the last quarter are constants in the handle's 16-bit store, filled once at rn_create
     // (rn_fused_post_alloc) and not computed (twelve-wave form).
     int live_q;
-    // rn_stage5x.hip (with live_q == 2): non-null = the input channels 48..63 are such constants; wfrag = rn_stage5x_pack48's
+    // rn_stage5x.hip (with live_q == 2): non-null = the input channels 48..63 are such constants; wfrag = rn_pack_k48's
     // fragments, cstart[cout] = what the constants add to every conv output (the accumulators' start value), and the waves of the
     // last quarter -- whose output channels are constants too -- do nothing.
     const float* cstart;
@@ -410,7 +410,7 @@ struct Stage23Args {
 struct Conv16Args {
     const unsigned short* in;     // [N, H, W, 64]
     unsigned short* out;          // [N, Ho, Wo, 128]
-    const i32x4* wfrag;           // [18 chunks][8 cout tiles][64 lanes] A-operand fragments (rn_conv16_pack)
+    const i32x4* wfrag;           // [18 chunks][8 cout tiles][64 lanes] A-operand fragments (rn_pack_k32)
     const float* ptab;            // folded BN: scale[128], shift[128]
     int H, W, Ho, Wo;
     int rows_per_band, n_bands, n_colblocks;

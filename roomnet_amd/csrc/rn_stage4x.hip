@@ -1,5 +1,5 @@
 // 32 -> 64 stage with avg-pool 4/2 (reference network.py:228, first step of conv_block(64, pool 4/2, depth 2)) on 16x16x32
-// matrix tiles with ROW-REGISTER BLOCKING -- the design of rn_stage5x.hip without the residual:
+// matrix tiles with ROW-REGISTER BLOCKING (the shared pieces: rn_rowreg.h) -- rn_stage5x.hip without the residual:
 //
 //   in [N, W, W, 32] -> conv3x3 VALID -> ReLU6 -> avg-pool 4x4 stride 2 -> BN  = out [N, Wo, Wo, 64]
 //
@@ -21,9 +21,7 @@
 // the whole row of the 224 x 224 network, two blocks at 420, three at 600; rn_colblock_plan).  Blocks do not overlap in the
 // output; the 4 halo columns of a block's input are read by both neighbours.
 #include "rn_fused.h"
-#include "rn_stage.h"
-
-#include <utility>
+#include "rn_rowreg.h"
 
 using namespace rnk;
 
@@ -69,12 +67,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
 
     char* const ring = smem + U_RING_OFF;
     const unsigned ring_lds = lds_addr(ring);
-    // pixels W .. 207 of every slot are never written by the row DMA: zero them once
-    for (int i = tid; i < U_NS * (U_RINGPX - U_WMIN) * 4; i += U_NTH) {
-        const int slot = i / ((U_RINGPX - U_WMIN) * 4), rest = i % ((U_RINGPX - U_WMIN) * 4);
-        const int p = U_WMIN + rest / 4, c = rest % 4;
-        if (p >= W) *reinterpret_cast<i32x4*>(ring + slot * U_ROW + p * 64 + c * 16) = i32x4{0, 0, 0, 0};
-    }
+    RN_ZERO_RING_TAIL(ring, W, tid, U_NS, U_RINGPX, U_WMIN, 4, U_NTH);
 
     // ---- this wave's tiles.  NQ = 4: run 0 = 7 tiles from column 0 (55 pooled columns), run 1 = 6 tiles from column 110 (47
     // pooled columns from 55).  NQ = 3: run 0 = 4 tiles (31 pooled columns), runs 1..3 = 3 tiles (23 each, from 31 / 54 / 77).
@@ -85,12 +78,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
     const int nout_run = NQ == 4 ? (has7 ? 55 : 47) : (has7 ? 31 : 23);
 
     // ---- weights: fragment f = ky * 3 + kx (all 32 channels of the tap), B operand of D'[pixel][cout]
-    i32x4 wf[9];
-#pragma unroll
-    for (int f = 0; f < 9; ++f) {
-        const i32x4* src = a.wfrag + (f * 4 + cq) * 64 + lane;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wf[f]) : "v"(src) : "memory");
-    }
+    RN_LOAD_WFRAGS(wf, 9, a.wfrag, 4, cq, lane);
 
     // ---- input rows by LDS-DMA: piece 0 = chunks tid (pixels 0..127); piece 1 = the remaining (W - 128) x 4 chunks, dealt
     // ceil(/8) to each wave, lane-masked (every wave keeps at least one active lane for W >= 193)
@@ -173,8 +161,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
 #pragma unroll
     for (int t = 0; t < 3; ++t) sd[t] = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + t + 1);
     wait_vmcnt<0>();
-#pragma unroll
-    for (int f = 0; f < 9; ++f) asm volatile("" : "+v"(wf[f]));
+    RN_PIN_WFRAGS(wf, 9);
     lds_barrier();
 
     // operand fragments double-buffered across tiles: tile k + 1's three reads go out before tile k's MFMAs (a tile's
@@ -215,35 +202,15 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
             constexpr int k = decltype(KC)::value;
             constexpr bool NEXT = decltype(NEXTC)::value != 0;        // tile k + 1's reads are issued here (3 more in flight)
             if constexpr (NEXT) reads_at(IC<k + 1>{}, IC<SLOT>{});
-            auto& cur = fq[k & 1];
-            [&]<int... F>(std::integer_sequence<int, F...>) {
-                (([&] {
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(cur[F]) : "n"((NEXT ? 3 : 0) + 2 - F));
-                     acc[iN][k] = mfma16<DT>(cur[F], wf[0 * 3 + F], F == 0 ? zero4 : acc[iN][k]);
-                     acc[iM][k] = mfma16<DT>(cur[F], wf[1 * 3 + F], acc[iM][k]);
-                     acc[iO][k] = mfma16<DT>(cur[F], wf[2 * 3 + F], acc[iO][k]);
-                     if constexpr (k == 0 && F == 0) {
-                         // the row DMA rides behind the step's first MFMAs: into the slot of row s - 1 (everybody is past it)
-                         issue_row(in_row, IC<(SLOT + U_AHEAD) % U_NS>{});
-                         in_row += in_adv;
-                     }
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 3>{});
-            // conv row j = s - 2 of this tile is complete: ReLU6 -> fp16 pairs; even rows wait in hp, odd rows form the pair
-            // sum and the pooling operand [previous pair sum | this pair sum]
-            const f32x4 v = acc[iO][k];
-            const int v0 = static_cast<int>(pack2_relu6_sixth(v[0], v[1]));
-            const int v1 = static_cast<int>(pack2_relu6_sixth(v[2], v[3]));
-            if constexpr (PAR == 0) {
-                hp[k][0] = v0;
-                hp[k][1] = v1;
-            } else {
-                const int n0 = pk_add_f16(hp[k][0], v0), n1 = pk_add_f16(hp[k][1], v1);
-                op[k] = i32x4{pp2[k][0], pp2[k][1], n0, n1};
-                pp2[k][0] = n0;
-                pp2[k][1] = n1;
-            }
+            // (the row DMA rides behind the step's first MFMAs: into the slot of row s - 1 -- everybody is past it)
+            frag_chain<DT, false, (NEXT ? 3 : 0), true, 3, 0, 1>(fq[k & 1], wf, acc[iN][k], acc[iM][k], acc[iO][k], zero4, [&](auto FC) __attribute__((always_inline)) {
+                if constexpr (k == 0 && decltype(FC)::value == 0) {
+                    issue_row(in_row, IC<(SLOT + U_AHEAD) % U_NS>{});
+                    in_row += in_adv;
+                }
+            });
+            // conv row j = s - 2 of this tile is complete: its pooling operand
+            pool_rows<PAR>(acc[iO][k], hp[k], pp2[k], op[k]);
         };
         [&]<int... K>(std::integer_sequence<int, K...>) {
             (tile(IC<K>{}, IC<(K + 1 < NTW ? 1 : 0)>{}), ...);
@@ -262,11 +229,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
                 float y[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) y[i] = __builtin_fmaf(H[i], sc[i], sh[i]);
-                i32x2 d;
-                if constexpr (DT == RN_DTYPE_BF16)
-                    d = i32x2{static_cast<int>(pack2_sr_bf16(y[0], y[1], seed)), static_cast<int>(pack2_sr_bf16(y[2], y[3], seed))};
-                else
-                    d = i32x2{static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
+                const i32x2 d = pack_out<DT>(y, seed);
                 const int vo = EARLY ? (voff[u] | early) : voff[u];
                 __builtin_amdgcn_raw_buffer_store_b64(d, rs, vo, 0, 0);
                 if constexpr (NQ == 3)
@@ -287,10 +250,7 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
         // first tile of the next row (published by this step's barrier)
         reads_at(IC<0>{}, IC<(SLOT + 1) % U_NS>{});
     };
-    // The steady loop: periods of 12 steps = lcm(ring slots 4, accumulator rotation 3, row parity 2).  nin is even, so a band ends
-    // behind an odd step: the loop is left there (no tail code: its last period is cut short).  Per pair of steps one compare decides
-    // whether the row pointer still advances: even step s loads row s + 3 and moves on iff s + 4 <= nin - 1, odd step s + 1 iff
-    // s + 5 <= nin - 1 -- with left = nin - s even, both are left >= 6.
+    // The steady loop (steady_pairs, rn_rowreg.h): periods of 12 steps = lcm(ring slots 4, accumulator rotation 3, row parity 2)
     auto steady = [&](auto H7C) __attribute__((always_inline)) {
         // row 0 is published by the prologue's barrier only after every wave's pieces have landed: wait_vmcnt<0> above.  (Read here,
         // inside the instantiation: in front of the choice between the two the compiler copied the fragments' registers for one of
@@ -300,26 +260,11 @@ __global__ __launch_bounds__(NQ == 4 ? 512 : 768, NQ == 4 ? 2 : 3) void stage4x_
         // return` between pairs of steps and the loop's back edge -- have the same straight-line code (the previous step) on every
         // path that reaches them, so fq is one set of registers there; a new branch AROUND a reads_at would break that.
         reads_at(IC<0>{}, IC<0>{});
-        int left = nin;                   // steps still to run, this pair included
-        int early = OOB;
-        unsigned early_adv = 0;
-        for (;;) {
-            bool done = false;
-            [&]<int... P>(std::integer_sequence<int, P...>) {
-                (([&] {
-                     if (done) return;
-                     const unsigned in_adv = left >= 6 ? static_cast<unsigned>(row_bytes) : 0u;
-                     step(IC<2 * P>{}, H7C, in_adv, early, early_adv);
-                     step(IC<2 * P + 1>{}, H7C, in_adv, early, early_adv);
-                     left -= 2;
-                     done = left == 0;
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 6>{});
-            if (done) break;
-            early = 0;
-            early_adv = static_cast<unsigned>(out_row_bytes);
-        }
+        steady_pairs<6>(nin, row_bytes, static_cast<unsigned>(out_row_bytes), [&](auto PC, unsigned in_adv, int early, unsigned early_adv) __attribute__((always_inline)) {
+            constexpr int P = decltype(PC)::value;
+            step(IC<2 * P>{}, H7C, in_adv, early, early_adv);
+            step(IC<2 * P + 1>{}, H7C, in_adv, early, early_adv);
+        });
     };
     // the longest run's waves and the others run two instantiations of the loop, chosen once (wave-uniform)
     if (has7)
@@ -343,35 +288,11 @@ bool rn_stage4x_supported(int cin, int cout, int pool_k, int pool_s, bool res, i
            rn_stage4x_plan((in_side - 6) / 2 + 1, &ncb, xo0, wo);
 }
 
-// B-operand fragments: frag[f = ky * 3 + kx][cout quarter q][lane][j] = W[tap f][channel 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage4x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(9) * 4 * 64 * 8, 0);
-    for (int f = 0; f < 9; ++f)
-        for (int q = 0; q < 4; ++q)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = f * 32 + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
-                    const float v = w_hwio[static_cast<size_t>(k) * 64 + co];
-                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
-                }
-}
-
 int rn_stage4x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
-    int nthreads = 512;
-    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
-        if (int rc = rn_allow_big_lds<Kern>()) return rc;
-        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cb, n), dim3(nthreads), U_LDS, s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
+    const dim3 grid(a.n_bands * a.n_cb, n);
     // three live quarters (StageArgs::live_q == 3): the twelve-wave form pools 100 columns per block at most
     bool q3 = a.live_q == 3;
     for (int b = 0; b < a.n_cb; ++b) q3 = q3 && a.cb_wo[b] <= 100;
-    if (q3) {
-        nthreads = 768;
-        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage4x_kernel<RN_DTYPE_BF16, 3>>{});
-        return launch(rn_kernel<stage4x_kernel<RN_DTYPE_F16, 3>>{});
-    }
-    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage4x_kernel<RN_DTYPE_BF16, 4>>{});
-    return launch(rn_kernel<stage4x_kernel<RN_DTYPE_F16, 4>>{});
+    if (q3) return rn_launch16<stage4x_kernel<RN_DTYPE_BF16, 3>, stage4x_kernel<RN_DTYPE_F16, 3>, true>(dtype, grid, 768, U_LDS, s, a);
+    return rn_launch16<stage4x_kernel<RN_DTYPE_BF16, 4>, stage4x_kernel<RN_DTYPE_F16, 4>, true>(dtype, grid, 512, U_LDS, s, a);
 }

@@ -1,5 +1,5 @@
 // 64 -> 64 residual stage with avg-pool 4/2 (reference network.py:228, second step of conv_block(64, pool 4/2, depth 2)) on
-// 16x16x32 matrix tiles with ROW-REGISTER BLOCKING:
+// 16x16x32 matrix tiles with ROW-REGISTER BLOCKING (the shared pieces: rn_rowreg.h):
 //
 //   A = s4.bn [N, W, W, 64] -> conv3x3 VALID -> ReLU6 -> avg-pool 4x4 stride 2 -> BN -> + legacy-bilinear(A) -> BN  = out [N, Wo, Wo, 64]
 //
@@ -27,9 +27,7 @@
 // the whole row of the 224 x 224 network, three blocks at 600; rn_stage5x_plan checks that every block's skip columns lie
 // inside the input columns it stages).
 #include "rn_fused.h"
-#include "rn_stage.h"
-
-#include <utility>
+#include "rn_rowreg.h"
 
 using namespace rnk;
 
@@ -79,13 +77,7 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     if (tid < 256) tab[tid] = a.ptab[tid];
     char* const ring = smem + V_RING_OFF;
     const unsigned ring_lds = lds_addr(ring);
-    // pixels W .. 111 of every slot are never written by the row DMA: zero them once (the conv fragments of the discarded
-    // right-hand columns read them; uninitialised LDS could hold NaN patterns)
-    for (int i = tid; i < V_NS * (V_RINGPX - V_WMIN) * 8; i += 512) {
-        const int slot = i / ((V_RINGPX - V_WMIN) * 8), rest = i % ((V_RINGPX - V_WMIN) * 8);
-        const int p = V_WMIN + rest / 8, c = rest % 8;
-        if (p >= W) *reinterpret_cast<i32x4*>(ring + slot * V_ROW + p * 128 + c * 16) = i32x4{0, 0, 0, 0};
-    }
+    RN_ZERO_RING_TAIL(ring, W, tid, V_NS, V_RINGPX, V_WMIN, 8, 512);
 
     // ---- this wave's tiles: pixel half 0 = 4 tiles from column 0 (31 pooled columns), half 1 = 3 tiles from column 62
     // (23 pooled columns from 31): the runs overlap by the 2 columns a stride-2 window reaches across
@@ -94,13 +86,8 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
     const int xo_run = ph ? 31 : 0;
     const int nout_run = has4 ? 31 : 23;
 
-    // ---- weights: fragment f = (ky * 3 + kx) * 2 + ch (K48: ky * 5 + j, rn_stage5x_pack48), B operand of D'[pixel][cout]
-    i32x4 wf[3 * NF];
-#pragma unroll
-    for (int f = 0; f < 3 * NF; ++f) {
-        const i32x4* src = a.wfrag + (f * 4 + cq) * 64 + lane;      // (frozen quarters: loaded, never used)
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wf[f]) : "v"(src) : "memory");
-    }
+    // ---- weights: fragment f = (ky * 3 + kx) * 2 + ch (K48: ky * 5 + j, rn_pack_k48), B operand of D'[pixel][cout]
+    RN_LOAD_WFRAGS(wf, 3 * NF, a.wfrag, 4, cq, lane);             // (frozen quarters: loaded, never used)
 
     // ---- input rows by LDS-DMA: two pieces per wave and row (piece 0: chunks tid = pixels 0..63; piece 1: the remaining
     // (W - 64) x 8 chunks, W - 64 per wave, lane-masked)
@@ -123,24 +110,8 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
         dma16_masked(row + o1, ring + slot_off + (512 + wave * tailn) * 16, tail_mask);
     };
 
-    // ---- operand read bases (slot 0): tap column kx, channel half ch; tile k adds 16 pixels = 2048 bytes (same swizzle)
-    unsigned base[3][2];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            const int p = xw + px16 + kx;
-            base[kx][ch] = ring_lds + static_cast<unsigned>(p * 128 + (((4 * ch + g) ^ swz8(p)) << 4));
-        }
-    if constexpr (K48) {
-        // fragments 3, 4: channels 32..47 of two taps -- lane groups 0, 1 read chunks 4, 5 of tap column 0 (fragment 4: column 2),
-        // groups 2, 3 those of column 1 (fragment 4: zero weights; they read what groups 0, 1 read)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int p = xw + px16 + (j == 0 ? (g >> 1) : 2);
-            base[j][1] = ring_lds + static_cast<unsigned>(p * 128 + (((4 + (g & 1)) ^ swz8(p)) << 4));
-        }
-    }
+    // ---- operand read bases (slot 0)
+    RN_READ_BASES(base, K48, ring_lds, xw, px16, g);
 
     // ---- pooling band matrices (stride 2)
     RN_POOL_BANDS_S2(pmA, pmB, pmC, px16, g);
@@ -226,8 +197,7 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
 #pragma unroll
     for (int t = 0; t < 3; ++t) sd[t] = (!a.dither || cq == a.plain_q) ? RN_SEED_PLAIN : rn_dither_seed(yo0 + t + 1);
     wait_vmcnt<0>();
-#pragma unroll
-    for (int f = 0; f < 3 * NF; ++f) asm volatile("" : "+v"(wf[f]));
+    RN_PIN_WFRAGS(wf, 3 * NF);
     // K48: what the constant input channels add to every conv output of the lane's cout (D'[pixel][cout]: cout = lane % 16)
     f32x4 cst4 = zero4;
     if constexpr (K48) {
@@ -264,32 +234,15 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
         // batches AND tiles: batch b + 1's reads go out before batch b's nine MFMAs, so the LDS round trip never stands at
         // the head of a chain (a batch is only 9 MFMAs long)
         i32x4 fq[2][3];
-        // reads of batch b: three fragments (channel half 0), then three (half 1) -- K48: two (the merged fragments)
         auto reads = [&](auto BC) __attribute__((always_inline)) {
-            constexpr int b = decltype(BC)::value, k = b >> 1, ch = b & 1;
-            constexpr int NR = (K48 && ch) ? 2 : 3;
-            auto& dst = fq[b & 1];
-            auto& bcr = bc;                                            // (named outside the asm: implicit capture)
-#pragma unroll
-            for (int kx = 0; kx < NR; ++kx) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[kx]) : "v"(bcr[kx][ch]), "n"(k * 2048));
+            constexpr int b = decltype(BC)::value;
+            reads3<(b >> 1), (b & 1)>(fq[b & 1], bc);
         };
         auto batch = [&](auto BC, auto NEXTC) __attribute__((always_inline)) {
             constexpr int b = decltype(BC)::value, k = b >> 1, ch = b & 1;
-            constexpr bool NEXT = decltype(NEXTC)::value != 0;        // batch b + 1's reads are issued here
-            constexpr int NR = (K48 && ch) ? 2 : 3;                    // this batch's fragments
-            constexpr int NRN = NEXT ? ((K48 && !ch) ? 2 : 3) : 0;     // the next batch's, in flight behind them
+            constexpr bool NEXT = decltype(NEXTC)::value != 0;        // batch b + 1's reads are issued here (3 more in flight)
             if constexpr (NEXT) reads(IC<b + 1>{});
-            auto& cur = fq[b & 1];
-            [&]<int... KX>(std::integer_sequence<int, KX...>) {
-                (([&] {
-                     constexpr int fi = K48 ? (ch ? 3 + KX : KX) : KX * 2 + ch;      // fragment index inside a kernel row
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(cur[KX]) : "n"(NRN + NR - 1 - KX));
-                     acc[iN][k] = mfma16<DT>(cur[KX], wf[0 * NF + fi], (ch == 0 && KX == 0) ? cst4 : acc[iN][k]);
-                     acc[iM][k] = mfma16<DT>(cur[KX], wf[1 * NF + fi], acc[iM][k]);
-                     acc[iO][k] = mfma16<DT>(cur[KX], wf[2 * NF + fi], acc[iO][k]);
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, NR>{});
+            frag_chain<DT, false, (NEXT ? 3 : 0), ch == 0, 6, ch, 2>(fq[b & 1], wf, acc[iN][k], acc[iM][k], acc[iO][k], cst4);
         };
         auto tile = [&](auto KC, auto LASTC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
@@ -297,52 +250,28 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
             batch(IC<2 * k>{}, IC<1>{});
             batch(IC<2 * k + 1>{}, IC<(LAST ? 0 : 1)>{});
         };
-        // conv row j = s - 2 is complete in acc[iO] after the tile's chain: ReLU6 -> fp16 pairs; even rows wait in hp, odd
-        // rows form the pair sum and the pooling operand [previous pair sum | this pair sum]
+        // conv row j = s - 2 is complete in acc[iO] after the tile's chain: its pooling operand
         i32x4 op[4];
         op[3] = i32x4{0, 0, 0, 0};
         auto finish = [&](auto KC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
-            const f32x4 v = acc[iO][k];
-            const int v0 = static_cast<int>(pack2_relu6_sixth(v[0], v[1]));
-            const int v1 = static_cast<int>(pack2_relu6_sixth(v[2], v[3]));
-            if constexpr (PAR == 0) {
-                hp[k][0] = v0;
-                hp[k][1] = v1;
-            } else {
-                const int n0 = pk_add_f16(hp[k][0], v0), n1 = pk_add_f16(hp[k][1], v1);
-                op[k] = i32x4{pp2[k][0], pp2[k][1], n0, n1};
-                pp2[k][0] = n0;
-                pp2[k][1] = n1;
-            }
+            pool_rows<PAR>(acc[iO][k], hp[k], pp2[k], op[k]);
         };
         // K48: a tile's five fragments are ONE batch of 15 MFMAs, read a whole tile ahead (a (3, 2) split left the two-fragment batch's
         // six MFMAs = ~100 cycles to cover an LDS round trip: the stage ran 5 % slower than with 18 MFMAs per tile)
         i32x4 fq5[2][K48 ? 5 : 1];
-        auto reads5 = [&](auto KC) __attribute__((always_inline)) {
+        auto reads5k = [&](auto KC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
-            auto& dst = fq5[k & 1];
-            auto& bcr = bc;
-#pragma unroll
-            for (int f = 0; f < 5; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[f]) : "v"(f < 3 ? bcr[f][0] : bcr[f - 3][1]), "n"(k * 2048));
+            reads5<k>(fq5[k & 1], bc);
         };
         auto tile5 = [&](auto KC, auto NEXTC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
             constexpr bool NEXT = decltype(NEXTC)::value != 0;        // tile k + 1's reads are issued here (5 more in flight)
-            if constexpr (NEXT) reads5(IC<k + 1>{});
-            auto& cur = fq5[k & 1];
-            [&]<int... F>(std::integer_sequence<int, F...>) {
-                (([&] {
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(cur[F]) : "n"((NEXT ? 5 : 0) + 4 - F));
-                     acc[iN][k] = mfma16<DT>(cur[F], wf[0 * NF + F], F == 0 ? cst4 : acc[iN][k]);
-                     acc[iM][k] = mfma16<DT>(cur[F], wf[1 * NF + F], acc[iM][k]);
-                     acc[iO][k] = mfma16<DT>(cur[F], wf[2 * NF + F], acc[iO][k]);
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 5>{});
+            if constexpr (NEXT) reads5k(IC<k + 1>{});
+            frag_chain<DT, false, (NEXT ? 5 : 0), true, 5, 0, 1>(fq5[k & 1], wf, acc[iN][k], acc[iM][k], acc[iO][k], cst4);
         };
         if constexpr (K48 && CL) {
-            reads5(IC<0>{});
+            reads5k(IC<0>{});
             tile5(IC<0>{}, IC<1>{});
             finish(IC<0>{});
             tile5(IC<1>{}, IC<1>{});
@@ -428,12 +357,7 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
                     const float rsv = __builtin_fmaf(r_hi[i] - lo, yl, lo);
                     y[i] = __builtin_fmaf(rsv, sc2[i], y1);
                 }
-                i32x2 d;
-                if constexpr (DT == RN_DTYPE_BF16)
-                    d = i32x2{static_cast<int>(pack2_sr_bf16(y[0], y[1], seed)), static_cast<int>(pack2_sr_bf16(y[2], y[3], seed))};
-                else
-                    d = i32x2{static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
-                __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff[u] | emask, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(pack_out<DT>(y, seed), rs, voff[u] | emask, 0, 0);
             }
             const int adv = EARLY ? early_adv : 1;
             rr += adv;
@@ -444,31 +368,13 @@ __global__ __launch_bounds__(512, 2) void stage5x_kernel(const StageArgs a) {
         ++s;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-    // The steady loop: periods of 6 steps (accumulator rotation 3 x row parity 2).  nin is even, so a band ends behind an odd step: the
-    // loop is left there (no tail code: its last period is cut short).  Per pair of steps one compare decides whether the row pointer
-    // still advances: even step s loads row s + 3 and moves on iff s + 4 <= nin - 1, odd step s + 1 iff s + 5 <= nin - 1 -- with
-    // left = nin - s even, both are left >= 6.
+    // The steady loop (steady_pairs, rn_rowreg.h): periods of 6 steps (accumulator rotation 3 x row parity 2)
     auto steady = [&](auto CLC, auto H4C, auto ELC) __attribute__((always_inline)) {
-        int left = nin;                   // steps still to run, this pair included
-        int early = OOB, early_adv = 0;
-#pragma nounroll      // (the compiler would peel the first period off for its constant `early`: twice the code in the instruction cache)
-        for (;;) {
-            bool done = false;
-            [&]<int... P>(std::integer_sequence<int, P...>) {
-                (([&] {
-                     if (done) return;
-                     const unsigned in_adv = left >= 6 ? static_cast<unsigned>(row_bytes) : 0u;
-                     step(IC<2 * P>{}, CLC, H4C, ELC, in_adv, early, early_adv);
-                     step(IC<2 * P + 1>{}, CLC, H4C, ELC, in_adv, early, early_adv);
-                     left -= 2;
-                     done = left == 0;
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 3>{});
-            if (done) break;
-            early = 0;
-            early_adv = 1;
-        }
+        steady_pairs<3>(nin, row_bytes, 1, [&](auto PC, unsigned in_adv, int early, int early_adv) __attribute__((always_inline)) {
+            constexpr int P = decltype(PC)::value;
+            step(IC<2 * P>{}, CLC, H4C, ELC, in_adv, early, early_adv);
+            step(IC<2 * P + 1>{}, CLC, H4C, ELC, in_adv, early, early_adv);
+        });
     };
     // one instantiation of the loop per kind of wave, chosen once (wave-uniform): computing waves with four / three tiles, the frozen
     // quarters' waves (residual epilogue only) and, K48, the constant quarter's (stores only)
@@ -502,59 +408,8 @@ bool rn_stage5x_supported(int cin, int cout, int pool_k, int pool_s, bool res, i
            in_side - 2 * out_side <= 5 && rn_stage5x_plan(out_side, &ncb, xo0, wo);
 }
 
-// B-operand fragments: frag[f = (ky * 3 + kx) * 2 + ch][cout quarter q][lane][j] = W[tap ky * 3 + kx][channel 32 ch + 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage5x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(18) * 4 * 64 * 8, 0);
-    for (int f = 0; f < 18; ++f)
-        for (int q = 0; q < 4; ++q)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int tap = f >> 1, ch = f & 1;
-                    const int k = tap * 64 + 32 * ch + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
-                    const float v = w_hwio[static_cast<size_t>(k) * 64 + co];
-                    (*out)[((static_cast<size_t>(f) * 4 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
-                }
-}
-
-// K48 fragments: frag[f = ky * 5 + j][cout quarter q][lane][e]: j < 3 = W[tap (ky, kx = j)][channel 8 (lane / 16) + e]; j = 3: lane groups
-// 0, 1 = W[tap (ky, 0)][channel 32 + 8 g + e], groups 2, 3 = W[tap (ky, 1)][channel 32 + 8 (g - 2) + e]; j = 4: groups 0, 1 =
-// W[tap (ky, 2)][channel 32 + 8 g + e], groups 2, 3 = 0.  Channels 48..63 (constants on the handle) do not appear.
-void rn_stage5x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(15) * 4 * 64 * 8, 0);
-    for (int ky = 0; ky < 3; ++ky)
-        for (int j = 0; j < 5; ++j)
-            for (int q = 0; q < 4; ++q)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int g = l >> 4, co = 16 * q + (l & 15);
-                        int kx, ch;
-                        if (j < 3) {
-                            kx = j;
-                            ch = 8 * g + e;
-                        } else if (j == 3) {
-                            kx = g >> 1;
-                            ch = 32 + 8 * (g & 1) + e;
-                        } else {
-                            if (g >= 2) continue;
-                            kx = 2;
-                            ch = 32 + 8 * g + e;
-                        }
-                        const float v = w_hwio[(static_cast<size_t>(ky * 3 + kx) * 64 + ch) * 64 + co];
-                        (*out)[((static_cast<size_t>(ky * 5 + j) * 4 + q) * 64 + l) * 8 + e] = rn_to16(v, dtype);
-                    }
-}
-
 int rn_stage5x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
-    auto launch = [&]<auto Kern>(rn_kernel<Kern>) -> int {
-        if (int rc = rn_allow_big_lds<Kern>()) return rc;
-        hipLaunchKernelGGL(Kern, dim3(a.n_bands * a.n_cb, n), dim3(512), V_LDS, s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
-    if (a.cstart && a.live_q == 2) {
-        if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage5x_kernel<RN_DTYPE_BF16, true>>{});
-        return launch(rn_kernel<stage5x_kernel<RN_DTYPE_F16, true>>{});
-    }
-    if (dtype == RN_DTYPE_BF16) return launch(rn_kernel<stage5x_kernel<RN_DTYPE_BF16, false>>{});
-    return launch(rn_kernel<stage5x_kernel<RN_DTYPE_F16, false>>{});
+    const dim3 grid(a.n_bands * a.n_cb, n);
+    if (a.cstart && a.live_q == 2) return rn_launch16<stage5x_kernel<RN_DTYPE_BF16, true>, stage5x_kernel<RN_DTYPE_F16, true>, true>(dtype, grid, 512, V_LDS, s, a);
+    return rn_launch16<stage5x_kernel<RN_DTYPE_BF16, false>, stage5x_kernel<RN_DTYPE_F16, false>, true>(dtype, grid, 512, V_LDS, s, a);
 }

@@ -1,5 +1,5 @@
 // Un-pooled 64 -> 128 stage (reference network.py:229, conv_block(128, pooling=False)) on 16x16x32 matrix tiles with
-// ROW-REGISTER BLOCKING (the design of rn_stage4x.hip / rn_stage5x.hip):
+// ROW-REGISTER BLOCKING (the design and its shared pieces: rn_rowreg.h):
 //
 //   in [N, W, W, 64] -> conv3x3 VALID -> ReLU6 -> BN(inference)  = out [N, W-2, W-2, 128]
 //
@@ -12,16 +12,15 @@
 // Wider rows are cut into COLUMN BLOCKS of 33..48 output columns (rn_colblock_plan: one block at 224, three at 600):
 // workgroup = image x band x block.  conv16_kernel (rn_conv16.hip) stays as the RN_FLAG_PAIR_32X32 arm.
 #include "rn_fused.h"
-#include "rn_stage.h"
-
-#include <utility>
+#include "rn_rowreg.h"
 
 using namespace rnk;
 
 namespace {
 
 constexpr int S6_NS = 4, S6_AHEAD = 3;
-constexpr int S6_ROW = 52 * 128;                  // bytes per ring row (padded)
+constexpr int S6_RINGPX = 52;                     // pixels per ring row (padded)
+constexpr int S6_ROW = S6_RINGPX * 128;           // bytes per ring row
 constexpr int S6_LDS = S6_NS * S6_ROW;
 constexpr int S6_WMIN = 35, S6_WMAX = 50;
 
@@ -50,20 +49,10 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
 
     char* const ring = smem;
     const unsigned ring_lds = lds_addr(ring);
-    // pixels W .. 51 of every slot are never written by the row DMA: zero them once
-    for (int i = tid; i < S6_NS * (52 - S6_WMIN) * 8; i += 512) {
-        const int slot = i / ((52 - S6_WMIN) * 8), rest = i % ((52 - S6_WMIN) * 8);
-        const int p = S6_WMIN + rest / 8, c = rest % 8;
-        if (p >= W) *reinterpret_cast<i32x4*>(ring + slot * S6_ROW + p * 128 + c * 16) = i32x4{0, 0, 0, 0};
-    }
+    RN_ZERO_RING_TAIL(ring, W, tid, S6_NS, S6_RINGPX, S6_WMIN, 8, 512);
 
-    // ---- weights: fragment f = (ky * 3 + kx) * 2 + ch (K48: ky * 5 + j, rn_stage6x_pack48), A operand of D[cout][pixel]
-    i32x4 wf[3 * NF];
-#pragma unroll
-    for (int f = 0; f < 3 * NF; ++f) {
-        const i32x4* src = a.wfrag + (f * 8 + wave) * 64 + lane;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wf[f]) : "v"(src) : "memory");
-    }
+    // ---- weights: fragment f = (ky * 3 + kx) * 2 + ch (K48: ky * 5 + j, rn_pack_k48), A operand of D[cout][pixel]
+    RN_LOAD_WFRAGS(wf, 3 * NF, a.wfrag, 8, wave, lane);
 
     // ---- input rows by LDS-DMA: one lane-masked piece per wave and row (W x 8 chunks, W per wave)
     const char* const in_img = reinterpret_cast<const char*>(a.in + static_cast<int64_t>(n) * Win * Win * 64) + x0 * 128;
@@ -82,23 +71,9 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
         dma16_masked(row + o, ring + slot * S6_ROW + wave * W * 16, dma_mask);
     };
 
-    unsigned base[3][2];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            const int p = px16 + kx;
-            base[kx][ch] = ring_lds + static_cast<unsigned>(p * 128 + (((4 * ch + g) ^ swz8(p)) << 4));
-        }
+    RN_READ_BASES(base, K48, ring_lds, 0, px16, g);
     f32x4 cst4 = zero4;
-    if constexpr (K48) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {          // merged fragments: lane groups 0, 1 = chunks 4, 5 of tap column 0 (j = 1: 2), groups 2, 3 of column 1
-            const int p = px16 + (j == 0 ? (g >> 1) : 2);
-            base[j][1] = ring_lds + static_cast<unsigned>(p * 128 + (((4 + (g & 1)) ^ swz8(p)) << 4));
-        }
-        cst4 = *reinterpret_cast<const f32x4*>(a.cstart + 16 * wave + 4 * g);      // (D[cout][pixel]: the lane's 4 couts)
-    }
+    if constexpr (K48) cst4 = *reinterpret_cast<const f32x4*>(a.cstart + 16 * wave + 4 * g);      // (D[cout][pixel]: the lane's 4 couts)
     int voff[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -119,8 +94,7 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
 #pragma unroll
     for (int j = 0; j < S6_AHEAD; ++j) issue_row(j, j);
     wait_vmcnt<0>();
-#pragma unroll
-    for (int f = 0; f < 3 * NF; ++f) asm volatile("" : "+v"(wf[f]));
+    RN_PIN_WFRAGS(wf, 3 * NF);
     lds_barrier();
 
     int slot_cur = 0;
@@ -149,27 +123,17 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(orow), 0, out_row_bytes, 0x00020000);
         const int emask = (j >= 0 && j < nrows) ? 0 : OOB;
         i32x4 fq[2][3];
+        // a tile's six fragments: two batches of three (channel half 0, then 1), double-buffered across batches and tiles: batch
+        // b + 1's reads go out before batch b's nine MFMAs
         auto reads = [&](auto BC) __attribute__((always_inline)) {
-            constexpr int b = decltype(BC)::value, k = b >> 1, ch = b & 1;
-            auto& dst = fq[b & 1];
-            auto& bcr = bc;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[kx]) : "v"(bcr[kx][ch]), "n"(k * 2048));
+            constexpr int b = decltype(BC)::value;
+            reads3<(b >> 1), (b & 1)>(fq[b & 1], bc);
         };
         auto batch = [&](auto BC, auto NEXTC) __attribute__((always_inline)) {
             constexpr int b = decltype(BC)::value, k = b >> 1, ch = b & 1;
             constexpr bool NEXT = decltype(NEXTC)::value != 0;
             if constexpr (NEXT) reads(IC<b + 1>{});
-            auto& cur = fq[b & 1];
-            [&]<int... KX>(std::integer_sequence<int, KX...>) {
-                (([&] {
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(cur[KX]) : "n"((NEXT ? 3 : 0) + 2 - KX));
-                     acc[iN][k] = mfma16<DT>(wf[(0 * 3 + KX) * 2 + ch], cur[KX], (ch == 0 && KX == 0) ? zero4 : acc[iN][k]);
-                     acc[iM][k] = mfma16<DT>(wf[(1 * 3 + KX) * 2 + ch], cur[KX], acc[iM][k]);
-                     acc[iO][k] = mfma16<DT>(wf[(2 * 3 + KX) * 2 + ch], cur[KX], acc[iO][k]);
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 3>{});
+            frag_chain<DT, true, (NEXT ? 3 : 0), ch == 0, 6, ch, 2>(fq[b & 1], wf, acc[iN][k], acc[iM][k], acc[iO][k], zero4);
         };
         auto emit = [&](auto KC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
@@ -177,34 +141,19 @@ __global__ __launch_bounds__(512, 2) void stage6x_kernel(const StageArgs a) {
             float y[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[i] = __builtin_fmaf(relu6f(v[i]), sc[i], sh[i]);
-            const i32x2 d = {static_cast<int>(pack2<DT>(y[0], y[1])), static_cast<int>(pack2<DT>(y[2], y[3]))};
+            const i32x2 d = pack_out<DT, false>(y, 0);
             __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff[k] | emask, 0, 0);
         };
         [[maybe_unused]] i32x4 fq5[2][K48 ? 5 : 1];
-        auto reads5 = [&](auto KC) __attribute__((always_inline)) {
-            constexpr int k = decltype(KC)::value;
-            auto& dst = fq5[k & 1];
-            auto& bcr = bc;
-#pragma unroll
-            for (int f = 0; f < 5; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[f]) : "v"(f < 3 ? bcr[f][0] : bcr[f - 3][1]), "n"(k * 2048));
-        };
+        // K48: a tile's five fragments are one batch of 15 MFMAs, read a whole tile ahead
         auto tile5 = [&](auto KC, auto NEXTC) __attribute__((always_inline)) {
             constexpr int k = decltype(KC)::value;
             constexpr bool NEXT = decltype(NEXTC)::value != 0;
-            if constexpr (NEXT) reads5(IC<k + 1>{});
-            auto& cur = fq5[k & 1];
-            [&]<int... F>(std::integer_sequence<int, F...>) {
-                (([&] {
-                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(cur[F]) : "n"((NEXT ? 5 : 0) + 4 - F));
-                     acc[iN][k] = mfma16<DT>(wf[0 * NF + F], cur[F], F == 0 ? cst4 : acc[iN][k]);
-                     acc[iM][k] = mfma16<DT>(wf[1 * NF + F], cur[F], acc[iM][k]);
-                     acc[iO][k] = mfma16<DT>(wf[2 * NF + F], cur[F], acc[iO][k]);
-                 }()),
-                 ...);
-            }(std::make_integer_sequence<int, 5>{});
+            if constexpr (NEXT) reads5<k + 1>(fq5[(k + 1) & 1], bc);
+            frag_chain<DT, true, (NEXT ? 5 : 0), true, 5, 0, 1>(fq5[k & 1], wf, acc[iN][k], acc[iM][k], acc[iO][k], cst4);
         };
         if constexpr (K48) {
-            reads5(IC<0>{});
+            reads5<0>(fq5[0], bc);
             tile5(IC<0>{}, IC<1>{});
             emit(IC<0>{});
             tile5(IC<1>{}, IC<1>{});
@@ -250,56 +199,8 @@ bool rn_stage6x_supported(int cin, int cout, int pool_k, bool res, int in_side) 
     return cin == 64 && cout == 128 && pool_k == 0 && !res && in_side >= S6_WMIN && rn_stage6x_plan(in_side - 2, &ncb, xo0, wo);
 }
 
-// A-operand fragments: frag[f = (ky * 3 + kx) * 2 + ch][cout group q][lane][j] = W[tap][channel 32 ch + 8 (lane / 16) + j][cout 16 q + lane % 16]
-void rn_stage6x_pack(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(18) * 8 * 64 * 8, 0);
-    for (int f = 0; f < 18; ++f)
-        for (int q = 0; q < 8; ++q)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int tap = f >> 1, ch = f & 1;
-                    const int k = tap * 64 + 32 * ch + 8 * (l >> 4) + j, co = 16 * q + (l & 15);
-                    const float v = w_hwio[static_cast<size_t>(k) * 128 + co];
-                    (*out)[((static_cast<size_t>(f) * 8 + q) * 64 + l) * 8 + j] = rn_to16(v, dtype);
-                }
-}
-
-// K48 fragments (rn_stage5x_pack48's layout with eight 16-cout groups): frag[f = ky * 5 + j][group q][lane][e]
-void rn_stage6x_pack48(const float* w_hwio, int dtype, std::vector<unsigned short>* out) {
-    out->assign(static_cast<size_t>(15) * 8 * 64 * 8, 0);
-    for (int ky = 0; ky < 3; ++ky)
-        for (int j = 0; j < 5; ++j)
-            for (int q = 0; q < 8; ++q)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int g = l >> 4, co = 16 * q + (l & 15);
-                        int kx, ch;
-                        if (j < 3) {
-                            kx = j;
-                            ch = 8 * g + e;
-                        } else if (j == 3) {
-                            kx = g >> 1;
-                            ch = 32 + 8 * (g & 1) + e;
-                        } else {
-                            if (g >= 2) continue;
-                            kx = 2;
-                            ch = 32 + 8 * g + e;
-                        }
-                        const float v = w_hwio[(static_cast<size_t>(ky * 3 + kx) * 64 + ch) * 128 + co];
-                        (*out)[((static_cast<size_t>(ky * 5 + j) * 8 + q) * 64 + l) * 8 + e] = rn_to16(v, dtype);
-                    }
-}
-
 int rn_stage6x_launch(int dtype, hipStream_t s, const StageArgs& a, int n) {
-    auto launch = [&](auto kern) -> int {
-        hipLaunchKernelGGL(kern, dim3(a.n_bands * a.n_cb, n), dim3(512), S6_LDS, s, a);
-        RN_CHECK_LAUNCH();
-        return RN_OK;
-    };
-    if (a.cstart) {
-        if (dtype == RN_DTYPE_BF16) return launch(stage6x_kernel<RN_DTYPE_BF16, true>);
-        return launch(stage6x_kernel<RN_DTYPE_F16, true>);
-    }
-    if (dtype == RN_DTYPE_BF16) return launch(stage6x_kernel<RN_DTYPE_BF16, false>);
-    return launch(stage6x_kernel<RN_DTYPE_F16, false>);
+    const dim3 grid(a.n_bands * a.n_cb, n);
+    if (a.cstart) return rn_launch16<stage6x_kernel<RN_DTYPE_BF16, true>, stage6x_kernel<RN_DTYPE_F16, true>, false>(dtype, grid, 512, S6_LDS, s, a);
+    return rn_launch16<stage6x_kernel<RN_DTYPE_BF16, false>, stage6x_kernel<RN_DTYPE_F16, false>, false>(dtype, grid, 512, S6_LDS, s, a);
 }

@@ -458,6 +458,57 @@ RN_API int rn_jpeg_overlay_batch_device(rn_handle* h, const rn_jpeg_source* srcs
 RN_API int rn_jpeg_encode_batch_device(rn_handle* h, const rn_jpeg_source* srcs, int n);
 RN_API int rn_jpeg_last_encode_ms(rn_handle* h, float* ms);
 
+/* ---- the Huffman pass of the output file on the GPU -----------------------------------------------
+ * DESIGN.md section 19.  The encode's Huffman pass has no serial dependency that a prefix sum does not remove: a block's code
+ * lengths depend on the block and on one earlier DC at a known address, bit positions are an exclusive scan of the lengths, and
+ * FF 00 stuffing is a second scan.  Per batch of images of individual sizes: (1) LENGTHS: a wave per block, a lane per zigzag
+ * position, writes the block's bit count; (2) OFFSETS: the exclusive scan of the counts per image in scan (MCU) order, whose
+ * last element is the image's unstuffed bit total; (3) SCATTER: every block's bits go to its offset in a zeroed, unstuffed
+ * stream (a block's inner words are stored, the first and last are merged with atomicOr, which commutes: the bytes repeat from
+ * call to call), the last byte padded with 1-bits; (4) STUFF: the FF bytes per chunk are counted and scanned, byte i goes to
+ * i + (FF bytes in front of it) with 00 behind every FF, then FF D9.  Order between phases is the launches' order; the host reads
+ * the n bit totals after (2) and the n lengths after the counting half of (4) to size the streams, so the calls are synchronous.
+ * Opt-in: nothing above changes.  No coefficient leaves the device in rn_jpeg_encode_files_device.
+ *
+ * The status of an image (int32):
+ *   RN_JPEG_ENC_ST_OK         files[i][0 .. lens[i]) is the file rn_jpeg_entropy_encode writes, byte for byte
+ *   RN_JPEG_ENC_ST_CATEGORY   a DC difference beyond category 11 or an AC value beyond category 10: what rn_jpeg_entropy_encode
+ *                             refuses in the coefficients, every case of it (lens[i] = 0)
+ *   RN_JPEG_ENC_ST_CAP        the file needs more than caps[i] bytes; lens[i] is what it needs; nothing is stored past caps[i]
+ *   RN_JPEG_ENC_ST_TOO_LARGE  more than RN_JPEG_HUFFENC_MAX_BLOCKS blocks (32-bit bit offsets: 1658 bits per block at most);
+ *                             decided from the info alone, before the coefficients are read or anything is enqueued for the image
+ * A non-zero status for one image does not disturb the others of the batch; the caller runs rn_jpeg_entropy_encode for it.
+ *
+ * rn_jpeg_encode_headers  SOI .. SOS of the file of an info rn_jpeg_encode_info fills, the first bytes rn_jpeg_entropy_encode
+ *                         writes (the same code): *len bytes; more than cap: RN_E_RANGE with nothing stored past cap.
+ * rn_jpeg_huffenc_model   the four phases on the host, work item after work item through the same code (csrc/rn_jpeg_huffenc.h):
+ *                         the CPU statement of the algorithm.  Arguments as rn_jpeg_entropy_encode's; a null pointer or an info
+ *                         rn_jpeg_encode_info does not fill: RN_E_INVALID; RN_OK with the image's status in *status otherwise.
+ * rn_jpeg_huffenc_batch   the kernels alone on arbitrary coefficients: coeffs_host[i] (rn_jpeg_coeff_count elements) go up, the
+ *                         four phases run, and the whole file -- the headers, written by the host, the scan and EOI behind them --
+ *                         arrives in files[i][0 .. caps[i]) (host; from rn_host_alloc memory the copy is asynchronous inside the
+ *                         call).  lens[n], status[n] are filled.  Synchronous.
+ * rn_jpeg_encode_files_device  rn_jpeg_encode_batch_device's overlays and pixel stage, then the four phases on the coefficients
+ *                         where they are, in device scratch; srcs[i].coeffs is ignored and may be NULL.  Synchronous.
+ *                         Both: n outside [1, max_batch]: RN_E_RANGE; a null pointer, an info rn_jpeg_encode_info does not fill,
+ *                         and for the second what rn_jpeg_encode_batch_device refuses in a source: RN_E_INVALID; nothing is
+ *                         enqueued and the handle stays usable.  Scratch belongs to the handle and grows to the streams' real
+ *                         sizes; when it cannot (RN_E_NOMEM), the call returns before the scatter is enqueued.
+ * rn_jpeg_last_huffenc_ms device time of the last call's launches of the four phases (the host's reads between them excluded);
+ *                         waits for them. */
+#define RN_JPEG_ENC_ST_OK 0
+#define RN_JPEG_ENC_ST_CATEGORY 1
+#define RN_JPEG_ENC_ST_CAP 2
+#define RN_JPEG_ENC_ST_TOO_LARGE 3
+#define RN_JPEG_HUFFENC_MAX_BLOCKS (0xFFFFFFFFu / 1658u)
+RN_API int rn_jpeg_encode_headers(const rn_jpeg_info* info, uint8_t* out, size_t cap, size_t* len);
+RN_API int rn_jpeg_huffenc_model(const rn_jpeg_info* info, const int16_t* coeffs, uint8_t* out, size_t cap, size_t* len, int32_t* status);
+RN_API int rn_jpeg_huffenc_batch(rn_handle* h, const rn_jpeg_info* infos, const int16_t* const* coeffs_host, int n,
+                                 uint8_t* const* files, const size_t* caps, size_t* lens, int32_t* status);
+RN_API int rn_jpeg_encode_files_device(rn_handle* h, const rn_jpeg_source* srcs, int n, uint8_t* const* files, const size_t* caps,
+                                       size_t* lens, int32_t* status);
+RN_API int rn_jpeg_last_huffenc_ms(rn_handle* h, float* ms);
+
 /* Run on a caller-provided hipStream_t (e.g. the framework's current stream)
  * instead of the handle's own; NULL restores the handle's stream (a non-blocking stream,
  * NOT ordered against the HIP null stream).  rn_set_stream_null selects the HIP null

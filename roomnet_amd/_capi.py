@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "rn_jpeg_last_huffman_ms", "rn_jpeg_last_huffman_rounds",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
     "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
+    "rn_jpeg_encode_headers", "rn_jpeg_huffenc_model", "rn_jpeg_huffenc_batch", "rn_jpeg_encode_files_device", "rn_jpeg_last_huffenc_ms",
     "rn_cam_overlay_batch_device", "rn_cam_last_overlay_ms",
 )
 
@@ -377,6 +378,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             getattr(lib, name).restype = i32
         lib.rn_jpeg_last_encode_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_jpeg_last_encode_ms.restype = i32
+    if hasattr(lib, "rn_jpeg_huffenc_model"):
+        lib.rn_jpeg_encode_headers.argtypes = [C.POINTER(rn_jpeg_info), vp, sz, C.POINTER(sz)]
+        lib.rn_jpeg_encode_headers.restype = i32
+        lib.rn_jpeg_huffenc_model.argtypes = [C.POINTER(rn_jpeg_info), vp, vp, sz, C.POINTER(sz), C.POINTER(i32)]
+        lib.rn_jpeg_huffenc_model.restype = i32
+        lib.rn_jpeg_huffenc_batch.argtypes = [vp, C.POINTER(rn_jpeg_info), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), vp]
+        lib.rn_jpeg_huffenc_batch.restype = i32
+        lib.rn_jpeg_encode_files_device.argtypes = [vp, C.POINTER(rn_jpeg_source), i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), vp]
+        lib.rn_jpeg_encode_files_device.restype = i32
+        lib.rn_jpeg_last_huffenc_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_jpeg_last_huffenc_ms.restype = i32
     if hasattr(lib, "rn_cam_overlay_batch_device"):
         lib.rn_cam_overlay_batch_device.argtypes = [vp, C.POINTER(rn_cam_target), i32, C.c_double]
         lib.rn_cam_overlay_batch_device.restype = i32
@@ -798,6 +810,56 @@ class Engine:
         """Device time of the last encoded batch's launches (``rn_jpeg_last_encode_ms``)."""
         ms = C.c_float(0)
         _check(self.lib, self.lib.rn_jpeg_last_encode_ms(self.handle, C.byref(ms)), "rn_jpeg_last_encode_ms")
+        return float(ms.value)
+
+    @staticmethod
+    def _file_buffers(bufs, caps):
+        """uint8 arrays (or ``PinnedArray``s) -> ``(pointers, caps, lens)`` C arrays; ``caps``: bytes announced per buffer
+        (default: all of each)."""
+        arrays = [b.array if isinstance(b, PinnedArray) else b for b in bufs]
+        for a in arrays:
+            assert a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"]
+        n = max(len(arrays), 1)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrays])
+        sizes = (C.c_size_t * n)(*[a.size if caps is None else int(caps[k]) for k, a in enumerate(arrays)])
+        return ptrs, sizes, (C.c_size_t * n)()
+
+    def jpeg_huffenc_batch(self, items, bufs=None, caps=None):
+        """``rn_jpeg_huffenc_batch`` over ``items`` ``[(rn_jpeg_info of jpegenc.encode_info, int16 coefficient array)]`` (at most
+        ``max_batch``): the Huffman pass of the output file on the GPU, on arbitrary coefficients.  ``bufs``: uint8 arrays the
+        files are written into (default: new arrays of ``jpegenc.encoded_bound`` bytes), ``caps`` the bytes announced of each.
+        Returns ``(files, lens, status)``: ``files[k]`` is ``bytes`` where ``status[k]`` is 0 (``RN_JPEG_ENC_ST_OK``: the file
+        ``jpegenc.entropy_encode`` writes), else None.  Synchronous."""
+        n = len(items)
+        infos = (rn_jpeg_info * max(n, 1))(*[info for info, _c in items])
+        coeffs = [np.ascontiguousarray(c, dtype=np.int16) for _i, c in items]
+        cptr = (C.c_void_p * max(n, 1))(*[c.ctypes.data for c in coeffs])
+        if bufs is None:
+            bufs = [np.empty(max(int(self.lib.rn_jpeg_encoded_bound(C.byref(info))), 1), np.uint8) for info, _c in items]
+        ptrs, sizes, lens = self._file_buffers(bufs, caps)
+        status = np.zeros(max(n, 1), np.int32)
+        _check(self.lib, self.lib.rn_jpeg_huffenc_batch(self.handle, infos, cptr, n, ptrs, sizes, lens, status.ctypes.data), "rn_jpeg_huffenc_batch")
+        arrays = [b.array if isinstance(b, PinnedArray) else b for b in bufs]
+        files = [arrays[k][:lens[k]].tobytes() if status[k] == 0 else None for k in range(n)]
+        return files, [int(lens[k]) for k in range(n)], status[:n]
+
+    def jpeg_encode_files(self, items, bufs, caps=None):
+        """``rn_jpeg_encode_files_device`` over ``items`` (as ``_jpeg_sources`` takes them; the coefficient entry is ignored): the
+        overlays, the encode's pixel stage and the Huffman pass on the GPU; file k arrives in ``bufs[k]`` -- page-locked
+        ``PinnedArray``s (or uint8 arrays); ``jpegenc.encoded_bound(info)`` bytes always suffice, a file that needs more than
+        its buffer gets status ``RN_JPEG_ENC_ST_CAP`` and its needed size in ``lens[k]``.  Returns ``(lens, status)``: where
+        ``status[k]`` is 0, ``bufs[k][:lens[k]]`` is the file ``jpegenc.entropy_encode`` writes for the image.  Synchronous."""
+        arr, _keep = self._jpeg_sources([(a, info, ov, None) for a, info, ov, *_rest in items])
+        ptrs, sizes, lens = self._file_buffers(bufs, caps)
+        status = np.zeros(max(len(items), 1), np.int32)
+        _check(self.lib, self.lib.rn_jpeg_encode_files_device(self.handle, arr, len(items), ptrs, sizes, lens, status.ctypes.data),
+               "rn_jpeg_encode_files_device")
+        return [int(lens[k]) for k in range(len(items))], status[:len(items)]
+
+    def jpeg_last_huffenc_ms(self) -> float:
+        """Device time of the last batch's Huffman-encode launches (``rn_jpeg_last_huffenc_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_jpeg_last_huffenc_ms(self.handle, C.byref(ms)), "rn_jpeg_last_huffenc_ms")
         return float(ms.value)
 
     def crop_resize(self, im_bgr_u8: np.ndarray) -> np.ndarray:

@@ -649,6 +649,7 @@ extern "C" void rn_destroy(rn_handle* h) {
     rn_bnstats_release(h);
     rn_jpeg_release(h);
     rn_jpeg_enc_release(h);
+    rn_jpeg_huffenc_release(h);
     rn_cam_overlay_release(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;

@@ -186,6 +186,7 @@ struct rn_handle {
     // the image stages' lazily allocated state: single stream-ordered scratch, two sets of batch tables (rn_batch_table.h), a timer
     void* jpeg = nullptr;        // rn_jpeg_*: coefficient / plane / image scratch, the JpegDev tables (rn_jpeg.hip; allocated by the first call)
     void* jpeg_enc = nullptr;    // rn_jpeg_overlay_* / rn_jpeg_encode_*: plane / coefficient scratch, the EncDev / OverlayDev / coverage tables (rn_jpeg_enc.hip; the same)
+    void* jpeg_huffenc = nullptr; // rn_jpeg_huffenc_* / rn_jpeg_encode_files_device: lengths, sums, both streams, the descriptor tables (rn_jpeg_huffenc.hip; the same)
     void* cam_overlay = nullptr; // rn_cam_overlay_*: the CamDev tables and the per-image maxima (rn_cam_overlay.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
@@ -248,6 +249,13 @@ int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids);
 void rn_jpeg_release(rn_handle* h);
 // ---- overlay + the encode's pixel stage (rn_jpeg_enc.hip)
 void rn_jpeg_enc_release(rn_handle* h);
+// the source checks of rn_jpeg_encode_batch_device, the coefficient pointer apart (nothing is enqueued)
+int rn_jpeg_enc_check(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n);
+// its overlays and pixel stage without the download: d_coef[i] = image i's coefficients in the handle's scratch, valid until the
+// handle's next encode call.  The sources (1 .. max_batch of them) passed rn_jpeg_enc_check.
+int rn_jpeg_enc_pixels(rn_handle* h, const rn_jpeg_source* srcs, int n, int16_t** d_coef);
+// ---- the Huffman pass of the output file (rn_jpeg_huffenc.hip)
+void rn_jpeg_huffenc_release(rn_handle* h);
 // ---- grad-CAM heat maps on resident images (rn_cam_overlay.hip)
 void rn_cam_overlay_release(rn_handle* h);
 // (rn_api.hip) the centred square window of network.py:137-146 (of a packed BGR image: its top left, side and row bytes), the tail

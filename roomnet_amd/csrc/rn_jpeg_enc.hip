@@ -256,7 +256,7 @@ int enc_state(rn_handle* h, EncState** out) {
     return RN_OK;
 }
 
-int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool encode) {
+int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool need_coeffs) {
     const int rc = rn_check_batch(who, h, srcs, n);
     if (rc != RN_OK) return rc;
     for (int i = 0; i < n; ++i) {
@@ -266,7 +266,7 @@ int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int
                          who, i, s.info.width, s.info.height, s.info.ncomp, s.info.hsamp, s.info.vsamp, s.info.supported);
             return RN_E_INVALID;
         }
-        if (!s.d_bgr || (encode && !s.coeffs)) {
+        if (!s.d_bgr || (need_coeffs && !s.coeffs)) {
             rn_set_error("%s: image %d has no %s", who, i, s.d_bgr ? "coefficient buffer" : "device image");
             return RN_E_INVALID;
         }
@@ -286,7 +286,10 @@ int check_sources(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int
     return RN_OK;
 }
 
-int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool encode) {
+// The overlays in order, then (encode) the two pixel-stage launches.  d_coef null: the coefficients go down to srcs[i].coeffs
+// (rn_jpeg_encode_batch_device); else they stay in the handle's scratch and d_coef[i] is where image i's are
+// (rn_jpeg_encode_files_device: the Huffman phases of rn_jpeg_huffenc.hip read them there).
+int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool encode, int16_t** d_coef) {
     int rc, set;
     if ((rc = st->turn.acquire(&set)) != RN_OK) return rc;
     EncSet& sl = st->set[set];
@@ -368,6 +371,10 @@ int enqueue(rn_handle* h, EncState* st, const rn_jpeg_source* srcs, int n, bool 
         hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, 3, n), dim3(256), 0, h->stream, sl.desc.dev);
         RN_CHECK_LAUNCH();
         if ((rc = st->timer.stop(h->stream)) != RN_OK) return rc;
+    }
+    if (encode && d_coef) {
+        for (int i = 0; i < n; ++i) d_coef[i] = sl.desc.host[i].coef[0];
+    } else if (encode) {
         // the coefficients go down on the copy stream; the handle's stream continues behind the download, so rn_sync covers it
         // and the next call's launches do not overwrite the scratch under it
         RN_HIP(hipEventRecord(st->encoded, h->stream));
@@ -387,10 +394,19 @@ int run(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n, bool e
     DeviceGuard guard(h->device);
     EncState* st = nullptr;
     if ((rc = enc_state(h, &st)) != RN_OK) return rc;
-    return enqueue(h, st, srcs, n, encode);
+    return enqueue(h, st, srcs, n, encode, nullptr);
 }
 
 }  // namespace
+
+int rn_jpeg_enc_check(const char* who, rn_handle* h, const rn_jpeg_source* srcs, int n) { return check_sources(who, h, srcs, n, false); }
+
+int rn_jpeg_enc_pixels(rn_handle* h, const rn_jpeg_source* srcs, int n, int16_t** d_coef) {
+    DeviceGuard guard(h->device);
+    EncState* st = nullptr;
+    const int rc = enc_state(h, &st);
+    return rc != RN_OK ? rc : enqueue(h, st, srcs, n, true, d_coef);
+}
 
 void rn_jpeg_enc_release(rn_handle* h) {
     EncState* s = static_cast<EncState*>(h->jpeg_enc);

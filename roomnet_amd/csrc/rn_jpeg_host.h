@@ -6,7 +6,8 @@
 // tools/jpeg_corrupt_main.cpp (the host-sanitizer corpus run).
 // Further down, the host half of the split ENCODE: the description of the output file
 // (rn_jpeg_encode_info) and its Huffman pass (rn_jpeg_entropy_encode), with the same properties; exported by rn_jpeg_enc.hip and
-// run stand-alone by tools/jpeg_encode_main.cpp.
+// run stand-alone by tools/jpeg_encode_main.cpp.  rn_jpeg_huffenc.h restates the pass per zigzag position for the GPU (DESIGN.md
+// section 19) on the tables, the header writer and the ByteWriter of this file.
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -576,32 +577,9 @@ struct ByteWriter {
     }
 };
 
-inline int bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
-
-// The whole file for the quantised coefficients `coeffs` ([component][block_y][block_x][64], natural order: the layout
-// entropy_decode writes).  *len: the file's size, also when it is more than cap (RN_E_RANGE; out[0 .. cap) is then its beginning).
-inline int entropy_encode(const rn_jpeg_info* info, const int16_t* coeffs, uint8_t* out, size_t cap, size_t* len, const char** why) {
-    static thread_local EncTable dc[2], ac[2];
-    static thread_local bool built = false;
-    *why = "";
-    if (!info || !coeffs || !len || (!out && cap)) {
-        *why = "null argument";
-        return RN_E_INVALID;
-    }
-    *len = 0;
-    if (!encode_info_ok(*info)) {
-        *why = "the info is not one rn_jpeg_encode_info fills (3 components, 4:2:0, whole-MCU grids, 8-bit tables)";
-        return RN_E_INVALID;
-    }
-    if (!built) {
-        for (int t = 0; t < 2; ++t) {
-            build_enc_table(kStdDcBits[t], kStdDcVals, dc[t]);
-            build_enc_table(kStdAcBits[t], kStdAcVals[t], ac[t]);
-        }
-        built = true;
-    }
-    const rn_jpeg_info& f = *info;
-    ByteWriter w{out, cap};
+// SOI .. SOS of the file of `f` (an info encode_info fills): kEncHeaderBytes bytes.  The one place the header is written:
+// entropy_encode and rn_jpeg_encode_headers (rn_jpeg_huffenc.h) both call it.
+inline void write_headers(const rn_jpeg_info& f, ByteWriter& w) {
     w.u16(0xFFD8);
     w.u16(0xFFE0);                                           // APP0: JFIF 1.01, no units, 1:1, no thumbnail
     w.u16(16);
@@ -633,6 +611,35 @@ inline int entropy_encode(const rn_jpeg_info* info, const int16_t* coeffs, uint8
     w.u16(0xFFDA);                                           // SOS: one interleaved scan
     w.u16(12);
     for (const uint8_t b : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) w.byte(b);
+}
+
+inline int bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+// The whole file for the quantised coefficients `coeffs` ([component][block_y][block_x][64], natural order: the layout
+// entropy_decode writes).  *len: the file's size, also when it is more than cap (RN_E_RANGE; out[0 .. cap) is then its beginning).
+inline int entropy_encode(const rn_jpeg_info* info, const int16_t* coeffs, uint8_t* out, size_t cap, size_t* len, const char** why) {
+    static thread_local EncTable dc[2], ac[2];
+    static thread_local bool built = false;
+    *why = "";
+    if (!info || !coeffs || !len || (!out && cap)) {
+        *why = "null argument";
+        return RN_E_INVALID;
+    }
+    *len = 0;
+    if (!encode_info_ok(*info)) {
+        *why = "the info is not one rn_jpeg_encode_info fills (3 components, 4:2:0, whole-MCU grids, 8-bit tables)";
+        return RN_E_INVALID;
+    }
+    if (!built) {
+        for (int t = 0; t < 2; ++t) {
+            build_enc_table(kStdDcBits[t], kStdDcVals, dc[t]);
+            build_enc_table(kStdAcBits[t], kStdAcVals[t], ac[t]);
+        }
+        built = true;
+    }
+    const rn_jpeg_info& f = *info;
+    ByteWriter w{out, cap};
+    write_headers(f, w);
 
     const int16_t* base[3];
     size_t off = 0;

@@ -260,7 +260,7 @@ def _heat_overlay_and_write(im, cam_map, weight, pred_label, pred_conf, out_fpat
 
 
 def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5,
-                    gpu_huffman=False):
+                    gpu_huffman=False, gpu_huffman_encode=False):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
@@ -270,7 +270,9 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     stays on the device from decode to encode and only the Huffman passes run on the host; files ``imread`` decodes are uploaded
     when their output is a JPEG file and go the host way otherwise.  Output files, workbook and printed lines are the same,
     byte for byte.  ``gpu_huffman`` (with ``gpu_decode``): the Huffman pass of the input files runs on the GPU too (DESIGN.md
-    section 18; with ``gpu_encode`` the input's Huffman pass stays on the host); same outputs."""
+    section 18; with ``gpu_encode`` the input's Huffman pass stays on the host); same outputs.  ``gpu_huffman_encode`` (with
+    ``gpu_encode``): the Huffman pass of the OUTPUT files runs on the GPU too: only the files' bytes come
+    back and the writer pool only writes them; same outputs."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     if gpu_huffman and not gpu_decode:
@@ -280,6 +282,9 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
                          "nothing to encode)")
     if gpu_encode and not gpu_decode:
         raise ValueError("classify_im_dir: gpu_encode=True needs gpu_decode=True (it encodes the image the GPU decode left on the device)")
+    if gpu_huffman_encode and not gpu_encode:
+        raise ValueError("classify_im_dir: gpu_huffman_encode=True needs gpu_encode=True (it encodes the coefficients the GPU encode "
+                         "left on the device)")
     if gpu_decode and overlay and not gpu_encode:
         raise ValueError("classify_im_dir: gpu_decode=True needs overlay=False (the overlay is drawn on the decoded image, "
                          "which the GPU decode path never brings to the host) or gpu_encode=True")
@@ -305,13 +310,15 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     row = 0      # unreadable files are skipped (the reference crashes on them): rows stay contiguous
     writers = ThreadPoolExecutor(max_workers=DECODE_THREADS) if overlay else None
     writing = deque()
-    heat = {} if heatmap is None else dict(heatmap=heatmap, heatmap_weight=heatmap_weight)      # (a model object without the arguments still works without a heat map)
+    extra = {} if heatmap is None else dict(heatmap=heatmap, heatmap_weight=heatmap_weight)      # (a model object without the arguments still works without a heat map)
+    if gpu_huffman_encode:
+        extra["gpu_huffman_encode"] = True
     if gpu_encode:
         results = _in_batches_of_readable(
             nn.classify_files_to_dir(all_im_paths,
                                      lambda i, idx: out_dir + os.sep + CLASS_LABELS[idx] + os.sep + all_im_paths[i].split(os.sep)[-1],
                                      lambda h, w, idx, conf: _overlay_lines(h, w, CLASS_LABELS[idx], conf),
-                                     writers, batch_size=batch_size, **heat), batch_size)
+                                     writers, batch_size=batch_size, **extra), batch_size)
     elif heatmap is not None:
         results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap))
     else:

@@ -188,6 +188,47 @@ def entropy_encode(info: rn_jpeg_info, coeffs, lib_path: Optional[str] = None) -
     return buf[:n].tobytes()
 
 
+# the status of an image after the GPU's Huffman pass (include/roomnet_hip.h: RN_JPEG_ENC_ST_*)
+ST_OK, ST_CATEGORY, ST_CAP, ST_TOO_LARGE = 0, 1, 2, 3
+HUFFENC_MAX_BLOCKS = 0xFFFFFFFF // 1658
+
+
+def encode_headers(info: rn_jpeg_info, lib_path: Optional[str] = None) -> bytes:
+    """SOI .. SOS of the file of ``info`` (``rn_jpeg_encode_headers``): the first bytes ``entropy_encode`` writes."""
+    lib = _capi.load_library(lib_path)
+    buf = np.empty(1024, np.uint8)
+    n = C.c_size_t(0)
+    _capi._check(lib, lib.rn_jpeg_encode_headers(C.byref(info), buf.ctypes.data, buf.size, C.byref(n)), "rn_jpeg_encode_headers")
+    return buf[:n.value].tobytes()
+
+
+def huffenc_model_rc(info: rn_jpeg_info, coeffs, out: np.ndarray, cap: Optional[int] = None, lib_path: Optional[str] = None) -> Tuple[int, int, int]:
+    """``rn_jpeg_huffenc_model`` into the uint8 array ``out`` with ``cap`` bytes announced (default: all of it):
+    ``(code, len, status)``.  ``coeffs``: an int16 array or the address of one."""
+    lib = _capi.load_library(lib_path)
+    assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+    if isinstance(coeffs, np.ndarray):
+        assert coeffs.dtype == np.int16 and coeffs.flags["C_CONTIGUOUS"]
+        coeffs = coeffs.ctypes.data
+    n, status = C.c_size_t(0), C.c_int32(0)
+    rc = lib.rn_jpeg_huffenc_model(C.byref(info), C.c_void_p(int(coeffs)), out.ctypes.data, out.size if cap is None else int(cap),
+                                   C.byref(n), C.byref(status))
+    return int(rc), int(n.value), int(status.value)
+
+
+def huffenc_model(info: rn_jpeg_info, coeffs, lib_path: Optional[str] = None) -> Tuple[Optional[bytes], int]:
+    """The host model of the GPU's Huffman encode: ``(file, status)``; ``file`` is what
+    ``entropy_encode`` writes where ``status`` is ``ST_OK``, else None."""
+    need = encoded_bound(info, lib_path)
+    if not need:
+        raise ValueError("huffenc_model: the info is not one encode_info fills")
+    blocks = coeff_count(info) // 64
+    buf = np.empty(need if blocks <= HUFFENC_MAX_BLOCKS else 1024, np.uint8)
+    rc, n, status = huffenc_model_rc(info, coeffs, buf, lib_path=lib_path)
+    _capi._check(_capi.load_library(lib_path), rc, "rn_jpeg_huffenc_model")
+    return (buf[:n].tobytes() if status == ST_OK else None), status
+
+
 def encode_bgr(im_bgr: np.ndarray, quality: int = QUALITY, lib_path: Optional[str] = None) -> bytes:
     """A BGR uint8 HWC image -> the bytes of the file ``imageio.imwrite`` writes for a ``.jpg`` name, byte for byte."""
     im_bgr = np.ascontiguousarray(im_bgr, dtype=np.uint8)

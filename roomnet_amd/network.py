@@ -107,6 +107,14 @@ def _layer_names(graph: Graph):
     return blocks
 
 
+def _huffenc_slot_bytes(info):
+    """Bytes of a page-locked output slot of ``classify_files_to_dir(gpu_huffman_encode=True)``: what the image's coefficients
+    would take (16 bits per coefficient).  The worst case, ``jpegenc.encoded_bound``, is 3.25 times that and page-locked memory is
+    not free; a file beyond its slot gets ``ST_CAP`` and goes through the host pass."""
+    from . import jpegdec, jpegenc
+    return min(jpegenc.encoded_bound(info), 1024 + 2 * jpegdec.coeff_count(info))
+
+
 class RoomNet:
 
     def __init__(self, num_classes, im_side=600, compute_bn_mean_var=True, start_step=0, dropout_enabled=False,
@@ -427,7 +435,7 @@ class RoomNet:
                 yield (k * chunk, res) if gpu_huffman is None else (k * chunk, res, pool)
 
     def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64, heatmap=None,
-                              heatmap_weight=0.5):
+                              heatmap_weight=0.5, gpu_huffman_encode=False):
         """Classify image FILES and write each with its overlay as a JPEG file, decode to encode on the GPU.  Yields, in list
         order, ``(index, id, conf, image, future)``: ``future`` is the pending write (on the ``writers`` pool) of a file that went
         through the device; ``image`` (BGR) is set instead for a file whose output name ``out_path_of(index, id)`` has no JPEG
@@ -446,7 +454,14 @@ class RoomNet:
         square the network saw with ``heatmap_weight``, UNDER the text.  The chunk then runs ``Engine.explain_resident`` (the
         forward pass and its adjoint; the same ids and confidences) and ``Engine.cam_overlay_batch`` in front of the text and the
         encode, all on the device; a file the caller writes comes back with its heat map drawn on the host (``grad_cam``,
-        ``cam.overlay_image``: the same bytes)."""
+        ``cam.overlay_image``: the same bytes).
+
+        ``gpu_huffman_encode``: the Huffman pass of the OUTPUT runs on the GPU as well (``Engine.jpeg_encode_files``, DESIGN.md
+        section 19): no coefficient leaves the device, the files arrive in a ring of page-locked byte buffers (two banks, the
+        same reuse rule) and the ``writers`` pool only writes ``buf[:len]``.  A file whose status is not 0 (in practice: one larger than its slot of 2 bytes per coefficient) is encoded again in
+        the same call through ``jpeg_encode_batch`` -- WITHOUT overlays where the first call drew them (they are in the image already),
+        with them for a ``ST_TOO_LARGE`` image, for which nothing was enqueued -- and
+        ``jpegenc.entropy_encode``; ``self.huffenc_fallbacks`` counts those.  The same bytes."""
         import os
         from . import cam, hershey, jpegdec, jpegenc
         from ._capi import GRAD_CAM_LAYERS
@@ -464,6 +479,14 @@ class RoomNet:
             if ring is not None:
                 ring.close()
             ring = self._jpeg_enc_ring = jpegdec.CoeffRing(2 * chunk)
+        out_ring = None
+        if gpu_huffman_encode:
+            out_ring = getattr(self, "_jpeg_out_ring", None)
+            if out_ring is None or len(out_ring) < 2 * chunk:
+                if out_ring is not None:
+                    out_ring.close()
+                out_ring = self._jpeg_out_ring = jpegdec.ByteRing(2 * chunk)
+            self.huffenc_fallbacks = 0
         pending = [[], []]                      # the writes that still read each bank's buffers
 
         def write(info, coeffs, out_path):
@@ -472,6 +495,14 @@ class RoomNet:
                 with open(out_path, "wb") as f:
                     f.write(data)
             except (OSError, ValueError):
+                return False
+            return True
+
+        def write_bytes(buf, n, out_path):
+            try:
+                with open(out_path, "wb") as f:
+                    f.write(buf[:n])
+            except OSError:
                 return False
             return True
 
@@ -499,11 +530,24 @@ class RoomNet:
                 confs = [probs[m][ids[m]] for m in range(len(ids))]
                 overlays = list(writers.map(rasterise, shapes, [lines_of(h, w, int(ids[m]), confs[m]) for m, (h, w) in enumerate(shapes)]))
                 infos = [jpegenc.encode_info(h, w) for h, w in shapes]
-                bufs = [ring.buffer(bank * chunk + m, jpegdec.coeff_count(info)) for m, info in enumerate(infos)]
-                eng.jpeg_encode_batch([(addrs[m], infos[m], overlays[m], bufs[m]) for m in range(len(infos))])
-                eng.sync()
+                host_pass = list(range(len(infos)))          # the files whose Huffman pass the writer pool runs
+                if gpu_huffman_encode:
+                    files = [out_ring.buffer(bank * chunk + m, _huffenc_slot_bytes(info)) for m, info in enumerate(infos)]
+                    lens, status = eng.jpeg_encode_files([(addrs[m], infos[m], overlays[m], None) for m in range(len(infos))], files)
+                    host_pass = [m for m in range(len(infos)) if status[m] != 0]
+                    self.huffenc_fallbacks += len(host_pass)
+                    # the call drew the overlays of every image it enqueued: those images hold them.  An image that is too
+                    # large got no launch at all, so its lines are still to be drawn
+                    overlays = [ov if status[m] == jpegenc.ST_TOO_LARGE else [] for m, ov in enumerate(overlays)]
+                if host_pass:
+                    bufs = {m: ring.buffer(bank * chunk + m, jpegdec.coeff_count(infos[m])) for m in host_pass}
+                    eng.jpeg_encode_batch([(addrs[m], infos[m], overlays[m], bufs[m]) for m in host_pass])
+                    eng.sync()
                 for m, j in enumerate(jp + up):
-                    fut = writers.submit(write, infos[m], bufs[m], out_path_of(lo + j, int(ids[m])))
+                    if m in host_pass:
+                        fut = writers.submit(write, infos[m], bufs[m], out_path_of(lo + j, int(ids[m])))
+                    else:
+                        fut = writers.submit(write_bytes, files[m], lens[m], out_path_of(lo + j, int(ids[m])))
                     pending[bank].append(fut)
                     out[j] = (int(ids[m]), confs[m], None, fut)
             if host and heatmap is None:

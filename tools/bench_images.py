@@ -16,6 +16,12 @@
         drivers with gpu_decode=True against gpu_decode=True, gpu_huffman=True (the Huffman pass on the GPU too)
         on the same files, alternating, three runs each after a warm-up of both; the ratio, the host's share per file and thread in
         both arms, the device time of the Huffman launches per batch, the synchronisation rounds, the count of host fallbacks
+  python tools/bench_images.py --dir --gpu-huffman-encode [--threads=T] [H W [N]]    a generated directory again, nothing of the above:
+        classify_im_dir(overlay=True) on the host, the gpu_decode + gpu_encode arm and the same with gpu_huffman_encode=True (the
+        Huffman pass of the OUTPUT on the GPU too) on the same files, alternating, three runs each after a
+        warm-up of all; the ratios, whether the files are identical, the host Huffman-encode pass alone on one thread, the device
+        time of the four phases per batch beside the pixel stage's, the bytes downloaded per batch in both GPU arms, the fallbacks.
+        The line that begins "overlay=True" is the --gpu-encode arm's own report from the same runs
   python tools/bench_images.py --heatmap [--threads=T] [H W [N]]    a generated directory again, nothing of the above: the device time
         of the two heat-map launches (rn_cam_last_overlay_ms) for one batch and both layers, next to the decode's and the encode's
         pixel stages of the same batch; then classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True) with heatmap="s6.bn",
@@ -370,8 +376,108 @@ def gpu_huffman_arm():
     shutil.rmtree(root, ignore_errors=True)
 
 
+def gpu_huffman_encode_arm():
+    """overlay=True on the host, gpu_decode + gpu_encode, and + gpu_huffman_encode: same files, same session, alternating."""
+    from roomnet_amd import hershey, infer, jpegdec, jpegenc
+    root, d, nn, paths, mb = generated_directory()
+
+    def outputs():
+        out = {}
+        for dirpath, _dirs, names in os.walk(d + '_classified'):
+            for name in names:
+                with open(os.path.join(dirpath, name), 'rb') as f:
+                    out[name] = f.read()
+        return out
+
+    arms = {'host': dict(), 'gpu_encode': dict(gpu_decode=True, gpu_encode=True),
+            'gpu_huffman_encode': dict(gpu_decode=True, gpu_encode=True, gpu_huffman_encode=True)}
+    times = {a: [] for a in arms}
+    files, fallbacks = {}, 0
+    sink = io.StringIO()
+    with contextlib.redirect_stdout(sink):
+        for rep_ in range(4):                             # (the first round is the warm-up of every arm)
+            for arm, kw in arms.items():
+                t0 = time.perf_counter()
+                infer.classify_im_dir(nn, d, overlay=True, batch_size=64, **kw)
+                if rep_:
+                    times[arm].append(time.perf_counter() - t0)
+                if 'gpu_huffman_encode' in kw:
+                    fallbacks += nn.huffenc_fallbacks
+                files[arm] = outputs()
+    same = files['host'] == files['gpu_encode'] == files['gpu_huffman_encode'] and len(files['host']) == len(paths)
+    # one batch on its own: the device time of the pixel stage and of the four phases, the bytes that come down, and the host's
+    # Huffman-encode pass of the same files on one thread
+    eng = nn._engine()
+    n = min(len(paths), eng.max_batch)
+    ims = [imageio.imread(p) for p in paths[:n]]
+    infos = [jpegenc.encode_info(im.shape[0], im.shape[1]) for im in ims]
+    pinned = [_capi.PinnedArray((jpegdec.coeff_count(i),), np.int16) for i in infos]
+    outs = [_capi.PinnedArray((min(jpegenc.encoded_bound(i), 1024 + 2 * jpegdec.coeff_count(i)),), np.uint8) for i in infos]
+    d_ims = [eng.device_malloc(im.nbytes) for im in ims]
+    for p, im in zip(d_ims, ims):
+        eng.h2d(p, im)
+    lines = [infer._overlay_lines(im.shape[0], im.shape[1], 'LivingRoom', np.float32(0.9987)) for im in ims]
+    ovs = [[(b[0], b[1], b[2], color) for b, color in ((hershey.coverage(t, o, s_, im.shape, 1), c) for t, o, s_, c in ln) if b is not None]
+           for im, ln in zip(ims, lines)]
+    px_ms, huff_ms, call_ms, coef_ms = [], [], [], []
+    for _ in range(6):
+        t0 = time.perf_counter()
+        eng.jpeg_encode_batch([(p, i, [], c.array) for p, i, c in zip(d_ims, infos, pinned)])
+        eng.sync()
+        coef_ms.append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        lens, status = eng.jpeg_encode_files([(p, i, [], None) for p, i in zip(d_ims, infos)], outs)
+        call_ms.append(1e3 * (time.perf_counter() - t0))
+        assert not status.any()
+        px_ms.append(eng.jpeg_last_encode_ms())
+        huff_ms.append(eng.jpeg_last_huffenc_ms())
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    px_ms, huff_ms, call_ms, coef_ms = med(px_ms[1:]), med(huff_ms[1:]), med(call_ms[1:]), med(coef_ms[1:])
+    t0 = time.perf_counter()
+    total = 0
+    for k, (i, c) in enumerate(zip(infos, pinned)):
+        data = jpegenc.entropy_encode(i, c.array)
+        assert data == outs[k].array[:lens[k]].tobytes()
+        total += len(data)
+    t_huff = (time.perf_counter() - t0) / n
+    # (the overlays: drawn once at the end so the timed calls above encode the same pixels every time)
+    eng.jpeg_encode_batch([(p, i, o, c.array) for p, i, o, c in zip(d_ims, infos, ovs, pinned)])
+    eng.sync()
+    ovl_ms = eng.jpeg_last_encode_ms()
+    for p in d_ims:
+        eng.device_free(p)
+    for c in pinned + outs:
+        c.close()
+    N_ = len(paths)
+    m = {a: med(t) for a, t in times.items()}
+    runs = {a: ' / '.join('%.1f' % (N_ / x) for x in t) for a, t in times.items()}
+    spread = {a: (max(t) - min(t)) / med(t) for a, t in times.items()}
+    coef_mb = sum(jpegdec.coeff_count(i) for i in infos) * 2 / 1e6
+    print('%d JPEG files %dx%d (%.0f MB), %d decode threads of %d host cores, classify_im_dir(overlay=True), same files, same session, '
+          'alternating, 3 runs each after a warm-up of all:' % (N_, W, H, mb, infer.DECODE_THREADS, os.cpu_count() or 1))
+    for arm in arms:
+        print('  %-20s %s img/s (median %.1f, spread of the run times %.1f %%)' % (arm + ':', runs[arm], N_ / m[arm], 100 * spread[arm]))
+    print('  ratio gpu_huffman_encode / gpu_encode (medians): x%.2f   gpu_encode / host: x%.2f   gpu_huffman_encode / host: x%.2f   '
+          'output files identical in all three: %s   host fallbacks: %d'
+          % (m['gpu_encode'] / m['gpu_huffman_encode'], m['host'] / m['gpu_encode'], m['host'] / m['gpu_huffman_encode'], same, fallbacks))
+    print('  one batch of %d without overlays: pixel stage on the device %.3f ms, the four Huffman phases %.3f ms (%.1f us per image); the '
+          'whole jpeg_encode_files call %.2f ms on the host clock against %.2f ms for jpeg_encode_batch + sync   downloaded per batch: '
+          '%.1f MB of files instead of %.1f MB of coefficients   host Huffman-encode pass alone, one thread: %.3f ms per file '
+          '(%.1f img/s, %.2f MB per file)'
+          % (n, px_ms, huff_ms, 1e3 * huff_ms / n, call_ms, coef_ms, sum(lens) / 1e6, coef_mb, 1e3 * t_huff, 1.0 / t_huff, total / n / 1e6))
+    print('overlay=True, same files, same session, alternating, 3 runs each after a warm-up: host decode + overlay + write %.1f img/s '
+          '(runs %s)   gpu_decode + gpu_encode %.1f img/s (runs %s)   x%.2f   output files identical: %s   host Huffman-encode pass '
+          'alone, one thread %.1f img/s (%.2f MB per file)   overlay + encode launches on the device %.3f ms per batch of %d (%.1f us '
+          'per image)'
+          % (N_ / m['host'], runs['host'], N_ / m['gpu_encode'], runs['gpu_encode'], m['host'] / m['gpu_encode'],
+             files['host'] == files['gpu_encode'], 1.0 / t_huff, total / n / 1e6, ovl_ms, n, 1e3 * ovl_ms / n))
+    shutil.rmtree(root, ignore_errors=True)
+
+
 if '--heatmap' in sys.argv:
     heatmap_arm()
+elif '--dir' in sys.argv and '--gpu-huffman-encode' in sys.argv:
+    gpu_huffman_encode_arm()
 elif '--dir' in sys.argv and '--gpu-huffman' in sys.argv:
     gpu_huffman_arm()
 elif '--dir' in sys.argv:

@@ -207,7 +207,15 @@ typedef struct rn_node_info {
  * rn_create replaces RoomNet.__init__(optimized_inference=True) + RoomNet.init()
  * + RoomNet.load(path) (reference network.py:21-48, :87-91, :105-126): it builds
  * the execution plan for `w`, packs/uploads the weights and sizes the workspace
- * for up to max_batch images per call. */
+ * for up to max_batch images per call.
+ *
+ * Supported im_side.  The graph needs im_side >= 183 (smaller: RN_E_INVALID).  A handle CLASSIFIES at im_side 183 .. 694:
+ * the head kernel keeps the flatten (16 channels of the last conv stage's square output) in LDS, 4096 values at the most --
+ * 16 x 16 x 16 at 663 .. 694, 17 x 17 x 16 = 4624 from 695 on.  rn_create accepts larger sides too: such a handle serves
+ * rn_features_* (the features lie in front of the head; that pass launches no head and leaves the head's nodes unwritten), and
+ * every call that classifies (rn_forward_*, rn_submit_u8, rn_grad_cam_*) enqueues the conv stages and then returns RN_E_STATE
+ * with "flatten length 4624 exceeds head kernel capacity 4096"; the handle stays usable.  Inside 183 .. 694 the tuned 16-bit
+ * kernels cut wide rows into one to four column blocks (the table of block counts per side). */
 RN_API int rn_create(const rn_weights* w, int device, int dtype, int max_batch, unsigned flags, rn_handle** out);
 RN_API void rn_destroy(rn_handle* h);
 RN_API const char* rn_last_error(void);

@@ -442,6 +442,9 @@ void fill_head_args(rn_handle* h, HeadArgs& a) {
 int run_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids) {
     HeadArgs a;
     fill_head_args(h, a);
+    // the features lie in front of the head: a handle whose flatten head_kernel cannot take (im_side > 694) still serves them, with
+    // no head launch and nothing written to the head's nodes; every classifying call is refused by rn_launch_head
+    if (h->features_pass && !rn_head_takes_flatten(a.nin[0])) return RN_OK;
     const NodeBuf& flat = h->nodes[h->node_flat];
     return rn_launch_head(h->stream, flat.ptr, flat.dtype, n, a, d_probs, d_ids);
 }
@@ -896,9 +899,9 @@ int features_check(rn_handle* h, int n, int* node, int depth) {
 }
 
 int features_device(rn_handle* h, const uint8_t* d_bgr, int n, int node7, float* d_feat) {
-    h->split_backend = true;
+    h->split_backend = h->features_pass = true;
     int rc = rn_forward_u8_device(h, d_bgr, n, h->d_probs, h->d_ids);
-    h->split_backend = false;
+    h->split_backend = h->features_pass = false;
     if (rc != RN_OK) return rc;
     const NodeBuf& nb = h->nodes[node7];
     bool elided = false;

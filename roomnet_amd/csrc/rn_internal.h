@@ -189,6 +189,7 @@ struct rn_handle {
     void* jpeg_huffenc = nullptr; // rn_jpeg_huffenc_* / rn_jpeg_encode_files_device: lengths, sums, both streams, the descriptor tables (rn_jpeg_huffenc.hip; the same)
     void* cam_overlay = nullptr; // rn_cam_overlay_*: the CamDev tables and the per-image maxima (rn_cam_overlay.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
+    bool features_pass = false;  // rn_features_*: this call reads s6.bn / s7.bn only; a flatten head_kernel cannot take does not fail it
     // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
     // node id -> position p of the stored tensor holds the reference's channel perm[p] (rn_tap puts them back in order)
     std::map<int, std::vector<int>> node_perm;
@@ -227,6 +228,7 @@ int rn_launch_resize_u8(hipStream_t s, const uint8_t* d_src, int src_h, int src_
                         int dst_h, int dst_w);
 int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const HeadArgs& a, float* probs,
                    int64_t* ids);
+bool rn_head_takes_flatten(int flat_len);      // head_kernel keeps the flatten in LDS: up to 4096 values (im_side <= 694)
 int rn_launch_convert_to_f32(hipStream_t s, const void* in, int dtype, float* out, int64_t n);
 
 // ---- grad-CAM (rn_gradcam.hip)

@@ -401,11 +401,15 @@ int rn_launch_convert_to_f32(hipStream_t s, const void* in, int dtype, float* ou
     return RN_OK;
 }
 
+bool rn_head_takes_flatten(int flat_len) { return flat_len <= HEAD_MAX_FLAT; }
+
 int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const HeadArgs& a, float* probs,
                    int64_t* ids) {
-    if (a.nin[0] > HEAD_MAX_FLAT) {
+    // rn_create accepted the graph (a handle that only serves rn_features_* needs no head): the arguments of the classifying call
+    // are in order, it is this handle that cannot classify
+    if (!rn_head_takes_flatten(a.nin[0])) {
         rn_set_error("flatten length %d exceeds head kernel capacity %d", a.nin[0], HEAD_MAX_FLAT);
-        return RN_E_INVALID;
+        return RN_E_STATE;
     }
     for (int d = 0; d < a.n_dense; ++d)
         if (a.nout[d] > 64 || (d > 0 && a.nin[d] > 64)) {

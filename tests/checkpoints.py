@@ -17,6 +17,10 @@ SEAM_IDX = [30, 14]
 # sides at which the tuned 16-bit kernels cut their rows into two or three column blocks (tests/block_plans.py); 600 is the
 # reference's own default side
 SEAM_SIDES = (409, 420, 600)
+# sides at which stage 6 (630, next to three-block plans of the pair and of stages 4 and 5) and stages 5 and 6 (686: no plan for the
+# pair or stage 4, flatten 4096, the head's limit) run FOUR column blocks with a ragged last block; 694 is the largest side with a head
+FOUR_BLOCK_SIDES = (630, 686)
+MAX_HEAD_SIDE = 694           # flatten 16 x 16 x 16 = 4096 = head_kernel's HEAD_MAX_FLAT; at 695 it is 17 x 17 x 16 = 4624
 LIVE_GAIN = 2.5               # conv-kernel gain at which every stage 1-9 has values at the clamp AND strictly inside (0, 6)
 
 

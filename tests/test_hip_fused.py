@@ -463,11 +463,12 @@ def test_cross_stage_fusion_at_600_is_bit_identical_to_stage_launches(weights, n
             plain.close()
 
 
-@pytest.mark.parametrize("side,blocks", [(202, 1), (211, 1), (409, 2), (634, 3), (439, 0), (190, 0)])
+@pytest.mark.parametrize("side,blocks", [(202, 1), (211, 1), (409, 2), (634, 3), (439, 0), (190, 0), (671, 0), (694, 0)])
 def test_cross_stage_fusion_geometry_sweep(weights, side, blocks):
     """Edges of the fused kernel's column-block plan: the narrowest supported row (stage-2 input 193 + 1: a one-lane tail
     DMA piece), an odd width, two equal blocks, three blocks of the maximum width 215 (615 output columns), and sides with
-    no plan (0 blocks: two launches).  Fused results must be the stage launches' bit for bit."""
+    no plan (0 blocks: two launches; 671 and 694: the first and the last side at which stage 5 runs four column blocks, the
+    flatten at the head's limit of 4096).  Fused results must be the stage launches' bit for bit."""
     from oracle import roomnet_ref as R
     from roomnet_amd.synth import parity_batch
     g = build_graph(6, side)
@@ -548,10 +549,11 @@ def test_conv16_stage_matches_the_generic_kernel_at_odd_sizes(weights, side):
             ref.close()
 
 
-@pytest.mark.parametrize("side", [205, 211, 212, 219, 225, 226, 240, 420, 600])
+@pytest.mark.parametrize("side", [205, 211, 212, 219, 225, 226, 240, 420, 600, 630, 686])
 def test_row_blocked_stage_kernels_match_the_round2_kernels_at_their_geometry_edges(weights, side):
     """Stages 4, 5 and 6 run with row-register blocking where their rows can be cut into column blocks of 194-206 / 66-110 /
-    35-50 input columns (rn_stage4x/5x/6x.hip: one block at sides 212-225, two at 420, three at 600: the block seams), and on the
+    35-50 input columns (rn_stage4x/5x/6x.hip: one block at sides 212-225, two at 420, three at 600, four of stage 6 at 630 and of
+    stages 5 and 6 at 686: the block seams), and on the
     round-2 kernels elsewhere.  `pair32=True` forces the round-2 kernels everywhere: the 32-channel block is bit-identical in
     both arms, so stage 4 sees identical inputs and may differ by the last 16-bit place (other accumulation order, fp16
     band-matrix pooling instead of fp32 sums); stages 5 and 6 inherit that.  1 and 3 images (one band / several bands)."""

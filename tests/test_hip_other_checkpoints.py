@@ -21,10 +21,10 @@ import checkpoints as CK
 import stage_ref as SR
 from conftest import parity_set_of
 from oracle import c_oracle, roomnet_ref as R
-from parity_bounds import FUSED_AWAY, MARGIN, STAGE_TOL, TIE_EDGE, _downstream_same, _same_up_to_sum_order, _tol
+from parity_bounds import FUSED_AWAY, _downstream_same, _same_up_to_sum_order
 from roomnet_amd import _capi
 from roomnet_amd.graph import build_graph
-from stage_ref import NOTHING_FOLDED, SECTION, STAGE_OUT, _check_nodes, check_stage_local
+from stage_ref import NOTHING_FOLDED, SECTION, STAGE_OUT, _check_nodes, check_head_local, check_stage_local
 
 pytestmark = pytest.mark.gpu
 
@@ -146,50 +146,6 @@ def test_one_launch_back_end_on_live_is_bit_identical_to_the_split_launches(grap
 
 
 # ---------------------------------------------------------------------------------------------- d. head width
-def check_head_local(eng, w, n, ids, probs, record=None, key=""):
-    """The float32 head (dense chain, softmax, argmax) of any handle against float64 computed from the handle's own s9.bn2."""
-    g = eng.graph
-    nc = g.num_classes
-    s9 = eng.tap("s9.bn2", n)
-    h64, h32 = SR.head_local(g, w, s9), SR.head_local_f32(g, w, s9)
-    logits = eng.tap("d3.relu", n)
-    assert logits.shape == (n, nc) and probs.shape == (n, nc) and ids.shape == (n,)
-    el, tl = float(np.abs(logits - h64["logits"]).max()), _tol(h64["logits"], h32["logits"])
-    ep, tp = float(np.abs(probs - h64["probs"]).max()), _tol(h64["probs"], h32["probs"])
-    # ids: the float64 winner where its margin over the runner-up is clear; an exact float64 tie for the first place (ReLU6 makes
-    # exact 0.0 and 6.0 common) must resolve to the lowest index, where the tie is not an accident of a pre-activation that
-    # float32 may put on the other side of the clamp's end
-    lg, mm = h64["logits"], h64["d%d.mm" % g.dense[-1].index]
-    checked = ties = 0
-    wrong = []
-    for i in range(n):
-        tied = np.flatnonzero(lg[i] == lg[i].max())
-        rest = np.delete(lg[i], tied)
-        clear = rest.size == 0 or lg[i].max() - rest.max() > MARGIN
-        solid = len(tied) == 1 or bool((np.minimum(np.abs(mm[i][tied]), np.abs(mm[i][tied] - 6.0)) > TIE_EDGE).all())
-        if clear and solid:
-            checked += 1
-            ties += len(tied) > 1
-            if ids[i] != tied[0]:
-                wrong.append((i, int(ids[i]), tied.tolist()))
-    psum = float(np.abs(probs.sum(1) - 1.0).max())
-    row = {"logits_err": el, "logits_tol": tl, "probs_err": ep, "probs_tol": tp, "ids_checked": checked, "of": n,
-           "exact_fp64_ties_checked": int(ties), "max_abs_probs_sum_minus_1": psum}
-    print("head nc=%d n=%d  logits %.3g / %.3g  probs %.3g / %.3g  ids checked %d (ties %d)  |sum - 1| %.2g" % (
-        nc, n, el, tl, ep, tp, checked, ties, psum))
-    if record:
-        record(SECTION, key, row)
-    assert el <= tl and ep <= tp, row
-    assert not wrong, wrong
-    assert psum <= 1e-5
-    # whatever the margins (at 64 classes none of these images has a clear one): the id is the first maximum of the handle's own probs
-    np.testing.assert_array_equal(ids, [int(np.flatnonzero(p == p.max())[0]) for p in probs])
-    if nc == 1:
-        np.testing.assert_array_equal(probs, np.float32(1.0))
-        np.testing.assert_array_equal(ids, 0)
-    return row
-
-
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("nc", [1, 2, 10, 64])
 def test_head_width_head_locally_vs_fp64(parity_images, record, nc, dtype):

@@ -318,7 +318,7 @@ typedef struct rn_jpeg_info {
     int32_t hsamp, vsamp;             /* luma sampling: 1x1, 2x1 or 2x2             */
     int32_t restart_interval;         /* MCUs between RSTn markers, 0: none         */
     int32_t blocks_w[3], blocks_h[3]; /* per component: 8x8 blocks, whole MCUs      */
-    int32_t supported;
+    int32_t supported;                /* 0: no; 1: yes; 2..8 (the oriented probes): yes, turned by that EXIF orientation */
     uint16_t qt[3][64];               /* per component, natural (row-major) order   */
     char reason[RN_JPEG_REASON_LEN];  /* why supported == 0                         */
 } rn_jpeg_info;
@@ -407,6 +407,42 @@ RN_API int rn_jpeg_huffman_batch(rn_handle* h, const rn_jpeg_file* files, int n,
 RN_API int rn_classify_jpeg_files(rn_handle* h, const rn_jpeg_file* files, int n, float* probs, int64_t* ids, int32_t* status);
 RN_API int rn_jpeg_last_huffman_ms(rn_handle* h, float* ms);
 RN_API int rn_jpeg_last_huffman_rounds(rn_handle* h, int n, int32_t* inside, int32_t* across);
+
+/* ---- files with an EXIF orientation, turned where the pixels are stored ---------------------------
+ * DESIGN.md section 20.  A camera held upright writes its JPEG in sensor geometry with EXIF orientation 6 or 8 (front cameras:
+ * 2, 4, 5, 7), and the general decoder turns the pixels after decoding them.  Coefficients, inverse DCT and chroma upsampling
+ * belong to the STORED geometry (the IDCT's two passes round differently and the "fancy" filters are not symmetric), so the turn
+ * is the address the pixel stage's last kernel stores each pixel at.  Opt-in: rn_jpeg_probe and rn_jpeg_scan_probe are what they
+ * were, and so is every call on the infos they fill.
+ *
+ * rn_jpeg_info.supported  0: not supported; 1: supported, upright; k in 2..8: supported, and the decoded pixels are to be turned by
+ *                         EXIF orientation k.  Only the two probes below write 2..8.  width, height, blocks_w / blocks_h stay those
+ *                         of the STORED image whatever `supported` is.  With I the stored height x width image (H x W) the image O
+ *                         the pixel stage writes is, as Pillow's ImageOps.exif_transpose gives it:
+ *                             2: O[y][x] = I[y][W-1-x]        3: I[H-1-y][W-1-x]     4: I[H-1-y][x]                    (O is H x W)
+ *                             5: O[y][x] = I[x][y]   6: I[H-1-x][y]   7: I[H-1-x][W-1-y]   8: I[x][W-1-y]              (O is W x H)
+ * rn_jpeg_probe_oriented  rn_jpeg_probe, except that an EXIF orientation is no refusal: supported = 1..8.  The first "Exif\0\0"
+ *                         APP1 segment decides; a tag value outside 2..8 reads as 1; supported = 0 with a reason for a later Exif
+ *                         segment whose own reading differs from the first one's ("conflicting EXIF segments"), for an orientation
+ *                         entry that is not one SHORT, for an orientation in an XMP packet, and for everything rn_jpeg_probe refuses
+ *                         otherwise.
+ * rn_jpeg_scan_probe_oriented  rn_jpeg_scan_probe on that walk: returns what rn_jpeg_probe_oriented returns; *out is zero for a file
+ *                         that is not supported.
+ * rn_jpeg_oriented_size   the size of O for a supported info: the stored one, swapped for 5..8.  An info that is not a supported
+ *                         one, a null pointer: RN_E_INVALID.
+ * rn_jpeg_entropy_decode, rn_jpeg_huffman_model  walk the headers by the oriented rules exactly when info->supported is 2..8, and
+ *                         then also refuse (RN_E_INVALID) bytes whose orientation is not info->supported.  The coefficients are
+ *                         those of the same file without its APP1 segment, byte for byte.
+ * rn_jpeg_decode_batch_device, rn_classify_jpegs, rn_jpeg_huffman_batch[_device], rn_classify_jpeg_files  take infos with supported
+ *                         1..8 (anything else: RN_E_INVALID).  d_bgr[i] receives O, rn_jpeg_oriented_size's height x width x 3
+ *                         tightly packed (the same number of bytes as I), and the centre crop is O's.  A batch of upright images
+ *                         is enqueued as before: the same two launches with the same grids.  Orientations 2..4 are stored by the
+ *                         same colour launch (the 12-byte run of 4 pixels goes to the mirrored address); a batch that holds an
+ *                         image of orientation 5..8 gets a THIRD launch, which turns 64 x 64 tiles of those images through LDS so
+ *                         that the stores stay runs of 192 contiguous bytes; rn_jpeg_last_decode_ms spans all of them. */
+RN_API int rn_jpeg_probe_oriented(const uint8_t* data, size_t len, rn_jpeg_info* out);
+RN_API int rn_jpeg_scan_probe_oriented(const uint8_t* data, size_t len, rn_jpeg_scan* out);
+RN_API int rn_jpeg_oriented_size(const rn_jpeg_info* info, int* height, int* width);
 
 /* ---- the overlay and the output JPEG, written where the image already is --------------------------
  * cv2.putText and cv2.imwrite of infer.py:89-93 for an image the GPU holds.  An encode is the decode

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "rn_jpeg_last_decode_ms",
     "rn_jpeg_scan_probe", "rn_jpeg_huffman_model", "rn_jpeg_huffman_batch_device", "rn_jpeg_huffman_batch", "rn_classify_jpeg_files",
     "rn_jpeg_last_huffman_ms", "rn_jpeg_last_huffman_rounds",
+    "rn_jpeg_probe_oriented", "rn_jpeg_scan_probe_oriented", "rn_jpeg_oriented_size",
     "rn_jpeg_encode_info", "rn_jpeg_encoded_bound", "rn_jpeg_entropy_encode", "rn_jpeg_overlay_batch_device",
     "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
     "rn_jpeg_encode_headers", "rn_jpeg_huffenc_model", "rn_jpeg_huffenc_batch", "rn_jpeg_encode_files_device", "rn_jpeg_last_huffenc_ms",
@@ -121,6 +122,13 @@ class rn_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hsamp", C.c_int32), ("vsamp", C.c_int32),
                 ("restart_interval", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
                 ("supported", C.c_int32), ("qt", (C.c_uint16 * 64) * 3), ("reason", C.c_char * RN_JPEG_REASON_LEN)]
+
+
+def jpeg_oriented_shape(info) -> Tuple[int, int]:
+    """``(height, width)`` of the image the pixel stage writes for a supported ``rn_jpeg_info``: the stored size, swapped when
+    ``supported`` is an EXIF orientation of 5..8 (``rn_jpeg_oriented_size``)."""
+    h, w = int(info.height), int(info.width)
+    return (w, h) if int(info.supported) >= 5 else (h, w)
 
 
 class rn_jpeg_image(C.Structure):
@@ -366,6 +374,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_jpeg_last_huffman_ms.restype = i32
         lib.rn_jpeg_last_huffman_rounds.argtypes = [vp, i32, vp, vp]
         lib.rn_jpeg_last_huffman_rounds.restype = i32
+    if hasattr(lib, "rn_jpeg_probe_oriented"):
+        lib.rn_jpeg_probe_oriented.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info)]
+        lib.rn_jpeg_probe_oriented.restype = i32
+        lib.rn_jpeg_scan_probe_oriented.argtypes = [vp, sz, C.POINTER(rn_jpeg_scan)]
+        lib.rn_jpeg_scan_probe_oriented.restype = i32
+        lib.rn_jpeg_oriented_size.argtypes = [C.POINTER(rn_jpeg_info), C.POINTER(i32), C.POINTER(i32)]
+        lib.rn_jpeg_oriented_size.restype = i32
     if hasattr(lib, "rn_jpeg_encode_info"):
         lib.rn_jpeg_encode_info.argtypes = [i32, i32, i32, C.POINTER(rn_jpeg_info)]
         lib.rn_jpeg_encode_info.restype = i32
@@ -638,7 +653,7 @@ class Engine:
         items = list(items)
         n = len(items)
         arr = self._jpeg_images(items)
-        shapes = [(int(info.height), int(info.width), 3) for info, _c in items]
+        shapes = [jpeg_oriented_shape(info) + (3,) for info, _c in items]
         d_out = [self.device_malloc(max(1, h * w * 3)) for h, w, _ in shapes]
         try:
             ptrs = (C.c_void_p * max(n, 1))(*d_out)
@@ -660,7 +675,7 @@ class Engine:
         uploaded into a device buffer this engine keeps and grows, then ONE crop + resize launch
         (``rn_crop_resize_batch_u8_device``) into ``self._jpeg_dst``.  Returns ``(addresses, shapes)`` of the full-size images,
         jpegs first; they stay valid until the next call.  Asynchronous; at most ``max_batch`` files."""
-        shapes = [(int(info.height), int(info.width)) for info, _c in jpegs] + [im.shape[:2] for im in images]
+        shapes = [jpeg_oriented_shape(info) for info, _c in jpegs] + [im.shape[:2] for im in images]
         m, s = len(shapes), self.graph.im_side
         if not getattr(self, "_jpeg_dst", 0):
             self._jpeg_dst, self._jpeg_src, self._jpeg_src_cap = self.device_malloc(self.max_batch * s * s * 3), 0, 0

@@ -8,8 +8,12 @@
 //                      |coef * q| <= RN_JPEG_COEF_LIMIT, which rn_jpeg_entropy_decode enforces (include/roomnet_hip.h).
 //   jpeg_color_kernel  4 pixels of a row per lane: "fancy" h2v1 / h2v2 chroma upsampling on the downsampled extent (replication
 //                      when that is at most 2 columns), fixed-point YCbCr -> BGR, 12 bytes stored as three dwords where the row
-//                      is dword-aligned.
-// Both are ONE launch per batch (blockIdx.z = image, a device table of per-image descriptors), as the batched resize is.
+//                      is dword-aligned.  Images with an EXIF orientation of 2..4 are stored by it at the
+//                      mirrored address.
+//   jpeg_color_turn_kernel  the same pixels for images of orientation 5..8, where a source row becomes an output column: 64 x 64
+//                      tiles turned through LDS so that the stores stay runs of 192 contiguous bytes.  Enqueued only for a
+//                      batch that holds such an image.
+// Each is ONE launch per batch (blockIdx.z = image, a device table of per-image descriptors), as the batched resize is.
 // HBM-bound byte work (2 B of coefficients in, 1 B of plane out and in again, 3 B of BGR out per sample); no MFMA.
 #include "rn_jpeg_dev.h"
 #include "rn_jpeg_host.h"
@@ -146,56 +150,157 @@ __device__ __forceinline__ void upsample4(const uint8_t* __restrict__ p, int64_t
     out[3] = (3 * t1 + t2 + 7) >> 4;
 }
 
+// The arithmetic of a pixel, stated once for both colour kernels: 4 pixels at columns x4 .. x4 + 3 (x4 a multiple of 4) of row y,
+// both in STORED geometry -- the luma read, the chroma reads or upsample4, the three colour formulas and the clamp -- each as
+// b | g << 8 | r << 16.  (Columns at or past the width are computed from the planes' padding; the callers store none of them.)
+__device__ __forceinline__ void jpeg_pixels4(const JpegDev& d, int x4, int y, uint32_t (&px)[4]) {
+    const int W = d.width, H = d.height;
+    // (the luma plane's rows are whole blocks: the 4 bytes at x4 are inside the row whatever W is)
+    const uint32_t y4 = *reinterpret_cast<const uint32_t*>(d.plane[0] + static_cast<int64_t>(y) * (d.bw[0] * 8) + x4);
+    if (d.ncomp == 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[k] = ((y4 >> (8 * k)) & 255) * 0x010101u;
+        return;
+    }
+    int cb[4], cr[4];
+    const int64_t cs = static_cast<int64_t>(d.bw[1]) * 8;
+    if (d.hsamp == 1) {
+        const uint32_t cb4 = *reinterpret_cast<const uint32_t*>(d.plane[1] + y * cs + x4);
+        const uint32_t cr4 = *reinterpret_cast<const uint32_t*>(d.plane[2] + y * cs + x4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cb[k] = (cb4 >> (8 * k)) & 255;
+            cr[k] = (cr4 >> (8 * k)) & 255;
+        }
+    } else {
+        const bool v2 = d.vsamp == 2;
+        const int cw = (W + 1) >> 1, ch = v2 ? (H + 1) >> 1 : H;
+        upsample4(d.plane[1], cs, cw, ch, v2, x4, y, cb);
+        upsample4(d.plane[2], cs, cw, ch, v2, x4, y, cr);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int yy = (y4 >> (8 * k)) & 255, u = cb[k] - 128, v = cr[k] - 128;
+        const int r = clamp255(yy + ((91881 * v + 32768) >> 16));
+        const int b = clamp255(yy + ((116130 * u + 32768) >> 16));
+        const int g = clamp255(yy + ((-22554 * u - 46802 * v + 32768) >> 16));
+        px[k] = static_cast<uint32_t>(b | (g << 8) | (r << 16));
+    }
+}
+
+// Orientations 1..4 (rows stay rows): the 12-byte run of a lane's 4 pixels goes to row y or H - 1 - y, at
+// column x4 or, with the pixels reversed inside it, at W - 4 - x4.  Images of orientation 5..8 are jpeg_color_turn_kernel's.
 __global__ __launch_bounds__(256) void jpeg_color_kernel(const JpegDev* __restrict__ descs) {
     const JpegDev& d = descs[blockIdx.z];
+    const int orient = d.orient;
+    if (orient >= 5) return;
     const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int W = d.width, H = d.height;
     if (x4 >= W || y >= H) return;
-    // (the luma plane's rows are whole blocks: the 4 bytes at x4 are inside the row whatever W is)
-    const uint32_t y4 = *reinterpret_cast<const uint32_t*>(d.plane[0] + static_cast<int64_t>(y) * (d.bw[0] * 8) + x4);
-    int b[4], g[4], r[4];
-    if (d.ncomp == 1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) b[k] = g[k] = r[k] = (y4 >> (8 * k)) & 255;
-    } else {
-        int cb[4], cr[4];
-        const int64_t cs = static_cast<int64_t>(d.bw[1]) * 8;
-        if (d.hsamp == 1) {
-            const uint32_t cb4 = *reinterpret_cast<const uint32_t*>(d.plane[1] + y * cs + x4);
-            const uint32_t cr4 = *reinterpret_cast<const uint32_t*>(d.plane[2] + y * cs + x4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                cb[k] = (cb4 >> (8 * k)) & 255;
-                cr[k] = (cr4 >> (8 * k)) & 255;
-            }
-        } else {
-            const bool v2 = d.vsamp == 2;
-            const int cw = (W + 1) >> 1, ch = v2 ? (H + 1) >> 1 : H;
-            upsample4(d.plane[1], cs, cw, ch, v2, x4, y, cb);
-            upsample4(d.plane[2], cs, cw, ch, v2, x4, y, cr);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int yy = (y4 >> (8 * k)) & 255, u = cb[k] - 128, v = cr[k] - 128;
-            r[k] = clamp255(yy + ((91881 * v + 32768) >> 16));
-            b[k] = clamp255(yy + ((116130 * u + 32768) >> 16));
-            g[k] = clamp255(yy + ((-22554 * u - 46802 * v + 32768) >> 16));
-        }
+    uint32_t px[4];
+    jpeg_pixels4(d, x4, y, px);
+    int ox = x4;                   // column of the run's first pixel; negative: the run begins left of the row (mirrored edge run)
+    if (orient == 2 || orient == 3) {
+        ox = W - 4 - x4;
+        uint32_t t = px[0];
+        px[0] = px[3];
+        px[3] = t;
+        t = px[1];
+        px[1] = px[2];
+        px[2] = t;
     }
-    uint8_t* o = d.bgr + (static_cast<int64_t>(y) * W + x4) * 3;
-    if (x4 + 3 < W && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+    const int oy = orient >= 3 ? H - 1 - y : y;
+    uint8_t* row = d.bgr + static_cast<int64_t>(oy) * W * 3;
+    uint8_t* o = row + static_cast<int64_t>(ox) * 3;
+    if (ox >= 0 && ox + 3 < W && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
         uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
-        o32[0] = b[0] | (g[0] << 8) | (r[0] << 16) | (b[1] << 24);
-        o32[1] = g[1] | (r[1] << 8) | (b[2] << 16) | (g[2] << 24);
-        o32[2] = r[2] | (b[3] << 8) | (g[3] << 16) | (r[3] << 24);
+        o32[0] = px[0] | (px[1] << 24);
+        o32[1] = (px[1] >> 8) | (px[2] << 16);
+        o32[2] = (px[2] >> 16) | (px[3] << 8);
     } else {
-        for (int k = 0; k < 4 && x4 + k < W; ++k) {
-            o[3 * k] = static_cast<uint8_t>(b[k]);
-            o[3 * k + 1] = static_cast<uint8_t>(g[k]);
-            o[3 * k + 2] = static_cast<uint8_t>(r[k]);
+        for (int k = 0; k < 4; ++k) {
+            const int x = ox + k;
+            if (x < 0 || x >= W) continue;
+            row[3 * x] = static_cast<uint8_t>(px[k]);
+            row[3 * x + 1] = static_cast<uint8_t>(px[k] >> 8);
+            row[3 * x + 2] = static_cast<uint8_t>(px[k] >> 16);
         }
     }
+}
+
+// Orientations 5..8 (a source row becomes an output column).  One workgroup takes a kTurnTile x kTurnTile
+// tile of SOURCE pixels: it computes them with jpeg_pixels4 (16 lanes x 4 pixels across, 16 rows per step), writes each as one
+// dword into LDS at its turned position, passes one barrier, and stores the tile's output rows from LDS: runs of up to 64 pixels
+// = 192 contiguous bytes, as dwords from the first 4-byte boundary of the run on and as bytes at its two ends.
+// LDS pitch 65 dwords.  Phase 1 (ds_write_b32, banks = dword address mod 32, lanes conflict within a 32-lane half): a half holds
+// 16 column groups x 2 source rows and writes dword (4 c + j) * 65 + row, bank (4 c + j + row) mod 32: groups c and c + 8 meet,
+// the two rows never do -- 2-way, which a ds_write_b32 absorbs (its 4 issue cycles cover 2 LDS-array cycles per half).  Phase 2
+// (ds_read_b32): lane 4 g + m (m < 3) builds dword 3 g + m of the run from pixels p and p + 1 with p in 4 g .. 4 g + 3, distinct for
+// m = 0, 1, 2 whatever the run's alignment -- 24 distinct dwords of one LDS row per half: conflict-free.  The lanes m = 3 store the
+// end bytes (at most 6 per run).
+constexpr int kTurnTile = 64;
+[[maybe_unused]] constexpr int kTurnPitch = kTurnTile + 1;      // (unused in a -DJPEG_TURN_DIRECT build)
+
+__global__ __launch_bounds__(256) void jpeg_color_turn_kernel(const JpegDev* __restrict__ descs) {
+    const JpegDev& d = descs[blockIdx.z];
+    const int orient = d.orient;
+    if (orient < 5) return;
+    const int W = d.width, H = d.height;
+    const int sx0 = blockIdx.x * kTurnTile, sy0 = blockIdx.y * kTurnTile;
+    if (sx0 >= W || sy0 >= H) return;              // (uniform per workgroup: in front of the barrier)
+    const int ncols = min(kTurnTile, W - sx0), nrows = min(kTurnTile, H - sy0);      // the tile's source extent
+    // output O is W x H (rows x columns): O[oy][ox] = I[sy][sx] with ox = sy (5, 8) or H - 1 - sy (6, 7), oy = sx (5, 6) or
+    // W - 1 - sx (7, 8).  The tile's output extent is ncols rows of nrows pixels from (oy0, ox0).
+    const bool flip_x = orient == 6 || orient == 7, flip_y = orient >= 7;
+    const int ox0 = flip_x ? H - sy0 - nrows : sy0;
+    const int oy0 = flip_y ? W - sx0 - ncols : sx0;
+    const int t = threadIdx.x, cx = (t & 15) * 4;
+#ifndef JPEG_TURN_DIRECT
+    __shared__ uint32_t s_tile[kTurnTile * kTurnPitch];
+#endif
+    for (int sy = t >> 4; sy < nrows; sy += 16) {
+        if (cx >= ncols) continue;
+        uint32_t px[4];
+        jpeg_pixels4(d, sx0 + cx, sy0 + sy, px);
+        const int lx = flip_x ? nrows - 1 - sy : sy;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (cx + j >= ncols) continue;
+            const int ly = flip_y ? ncols - 1 - (cx + j) : cx + j;
+#ifndef JPEG_TURN_DIRECT
+            s_tile[ly * kTurnPitch + lx] = px[j];
+#else
+            // the comparison arm: 3 bytes at a stride of 3 H straight from registers
+            uint8_t* o = d.bgr + (static_cast<int64_t>(oy0 + ly) * H + ox0 + lx) * 3;
+            o[0] = static_cast<uint8_t>(px[j]);
+            o[1] = static_cast<uint8_t>(px[j] >> 8);
+            o[2] = static_cast<uint8_t>(px[j] >> 16);
+#endif
+        }
+    }
+#ifndef JPEG_TURN_DIRECT
+    __syncthreads();
+    const int lane = t & 63, g = lane >> 2, m = lane & 3;
+    const int run_bytes = nrows * 3;
+    for (int ly = t >> 6; ly < ncols; ly += 4) {
+        uint8_t* run = d.bgr + (static_cast<int64_t>(oy0 + ly) * H + ox0) * 3;
+        const uint32_t* src = s_tile + ly * kTurnPitch;
+        const int head = static_cast<int>((0 - reinterpret_cast<uintptr_t>(run)) & 3);      // bytes in front of the first boundary
+        const int ndw = run_bytes > head ? (run_bytes - head) >> 2 : 0;
+        if (m < 3) {
+            const int k = 3 * g + m;
+            if (k < ndw) {                         // bytes n .. n + 3 of the run: pixels p and p + 1 <= nrows - 1
+                const int n = head + 4 * k, p = n / 3;
+                const uint64_t two = src[p] | (static_cast<uint64_t>(src[p + 1]) << 24);
+                *reinterpret_cast<uint32_t*>(run + n) = static_cast<uint32_t>(two >> (8 * (n - 3 * p)));
+            }
+        } else if (g < 6) {                        // end byte g: the head's, then the tail's (at most 3 each)
+            const int n = g < head ? g : head + 4 * ndw + (g - head);
+            if (n < run_bytes) run[n] = static_cast<uint8_t>(src[n / 3] >> (8 * (n % 3)));
+        }
+    }
+#endif
 }
 
 }  // namespace
@@ -223,9 +328,10 @@ int rn_jpeg_state(rn_handle* h, JpegState** out) {
     return RN_OK;
 }
 
-// a supported image as rn_jpeg_probe fills it: every size the kernels index with is recomputed from width, height and sampling
+// a supported image as rn_jpeg_probe or rn_jpeg_probe_oriented fills it (supported 1, or the orientation 2..8): every size the
+// kernels index with is recomputed from width, height and sampling
 bool rn_jpeg_info_ok(const rn_jpeg_info& f) {
-    if (f.supported != 1 || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
+    if (f.supported < 1 || f.supported > 8 || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
     if (f.ncomp != 1 && f.ncomp != 3) return false;
     const bool s11 = f.hsamp == 1 && f.vsamp == 1, s21 = f.hsamp == 2 && f.vsamp == 1, s22 = f.hsamp == 2 && f.vsamp == 2;
     if (!(s11 || ((s21 || s22) && f.ncomp == 3))) return false;
@@ -237,11 +343,11 @@ bool rn_jpeg_info_ok(const rn_jpeg_info& f) {
 
 namespace {
 
-// Upload + the two launches for n checked images, all with host coefficients or all with coefficients a launch on the handle's stream
+// Upload + the launches (two; three when an image of orientation 5..8 is among them) for n checked images, all with host coefficients or all with coefficients a launch on the handle's stream
 // left in device memory.  d_bgr == nullptr: into the handle's own image scratch (st->bgr_ptrs).
 int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, uint8_t* const* d_bgr) {
     size_t coef_total = 0, plane_total = 0, bgr_total = 0;
-    int max_blocks = 0, max_w = 0, max_h = 0;
+    int max_blocks = 0, max_w = 0, max_h = 0, turn_w = 0, turn_h = 0;      // (stored sizes; turn_*: of the images of orientation 5..8)
     for (int i = 0; i < n; ++i) {
         const rn_jpeg_info& f = *jobs[i].info;
         for (int c = 0; c < f.ncomp; ++c) {
@@ -253,6 +359,10 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, 
         bgr_total += (static_cast<size_t>(f.width) * f.height * 3 + 15) & ~static_cast<size_t>(15);
         max_w = std::max(max_w, f.width);
         max_h = std::max(max_h, f.height);
+        if (f.supported >= 5) {
+            turn_w = std::max(turn_w, f.width);
+            turn_h = std::max(turn_h, f.height);
+        }
     }
     int rc, set;
     if ((rc = st->turn.acquire(&set)) != RN_OK) return rc;
@@ -287,6 +397,7 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, 
         d.ncomp = f.ncomp;
         d.hsamp = f.hsamp;
         d.vsamp = f.vsamp;
+        d.orient = f.supported;
         if (d_bgr) {
             d.bgr = d_bgr[i];
         } else {
@@ -303,6 +414,11 @@ int enqueue_decode(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, 
     RN_CHECK_LAUNCH();
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((max_w + 255) / 256, (max_h + 3) / 4, n), dim3(256), 0, h->stream, tab.dev);
     RN_CHECK_LAUNCH();
+    if (turn_w) {
+        hipLaunchKernelGGL(jpeg_color_turn_kernel, dim3((turn_w + kTurnTile - 1) / kTurnTile, (turn_h + kTurnTile - 1) / kTurnTile, n),
+                           dim3(256), 0, h->stream, tab.dev);
+        RN_CHECK_LAUNCH();
+    }
     if ((rc = st->timer.stop(h->stream)) != RN_OK) return rc;
     RN_HIP(hipEventRecord(st->done, h->stream));
     return st->turn.retire(h->stream);
@@ -313,7 +429,7 @@ int check_images(const char* who, rn_handle* h, const rn_jpeg_image* ims, int n)
     if (rc != RN_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (!ims[i].coeffs || !rn_jpeg_info_ok(ims[i].info)) {
-            rn_set_error("%s: image %d is not a supported JPEG as rn_jpeg_probe describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
+            rn_set_error("%s: image %d is not a supported JPEG as rn_jpeg_probe[_oriented] describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
                          who, i, ims[i].info.width, ims[i].info.height, ims[i].info.ncomp, ims[i].info.hsamp, ims[i].info.vsamp,
                          ims[i].info.supported);
             return RN_E_INVALID;
@@ -333,7 +449,7 @@ int rn_jpeg_classify_jobs(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, 
     int rc = enqueue_decode(h, st, jobs, n, nullptr);
     if (rc != RN_OK) return rc;
     // from here on it is rn_crop_resize_batch_u8_device + rn_forward_u8_device, as rn_classify_images_u8 runs them
-    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) { return rn_center_window(st->bgr_ptrs[i], jobs[i].info->height, jobs[i].info->width); });
+    rc = rn_enqueue_resize_batch(h, n, h->d_in_u8, [&](int i) { return rn_center_window(st->bgr_ptrs[i], rn_jpeg_out_height(*jobs[i].info), rn_jpeg_out_width(*jobs[i].info)); });
     if (rc != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, h->d_in_u8, n, h->d_probs, h->d_ids)) != RN_OK) return rc;
     return rn_results_to_host(h, n, probs, ids);
@@ -365,6 +481,31 @@ extern "C" int rn_jpeg_probe(const uint8_t* data, size_t len, rn_jpeg_info* out)
         return rc;
     }
     *out = p.info;
+    return RN_OK;
+}
+
+extern "C" int rn_jpeg_probe_oriented(const uint8_t* data, size_t len, rn_jpeg_info* out) {
+    if (!data || !out) {
+        rn_set_error("rn_jpeg_probe_oriented: null argument");
+        return RN_E_INVALID;
+    }
+    static thread_local rn_jpeg::Parsed p;
+    const int rc = rn_jpeg::parse(data, len, p, true);
+    if (rc != RN_OK) {
+        rn_set_error("rn_jpeg_probe_oriented: not a JPEG file, or its headers are truncated");
+        return rc;
+    }
+    *out = p.info;
+    return RN_OK;
+}
+
+extern "C" int rn_jpeg_oriented_size(const rn_jpeg_info* info, int* height, int* width) {
+    if (!info || !height || !width || !rn_jpeg_info_ok(*info)) {
+        rn_set_error("rn_jpeg_oriented_size: a null pointer, or not a supported info as rn_jpeg_probe[_oriented] fills it");
+        return RN_E_INVALID;
+    }
+    *height = rn_jpeg_out_height(*info);
+    *width = rn_jpeg_out_width(*info);
     return RN_OK;
 }
 

@@ -10,8 +10,9 @@
 struct JpegDev {
     const int16_t* coef[3];   // [blocks_h][blocks_w][64] per component
     uint8_t* plane[3];        // [blocks_h * 8][blocks_w * 8] per component
-    uint8_t* bgr;             // [height][width][3]
-    int32_t width, height, ncomp, hsamp, vsamp;
+    uint8_t* bgr;             // [height][width][3]; orient 5..8: [width][height][3]
+    int32_t width, height, ncomp, hsamp, vsamp;      // the STORED size
+    int32_t orient;           // EXIF orientation 1..8 the store turns the pixels by
     int32_t bw[3], bh[3];
     uint16_t qt[3][64];
 };
@@ -66,5 +67,8 @@ struct rn_jpeg_job {
 // (rn_jpeg.hip)
 int rn_jpeg_state(rn_handle* h, JpegState** out);
 bool rn_jpeg_info_ok(const rn_jpeg_info& f);
+// the size of the image the pixel stage leaves for a checked info: the stored one, swapped for orientations 5..8
+inline int rn_jpeg_out_height(const rn_jpeg_info& f) { return f.supported >= 5 ? f.width : f.height; }
+inline int rn_jpeg_out_width(const rn_jpeg_info& f) { return f.supported >= 5 ? f.height : f.width; }
 // upload + the two pixel-stage launches, then crop + resize + forward pass, results to the host: the body of rn_classify_jpegs
 int rn_jpeg_classify_jobs(rn_handle* h, JpegState* st, const rn_jpeg_job* jobs, int n, float* probs, int64_t* ids);

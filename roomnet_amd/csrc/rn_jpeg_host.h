@@ -41,6 +41,7 @@ struct Parsed {
     HuffTable dc[4], ac[4];
     int comp_dc[3], comp_ac[3];
     size_t scan_begin;           // first byte of the entropy-coded segment
+    int orient;                  // oriented walk: the EXIF orientation the first Exif segment gives, 1..8
 };
 
 inline int unsupported(rn_jpeg_info& info, const char* why) {
@@ -76,8 +77,9 @@ inline bool build_table(HuffTable& t) {
 }
 
 // APP1 "Exif\0\0": IFD0 tag 0x0112 (orientation), either byte order.  Returns the value, 0 when the tag is absent or the segment
-// is not readable as TIFF.
-inline int exif_orientation(const uint8_t* p, size_t n) {
+// is not readable as TIFF.  *plain (when asked for): false for an entry that is not one SHORT, the only form the oriented walk takes.
+inline int exif_orientation(const uint8_t* p, size_t n, bool* plain = nullptr) {
+    if (plain) *plain = true;
     if (n < 14 || std::memcmp(p, "Exif\0\0", 6) != 0) return 0;
     const uint8_t* t = p + 6;
     const size_t tn = n - 6;
@@ -99,7 +101,10 @@ inline int exif_orientation(const uint8_t* p, size_t n) {
     for (size_t i = 0; i < count; ++i) {
         const size_t e = ifd + 2 + 12 * i;
         if (e > tn || tn - e < 12) return 0;
-        if (u16(e) == 0x0112) return static_cast<int>(u16(e + 8));
+        if (u16(e) == 0x0112) {
+            if (plain) *plain = u16(e + 2) == 3 && u32(e + 4) == 1;
+            return static_cast<int>(u16(e + 8));
+        }
     }
     return 0;
 }
@@ -114,10 +119,15 @@ inline bool contains(const uint8_t* p, size_t n, const char* word) {
 
 // The marker walk up to the first byte of the scan.  RN_E_INVALID: not a JPEG / truncated or inconsistent headers.
 // RN_OK with info.supported = 0 and a reason: a JPEG this decoder leaves to the general one.
-inline int parse(const uint8_t* data, size_t len, Parsed& p) {
+// `oriented` (rn_jpeg_probe_oriented): an EXIF orientation of 2..8 is no refusal; the file's info.supported
+// becomes that orientation.  The first Exif segment decides, as it does for Pillow; a tag value outside 2..8 reads as 1; a later
+// Exif segment that reads otherwise, and an orientation entry that is not one SHORT, are refusals.  Everything else is the same walk.
+inline int parse(const uint8_t* data, size_t len, Parsed& p, bool oriented = false) {
     rn_jpeg_info& info = p.info;
     std::memset(&info, 0, sizeof(info));
     info.supported = 1;
+    p.orient = 1;
+    bool have_exif = false;
     for (auto& t : p.dc) t.present = false;
     for (auto& t : p.ac) t.present = false;
     if (!data || len < 4 || data[0] != 0xFF || data[1] != 0xD8) return RN_E_INVALID;
@@ -202,8 +212,22 @@ inline int parse(const uint8_t* data, size_t len, Parsed& p) {
         } else if (m == 0xEE) {                                               // APP14
             if (n >= 5 && std::memcmp(s, "Adobe", 5) == 0) unsupported(info, "Adobe APP14 segment");
         } else if (m == 0xE1) {                                               // APP1: EXIF or XMP
-            const int o = exif_orientation(s, n);
-            if (o >= 2 && o <= 8) unsupported(info, "EXIF orientation is not 1");
+            if (!oriented) {
+                const int o = exif_orientation(s, n);
+                if (o >= 2 && o <= 8) unsupported(info, "EXIF orientation is not 1");
+            } else if (n >= 6 && std::memcmp(s, "Exif\0\0", 6) == 0) {
+                bool plain = true;
+                const int o = exif_orientation(s, n, &plain);
+                const int reading = o >= 2 && o <= 8 ? o : 1;
+                if (!plain) {
+                    unsupported(info, "EXIF orientation entry is not one SHORT");
+                } else if (!have_exif) {
+                    have_exif = true;
+                    p.orient = reading;
+                } else if (reading != p.orient) {
+                    unsupported(info, "conflicting EXIF segments");
+                }
+            }
             // (an XMP packet can carry tiff:Orientation as well, and the general decoder honours it when EXIF has none)
             if (n >= 4 && std::memcmp(s, "http", 4) == 0 && contains(s, n, "Orientation")) unsupported(info, "XMP orientation");
         } else if (m == 0xDC) {
@@ -244,6 +268,7 @@ inline int parse(const uint8_t* data, size_t len, Parsed& p) {
                 std::memcpy(info.qt[c], qtab[comp_q[c]], sizeof(info.qt[c]));
             }
             p.scan_begin = pos;
+            info.supported = p.orient;       // (1 unless the walk is the oriented one)
             return RN_OK;
         }
         // every other segment (APPn, COM, ...) is skipped
@@ -322,8 +347,18 @@ inline int receive_extend(BitReader& br, int s) {
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-// The Huffman pass.  `info` must be what rn_jpeg_probe returned for these bytes (the headers are walked again here: the
-// Huffman tables are not part of rn_jpeg_info, and the sizes every index is bounded by are taken from THESE bytes).
+// info.supported of a file the oriented walk took: the EXIF orientation the pixels are to be turned by
+inline bool turned(const rn_jpeg_info& info) { return info.supported >= 2 && info.supported <= 8; }
+
+// what a second walk of the bytes must find again for `info` to describe them; the orientation too when the info carries one
+inline bool describes(const rn_jpeg_info& info, const rn_jpeg_info& pi) {
+    return info.width == pi.width && info.height == pi.height && info.ncomp == pi.ncomp && info.hsamp == pi.hsamp &&
+           info.vsamp == pi.vsamp && (!turned(info) || info.supported == pi.supported);
+}
+
+// The Huffman pass.  `info` must be what rn_jpeg_probe (or rn_jpeg_probe_oriented: the walk is then the oriented one) returned for
+// these bytes (the headers are walked again here: the Huffman tables are not part of rn_jpeg_info, and the sizes every index is
+// bounded by are taken from THESE bytes).
 // coeffs [component][block_y][block_x][64] natural order, `cap` int16 elements available.
 inline int entropy_decode(const uint8_t* data, size_t len, const rn_jpeg_info* info, int16_t* coeffs, size_t cap, const char** why) {
     static thread_local Parsed p;      // 12 KB of tables: not on the stack of a pool thread, not allocated per image
@@ -332,7 +367,7 @@ inline int entropy_decode(const uint8_t* data, size_t len, const rn_jpeg_info* i
         *why = "null argument";
         return RN_E_INVALID;
     }
-    if (parse(data, len, p) != RN_OK) {
+    if (parse(data, len, p, turned(*info)) != RN_OK) {
         *why = "not a JPEG file, or its headers are truncated";
         return RN_E_INVALID;
     }
@@ -341,8 +376,7 @@ inline int entropy_decode(const uint8_t* data, size_t len, const rn_jpeg_info* i
         return RN_E_INVALID;
     }
     const rn_jpeg_info& pi = p.info;
-    if (info->width != pi.width || info->height != pi.height || info->ncomp != pi.ncomp || info->hsamp != pi.hsamp ||
-        info->vsamp != pi.vsamp) {
+    if (!describes(*info, pi)) {
         *why = "the info does not describe these bytes";
         return RN_E_INVALID;
     }

@@ -194,7 +194,7 @@ int check_files(const char* who, rn_handle* h, const rn_jpeg_file* files, int n,
     }
     for (int i = 0; i < n; ++i)
         if (!files[i].bytes || !rn_jpeg_info_ok(files[i].info)) {
-            rn_set_error("%s: file %d is not a supported JPEG as rn_jpeg_probe describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
+            rn_set_error("%s: file %d is not a supported JPEG as rn_jpeg_probe[_oriented] describes one (%dx%d, %d components, sampling %dx%d, supported %d)",
                          who, i, files[i].info.width, files[i].info.height, files[i].info.ncomp, files[i].info.hsamp,
                          files[i].info.vsamp, files[i].info.supported);
             return RN_E_INVALID;
@@ -306,6 +306,16 @@ extern "C" int rn_jpeg_scan_probe(const uint8_t* data, size_t len, rn_jpeg_scan*
     }
     const int rc = scan_probe(data, len, out);
     if (rc != RN_OK) rn_set_error("rn_jpeg_scan_probe: not a JPEG file, or its headers are truncated");
+    return rc;
+}
+
+extern "C" int rn_jpeg_scan_probe_oriented(const uint8_t* data, size_t len, rn_jpeg_scan* out) {
+    if (!data || !out) {
+        rn_set_error("rn_jpeg_scan_probe_oriented: null argument");
+        return RN_E_INVALID;
+    }
+    const int rc = scan_probe(data, len, out, true);
+    if (rc != RN_OK) rn_set_error("rn_jpeg_scan_probe_oriented: not a JPEG file, or its headers are truncated");
     return rc;
 }
 

@@ -32,10 +32,10 @@ inline void fill_scan(const rn_jpeg::Parsed& p, size_t len, rn_jpeg_scan* out) {
     }
 }
 
-inline int scan_probe(const uint8_t* data, size_t len, rn_jpeg_scan* out) {
+inline int scan_probe(const uint8_t* data, size_t len, rn_jpeg_scan* out, bool oriented = false) {
     static thread_local rn_jpeg::Parsed p;
     std::memset(out, 0, sizeof(*out));
-    const int rc = rn_jpeg::parse(data, len, p);
+    const int rc = rn_jpeg::parse(data, len, p, oriented);
     if (rc != RN_OK) return rc;
     if (p.info.supported) fill_scan(p, len, out);
     return RN_OK;
@@ -150,7 +150,7 @@ inline int model(const uint8_t* data, size_t len, const rn_jpeg_info* info, int1
         *why = "subseq_bytes outside 4 .. 4096";
         return RN_E_RANGE;
     }
-    if (rn_jpeg::parse(data, len, p) != RN_OK) {
+    if (rn_jpeg::parse(data, len, p, rn_jpeg::turned(*info)) != RN_OK) {
         *why = "not a JPEG file, or its headers are truncated";
         return RN_E_INVALID;
     }
@@ -159,8 +159,7 @@ inline int model(const uint8_t* data, size_t len, const rn_jpeg_info* info, int1
         return RN_E_INVALID;
     }
     const rn_jpeg_info& pi = p.info;
-    if (info->width != pi.width || info->height != pi.height || info->ncomp != pi.ncomp || info->hsamp != pi.hsamp ||
-        info->vsamp != pi.vsamp) {
+    if (!rn_jpeg::describes(*info, pi)) {
         *why = "the info does not describe these bytes";
         return RN_E_INVALID;
     }

@@ -127,18 +127,24 @@ def _decode_files(fpaths, batch_size, decode_threads=None):
             yield i, fpath, im
 
 
-def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False, gpu_huffman=False):
+def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False, gpu_huffman=False, gpu_orient=False):
     """Yield ``(index, image_bgr, idx, conf)`` per readable file, in list order.  Files are decoded on a small thread
     pool (Pillow releases the GIL while it decodes) that runs up to two batches ahead of the GPU; the GPU gets the
     decoded images in batches of ``batch_size``.  ``gpu_decode``: ``RoomNet.infer_files`` instead -- baseline JPEG files
     only pass their Huffman stage on the pool and become pixels on the GPU; ``image_bgr`` is then None (the decoded image
     never exists on the host); same ids and confidences.  ``gpu_huffman`` (with ``gpu_decode``): their Huffman stage runs on the GPU
-    too and the pool only reads the files."""
+    too and the pool only reads the files.  ``gpu_orient`` (with ``gpu_decode``): files with an EXIF orientation of 2..8 are decoded
+    and turned on the GPU too instead of by ``imread``."""
     if gpu_huffman and not gpu_decode:
         raise ValueError("gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
+    if gpu_orient and not gpu_decode:
+        raise ValueError("gpu_orient=True needs gpu_decode=True (it is the GPU's pixel stage that turns the image)")
     if gpu_decode:
-        # (a model object without the argument still works while it is off)
-        ids, probs, ok = nn.infer_files(fpaths, decode_threads=decode_threads, batch_size=batch_size, **(dict(gpu_huffman=True) if gpu_huffman else {}))
+        # (a model object without the arguments still works while they are off)
+        extra = dict(gpu_huffman=True) if gpu_huffman else {}
+        if gpu_orient:
+            extra["gpu_orient"] = True
+        ids, probs, ok = nn.infer_files(fpaths, decode_threads=decode_threads, batch_size=batch_size, **extra)
         for i, fpath in enumerate(fpaths):
             if not ok[i]:
                 print(fpath, '---> unreadable image, skipped')
@@ -171,18 +177,21 @@ def _infer_files(nn, fpaths, batch_size, decode_threads=None, gpu_decode=False, 
         yield r
 
 
-def groundtruth_validation(nn, list_fpath=None, batch_size=64, gpu_decode=False, gpu_huffman=False):
+def groundtruth_validation(nn, list_fpath=None, batch_size=64, gpu_decode=False, gpu_huffman=False, gpu_orient=False):
     """infer.py:41-57, with the list file it reads made an argument (the reference's global is
     commented out, infer.py:28).  Prints and returns accuracy and per-class precision / recall /
     f-score, computed like ``train.py:146-152``.  ``gpu_decode``: baseline JPEG files are decoded on the GPU
-    (``RoomNet.infer_files``); same predictions.  ``gpu_huffman`` (with ``gpu_decode``): their Huffman pass too."""
+    (``RoomNet.infer_files``); same predictions.  ``gpu_huffman`` (with ``gpu_decode``): their Huffman pass too.  ``gpu_orient``
+    (with ``gpu_decode``): so are the files with an EXIF orientation of 2..8; same predictions."""
     if gpu_huffman and not gpu_decode:
         raise ValueError("groundtruth_validation: gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
+    if gpu_orient and not gpu_decode:
+        raise ValueError("groundtruth_validation: gpu_orient=True needs gpu_decode=True (it is the GPU's pixel stage that turns the image)")
     from sklearn.metrics import accuracy_score, precision_recall_fscore_support
     fpaths, labels, num_fpaths = read_fpaths(list_fpath or INPUT_IMG_PATH_LIST_FILE)
     print('Inferring Images...')
     y_preds, y_truths = [], []
-    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman):
+    for i, _im, idx, _conf in _infer_files(nn, fpaths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman, gpu_orient=gpu_orient):
         y_preds.append(idx)
         y_truths.append(labels[i])
     acc = accuracy_score(y_truths, y_preds)
@@ -260,7 +269,7 @@ def _heat_overlay_and_write(im, cam_map, weight, pred_label, pred_conf, out_fpat
 
 
 def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5,
-                    gpu_huffman=False, gpu_huffman_encode=False):
+                    gpu_huffman=False, gpu_huffman_encode=False, gpu_orient=False):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
@@ -272,11 +281,15 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     byte for byte.  ``gpu_huffman`` (with ``gpu_decode``): the Huffman pass of the input files runs on the GPU too (DESIGN.md
     section 18; with ``gpu_encode`` the input's Huffman pass stays on the host); same outputs.  ``gpu_huffman_encode`` (with
     ``gpu_encode``): the Huffman pass of the OUTPUT files runs on the GPU too: only the files' bytes come
-    back and the writer pool only writes them; same outputs."""
+    back and the writer pool only writes them; same outputs.  ``gpu_orient`` (with ``gpu_decode``): files with an EXIF orientation of
+    2..8 -- portrait phone photos -- are decoded and turned on the GPU too instead of by ``imread``; same
+    outputs."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     if gpu_huffman and not gpu_decode:
         raise ValueError("classify_im_dir: gpu_huffman=True needs gpu_decode=True (it feeds the GPU's pixel stage)")
+    if gpu_orient and not gpu_decode:
+        raise ValueError("classify_im_dir: gpu_orient=True needs gpu_decode=True (it is the GPU's pixel stage that turns the image)")
     if gpu_encode and not overlay:
         raise ValueError("classify_im_dir: gpu_encode=True needs overlay=True (without the overlay the files are copied: there is "
                          "nothing to encode)")
@@ -313,6 +326,8 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     extra = {} if heatmap is None else dict(heatmap=heatmap, heatmap_weight=heatmap_weight)      # (a model object without the arguments still works without a heat map)
     if gpu_huffman_encode:
         extra["gpu_huffman_encode"] = True
+    if gpu_orient and gpu_encode:
+        extra["gpu_orient"] = True
     if gpu_encode:
         results = _in_batches_of_readable(
             nn.classify_files_to_dir(all_im_paths,
@@ -323,7 +338,7 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
         results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap))
     else:
         results = ((i, idx, conf, im, None) for i, im, idx, conf in
-                   _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman))
+                   _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman, gpu_orient=gpu_orient))
     try:
         for i, idx, pred_conf, im, written in results:
             fpath = all_im_paths[i]
@@ -355,17 +370,21 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     return xl_fpath
 
 
-def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=False):
+def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=False, gpu_orient=False):
     """Re-estimate the model's BN statistics on the images of a directory (``RoomNet.recalibrate_bn``; not in the reference,
     whose statistics only move while it trains, network.py:64-67): the files are decoded as ``classify_im_dir`` decodes them
     and fed in batches of ``batch_size`` (at most the model's ``max_batch``; a last batch of ONE image is dropped: its variance is 0).
     ``momentum=None``: the statistics become the average over the batches.  Returns the new statistics.  ``gpu_decode``: baseline
-    JPEG files are decoded, cropped and resized on the GPU (``RoomNet.prepare_files``); the batches are the same bytes."""
+    JPEG files are decoded, cropped and resized on the GPU (``RoomNet.prepare_files``); the batches are the same bytes.
+    ``gpu_orient`` (with ``gpu_decode``): so are the files with an EXIF orientation of 2..8."""
+    if gpu_orient and not gpu_decode:
+        raise ValueError("recalibrate_from_dir: gpu_orient=True needs gpu_decode=True (it is the GPU's pixel stage that turns the image)")
     all_im_paths = sorted(glob(imgs_dir + '/*'))
+    orient = dict(gpu_orient=True) if gpu_orient else {}      # (a model object without the argument still works while it is off)
 
     def gpu_batches():
         pending = np.zeros((0, nn.im_side, nn.im_side, 3), np.uint8)
-        for _at, batch, bad in nn.prepare_files(all_im_paths, batch_size=batch_size):
+        for _at, batch, bad in nn.prepare_files(all_im_paths, batch_size=batch_size, **orient):
             for i in bad:
                 print(all_im_paths[i], '---> unreadable image, skipped')
             pending = np.concatenate([pending, batch], 0)
@@ -392,13 +411,14 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=
 
 
 def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2,
-                        gpu_decode=False, dropout_rate=None, val_every=None, keep="last", stats_fpath=None):
+                        gpu_decode=False, dropout_rate=None, val_every=None, keep="last", stats_fpath=None, gpu_orient=False):
     """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
     infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
     batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
     features.  ``val_list_fpath``: a second list evaluated after the last step.  ``depth=3`` trains the whole last conv block on
     cached ``s6.bn`` (1.08 MB per image at 224, against 28 KB at depth 2).  Returns what ``fine_tune`` returns.  ``gpu_decode``:
-    the feature extraction decodes baseline JPEG files on the GPU (``RoomNet.prepare_files``); same features.
+    the feature extraction decodes baseline JPEG files on the GPU (``RoomNet.prepare_files``); same features.  ``gpu_orient`` (with
+    ``gpu_decode``): also the files with an EXIF orientation of 2..8; same features.
     ``dropout_rate``: passed to ``fine_tune`` (dropout at every site at or behind the cached feature).
     ``val_every``, ``keep``: passed to ``fine_tune`` (validation on the GPU every ``val_every`` steps; ``keep="best"`` keeps the best
     point's variables).  ``stats_fpath``: every point's ``step``, ``accuracy``, ``precisions``, ``recalls`` and ``f-scores`` are
@@ -406,11 +426,14 @@ def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_f
     ``plotter.py`` reads it as it is; needs ``val_every``."""
     if stats_fpath is not None and val_every is None:
         raise ValueError("fine_tune_from_list: stats_fpath records validation points: pass val_every= (and val_list_fpath=)")
+    if gpu_orient and not gpu_decode:
+        raise ValueError("fine_tune_from_list: gpu_orient=True needs gpu_decode=True (it is the GPU's pixel stage that turns the image)")
+    orient = dict(gpu_orient=True) if gpu_orient else {}      # (a model object without the argument still works while it is off)
     def features_of(path):
         fpaths, labels, _n = read_fpaths(path)
         feats, kept, pending = [], [], []
         if gpu_decode:
-            for at, batch, bad in nn.prepare_files(fpaths, batch_size=extract_batch):
+            for at, batch, bad in nn.prepare_files(fpaths, batch_size=extract_batch, **orient):
                 for i in bad:
                     print(fpaths[i], '---> unreadable image, skipped')
                 if at:

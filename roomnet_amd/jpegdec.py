@@ -8,6 +8,9 @@ GPU kernels of ``csrc/rn_jpeg.hip`` are compared against byte for byte, and whic
 ``decode_bgr`` composes them: the bytes of a supported file -> what ``imageio.imread`` returns for it.
 ``scan_probe_rc``, ``huffman_model_rc`` and ``load_file_bytes`` belong to the second opt-in, the Huffman pass on the GPU (DESIGN.md
 section 18): the scan's byte range and lookup tables, the host model of the parallel decode, and the loader that leaves the pass out.
+``probe_oriented``, ``oriented_shape``, ``turn`` and the ``orient=`` arguments belong to the third, files with an EXIF orientation
+(DESIGN.md section 20): the probe that reads the orientation into ``info.supported`` instead of refusing the file, and the NumPy
+statement of the turn the pixel stage's store applies.
 """
 from __future__ import annotations
 
@@ -54,6 +57,47 @@ def probe(data, lib_path: Optional[str] = None) -> rn_jpeg_info:
     rc, info = probe_rc(data, lib_path)
     _capi._check(_capi.load_library(lib_path), rc, "rn_jpeg_probe")
     return info
+
+
+def probe_oriented_rc(data, lib_path: Optional[str] = None) -> Tuple[int, rn_jpeg_info]:
+    """``rn_jpeg_probe_oriented`` as it returns: ``(code, info)``; ``info.supported`` is 0, 1 or the EXIF orientation 2..8."""
+    lib = _capi.load_library(lib_path)
+    b, n = _as_buffer(data)
+    info = rn_jpeg_info()
+    return int(lib.rn_jpeg_probe_oriented(b, n, C.byref(info))), info
+
+
+def probe_oriented(data, lib_path: Optional[str] = None) -> rn_jpeg_info:
+    """``probe`` for files with an EXIF orientation: ``supported`` is 1 for an upright file and k in 2..8 for one whose decoded
+    pixels are to be turned by orientation k; ``width`` and ``height`` stay the stored ones (``oriented_shape`` gives the turned)."""
+    rc, info = probe_oriented_rc(data, lib_path)
+    _capi._check(_capi.load_library(lib_path), rc, "rn_jpeg_probe_oriented")
+    return info
+
+
+def scan_probe_oriented_rc(data, lib_path: Optional[str] = None) -> Tuple[int, _capi.rn_jpeg_scan]:
+    """``rn_jpeg_scan_probe_oriented`` as it returns: ``(code, scan)``."""
+    lib = _capi.load_library(lib_path)
+    b, n = _as_buffer(data)
+    scan = _capi.rn_jpeg_scan()
+    return int(lib.rn_jpeg_scan_probe_oriented(b, n, C.byref(scan))), scan
+
+
+def oriented_shape(info: rn_jpeg_info) -> Tuple[int, int]:
+    """``(height, width)`` of a supported file's image after the turn (``rn_jpeg_oriented_size``): swapped for orientations 5..8."""
+    return _capi.jpeg_oriented_shape(info)
+
+
+def turn(im: np.ndarray, k: int) -> np.ndarray:
+    """The stored image ``im`` ``[H, W, ...]`` turned by EXIF orientation ``k`` (1..8), as ``ImageOps.exif_transpose`` turns it:
+    2: ``O[y][x] = I[y][W-1-x]``, 3: ``I[H-1-y][W-1-x]``, 4: ``I[H-1-y][x]`` (``O`` is ``H x W``); 5: ``I[x][y]``, 6: ``I[H-1-x][y]``,
+    7: ``I[H-1-x][W-1-y]``, 8: ``I[x][W-1-y]`` (``O`` is ``W x H``)."""
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("turn: orientation %d (1..8)" % k)
+    t = np.swapaxes(im, 0, 1)                    # t[y][x] = I[x][y]
+    out = (im, im[:, ::-1], im[::-1, ::-1], im[::-1], t, t[:, ::-1], t[::-1, ::-1], t[::-1])[k - 1]
+    return np.ascontiguousarray(out)
 
 
 def coeff_count(info: rn_jpeg_info) -> int:
@@ -209,10 +253,14 @@ def pixels_from_coeffs(info: rn_jpeg_info, coeffs: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.clip(np.stack([b, g, r], 2), 0, 255).astype(np.uint8))
 
 
-def decode_bgr(data, lib_path: Optional[str] = None) -> np.ndarray:
-    """The bytes of a supported baseline JPEG file -> BGR uint8 HWC, byte for byte ``imageio.imread`` of that file."""
-    info, coeffs = entropy_decode(data, lib_path=lib_path)
-    return pixels_from_coeffs(info, coeffs)
+def decode_bgr(data, lib_path: Optional[str] = None, orient: bool = False) -> np.ndarray:
+    """The bytes of a supported baseline JPEG file -> BGR uint8 HWC, byte for byte ``imageio.imread`` of that file.  ``orient``:
+    files with an EXIF orientation are supported too: ``probe_oriented``, the stored image, ``turn``."""
+    if not orient:
+        info, coeffs = entropy_decode(data, lib_path=lib_path)
+        return pixels_from_coeffs(info, coeffs)
+    info, coeffs = entropy_decode(data, probe_oriented(data, lib_path), lib_path=lib_path)
+    return turn(pixels_from_coeffs(info, coeffs), int(info.supported))
 
 
 # ---- files -> coefficients on a thread pool (RoomNet.infer_files) ------------------------------------------------------------
@@ -269,13 +317,16 @@ class ByteRing:
         self._bufs = [None] * len(self._bufs)
 
 
-def load_file_bytes(path: str, ring: ByteRing, slot: int):
+def load_file_bytes(path: str, ring: ByteRing, slot: int, orient: bool = False):
     """One file for the classifier when the GPU runs the Huffman pass too: ``("file", info, scan, bytes)``
     -- a supported baseline JPEG, read into the ring's slot and only its markers walked (``rn_jpeg_probe``,
     ``rn_jpeg_scan_probe``); ``bytes`` is the view of the scan's bytes inside the slot; ``("image", bgr)`` -- anything else
-    ``imageio.imread`` reads; ``None`` -- not a readable image.  Runs on a pool thread; the file read and both probes release the GIL."""
+    ``imageio.imread`` reads; ``None`` -- not a readable image.  Runs on a pool thread; the file read and both probes release the GIL.
+    ``orient``: the oriented probes: a file with an EXIF orientation is a ``"file"`` as well, its
+    ``info.supported`` the orientation."""
     from .imageio import imread
     lib = _capi.load_library()
+    probe_fn, scan_fn = (lib.rn_jpeg_probe_oriented, lib.rn_jpeg_scan_probe_oriented) if orient else (lib.rn_jpeg_probe, lib.rn_jpeg_scan_probe)
     try:
         with open(path, "rb") as f:
             size = os.fstat(f.fileno()).st_size
@@ -285,26 +336,28 @@ def load_file_bytes(path: str, ring: ByteRing, slot: int):
         return None
     if got == size and size:
         info = rn_jpeg_info()
-        if lib.rn_jpeg_probe(C.cast(buf.ctypes.data, C.c_char_p), size, C.byref(info)) == 0 and info.supported and \
+        if probe_fn(C.cast(buf.ctypes.data, C.c_char_p), size, C.byref(info)) == 0 and info.supported and \
                 coeff_count(info) <= MAX_COEFFS:
             scan = _capi.rn_jpeg_scan()
-            if lib.rn_jpeg_scan_probe(buf.ctypes.data, size, C.byref(scan)) == 0 and scan.scan_len:
+            if scan_fn(buf.ctypes.data, size, C.byref(scan)) == 0 and scan.scan_len:
                 return ("file", info, scan, buf[int(scan.scan_begin):int(scan.scan_begin) + int(scan.scan_len)])
     im = imread(path)
     return None if im is None else ("image", im)
 
 
-def load_file(path: str, ring: CoeffRing, slot: int):
+def load_file(path: str, ring: CoeffRing, slot: int, orient: bool = False):
     """One file for the classifier: ``("jpeg", info, coeffs)`` -- a supported baseline JPEG, Huffman-decoded into the ring's slot;
     ``("image", bgr)`` -- anything else ``imageio.imread`` reads (other JPEG kinds, damaged JPEG data, PNG, ...); ``None`` -- not
-    a readable image.  Runs on a pool thread: file read, ``rn_jpeg_probe`` and ``rn_jpeg_entropy_decode`` all release the GIL."""
+    a readable image.  Runs on a pool thread: file read, ``rn_jpeg_probe`` and ``rn_jpeg_entropy_decode`` all release the GIL.
+    ``orient``: ``rn_jpeg_probe_oriented``: a file with an EXIF orientation is a ``"jpeg"`` as well, its
+    coefficients those of the stored image and ``info.supported`` the orientation the GPU's store turns the pixels by."""
     from .imageio import imread
     try:
         with open(path, "rb") as f:
             data = f.read()
     except OSError:
         return None
-    rc, info = probe_rc(data)
+    rc, info = probe_oriented_rc(data) if orient else probe_rc(data)
     if rc == 0 and info.supported:
         count = coeff_count(info)
         if count <= MAX_COEFFS:

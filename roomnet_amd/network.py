@@ -334,21 +334,28 @@ class RoomNet:
             prepared.append(np.ascontiguousarray(im))
         return self.infer(np.stack(prepared, 0))
 
-    def infer_files(self, paths, decode_threads=None, batch_size=64, gpu_huffman=False):
+    def infer_files(self, paths, decode_threads=None, batch_size=64, gpu_huffman=False, gpu_orient=False):
         """Classify image FILES, decoding baseline JPEG on the GPU: ``(ids int64[N], probs float32[N,C], ok bool[N])`` in list
         order; ``ok[i]`` False (id -1, zero probabilities) marks a file that is not a readable image.  A pool of
         ``decode_threads`` threads (default ``infer.DECODE_THREADS``, at most 16) reads each file, walks its markers and runs its
         Huffman pass into a ring of reused page-locked buffers (``roomnet_amd.jpegdec``); dequantisation, inverse DCT, chroma
         upsampling, colour conversion, crop, resize and the forward pass run on the GPU, ``batch_size`` files (at most
         ``max_batch``) per call (``rn_classify_jpegs``) while the pool works on the next batch.  Files the split decoder does
-        not take -- progressive, CMYK, rotated by EXIF, damaged, not JPEG at all -- are decoded by ``imageio.imread`` on the same
-        pool and classified by ``infer_images`` in the same call.  Every result equals ``infer_images`` of the ``imread``
+        not take -- progressive, CMYK, with an EXIF orientation other than 1 (unless ``gpu_orient``), damaged, not JPEG at all --
+        are decoded by ``imageio.imread`` on the same pool and classified by ``infer_images`` in the same call.  Every result equals ``infer_images`` of the ``imread``
         images bit for bit.  Not in the reference (infer.py:79-82 decodes with ``cv2.imread``).
 
         ``gpu_huffman``: the Huffman pass runs on the GPU as well.  The pool then only reads each file
         into page-locked memory and walks its markers; the file's bytes go up as they are (``rn_classify_jpeg_files``).  A file
         whose status comes back non-zero is decoded by the host's Huffman pass on the same pool and classified in the same call
-        (``self.huffman_fallbacks`` counts them); the results are the same bits either way."""
+        (``self.huffman_fallbacks`` counts them); the results are the same bits either way.
+
+        ``gpu_orient``: files with an EXIF orientation of 2..8 -- what a phone held upright writes -- go through the split decoder
+        too: the pool reads the orientation (``rn_jpeg_probe_oriented``), the coefficients stay those of the
+        stored image, and the store of the GPU's colour kernel turns the pixels.  The same bits as ``imread``'s turned image.
+
+        After the call ``self.last_decode_paths`` holds how many files took which way: ``"jpeg"`` (split decoder, Huffman pass on
+        the host), ``"file"`` (split decoder, Huffman pass on the GPU), ``"image"`` (``imread``) and ``"unreadable"``."""
         paths = list(paths)
         n = len(paths)
         ids = np.full((n,), -1, np.int64)
@@ -356,9 +363,14 @@ class RoomNet:
         ok = np.zeros((n,), bool)
         eng = self._engine() if n else None
         self.huffman_fallbacks = 0
-        for lo, loaded, pool in self._file_chunks(paths, batch_size, decode_threads, gpu_huffman=gpu_huffman):
+        self.last_decode_paths = self._new_decode_paths()
+        for lo, loaded, pool in self._file_chunks(paths, batch_size, decode_threads, gpu_huffman=gpu_huffman, gpu_orient=gpu_orient):
+            taken = 0
             if gpu_huffman:
-                loaded = self._classify_file_bytes(eng, paths, lo, loaded, pool, ids, probs, ok)
+                before = self.last_decode_paths["file"]
+                loaded = self._classify_file_bytes(eng, paths, lo, loaded, pool, ids, probs, ok, gpu_orient)
+                taken = self.last_decode_paths["file"] - before
+            self._count_decode_paths(loaded, taken)
             jp = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "jpeg"]
             im = [(lo + j, r) for j, r in enumerate(loaded) if r is not None and r[0] == "image"]
             if jp:
@@ -371,7 +383,18 @@ class RoomNet:
                 ids[at], probs[at], ok[at] = a, b, True
         return ids, probs, ok
 
-    def _classify_file_bytes(self, eng, paths, lo, loaded, pool, ids, probs, ok):
+    @staticmethod
+    def _new_decode_paths():
+        return {"jpeg": 0, "file": 0, "image": 0, "unreadable": 0}
+
+    def _count_decode_paths(self, loaded, taken=0):
+        """Add a chunk of loader results to ``self.last_decode_paths``; ``taken`` of its None entries are files
+        ``_classify_file_bytes`` classified and counted."""
+        for r in loaded:
+            self.last_decode_paths["unreadable" if r is None else r[0]] += 1
+        self.last_decode_paths["unreadable"] -= taken
+
+    def _classify_file_bytes(self, eng, paths, lo, loaded, pool, ids, probs, ok, gpu_orient=False):
         """The ``gpu_huffman`` half of ``infer_files`` for one chunk of ``jpegdec.load_file_bytes`` results: the ``"file"`` entries
         are classified from their bytes (``rn_classify_jpeg_files``) and their results stored; returns the chunk with them taken
         out (None in their place, already counted) and every file whose status is not 0 replaced by what ``jpegdec.load_file``
@@ -386,21 +409,23 @@ class RoomNet:
         at = [lo + fl[k][0] for k in good]
         if good:
             ids[at], probs[at], ok[at] = a[good], b[good], True
+            self.last_decode_paths["file"] += len(good)
         for j, _r in fl:
             loaded[j] = None
         again = [fl[k][0] for k in range(len(fl)) if status[k] != 0]
         self.huffman_fallbacks += len(again)
         # (the coefficient ring is free in this mode: the slots of the chunk's first bank take the fallbacks)
-        futures = [(j, pool.submit(jpegdec.load_file, paths[lo + j], self._jpeg_ring, j)) for j in again]
+        futures = [(j, pool.submit(jpegdec.load_file, paths[lo + j], self._jpeg_ring, j, gpu_orient)) for j in again]
         for j, f in futures:
             loaded[j] = f.result()
         return loaded
 
-    def _file_chunks(self, paths, batch_size, decode_threads=None, gpu_huffman=None):
+    def _file_chunks(self, paths, batch_size, decode_threads=None, gpu_huffman=None, gpu_orient=False):
         """Yield ``(lo, [jpegdec.load_file result of paths[lo + j]])`` chunk by chunk (``batch_size``, at most ``max_batch``, files
         each): the pool decodes chunk k + 1 into the other half of the coefficient ring while the consumer works on chunk k.  A
         chunk's coefficient buffers are valid until the consumer asks for the next chunk.  ``gpu_huffman`` not None (``infer_files``):
-        yields ``(lo, results, pool)``, and when it is true the results are ``jpegdec.load_file_bytes``'s, in a ring of byte buffers."""
+        yields ``(lo, results, pool)``, and when it is true the results are ``jpegdec.load_file_bytes``'s, in a ring of byte buffers.
+        ``gpu_orient``: the loaders run with ``orient=True``."""
         from concurrent.futures import ThreadPoolExecutor
         from . import jpegdec
         from .infer import DECODE_THREADS
@@ -422,12 +447,13 @@ class RoomNet:
                     ring.close()
                 ring = self._jpeg_byte_ring = jpegdec.ByteRing(2 * chunk)
             loader = jpegdec.load_file_bytes
+        orient = (True,) if gpu_orient else ()
         n_chunks = (n + chunk - 1) // chunk
         with ThreadPoolExecutor(max_workers=nthreads) as pool:
             def submit(k):
                 # chunk k decodes into bank k % 2 of the ring: that bank was chunk k - 2's, which the consumer was done with when it asked for chunk k - 1
                 lo = k * chunk
-                return [pool.submit(loader, paths[i], ring, (k % 2) * chunk + i - lo) for i in range(lo, min(n, lo + chunk))]
+                return [pool.submit(loader, paths[i], ring, (k % 2) * chunk + i - lo, *orient) for i in range(lo, min(n, lo + chunk))]
             ahead = submit(0)
             for k in range(n_chunks):
                 cur, ahead = ahead, (submit(k + 1) if k + 1 < n_chunks else [])
@@ -435,7 +461,7 @@ class RoomNet:
                 yield (k * chunk, res) if gpu_huffman is None else (k * chunk, res, pool)
 
     def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64, heatmap=None,
-                              heatmap_weight=0.5, gpu_huffman_encode=False):
+                              heatmap_weight=0.5, gpu_huffman_encode=False, gpu_orient=False):
         """Classify image FILES and write each with its overlay as a JPEG file, decode to encode on the GPU.  Yields, in list
         order, ``(index, id, conf, image, future)``: ``future`` is the pending write (on the ``writers`` pool) of a file that went
         through the device; ``image`` (BGR) is set instead for a file whose output name ``out_path_of(index, id)`` has no JPEG
@@ -461,7 +487,11 @@ class RoomNet:
         same reuse rule) and the ``writers`` pool only writes ``buf[:len]``.  A file whose status is not 0 (in practice: one larger than its slot of 2 bytes per coefficient) is encoded again in
         the same call through ``jpeg_encode_batch`` -- WITHOUT overlays where the first call drew them (they are in the image already),
         with them for a ``ST_TOO_LARGE`` image, for which nothing was enqueued -- and
-        ``jpegenc.entropy_encode``; ``self.huffenc_fallbacks`` counts those.  The same bytes."""
+        ``jpegenc.entropy_encode``; ``self.huffenc_fallbacks`` counts those.  The same bytes.
+
+        ``gpu_orient``: files with an EXIF orientation of 2..8 are decoded -- and turned -- on the GPU too
+        instead of by ``imread``; everything behind the decode starts from the upright image either way.  The same bytes.
+        ``self.last_decode_paths`` counts the ways the files took, as after ``infer_files``."""
         import os
         from . import cam, hershey, jpegdec, jpegenc
         from ._capi import GRAD_CAM_LAYERS
@@ -488,6 +518,7 @@ class RoomNet:
                 out_ring = self._jpeg_out_ring = jpegdec.ByteRing(2 * chunk)
             self.huffenc_fallbacks = 0
         pending = [[], []]                      # the writes that still read each bank's buffers
+        self.last_decode_paths = self._new_decode_paths()
 
         def write(info, coeffs, out_path):
             try:
@@ -510,8 +541,9 @@ class RoomNet:
             boxes = [(hershey.coverage(text, org, scale, shape, 1), color) for text, org, scale, color in lines]
             return [(b[0], b[1], b[2], color) for b, color in boxes if b is not None]
 
-        for k, (lo, loaded) in enumerate(self._file_chunks(paths, chunk, decode_threads)):
+        for k, (lo, loaded) in enumerate(self._file_chunks(paths, chunk, decode_threads, gpu_orient=gpu_orient)):
             bank = k % 2
+            self._count_decode_paths(loaded)
             for f in pending[bank]:
                 f.result()
             pending[bank] = []
@@ -561,15 +593,19 @@ class RoomNet:
             for j in range(len(loaded)):
                 yield (lo + j,) + out.get(j, (None, None, None, None))
 
-    def prepare_files(self, paths, decode_threads=None, batch_size=64):
+    def prepare_files(self, paths, decode_threads=None, batch_size=64, gpu_orient=False):
         """Image files -> the batches ``infer`` takes, decoding baseline JPEG on the GPU: yields ``(indices, batch, unreadable)`` per
         chunk of ``batch_size`` files: ``batch`` the uint8 BGR ``[m, S, S, 3]`` centre-cropped, resized images of the readable files
         ``paths[indices]``, ``unreadable`` the indices of the chunk's files that are no readable image -- byte for byte ``center_crop`` + the ``cv2.resize`` restatement of their ``imread`` images.  JPEG
         files the split decoder takes become pixels, are cropped and resized on the GPU and only the ``S x S`` result comes back;
         other files are prepared on the host.  For the callers that need a batch and not a classification: ``recalibrate_bn``
-        (its statistics are the whole batch's) and ``extract_features``."""
+        (its statistics are the whole batch's) and ``extract_features``.  ``gpu_orient``: files with an EXIF orientation of 2..8
+        are among those the split decoder takes; the same bytes.  ``self.last_decode_paths`` counts the
+        ways the files took, as after ``infer_files``."""
         eng = self._engine() if len(paths) else None
-        for lo, loaded in self._file_chunks(list(paths), batch_size, decode_threads):
+        self.last_decode_paths = self._new_decode_paths()
+        for lo, loaded in self._file_chunks(list(paths), batch_size, decode_threads, gpu_orient=gpu_orient):
+            self._count_decode_paths(loaded)
             at = [lo + j for j, r in enumerate(loaded) if r is not None]
             bad = [lo + j for j, r in enumerate(loaded) if r is None]
             if not at:

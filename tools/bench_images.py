@@ -22,6 +22,13 @@
         warm-up of all; the ratios, whether the files are identical, the host Huffman-encode pass alone on one thread, the device
         time of the four phases per batch beside the pixel stage's, the bytes downloaded per batch in both GPU arms, the fallbacks.
         The line that begins "overlay=True" is the --gpu-encode arm's own report from the same runs
+  python tools/bench_images.py --dir --gpu-orient [--orientation=K] [--stage-only] [--threads=T] [H W [N]]    generated directories whose
+        files carry a spliced EXIF orientation, cycling 1..8 or all K, nothing of the above; at 640x480 and
+        1920x1080 unless a size is given: both drivers with gpu_decode=True (turned files fall back to imread: what the option is
+        compared with) against gpu_decode=True, gpu_orient=True on the same files, alternating, three runs each after a warm-up
+        of both, with the spread of the run times and the ways the files took (RoomNet.last_decode_paths); then the device time of
+        the pixel stage (rn_jpeg_last_decode_ms) for one batch of 64 1920x1080 files, all at orientation 1, at 3 and at 6.
+        --stage-only: only that last line (run it with ROOMNET_HIP_LIB=<a -DJPEG_TURN_DIRECT variant> for the comparison arm)
   python tools/bench_images.py --heatmap [--threads=T] [H W [N]]    a generated directory again, nothing of the above: the device time
         of the two heat-map launches (rn_cam_last_overlay_ms) for one batch and both layers, next to the decode's and the encode's
         pixel stages of the same batch; then classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True) with heatmap="s6.bn",
@@ -474,8 +481,111 @@ def gpu_huffman_encode_arm():
     shutil.rmtree(root, ignore_errors=True)
 
 
+def exif_app1(orientation):
+    """An APP1 Exif segment (little-endian TIFF) whose IFD0 holds only the orientation tag."""
+    import struct
+    tiff = b'II' + struct.pack('<HI', 42, 8) + struct.pack('<H', 1) + struct.pack('<HHIHH', 0x0112, 3, 1, orientation, 0) + struct.pack('<I', 0)
+    body = b'Exif\x00\x00' + tiff
+    return b'\xff\xe1' + struct.pack('>H', len(body) + 2) + body
+
+
+def splice_orientations(paths, fixed=None):
+    """Rewrite every file with an orientation spliced in behind SOI: ``fixed``, or 1..8 in turn.  Returns the count of turned files."""
+    turned = 0
+    for k, p in enumerate(paths):
+        o = fixed or 1 + k % 8
+        with open(p, 'rb') as f:
+            data = f.read()
+        assert data[:2] == b'\xff\xd8'
+        with open(p, 'wb') as f:
+            f.write(data[:2] + exif_app1(o) + data[2:])
+        turned += o != 1
+    return turned
+
+
+def pixel_stage_by_orientation():
+    """Device time of the pixel stage for one batch of 64 1920x1080 files, all at orientation 1, 3 and 6: the same coefficients,
+    only info.supported differs."""
+    global H, W, N
+    from roomnet_amd import jpegdec
+    H, W, N = 1080, 1920, 64
+    root, d, nn, paths, mb = generated_directory()
+    eng = nn._engine()
+    items = [jpegdec.entropy_decode(open(p, 'rb').read()) for p in paths]
+    out = {}
+    for rep_ in range(2):                                     # (both rounds are timed; the first call of all is the warm-up)
+        for o in (1, 3, 6):
+            for info, _c in items:
+                info.supported = o
+            ms = []
+            for _ in range(6):
+                eng.classify_jpegs(items)
+                ms.append(eng.jpeg_last_decode_ms())
+            out.setdefault(o, []).append(sorted(ms[1:])[2])
+    px = N * H * W
+    print('pixel stage on the device (%s), one batch of %d files 1920x1080 4:2:0, median of 5 calls, two rounds:   '
+          % (os.environ.get('ROOMNET_HIP_LIB', 'product library'), N)
+          + '   '.join('orientation %d: %s ms (%.0f GB/s of the 3 B coefficients + 3 B planes + 3 B image per pixel)'
+                       % (o, ' / '.join('%.3f' % m for m in v), 9 * px / min(v) / 1e6) for o, v in out.items()))
+    shutil.rmtree(root, ignore_errors=True)
+
+
+def gpu_orient_arm():
+    """gpu_decode=True (turned files go to imread) against gpu_decode=True, gpu_orient=True: same files, same session, alternating."""
+    global H, W
+    from roomnet_amd import infer
+    import sklearn.metrics  # noqa: F401
+    fixed = None
+    for a in sys.argv[1:]:
+        if a.startswith('--orientation='):
+            fixed = int(a.split('=', 1)[1])
+    sizes = [(H, W)] if args else [(480, 640), (1080, 1920)]
+    for H, W in sizes if '--stage-only' not in sys.argv else []:
+        root, d, nn, paths, mb = generated_directory()
+        turned = splice_orientations(paths, fixed)
+        lst = os.path.join(root, 'list.txt')
+        with open(lst, 'w') as f:
+            f.writelines('%s %d\n' % (p, 0) for p in paths)
+        arms = {'gpu_decode': dict(gpu_decode=True), 'gpu_decode + gpu_orient': dict(gpu_decode=True, gpu_orient=True)}
+        t_dir = {a: [] for a in arms}
+        t_val = {a: [] for a in arms}
+        xls, ways = {}, {}
+        with contextlib.redirect_stdout(io.StringIO()):
+            for rep_ in range(4):                                  # round 0 is the warm-up of both arms
+                for arm, kw in arms.items():
+                    t0 = time.perf_counter()
+                    xl = infer.classify_im_dir(nn, d, overlay=False, batch_size=64, **kw)
+                    t1 = time.perf_counter()
+                    ways[arm] = dict(nn.last_decode_paths)
+                    with open(xl, 'rb') as f:
+                        xls[arm] = f.read()
+                    t2 = time.perf_counter()
+                    infer.groundtruth_validation(nn, lst, batch_size=64, **kw)
+                    t3 = time.perf_counter()
+                    if rep_:
+                        t_dir[arm].append(t1 - t0)
+                        t_val[arm].append(t3 - t2)
+        med = lambda t: sorted(t)[len(t) // 2]      # noqa: E731
+        spread = lambda t: 100 * (max(t) - min(t)) / med(t)      # noqa: E731
+        N_ = len(paths)
+        print('%d JPEG files %dx%d (%.0f MB), orientation %s (%d turned), %d decode threads of %d host cores, same files, same session, '
+              'alternating, 3 runs each after a warm-up of both:' % (N_, W, H, mb, fixed or 'cycling 1..8', turned, infer.DECODE_THREADS,
+                                                                     os.cpu_count() or 1))
+        for arm in arms:
+            print('  %-24s classify_im_dir(overlay=False) %s img/s (spread of the run times %.1f %%)   groundtruth_validation %s img/s '
+                  '(spread %.1f %%)   ways: %s' % (arm + ':', ' / '.join('%.1f' % (N_ / x) for x in t_dir[arm]), spread(t_dir[arm]),
+                                                   ' / '.join('%.1f' % (N_ / x) for x in t_val[arm]), spread(t_val[arm]), ways[arm]))
+        a, b = 'gpu_decode', 'gpu_decode + gpu_orient'
+        print('  ratio gpu_orient / gpu_decode alone (medians): classify_im_dir x%.2f   groundtruth_validation x%.2f   workbook identical: %s'
+              % (med(t_dir[a]) / med(t_dir[b]), med(t_val[a]) / med(t_val[b]), xls[a] == xls[b]))
+        shutil.rmtree(root, ignore_errors=True)
+    pixel_stage_by_orientation()
+
+
 if '--heatmap' in sys.argv:
     heatmap_arm()
+elif '--dir' in sys.argv and '--gpu-orient' in sys.argv:
+    gpu_orient_arm()
 elif '--dir' in sys.argv and '--gpu-huffman-encode' in sys.argv:
     gpu_huffman_encode_arm()
 elif '--dir' in sys.argv and '--gpu-huffman' in sys.argv:

@@ -783,6 +783,86 @@ RN_API int rn_ft_set_dropout(rn_ft* ft, float rate, uint64_t seed);
 RN_API int rn_ft_dropout(const rn_ft* ft, float* rate, uint64_t* seed);
 RN_API int rn_ft_dropout_mask(rn_ft* ft, int site, int64_t step, int slot, int64_t count, uint8_t* keep);
 
+/* ---- fine-tuning on fresh random views ----------------------------------------------------------
+ * The reference trains on a feeder built with random_crop=True, preprocess=True (train.py:117-118): every sample of every step is a
+ * fresh random square window slid along the photograph's long axis (generator.py:52-67), resized to the network's side, mirrored
+ * left-right with probability 1/2 and upside-down with probability 1/2 (:85-92).  A cached feature cannot be augmented afterwards
+ * (stages 0-7 are VALID convolutions and pools: their geometry does not commute with a flip or a shifted window), so the views are
+ * made in front of the trunk, every step, from photographs that stay resident on the device.
+ *
+ * The draw, a pure function (csrc/rn_views.h).  For global step t (what rn_ft_step_count returns before the step), minibatch slot b,
+ * a 64-bit seed and a photograph of height x width, with Philox4x32-10 exactly as the dropout section above has it:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (0, b, (uint32) t, RN_VIEW_SITE | ((uint32)(t >> 32) << 8));  site 254 is one no dropout site can take, so the view
+ *             draws and the dropout masks of one seed never share a counter
+ *   side = min(height, width),  range = max(height, width) - side
+ *   RN_VIEW_CROP  offset = (uint64) out[0] * range >> 32: a value in [0, range), as np.random.randint(range) draws one (never
+ *                 offset == range; range == 0: offset 0, the whole image).  Its bias against a true uniform is below range / 2^32.
+ *                 Without the flag: the centre window, exactly rn_center_crop_window (the reference's center_crop).
+ *                 height < width: the window is columns [offset, offset + side); otherwise rows [offset, offset + side).
+ *   RN_VIEW_FLIP  fliplr = out[1] >> 31, flipud = out[2] >> 31.  Without the flag: neither.
+ * The view is flipud(fliplr(resize(window, (S, S)))), the flips behind the resize as in preprocess_set: view[y][x] =
+ * R[flipud ? S-1-y : y][fliplr ? S-1-x : x] with R the integer-exact cv2.resize(INTER_LINEAR) of rn_crop_resize_*, its copy mode
+ * and its 2x2-box mode included.  NumPy's own random stream is not reproduced; the distribution and the sampling rules are.
+ * No draw reads outside the photograph: offset <= range in both modes, so offset + side <= max(height, width).
+ *
+ * rn_view_draw   the draw on the host (no device): x0, y0 and side of the window, and the two flips.  A null `out`, an empty image or
+ *                unknown flag bits: RN_E_INVALID; step < 0 or slot < 0: RN_E_RANGE.
+ * rn_views_create  the training set as a device table that lives for the whole run: per photograph (whole, decoded, tightly packed
+ *                BGR, resident on the handle's device -- the caller keeps the pixels alive) what does not change from step to step:
+ *                base pointer, row stride, side, range, axis, and the two double-precision scales and the mode of the resize, formed
+ *                on the host as rn_crop_resize_* forms them (they depend on the side alone, not on the offset).  A null argument,
+ *                n_items < 1 or an empty photograph: RN_E_INVALID; a failed allocation: RN_E_NOMEM.
+ * rn_views_destroy  frees the table (not the photographs).
+ * rn_views_batch_device  ONE launch on the handle's stream makes the n views of a minibatch into d_dst [n, S, S, 3] uint8: slot b
+ *                reads item d_index[base + b] (device int32), draws its own window and flips on the device and stores every pixel
+ *                at its flipped address.  No per-step table, no per-step upload.  Only enqueues.  Checked on the host before
+ *                anything is enqueued: a null argument, unknown flag bits, or a table made on another device or for another side:
+ *                RN_E_INVALID; n outside [1, max_batch], step < 0 or base < 0: RN_E_RANGE.  The index lives on the device and is not
+ *                read back here: a slot whose index lies outside [0, n_items) is left unwritten. */
+#define RN_VIEW_CROP 1u
+#define RN_VIEW_FLIP 2u
+#define RN_VIEW_SITE 254u
+typedef struct rn_view {
+    int32_t x0, y0, side, fliplr, flipud;
+} rn_view;
+typedef struct rn_view_source {
+    const uint8_t* d_bgr;     /* [height, width, 3] uint8 on the handle's device */
+    int32_t height, width;
+} rn_view_source;
+typedef struct rn_views rn_views;
+RN_API int rn_view_draw(uint64_t seed, int64_t step, int slot, int height, int width, unsigned flags, rn_view* out);
+RN_API int rn_views_create(rn_handle* h, const rn_view_source* srcs, int64_t n_items, rn_views** out);
+RN_API void rn_views_destroy(rn_views* v);
+RN_API int rn_views_batch_device(rn_handle* h, const rn_views* v, const int32_t* d_index, int64_t base, int n, uint64_t seed,
+                                 int64_t step, unsigned flags, uint8_t* d_dst);
+/* rn_ft_run_views  rn_ft_run / rn_ft_run_validated (the six validation arguments all NULL / 0: no validation) with one difference:
+ *                step s does not read resident features.  On the handle's stream it makes the views of slots
+ *                [s * batch, (s + 1) * batch) at the trainer's global step into the handle's input batch (rn_views_batch_device) and
+ *                runs the trunk's feature pass of the trainer's depth (rn_features_depth_u8_device) into a feature slot
+ *                [batch, side, side, C] float32 the trainer owns (two slots taken in turn, allocated by the first such run, so
+ *                that the trunk pass of step s + 1 overlaps the trainer's step s); behind an event the trainer's stream runs the
+ *                step's launches on that slot, with labels gathered once per call in slot order, d_labels[d_index[s * batch + b]];
+ *                an event back keeps the handle from overwriting a slot the trainer still reads.  The handle's stream and its
+ *                input batch are in use until the call returns.  The step's kernels are those of rn_ft_run, the
+ *                loop, the validation schedule and the one synchronisation at the end are the same code.  Dropout is unchanged
+ *                (keyed by slot and step already); the validation set stays cached centre-crop features, as the reference
+ *                validates on random_crop=False, preprocess=False.  d_labels [n_items] and d_index [steps, batch] are device
+ *                memory; `flags` are RN_VIEW_CROP | RN_VIEW_FLIP.
+ *                The handle's weights being the trainer's frozen trunk (stages 0-7 of the model the trainer was created from) is
+ *                the caller's contract: neither object knows the other's weights.
+ *                Guarantees: the same call gives the same bits; one call of k steps equals k calls of one step (the global step
+ *                drives the draws, so a resumed run continues the same sequence); losses, parameters, gradients and Adam slots are
+ *                byte for byte those of the manual loop rn_views_batch_device, rn_features_depth_u8_device, one rn_ft_run step.
+ *                Errors, on the host before anything is enqueued, trainer unchanged: everything rn_ft_run (rn_ft_run_validated)
+ *                refuses; a handle on another device than the trainer's, a graph whose feature shape differs from the trainer's,
+ *                views of another device or side, unknown flag bits, or only some of the validation arguments: RN_E_INVALID;
+ *                batch > the handle's max_batch: RN_E_RANGE; an RN_FLAG_BATCH_STATS handle: RN_E_STATE; a failed allocation of
+ *                the feature slot: RN_E_NOMEM. */
+RN_API int rn_ft_run_views(rn_ft* ft, rn_handle* h, const rn_views* v, const int32_t* d_labels, int64_t n_items, const int32_t* d_index,
+                           int batch, int steps, uint64_t view_seed, unsigned flags, float* losses, const float* d_val_feats,
+                           const int32_t* d_val_labels, int64_t n_val, int val_every, float* val_losses, int32_t* val_confusion);
+
 /* ---- introspection -----------------------------------------------------------
  * rn_tap copies graph node `node_id` of the last forward call to host float32
  * (layout [n, h, w, c]); needs RN_FLAG_TAPS for conv/pool/add nodes; the

@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "rn_ft_step_count", "rn_ft_last_run_ms", "rn_ft_upload", "rn_ft_free",
     "rn_ft_set_dropout", "rn_ft_dropout", "rn_ft_dropout_mask",
     "rn_ft_val_points", "rn_ft_run_validated", "rn_ft_best",
+    "rn_view_draw", "rn_views_create", "rn_views_destroy", "rn_views_batch_device", "rn_ft_run_views",
     "rn_jpeg_probe", "rn_jpeg_coeff_count", "rn_jpeg_entropy_decode", "rn_jpeg_decode_batch_device", "rn_classify_jpegs",
     "rn_jpeg_last_decode_ms",
     "rn_jpeg_scan_probe", "rn_jpeg_huffman_model", "rn_jpeg_huffman_batch_device", "rn_jpeg_huffman_batch", "rn_classify_jpeg_files",
@@ -66,6 +67,9 @@ EXPORTED_SYMBOLS = (
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
 RN_FT_PARAM, RN_FT_GRAD, RN_FT_ADAM_M, RN_FT_ADAM_V = 0, 1, 2, 3
 RN_FT_BEST = 4                           # the master parameters as they were at the best validation point
+
+# rn_views_batch_device / rn_ft_run_views flags (include/roomnet_hip.h: fine-tuning on fresh random views)
+RN_VIEW_CROP, RN_VIEW_FLIP, RN_VIEW_SITE = 1, 2, 254
 
 # the layers rn_grad_cam_* explains (include/roomnet_hip.h: grad-CAM)
 GRAD_CAM_LAYERS = ("s6.bn", "s7.bn")
@@ -115,6 +119,14 @@ class rn_ft_config(C.Structure):
 
 
 RN_JPEG_REASON_LEN = 48
+
+
+class rn_view(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("side", C.c_int32), ("fliplr", C.c_int32), ("flipud", C.c_int32)]
+
+
+class rn_view_source(C.Structure):
+    _fields_ = [("d_bgr", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
 
 
 class rn_jpeg_info(C.Structure):
@@ -347,6 +359,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_ft_run_validated.restype = i32
         lib.rn_ft_best.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.rn_ft_best.restype = i32
+    if hasattr(lib, "rn_ft_run_views"):
+        lib.rn_view_draw.argtypes = [C.c_uint64, C.c_int64, i32, i32, i32, C.c_uint, C.POINTER(rn_view)]
+        lib.rn_view_draw.restype = i32
+        lib.rn_views_create.argtypes = [vp, C.POINTER(rn_view_source), C.c_int64, C.POINTER(vp)]
+        lib.rn_views_create.restype = i32
+        lib.rn_views_destroy.argtypes = [vp]
+        lib.rn_views_destroy.restype = None
+        lib.rn_views_batch_device.argtypes = [vp, vp, vp, C.c_int64, i32, C.c_uint64, C.c_int64, C.c_uint, vp]
+        lib.rn_views_batch_device.restype = i32
+        lib.rn_ft_run_views.argtypes = [vp, vp, vp, vp, C.c_int64, vp, i32, i32, C.c_uint64, C.c_uint, vp, vp, vp, C.c_int64, i32, vp, vp]
+        lib.rn_ft_run_views.restype = i32
     if hasattr(lib, "rn_jpeg_probe"):
         lib.rn_jpeg_probe.argtypes = [C.c_char_p, sz, C.POINTER(rn_jpeg_info)]
         lib.rn_jpeg_probe.restype = i32
@@ -921,6 +944,66 @@ class Engine:
                 self.device_free(d)
             self.device_free(d_dst)
 
+    # -- training views (include/roomnet_hip.h: fine-tuning on fresh random views)
+    def views_create(self, images) -> "Views":
+        """A list of whole BGR uint8 photographs of any size, uploaded ONCE into one device allocation, and the table
+        ``rn_views_create`` makes of them: the resident training set of ``views_batch`` and ``Trainer.run_views``.  A failed
+        allocation raises ``RoomNetLibraryError`` naming the bytes the set needs.  ``views_destroy`` (or ``Views.close``) frees both."""
+        ims = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        for i, im in enumerate(ims):
+            if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError("views_create: image %d is not a BGR [H, W, 3] array (shape %s)" % (i, im.shape))
+        if not ims:
+            raise ValueError("views_create: no image")
+        offsets, total = [], 0
+        for im in ims:
+            offsets.append(total)
+            total += (im.nbytes + 255) & ~255
+        try:
+            d_pixels = self.device_malloc(total)
+        except RoomNetLibraryError as e:
+            raise RoomNetLibraryError("views_create: the %d photographs need %d bytes of device memory: %s" % (len(ims), total, e)) from None
+        v = C.c_void_p()
+        try:
+            srcs = (rn_view_source * len(ims))()
+            for k, (im, off) in enumerate(zip(ims, offsets)):
+                self.h2d(d_pixels + off, im)
+                srcs[k] = rn_view_source(d_pixels + off, im.shape[0], im.shape[1])
+            _check(self.lib, self.lib.rn_views_create(self.handle, srcs, len(ims), C.byref(v)), "rn_views_create")
+        except Exception:
+            self.device_free(d_pixels)
+            raise
+        return Views(self, v, d_pixels, [im.shape[:2] for im in ims], total)
+
+    def views_destroy(self, views: "Views") -> None:
+        views.close()
+
+    def views_batch(self, views: "Views", index, step: int, seed: int = 0, crop: bool = True, flip: bool = True, repeat: int = 1) -> np.ndarray:
+        """The views of one minibatch, made on the GPU in one launch (``rn_views_batch_device``): slot ``b`` is the view of item
+        ``index[b]`` at global step ``step``; returns uint8 ``[n, S, S, 3]`` (``finetune.make_view`` of ``finetune.view_draw`` states
+        the same bytes).  ``repeat`` > 1 launches it that often back to back, without a synchronisation in between."""
+        index = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n, s = int(index.size), self.graph.im_side
+        if index.size and (index.min() < 0 or index.max() >= views.n_items):
+            raise ValueError("views_batch: an index outside [0, %d)" % views.n_items)
+        flags = (RN_VIEW_CROP if crop else 0) | (RN_VIEW_FLIP if flip else 0)
+        d_index = self.device_malloc(max(index.nbytes, 4))
+        d_dst = self.device_malloc(self.max_batch * s * s * 3)
+        try:
+            if n:
+                self.h2d(d_index, index)
+            for _ in range(max(1, int(repeat))):
+                _check(self.lib, self.lib.rn_views_batch_device(self.handle, views.handle, C.c_void_p(d_index), 0, n,
+                                                                C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(step), flags,
+                                                                C.c_void_p(d_dst)), "rn_views_batch_device")
+            self.sync()
+            out = np.empty((n, s, s, 3), np.uint8)
+            self.d2h(out, d_dst)
+            return out
+        finally:
+            self.device_free(d_index)
+            self.device_free(d_dst)
+
     def forward_f32(self, x_rgb: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         s = self.graph.im_side
         x = np.ascontiguousarray(x_rgb, dtype=np.float32)
@@ -1170,6 +1253,34 @@ class Engine:
         return [groups[k] for k in sorted(groups)]
 
 
+class Views:
+    """A resident training set of ``Engine.views_create``: the photographs' pixels in one device allocation and the ``rn_views``
+    table over them.  ``shapes``: ``(height, width)`` of every photograph; ``nbytes``: the size of the pixel allocation."""
+
+    def __init__(self, engine: "Engine", handle: C.c_void_p, d_pixels: int, shapes, nbytes: int):
+        self.engine, self._v, self.d_pixels, self.shapes, self.nbytes = engine, handle, d_pixels, list(shapes), int(nbytes)
+        self.n_items = len(self.shapes)
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if not self._v:
+            raise RoomNetLibraryError("the views are closed")
+        return self._v
+
+    def close(self) -> None:
+        if getattr(self, "_v", None):
+            self.engine.lib.rn_views_destroy(self._v)
+            self._v = None
+            if getattr(self.engine, "_h", None):
+                self.engine.device_free(self.d_pixels)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Trainer:
     """One rn_ft: float32 master copies of the last two conv stages and the dense head, Adam slots and the step counter on one
     GPU (include/roomnet_hip.h: fine-tuning).  Trains on features that stay resident in device memory: ``upload`` the
@@ -1282,6 +1393,30 @@ class Trainer:
             losses.ctypes.data, C.c_void_p(d_val_feats), C.c_void_p(d_val_labels), int(n_val), int(val_every), val_losses.ctypes.data,
             confusion.ctypes.data), "rn_ft_run_validated")
         return losses, points, val_losses, confusion
+
+    def run_views(self, engine: "Engine", views: "Views", d_labels: int, d_index: int, batch: int, steps: int, seed: int = 0,
+                  crop: bool = True, flip: bool = True, d_val_feats: Optional[int] = None, d_val_labels: Optional[int] = None,
+                  n_val: int = 0, val_every: Optional[int] = None):
+        """``steps`` Adam steps on fresh views (``rn_ft_run_views``): every step ``engine`` makes the minibatch's views of the resident
+        photographs ``views`` at the trainer's global step (``seed``, ``crop``, ``flip``: ``finetune.view_draw``) and runs its trunk
+        into a feature slot the trainer reads.  ``d_labels`` ``[n_items]`` and ``d_index`` ``[steps, batch]`` are device int32 (e.g.
+        of ``upload``).  ``engine``'s weights being this trainer's frozen trunk is the caller's contract.  Returns the losses, or with
+        ``val_every`` (and the cached validation features ``d_val_feats``, ``d_val_labels``, ``n_val``) what ``run_validated``
+        returns."""
+        flags = (RN_VIEW_CROP if crop else 0) | (RN_VIEW_FLIP if flip else 0)
+        losses = np.empty((max(int(steps), 1),), np.float32)
+        head = (self.handle, engine.handle, views.handle, C.c_void_p(d_labels), int(views.n_items), C.c_void_p(d_index), int(batch),
+                int(steps), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), flags, losses.ctypes.data)
+        if val_every is None:
+            _check(self.lib, self.lib.rn_ft_run_views(*head, None, None, 0, 0, None, None), "rn_ft_run_views")
+            return losses[:steps]
+        nc = self.graph.num_classes
+        points = self.val_points(steps, val_every)
+        val_losses = np.empty((points.size,), np.float32)
+        confusion = np.empty((points.size, nc, nc), np.int32)
+        _check(self.lib, self.lib.rn_ft_run_views(*head, C.c_void_p(d_val_feats), C.c_void_p(d_val_labels), int(n_val), int(val_every),
+                                                  val_losses.ctypes.data, confusion.ctypes.data), "rn_ft_run_views")
+        return losses[:steps], points, val_losses, confusion
 
     def best(self) -> Tuple[int, int, int]:
         """``(step, correct, n_val)`` of the best validation point so far on this trainer (``rn_ft_best``): the earliest point with

@@ -67,6 +67,13 @@
 // device ft_val_chunk_kernel adds each chunk to the point's confusion matrix and float64 cross-entropy sum, ft_val_close_kernel
 // writes the point's loss, counts the correct predictions and decides whether the point beats the best so far (strictly more
 // correct), and ft_val_snapshot_kernel then copies the parameter slab aside.  Nothing is synchronised until the run's one read-back.
+//
+// Fresh views (rn_ft_run_views; rn_views.h).  The same loop with a per-step feature provider (FtFeed): in front of step s the
+// handle's stream makes the minibatch's views at the trainer's global step (one launch, rn_imageops.hip) and runs the trunk's feature
+// pass into one of FT_VIEW_SLOTS = 2 feature slots the trainer owns, taken in turn; an event lets the trainer's stream run the unchanged
+// pass on that slot (index 0, 1, ...; labels gathered once per call in slot order by ft_gather_labels_kernel), and an event back keeps
+// the handle from overwriting a slot before the pass that reads it is through.  With two slots the trunk pass of step s + 1 overlaps
+// the trainer's step s (profiles/finetune_views_timing.json has the A/B against one slot); the bits do not depend on it.
 #include "rn_dropout.h"
 #include "rn_finetune7.h"
 #include "rn_internal.h"
@@ -87,6 +94,9 @@ constexpr int FT_W = 9 * LB_C * LB_C;
 constexpr int FT_WG_PAIRS = 9 * LB_C;  // (tap, cin) pairs of a weight gradient
 constexpr int FT_WG_GROUPS = 3;        // row groups (FT_WG_PAIRS * FT_WG_GROUPS <= FT_NT)
 constexpr int FT_MAX_VARS = 11 + 3 * RN_MAX_DENSE;   // depth 3: conv 7's three in front
+#ifndef FT_VIEW_SLOTS     // (measurement arm: csrc/build.sh RN_VARIANT_FLAGS=-DFT_VIEW_SLOTS=1 is rn_ft_run_views without the overlap)
+#define FT_VIEW_SLOTS 2   // feature slots of rn_ft_run_views: the trunk pass of step s + 1 overlaps the trainer's step s
+#endif
 
 struct FtItemArgs {
     const float* feats;              // [n_items, S7, S7, 16] (depth 3: unused, the item kernel reads x7ws)
@@ -644,6 +654,12 @@ __global__ __launch_bounds__(256) void ft_val_snapshot_kernel(const int32_t* fla
     if (q < quads) reinterpret_cast<f32x4*>(best)[q] = reinterpret_cast<const f32x4*>(P)[q];
 }
 
+// rn_ft_run_views: a call's labels in slot order, out[k] = labels[index[k]] (the index was range-checked on the host)
+__global__ __launch_bounds__(256) void ft_gather_labels_kernel(const int32_t* labels, const int32_t* index, int64_t count, int32_t* out) {
+    const int64_t k = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (k < count) out[k] = labels[index[k]];
+}
+
 struct FtVarHost {
     std::string name;
     int off = 0, count = 0;
@@ -685,6 +701,12 @@ struct rn_ft {
     FtBestDev best{};                              // ... and its host copy, read back behind every validated run
     void* d_val = nullptr;                         // the per-point tables of a run: [cap] ce | [cap] loss | [cap] flag | [cap, nc, nc]
     int val_cap = 0;
+    // training on fresh views (rn_ft_run_views): allocated when the first such run needs them
+    float* d_vfeat[FT_VIEW_SLOTS] = {};            // the feature slots [max_batch, side, side, C] the handle's trunk fills in turn
+    int32_t* d_iota = nullptr;                     // [max_batch] 0, 1, ...: the index of a pass over the slot
+    int32_t* d_glabels = nullptr;                  // [glabels_cap] a call's labels in slot order
+    size_t glabels_cap = 0;
+    hipEvent_t ev_feats[FT_VIEW_SLOTS] = {}, ev_read[FT_VIEW_SLOTS] = {};   // slot k is filled (handle's stream) / has been read (trainer's)
 };
 
 namespace {
@@ -1011,6 +1033,11 @@ extern "C" void rn_ft_destroy(rn_ft* ft) {
     for (void* p : ft->user) (void)hipFree(p);
     if (ft->d_losses) (void)hipFree(ft->d_losses);
     if (ft->d_val) (void)hipFree(ft->d_val);
+    if (ft->d_glabels) (void)hipFree(ft->d_glabels);
+    for (hipEvent_t e : ft->ev_feats)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ft->ev_read)
+        if (e) (void)hipEventDestroy(e);
     if (ft->stream) (void)hipStreamDestroy(ft->stream);
     (void)hipGetLastError();
     delete ft;
@@ -1233,10 +1260,21 @@ static int ft_enqueue_point(rn_ft* ft, const FtValidation& v, const FtValTables&
     return RN_OK;
 }
 
-// The step loop of rn_ft_run and rn_ft_run_validated (`who` in the messages): the checks, `steps` training passes enqueued back to
-// back, with `v` a validation point behind every step the schedule names, and one synchronisation at the end.
+// A per-step feature provider of the step loop (rn_ft_run_views).  Without one a step reads the resident d_feats through d_index.
+//   prepare  once, behind the loop's checks and before anything of the run is enqueued: what the provider allocates and gathers
+//   before   in front of step s at global step g: makes the step's features and names them in the pass's arguments (feats, labels,
+//            index, base); the trainer's stream must wait for them
+//   after    behind the pass of step s: the features have been read
+struct FtFeed {
+    std::function<int()> prepare;
+    std::function<int(int s, int64_t g, FtItemArgs& a)> before;
+    std::function<int(int s)> after;
+};
+
+// The step loop of rn_ft_run, rn_ft_run_validated and rn_ft_run_views (`who` in the messages): the checks, `steps` training passes
+// enqueued back to back, with `v` a validation point behind every step the schedule names, and one synchronisation at the end.
 static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const int32_t* d_labels, int64_t n_items, const int32_t* d_index,
-                       int batch, int steps, float* losses, const FtValidation* v) {
+                       int batch, int steps, float* losses, const FtValidation* v, const FtFeed* feed = nullptr) {
     if (batch < 1 || batch > ft->max_batch) {
         rn_set_error("%s: batch = %d out of range (1..%d)", who, batch, ft->max_batch);
         return RN_E_RANGE;
@@ -1281,6 +1319,7 @@ static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const i
     u.n = batch;
     const double b1 = ft->cfg.beta1, b2 = ft->cfg.beta2;
     const bool dropping = ft->drop.thr != 0;
+    if (feed && (rc = feed->prepare()) != RN_OK) return rc;
     if ((rc = ft->timer.start(ft->stream)) != RN_OK) return rc;
     if (v) RN_HIP(hipMemsetAsync(ft->d_val, 0, t.bytes, ft->stream));
     int point = 0;
@@ -1296,7 +1335,9 @@ static int ft_run_loop(rn_ft* ft, const char* who, const float* d_feats, const i
             a.drop.step_lo = static_cast<uint32_t>(gstep);
             a.drop.step_hi = static_cast<uint32_t>(gstep >> 32);
         }
+        if (feed && (rc = feed->before(s, ft->cfg.start_step + ft->steps_done, a)) != RN_OK) return rc;
         if ((rc = ft_enqueue_pass(ft, a, &u, batch)) != RN_OK) return rc;
+        if (feed && (rc = feed->after(s)) != RN_OK) return rc;
         ++ft->steps_done;
         if (v) {
             const int64_t g = ft->cfg.start_step + ft->steps_done;
@@ -1333,6 +1374,107 @@ extern "C" int rn_ft_run_validated(rn_ft* ft, const float* d_feats, const int32_
     }
     const FtValidation v{d_val_feats, d_val_labels, n_val, val_every, val_losses, val_confusion};
     return ft_run_loop(ft, "rn_ft_run_validated", d_feats, d_labels, n_items, d_index, batch, steps, losses, &v);
+}
+
+// what a run on fresh views needs beside the trainer's own memory (FtFeed::prepare: the loop's checks have passed and
+// ft_check_labels has drained the stream); a failed allocation leaves the trainer as it was.  Then the call's labels are gathered
+// in slot order on the trainer's stream, in front of the first step.
+static int ft_views_prepare(rn_ft* ft, const int32_t* d_labels, const int32_t* d_index, size_t count) {
+    int rc;
+    const size_t per = ft->depth == 3 ? static_cast<size_t>(ft->sd.S6) * ft->sd.S6 * LB_CIN7 : static_cast<size_t>(ft->sd.S7) * ft->sd.S7 * LB_C;
+    for (int k = 0; k < FT_VIEW_SLOTS; ++k) {
+        if (!ft->d_vfeat[k] && (rc = ft_zeroed(ft, static_cast<size_t>(ft->max_batch) * per, &ft->d_vfeat[k])) != RN_OK) return rc;
+        if (!ft->ev_feats[k]) RN_HIP(hipEventCreateWithFlags(&ft->ev_feats[k], hipEventDisableTiming));
+        if (!ft->ev_read[k]) RN_HIP(hipEventCreateWithFlags(&ft->ev_read[k], hipEventDisableTiming));
+    }
+    if (!ft->d_iota) {
+        std::vector<int32_t> iota(static_cast<size_t>(ft->max_batch));
+        for (size_t i = 0; i < iota.size(); ++i) iota[i] = static_cast<int32_t>(i);
+        if ((rc = ft_upload(ft, iota.data(), iota.size(), &ft->d_iota)) != RN_OK) return rc;
+    }
+    if (count > ft->glabels_cap) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, count * 4);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rn_set_error("rn_ft_run_views: hipMalloc(%zu bytes of labels) failed: %s", count * 4, hipGetErrorString(e));
+            return RN_E_NOMEM;
+        }
+        if (ft->d_glabels) (void)hipFree(ft->d_glabels);
+        ft->d_glabels = static_cast<int32_t*>(p);
+        ft->glabels_cap = count;
+    }
+    hipLaunchKernelGGL(ft_gather_labels_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, ft->stream, d_labels,
+                       d_index, static_cast<int64_t>(count), ft->d_glabels);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
+extern "C" int rn_ft_run_views(rn_ft* ft, rn_handle* h, const rn_views* v, const int32_t* d_labels, int64_t n_items, const int32_t* d_index,
+                               int batch, int steps, uint64_t view_seed, unsigned flags, float* losses, const float* d_val_feats,
+                               const int32_t* d_val_labels, int64_t n_val, int val_every, float* val_losses, int32_t* val_confusion) {
+    const char* who = "rn_ft_run_views";
+    if (!ft || !h || !v || !d_labels || !d_index || !losses) {
+        rn_set_error("%s: null argument", who);
+        return RN_E_INVALID;
+    }
+    const bool validated = d_val_feats || d_val_labels || n_val || val_every || val_losses || val_confusion;
+    if (validated && (!d_val_feats || !d_val_labels || !val_losses || !val_confusion)) {
+        rn_set_error("%s: validation takes all six of its arguments, or none", who);
+        return RN_E_INVALID;
+    }
+    if (h->device != ft->device) {
+        rn_set_error("%s: the handle is on device %d, the trainer on device %d", who, h->device, ft->device);
+        return RN_E_INVALID;
+    }
+    if (h->bnstats) {
+        rn_set_error("%s: the features are those of the inference graph; this handle normalises with batch moments (RN_FLAG_BATCH_STATS)", who);
+        return RN_E_STATE;
+    }
+    int side = 0, channels = 0;
+    int rc = rn_features_depth_shape(h, ft->depth, &side, &channels);
+    if (rc != RN_OK) return rc;
+    const int want_side = ft->depth == 3 ? ft->sd.S6 : ft->sd.S7, want_c = ft->depth == 3 ? LB_CIN7 : LB_C;
+    if (side != want_side || channels != want_c) {
+        rn_set_error("%s: the handle's depth-%d feature is %d x %d x %d, the trainer's %d x %d x %d", who, ft->depth, side, side, channels,
+                     want_side, want_side, want_c);
+        return RN_E_INVALID;
+    }
+    if (batch > h->max_batch) {
+        rn_set_error("%s: batch = %d exceeds the handle's max_batch %d", who, batch, h->max_batch);
+        return RN_E_RANGE;
+    }
+    if (n_items != v->n_items) {
+        rn_set_error("%s: n_items = %lld, the views hold %lld photographs", who, static_cast<long long>(n_items),
+                     static_cast<long long>(v->n_items));
+        return RN_E_INVALID;
+    }
+    // (n = 1 and step 0 here: the loop checks the batch, and the trainer's global step is never negative)
+    if ((rc = rn_views_check(who, h, v, d_index, 1, 0, flags, h->d_in_u8)) != RN_OK) return rc;
+    FtFeed feed;
+    feed.prepare = [&]() { return ft_views_prepare(ft, d_labels, d_index, static_cast<size_t>(steps) * batch); };
+    feed.before = [&](int s, int64_t g, FtItemArgs& a) -> int {
+        int rc2;
+        const int k = s % FT_VIEW_SLOTS;
+        // the pass that read slot k last (step s - FT_VIEW_SLOTS of this call) must be through with it
+        if (s >= FT_VIEW_SLOTS) RN_HIP(hipStreamWaitEvent(h->stream, ft->ev_read[k], 0));
+        if ((rc2 = rn_views_enqueue(h, v, d_index, static_cast<int64_t>(s) * batch, batch, view_seed, g, flags, h->d_in_u8)) != RN_OK) return rc2;
+        if ((rc2 = rn_features_depth_u8_device(h, ft->depth, h->d_in_u8, batch, ft->d_vfeat[k])) != RN_OK) return rc2;
+        RN_HIP(hipEventRecord(ft->ev_feats[k], h->stream));
+        RN_HIP(hipStreamWaitEvent(ft->stream, ft->ev_feats[k], 0));
+        a.feats = ft->d_vfeat[k];
+        a.labels = ft->d_glabels + static_cast<int64_t>(s) * batch;
+        a.index = ft->d_iota;
+        a.base = 0;
+        return RN_OK;
+    };
+    feed.after = [&](int s) -> int {
+        RN_HIP(hipEventRecord(ft->ev_read[s % FT_VIEW_SLOTS], ft->stream));
+        return RN_OK;
+    };
+    if (!validated) return ft_run_loop(ft, who, nullptr, d_labels, n_items, d_index, batch, steps, losses, nullptr, &feed);
+    const FtValidation val{d_val_feats, d_val_labels, n_val, val_every, val_losses, val_confusion};
+    return ft_run_loop(ft, who, nullptr, d_labels, n_items, d_index, batch, steps, losses, &val, &feed);
 }
 
 extern "C" int rn_ft_val_points(const rn_ft* ft, int steps, int val_every, int64_t* point_steps, int cap) {

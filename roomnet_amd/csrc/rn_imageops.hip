@@ -9,11 +9,19 @@
 // special case that an exact 2x2 down-scale is a 2x2 box average.  HBM-bound byte work: one thread
 // per destination pixel, 12 source bytes in, 3 bytes out; no LDS, no MFMA.  A batch of images is ONE launch
 // (resize_batch_u8_kernel: blockIdx.z = image, a device table of crop windows); profiles/r6_imageops.*.
+//
+// Training views (rn_views.h: the draw and why no draw reads outside the photograph; rn_views_*): views_batch_u8_kernel is the same
+// launch over a table that lives for a whole training run.  Slot b looks up item index[base + b], draws its own window offset and
+// flips from the trainers' Philox (rn_dropout.h, shared), runs the same per-pixel arithmetic (resize_pixel_to) on the window at
+// that offset and stores the pixel at the flipped address: no per-step table, no per-step upload.
 #include "rn_internal.h"
+#include "rn_views.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <vector>
 
 namespace {
 
@@ -42,8 +50,8 @@ __device__ __forceinline__ void lin_coeff(int d, double scale, int ssize, bool c
     s = si; c0 = a0; c1 = a1;
 }
 
-__device__ __forceinline__ void resize_pixel(const ResizeArgs& a, int x, int y) {
-    uint8_t* o = a.dst + (static_cast<int64_t>(y) * a.dst_w + x) * 3;
+// destination pixel (x, y) of the resize, written to o[0 .. 3)
+__device__ __forceinline__ void resize_pixel_to(const ResizeArgs& a, int x, int y, uint8_t* o) {
     if (a.mode == 1) {
         const uint8_t* p = a.src + static_cast<int64_t>(y) * a.src_row_bytes + x * 3;
         o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
@@ -74,6 +82,10 @@ __device__ __forceinline__ void resize_pixel(const ResizeArgs& a, int x, int y) 
     }
 }
 
+__device__ __forceinline__ void resize_pixel(const ResizeArgs& a, int x, int y) {
+    resize_pixel_to(a, x, y, a.dst + (static_cast<int64_t>(y) * a.dst_w + x) * 3);
+}
+
 __global__ __launch_bounds__(256) void resize_linear_u8_kernel(const ResizeArgs a) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -100,6 +112,32 @@ __global__ __launch_bounds__(256) void resize_batch_u8_kernel(const rn_resize_it
     a.scale_y = it.scale_y;
     a.mode = it.mode;
     resize_pixel(a, x, y);
+}
+
+// The views of a minibatch in one launch (blockIdx.z = slot).  An index outside the table leaves its slot unwritten (the host
+// entry points that can check the index do; this keeps the others inside the table).
+__global__ __launch_bounds__(256) void views_batch_u8_kernel(const rn_view_item* items, int64_t n_items, const int32_t* index, int64_t base,
+                                                             const RnViewKey key, uint8_t* dst_base, int S) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= S || y >= S) return;
+    const int64_t item = index[base + blockIdx.z];
+    if (item < 0 || item >= n_items) return;
+    const rn_view_item it = items[item];
+    int32_t offset, fliplr, flipud;
+    rn_view_draw_slot(key, blockIdx.z, it.range, it.centre, &offset, &fliplr, &flipud);
+    ResizeArgs a;
+    a.src = it.win.src + (it.axis ? static_cast<int64_t>(offset) * it.win.src_row_bytes : static_cast<int64_t>(offset) * 3);
+    a.dst = dst_base + static_cast<int64_t>(blockIdx.z) * S * S * 3;
+    a.src_h = it.win.src_h;
+    a.src_w = it.win.src_w;
+    a.src_row_bytes = it.win.src_row_bytes;
+    a.dst_h = a.dst_w = S;
+    a.scale_x = it.win.scale_x;
+    a.scale_y = it.win.scale_y;
+    a.mode = it.win.mode;
+    const int ox = fliplr ? S - 1 - x : x, oy = flipud ? S - 1 - y : y;
+    resize_pixel_to(a, x, y, a.dst + (static_cast<int64_t>(oy) * S + ox) * 3);
 }
 
 }  // namespace
@@ -150,4 +188,129 @@ int rn_launch_resize_u8(hipStream_t s, const uint8_t* d_src, int src_h, int src_
     hipLaunchKernelGGL(resize_linear_u8_kernel, grid, dim3(256), 0, s, a);
     RN_CHECK_LAUNCH();
     return RN_OK;
+}
+
+// ---- training views (rn_views.h)
+// the window geometry of a height x width photograph: side, range, axis and the centre offset
+static void view_geometry(int height, int width, int* side, int* range, int* axis, int* centre) {
+    int x0, y0;
+    rn_center_crop_window(height, width, &x0, &y0, side);
+    *range = std::max(height, width) - *side;
+    *axis = height < width ? 0 : 1;
+    *centre = *axis ? y0 : x0;
+}
+
+extern "C" int rn_view_draw(uint64_t seed, int64_t step, int slot, int height, int width, unsigned flags, rn_view* out) {
+    if (!out || height < 1 || width < 1 || (flags & ~(RN_VIEW_CROP | RN_VIEW_FLIP))) {
+        rn_set_error("rn_view_draw: bad argument (image %dx%d, flags %u)", width, height, flags);
+        return RN_E_INVALID;
+    }
+    if (step < 0 || slot < 0) {
+        rn_set_error("rn_view_draw: step = %lld, slot = %d", static_cast<long long>(step), slot);
+        return RN_E_RANGE;
+    }
+    int side, range, axis, centre, offset, fliplr, flipud;
+    view_geometry(height, width, &side, &range, &axis, &centre);
+    rn_view_draw_slot(rn_view_key(seed, step, flags), static_cast<uint32_t>(slot), range, centre, &offset, &fliplr, &flipud);
+    out->x0 = axis ? 0 : offset;
+    out->y0 = axis ? offset : 0;
+    out->side = side;
+    out->fliplr = fliplr;
+    out->flipud = flipud;
+    return RN_OK;
+}
+
+extern "C" int rn_views_create(rn_handle* h, const rn_view_source* srcs, int64_t n_items, rn_views** out) {
+    if (out) *out = nullptr;
+    if (!h || !srcs || !out || n_items < 1 || n_items > std::numeric_limits<int32_t>::max()) {
+        rn_set_error("rn_views_create: bad argument (%lld photographs)", static_cast<long long>(n_items));
+        return RN_E_INVALID;
+    }
+    std::vector<rn_view_item> items(static_cast<size_t>(n_items));
+    for (int64_t i = 0; i < n_items; ++i) {
+        const rn_view_source& s = srcs[i];
+        if (!s.d_bgr || s.height < 1 || s.width < 1) {
+            rn_set_error("rn_views_create: photograph %lld is empty", static_cast<long long>(i));
+            return RN_E_INVALID;
+        }
+        rn_view_item& it = items[static_cast<size_t>(i)];
+        int side;
+        view_geometry(s.height, s.width, &side, &it.range, &it.axis, &it.centre);
+        it.pad = 0;
+        rn_resize_item_fill(&it.win, s.d_bgr, side, side, static_cast<int64_t>(s.width) * 3, h->im_side);
+    }
+    DeviceGuard guard(h->device);
+    void* p = nullptr;
+    const size_t bytes = items.size() * sizeof(rn_view_item);
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rn_set_error("rn_views_create: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return RN_E_NOMEM;
+    }
+    if ((e = hipMemcpy(p, items.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        rn_set_error("rn_views_create: hipMemcpy failed: %s", hipGetErrorString(e));
+        return RN_E_HIP;
+    }
+    rn_views* v = new rn_views();
+    v->device = h->device;
+    v->im_side = h->im_side;
+    v->n_items = n_items;
+    v->d_items = static_cast<rn_view_item*>(p);
+    *out = v;
+    return RN_OK;
+}
+
+extern "C" void rn_views_destroy(rn_views* v) {
+    if (!v) return;
+    DeviceGuard guard(v->device);
+    (void)hipDeviceSynchronize();      // (a launch that still reads the table)
+    (void)hipFree(v->d_items);
+    (void)hipGetLastError();
+    delete v;
+}
+
+int rn_views_check(const char* who, const rn_handle* h, const rn_views* v, const void* d_index, int n, int64_t step, unsigned flags,
+                   const void* d_dst) {
+    if (!v || (flags & ~(RN_VIEW_CROP | RN_VIEW_FLIP))) {
+        rn_set_error("%s: bad argument (flags %u)", who, flags);
+        return RN_E_INVALID;
+    }
+    int rc = rn_check_batch(who, h, d_index && d_dst ? d_index : nullptr, n);
+    if (rc != RN_OK) return rc;
+    if (v->device != h->device || v->im_side != h->im_side) {
+        rn_set_error("%s: the views were created on device %d for side %d, the handle is on device %d with side %d", who, v->device,
+                     v->im_side, h->device, h->im_side);
+        return RN_E_INVALID;
+    }
+    if (step < 0) {
+        rn_set_error("%s: step = %lld", who, static_cast<long long>(step));
+        return RN_E_RANGE;
+    }
+    return RN_OK;
+}
+
+int rn_views_enqueue(rn_handle* h, const rn_views* v, const int32_t* d_index, int64_t base, int n, uint64_t seed, int64_t step,
+                     unsigned flags, uint8_t* d_dst) {
+    const int S = h->im_side;
+    dim3 grid((S + 63) / 64, (S + 3) / 4, n);
+    hipLaunchKernelGGL(views_batch_u8_kernel, grid, dim3(256), 0, h->stream, v->d_items, v->n_items, d_index, base,
+                       rn_view_key(seed, step, flags), d_dst, S);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
+
+extern "C" int rn_views_batch_device(rn_handle* h, const rn_views* v, const int32_t* d_index, int64_t base, int n, uint64_t seed,
+                                     int64_t step, unsigned flags, uint8_t* d_dst) {
+    int rc = rn_views_check("rn_views_batch_device", h, v, d_index, n, step, flags, d_dst);
+    if (rc != RN_OK) return rc;
+    if (base < 0) {
+        rn_set_error("rn_views_batch_device: base = %lld", static_cast<long long>(base));
+        return RN_E_RANGE;
+    }
+    DeviceGuard guard(h->device);
+    (void)hipGetLastError();
+    return rn_views_enqueue(h, v, d_index, base, n, seed, step, flags, d_dst);
 }

@@ -140,6 +140,24 @@ struct rn_resize_item {
     int mode;
 };
 
+// one photograph of a training set (rn_views_create; rn_views.h): what does not change from step to step.  `win` is the square
+// window at offset 0 -- the whole short axis, `side` along the long one -- with the scales and the mode rn_resize_item_fill forms on
+// the host: they depend on the side alone, not on the offset a step draws.
+struct rn_view_item {
+    rn_resize_item win;
+    int32_t range;               // max(height, width) - side: the offsets a draw can take are [0, range) (0 when range is 0)
+    int32_t axis;                // 0: the window slides along the columns (height < width); 1: along the rows
+    int32_t centre;              // the offset of rn_center_crop_window, what a launch without RN_VIEW_CROP takes
+    int32_t pad;
+};
+
+struct rn_views {
+    int device = 0;
+    int im_side = 0;             // the side the scales were formed for: the creating handle's
+    int64_t n_items = 0;
+    rn_view_item* d_items = nullptr;   // [n_items]
+};
+
 struct rn_handle {
     int device = 0;
     int dtype = RN_DTYPE_F32;
@@ -226,6 +244,12 @@ void rn_resize_item_fill(rn_resize_item* it, const uint8_t* d_src, int src_h, in
 int rn_launch_resize_batch_u8(hipStream_t s, const rn_resize_item* d_items, int n, uint8_t* d_dst_base, int S);
 int rn_launch_resize_u8(hipStream_t s, const uint8_t* d_src, int src_h, int src_w, int64_t src_row_bytes, uint8_t* d_dst,
                         int dst_h, int dst_w);
+// the body of rn_views_batch_device behind its checks (rn_ft_run_views calls it once per step): one launch on the handle's stream
+int rn_views_enqueue(rn_handle* h, const rn_views* v, const int32_t* d_index, int64_t base, int n, uint64_t seed, int64_t step,
+                     unsigned flags, uint8_t* d_dst);
+// its checks: null arguments, a table of another device or side (RN_E_INVALID), n outside [1, max_batch] or step < 0 (RN_E_RANGE)
+int rn_views_check(const char* who, const rn_handle* h, const rn_views* v, const void* d_index, int n, int64_t step, unsigned flags,
+                   const void* d_dst);
 int rn_launch_head(hipStream_t s, const void* flat, int flat_dtype, int n, const HeadArgs& a, float* probs,
                    int64_t* ids);
 bool rn_head_takes_flatten(int flat_len);      // head_kernel keeps the flatten in LDS: up to 4096 values (im_side <= 694)

@@ -169,6 +169,62 @@ def dropout_sites(graph: Graph, depth: int = 2):
     return sites
 
 
+# ---- training views (csrc/rn_views.h, include/roomnet_hip.h: fine-tuning on fresh random views)
+VIEW_SITE = 254                          # a site no dropout site can take: view draws and dropout masks never share a counter
+VIEW_CROP, VIEW_FLIP = 1, 2              # RN_VIEW_CROP, RN_VIEW_FLIP
+
+
+def view_flags(crop=True, flip=True) -> int:
+    return (VIEW_CROP if crop else 0) | (VIEW_FLIP if flip else 0)
+
+
+def view_counter(step, slot):
+    """The Philox counter of the view draw of minibatch slot ``slot`` at global step ``step``:
+    ``(0, slot, step & 0xffffffff, VIEW_SITE | (step >> 32) << 8)``."""
+    step = int(step)
+    return (0, int(slot), step & 0xFFFFFFFF, (VIEW_SITE | ((step >> 32) << 8)) & 0xFFFFFFFF)
+
+
+def center_crop_window(height, width):
+    """``(x0, y0, side)`` of the centred square window of network.py:137-146 (``rn_center_crop_window``)."""
+    height, width = int(height), int(width)
+    if width > height:
+        return (width - height) // 2, 0, height
+    return 0, abs((width - height) // 2), width
+
+
+def view_draw(seed, step, slot, height, width, crop=True, flip=True):
+    """The view the feeder's augmentation gives minibatch slot ``slot`` at global step ``step`` of a ``height x width`` photograph
+    (``rn_view_draw``): ``{"x0", "y0", "side", "fliplr", "flipud"}``.  ``crop``: a random square window slid along the long axis
+    (generator.py:52-67), offset ``word0 * range >> 32`` in ``[0, range)`` with ``range = max(h, w) - min(h, w)`` (0: the whole
+    image); otherwise the centre window.  ``flip``: each mirror with probability 1/2 (generator.py:85-92), ``word1 >> 31`` and
+    ``word2 >> 31``.  The words are ``philox4x32(view_counter(step, slot), (seed & 0xffffffff, seed >> 32))``; NumPy's own stream
+    is not reproduced, the distribution and the sampling rules are."""
+    seed, step, slot, height, width = int(seed), int(step), int(slot), int(height), int(width)
+    if seed < 0 or seed >> 64 or step < 0 or slot < 0 or height < 1 or width < 1:
+        raise ValueError("view_draw: seed %d, step %d, slot %d, image %dx%d" % (seed, step, slot, width, height))
+    w = [int(x) for x in philox4x32(view_counter(step, slot), (seed & 0xFFFFFFFF, seed >> 32))]
+    side, rng = min(height, width), abs(height - width)
+    x0, y0, _ = center_crop_window(height, width)
+    if crop:
+        offset = (w[0] * rng) >> 32
+        x0, y0 = (offset, 0) if height < width else (0, offset)
+    return {"x0": x0, "y0": y0, "side": side, "fliplr": (w[1] >> 31) if flip else 0, "flipud": (w[2] >> 31) if flip else 0}
+
+
+def make_view(im, draw, S) -> np.ndarray:
+    """The ``[S, S, 3]`` view ``draw`` (of ``view_draw``) takes of the BGR uint8 photograph ``im``:
+    ``flipud(fliplr(resize(window, (S, S))))``, the flips behind the resize as in the reference's ``preprocess_set``."""
+    from .imageops import resize_linear_u8
+    x0, y0, side = draw["x0"], draw["y0"], draw["side"]
+    out = resize_linear_u8(np.asarray(im)[y0:y0 + side, x0:x0 + side], int(S), int(S))
+    if draw["fliplr"]:
+        out = out[:, ::-1]
+    if draw["flipud"]:
+        out = out[::-1]
+    return np.ascontiguousarray(out)
+
+
 def dropout_keep(seed, step, slot, site, count, rate) -> np.ndarray:
     """The keep mask (bool ``[count]``) of elements ``0 .. count - 1`` of ``site`` in minibatch slot ``slot`` at global step
     ``step``: key ``(seed & 0xffffffff, seed >> 32)``, counter ``(e >> 2, slot, step & 0xffffffff, site | (step >> 32) << 8)``,

@@ -411,7 +411,8 @@ def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=
 
 
 def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_fpath=None, extract_batch=64, depth=2,
-                        gpu_decode=False, dropout_rate=None, val_every=None, keep="last", stats_fpath=None, gpu_orient=False):
+                        gpu_decode=False, dropout_rate=None, val_every=None, keep="last", stats_fpath=None, gpu_orient=False,
+                        views=False, random_crop=True, flip=True):
     """``RoomNet.fine_tune`` on the images of a list file in the reference's ``path label`` format (``train_list.txt``, read as
     infer.py:31-38 reads it): the files are decoded as ``classify_im_dir`` decodes them, their features are extracted batch by
     batch (``RoomNet.extract_features``; unreadable files are reported and skipped), then the model is trained on the cached
@@ -423,7 +424,14 @@ def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_f
     ``val_every``, ``keep``: passed to ``fine_tune`` (validation on the GPU every ``val_every`` steps; ``keep="best"`` keeps the best
     point's variables).  ``stats_fpath``: every point's ``step``, ``accuracy``, ``precisions``, ``recalls`` and ``f-scores`` are
     appended to that JSON file as train.py:129-155 keeps ``all_train_stats.json`` (``metrics.append_stats``), so the reference's
-    ``plotter.py`` reads it as it is; needs ``val_every``."""
+    ``plotter.py`` reads it as it is; needs ``val_every``.
+    ``views=True``: the reference's training regime (train.py:117-118) -- the training list is decoded on the pool and kept
+    resident on the GPU as whole photographs, and every step trains on fresh random views of them (``RoomNet.fine_tune_views``;
+    ``random_crop``, ``flip``: its arguments); the validation list still goes through the cached centre-crop features.  Not together
+    with ``gpu_decode``: keeping the GPU decoder's output resident is a later step (``ValueError``)."""
+    if views and gpu_decode:
+        raise ValueError("fine_tune_from_list: views=True keeps host-decoded photographs resident and does not take gpu_decode=True "
+                         "yet (keeping the GPU decoder's output resident is a later step)")
     if stats_fpath is not None and val_every is None:
         raise ValueError("fine_tune_from_list: stats_fpath records validation points: pass val_every= (and val_list_fpath=)")
     if gpu_orient and not gpu_decode:
@@ -461,10 +469,29 @@ def fine_tune_from_list(nn, list_fpath, steps, batch_size=45, seed=0, val_list_f
             raise ValueError("fine_tune_from_list: no readable image in %r" % path)
         return np.concatenate(feats, 0), np.asarray(kept, np.int32)
 
-    feats, labels = features_of(list_fpath)
-    val = features_of(val_list_fpath) if val_list_fpath else None
-    out = nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val, depth=depth, dropout_rate=dropout_rate,
-                       val_every=val_every, keep=keep)
+    def photographs_of(path):
+        fpaths, labels, _n = read_fpaths(path)
+        ims, kept = [], []
+        for i, fpath, im in _decode_files(fpaths, extract_batch):
+            if im is None or im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                print(fpath, '---> unreadable image, skipped')
+                continue
+            ims.append(im)
+            kept.append(labels[i])
+        if not ims:
+            raise ValueError("fine_tune_from_list: no readable image in %r" % path)
+        return ims, np.asarray(kept, np.int32)
+
+    if views:
+        ims, labels = photographs_of(list_fpath)
+        val = features_of(val_list_fpath) if val_list_fpath else None
+        out = nn.fine_tune_views(ims, labels, steps, batch_size=batch_size, seed=seed, depth=depth, random_crop=random_crop, flip=flip,
+                                 val=val, val_every=val_every, keep=keep, dropout_rate=dropout_rate)
+    else:
+        feats, labels = features_of(list_fpath)
+        val = features_of(val_list_fpath) if val_list_fpath else None
+        out = nn.fine_tune(feats, labels, steps, batch_size=batch_size, seed=seed, val=val, depth=depth, dropout_rate=dropout_rate,
+                           val_every=val_every, keep=keep)
     if stats_fpath is not None:
         from . import metrics
         metrics.append_stats(stats_fpath, out["val_history"])

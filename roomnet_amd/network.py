@@ -758,6 +758,34 @@ class RoomNet:
                 raise ValueError("extract_features takes uint8 images (or integral values in [0, 255]), got %s" % im.dtype)
         return self._engine().features_u8(im, depth=depth)
 
+    def _fine_tune_checked(self, who, keep, val_every, val, dropout_rate):
+        """The argument rules ``fine_tune`` and ``fine_tune_views`` share, before a device is touched; returns the dropout rate as a
+        float (or None)."""
+        if keep not in ("last", "best"):
+            raise ValueError("%s: keep = %r is neither 'last' nor 'best'" % (who, keep))
+        if val_every is not None:
+            if isinstance(val_every, bool) or not isinstance(val_every, (int, np.integer)) or val_every < 1:
+                raise ValueError("%s: val_every = %r is not a positive number of steps" % (who, val_every))
+            if val is None:
+                raise ValueError("%s: val_every = %d needs a validation set: pass val=(features, labels)" % (who, val_every))
+        elif keep == "best":
+            raise ValueError("%s: keep='best' needs validation points: pass val= and val_every=" % who)
+        if dropout_rate is None:
+            if self.dropout_enabled:
+                raise ValueError("%s: dropout on the GPU path covers the sites at or behind the cached feature only and is "
+                                 "asked for explicitly: pass dropout_rate= (e.g. dropout_rate=nn.dropout_rate), or construct "
+                                 "with dropout_enabled=False" % who)
+        else:
+            try:
+                dropout_rate = float(dropout_rate)
+            except (TypeError, ValueError):
+                raise ValueError("%s: dropout_rate = %r is not a number" % (who, dropout_rate)) from None
+            if not (0.0 <= dropout_rate < 1.0):
+                raise ValueError("%s: dropout_rate = %r outside [0, 1)" % (who, dropout_rate))
+        if not self.sess:
+            raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
+        return dropout_rate
+
     def fine_tune(self, features, labels, steps, batch_size=45, seed=0, val=None, depth=None, dropout_rate=None, val_every=None,
                   keep="last"):
         """Train stages 8 and 9 and the dense head on cached features, on the GPU (``rn_ft_*``; not the reference's whole-network
@@ -786,31 +814,8 @@ class RoomNet:
         label), and ``"best_step"``: the earliest point with the most correct predictions; ``"val"`` is the last point's.
         ``keep="best"`` writes that point's variables back instead of the last step's (``self.step`` advances by ``steps`` either
         way); any other ``keep`` than ``"last"`` or ``"best"`` raises ``ValueError``."""
-        from . import finetune, metrics
-        from ._capi import RN_FT_BEST, RN_FT_PARAM, Trainer
-        if keep not in ("last", "best"):
-            raise ValueError("fine_tune: keep = %r is neither 'last' nor 'best'" % (keep,))
-        if val_every is not None:
-            if isinstance(val_every, bool) or not isinstance(val_every, (int, np.integer)) or val_every < 1:
-                raise ValueError("fine_tune: val_every = %r is not a positive number of steps" % (val_every,))
-            if val is None:
-                raise ValueError("fine_tune: val_every = %d needs a validation set: pass val=(features, labels)" % val_every)
-        elif keep == "best":
-            raise ValueError("fine_tune: keep='best' needs validation points: pass val= and val_every=")
-        if dropout_rate is None:
-            if self.dropout_enabled:
-                raise ValueError("fine_tune: dropout on the GPU path covers the sites at or behind the cached feature only and is "
-                                 "asked for explicitly: pass dropout_rate= (e.g. dropout_rate=nn.dropout_rate), or construct "
-                                 "with dropout_enabled=False")
-        else:
-            try:
-                dropout_rate = float(dropout_rate)
-            except (TypeError, ValueError):
-                raise ValueError("fine_tune: dropout_rate = %r is not a number" % (dropout_rate,)) from None
-            if not (0.0 <= dropout_rate < 1.0):
-                raise ValueError("fine_tune: dropout_rate = %r outside [0, 1)" % (dropout_rate,))
-        if not self.sess:
-            raise RuntimeError("Attempted to use a closed Session. (call init() or load() first)")
+        from . import finetune
+        dropout_rate = self._fine_tune_checked("fine_tune", keep, val_every, val, dropout_rate)
         feats = np.ascontiguousarray(features, np.float32)
         labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
         if depth is not None:
@@ -830,6 +835,22 @@ class RoomNet:
         if steps < 1:
             raise ValueError("fine_tune: steps = %d" % steps)
         index = finetune.epoch_indices(feats.shape[0], batch_size, steps, seed=[int(seed), int(self.step)])
+        def run(tr):
+            return tr.run_host(feats, labels, index)
+
+        def run_validated(tr, d_vf, d_vl, n_val):
+            d = [tr.upload(feats), tr.upload(labels), tr.upload(index)]
+            return tr.run_validated(d[0], d[1], feats.shape[0], d[2], index.shape[1], index.shape[0], d_vf, d_vl, n_val, val_every)
+
+        return self._fine_tune_run("fine_tune", depth, index, dropout_rate, seed, val, val_every, keep, run, run_validated)
+
+    def _fine_tune_run(self, who, depth, index, dropout_rate, seed, val, val_every, keep, run, run_validated):
+        """What ``fine_tune`` and ``fine_tune_views`` share behind their own checks: the trainer, the run -- ``run(tr)`` gives the
+        losses, ``run_validated(tr, d_val_feats, d_val_labels, n_val)`` what ``Trainer.run_validated`` returns --, the validation
+        record, the write-back and the result."""
+        from . import finetune, metrics
+        from ._capi import RN_FT_BEST, RN_FT_PARAM, Trainer
+        shape = finetune.feature_shape(self.graph, depth)
         tr = Trainer(self.graph, self.sess.variables, device=self.device, max_batch=max(index.shape[1], min(self.max_batch, 256)),
                      learn_rate=self.learn_rate, num_steps=self.num_steps, start_step=self.step,
                      l2_coeff=self.l2_regularizer_coeff, depth=depth, dropout_rate=dropout_rate or 0.0,
@@ -841,11 +862,9 @@ class RoomNet:
                 vf = np.ascontiguousarray(val[0], np.float32)
                 vl = np.ascontiguousarray(val[1], np.int32).reshape(-1)
                 if vf.ndim != 4 or vf.shape[1:] != shape or vf.shape[0] != vl.shape[0] or vf.shape[0] < 1:
-                    raise ValueError("fine_tune: validation features %s and labels %s do not form [N, %d, %d, %d] and [N] (depth %d)"
-                                     % (vf.shape, vl.shape, shape[0], shape[1], shape[2], depth))
-                d = [tr.upload(feats), tr.upload(labels), tr.upload(index), tr.upload(vf), tr.upload(vl)]
-                losses, points, val_losses, confusion = tr.run_validated(d[0], d[1], feats.shape[0], d[2], index.shape[1],
-                                                                         index.shape[0], d[3], d[4], vf.shape[0], val_every)
+                    raise ValueError("%s: validation features %s and labels %s do not form [N, %d, %d, %d] and [N] (depth %d)"
+                                     % (who, vf.shape, vl.shape, shape[0], shape[1], shape[2], depth))
+                losses, points, val_losses, confusion = run_validated(tr, tr.upload(vf), tr.upload(vl), vf.shape[0])
                 history = []
                 for g, vloss, cm in zip(points, val_losses, confusion):
                     entry = {"step": int(g), "loss": float(vloss), "confusion": cm.copy()}
@@ -854,7 +873,7 @@ class RoomNet:
                 extra = {"val_history": history, "best_step": tr.best()[0]}
                 out_val = (history[-1]["loss"], history[-1]["accuracy"])
             else:
-                losses = tr.run_host(feats, labels, index)
+                losses = run(tr)
                 if val is not None:
                     vf, vl = val
                     vl = np.ascontiguousarray(vl, np.int32).reshape(-1)
@@ -870,6 +889,62 @@ class RoomNet:
                "learn_rate": finetune.learn_rate_at(step, self.learn_rate, self.num_steps)}
         out.update(extra)
         return out
+
+    def fine_tune_views(self, images, labels, steps, batch_size=45, seed=0, depth=2, random_crop=True, flip=True, val=None,
+                        val_every=None, keep="last", dropout_rate=None):
+        """``fine_tune`` on fresh random views of whole photographs instead of cached features, the reference's training regime
+        (train.py:117-118, a feeder with ``random_crop=True, preprocess=True``): every sample of every step is a fresh random square
+        window slid along the photograph's long axis, resized to the network's side and mirrored left-right and upside-down with
+        probability 1/2 each (``finetune.view_draw``, ``finetune.make_view``: the draws come from the trainers' Philox generator,
+        keyed by ``seed``, the global step and the minibatch slot; NumPy's own stream is not reproduced).  ``images``: a list of BGR
+        uint8 arrays of any size, uploaded once into one device allocation (a failed allocation raises and says how many bytes the
+        set needs); every step the GPU makes the minibatch's views, runs the frozen trunk on them and trains on those features
+        (``rn_ft_run_views``).  ``depth``: 2 trains stages 8-9 and the head, 3 the whole last conv block.  ``random_crop=False`` takes
+        the centre window, ``flip=False`` never mirrors.  ``val``: ``(features, labels)`` as ``fine_tune`` takes it -- cached
+        centre-crop features of ``extract_features(..., depth=depth)``: the reference validates on ``random_crop=False,
+        preprocess=False``.  Everything else -- ``val_every``, ``keep``, ``dropout_rate``, the result and the write-back -- is
+        ``fine_tune``'s."""
+        from . import finetune
+        dropout_rate = self._fine_tune_checked("fine_tune_views", keep, val_every, val, dropout_rate)
+        depth = finetune._checked_depth(depth)
+        images = list(images)
+        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if not images or len(images) != labels.shape[0]:
+            raise ValueError("fine_tune_views: %d images and labels %s do not form N photographs and [N]" % (len(images), labels.shape))
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("fine_tune_views: steps = %d" % steps)
+        index = finetune.epoch_indices(len(images), batch_size, steps, seed=[int(seed), int(self.step)])
+        if index.shape[1] > self.max_batch:
+            raise ValueError("fine_tune_views: a minibatch of %d views exceeds max_batch=%d (the trunk runs on every minibatch; "
+                             "construct with a larger max_batch)" % (index.shape[1], self.max_batch))
+        eng = self._engine()
+        views = eng.views_create(images)
+
+        def run(tr, **validation):
+            return tr.run_views(eng, views, tr.upload(labels), tr.upload(index), index.shape[1], index.shape[0], seed=int(seed),
+                                crop=bool(random_crop), flip=bool(flip), **validation)
+
+        def run_validated(tr, d_vf, d_vl, n_val):
+            return run(tr, d_val_feats=d_vf, d_val_labels=d_vl, n_val=n_val, val_every=val_every)
+
+        try:
+            return self._fine_tune_run("fine_tune_views", depth, index, dropout_rate, seed, val, val_every, keep, run, run_validated)
+        finally:
+            views.close()
+
+    def training_views(self, images, step, seed=0, index=None, random_crop=True, flip=True):
+        """The ``[n, S, S, 3]`` uint8 views the GPU makes of the BGR photographs ``images`` at global step ``step``
+        (``rn_views_batch_device``): slot ``b`` is the view of ``images[index[b]]`` (``index=None``: every image in order), what
+        ``fine_tune_views`` with the same ``seed`` feeds the trunk in that slot at that step.  At most ``max_batch`` slots."""
+        images = list(images)
+        index = np.arange(len(images), dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32).reshape(-1)
+        eng = self._engine()
+        views = eng.views_create(images)
+        try:
+            return eng.views_batch(views, index, int(step), seed=int(seed), crop=bool(random_crop), flip=bool(flip))
+        finally:
+            views.close()
 
     def train_step(self, x_in, y):
         raise NotImplementedError("training (network.py:158-170) is out of scope of the MI355X inference path")

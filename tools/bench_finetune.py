@@ -16,7 +16,14 @@ build, a parent-commit build for instance -- and states whether this build's dro
 --val-every K measures what a validation point costs at batch 45 / 224, both depths and validation sets of 256 and 2048 items: inside
 the run (rn_ft_run_validated) and the way there was before, K steps of rn_ft_run and an rn_ft_eval from the host in turn.
 
+--views measures training on fresh random views (rn_ft_run_views) at batch 45 / 224 on a bf16 handle, depth 2 and depth 3, in one
+session: the cached-feature run (rn_ft_run) and the views run alternate, --runs runs each after a warm-up round; and, between events
+on the handle's stream, the view launch alone (rn_views_batch_device) and the trunk's feature pass alone (rn_features_depth_u8_device).
+With --lib PATH a third arm runs the views step of that other build (handle and trainer both from it) in the same rotation: the A/B of
+the two feature slots against one is --lib of a build with RN_VARIANT_FLAGS=-DFT_VIEW_SLOTS=1 (csrc/build.sh, RN_FILES=rn_finetune).
+
     python tools/bench_finetune.py [--depth 3] [--steps 200] [--runs 5] [--steps-only] [--lib PATH]
+    python tools/bench_finetune.py --views [--lib ONE_SLOT_BUILD.so] [--steps 200] [--runs 3] [--out profiles/finetune_views_timing.json]
     python tools/bench_finetune.py --dropout 0.35 [--lib PARENT_BUILD.so] [--steps 200] [--runs 7]
     python tools/bench_finetune.py --val-every 10 [--steps 200] [--runs 5] [--out profiles/finetune_validate_timing.json]
     rocprofv3 --kernel-trace --stats -d DIR -o kt --output-format csv -- python tools/bench_finetune.py [--depth 3] --trace-run
@@ -183,6 +190,96 @@ def validate_case(side, batch, steps, runs, depth, n_val, val_every):
             tr.close()
 
 
+VIEW_SHAPES = ((480, 640), (640, 480), (1080, 1920), (224, 224), (448, 448), (600, 800))      # (height, width) of the resident photographs
+VIEW_ITEMS = 96
+
+
+def views_case(depth, steps, runs, batch=45, lib=None):
+    """The cached-feature step beside the step on fresh views -- and (``lib``) beside the views step of another build, handle and
+    trainer both of that build: a one-slot build, say --, the arms in an order that rotates run by run after a warm-up round; then
+    the view launch and the trunk's feature pass of one minibatch alone, between events on the handle's stream."""
+    import torch
+    from roomnet_amd import _capi, finetune
+    g, w = _weights(224)
+    rng = np.random.default_rng(11)
+    photos = [rng.integers(0, 256, VIEW_SHAPES[k % len(VIEW_SHAPES)] + (3,), dtype=np.uint8) for k in range(VIEW_ITEMS)]
+    feats, labels = _data(g, VIEW_ITEMS, depth)
+    index = finetune.epoch_indices(VIEW_ITEMS, batch, steps, seed=1)
+    eng = _capi.Engine(g, w, device=0, dtype="bf16", max_batch=batch)
+    arms = ["cached", "views"] + (["views_other"] if lib else [])
+    views, trainers, us, other = None, {}, {a: [] for a in arms}, None
+    try:
+        views = eng.views_create(photos)
+        if lib:
+            other_eng = _capi.Engine(g, w, device=0, dtype="bf16", max_batch=batch, lib_path=lib)
+            other = (other_eng, other_eng.views_create(photos))
+        for name in arms:
+            tr = _capi.Trainer(g, w, device=0, max_batch=batch, learn_rate=2e-4, l2_coeff=0.06, depth=depth,
+                               lib_path=lib if name == "views_other" else None)
+            trainers[name] = (tr, [tr.upload(feats) if name == "cached" else 0, tr.upload(labels), tr.upload(index)])
+        del feats
+        for r in range(runs + 1):                                   # the first round is the warm-up
+            k = r % len(arms)
+            for name in arms[k:] + arms[:k]:
+                tr, d = trainers[name]
+                if name == "cached":
+                    tr.run(d[0], d[1], VIEW_ITEMS, d[2], batch, steps)
+                elif name == "views":
+                    tr.run_views(eng, views, d[1], d[2], batch, steps, seed=1)
+                else:
+                    tr.run_views(other[0], other[1], d[1], d[2], batch, steps, seed=1)
+                us[name].append(tr.last_run_ms() * 1e3 / steps)
+        out = {"side": 224, "dtype": "bf16", "batch": batch, "depth": depth, "steps_per_run": steps, "runs": runs,
+               "photographs": VIEW_ITEMS, "photograph_shapes": [list(s) for s in VIEW_SHAPES], "resident_bytes": views.nbytes,
+               "other_lib": lib}
+        for name, v in us.items():
+            v = v[1:]
+            out[name] = {"us_per_step": round(statistics.median(v), 2), "us_per_step_min": round(min(v), 2),
+                         "us_per_step_max": round(max(v), 2)}
+        out["views_minus_cached_us"] = round(out["views"]["us_per_step"] - out["cached"]["us_per_step"], 2)
+        if lib:
+            a, b = out["views"], out["views_other"]
+            out["views_ranges_overlap"] = bool(a["us_per_step_min"] <= b["us_per_step_max"] and b["us_per_step_min"] <= a["us_per_step_max"])
+        # the two launches in front of a step, alone
+        eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        d_index = torch.from_numpy(index[0].copy()).cuda()
+        d_bgr = torch.empty((batch, 224, 224, 3), dtype=torch.uint8, device="cuda")
+        d_f = torch.empty((batch,) + finetune.feature_shape(g, depth), dtype=torch.float32, device="cuda")
+        import ctypes as C
+
+        def make_views():
+            _capi._check(eng.lib, eng.lib.rn_views_batch_device(eng.handle, views.handle, C.c_void_p(d_index.data_ptr()), 0, batch, 1, 0, 3,
+                                                                C.c_void_p(d_bgr.data_ptr())), "rn_views_batch_device")
+
+        def timed(fn, reps=50, warmup=5):
+            for _ in range(warmup):
+                fn()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / reps
+
+        vl = [timed(make_views) for _ in range(max(runs, 1))]
+        fp = [timed(lambda: eng.features_u8_device(d_bgr.data_ptr(), batch, d_f.data_ptr(), depth=depth)) for _ in range(max(runs, 1))]
+        eng.set_stream(None)
+        out["view_launch_us"] = {"median": round(statistics.median(vl), 2), "min": round(min(vl), 2), "max": round(max(vl), 2)}
+        out["feature_pass_us"] = {"median": round(statistics.median(fp), 2), "min": round(min(fp), 2), "max": round(max(fp), 2)}
+        return out
+    finally:
+        for tr, _ in trainers.values():
+            tr.close()
+        if views is not None:
+            views.close()
+        if other is not None:
+            other[1].close()
+            other[0].close()
+        eng.close()
+
+
 def step_case(side, batch, steps, runs, depth=2, lib=None, dropout=0.0):
     from roomnet_amd import _capi, finetune
     g, w = _weights(side)
@@ -316,6 +413,8 @@ def main():
                     help="the dropout-on arm beside the dropout-off arm (and beside --lib's dropout-off arm) at both depths")
     ap.add_argument("--val-every", type=int, default=0, metavar="K",
                     help="what a validation point costs inside the run (rn_ft_run_validated) and from the host (rn_ft_run / rn_ft_eval)")
+    ap.add_argument("--views", action="store_true",
+                    help="the step on fresh random views (rn_ft_run_views) beside the cached-feature step, both depths, and the view launch alone")
     args = ap.parse_args()
     if not args.summarise:
         import torch  # noqa: F401  (before libroomnet_hip.so is loaded: one HIP runtime in the process, torch's)
@@ -327,6 +426,18 @@ def main():
         return
     if args.trace_run:
         trace_run(args.depth, args.dropout)
+        return
+    if args.views:
+        doc = {"what": "fine-tuning on fresh random views (rn_ft_run_views) at batch 45 / 224 on a bf16 handle, one session on one MI355X: "
+                       "us per Adam step (device time of the step loop, rn_ft_last_run_ms) of the cached-feature run and of the views "
+                       "run, the arms alternating run by run after a warm-up round; the view launch and the trunk's feature pass of "
+                       "one minibatch alone, between events on the handle's stream; views_other: the views run of the build given with "
+                       "--lib (handle and trainer both of that build)",
+               "cases": [views_case(depth, args.steps, args.runs, lib=args.lib) for depth in (2, 3)]}
+        text = json.dumps(doc, indent=1)
+        if args.out:
+            open(args.out, "w").write(text + "\n")
+        print(json.dumps(doc))
         return
     if args.val_every:
         doc = {"what": "validation inside a fine-tuning run at batch 45 / 224, val_every %d, both depths, n_val 256 and 2048, the arms "

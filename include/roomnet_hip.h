@@ -628,6 +628,48 @@ typedef struct rn_cam_target {
 RN_API int rn_cam_overlay_batch_device(rn_handle* h, const rn_cam_target* targets, int n, double weight);
 RN_API int rn_cam_last_overlay_ms(rn_handle* h, float* ms);
 
+/* ---- occlusion-sensitivity maps ------------------------------------------------------------------
+ * An input-resolution answer to "where did the network see class c?" that needs no backward pass: cover a
+ * square of the network's input, run the forward pass, record how far the class probability falls, slide the square.  For a
+ * handle of side S, patch side P and stride T with 1 <= T <= P <= S (roomnet_amd/occlusion.py states the same in NumPy):
+ *   positions  per axis p_k = min(k T, S - P) for k = 0 .. G - 1, G = ceil((S - P) / T) + 1: the last window is flush with the
+ *              edge and may overlap its neighbour irregularly; every pixel is covered (T <= P); P = S gives G = 1.
+ *   window     w = ky G + kx covers rows p_ky .. p_ky + P - 1 and columns p_kx .. p_kx + P - 1 of the S x S x 3 uint8 BGR input.
+ *   fill       fill_bgr[3], or NULL for the image's own mean per channel, (2 sum + S S) / (2 S S) in integer arithmetic over its
+ *              S x S input (the mean rounded half up).
+ *   pass 0     the forward pass of the n unmasked images: probs / ids are the bits rn_forward_u8_device returns for that batch.
+ *              The class c_i is class_ids[i], or ids[i] of pass 0 when class_ids is NULL; it is read on the device.
+ *   passes     the n G G (image, window) pairs, flattened as i G G + w, are cut into chunks of max_batch (the last one shorter;
+ *              chunks cross image boundaries).  Per chunk: one mask launch into a workspace [max_batch, S, S, 3], the forward pass
+ *              of the chunk, one score launch: drop[i, ky, kx] = p0[i, c_i] - p_w[i, c_i], a float32 subtraction.
+ *   map        map[i, y, x] = (float32 sum of drop[i, ky, kx] over the windows covering (y, x), ky ascending, then kx ascending)
+ *              / float(count of those windows): additions and one division, one thread per pixel.  Negative entries are kept
+ *              (rn_cam_overlay_batch_device, which draws any float32 map on the crop window, takes the positive part itself).
+ * The workspaces -- the masked chunk, its probabilities and ids, the per-image fills -- belong to the handle (allocated by the
+ * first call, sized for max_batch, freed by rn_destroy); everything runs on the handle's stream, so back-to-back calls without a
+ * sync are fine.  All three dtypes: the pipeline only feeds the uint8 forward entry.
+ *
+ * rn_occlusion_plan          host only, no device: G, n_windows = n G G and n_chunks = ceil(n_windows / max_batch) (each pointer
+ *                            may be NULL).  RN_E_INVALID for stride > patch, patch > side or any value below 1; RN_E_RANGE for
+ *                            n > max_batch or n G G > 2^20.
+ * rn_occlusion_masks_device  the masked images of the flattened indices [first, first + count) into d_out [count, S, S, 3]: the
+ *                            mask enqueuer of the full call on its own.  count outside [1, max_batch] or a range outside the
+ *                            call's n G G: RN_E_RANGE.  Asynchronous.
+ * rn_occlusion_u8_device     pass 0, the masked passes and (d_map not NULL) the map: d_drop [n, G, G], d_map [n, S, S],
+ *                            d_probs [n, num_classes], d_ids [n].  It only enqueues; class ids, when given, are read back and
+ *                            checked first (outside [0, num_classes): RN_E_INVALID).  The plan's refusals are this call's; a
+ *                            refused call enqueues nothing and leaves the handle usable.
+ * rn_occlusion_u8            the same for host buffers; blocks.
+ * rn_occlusion_last_ms       device time of the last call, pass 0 to the map; waits for it. */
+RN_API int rn_occlusion_plan(int side, int patch, int stride, int n, int max_batch, int* G, int* n_windows, int* n_chunks);
+RN_API int rn_occlusion_masks_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, int patch, int stride, const uint8_t* fill_bgr,
+                                     int first, int count, uint8_t* d_out);
+RN_API int rn_occlusion_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, int n, const int32_t* d_class_ids, int patch, int stride,
+                                  const uint8_t* fill_bgr, float* d_drop, float* d_map, float* d_probs, int64_t* d_ids);
+RN_API int rn_occlusion_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, const int32_t* class_ids, int patch, int stride,
+                           const uint8_t* fill_bgr, float* drop, float* map, float* probs, int64_t* ids);
+RN_API int rn_occlusion_last_ms(rn_handle* h, float* ms);
+
 /* ---- fine-tuning stages 8-9 and the dense head on cached features ------------------------------
  * What the reference's RoomNet(optimized_inference=False).load() prepares (network.py:242, restore_excluded_vars: the conv trunk
  * restored, the dense head left at its initial values, to be trained), cut where it is cheap: stages 0-7 stay frozen, and

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "rn_jpeg_encode_batch_device", "rn_jpeg_last_encode_ms",
     "rn_jpeg_encode_headers", "rn_jpeg_huffenc_model", "rn_jpeg_huffenc_batch", "rn_jpeg_encode_files_device", "rn_jpeg_last_huffenc_ms",
     "rn_cam_overlay_batch_device", "rn_cam_last_overlay_ms",
+    "rn_occlusion_plan", "rn_occlusion_masks_device", "rn_occlusion_u8_device", "rn_occlusion_u8", "rn_occlusion_last_ms",
 )
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
@@ -432,6 +433,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.rn_cam_overlay_batch_device.restype = i32
         lib.rn_cam_last_overlay_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_cam_last_overlay_ms.restype = i32
+    if hasattr(lib, "rn_occlusion_plan"):
+        lib.rn_occlusion_plan.argtypes = [i32] * 5 + [C.POINTER(C.c_int)] * 3
+        lib.rn_occlusion_plan.restype = i32
+        lib.rn_occlusion_masks_device.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp]
+        lib.rn_occlusion_masks_device.restype = i32
+        for name in ("rn_occlusion_u8_device", "rn_occlusion_u8"):
+            fn = getattr(lib, name)
+            fn.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+            fn.restype = i32
+        lib.rn_occlusion_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_occlusion_last_ms.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -533,10 +545,12 @@ class Engine:
     def close(self) -> None:
         if getattr(self, "_h", None):
             for p in (getattr(self, "_jpeg_dst", 0), getattr(self, "_jpeg_src", 0), getattr(self, "_jpeg_res", 0),
-                      getattr(self, "_cam_maps", 0)):      # (jpegs_to_batch's / classify_resident's / explain_resident's device buffers)
+                      getattr(self, "_cam_maps", 0), getattr(self, "_occ_maps", 0), getattr(self, "_occ_drops", 0)):
+                # (jpegs_to_batch's / classify_resident's / explain_resident's / occlusion_resident's device buffers)
                 if p:
                     self.lib.rn_device_free(self._h, C.c_void_p(p))
             self._jpeg_dst = self._jpeg_src = self._jpeg_src_cap = self._jpeg_res = self._cam_maps = 0
+            self._occ_maps = self._occ_drops = self._occ_drops_cap = 0
             self.lib.rn_destroy(self._h)
             self._h = None
 
@@ -786,6 +800,41 @@ class Engine:
         self.d2h(ids, d_ids)
         mh, mw, _c = self.nodes()[layer][1]
         return ids, probs, addrs, shapes, [self._cam_maps + k * mh * mw * 4 for k in range(m)], (mh, mw)
+
+    def occlusion_resident(self, jpegs, images, patch: int = 32, stride: int = 16, fill="mean", class_ids=None):
+        """``explain_resident`` with occlusion-sensitivity maps: the chunk is staged the same way, then ``rn_occlusion_u8_device`` runs
+        on the cropped, resized batch -- pass 0, the masked passes, the pixel map -- and the maps STAY on the device.  Returns
+        ``(ids, probs, addresses, shapes, d_maps, (S, S))``: ``ids`` / ``probs`` are ``classify_resident``'s bits, ``d_maps[k]`` the
+        device address of file k's float32 ``[S, S]`` map, valid like the image addresses until the next ``occlusion_resident``
+        (``cam_overlay_batch`` takes both)."""
+        jpegs, images = list(jpegs), [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        m, nc, s = len(jpegs) + len(images), self.graph.num_classes, self.graph.im_side
+        if not 1 <= m <= self.max_batch:
+            raise ValueError("occlusion_resident: %d files (1..%d)" % (m, self.max_batch))
+        _g, n_windows, _c = self.occlusion_plan(m, patch, stride)
+        self._occlusion_fill(fill)               # (a bad fill is refused before anything is staged)
+        addrs, shapes = self._stage_resident(jpegs, images)
+        if not getattr(self, "_jpeg_res", 0):
+            self._jpeg_res = self.device_malloc(self.max_batch * (nc * 4 + 8))
+        if not getattr(self, "_occ_maps", 0):
+            self._occ_maps, self._occ_drops, self._occ_drops_cap = self.device_malloc(self.max_batch * (s * s * 4 + 4)), 0, 0    # the maps, then the class ids
+        if n_windows > self._occ_drops_cap:
+            self.sync()
+            if self._occ_drops:
+                self.device_free(self._occ_drops)
+            self._occ_drops_cap = n_windows + n_windows // 4
+            self._occ_drops = self.device_malloc(self._occ_drops_cap * 4)
+        d_probs, d_ids = self._jpeg_res, self._jpeg_res + self.max_batch * nc * 4
+        d_cls = None
+        if class_ids is not None:
+            d_cls = self._occ_maps + self.max_batch * s * s * 4
+            self.h2d(d_cls, np.ascontiguousarray(np.broadcast_to(np.asarray(class_ids), (m,)), dtype=np.int32))
+        self.occlusion_u8_device(self._jpeg_dst, m, d_cls, patch, stride, fill, self._occ_drops, self._occ_maps, d_probs, d_ids)
+        self.sync()
+        probs, ids = np.empty((m, nc), np.float32), np.empty((m,), np.int64)
+        self.d2h(probs, d_probs)
+        self.d2h(ids, d_ids)
+        return ids, probs, addrs, shapes, [self._occ_maps + k * s * s * 4 for k in range(m)], (s, s)
 
     def cam_overlay_batch(self, items, weight: float = 0.5) -> None:
         """``rn_cam_overlay_batch_device`` over ``items`` ``[(device image address, (height, width), device map address, (mh, mw))]``
@@ -1067,6 +1116,68 @@ class Engine:
                                             self.nodes()[layer][0], C.c_void_p(d_cam), C.c_void_p(d_alpha) if d_alpha else None,
                                             C.c_void_p(d_probs), C.c_void_p(d_ids))
         _check(self.lib, rc, "rn_grad_cam_u8_device")
+
+    # -- occlusion-sensitivity maps (include/roomnet_hip.h; roomnet_amd/occlusion.py is the NumPy statement)
+    @staticmethod
+    def _occlusion_fill(fill):
+        """``"mean"`` -> None (the library computes the per-image means), a BGR triple -> three bytes."""
+        if isinstance(fill, str):
+            if fill != "mean":
+                raise ValueError("occlusion: fill must be 'mean' or a BGR triple, got %r" % (fill,))
+            return None
+        f = np.asarray(fill)
+        if f.shape != (3,) or (f < 0).any() or (f > 255).any():
+            raise ValueError("occlusion: fill must be 'mean' or a BGR triple of 0..255, got %r" % (fill,))
+        return (C.c_uint8 * 3)(*[int(v) for v in f])
+
+    def occlusion_plan(self, n: int, patch: int, stride: int) -> Tuple[int, int, int]:
+        """``rn_occlusion_plan`` for this engine's side and ``max_batch``: ``(G, n_windows, n_chunks)``."""
+        return occlusion_plan(self.graph.im_side, patch, stride, n, self.max_batch, lib=self.lib)
+
+    def occlusion_masks_device(self, d_bgr: int, n: int, patch: int, stride: int, fill, first: int, count: int, d_out: int) -> None:
+        """Asynchronous ``rn_occlusion_masks_device`` on raw device pointers: the masked images ``[first, first + count)``."""
+        rc = self.lib.rn_occlusion_masks_device(self.handle, C.c_void_p(d_bgr), n, patch, stride, self._occlusion_fill(fill), first, count,
+                                                C.c_void_p(d_out))
+        _check(self.lib, rc, "rn_occlusion_masks_device")
+
+    def occlusion_u8_device(self, d_bgr: int, n: int, d_class_ids: Optional[int], patch: int, stride: int, fill, d_drop: int,
+                            d_map: Optional[int], d_probs: int, d_ids: int) -> None:
+        """Asynchronous ``rn_occlusion_u8_device`` on raw device pointers."""
+        rc = self.lib.rn_occlusion_u8_device(self.handle, C.c_void_p(d_bgr), n, C.c_void_p(d_class_ids) if d_class_ids else None, patch,
+                                             stride, self._occlusion_fill(fill), C.c_void_p(d_drop), C.c_void_p(d_map) if d_map else None,
+                                             C.c_void_p(d_probs), C.c_void_p(d_ids))
+        _check(self.lib, rc, "rn_occlusion_u8_device")
+
+    def occlusion_u8(self, im_bgr_u8: np.ndarray, class_ids=None, patch: int = 32, stride: int = 16, fill="mean", with_map: bool = True):
+        """Occlusion-sensitivity maps of a uint8 BGR ``[N,S,S,3]`` batch (``rn_occlusion_u8`` per ``max_batch`` images).  Returns
+        ``(maps [N,S,S] float32 or None, drops [N,G,G] float32, ids [N] int64, probs [N,C] float32)``."""
+        s = self.graph.im_side
+        im = np.ascontiguousarray(im_bgr_u8, dtype=np.uint8)
+        if im.ndim != 4 or im.shape[1:] != (s, s, 3):
+            raise ValueError("expected a [N,%d,%d,3] uint8 batch, got %s" % (s, s, im.shape))
+        n = im.shape[0]
+        g = self.occlusion_plan(min(n, self.max_batch), patch, stride)[0]         # (refuses an empty batch and a bad grid)
+        fill_c = self._occlusion_fill(fill)
+        cls = None
+        if class_ids is not None:
+            cls = np.ascontiguousarray(np.broadcast_to(np.asarray(class_ids), (n,)), dtype=np.int32)
+        maps = np.empty((n, s, s), np.float32) if with_map else None
+        drops = np.empty((n, g, g), np.float32)
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            rc = self.lib.rn_occlusion_u8(self.handle, im[i:i + m].ctypes.data, m, None if cls is None else cls[i:i + m].ctypes.data,
+                                          patch, stride, fill_c, drops[i:i + m].ctypes.data, maps[i:i + m].ctypes.data if with_map else None,
+                                          probs[i:i + m].ctypes.data, ids[i:i + m].ctypes.data)
+            _check(self.lib, rc, "rn_occlusion_u8")
+        return maps, drops, ids, probs
+
+    def occlusion_last_ms(self) -> float:
+        """Device time of the last occlusion call, pass 0 to the map (``rn_occlusion_last_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_occlusion_last_ms(self.handle, C.byref(ms)), "rn_occlusion_last_ms")
+        return float(ms.value)
 
     def features_shape(self, depth: int = 2) -> Tuple[int, int, int]:
         """Per-image shape of the fine-tuning feature of a trainer of ``depth``: ``s7.bn`` at depth 2 (``rn_features_shape``),
@@ -1529,6 +1640,14 @@ def group_plan(n: int, ndev: int, max_batch_per_device: int, num_classes: int = 
     counts, offsets, slot = (C.c_int * ndev)(), (C.c_int * ndev)(), C.c_size_t(0)
     _check(lib, lib.rn_group_plan(n, ndev, max_batch_per_device, num_classes, counts, offsets, C.byref(slot)), "rn_group_plan")
     return list(counts), list(offsets), int(slot.value)
+
+
+def occlusion_plan(side: int, patch: int, stride: int, n: int, max_batch: int, lib: Optional[C.CDLL] = None) -> Tuple[int, int, int]:
+    """``rn_occlusion_plan``: (G, n_windows, n_chunks) of an n-image occlusion call -- no GPU needed."""
+    lib = lib or load_library()
+    g, nw, nc = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib, lib.rn_occlusion_plan(side, patch, stride, n, max_batch, C.byref(g), C.byref(nw), C.byref(nc)), "rn_occlusion_plan")
+    return int(g.value), int(nw.value), int(nc.value)
 
 
 # launch families of rn_band_plan (include/roomnet_hip.h: RN_BANDS_*)

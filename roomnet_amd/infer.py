@@ -239,15 +239,19 @@ def _in_batches_of_readable(results, batch_size):
     yield from pending
 
 
-def _explain_files(nn, fpaths, batch_size, layer):
+def _explain_files(nn, fpaths, batch_size, layer, occlusion=None):
     """``_infer_files`` with the evidence: yields ``(index, image_bgr, idx, conf, cam)``, the grad-CAM map of each file's predicted
-    class from ``nn.grad_cam`` on the same batches; ids and confidences are ``_infer_files``'s (the grad-CAM contract)."""
+    class from ``nn.grad_cam`` on the same batches; ids and confidences are ``_infer_files``'s (the grad-CAM contract).
+    ``layer`` "occlusion": the occlusion-sensitivity map from ``nn.occlusion_map(..., **occlusion)`` instead (the same contract)."""
     pending = []
 
     def flush():
         if not pending:
             return []
-        cams, ids, probs = nn.grad_cam([p[1] for p in pending], layer=layer)
+        if layer == 'occlusion':
+            cams, _drops, ids, probs = nn.occlusion_map([p[1] for p in pending], **(occlusion or {}))
+        else:
+            cams, ids, probs = nn.grad_cam([p[1] for p in pending], layer=layer)
         res = [(p[0], p[1], int(ids[k]), probs[k][ids[k]], cams[k]) for k, p in enumerate(pending)]
         pending.clear()
         return res
@@ -269,7 +273,7 @@ def _heat_overlay_and_write(im, cam_map, weight, pred_label, pred_conf, out_fpat
 
 
 def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False, gpu_encode=False, heatmap=None, heatmap_weight=0.5,
-                    gpu_huffman=False, gpu_huffman_encode=False, gpu_orient=False):
+                    gpu_huffman=False, gpu_huffman_encode=False, gpu_orient=False, occlusion_patch=32, occlusion_stride=16):
     """infer.py:65-100.  The overlay and the encoding of the output file (the reference does both between two ``sess.run`` calls)
     run on a second thread pool behind the loop -- per 1920 x 1080 image they cost what decoding it cost -- and the function
     returns when every file is written; printed lines, workbook rows and file names are the loop's, in list order.
@@ -283,7 +287,11 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     ``gpu_encode``): the Huffman pass of the OUTPUT files runs on the GPU too: only the files' bytes come
     back and the writer pool only writes them; same outputs.  ``gpu_orient`` (with ``gpu_decode``): files with an EXIF orientation of
     2..8 -- portrait phone photos -- are decoded and turned on the GPU too instead of by ``imread``; same
-    outputs."""
+    outputs.  ``heatmap`` ("s6.bn", "s7.bn": the grad-CAM map of the predicted class; "occlusion": its occlusion-sensitivity map,
+    DESIGN.md section 22, with squares of ``occlusion_patch`` slid by ``occlusion_stride`` and the mean fill) is drawn on the square
+    the network saw, under the text: with ``gpu_decode`` and ``gpu_encode`` on the device (``Engine.occlusion_resident`` /
+    ``explain_resident``, then ``cam_overlay_batch``), otherwise per batch by ``RoomNet.occlusion_map`` / ``grad_cam`` and
+    ``cam.overlay_image`` on the writer pool; same outputs."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     if gpu_huffman and not gpu_decode:
@@ -304,8 +312,11 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     if heatmap is not None and not overlay:
         raise ValueError("classify_im_dir: heatmap=%r needs overlay=True (without the overlay the files are copied: there is "
                          "nothing to draw on)" % (heatmap,))
-    if heatmap is not None and heatmap not in ('s6.bn', 's7.bn'):
-        raise ValueError("classify_im_dir: heatmap must be None, 's6.bn' or 's7.bn', got %r" % (heatmap,))
+    if heatmap is not None and heatmap not in ('s6.bn', 's7.bn', 'occlusion'):
+        raise ValueError("classify_im_dir: heatmap must be None, 's6.bn', 's7.bn' or 'occlusion', got %r" % (heatmap,))
+    if heatmap == 'occlusion' and not 1 <= occlusion_stride <= occlusion_patch:
+        raise ValueError("classify_im_dir: 1 <= occlusion_stride <= occlusion_patch does not hold for stride %r, patch %r"
+                         % (occlusion_stride, occlusion_patch))
     if heatmap is not None and not 0.0 <= heatmap_weight <= 1.0:
         raise ValueError("classify_im_dir: heatmap_weight must be in [0, 1], got %r" % (heatmap_weight,))
     print('Classifying images in', imgs_dir)
@@ -324,6 +335,10 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     writers = ThreadPoolExecutor(max_workers=DECODE_THREADS) if overlay else None
     writing = deque()
     extra = {} if heatmap is None else dict(heatmap=heatmap, heatmap_weight=heatmap_weight)      # (a model object without the arguments still works without a heat map)
+    occlusion = None
+    if heatmap == 'occlusion':
+        occlusion = dict(patch=occlusion_patch, stride=occlusion_stride)
+        extra.update(occlusion_patch=occlusion_patch, occlusion_stride=occlusion_stride)
     if gpu_huffman_encode:
         extra["gpu_huffman_encode"] = True
     if gpu_orient and gpu_encode:
@@ -335,7 +350,7 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
                                      lambda h, w, idx, conf: _overlay_lines(h, w, CLASS_LABELS[idx], conf),
                                      writers, batch_size=batch_size, **extra), batch_size)
     elif heatmap is not None:
-        results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap))
+        results = ((i, idx, conf, (im, cam_map), None) for i, im, idx, conf, cam_map in _explain_files(nn, all_im_paths, batch_size, heatmap, occlusion))
     else:
         results = ((i, idx, conf, im, None) for i, im, idx, conf in
                    _infer_files(nn, all_im_paths, batch_size, gpu_decode=gpu_decode, gpu_huffman=gpu_huffman, gpu_orient=gpu_orient))

@@ -461,7 +461,7 @@ class RoomNet:
                 yield (k * chunk, res) if gpu_huffman is None else (k * chunk, res, pool)
 
     def classify_files_to_dir(self, paths, out_path_of, lines_of, writers, decode_threads=None, batch_size=64, heatmap=None,
-                              heatmap_weight=0.5, gpu_huffman_encode=False, gpu_orient=False):
+                              heatmap_weight=0.5, gpu_huffman_encode=False, gpu_orient=False, occlusion_patch=32, occlusion_stride=16):
         """Classify image FILES and write each with its overlay as a JPEG file, decode to encode on the GPU.  Yields, in list
         order, ``(index, id, conf, image, future)``: ``future`` is the pending write (on the ``writers`` pool) of a file that went
         through the device; ``image`` (BGR) is set instead for a file whose output name ``out_path_of(index, id)`` has no JPEG
@@ -480,7 +480,10 @@ class RoomNet:
         square the network saw with ``heatmap_weight``, UNDER the text.  The chunk then runs ``Engine.explain_resident`` (the
         forward pass and its adjoint; the same ids and confidences) and ``Engine.cam_overlay_batch`` in front of the text and the
         encode, all on the device; a file the caller writes comes back with its heat map drawn on the host (``grad_cam``,
-        ``cam.overlay_image``: the same bytes).
+        ``cam.overlay_image``: the same bytes).  ``heatmap="occlusion"`` draws the occlusion-sensitivity map of the predicted class
+        instead (``occlusion_patch``, ``occlusion_stride``, mean fill): the chunk runs
+        ``Engine.occlusion_resident`` -- pass 0 gives the same ids and confidences, the masked passes and the ``S x S`` map stay on the
+        device -- and the same ``Engine.cam_overlay_batch``; the host way is ``occlusion_map`` and ``cam.overlay_image``.
 
         ``gpu_huffman_encode``: the Huffman pass of the OUTPUT runs on the GPU as well (``Engine.jpeg_encode_files``, DESIGN.md
         section 19): no coefficient leaves the device, the files arrive in a ring of page-locked byte buffers (two banks, the
@@ -495,8 +498,8 @@ class RoomNet:
         import os
         from . import cam, hershey, jpegdec, jpegenc
         from ._capi import GRAD_CAM_LAYERS
-        if heatmap is not None and heatmap not in GRAD_CAM_LAYERS:
-            raise ValueError("classify_files_to_dir: heatmap must be None or one of %s, got %r" % (GRAD_CAM_LAYERS, heatmap))
+        if heatmap is not None and heatmap != "occlusion" and heatmap not in GRAD_CAM_LAYERS:
+            raise ValueError("classify_files_to_dir: heatmap must be None, 'occlusion' or one of %s, got %r" % (GRAD_CAM_LAYERS, heatmap))
         if not 0.0 <= heatmap_weight <= 1.0:
             raise ValueError("classify_files_to_dir: heatmap_weight must be in [0, 1]")
         paths = list(paths)
@@ -557,7 +560,10 @@ class RoomNet:
                 if heatmap is None:
                     ids, probs, addrs, shapes = eng.classify_resident(*staged)
                 else:
-                    ids, probs, addrs, shapes, d_cams, map_shape = eng.explain_resident(*staged, heatmap)
+                    if heatmap == "occlusion":
+                        ids, probs, addrs, shapes, d_cams, map_shape = eng.occlusion_resident(*staged, occlusion_patch, occlusion_stride)
+                    else:
+                        ids, probs, addrs, shapes, d_cams, map_shape = eng.explain_resident(*staged, heatmap)
                     eng.cam_overlay_batch([(addrs[m], shapes[m], d_cams[m], map_shape) for m in range(len(addrs))], heatmap_weight)
                 confs = [probs[m][ids[m]] for m in range(len(ids))]
                 overlays = list(writers.map(rasterise, shapes, [lines_of(h, w, int(ids[m]), confs[m]) for m, (h, w) in enumerate(shapes)]))
@@ -587,7 +593,10 @@ class RoomNet:
                 for m, j in enumerate(host):
                     out[j] = (int(ids[m]), probs[m][ids[m]], loaded[j][1], None)
             elif host:
-                cams, ids, probs = self.grad_cam([loaded[j][1] for j in host], layer=heatmap)
+                if heatmap == "occlusion":
+                    cams, _drops, ids, probs = self.occlusion_map([loaded[j][1] for j in host], patch=occlusion_patch, stride=occlusion_stride)
+                else:
+                    cams, ids, probs = self.grad_cam([loaded[j][1] for j in host], layer=heatmap)
                 for m, j in enumerate(host):
                     out[j] = (int(ids[m]), probs[m][ids[m]], cam.overlay_image(loaded[j][1], cams[m], heatmap_weight), None)
             for j in range(len(loaded)):
@@ -662,6 +671,23 @@ class RoomNet:
             x = (((im[:, :, :, [2, 1, 0]] / 255.) * 2) - 1).astype(np.float32)
             cams, ids, probs = eng.grad_cam(x, class_ids=class_ids, layer=layer)
         return cams, ids, probs
+
+    def occlusion_map(self, im_in, class_ids=None, patch=32, stride=16, fill="mean"):
+        """Occlusion-sensitivity maps (not in the reference): how far each image's class probability falls when a ``patch x patch``
+        square of the network's input, slid by ``stride``, is covered with ``fill`` ("mean": the image's own mean colour, or a BGR
+        triple) -- an input-resolution map from forward passes alone (``roomnet_amd.occlusion`` states the definition).  ``im_in``
+        as ``grad_cam`` takes it (uint8 values); ``class_ids``: the class per image (None: each image's argmax).  Returns
+        ``(maps [N,S,S] float32, drops [N,G,G] float32, ids int64[N], probs float32[N,C])``; negative entries (covering the square
+        RAISED the probability) are kept, ``roomnet_amd.cam.overlay_image`` clips them."""
+        if isinstance(im_in, np.ndarray) and im_in.ndim == 3:
+            im_in = [im_in]                                   # one HWC image: a batch of one
+        if isinstance(im_in, np.ndarray) and im_in.ndim != 4:
+            raise ValueError("occlusion_map: expected an [N,S,S,3] batch, one [H,W,3] image or a list of images, got shape %s"
+                             % (im_in.shape,))
+        im = self._as_feed(np.asarray(self._batch_from(im_in, "occlusion_map")))
+        if im.dtype != np.uint8:
+            raise ValueError("occlusion_map: the squares are cut out of the uint8 input; got %s" % im.dtype)
+        return self._engine().occlusion_u8(im, class_ids=class_ids, patch=patch, stride=stride, fill=fill)
 
     # ------------------------------------------------------ batch-statistics BN
     def _batch_from(self, im_in, who):

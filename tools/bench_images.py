@@ -33,6 +33,13 @@
         of the two heat-map launches (rn_cam_last_overlay_ms) for one batch and both layers, next to the decode's and the encode's
         pixel stages of the same batch; then classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True) with heatmap="s6.bn",
         the same call with heatmap=None and the host arm with the heat map, alternating, twice each after a warm-up round
+  python tools/bench_images.py --occlusion [--out=PATH] [--threads=T] [N]    occlusion-sensitivity maps, nothing
+        of the above; the lines also go to PATH (default profiles/occlusion_bench.txt).  (a) one rn_occlusion_u8_device call for N
+        (default 64) resident images at 224 and the default grid (patch 32, stride 16) against the same number of plain
+        rn_forward_u8_device calls with the same chunk sizes on a resident buffer: alternating in one session, three runs each
+        after a warm-up of both, enqueue to sync on the host's clock, and the call's own device time (rn_occlusion_last_ms);
+        (b) the same call against the Python route, occlusion.occlusion_map_host over nn.infer; (c) classify_im_dir(overlay=True,
+        gpu_decode=True, gpu_encode=True) with heatmap="occlusion" against heatmap="s6.bn" on N generated 640x480 and 1920x1080 files
 """
 import contextlib
 import io
@@ -582,7 +589,99 @@ def gpu_orient_arm():
     pixel_stage_by_orientation()
 
 
-if '--heatmap' in sys.argv:
+def occlusion_arm():
+    """(a) the device call against the plain passes it is made of, (b) against the Python route, (c) the directory driver."""
+    global H, W, N
+    from roomnet_amd import infer, occlusion
+    from roomnet_amd.network import RoomNet
+    n = int(args[0]) if args else 64
+    out_path = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--out=')), os.path.join('profiles', 'occlusion_bench.txt'))
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    patch, stride, S = 32, 16, 224
+    nn = RoomNet(num_classes=6, im_side=S, compute_bn_mean_var=False, optimized_inference=True, dtype='bf16', max_batch=64)
+    nn.load(os.path.join('roomnet_amd', 'final_model', 'roomnet'))
+    eng = nn._engine()
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+    ims = np.stack([np.clip(np.stack([127 + 100 * np.sin(f[2 * c] * xx + k) * np.cos(f[2 * c + 1] * yy) for c in range(3)], -1)
+                            + rng.normal(0, 6, (S, S, 3)), 0, 255).astype(np.uint8)
+                    for k, f in enumerate(rng.uniform(0.01, 0.08, (n, 6)))])
+    G, n_windows, n_chunks = eng.occlusion_plan(n, patch, stride)
+    plan = occlusion.chunks(n_windows, eng.max_batch)
+    d_bgr, d_work = eng.device_malloc(ims.nbytes), eng.device_malloc(eng.max_batch * S * S * 3)
+    d_drop, d_map = eng.device_malloc(n_windows * 4), eng.device_malloc(n * S * S * 4)
+    d_probs, d_ids = eng.device_malloc(eng.max_batch * 6 * 4), eng.device_malloc(eng.max_batch * 8)
+    eng.h2d(d_bgr, ims)
+    eng.h2d(d_work, np.ascontiguousarray(np.resize(ims, (eng.max_batch, S, S, 3))))
+
+    def occluded():
+        t0 = time.perf_counter()
+        eng.occlusion_u8_device(d_bgr, n, None, patch, stride, 'mean', d_drop, d_map, d_probs, d_ids)
+        eng.sync()
+        return 1e3 * (time.perf_counter() - t0), eng.occlusion_last_ms()
+
+    def plain():
+        t0 = time.perf_counter()
+        eng.forward_u8_device(d_bgr, n, d_probs, d_ids)
+        for _first, count in plan:
+            eng.forward_u8_device(d_work, count, d_probs, d_ids)
+        eng.sync()
+        return 1e3 * (time.perf_counter() - t0)
+
+    occluded(), plain()                                  # the warm-up of both (the first call allocates the workspaces)
+    t_occ, t_dev, t_plain = [], [], []
+    for _ in range(3):
+        a, b = occluded()
+        t_occ.append(a)
+        t_dev.append(b)
+        t_plain.append(plain())
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    say('(a) %d resident images at %d, patch %d, stride %d: G = %d, %d masked passes in %d chunks of %d, bf16.  One rn_occlusion_u8_device '
+        'call, enqueue to sync: %s ms (device time of the call: %s ms)   the same %d + %d plain rn_forward_u8_device calls on a resident '
+        'buffer: %s ms   alternating, same session, 3 runs each after a warm-up of both   ratio of the medians: %.3f   %.0f masked '
+        'passes/ms' % (n, S, patch, stride, G, n_windows, n_chunks, eng.max_batch, ' / '.join('%.2f' % x for x in t_occ),
+                       ' / '.join('%.2f' % x for x in t_dev), 1, n_chunks, ' / '.join('%.2f' % x for x in t_plain),
+                       med(t_occ) / med(t_plain), n_windows / med(t_occ)))
+    maps = np.empty((n, S, S), np.float32)
+    eng.d2h(maps, d_map)
+    t0 = time.perf_counter()
+    want = occlusion.occlusion_map_host(lambda b: nn.infer(b)[1], ims, patch=patch, stride=stride, max_batch=eng.max_batch)
+    t_py = 1e3 * (time.perf_counter() - t0)
+    say('(b) the Python route, occlusion.occlusion_map_host over nn.infer (masked copies built with NumPy, %.0f MB uploaded): %.0f ms, '
+        'x%.1f the device call; maps identical: %s' % (n_windows * S * S * 3 / 1e6, t_py, t_py / med(t_occ), bool(np.array_equal(maps, want[0]))))
+    for d in (d_bgr, d_work, d_drop, d_map, d_probs, d_ids):
+        eng.device_free(d)
+    nn.sess.close()
+    for H, W in ((480, 640), (1080, 1920)):
+        N = n
+        root, d, nn2, paths, mb = generated_directory()
+        arms = {'occlusion': dict(heatmap='occlusion'), 's6.bn': dict(heatmap='s6.bn')}
+        times = {a: [] for a in arms}
+        with contextlib.redirect_stdout(io.StringIO()):
+            for rep in range(3):                          # (the first round is the warm-up of both arms)
+                for arm, kw in arms.items():
+                    t0 = time.perf_counter()
+                    infer.classify_im_dir(nn2, d, overlay=True, batch_size=64, gpu_decode=True, gpu_encode=True, **kw)
+                    if rep:
+                        times[arm].append(time.perf_counter() - t0)
+        say('(c) %d JPEG files %dx%d (%.0f MB), classify_im_dir(overlay=True, gpu_decode=True, gpu_encode=True), %d decode threads, alternating, '
+            '2 runs each after a warm-up:   ' % (len(paths), W, H, mb, infer.DECODE_THREADS)
+            + '   '.join('heatmap=%r %s img/s' % (a, ' / '.join('%.1f' % (len(paths) / x) for x in t)) for a, t in times.items()))
+        nn2.sess.close()
+        shutil.rmtree(root, ignore_errors=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, 'w') as f:
+        f.write('python tools/bench_images.py --occlusion %d\n' % n + '\n'.join(lines) + '\n')
+
+
+if '--occlusion' in sys.argv:
+    occlusion_arm()
+elif '--heatmap' in sys.argv:
     heatmap_arm()
 elif '--dir' in sys.argv and '--gpu-orient' in sys.argv:
     gpu_orient_arm()

@@ -950,7 +950,11 @@ RN_API int rn_tap(rn_handle* h, int node_id, float* out, size_t cap_elems, size_
  *   rn_bn_batch_stats  mean[c] = sum x / count and var_biased[c] = sum (x - mean)^2 / count over the count =
  *                      n * h * w values per channel of the BN's input (dense BNs: n), float32; any of the three
  *                      output pointers may be NULL.  Computed as float32 Welford partials merged in float64
- *                      (rn_bnstats.hip): deterministic, and close to a float64 two-pass result.  The update
+ *                      (rn_bnstats.hip): deterministic, and close to a float64 two-pass result.  count is
+ *                      read back from the device: the number of values the merge of that call really saw per
+ *                      channel (dense BNs: the n their kernel ran over), not a product formed on the host.
+ *                      RN_E_STATE "merged counts disagree" -- the one message for all of these -- if the channels
+ *                      of a BN saw different counts, or the value is not a whole number, or it is below 1.  The update
  *                      of the moving statistics itself is host arithmetic on 32 short vectors
  *                      (roomnet_amd/bnstats.py: moving_update, variance_for_update).
  * RN_E_STATE on a handle without the flag or before the first forward call, RN_E_RANGE for a bad index. */

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(MOM_THREADS) void bn_moments_kernel(const float4* _
 // moments as moving statistics normalises with the same table.
 __global__ __launch_bounds__(64) void bn_finalise_kernel(const Part* __restrict__ parts, int nparts, int C, const float* __restrict__ gamma,
                                                          float eps, float* __restrict__ mean_out, float* __restrict__ var_out,
-                                                         float* __restrict__ inv_out) {
+                                                         float* __restrict__ inv_out, double* __restrict__ n_out) {
     const int c = blockIdx.x, lane = threadIdx.x;
     double sn = 0, snm = 0;
     for (int b = lane; b < nparts; b += 64) {
@@ -143,7 +143,12 @@ __global__ __launch_bounds__(64) void bn_finalise_kernel(const Part* __restrict_
         const float var = static_cast<float>(q / sn);
         mean_out[c] = static_cast<float>(mean);
         var_out[c] = var;
-        inv_out[c] = __fmul_rn(__fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, eps))), gamma[c]);
+        // sqrtf, not __fsqrt_rn: the intrinsic is the hardware's one-ulp square root here, sqrtf and the division are correctly
+        // rounded, as the host's are in rn_bn_inv.  That rests on hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt: no
+        // fast-math flag and no -fno-hip-fp32-correctly-rounded-divide-sqrt may reach build.sh
+        // (tests/test_hip_bnstats_local.py's output check sees an inv one ulp off)
+        inv_out[c] = __fmul_rn(__fdiv_rn(1.0f, sqrtf(__fadd_rn(var, eps))), gamma[c]);
+        n_out[c] = sn;      // the count this channel's merge really saw (rn_bn_batch_stats reports it)
     }
 }
 
@@ -187,7 +192,7 @@ __global__ __launch_bounds__(1024) void dense_relu6_kernel(const float* __restri
 __global__ __launch_bounds__(256) void dense_bn_batch_kernel(const float* __restrict__ x, int n, int nout, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps, float* __restrict__ mean_out,
                                                              float* __restrict__ var_out, float* __restrict__ inv_out,
-                                                             float* __restrict__ shift_out, float* __restrict__ y) {
+                                                             float* __restrict__ shift_out, double* __restrict__ n_out, float* __restrict__ y) {
     __shared__ float s_inv[64], s_shift[64];
     const int t = threadIdx.x;
     if (t < nout) {
@@ -200,12 +205,13 @@ __global__ __launch_bounds__(256) void dense_bn_batch_kernel(const float* __rest
             q = fma(d, d, q);
         }
         const float meanf = static_cast<float>(mean), var = static_cast<float>(q / n);
-        const float inv = __fmul_rn(__fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, eps))), gamma[t]);
+        const float inv = __fmul_rn(__fdiv_rn(1.0f, sqrtf(__fadd_rn(var, eps))), gamma[t]);      // (sqrtf: see bn_finalise_kernel)
         const float shift = __fsub_rn(beta[t], __fmul_rn(meanf, inv));
         mean_out[t] = meanf;
         var_out[t] = var;
         inv_out[t] = inv;
         shift_out[t] = shift;
+        n_out[t] = n;
         s_inv[t] = inv;
         s_shift[t] = shift;
     }
@@ -225,6 +231,7 @@ struct BnSlot {
     float* beta = nullptr;      // [c] device (dense BNs; the conv-side table keeps its own)
     float* mean = nullptr;      // [c] device: the last call's batch mean ...
     float* var = nullptr;       // ... and biased variance
+    double* merged_n = nullptr; // [c] device: how many values the last call's merge saw per channel (the count rn_bn_batch_stats returns)
     float* inv = nullptr;       // the table entries the BN launch reads (conv side: BnDev.mean / .inv; dense: DensePlan.inv / .shift)
     float* shift = nullptr;
 };
@@ -276,6 +283,8 @@ int rn_bnstats_prepare(rn_handle* h, const rn_weights* w) {
         }
         if ((rc = dev_alloc(h, static_cast<size_t>(c) * 4, &p)) != RN_OK) return rc;
         b.var = static_cast<float*>(p);
+        if ((rc = dev_alloc(h, static_cast<size_t>(c) * sizeof(double), &p)) != RN_OK) return rc;
+        b.merged_n = static_cast<double*>(p);
         *index = static_cast<int>(pl->bns.size());
         pl->bns.push_back(b);
         return static_cast<int>(RN_OK);
@@ -334,7 +343,8 @@ int rn_bnstats_conv(rn_handle* h, int stage, bool second, const float* x, int64_
         default: launch_moments<128>(h->stream, x, total4, blocks, pl->parts); break;
     }
     RN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_finalise_kernel, dim3(b.c), dim3(64), 0, h->stream, pl->parts, blocks, b.c, b.gamma, h->bn_eps, b.mean, b.var, b.inv);
+    hipLaunchKernelGGL(bn_finalise_kernel, dim3(b.c), dim3(64), 0, h->stream, pl->parts, blocks, b.c, b.gamma, h->bn_eps, b.mean, b.var, b.inv,
+                       b.merged_n);
     RN_CHECK_LAUNCH();
     return RN_OK;
 }
@@ -359,7 +369,7 @@ int rn_bnstats_head(rn_handle* h, int n, float* d_probs, int64_t* d_ids) {
         hipLaunchKernelGGL(dense_relu6_kernel, dim3(n), dim3(threads), 0, h->stream, cur, dp.w, dp.bias, dp.nin, dp.nout, mm, relu);
         RN_CHECK_LAUNCH();
         hipLaunchKernelGGL(dense_bn_batch_kernel, dim3(1), dim3(256), 0, h->stream, relu, n, dp.nout, b.gamma, b.beta, h->bn_eps, b.mean, b.var,
-                           b.inv, b.shift, bn);
+                           b.inv, b.shift, b.merged_n, bn);
         RN_CHECK_LAUNCH();
         cur = bn;
     }
@@ -426,11 +436,24 @@ extern "C" int rn_bn_batch_stats(rn_handle* h, int i, float* mean, float* var_bi
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && mean) e = hipMemcpy(mean, b.mean, static_cast<size_t>(b.c) * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && var_biased) e = hipMemcpy(var_biased, b.var, static_cast<size_t>(b.c) * 4, hipMemcpyDeviceToHost);
+    double merged[MAX_BN_CHANNELS];
+    if (e == hipSuccess && count) e = hipMemcpy(merged, b.merged_n, static_cast<size_t>(b.c) * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) {
         rn_set_error("rn_bn_batch_stats: device copy failed: %s", hipGetErrorString(e));
         (void)hipGetLastError();
         return RN_E_HIP;
     }
-    if (count) *count = static_cast<int64_t>(h->last_n) * b.per_image;
+    if (count) {
+        // the count the device merged, not last_n * per_image: a float4 the partition dropped or read twice shows here
+        // (one message for all three: a count that is no whole number in [1, 2^53), channels that differ)
+        const double n0 = merged[0];
+        bool ok = n0 >= 1.0 && n0 < 9.0e15 && n0 == static_cast<double>(static_cast<int64_t>(n0));
+        for (int c = 1; ok && c < b.c; ++c) ok = merged[c] == n0;
+        if (!ok) {
+            rn_set_error("rn_bn_batch_stats: merged counts disagree");
+            return RN_E_STATE;
+        }
+        *count = static_cast<int64_t>(n0);
+    }
     return RN_OK;
 }

@@ -670,6 +670,64 @@ RN_API int rn_occlusion_u8(rn_handle* h, const uint8_t* bgr_nhwc, int n, const i
                            const uint8_t* fill_bgr, float* drop, float* map, float* probs, int64_t* ids);
 RN_API int rn_occlusion_last_ms(rn_handle* h, float* ms);
 
+/* ---- deletion and insertion curves of a heat map ------------------------------------------------
+ * Which heat map to believe: take away the pixels a map ranks highest, a fraction at a time, and watch the
+ * class probability fall (deletion); start from nothing, put them back in the same order and watch it rise (insertion).  A map that
+ * points at the evidence gives a small deletion area and a large insertion area.  For a handle of side S, an image im [S, S, 3]
+ * uint8 BGR, a map m [S, S] float32 of any values, a class c and a step count J with 1 <= J <= S S (roomnet_amd/faithfulness.py
+ * states the same in NumPy, csrc/rn_faith.hip in its header comment):
+ *   order      pixels by map value descending, equal values by raster index y S + x ascending, -0.0 equal to +0.0, NaN behind
+ *              everything else and NaNs among themselves by index: np.argsort(-m.ravel(), kind="stable").  rank[p] is the position
+ *              of pixel p in that order, a permutation of 0 .. S S - 1.
+ *   sort key   0 for NaN; otherwise u = bits(v + 0.0f) and key = u ^ 0xFFFFFFFF when the sign bit of u is set, else
+ *              u ^ 0x80000000; sorted by 0xFFFFFFFF - key ascending, stably (a radix sort in which no atomic decides a position:
+ *              the same map gives the same ranks on every run).
+ *   steps      n_j = (j S S) / J in 64-bit integers for j = 0 .. J: n_0 = 0, n_J = S S.
+ *   fill       fill_bgr[3], or NULL for the image's own mean per channel, (2 sum + S S) / (2 S S), exactly as occlusion's.
+ *   images     deletion image j: pixels with rank < n_j hold the fill, the rest im.  Insertion image j: pixels with rank >= n_j
+ *              hold the fill, the rest im.  J + 1 points per curve, each its own forward pass; the endpoints the two curves share
+ *              are not deduplicated (a forward pass need not give an image the same bits at another batch size or slot).
+ *   pass 0     the forward pass of the n <= max_batch unmasked images: probs / ids are the bits rn_forward_u8_device returns.
+ *              The class c_i is class_ids[i], or ids[i] of pass 0 when class_ids is NULL; it is read on the device.
+ *   passes     modes is a bit mask of RN_FAITH_DELETION | RN_FAITH_INSERTION, M the number of set bits, deletion first.  The
+ *              n M (J + 1) passes, flattened as f = (i M + mode_slot) (J + 1) + j, are cut into chunks of max_batch (the last one
+ *              shorter; chunks cross curve and image boundaries).  Per chunk: one mask launch into the workspace occlusion uses
+ *              too, the forward pass of the chunk, one score launch: curve[i, mode_slot, j] = p_f[c_i], a float32 copy.
+ *   area       auc[i, mode_slot] = float32((sum over j = 0 .. J - 1, ascending, of float64(c_j) + float64(c_{j+1})) / (2 J)):
+ *              a sequential float64 sum without fma.
+ * The ranking's workspace (16 bytes per pixel of max_batch images, which also keeps a call's ranks) belongs to the handle: allocated
+ * by the first call, freed by rn_destroy.  Everything runs on the handle's stream, so these calls and occlusion calls follow each
+ * other without a sync.  All three dtypes: the pipeline only feeds the uint8 forward entry.
+ *
+ * rn_faith_plan          host only, no device: n_passes = n M (J + 1) and n_chunks = ceil(n_passes / max_batch) (each pointer may
+ *                        be NULL).  RN_E_INVALID for steps < 1, steps > side^2, modes outside 1..3 or n, side, max_batch below 1;
+ *                        RN_E_RANGE for n > max_batch or n_passes > 2^20.
+ * rn_faith_rank_model    host only: the ranks of n maps of npix values each (any npix >= 1) by the kernel's own steps, its waves,
+ *                        tiles and lanes run one after another (csrc/rn_faith_rank.h): the CPU statement of the sort.
+ * rn_faith_ranks_device  the ranks alone: d_map [n, S, S] float32 -> d_rank [n, S, S] uint32.  Asynchronous.
+ * rn_faith_masks_device  the masked images of the flattened passes [first, first + count) into d_out [count, S, S, 3]: the rank and
+ *                        mask enqueuers of the full call on their own.  count outside [1, max_batch] or a range outside the call's
+ *                        n M (J + 1): RN_E_RANGE.  Asynchronous.
+ * rn_faith_u8_device     pass 0, the ranks, the masked passes and the areas: d_curve [n, M, J + 1], d_auc [n, M],
+ *                        d_probs [n, num_classes], d_ids [n].  It only enqueues; class ids, when given, are read back and checked
+ *                        first (outside [0, num_classes): RN_E_INVALID).  A null buffer is RN_E_INVALID; the plan's refusals are
+ *                        this call's; a refused call enqueues nothing and leaves the handle usable.
+ * rn_faith_u8            the same for host buffers; blocks.
+ * rn_faith_last_ms       device time of the last rn_faith_u8_device / rn_faith_u8 call, pass 0 to the areas, or of the rank launch
+ *                        of the last rn_faith_ranks_device, whichever came last; waits for it. */
+#define RN_FAITH_DELETION 1
+#define RN_FAITH_INSERTION 2
+RN_API int rn_faith_plan(int side, int steps, int modes, int n, int max_batch, int* n_passes, int* n_chunks);
+RN_API int rn_faith_rank_model(const float* map, int n, int npix, uint32_t* rank);
+RN_API int rn_faith_ranks_device(rn_handle* h, const float* d_map, int n, uint32_t* d_rank);
+RN_API int rn_faith_masks_device(rn_handle* h, const uint8_t* d_bgr_nhwc, const float* d_map, int n, int steps, int modes,
+                                 const uint8_t* fill_bgr, int first, int count, uint8_t* d_out);
+RN_API int rn_faith_u8_device(rn_handle* h, const uint8_t* d_bgr_nhwc, const float* d_map, int n, const int32_t* d_class_ids, int steps,
+                              int modes, const uint8_t* fill_bgr, float* d_curve, float* d_auc, float* d_probs, int64_t* d_ids);
+RN_API int rn_faith_u8(rn_handle* h, const uint8_t* bgr_nhwc, const float* map, int n, const int32_t* class_ids, int steps, int modes,
+                       const uint8_t* fill_bgr, float* curve, float* auc, float* probs, int64_t* ids);
+RN_API int rn_faith_last_ms(rn_handle* h, float* ms);
+
 /* ---- fine-tuning stages 8-9 and the dense head on cached features ------------------------------
  * What the reference's RoomNet(optimized_inference=False).load() prepares (network.py:242, restore_excluded_vars: the conv trunk
  * restored, the dense head left at its initial values, to be trained), cut where it is cheap: stages 0-7 stay frozen, and

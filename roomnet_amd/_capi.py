@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "rn_jpeg_encode_headers", "rn_jpeg_huffenc_model", "rn_jpeg_huffenc_batch", "rn_jpeg_encode_files_device", "rn_jpeg_last_huffenc_ms",
     "rn_cam_overlay_batch_device", "rn_cam_last_overlay_ms",
     "rn_occlusion_plan", "rn_occlusion_masks_device", "rn_occlusion_u8_device", "rn_occlusion_u8", "rn_occlusion_last_ms",
+    "rn_faith_plan", "rn_faith_rank_model", "rn_faith_ranks_device", "rn_faith_masks_device", "rn_faith_u8_device", "rn_faith_u8",
+    "rn_faith_last_ms",
 )
 
 # what rn_ft_read returns of a trained variable (include/roomnet_hip.h: fine-tuning)
@@ -444,6 +446,21 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             fn.restype = i32
         lib.rn_occlusion_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.rn_occlusion_last_ms.restype = i32
+    if hasattr(lib, "rn_faith_plan"):
+        lib.rn_faith_plan.argtypes = [i32] * 5 + [C.POINTER(C.c_int)] * 2
+        lib.rn_faith_plan.restype = i32
+        lib.rn_faith_rank_model.argtypes = [vp, i32, i32, vp]
+        lib.rn_faith_rank_model.restype = i32
+        lib.rn_faith_ranks_device.argtypes = [vp, vp, i32, vp]
+        lib.rn_faith_ranks_device.restype = i32
+        lib.rn_faith_masks_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]
+        lib.rn_faith_masks_device.restype = i32
+        for name in ("rn_faith_u8_device", "rn_faith_u8"):
+            fn = getattr(lib, name)
+            fn.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+            fn.restype = i32
+        lib.rn_faith_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.rn_faith_last_ms.restype = i32
     if path is None:
         _lib = lib
     return lib
@@ -1179,6 +1196,68 @@ class Engine:
         _check(self.lib, self.lib.rn_occlusion_last_ms(self.handle, C.byref(ms)), "rn_occlusion_last_ms")
         return float(ms.value)
 
+    # -- deletion / insertion curves of a heat map (include/roomnet_hip.h; roomnet_amd/faithfulness.py is the NumPy statement)
+    def faith_plan(self, n: int, steps: int, modes=3) -> Tuple[int, int]:
+        """``rn_faith_plan`` for this engine's side and ``max_batch``: ``(n_passes, n_chunks)``."""
+        from .faithfulness import mode_mask
+        return faith_plan(self.graph.im_side, steps, modes if isinstance(modes, int) else mode_mask(modes), n, self.max_batch, lib=self.lib)
+
+    def faith_ranks_device(self, d_map: int, n: int, d_rank: int) -> None:
+        """Asynchronous ``rn_faith_ranks_device`` on raw device pointers: ``[n,S,S]`` float32 maps -> ``[n,S,S]`` uint32 ranks."""
+        _check(self.lib, self.lib.rn_faith_ranks_device(self.handle, C.c_void_p(d_map), n, C.c_void_p(d_rank)), "rn_faith_ranks_device")
+
+    def faith_masks_device(self, d_bgr: int, d_map: int, n: int, steps: int, modes, fill, first: int, count: int, d_out: int) -> None:
+        """Asynchronous ``rn_faith_masks_device`` on raw device pointers: the masked images of the passes ``[first, first + count)``."""
+        from .faithfulness import mode_mask
+        rc = self.lib.rn_faith_masks_device(self.handle, C.c_void_p(d_bgr), C.c_void_p(d_map), n, steps, mode_mask(modes),
+                                            self._occlusion_fill(fill), first, count, C.c_void_p(d_out))
+        _check(self.lib, rc, "rn_faith_masks_device")
+
+    def faith_u8_device(self, d_bgr: int, d_map: int, n: int, d_class_ids: Optional[int], steps: int, modes, fill, d_curve: int,
+                        d_auc: int, d_probs: int, d_ids: int) -> None:
+        """Asynchronous ``rn_faith_u8_device`` on raw device pointers."""
+        from .faithfulness import mode_mask
+        rc = self.lib.rn_faith_u8_device(self.handle, C.c_void_p(d_bgr), C.c_void_p(d_map), n, C.c_void_p(d_class_ids) if d_class_ids else None,
+                                         steps, mode_mask(modes), self._occlusion_fill(fill), C.c_void_p(d_curve), C.c_void_p(d_auc),
+                                         C.c_void_p(d_probs), C.c_void_p(d_ids))
+        _check(self.lib, rc, "rn_faith_u8_device")
+
+    def faith_u8(self, im_bgr_u8: np.ndarray, maps: np.ndarray, class_ids=None, steps: int = 32, modes=3, fill="mean"):
+        """Deletion / insertion curves of ``[N,S,S]`` float32 maps on a uint8 BGR ``[N,S,S,3]`` batch (``rn_faith_u8`` per ``max_batch``
+        images).  Returns ``(curves [N,M,J+1] float32, aucs [N,M] float32, ids [N] int64, probs [N,C] float32)``."""
+        from .faithfulness import mode_mask, mode_slots
+        s = self.graph.im_side
+        im = np.ascontiguousarray(im_bgr_u8, dtype=np.uint8)
+        if im.ndim != 4 or im.shape[1:] != (s, s, 3):
+            raise ValueError("expected a [N,%d,%d,3] uint8 batch, got %s" % (s, s, im.shape))
+        n = im.shape[0]
+        maps = np.ascontiguousarray(maps, dtype=np.float32)
+        if maps.shape != (n, s, s):
+            raise ValueError("expected [%d,%d,%d] float32 maps, got %s" % (n, s, s, maps.shape))
+        mask, m_curves = mode_mask(modes), len(mode_slots(modes))
+        self.faith_plan(min(n, self.max_batch), steps, mask)          # (refuses an empty batch and bad steps)
+        fill_c = self._occlusion_fill(fill)
+        cls = None
+        if class_ids is not None:
+            cls = np.ascontiguousarray(np.broadcast_to(np.asarray(class_ids), (n,)), dtype=np.int32)
+        curves = np.empty((n, m_curves, steps + 1), np.float32)
+        aucs = np.empty((n, m_curves), np.float32)
+        probs = np.empty((n, self.graph.num_classes), np.float32)
+        ids = np.empty((n,), np.int64)
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            rc = self.lib.rn_faith_u8(self.handle, im[i:i + m].ctypes.data, maps[i:i + m].ctypes.data, m,
+                                      None if cls is None else cls[i:i + m].ctypes.data, steps, mask, fill_c, curves[i:i + m].ctypes.data,
+                                      aucs[i:i + m].ctypes.data, probs[i:i + m].ctypes.data, ids[i:i + m].ctypes.data)
+            _check(self.lib, rc, "rn_faith_u8")
+        return curves, aucs, ids, probs
+
+    def faith_last_ms(self) -> float:
+        """Device time of the last faithfulness call, or of the last ``faith_ranks_device``'s rank launch (``rn_faith_last_ms``)."""
+        ms = C.c_float(0)
+        _check(self.lib, self.lib.rn_faith_last_ms(self.handle, C.byref(ms)), "rn_faith_last_ms")
+        return float(ms.value)
+
     def features_shape(self, depth: int = 2) -> Tuple[int, int, int]:
         """Per-image shape of the fine-tuning feature of a trainer of ``depth``: ``s7.bn`` at depth 2 (``rn_features_shape``),
         ``s6.bn`` at depth 3 (``rn_features_depth_shape``)."""
@@ -1648,6 +1727,26 @@ def occlusion_plan(side: int, patch: int, stride: int, n: int, max_batch: int, l
     g, nw, nc = C.c_int(0), C.c_int(0), C.c_int(0)
     _check(lib, lib.rn_occlusion_plan(side, patch, stride, n, max_batch, C.byref(g), C.byref(nw), C.byref(nc)), "rn_occlusion_plan")
     return int(g.value), int(nw.value), int(nc.value)
+
+
+def faith_plan(side: int, steps: int, modes, n: int, max_batch: int, lib: Optional[C.CDLL] = None) -> Tuple[int, int]:
+    """``rn_faith_plan``: (n_passes, n_chunks) of an n-image deletion / insertion call -- no GPU needed.  ``modes``: the bit mask
+    (1 deletion, 2 insertion, 3 both)."""
+    lib = lib or load_library()
+    npass, nc = C.c_int(0), C.c_int(0)
+    _check(lib, lib.rn_faith_plan(side, steps, int(modes), n, max_batch, C.byref(npass), C.byref(nc)), "rn_faith_plan")
+    return int(npass.value), int(nc.value)
+
+
+def faith_rank_model(maps: np.ndarray, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """``rn_faith_rank_model``: the ranks of ``[n, npix]`` float32 maps by the rank kernel's own steps on the host -- no GPU needed."""
+    lib = lib or load_library()
+    maps = np.ascontiguousarray(maps, dtype=np.float32)
+    if maps.ndim != 2:
+        raise ValueError("faith_rank_model: expected [n, npix] maps, got %s" % (maps.shape,))
+    rank = np.empty(maps.shape, np.uint32)
+    _check(lib, lib.rn_faith_rank_model(maps.ctypes.data, maps.shape[0], maps.shape[1], rank.ctypes.data), "rn_faith_rank_model")
+    return rank
 
 
 # launch families of rn_band_plan (include/roomnet_hip.h: RN_BANDS_*)

@@ -14,7 +14,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 
-PLAIN="rn_api rn_kernels_f32 rn_fused rn_generic rn_imageops rn_jpeg rn_jpeg_huff rn_jpeg_enc rn_jpeg_huffenc rn_cam_overlay rn_occlusion rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam rn_bnstats rn_finetune rn_finetune7"
+PLAIN="rn_api rn_kernels_f32 rn_fused rn_generic rn_imageops rn_jpeg rn_jpeg_huff rn_jpeg_enc rn_jpeg_huffenc rn_cam_overlay rn_occlusion rn_faith rn_group rn_tail rn_conv16 rn_stage_f32m rn_backend rn_gradcam rn_bnstats rn_finetune rn_finetune7"
 # MFMA results stay in VGPRs: the epilogue reads every accumulator with the VALU, and AGPR
 # accumulators cost one v_accvgpr_read each (64 per row in the residual variant).
 # (max-ilp scheduling was measured slower, see NOTES.md)

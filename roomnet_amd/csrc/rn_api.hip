@@ -655,6 +655,7 @@ extern "C" void rn_destroy(rn_handle* h) {
     rn_jpeg_huffenc_release(h);
     rn_cam_overlay_release(h);
     rn_occlusion_release(h);
+    rn_faith_release(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }

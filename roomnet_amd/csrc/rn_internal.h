@@ -207,6 +207,7 @@ struct rn_handle {
     void* jpeg_huffenc = nullptr; // rn_jpeg_huffenc_* / rn_jpeg_encode_files_device: lengths, sums, both streams, the descriptor tables (rn_jpeg_huffenc.hip; the same)
     void* cam_overlay = nullptr; // rn_cam_overlay_*: the CamDev tables and the per-image maxima (rn_cam_overlay.hip; the same)
     void* occlusion = nullptr;   // rn_occlusion_*: the masked chunk, its probabilities and ids, the per-image fills (rn_occlusion.hip; the same)
+    void* faith = nullptr;       // rn_faith_*: the ranking's (key, index) sets, which also keep a call's ranks (rn_faith.hip; the same)
     bool split_backend = false;  // 16-bit handles: this call runs the back end as its split launches (grad-CAM: s6.bn, s7.bn in HBM)
     bool features_pass = false;  // rn_features_*: this call reads s6.bn / s7.bn only; a flatten head_kernel cannot take does not fail it
     // channel relabelling of the tensors the frozen-channel folds touch, float32 (rn_f32m_prepare) and 16-bit (rn_fused_prepare) alike:
@@ -287,6 +288,8 @@ void rn_jpeg_huffenc_release(rn_handle* h);
 void rn_cam_overlay_release(rn_handle* h);
 // ---- occlusion-sensitivity maps (rn_occlusion.hip)
 void rn_occlusion_release(rn_handle* h);
+// ---- deletion / insertion curves of a heat map (rn_faith.hip; what it shares with occlusion: rn_masked_chunk.h)
+void rn_faith_release(rn_handle* h);
 // (rn_api.hip) the centred square window of network.py:137-146 (of a packed BGR image: its top left, side and row bytes), the tail
 // of a host entry point, the null-argument (RN_E_INVALID) / n in 1..max_batch (RN_E_RANGE) check the batched image stages open with
 struct rn_window {

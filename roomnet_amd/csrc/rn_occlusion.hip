@@ -23,9 +23,7 @@
 //   occlusion_score_kernel  one thread per masked image of the chunk.
 //   occlusion_map_kernel    one thread per pixel; the window positions are recomputed from k, T, S, P.
 // Every kernel parameter is passed by value.
-#include "rn_internal.h"
-
-#include <algorithm>
+#include "rn_masked_chunk.h"
 
 #pragma clang fp contract(off)
 
@@ -160,41 +158,7 @@ __global__ __launch_bounds__(256) void occlusion_map_kernel(const float* __restr
     map[(static_cast<int64_t>(blockIdx.z) * S + y) * S + x] = sum / static_cast<float>(count);      // (T <= P: count >= 1)
 }
 
-// What the handle keeps for the masked passes, sized for max_batch, and the staging of the host entry point.
-struct OccState {
-    uint8_t* d_masked = nullptr;     // [max_batch, S, S, 3] the chunk's masked images
-    float* d_probs = nullptr;        // [max_batch, num_classes] the chunk's probabilities
-    int64_t* d_ids = nullptr;        // [max_batch] ... and classes (not read)
-    uint8_t* d_fill = nullptr;       // [max_batch, 3] the per-image mean fills
-    int32_t* d_cls = nullptr;        // [max_batch] rn_occlusion_u8's class ids
-    float* d_map = nullptr;          // [max_batch, S, S] rn_occlusion_u8's map
-    float* d_drop = nullptr;         // rn_occlusion_u8's drops (grow-only)
-    size_t drop_cap = 0;
-    rn_timer timer;
-    bool ready = false;
-};
-
-int occ_state(rn_handle* h, OccState** out) {
-    if (!h->occlusion) {
-        OccState* s = new OccState();
-        h->occlusion = s;              // (rn_occlusion_release frees whatever of it exists)
-        const size_t nb = static_cast<size_t>(h->max_batch), px = static_cast<size_t>(h->im_side) * h->im_side;
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_masked), nb * px * 3));
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_probs), nb * h->num_classes * sizeof(float)));
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ids), nb * sizeof(int64_t)));
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_fill), nb * 3));
-        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_cls), nb * sizeof(int32_t)));
-        int rc;
-        if ((rc = s->timer.create()) != RN_OK) return rc;
-        s->ready = true;
-    }
-    *out = static_cast<OccState*>(h->occlusion);
-    if (!(*out)->ready) {
-        rn_set_error("rn_occlusion: the workspace could not be allocated earlier");
-        return RN_E_STATE;
-    }
-    return RN_OK;
-}
+using OccState = rn_masked_chunk;      // (rn_masked_chunk.h: rn_faith.hip runs its masked passes through the same workspace)
 
 struct OccPlan {
     int G, n_windows, n_chunks;
@@ -211,27 +175,6 @@ int check_plan(const char* who, const rn_handle* h, int n, int patch, int stride
         rn_set_error("%s: %s", who, why.c_str());
     }
     return rc;
-}
-
-int check_classes(const char* who, const rn_handle* h, const int32_t* cls, int n) {
-    for (int i = 0; i < n; ++i)
-        if (cls[i] < 0 || cls[i] >= h->num_classes) {
-            rn_set_error("%s: class_ids[%d] = %d outside [0, %d)", who, i, cls[i], h->num_classes);
-            return RN_E_INVALID;
-        }
-    return RN_OK;
-}
-
-// the per-image fills of a call without a triple -> st->d_fill
-int enqueue_mean(rn_handle* h, OccState* st, const uint8_t* d_bgr, int n) {
-    const bool dwords = (3 * h->im_side * h->im_side) % 4 == 0 && (reinterpret_cast<uintptr_t>(d_bgr) & 3) == 0;
-    (void)hipGetLastError();
-    if (dwords)
-        hipLaunchKernelGGL(occlusion_mean_kernel<true>, dim3(n), dim3(256), 0, h->stream, d_bgr, h->im_side, st->d_fill);
-    else
-        hipLaunchKernelGGL(occlusion_mean_kernel<false>, dim3(n), dim3(256), 0, h->stream, d_bgr, h->im_side, st->d_fill);
-    RN_CHECK_LAUNCH();
-    return RN_OK;
 }
 
 // The one mask enqueuer: the masked images of the flattened pairs [first, first + count) into d_out.  `mean`: the fills are
@@ -269,17 +212,19 @@ int enqueue_all(rn_handle* h, OccState* st, const OccPlan& plan, const uint8_t* 
     //  rn_occlusion_last_ms answering RN_E_STATE, never a half-recorded interval)
     if ((rc = st->timer.start(h->stream)) != RN_OK) return rc;
     if ((rc = rn_forward_u8_device(h, d_bgr, n, d_probs, d_ids)) != RN_OK) return rc;
-    if (!fill && (rc = enqueue_mean(h, st, d_bgr, n)) != RN_OK) return rc;
+    if (!fill && (rc = rn_masked_enqueue_mean(h, st, d_bgr, n)) != RN_OK) return rc;
     const int gg = plan.G * plan.G;
-    for (int first = 0; first < plan.n_windows; first += h->max_batch) {
-        const int count = std::min(h->max_batch, plan.n_windows - first);
-        if ((rc = enqueue_masks(h, st, d_bgr, patch, stride, plan.G, !fill, fill, first, count, st->d_masked)) != RN_OK) return rc;
-        if ((rc = rn_forward_u8_device(h, st->d_masked, count, st->d_probs, st->d_ids)) != RN_OK) return rc;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(occlusion_score_kernel, dim3((count + 63) / 64), dim3(64), 0, h->stream, d_probs, d_ids, d_cls, st->d_probs,
-                           h->num_classes, gg, first, count, d_drop);
-        RN_CHECK_LAUNCH();
-    }
+    rc = rn_masked_passes(
+        h, st, plan.n_windows,
+        [&](int first, int count) { return enqueue_masks(h, st, d_bgr, patch, stride, plan.G, !fill, fill, first, count, st->d_masked); },
+        [&](int first, int count) {
+            (void)hipGetLastError();
+            hipLaunchKernelGGL(occlusion_score_kernel, dim3((count + 63) / 64), dim3(64), 0, h->stream, d_probs, d_ids, d_cls, st->d_probs,
+                               h->num_classes, gg, first, count, d_drop);
+            RN_CHECK_LAUNCH();
+            return RN_OK;
+        });
+    if (rc != RN_OK) return rc;
     if (d_map) {
         (void)hipGetLastError();
         hipLaunchKernelGGL(occlusion_map_kernel, dim3((h->im_side + 63) / 64, (h->im_side + 3) / 4, n), dim3(256), 0, h->stream, d_drop,
@@ -290,6 +235,57 @@ int enqueue_all(rn_handle* h, OccState* st, const OccPlan& plan, const uint8_t* 
 }
 
 }  // namespace
+
+// ---- what rn_faith.hip shares (rn_masked_chunk.h)
+int rn_masked_chunk_get(rn_handle* h, rn_masked_chunk** out) {
+    if (!h->occlusion) {
+        OccState* s = new OccState();
+        h->occlusion = s;              // (rn_occlusion_release frees whatever of it exists)
+        const size_t nb = static_cast<size_t>(h->max_batch), px = static_cast<size_t>(h->im_side) * h->im_side;
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_masked), nb * px * 3));
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_probs), nb * h->num_classes * sizeof(float)));
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ids), nb * sizeof(int64_t)));
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_fill), nb * 3));
+        RN_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_cls), nb * sizeof(int32_t)));
+        int rc;
+        if ((rc = s->timer.create()) != RN_OK) return rc;
+        s->ready = true;
+    }
+    *out = static_cast<OccState*>(h->occlusion);
+    if (!(*out)->ready) {
+        rn_set_error("rn_occlusion: the workspace could not be allocated earlier");
+        return RN_E_STATE;
+    }
+    return RN_OK;
+}
+
+int rn_masked_check_classes(const char* who, const rn_handle* h, const int32_t* cls, int n) {
+    for (int i = 0; i < n; ++i)
+        if (cls[i] < 0 || cls[i] >= h->num_classes) {
+            rn_set_error("%s: class_ids[%d] = %d outside [0, %d)", who, i, cls[i], h->num_classes);
+            return RN_E_INVALID;
+        }
+    return RN_OK;
+}
+
+int rn_masked_check_classes_device(const char* who, rn_handle* h, const int32_t* d_cls, int n) {
+    std::vector<int32_t> cls(static_cast<size_t>(n));
+    RN_HIP(hipMemcpyAsync(cls.data(), d_cls, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, h->stream));
+    RN_HIP(hipStreamSynchronize(h->stream));
+    return rn_masked_check_classes(who, h, cls.data(), n);
+}
+
+// the per-image fills of a call without a triple -> st->d_fill
+int rn_masked_enqueue_mean(rn_handle* h, rn_masked_chunk* st, const uint8_t* d_bgr, int n) {
+    const bool dwords = (3 * h->im_side * h->im_side) % 4 == 0 && (reinterpret_cast<uintptr_t>(d_bgr) & 3) == 0;
+    (void)hipGetLastError();
+    if (dwords)
+        hipLaunchKernelGGL(occlusion_mean_kernel<true>, dim3(n), dim3(256), 0, h->stream, d_bgr, h->im_side, st->d_fill);
+    else
+        hipLaunchKernelGGL(occlusion_mean_kernel<false>, dim3(n), dim3(256), 0, h->stream, d_bgr, h->im_side, st->d_fill);
+    RN_CHECK_LAUNCH();
+    return RN_OK;
+}
 
 void rn_occlusion_release(rn_handle* h) {
     OccState* s = static_cast<OccState*>(h->occlusion);
@@ -349,8 +345,8 @@ extern "C" int rn_occlusion_masks_device(rn_handle* h, const uint8_t* d_bgr, int
     }
     DeviceGuard guard(h->device);
     OccState* st = nullptr;
-    if ((rc = occ_state(h, &st)) != RN_OK) return rc;
-    if (!fill_bgr && (rc = enqueue_mean(h, st, d_bgr, n)) != RN_OK) return rc;
+    if ((rc = rn_masked_chunk_get(h, &st)) != RN_OK) return rc;
+    if (!fill_bgr && (rc = rn_masked_enqueue_mean(h, st, d_bgr, n)) != RN_OK) return rc;
     return enqueue_masks(h, st, d_bgr, patch, stride, plan.G, !fill_bgr, fill_bgr, first, count, d_out);
 }
 
@@ -365,15 +361,10 @@ extern "C" int rn_occlusion_u8_device(rn_handle* h, const uint8_t* d_bgr, int n,
         return RN_E_INVALID;
     }
     DeviceGuard guard(h->device);
-    if (d_class_ids) {
-        // (validated before anything is launched: the classes are read back on the handle's stream)
-        std::vector<int32_t> cls(static_cast<size_t>(n));
-        RN_HIP(hipMemcpyAsync(cls.data(), d_class_ids, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, h->stream));
-        RN_HIP(hipStreamSynchronize(h->stream));
-        if ((rc = check_classes(who, h, cls.data(), n)) != RN_OK) return rc;
-    }
+    // (validated before anything is launched: the classes are read back on the handle's stream)
+    if (d_class_ids && (rc = rn_masked_check_classes_device(who, h, d_class_ids, n)) != RN_OK) return rc;
     OccState* st = nullptr;
-    if ((rc = occ_state(h, &st)) != RN_OK) return rc;
+    if ((rc = rn_masked_chunk_get(h, &st)) != RN_OK) return rc;
     return enqueue_all(h, st, plan, d_bgr, n, d_class_ids, patch, stride, fill_bgr, d_drop, d_map, d_probs, d_ids);
 }
 
@@ -387,10 +378,10 @@ extern "C" int rn_occlusion_u8(rn_handle* h, const uint8_t* bgr, int n, const in
         rn_set_error("%s: null buffer", who);
         return RN_E_INVALID;
     }
-    if (class_ids && (rc = check_classes(who, h, class_ids, n)) != RN_OK) return rc;
+    if (class_ids && (rc = rn_masked_check_classes(who, h, class_ids, n)) != RN_OK) return rc;
     DeviceGuard guard(h->device);
     OccState* st = nullptr;
-    if ((rc = occ_state(h, &st)) != RN_OK) return rc;
+    if ((rc = rn_masked_chunk_get(h, &st)) != RN_OK) return rc;
     const size_t px = static_cast<size_t>(h->im_side) * h->im_side;
     if ((rc = rn_grow_scratch(h, &st->d_drop, &st->drop_cap, static_cast<size_t>(plan.n_windows), "occlusion drops")) != RN_OK) return rc;
     if (map && !st->d_map) {

@@ -385,6 +385,56 @@ def classify_im_dir(nn, imgs_dir, overlay=True, batch_size=64, gpu_decode=False,
     return xl_fpath
 
 
+def compare_heatmaps(nn, im_paths_or_dir, methods=('s6.bn', 's7.bn', 'occlusion'), steps=32, batch_size=64, **occlusion_kw):
+    """Which heat map to believe on these photographs (not in the reference): per method the mean deletion area and the mean
+    insertion area over the files (``RoomNet.map_faithfulness``, DESIGN.md section 23: a map that points at the evidence has a
+    SMALL deletion area and a LARGE insertion area).  ``im_paths_or_dir``: a directory or a list of image files; ``methods``:
+    "s6.bn" / "s7.bn" (``grad_cam`` at that layer) and "occlusion" (``occlusion_map(**occlusion_kw)``: patch, stride, fill), each for
+    the predicted class with the mean fill; ``steps`` points per curve.  Prints one line per method and returns
+    ``{method: {"deletion": area, "insertion": area, "images": count}}``.  A report on host arrays, not a loop anyone waits on."""
+    methods = tuple(methods)
+    for m in methods:
+        if m not in ('s6.bn', 's7.bn', 'occlusion'):
+            raise ValueError("compare_heatmaps: methods are 's6.bn', 's7.bn' and 'occlusion', got %r" % (m,))
+    if not methods:
+        raise ValueError("compare_heatmaps: no methods")
+    paths = sorted(glob(im_paths_or_dir + '/*')) if isinstance(im_paths_or_dir, str) else list(im_paths_or_dir)
+    batch_size = max(1, min(int(batch_size), nn.max_batch))
+    sums = {m: np.zeros(2, np.float64) for m in methods}
+    count = 0
+
+    def flush(pending):
+        batch = np.asarray(nn._batch_from(pending, "compare_heatmaps"))
+        for m in methods:
+            if m == 'occlusion':
+                maps = nn.occlusion_map(batch, **occlusion_kw)[0]
+            else:
+                maps = nn.grad_cam(batch, layer=m)[0]
+            _curves, aucs, _ids, _probs = nn.map_faithfulness(batch, maps, steps=steps)
+            sums[m] += aucs.astype(np.float64).sum(0)
+        return len(pending)
+
+    pending = []
+    for _i, fpath, im in _decode_files(paths, batch_size):
+        if im is None:
+            print(fpath, '---> unreadable image, skipped')
+            continue
+        pending.append(im)
+        if len(pending) >= batch_size:
+            count += flush(pending)
+            pending = []
+    if pending:
+        count += flush(pending)
+    if not count:
+        raise ValueError("compare_heatmaps: no readable image")
+    report = {}
+    for m in methods:
+        report[m] = {'deletion': float(sums[m][0] / count), 'insertion': float(sums[m][1] / count), 'images': count}
+        print('%-10s deletion area %.4f   insertion area %.4f   (%d images, %d steps)' % (m, report[m]['deletion'], report[m]['insertion'],
+                                                                                        count, steps))
+    return report
+
+
 def recalibrate_from_dir(nn, imgs_dir, batch_size=64, momentum=None, gpu_decode=False, gpu_orient=False):
     """Re-estimate the model's BN statistics on the images of a directory (``RoomNet.recalibrate_bn``; not in the reference,
     whose statistics only move while it trains, network.py:64-67): the files are decoded as ``classify_im_dir`` decodes them

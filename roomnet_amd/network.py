@@ -689,6 +689,35 @@ class RoomNet:
             raise ValueError("occlusion_map: the squares are cut out of the uint8 input; got %s" % im.dtype)
         return self._engine().occlusion_u8(im, class_ids=class_ids, patch=patch, stride=stride, fill=fill)
 
+    def map_faithfulness(self, im_in, maps, class_ids=None, steps=32, modes=("deletion", "insertion"), fill="mean"):
+        """Deletion and insertion curves of heat maps (not in the reference): which map to believe.  Per image the pixels are ranked
+        by ``maps`` (highest first, ties in raster order); the deletion curve is the class probability with the top ``j / steps`` of
+        them replaced by ``fill`` ("mean": the image's own mean colour, or a BGR triple), ``j = 0 .. steps``, the insertion curve the
+        probability with only those pixels present.  A map that points at the evidence gives a SMALL deletion area and a LARGE
+        insertion area (``roomnet_amd.faithfulness`` states the definition; ``rn_faith_u8`` runs it on the GPU).  ``im_in`` as
+        ``occlusion_map`` takes it (uint8 values); ``maps`` one map per image, ``[N,h,w]`` of any values, e.g. ``grad_cam``'s or
+        ``occlusion_map``'s; ``class_ids``: the class per image (None: each image's argmax).  Maps that are not ``S x S`` go through
+        ``cam.upsample(maps, S)`` first: bilinear, positive part, scaled to [0, 1] -- order-preserving up to its own rounding, and
+        every negative entry joins the zero plateau, which then ranks in raster order.  Returns ``(curves [N,M,steps+1] float32,
+        aucs [N,M] float32, ids int64[N], probs float32[N,C])``, ``M`` curves in the order deletion, insertion."""
+        from . import cam
+        if isinstance(im_in, np.ndarray) and im_in.ndim == 3:
+            im_in = [im_in]                                   # one HWC image: a batch of one
+        if isinstance(im_in, np.ndarray) and im_in.ndim != 4:
+            raise ValueError("map_faithfulness: expected an [N,S,S,3] batch, one [H,W,3] image or a list of images, got shape %s"
+                             % (im_in.shape,))
+        im = self._as_feed(np.asarray(self._batch_from(im_in, "map_faithfulness")))
+        if im.dtype != np.uint8:
+            raise ValueError("map_faithfulness: the pixels are replaced in the uint8 input; got %s" % im.dtype)
+        maps = np.asarray(maps, np.float32)
+        if maps.ndim == 2:
+            maps = maps[None]
+        if maps.ndim != 3 or maps.shape[0] != im.shape[0]:
+            raise ValueError("map_faithfulness: expected one [h,w] map per image (%d), got shape %s" % (im.shape[0], maps.shape))
+        if maps.shape[1:] != (self.im_side, self.im_side):
+            maps = cam.upsample(maps, self.im_side)
+        return self._engine().faith_u8(im, maps, class_ids=class_ids, steps=steps, modes=modes, fill=fill)
+
     # ------------------------------------------------------ batch-statistics BN
     def _batch_from(self, im_in, who):
         """``[N,S,S,3]`` array as it is (the feed rules of ``infer``); a list of BGR ``[H,W,3]`` images of any size through

@@ -40,6 +40,13 @@
         after a warm-up of both, enqueue to sync on the host's clock, and the call's own device time (rn_occlusion_last_ms);
         (b) the same call against the Python route, occlusion.occlusion_map_host over nn.infer; (c) classify_im_dir(overlay=True,
         gpu_decode=True, gpu_encode=True) with heatmap="occlusion" against heatmap="s6.bn" on N generated 640x480 and 1920x1080 files
+  python tools/bench_images.py --faithfulness [--out=PATH] [N]    deletion / insertion curves of heat maps,
+        nothing of the above; the lines also go to PATH (default profiles/faithfulness_bench.txt).  (a) one rn_faith_u8_device call
+        for N (default 64) resident images at 224 with 32 steps and both curves against the same number of plain
+        rn_forward_u8_device calls with the same chunk sizes on a resident buffer: alternating in one session, three runs each
+        after a warm-up of both, enqueue to sync on the host's clock, the call's own device time (rn_faith_last_ms), and the rank
+        launch's device time alone (rn_faith_ranks_device); (b) the same call against the Python route, faithfulness.curves_host
+        over nn.infer; (c) infer.compare_heatmaps on N generated 640x480 files: the three methods' mean areas
 """
 import contextlib
 import io
@@ -679,7 +686,112 @@ def occlusion_arm():
         f.write('python tools/bench_images.py --occlusion %d\n' % n + '\n'.join(lines) + '\n')
 
 
-if '--occlusion' in sys.argv:
+def faithfulness_arm():
+    """(a) the device call against the plain passes it is made of and the rank launch alone, (b) against the Python route,
+    (c) compare_heatmaps on generated files."""
+    global H, W, N
+    from roomnet_amd import faithfulness, infer
+    from roomnet_amd.network import RoomNet
+    n = int(args[0]) if args else 64
+    out_path = next((a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--out=')), os.path.join('profiles', 'faithfulness_bench.txt'))
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    steps, modes, S = 32, 3, 224
+    nn = RoomNet(num_classes=6, im_side=S, compute_bn_mean_var=False, optimized_inference=True, dtype='bf16', max_batch=64)
+    nn.load(os.path.join('roomnet_amd', 'final_model', 'roomnet'))
+    eng = nn._engine()
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float32)
+    ims = np.stack([np.clip(np.stack([127 + 100 * np.sin(f[2 * c] * xx + k) * np.cos(f[2 * c + 1] * yy) for c in range(3)], -1)
+                            + rng.normal(0, 6, (S, S, 3)), 0, 255).astype(np.uint8)
+                    for k, f in enumerate(rng.uniform(0.01, 0.08, (n, 6)))])
+    # maps as a caller has them: smooth bumps with a zero plateau (an upsampled ReLU'd coarse map)
+    from roomnet_amd import cam
+    maps = np.ascontiguousarray(cam.upsample(rng.normal(-0.3, 1, (n, 46, 46)), S), dtype=np.float32)
+    n_passes, n_chunks = eng.faith_plan(n, steps, modes)
+    plan = faithfulness.chunks(n_passes, eng.max_batch)
+    d_bgr, d_work = eng.device_malloc(ims.nbytes), eng.device_malloc(eng.max_batch * S * S * 3)
+    d_map, d_rank = eng.device_malloc(maps.nbytes), eng.device_malloc(n * S * S * 4)
+    d_curve, d_auc = eng.device_malloc(n_passes * 4), eng.device_malloc(n * 2 * 4)
+    d_probs, d_ids = eng.device_malloc(eng.max_batch * 6 * 4), eng.device_malloc(eng.max_batch * 8)
+    eng.h2d(d_bgr, ims)
+    eng.h2d(d_map, maps)
+    eng.h2d(d_work, np.ascontiguousarray(np.resize(ims, (eng.max_batch, S, S, 3))))
+
+    def curves():
+        t0 = time.perf_counter()
+        eng.faith_u8_device(d_bgr, d_map, n, None, steps, modes, 'mean', d_curve, d_auc, d_probs, d_ids)
+        eng.sync()
+        return 1e3 * (time.perf_counter() - t0), eng.faith_last_ms()
+
+    def plain():
+        t0 = time.perf_counter()
+        eng.forward_u8_device(d_bgr, n, d_probs, d_ids)
+        for _first, count in plan:
+            eng.forward_u8_device(d_work, count, d_probs, d_ids)
+        eng.sync()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def rank_alone():
+        eng.faith_ranks_device(d_map, n, d_rank)
+        eng.sync()
+        return eng.faith_last_ms()
+
+    curves(), plain()                                    # the warm-up of both (the first call allocates the workspaces)
+    t_call, t_dev, t_plain = [], [], []
+    for _ in range(3):
+        a, b = curves()
+        t_call.append(a)
+        t_dev.append(b)
+        t_plain.append(plain())
+    got_curves, got_aucs = np.empty((n, 2, steps + 1), np.float32), np.empty((n, 2), np.float32)
+    eng.d2h(got_curves, d_curve)
+    eng.d2h(got_aucs, d_auc)
+    rank_alone()
+    t_rank = [rank_alone() for _ in range(3)]
+    ranks = np.empty((n, S, S), np.uint32)
+    eng.d2h(ranks, d_rank)
+    ranks_ok = all(np.array_equal(ranks[k], faithfulness.ranks(maps[k])) for k in range(n))
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    say('(a) %d resident images at %d, %d steps, both curves: %d masked passes in %d chunks of %d, bf16.  One rn_faith_u8_device call, '
+        'enqueue to sync: %s ms (device time of the call: %s ms)   the same %d + %d plain rn_forward_u8_device calls on a resident buffer: '
+        '%s ms   alternating, same session, 3 runs each after a warm-up of both   ratio of the medians: %.3f   %.0f masked passes/ms   '
+        'the rank launch alone (rn_faith_ranks_device, %d maps, one workgroup each): %s ms of device time, %.4f of the call; ranks equal '
+        'the stable argsort: %s'
+        % (n, S, steps, n_passes, n_chunks, eng.max_batch, ' / '.join('%.2f' % x for x in t_call), ' / '.join('%.2f' % x for x in t_dev), 1,
+           n_chunks, ' / '.join('%.2f' % x for x in t_plain), med(t_call) / med(t_plain), n_passes / med(t_call), n,
+           ' / '.join('%.3f' % x for x in t_rank), med(t_rank) / med(t_dev), ranks_ok))
+    t0 = time.perf_counter()
+    want = faithfulness.curves_host(lambda b: nn.infer(b)[1], ims, maps, steps=steps, modes=modes, max_batch=eng.max_batch)
+    t_py = 1e3 * (time.perf_counter() - t0)
+    say('(b) the Python route, faithfulness.curves_host over nn.infer (one argsort per map, masked copies built with NumPy, %.0f MB uploaded): '
+        '%.0f ms, x%.1f the device call; curves identical: %s, areas identical: %s'
+        % (n_passes * S * S * 3 / 1e6, t_py, t_py / med(t_call), bool(np.array_equal(got_curves, want[0])), bool(np.array_equal(got_aucs, want[1]))))
+    for d in (d_bgr, d_work, d_map, d_rank, d_curve, d_auc, d_probs, d_ids):
+        eng.device_free(d)
+    nn.sess.close()
+    H, W, N = 480, 640, n
+    root, d, nn2, paths, mb = generated_directory()
+    with contextlib.redirect_stdout(io.StringIO()):
+        t0 = time.perf_counter()
+        report = infer.compare_heatmaps(nn2, d, steps=steps, batch_size=64)
+        t_cmp = time.perf_counter() - t0
+    say('(c) %d JPEG files %dx%d (%.0f MB), infer.compare_heatmaps(steps=%d), mean areas (deletion / insertion):   ' % (len(paths), W, H, mb, steps)
+        + '   '.join('%s %.4f / %.4f' % (m, r['deletion'], r['insertion']) for m, r in report.items()) + '   in %.1f s' % t_cmp)
+    nn2.sess.close()
+    shutil.rmtree(root, ignore_errors=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, 'w') as f:
+        f.write('python tools/bench_images.py --faithfulness %d\n' % n + '\n'.join(lines) + '\n')
+
+
+if '--faithfulness' in sys.argv:
+    faithfulness_arm()
+elif '--occlusion' in sys.argv:
     occlusion_arm()
 elif '--heatmap' in sys.argv:
     heatmap_arm()
